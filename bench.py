@@ -28,7 +28,13 @@ real reference's goldens on EVERY model family D0..D6 (profiles/r06_parity_error
   inference / inference_d4   configs[1] (batch-32 eval forward + decode + on-device NMS, ms/img) and configs[4] (D4 batch 8 @ 1024) in the
                          headline's forward arithmetic (exact fp32), the other modes as named extras;
   cpu_baseline           the oracle = torch-CPU restatement of the reference, bounded sample, thread sweep + configs[0].
-Every train leg is timed over >= 20 steps.
+The headline leg times exactly --steps steps; every extra-mode leg --extra-steps (default 20).
+
+--dump-outputs DIR writes what the headline's timed step computed in its LAST timed step (before the instrumented roofline step):
+DIR/cls_loss.npy and DIR/reg_loss.npy (what the step returns) and DIR/parameters.npy (every trainable parameter after the optimizer
+update, flattened in named_parameters() order), float32, at most 64 MB in all (a larger output is cut to a fixed, seeded sample of its
+elements).  Weights (torch.manual_seed(0)), the synthetic batch and the drop_connect stream are seeded, so the same arguments give the
+same inputs on every run: two builds can be compared output for output.
 
 N > 1 (one process per GPU, RCCL): the ranks the launcher started only SUPERVISE -- each runs its share of a leg in a child process, so
 a leg that crashes or hangs (a failed hipGraph capture of the DDP step is not recoverable in-process) costs that attempt, not the run:
@@ -106,8 +112,48 @@ def parse(argv=None):
     ap.add_argument('--leg-timeout', type=float, default=240.0, help='N > 1: seconds the child processes of one attempt get before it is abandoned')
     ap.add_argument('--infer-reps', type=int, default=20, help='timed repetitions of every inference leg')
     ap.add_argument('--torch-optim', action='store_true', help='stock clip_grad_norm_ + torch.optim.AdamW(fused) instead of the HIP ClipAdamW')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the headline leg\'s last timed step to DIR/<name>.npy (float32, <= 64 MB in all)')
     ap.add_argument('--_leg', dest='leg', default=None, choices=['graph', 'eager', 'dry'], help=argparse.SUPPRESS)   # internal: this process IS one rank of a DDP leg
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.extra_steps < 1:
+        ap.error('--steps and --extra-steps must be >= 1')
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)       # (DDP legs run in child processes started with cwd=ROOT)
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000       # files included (an .npy header is < 4 KiB)
+
+
+def dump_outputs(dirname, outputs, budget=DUMP_BUDGET_BYTES, seed=0):
+    """{name: tensor | array} -> dirname/<name>.npy, float32 (float64 stays float64), at most `budget` bytes in all.  Arrays that fit
+    their share are written whole; a larger one is cut to a fixed, seeded sample of its flattened elements (sorted indices, the same on
+    every run for the same size), each of the cut arrays getting an equal share of what the whole ones leave.  A directory this creates
+    gets a '*' .gitignore, like pytest's cache."""
+    import numpy as np
+    import torch
+    arrs = {}
+    for k, v in outputs.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu()
+            v = (v.double() if v.dtype == torch.float64 else v.float()).numpy()        # (numpy has no bf16)
+        v = np.asarray(v)
+        arrs[k] = np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+    left, todo = budget - 4096 * len(arrs), sorted(arrs, key=lambda k: arrs[k].nbytes)
+    if not os.path.isdir(dirname):
+        os.makedirs(dirname)
+        with open(os.path.join(dirname, '.gitignore'), 'w') as f:     # a dump made inside a checkout stays out of `git status`
+            f.write('*\n')
+    for i, k in enumerate(todo):
+        v, share = arrs[k], left // (len(todo) - i)
+        if v.nbytes > share:
+            n = share // v.itemsize
+            idx = np.sort(np.random.default_rng(seed).choice(v.size, size=n, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirname, k + '.npy'), v)
+        left -= v.nbytes
+    return sorted(arrs)
 
 
 def free_port():
@@ -267,9 +313,10 @@ def graph_self_check(graphed, dev, world, use_dist=True):
     return note
 
 
-def train_leg(a, dtype_name, steps, warmup, rank, world, local, dev, want_roofline, use_ddp=False, ddp_graph=False):
+def train_leg(a, dtype_name, steps, warmup, rank, world, local, dev, want_roofline, use_ddp=False, ddp_graph=False, dump_dir=None):
     """EXACTLY `steps` timed train steps (after `warmup` untimed ones) in one compute dtype
-    -> dict(value img/s, ms_per_step, final_loss, roofline, graphed, host_ms, self_check[, img])."""
+    -> dict(value img/s, ms_per_step, final_loss, roofline, graphed, host_ms, self_check[, img]).
+    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs) before the instrumented roofline step."""
     import contextlib
     import torch
     import torch.distributed as dist
@@ -292,6 +339,8 @@ def train_leg(a, dtype_name, steps, warmup, rank, world, local, dev, want_roofli
     img, ann = img.to(dev), ann.to(dev)
 
     def step():
+        # -> (loss, (cls_loss, reg_loss)).  Whoever keeps them keeps this step's autograd graph alive, its AccumulateGrad nodes
+        # included; warm-up outputs kept across the hipGraph capture below made the captured run segfault -- only the timed loop keeps them.
         opt.zero_grad(set_to_none=True)
         cl, rl = net([img, ann])
         loss = cl.mean() + rl.mean()
@@ -299,7 +348,7 @@ def train_leg(a, dtype_name, steps, warmup, rank, world, local, dev, want_roofli
         if a.torch_optim:
             torch.nn.utils.clip_grad_norm_(params, 0.1)
         opt.step()
-        return loss
+        return loss, (cl, rl)
 
     def sync_all():
         if use_ddp:
@@ -351,7 +400,7 @@ def train_leg(a, dtype_name, steps, warmup, rank, world, local, dev, want_roofli
     else:
         with on_stream():
             for _ in range(steps):
-                loss = step()
+                loss, cl_rl = step()
     host_dt = time.perf_counter() - t0          # time the HOST needed to issue the steps (a host-bound regime shows as host ~= wall)
     sync_all()
     dt = time.perf_counter() - t0
@@ -363,6 +412,10 @@ def train_leg(a, dtype_name, steps, warmup, rank, world, local, dev, want_roofli
         hm = [torch.zeros(1, device=dev, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(hm, torch.tensor([host_ms[0]], device=dev, dtype=torch.float64))
         host_ms = [round(float(x.item()), 3) for x in hm]
+    if dump_dir and rank == 0:
+        cl, rl = cl_rl
+        dump_outputs(dump_dir, {'cls_loss': cl, 'reg_loss': rl,
+                                'parameters': torch.cat([p.detach().reshape(-1).float() for p in params])})
     roof = None
     if want_roofline:
         # live per-launch timing with HIP events on the launch stream (one instrumented step).  EVERY rank runs the step
@@ -505,7 +558,7 @@ def single_gpu_main(a):
     cfg = EFFICIENTDET[a.network]
     d0_512 = a.network == 'efficientdet-d0' and a.size == 512
     others = [m for m in ('f32_hf16x3_bwd_bf16x3', 'f32_bwd_bf16x3', 'f32', 'f32_bf16x3', 'bf16') if m != a.dtype]
-    leg = train_leg(a, a.dtype, a.steps, a.warmup, 0, 1, 0, dev, not a.no_roofline)
+    leg = train_leg(a, a.dtype, a.steps, a.warmup, 0, 1, 0, dev, not a.no_roofline, dump_dir=a.dump_outputs)
     img = leg.pop('img')
     out = result_line(a, 1, leg, cfg)
     if not a.no_extra_modes:
@@ -587,7 +640,7 @@ def leg_main(a):
     ddp.init_process_group_from_env(backend, for_capture=(a.leg == 'graph'))
     try:
         leg = train_leg(a, a.dtype, a.steps, a.warmup, rank, world, local, dev, not a.no_roofline, use_ddp=True,
-                        ddp_graph=(a.leg == 'graph' and backend == 'nccl'))
+                        ddp_graph=(a.leg == 'graph' and backend == 'nccl'), dump_dir=a.dump_outputs)
     except DdpSelfCheckFailed as e:
         sys.stderr.write('%s\n' % e)
         sys.stderr.flush()
@@ -625,7 +678,7 @@ def run_attempt(a, path, attempt, rank, world, local, base_port, store, dry):
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'), EFFDET_BENCH_DRY_PATH=path)
     if path == 'graph':
         env.setdefault('TORCH_NCCL_ASYNC_ERROR_HANDLING', '0')       # torch's recipe for DDP inside a captured graph (the capture leg only)
-    argv = [x for x in sys.argv[1:] if x != '--ddp-single']
+    argv = [x for x in sys.argv[1:] if x != '--ddp-single'] + (['--dump-outputs', a.dump_outputs] if a.dump_outputs else [])
     cmd = [sys.executable, os.path.abspath(__file__)] + argv + ['--_leg', 'dry' if dry else path]
     t0 = time.time()
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True, cwd=ROOT)
@@ -735,7 +788,7 @@ def supervisor_main(a, rank, world, local):
 def self_launch(a):
     """`python bench.py --gpus N` (N > 1) started by hand: become the launcher (one process per GPU; train.py:311-326 self-spawns too)."""
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(a.gpus), '--master-addr', '127.0.0.1',
-           '--master-port', str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
+           '--master-port', str(free_port()), os.path.abspath(__file__)] + sys.argv[1:] + (['--dump-outputs', a.dump_outputs] if a.dump_outputs else [])
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))
     return subprocess.call(cmd, env=env, cwd=ROOT)
 
