@@ -16,6 +16,7 @@
 //   All loops are bounded by device-side counts; the host launches ceil(A / round) rounds blindly; every
 //   launch geometry depends on shapes only and the call consists of kernel nodes only: capture-safe.
 #include "common.h"
+#include "radix_sort.h"
 #include <stdlib.h>
 
 namespace {
@@ -307,7 +308,6 @@ __global__ __launch_bounds__(NT) void nms_cross_kernel(const float4* __restrict_
 //     kept words AND-ed against the row, one ballot per kept box inside the block), appends the kept boxes in order and files them
 //     into the kept-box grid.  The old per-image round kernel did all of this on ONE CU per image (32 of 256 CUs at B = 32) and was
 //     2/3 of the decode + NMS time.
-constexpr int RS_TILE = 2048;                    // keys per workgroup and pass
 
 // The per-call resets as ONE kernel (three integer regions) instead of hipMemsetAsync nodes, and the final count written by the
 // resolve kernel instead of a hipMemcpyAsync: the captured NMS is then made of kernel nodes only.
@@ -343,73 +343,6 @@ __global__ __launch_bounds__(256) void nms_keys32_kernel(const float* __restrict
     const int t = cnt[0] + cnt[1] + cnt[2] + cnt[3];
     if (t) atomicAdd(nvalid + b, t);
     if (blockIdx.x == 0) kept[b] = 0;
-  }
-}
-
-// hist[b][digit][tile]
-__global__ __launch_bounds__(256) void rs_hist_kernel(const unsigned* __restrict__ keys, unsigned* __restrict__ hist, long long A, int T, int shift) {
-  __shared__ unsigned digit_counter[256];            // (integer LDS atomics: order-independent)
-  const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  digit_counter[tid] = 0u;
-  __syncthreads();
-  const unsigned* k = keys + (long long)b * A;
-  const long long i0 = (long long)tile * RS_TILE, i1 = min(A, i0 + RS_TILE);
-  for (long long i = i0 + tid; i < i1; i += 256) atomicAdd(&digit_counter[(k[i] >> shift) & 255u], 1u);
-  __syncthreads();
-  hist[((long long)b * 256 + tid) * T + tile] = digit_counter[tid];
-}
-
-// per image: exclusive scan over (digit, tile) in digit-major order, in place
-__global__ __launch_bounds__(256) void rs_scan_kernel(unsigned* __restrict__ hist, int T) {
-  __shared__ unsigned tot[256];
-  const int b = blockIdx.x, d = threadIdx.x;
-  unsigned* row = hist + ((long long)b * 256 + d) * T;
-  unsigned s = 0u;
-  for (int t = 0; t < T; ++t) s += row[t];
-  tot[d] = s;
-  __syncthreads();
-  if (d == 0) { unsigned run = 0u; for (int q = 0; q < 256; ++q) { const unsigned c = tot[q]; tot[q] = run; run += c; } }
-  __syncthreads();
-  unsigned run = tot[d];
-  for (int t = 0; t < T; ++t) { const unsigned c = row[t]; row[t] = run; run += c; }
-}
-
-__global__ __launch_bounds__(256) void rs_scatter_kernel(const unsigned* __restrict__ kin, const unsigned* __restrict__ vin,
-                                                         unsigned* __restrict__ kout, unsigned* __restrict__ vout,
-                                                         const unsigned* __restrict__ hist, long long A, int T, int shift) {
-  __shared__ unsigned cur[256];                  // next output slot of each digit for this tile
-  __shared__ unsigned wcnt[4][256];              // per-wave digit counts of the current 256-key chunk
-  const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  cur[tid] = hist[((long long)b * 256 + tid) * T + tile];
-  const long long base = (long long)b * A, i0 = (long long)tile * RS_TILE;
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  for (int c = 0; c < RS_TILE / 256; ++c) {
-    const long long i = i0 + c * 256 + tid;
-    if (i0 + c * 256 >= A) break;                                      // uniform
-    const bool valid = i < A;
-    const unsigned key = valid ? kin[base + i] : 0u, val = valid ? vin[base + i] : 0u;
-    const unsigned d = (key >> shift) & 255u;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-    __syncthreads();
-    unsigned long long peers = __ballot(valid);                        // lanes of this wave holding the same digit
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const bool on = (d >> bit) & 1u;
-      const unsigned long long bb = __ballot(on);
-      peers &= on ? bb : ~bb;
-    }
-    const int rank = __popcll(peers & lt);
-    if (valid && rank == 0) wcnt[wave][d] = (unsigned)__popcll(peers);
-    __syncthreads();
-    if (valid) {
-      unsigned pos = cur[d] + (unsigned)rank;
-      for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
-      kout[base + pos] = key; vout[base + pos] = val;
-    }
-    __syncthreads();
-    cur[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
-    __syncthreads();                                                   // (the next chunk zeroes wcnt)
   }
 }
 
@@ -708,9 +641,9 @@ extern "C" int effdet_nms(const float* boxes, const float* score, float threshol
     EFFDET_CHECK_LAUNCH();
     unsigned *ki = w.k32a, *vi = w.vals_in, *ko = w.k32b, *vo = w.v32b;
     for (int pass = 0; pass < 4; ++pass) {
-      hipLaunchKernelGGL(rs_hist_kernel, dim3(w.T, B), dim3(256), 0, st, (const unsigned*)ki, w.hist, A, w.T, pass * 8);
+      hipLaunchKernelGGL(rs_hist_kernel<unsigned>, dim3(w.T, B), dim3(256), 0, st, (const unsigned*)ki, w.hist, A, w.T, pass * 8);
       hipLaunchKernelGGL(rs_scan_kernel, dim3(B), dim3(256), 0, st, w.hist, w.T);
-      hipLaunchKernelGGL(rs_scatter_kernel, dim3(w.T, B), dim3(256), 0, st, (const unsigned*)ki, (const unsigned*)vi, ko, vo, (const unsigned*)w.hist, A, w.T, pass * 8);
+      hipLaunchKernelGGL(rs_scatter_kernel<unsigned>, dim3(w.T, B), dim3(256), 0, st, (const unsigned*)ki, (const unsigned*)vi, ko, vo, (const unsigned*)w.hist, A, w.T, pass * 8);
       EFFDET_CHECK_LAUNCH();
       unsigned* t = ki; ki = ko; ko = t; t = vi; vi = vo; vo = t;
     }

@@ -1,0 +1,280 @@
+// Device-side VOC mean AP (the reference's eval.py:165-257 `evaluate`, after `_get_detections`): greedy matching of every
+// detection against the ground truth of its image and class, the per-class score sort, the TP / FP cumsums, recall / precision
+// and `_compute_ap` (eval.py:46-73).  Compiled with -ffp-contract=off: the fp64 IoU of `compute_overlap` (eval.py:19-43) must
+// round exactly like NumPy's unfused operations, or IoUs at exactly the threshold change their decision.
+//
+//   effdet_voc_match (one workgroup per image): the image's GT rows are staged in LDS; one thread per detection slot finds its
+//     assigned GT (first maximum of the IoU over the class's GT rows, in row order) and cond = IoU >= threshold.  The reference
+//     walks an image's detections of one class in score order and a detection whose best GT is already taken is a false positive
+//     (no fall-back to the second best), so TP(d) = cond(d) and d is the FIRST slot with cond and that assigned GT: an LDS
+//     atomicMin of the slot index per GT decides it order-independently.  One record per slot: 64-bit sort key
+//     (class << 32 | descending-score key), TP byte; empty slots get class C (they sort after every real class).  GT rows are
+//     counted per class with integer atomics.
+//   effdet_voc_ap: a stable LSD radix sort of all records by (class, score key) -- 4 score passes + 1 class pass (2 above 255
+//     classes) -- so ties keep insertion order (image, then slot); per-class segment bounds from the class changes of the sorted
+//     keys; then one workgroup per class: forward sweep (exact integer TP / FP cumsums -> fp64 recall, precision), reverse sweep
+//     (precision envelope = running max from the right, AP terms (r_k - r_{k-1}) * env_k at the TP positions k), and a fixed
+//     LDS tree over the per-thread partial sums.  Every launch geometry follows from (B, max_det, G, C, N) alone.
+#include "common.h"
+#include "radix_sort.h"
+#include <float.h>
+#include <limits.h>
+
+namespace {
+
+constexpr int VOC_MAX_GT = 2048;              // GT rows per image staged in LDS: 40 bytes each (4 fp64 box, label, claim)
+constexpr int VOC_MAX_CLASSES = 65535;        // class values 0..C fit the two class passes of the sort
+
+// descending-score key of a positive fp32 score (nms_keys32_kernel's transform)
+__device__ __forceinline__ unsigned voc_score_key(float s) {
+  unsigned u = __float_as_uint(s);
+  u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;     // ascending-orderable
+  return ~u;                                      // descending
+}
+
+// compute_overlap(d, gts of class c) and np.argmax, in the reference's fp64 operation order
+__device__ __forceinline__ int voc_assign(const double a0, const double a1, const double a2, const double a3, int c,
+                                          const double* gb, const int* gl, int G, double& best) {
+  const double aarea = (a2 - a0) * (a3 - a1);
+  int arg = -1;
+  best = -1.0;
+  for (int j = 0; j < G; ++j) {
+    if (gl[j] != c) continue;
+    const double b0 = gb[4 * j], b1 = gb[4 * j + 1], b2 = gb[4 * j + 2], b3 = gb[4 * j + 3];
+    const double area = (b2 - b0) * (b3 - b1);
+    double iw = fmin(a2, b2) - fmax(a0, b0);
+    double ih = fmin(a3, b3) - fmax(a1, b1);
+    iw = fmax(iw, 0.0);
+    ih = fmax(ih, 0.0);
+    double ua = aarea + area - iw * ih;
+    ua = fmax(ua, DBL_EPSILON);
+    const double iou = iw * ih / ua;
+    if (iou > best) { best = iou; arg = j; }       // first maximum
+  }
+  return arg;
+}
+
+// dets [B][max_det][6] (x1, y1, x2, y2, score, label) fp32, counts [B]; gt_boxes [B][G][4] fp64, gt_labels [B][G] (-1 = pad).
+// rec_key / rec_tp point at the B * max_det records of this batch.
+__global__ __launch_bounds__(256) void voc_match_kernel(const float* __restrict__ dets, const int* __restrict__ counts,
+                                                        const double* __restrict__ gt_boxes, const int* __restrict__ gt_labels,
+                                                        int max_det, int G, int C, double thr, unsigned long long* __restrict__ rec_key,
+                                                        unsigned char* __restrict__ rec_tp, int* __restrict__ gt_counter) {
+  extern __shared__ double voc_lds[];
+  double* gb = voc_lds;                       // [G][4]
+  int* gl = (int*)(gb + 4 * G);               // [G]
+  int* claim = gl + G;                        // [G] first slot claiming the GT
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int j = tid; j < G; j += 256) {
+    const double* src = gt_boxes + ((long long)b * G + j) * 4;
+    gb[4 * j] = src[0]; gb[4 * j + 1] = src[1]; gb[4 * j + 2] = src[2]; gb[4 * j + 3] = src[3];
+    const int lab = gt_labels[(long long)b * G + j];
+    gl[j] = lab;
+    claim[j] = INT_MAX;
+    if (lab >= 0 && lab < C) atomicAdd(&gt_counter[lab], 1);
+  }
+  __syncthreads();
+  int n = counts[b];
+  n = n < 0 ? 0 : (n > max_det ? max_det : n);
+  const float* d = dets + (long long)b * max_det * 6;
+  for (int k = tid; k < n; k += 256) {
+    const float* r = d + (long long)k * 6;
+    const float lf = r[5];
+    const int c = (int)lf;
+    if (!(lf >= 0.f && lf < (float)C) || (float)c != lf) continue;
+    double best;
+    const int a = voc_assign(r[0], r[1], r[2], r[3], c, gb, gl, G, best);
+    if (a >= 0 && best >= thr) atomicMin(&claim[a], k);
+  }
+  __syncthreads();
+  for (int k = tid; k < max_det; k += 256) {
+    const long long o = (long long)b * max_det + k;
+    unsigned long long key = ((unsigned long long)C << 32) | 0xffffffffull;
+    unsigned char tp = 0;
+    if (k < n) {
+      const float* r = d + (long long)k * 6;
+      const float lf = r[5];
+      const int c = (int)lf;
+      if (lf >= 0.f && lf < (float)C && (float)c == lf) {
+        double best;
+        const int a = voc_assign(r[0], r[1], r[2], r[3], c, gb, gl, G, best);
+        tp = (a >= 0 && best >= thr && claim[a] == k) ? 1 : 0;
+        key = ((unsigned long long)c << 32) | voc_score_key(r[4]);
+      }
+    }
+    rec_key[o] = key;
+    rec_tp[o] = tp;
+  }
+}
+
+// sort input (keys + record index) and the reset of the per-class segment bounds
+__global__ __launch_bounds__(256) void voc_sort_init_kernel(const unsigned long long* __restrict__ rec_key, unsigned long long* __restrict__ ka,
+                                                            unsigned* __restrict__ va, long long N, int* __restrict__ seg, int C) {
+  const long long n = N > 2LL * C ? N : 2LL * C;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    if (i < N) { ka[i] = rec_key[i]; va[i] = (unsigned)i; }
+    if (i < 2LL * C) seg[i] = 0;
+  }
+}
+
+// seg[2c], seg[2c + 1] = [first, last + 1) sorted position of class c (0, 0 when the class has no records)
+__global__ __launch_bounds__(256) void voc_segments_kernel(const unsigned long long* __restrict__ skey, long long N, int C, int* __restrict__ seg) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
+    const unsigned c = (unsigned)(skey[i] >> 32);
+    if (c >= (unsigned)C) continue;
+    if (i == 0 || (unsigned)(skey[i - 1] >> 32) != c) seg[2 * c] = (int)i;
+    if (i == N - 1 || (unsigned)(skey[i + 1] >> 32) != c) seg[2 * c + 1] = (int)(i + 1);
+  }
+}
+
+// block-wide inclusive scan (sum for int, max for double) over threadIdx order; *total = the whole block's result
+__device__ __forceinline__ int block_scan_sum(int x, int* wtot, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(x, o, 64); if (lane >= o) x += t; }
+  if (lane == 63) wtot[wave] = x;
+  __syncthreads();
+  int pre = 0;
+  for (int w = 0; w < wave; ++w) pre += wtot[w];
+  *total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+  __syncthreads();
+  return x + pre;
+}
+
+__device__ __forceinline__ double block_scan_max(double x, double* wtot, double* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const double t = __shfl_up(x, o, 64); if (lane >= o) x = fmax(x, t); }
+  if (lane == 63) wtot[wave] = x;
+  __syncthreads();
+  double pre = 0.0;                                  // (every value is >= 0)
+  for (int w = 0; w < wave; ++w) pre = fmax(pre, wtot[w]);
+  *total = fmax(fmax(wtot[0], wtot[1]), fmax(wtot[2], wtot[3]));
+  __syncthreads();
+  return fmax(x, pre);
+}
+
+// one workgroup per class: eval.py:225-241 + _compute_ap on the class's sorted records [seg[2c], seg[2c+1])
+__global__ __launch_bounds__(256) void voc_ap_kernel(const unsigned* __restrict__ sval, const unsigned char* __restrict__ rec_tp,
+                                                     const int* __restrict__ seg, const int* __restrict__ gt_counter,
+                                                     double* __restrict__ recall, double* __restrict__ precision,
+                                                     double* __restrict__ ap, double* __restrict__ num_ann) {
+  __shared__ int itot[4];
+  __shared__ double dtot[4];
+  __shared__ double red[256];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const int ngt = gt_counter[c];
+  if (ngt == 0) {                                    // eval.py:221-223: AP 0 (the class still counts in the mean)
+    if (tid == 0) { ap[c] = 0.0; num_ann[c] = 0.0; }
+    return;
+  }
+  const double n = (double)ngt;
+  const long long s0 = seg[2 * c], s1 = seg[2 * c + 1];
+  int carry = 0;
+  for (long long base = s0; base < s1; base += 256) {            // (uniform bounds: every thread reaches every barrier)
+    const long long i = base + tid;
+    const int v = i < s1 ? (int)rec_tp[sval[i]] : 0;
+    int tot;
+    const int incl = block_scan_sum(v, itot, &tot);
+    if (i < s1) {
+      const int tp = carry + incl;
+      const int fp = (int)(i - s0 + 1) - tp;
+      recall[i] = (double)tp / n;
+      precision[i] = (double)tp / fmax((double)tp + (double)fp, DBL_EPSILON);
+    }
+    carry += tot;
+  }
+  __syncthreads();                                   // recall / precision of the whole segment visible to the block
+  double env = 0.0, acc = 0.0;
+  for (long long top = s1; top > s0; top -= 256) {
+    const long long i = top - 1 - tid;
+    const bool valid = i >= s0;
+    double tot;
+    const double m = block_scan_max(valid ? precision[i] : 0.0, dtot, &tot);
+    if (valid && rec_tp[sval[i]]) {
+      const double rprev = i > s0 ? recall[i - 1] : 0.0;
+      acc += (recall[i] - rprev) * fmax(m, env);
+    }
+    env = fmax(env, tot);
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) { ap[c] = red[0]; num_ann[c] = n; }
+}
+
+inline int voc_grid(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
+inline size_t voc_al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct VocWs { unsigned long long *ka, *kb; unsigned *va, *vb, *hist; int T; };
+
+size_t voc_carve(VocWs& w, void* base, long long N) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) { void* p = base ? (char*)base + off : nullptr; off += voc_al(bytes); return p; };
+  const size_t n = (size_t)(N > 0 ? N : 1);
+  w.T = (int)((n + RS_TILE - 1) / RS_TILE);
+  w.ka = (unsigned long long*)take(n * 8); w.kb = (unsigned long long*)take(n * 8);
+  w.va = (unsigned*)take(n * 4); w.vb = (unsigned*)take(n * 4);
+  w.hist = (unsigned*)take((size_t)256 * w.T * 4);
+  return off;
+}
+
+}  // namespace
+
+extern "C" int effdet_voc_match(const float* dets, const int* counts, const double* gt_boxes, const int* gt_labels, int B, int max_det,
+                                int G, int num_classes, double iou_threshold, unsigned long long* rec_key, unsigned char* rec_tp,
+                                int* gt_count, effdet_stream_t stream) {
+  if (!dets || !counts || !gt_boxes || !gt_labels || !rec_key || !rec_tp || !gt_count || B < 1 || max_det < 1 || G < 1 ||
+      num_classes < 1 || num_classes > VOC_MAX_CLASSES)
+    return EFFDET_EINVAL;
+  if (G > VOC_MAX_GT) return EFFDET_EUNSUPPORTED;
+  const size_t lds = (size_t)G * (4 * sizeof(double) + 2 * sizeof(int));
+  EFFDET_SET_MAX_LDS(voc_match_kernel, (size_t)VOC_MAX_GT * (4 * sizeof(double) + 2 * sizeof(int)));
+  hipLaunchKernelGGL(voc_match_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dets, counts, gt_boxes, gt_labels, max_det, G,
+                     num_classes, iou_threshold, rec_key, rec_tp, gt_count);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+extern "C" long long effdet_voc_ap_workspace_bytes(long long num_records) {
+  VocWs w;
+  return (long long)voc_carve(w, nullptr, num_records);
+}
+
+extern "C" int effdet_voc_ap(const unsigned long long* rec_key, const unsigned char* rec_tp, long long num_records, const int* gt_count,
+                             int num_classes, void* workspace, long long workspace_bytes, double* ap, double* num_annotations,
+                             double* recall, double* precision, int* seg, effdet_stream_t stream) {
+  const long long N = num_records;
+  if (!gt_count || !workspace || !ap || !num_annotations || !seg || N < 0 || N > (long long)INT_MAX || num_classes < 1 ||
+      num_classes > VOC_MAX_CLASSES || (N > 0 && (!rec_key || !rec_tp || !recall || !precision)))
+    return EFFDET_EINVAL;
+  VocWs w;
+  if ((long long)voc_carve(w, workspace, N) > workspace_bytes) return EFFDET_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int C = num_classes;
+  hipLaunchKernelGGL(voc_sort_init_kernel, dim3(voc_grid(N > 2LL * C ? N : 2LL * C)), dim3(256), 0, st, rec_key, w.ka, w.va, N, seg, C);
+  EFFDET_CHECK_LAUNCH();
+  unsigned long long *ki = w.ka, *ko = w.kb;
+  unsigned *vi = w.va, *vo = w.vb;
+  if (N > 0) {
+    const int passes = 4 + (C <= 255 ? 1 : 2);       // class values 0..C (C = empty slot)
+    for (int pass = 0; pass < passes; ++pass) {
+      hipLaunchKernelGGL((rs_hist_kernel<unsigned long long>), dim3(w.T, 1), dim3(256), 0, st, (const unsigned long long*)ki, w.hist, N, w.T, pass * 8);
+      hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(256), 0, st, w.hist, w.T);
+      hipLaunchKernelGGL((rs_scatter_kernel<unsigned long long>), dim3(w.T, 1), dim3(256), 0, st, (const unsigned long long*)ki,
+                         (const unsigned*)vi, ko, vo, (const unsigned*)w.hist, N, w.T, pass * 8);
+      EFFDET_CHECK_LAUNCH();
+      unsigned long long* t = ki; ki = ko; ko = t;
+      unsigned* u = vi; vi = vo; vo = u;
+    }
+    hipLaunchKernelGGL(voc_segments_kernel, dim3(voc_grid(N)), dim3(256), 0, st, (const unsigned long long*)ki, N, C, seg);
+    EFFDET_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(256), 0, st, (const unsigned*)vi, rec_tp, (const int*)seg, gt_count, recall, precision,
+                     ap, num_annotations);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}

@@ -1213,6 +1213,41 @@ def finalize_dets(score, label, boxes, count, scale, score_threshold, max_det, x
     return out, oc
 
 
+VOC_MAX_GT = 2048                  # GT rows per image effdet_voc_match stages in LDS
+
+
+def voc_match(dets, counts, gt_boxes, gt_labels, num_classes, iou_threshold, rec_key, rec_tp, gt_count):
+    """VOC matching of one batch: dets [B,max_det,6] fp32 + counts [B] int32 (finalize_dets), gt_boxes [B,G,4] fp64, gt_labels [B,G]
+    int32 (-1 = pad) -> writes rec_key / rec_tp [B*max_det] (int64 viewed as uint64 / uint8) and adds to gt_count [num_classes] int32."""
+    B, max_det = int(dets.shape[0]), int(dets.shape[1])
+    G = int(gt_boxes.shape[1])
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.shape[2] == 6
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == B
+    assert gt_boxes.dtype == torch.float64 and gt_boxes.is_contiguous() and tuple(gt_boxes.shape) == (B, G, 4)
+    assert gt_labels.dtype == torch.int32 and gt_labels.is_contiguous() and tuple(gt_labels.shape) == (B, G)
+    assert rec_key.dtype == torch.int64 and rec_tp.dtype == torch.uint8 and rec_key.numel() >= B * max_det and rec_tp.numel() >= B * max_det
+    assert gt_count.dtype == torch.int32 and gt_count.numel() == num_classes
+    L.check(L.lib().effdet_voc_match(L.ptr(dets), L.ptr(counts), L.ptr(gt_boxes), L.ptr(gt_labels), B, max_det, G, int(num_classes),
+                                     C.c_double(iou_threshold), L.ptr(rec_key), L.ptr(rec_tp), L.ptr(gt_count), L.stream_ptr()),
+            'effdet_voc_match')
+
+
+def voc_ap(rec_key, rec_tp, num_records, gt_count, num_classes):
+    """Per-class AP over the first num_records records -> (out [2, C] fp64 = (ap, num_annotations), recall [N] fp64, precision [N]
+    fp64 in sorted order, seg [C, 2] int32 = each class's [start, end) in that order)."""
+    dev = gt_count.device
+    N = int(num_records)
+    ws = torch.empty(int(L.lib().effdet_voc_ap_workspace_bytes(C.c_longlong(N))), dtype=torch.uint8, device=dev)
+    out = torch.empty((2, num_classes), dtype=torch.float64, device=dev)
+    recall = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
+    precision = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
+    seg = torch.empty((num_classes, 2), dtype=torch.int32, device=dev)
+    L.check(L.lib().effdet_voc_ap(L.ptr(rec_key), L.ptr(rec_tp), C.c_longlong(N), L.ptr(gt_count), int(num_classes), L.ptr(ws),
+                                  C.c_longlong(ws.numel()), L.ptr(out[0]), L.ptr(out[1]), L.ptr(recall), L.ptr(precision), L.ptr(seg),
+                                  L.stream_ptr()), 'effdet_voc_ap')
+    return out, recall[:N], precision[:N], seg
+
+
 def head_out_bwd(dprob, prob, dreg, dtype):
     """(d loss / d probability, probability, d loss / d regression) fp32 -> (dlogit, dreg) in the compute dtype."""
     dl = torch.empty(prob.shape, dtype=dtype, device=prob.device)

@@ -602,6 +602,30 @@ int effdet_finalize_dets(const float* score, const long long* label, const float
                          float score_threshold, int max_det, int xywh, float* out, int* out_count, int B, long long A,
                          effdet_stream_t stream);
 
+/* Device-side VOC mean AP, matching half (eval.py:185-219: _get_annotations, compute_overlap :19-43, the greedy assignment),
+ * over effdet_finalize_dets' rows of a batch:
+ *   dets [B][max_det][6] fp32 + counts [B] (the first counts[b] rows of image b are its detections, score-descending);
+ *   gt_boxes [B][G][4] fp64, gt_labels [B][G] int32 (-1 or any label outside [0, num_classes) = no row), 1 <= G <= 2048.
+ * A detection is a TP iff its fp64 IoU with its assigned GT (the first maximum over the image's GT rows of its class, in row
+ * order) is >= iou_threshold and it is the first of the image's detections of that class with that assigned GT to qualify.
+ * Writes B * max_det records (rec_key[b * max_det + k]: (class << 32) | descending-score key, class = num_classes for an empty
+ * slot; rec_tp: 1 = TP) and ADDS the image's GT rows per class to gt_count[num_classes] (integer atomics).  No workspace. */
+int effdet_voc_match(const float* dets, const int* counts, const double* gt_boxes, const int* gt_labels, int B, int max_det,
+                     int G, int num_classes, double iou_threshold, unsigned long long* rec_key, unsigned char* rec_tp,
+                     int* gt_count, effdet_stream_t stream);
+
+/* Device-side VOC mean AP, scoring half (eval.py:221-241 and _compute_ap :46-73) over num_records records of effdet_voc_match:
+ * a stable sort by (class, descending score) -- tied scores keep record order --, exact integer TP / FP cumsums, fp64
+ * recall = tp / n and precision = tp / max(tp + fp, DBL_EPSILON), the precision envelope and AP = sum over the TP positions k
+ * of (recall[k] - recall[k-1]) * envelope[k] in a fixed order.  Outputs: ap[num_classes], num_annotations[num_classes] fp64
+ * (0 and 0 for a class without GT), recall / precision [num_records] fp64 in sorted order and seg[2 * num_classes] int32:
+ * class c occupies sorted positions [seg[2c], seg[2c+1]) (its curves, when num_annotations[c] > 0).
+ * workspace: effdet_voc_ap_workspace_bytes(num_records) bytes. */
+long long effdet_voc_ap_workspace_bytes(long long num_records);
+int effdet_voc_ap(const unsigned long long* rec_key, const unsigned char* rec_tp, long long num_records, const int* gt_count,
+                  int num_classes, void* workspace, long long workspace_bytes, double* ap, double* num_annotations,
+                  double* recall, double* precision, int* seg, effdet_stream_t stream);
+
 /* Gradient of the head outputs (models/retinahead.py:119-127 under autograd):  dlogit = dprob * p * (1 - p) and dreg,
  * both stored in `dtype` for the head's data-gradient convs.  ncls / nreg: element counts. */
 int effdet_head_out_bwd(const float* dprob, const float* prob, const float* dreg, void* dlogit, void* dreg_out, int dtype,
@@ -613,7 +637,7 @@ const char* effdet_version(void);
 /* ABI generation of this header: bumped whenever an entry point's signature or a descriptor struct's layout changes.  A binding
  * compares effdet_abi_version() of the library it loaded with the EFFDET_ABI_VERSION it was written against and refuses a
  * mismatch (a stale .so called through ctypes / cgo with shifted arguments reads garbage instead of failing). */
-#define EFFDET_ABI_VERSION 10
+#define EFFDET_ABI_VERSION 11
 int effdet_abi_version(void);
 
 #ifdef __cplusplus
