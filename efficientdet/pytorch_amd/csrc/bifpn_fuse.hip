@@ -25,7 +25,7 @@ struct FuseW { float n[3]; float inv; float t_inv; float relu_mask[3]; };
 __device__ __forceinline__ FuseW fuse_weights(const float* wraw, int wrows, int wcols, int col, int nin) {
   FuseW f;
   float r[3] = {0.f, 0.f, 0.f}, T = 0.f;
-  for (int i = 0; i < wrows; ++i) { const float v = wraw[i * wcols + col]; r[i] = fmaxf(v, 0.f); f.relu_mask[i] = v > 0.f ? 1.f : 0.f; T += r[i]; }
+  for (int i = 0; i < wrows; ++i) { const float v = wraw[i * wcols + col]; r[i] = relu_(v); f.relu_mask[i] = relu_bwd_(v, 1.f); T += r[i]; }
   for (int i = wrows; i < 3; ++i) f.relu_mask[i] = 0.f;
   f.t_inv = 1.0f / (T + FEPS);
   float S = 0.f;
@@ -66,13 +66,13 @@ __global__ void fuse_fwd_kernel(const FuseK p) {
       Chunk<T>::unpack(((const uint4*)p.b)[base], bv);
       Chunk<T>::unpack(((const uint4*)p.b)[base + cpr], t);
 #pragma unroll
-      for (int e = 0; e < CE; ++e) bv[e] = fmaxf(bv[e], t[e]);
+      for (int e = 0; e < CE; ++e) bv[e] = nan_max(bv[e], t[e]);
       Chunk<T>::unpack(((const uint4*)p.b)[base + (long long)W2 * cpr], t);
 #pragma unroll
-      for (int e = 0; e < CE; ++e) bv[e] = fmaxf(bv[e], t[e]);
+      for (int e = 0; e < CE; ++e) bv[e] = nan_max(bv[e], t[e]);
       Chunk<T>::unpack(((const uint4*)p.b)[base + (long long)W2 * cpr + cpr], t);
 #pragma unroll
-      for (int e = 0; e < CE; ++e) bv[e] = fmaxf(bv[e], t[e]);
+      for (int e = 0; e < CE; ++e) bv[e] = nan_max(bv[e], t[e]);
     }
 #pragma unroll
     for (int e = 0; e < CE; ++e) o[e] = f.n[0] * av[e] + f.n[1] * bv[e];
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void fuse_bwd_kernel(const FuseK p) {
       }
       put<T>(p.db, i, dbv, p.db_acc);
     } else {
-      // a/out/c coarse grid, b fine (2H x 2W): route db to the first arg-max of the 2x2 window
+      // a/out/c coarse grid, b fine (2H x 2W): route db to the first arg-max of the 2x2 window, or to its last NaN (torch's max_pool2d)
       const int H2 = p.H * 2, W2 = p.W * 2;
       float av[CE], d[CE], bq[4][CE], bm[CE], cv[CE], dav[CE], dcv[CE];
       int arg[CE];
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void fuse_bwd_kernel(const FuseK p) {
       for (int e = 0; e < CE; ++e) {
         bm[e] = bq[0][e]; arg[e] = 0;
 #pragma unroll
-        for (int q = 1; q < 4; ++q) if (bq[q][e] > bm[e]) { bm[e] = bq[q][e]; arg[e] = q; }
+        for (int q = 1; q < 4; ++q) if (bq[q][e] > bm[e] || bq[q][e] != bq[q][e]) { bm[e] = bq[q][e]; arg[e] = q; }
       }
       if (p.mode == 1) Chunk<T>::unpack(((const uint4*)p.c)[i], cv);
       float dbm[CE];
@@ -212,16 +212,14 @@ __global__ __launch_bounds__(256) void fuse_weight_bwd_kernel(const float* wraw,
   if (threadIdx.x != 0) return;
   float r[3] = {0, 0, 0}, d[3] = {0, 0, 0}, T = 0.f;
   for (int i = 0; i < wrows; ++i) {
-    r[i] = fmaxf(wraw[i * wcols + col], 0.f); T += r[i];
+    r[i] = relu_(wraw[i * wcols + col]); T += r[i];
     d[i] = (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
   }
   const float ti = 1.0f / (T + FEPS);
   float dot = 0.f;
   for (int i = 0; i < wrows; ++i) dot += d[i] * r[i] * ti;
-  for (int i = 0; i < wrows; ++i) {
-    const float m = wraw[i * wcols + col] > 0.f ? 1.f : 0.f;
-    dwraw[i * wcols + col] += m * ti * (d[i] - dot);
-  }
+  for (int i = 0; i < wrows; ++i)       // (a select, not a multiply by the mask: torch's relu backward gives 0 there even if d is NaN)
+    if (relu_bwd_(wraw[i * wcols + col], 1.f) != 0.f) dwraw[i * wcols + col] += ti * (d[i] - dot);
 }
 
 inline int grid_for(long long n, int cap = 4096) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > cap ? cap : g)); }

@@ -39,6 +39,22 @@ __device__ __forceinline__ uint32_t pack2bf(float a, float b) {
 }
 __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack2bf(f, 0.f) & 0xffffu); }
 
+// NaN-propagating max / min (llvm.maximum / minimum: one v_maximum3_f32 / v_minimum3_f32 on gfx950, like the v_max_f32 of fmaxf).
+// fmaxf / fminf return the operand that is not NaN; torch's relu, clamp and max_pool2d keep the NaN, and so must every kernel
+// that restates one of them -- a diverged activation has to stay visible downstream, not become a plausible 0 or a clamp bound.
+__device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float nan_min(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float relu_(float v) { return nan_max(v, 0.f); }
+// ReLU backward from the forward OUTPUT q (torch's threshold_backward): the gradient is dropped where q <= 0 and passes elsewhere,
+// a NaN output included
+__device__ __forceinline__ float relu_bwd_(float q, float g) { return q <= 0.f ? 0.f : g; }
+// the same test on the bf16 bit pattern of q (hi half of a split activation): drop for +-0 and negative numbers, keep for positive
+// numbers and for a NaN of either sign
+__device__ __forceinline__ bool bf_relu_keep(unsigned h) {
+  const unsigned m = h & 0x7fffu;
+  return m != 0u && (!(h & 0x8000u) || m > 0x7f80u);
+}
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int CE = 4;  // elements per 16-byte chunk
@@ -124,7 +140,7 @@ __device__ __forceinline__ void hsplit_watch(const f32x4& v, int* flag) {
   (void)v; (void)flag; return;
 #endif
   if (flag) {
-    const float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    const float m = nan_max(nan_max(fabsf(v[0]), fabsf(v[1])), nan_max(fabsf(v[2]), fabsf(v[3])));     // (NaN in any lane -> NaN)
     if (!(m < 65520.f)) atomicOr(flag, 1);          // (also true for NaN)
   }
 }

@@ -455,7 +455,7 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
       else
         for (int r = 0; r < 4; ++r) if (n0 + r < p.Cout) Elem<T>::st((T*)p.z + o + r, v[r]);
     }
-    if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f); }
+    if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = relu_(v[r]); }
     else if (p.act == EFFDET_ACT_SWISH) { for (int r = 0; r < 4; ++r) v[r] = swishf_(v[r]); }
     else if (p.act == EFFDET_ACT_SIGMOID) { for (int r = 0; r < 4; ++r) v[r] = sigmoidf_(v[r]); }
     if (p.rowscale) v *= rs;
@@ -472,11 +472,11 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
         // split layout: channel n of a pixel row sits at byte (n >> 5) * 128 + (n & 31) * 2 (hi) and + 64 (lo); the lane's 4
         // consecutive channels (n0 % 4 == 0) are two 8-byte stores.  Host guarantees Cout % 32 == 0 and 128-byte aligned rows.
         const unsigned goff = (unsigned)(n0 >> 5) * 128u + (unsigned)(n0 & 31) * 2u;
-        if (p.res_mode == EFFDET_RES_RELU_MASK) {         // res = the forward activation in the same layout: sign of hi decides
+        if (p.res_mode == EFFDET_RES_RELU_MASK) {         // res = the forward activation in the same layout: hi decides
           const uint2 rh = *(const uint2*)((const char*)p.res + orow * 4 + goff);
           const unsigned rv[4] = {rh.x & 0xffffu, rh.x >> 16, rh.y & 0xffffu, rh.y >> 16};
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = ((rv[r] & 0x7fffu) != 0u && !(rv[r] & 0x8000u)) ? v[r] : 0.f;
+          for (int r = 0; r < 4; ++r) v[r] = bf_relu_keep(rv[r]) ? v[r] : 0.f;
         }
         uint2 hi, lo;
         hi.x = pack2bf(v[0], v[1]); hi.y = pack2bf(v[2], v[3]);
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
       else
         for (int r = 0; r < 4; ++r) q[r] = (n0 + r < p.Cout) ? Elem<T>::ld((const T*)p.res + o + r) : 0.f;
       if (p.res_mode == EFFDET_RES_ADD) { v += q; }
-      else if (p.res_mode == EFFDET_RES_RELU_MASK) { for (int r = 0; r < 4; ++r) v[r] = q[r] > 0.f ? v[r] : 0.f; }
+      else if (p.res_mode == EFFDET_RES_RELU_MASK) { for (int r = 0; r < 4; ++r) v[r] = relu_bwd_(q[r], v[r]); }
       else { for (int r = 0; r < 4; ++r) v[r] *= swish_gradf_(q[r]); }
     }
     if (p.out_f32) {
@@ -906,7 +906,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_pers_kernel(const Con
               for (int r = 0; r < 4; ++r)
                 if (n0 + r < p.Cout) { if (p.scale) v[r] *= p.scale[n0 + r]; if (p.shift) v[r] += p.shift[n0 + r]; }
             }
-            if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f); }
+            if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = relu_(v[r]); }
             else if (p.act == EFFDET_ACT_SWISH) { for (int r = 0; r < 4; ++r) v[r] = swishf_(v[r]); }
             else if (p.act == EFFDET_ACT_SIGMOID) { for (int r = 0; r < 4; ++r) v[r] = sigmoidf_(v[r]); }
             if (p.rowscale) v *= rs;
@@ -916,7 +916,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_pers_kernel(const Con
                 const uint2 rh = *(const uint2*)((const char*)p.res + orow * 4 + goff);
                 const unsigned rv[4] = {rh.x & 0xffffu, rh.x >> 16, rh.y & 0xffffu, rh.y >> 16};
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = ((rv[r] & 0x7fffu) != 0u && !(rv[r] & 0x8000u)) ? v[r] : 0.f;
+                for (int r = 0; r < 4; ++r) v[r] = bf_relu_keep(rv[r]) ? v[r] : 0.f;
               }
               uint2 hi, lo;
               hi.x = pack2bf(v[0], v[1]); hi.y = pack2bf(v[2], v[3]);
@@ -968,9 +968,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_pers_kernel(const Con
             for (int b = 0; b < 2; ++b)
               rr[a][h][b] = mok[b] ? *(const uint4*)((const bf16_t*)p.res + orow[b] + nw0 + a * 32 + h * 16 + lh * 8) : make_uint4(0u, 0u, 0u, 0u);
       }
-      auto relu_mask2 = [](unsigned v, unsigned r) -> unsigned {      // two packed bf16: keep v's half where r's half > 0
-        const unsigned lo = ((r & 0x7fffu) != 0u && !(r & 0x8000u)) ? 0x0000ffffu : 0u;
-        const unsigned hi = ((r & 0x7fff0000u) != 0u && !(r & 0x80000000u)) ? 0xffff0000u : 0u;
+      auto relu_mask2 = [](unsigned v, unsigned r) -> unsigned {      // two packed bf16: keep v's half where r's half > 0 or is NaN
+        const unsigned lo = bf_relu_keep(r & 0xffffu) ? 0x0000ffffu : 0u;
+        const unsigned hi = bf_relu_keep(r >> 16) ? 0xffff0000u : 0u;
         return v & (lo | hi);
       };
 #pragma unroll
@@ -1006,7 +1006,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_pers_kernel(const Con
               else
                 for (int r = 0; r < 4; ++r) if (n0 + r < p.Cout) Elem<bf16_t>::st((bf16_t*)p.z + o + r, v[r]);
             }
-            if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f); }
+            if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = relu_(v[r]); }
             else if (p.act == EFFDET_ACT_SWISH) { for (int r = 0; r < 4; ++r) v[r] = swishf_(v[r]); }
             else if (p.act == EFFDET_ACT_SIGMOID) { for (int r = 0; r < 4; ++r) v[r] = sigmoidf_(v[r]); }
             if (p.rowscale) v *= rsv[b];
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_pers_kernel(const Con
               else
                 for (int r = 0; r < 4; ++r) q[r] = (n0 + r < p.Cout) ? Elem<bf16_t>::ld((const bf16_t*)p.res + o + r) : 0.f;
               if (p.res_mode == EFFDET_RES_ADD) { v += q; }
-              else if (p.res_mode == EFFDET_RES_RELU_MASK) { for (int r = 0; r < 4; ++r) v[r] = q[r] > 0.f ? v[r] : 0.f; }
+              else if (p.res_mode == EFFDET_RES_RELU_MASK) { for (int r = 0; r < 4; ++r) v[r] = relu_bwd_(q[r], v[r]); }
               else { for (int r = 0; r < 4; ++r) v[r] *= swish_gradf_(q[r]); }
             }
             pk[gg][b] = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
@@ -1131,7 +1131,7 @@ __global__ __launch_bounds__(256) void conv_pw_f32_kernel(const ConvK p, int M, 
         }
         f32x4 v = f32x4{a01[0], a01[1], a23[0], a23[1]} * sc + sh;
         if (p.z) *(f32x4*)((float*)p.z + o) = v;
-        if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f); }
+        if (p.act == EFFDET_ACT_RELU) { for (int r = 0; r < 4; ++r) v[r] = relu_(v[r]); }
         else if (p.act == EFFDET_ACT_SWISH) { for (int r = 0; r < 4; ++r) v[r] = swishf_(v[r]); }
         else if (p.act == EFFDET_ACT_SIGMOID) { for (int r = 0; r < 4; ++r) v[r] = sigmoidf_(v[r]); }
         if (p.rowscale || p.bc_scale) {
@@ -1140,7 +1140,7 @@ __global__ __launch_bounds__(256) void conv_pw_f32_kernel(const ConvK p, int M, 
           if (p.bc_scale) { const int bo = bi * p.Cout + n0; v = v * *(const f32x4*)(p.bc_scale + bo) + *(const f32x4*)(p.bc_shift + bo); }
         }
         if (p.res_mode == EFFDET_RES_ADD) { v += q; }
-        else if (p.res_mode == EFFDET_RES_RELU_MASK) { for (int r = 0; r < 4; ++r) v[r] = q[r] > 0.f ? v[r] : 0.f; }
+        else if (p.res_mode == EFFDET_RES_RELU_MASK) { for (int r = 0; r < 4; ++r) v[r] = relu_bwd_(q[r], v[r]); }
         else if (p.res_mode == EFFDET_RES_SWISH_GRAD) { for (int r = 0; r < 4; ++r) v[r] *= swish_gradf_(q[r]); }
         *(f32x4*)((float*)p.y + o) = v;
       }

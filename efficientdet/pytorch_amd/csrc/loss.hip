@@ -104,9 +104,13 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const LossK p) {
   }
 }
 
+// d(loss)/d(logit) where the class term does not reach p (ignored anchor, image without annotations): 0 -- but NaN for a NaN (or inf)
+// p, because autograd's sigmoid backward still multiplies that zero by p (1 - p) (models/losses.py:53-57, :96)
+__device__ __forceinline__ float nan_zero(float p) { return p - p; }
+
 // per-element focal term and its derivative wrt the (unclamped) probability p
 __device__ __forceinline__ float focal_elem(float praw, bool target_one, float& dldp) {
-  const float pc = fminf(fmaxf(praw, 1e-4f), 1.0f - 1e-4f);
+  const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);         // (torch.clamp keeps a NaN: so does the loss)
   const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);   // clamp passes the gradient inside the range
   float l, d;
   if (target_one) {
@@ -207,6 +211,8 @@ __global__ __launch_bounds__(256) void loss_bwd_cls_kernel(const LossK p) {
     if (active && code != -2) {
       float d; (void)focal_elem(v[q], lab == k, d);
       g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
+    } else {
+      g[q] = nan_zero(v[q]);
     }
     if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1; }
   }
@@ -228,18 +234,21 @@ __global__ __launch_bounds__(256) void loss_bwd_cls_pix_kernel(const LossK p) {
   T* out = (T*)p.dcls + (long long)b * perp + e0;
   f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
   const float* st = p.stat + b * SS;
-  if (ch < cmax && st[3] > 0.f) {
+  if (ch < cmax) {
     const int an = ch / p.nc, k = ch - an * p.nc, a = pix * 9 + an;
-    const int code = p.assign[(long long)b * p.A + a];
+    const int code = st[3] > 0.f ? p.assign[(long long)b * p.A + a] : -2;
+    const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
     if (code != -2) {
       const float gs = p.gscale[0] / ((float)p.B * fmaxf(npos(st), 1.0f));
       const int lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
-      const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float d; (void)focal_elem(v[q], lab == k + q, d);
         g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
       }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) g[q] = nan_zero(v[q]);
     }
   }
   store4(out, g);
@@ -265,17 +274,20 @@ __global__ __launch_bounds__(256) void loss_cls_grad_pix_kernel(const LossK p) {
     if (e0 >= perp) break;
     const int pix = e0 / p.dld, ch = e0 - pix * p.dld;
     f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (ch < cmax && active) {
+    if (ch < cmax) {
       const int an = ch / p.nc, k = ch - an * p.nc, a = pix * 9 + an;
-      const int code = p.assign[(long long)b * p.A + a];
+      const int code = active ? p.assign[(long long)b * p.A + a] : -2;
+      const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
       if (code != -2) {
         const int lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
-        const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float d; s += focal_elem(v[q], lab == k + q, d);
           g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
         }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = nan_zero(v[q]);
       }
     }
     store4((T*)p.dcls + (long long)b * perp + e0, g);
@@ -310,7 +322,9 @@ __global__ void loss_bwd_reg_kernel(const LossK p) {
       for (int q = 0; q < 4; ++q) {
         const float diff = rv[q] - t[q], d = fabsf(diff);
         const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-        g[q] = gs * ((d <= 1.0f / 9.0f) ? 9.0f * d * sgn : sgn);
+        // (0 * d: autograd of the reference's where(d <= 1/9, 4.5 d^2, d - 1/18) sends 0 * 9d into the branch not taken -- NaN when d is
+        //  NaN or inf, and the gradient with it)
+        g[q] = gs * ((d <= 1.0f / 9.0f) ? 9.0f * d * sgn : sgn + 0.f * d);
       }
     }
     if (p.reg_ld) {       // pixel-major rows with a padded pitch (the layout the head's data-gradient conv reads; pad channels zeroed here)

@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void opt_adamw_kernel(const OptK kk) {
   float* g = (float*)kk.g[ti];
   if (!g) return;
   float* p = (float*)kk.p[ti]; float* m = (float*)kk.m[ti]; float* v = (float*)kk.v[ti];
-  const float coef = k.max_norm > 0.f ? fminf(1.0f, k.max_norm / (kk.norm[0] + 1e-6f)) : 1.0f;
+  // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)) with torch.clamp's NaN rule -- a NaN norm turns every gradient into NaN
+  const float coef = k.max_norm > 0.f ? nan_min(1.0f, k.max_norm / (kk.norm[0] + 1e-6f)) : 1.0f;
   const float t = (float)kk.steps[ti];                       // already advanced by opt_norm_final_kernel
   const float step_size = k.lr / (1.0f - powf(k.beta1, t)), bc2_sqrt = sqrtf(1.0f - powf(k.beta2, t));
   const long long n = kk.n[ti], off = (long long)(blockIdx.x - kk.block_first[ti]) * OPT_CHUNK;

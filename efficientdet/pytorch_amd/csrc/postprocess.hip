@@ -59,12 +59,14 @@ __global__ __launch_bounds__(256) void decode_score_kernel(const float* __restri
   const int r = threadIdx.x >> 2, q = threadIdx.x & 3;
   float m = -1.0f; int arg = 0x7fffffff;
   if (r < na) {
-    for (int k = q; k < nc; k += 4) { const float v = tile[r * ld + k]; if (v > m) { m = v; arg = k; } }
+    // (torch.max: a NaN is the maximum -- the first NaN; the anchor's score is then NaN and the NMS threshold drops it)
+    for (int k = q; k < nc; k += 4) { const float v = tile[r * ld + k]; if (v > m || (v != v && m == m)) { m = v; arg = k; } }
   }
 #pragma unroll
   for (int o = 1; o <= 2; o <<= 1) {
     const float om = __shfl_xor(m, o, 64); const int oa = __shfl_xor(arg, o, 64);
-    if (om > m || (om == m && oa < arg)) { m = om; arg = oa; }
+    const bool on = om != om, mn = m != m;
+    if (on ? (!mn || oa < arg) : (!mn && (om > m || (om == m && oa < arg)))) { m = om; arg = oa; }
   }
   if (r < na && q == 0) {
     const long long i = i0 + r;
@@ -77,8 +79,9 @@ __global__ __launch_bounds__(256) void decode_score_kernel(const float* __restri
     const float pcx = cx + dx * w, pcy = cy + dy * h;
     const float pw = expf(dw) * w, ph = expf(dh) * h;
     float4 b;
-    b.x = fmaxf(pcx - 0.5f * pw, 0.f); b.y = fmaxf(pcy - 0.5f * ph, 0.f);
-    b.z = fminf(pcx + 0.5f * pw, img_w); b.w = fminf(pcy + 0.5f * ph, img_h);
+    // (torch.clamp of ClipBoxes keeps a NaN coordinate; the NMS below files no NaN box and cell_of stays in range for one)
+    b.x = nan_max(pcx - 0.5f * pw, 0.f); b.y = nan_max(pcy - 0.5f * ph, 0.f);
+    b.z = nan_min(pcx + 0.5f * pw, img_w); b.w = nan_min(pcy + 0.5f * ph, img_h);
     ((float4*)boxes)[i] = b;
     score[i] = m; label[i] = arg;
   }

@@ -337,7 +337,7 @@ __global__ void act_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ a
     if (act != EFFDET_ACT_NONE) {
       Chunk<T>::unpack(((const uint4*)aux)[i], a);
 #pragma unroll
-      for (int e = 0; e < CE; ++e) d[e] = (act == EFFDET_ACT_RELU) ? (a[e] > 0.f ? d[e] : 0.f) : d[e] * swish_gradf_(a[e]);
+      for (int e = 0; e < CE; ++e) d[e] = (act == EFFDET_ACT_RELU) ? relu_bwd_(a[e], d[e]) : d[e] * swish_gradf_(a[e]);
     }
     if (rowscale) { const float r = rowscale[i / per_image_chunks];
 #pragma unroll

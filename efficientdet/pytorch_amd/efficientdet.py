@@ -528,6 +528,9 @@ class EfficientDet(nn.Module):
     def detect(self, img):
         """Eval post-processing for EVERY image of the batch (the reference handles image 0 only).
         -> list of (scores[K], labels[K] int64, boxes[K,4]) per image, score-descending."""
+        f16x3 = ops.MODEL_ARITH[self.f32_arith][2] == 'f16x3'
+        if f16x3:
+            ops.clear_range_flag(img.device)                     # (report this call's overflow only, not one of an earlier training step)
         with torch.no_grad():
             cls, reg, anc = self.forward_raw(img)
         H, W = int(img.shape[2]), int(img.shape[3])
@@ -535,7 +538,7 @@ class EfficientDet(nn.Module):
         idx, count = ops.nms(boxes, score, float(self.threshold), float(self.iou_threshold))
         s, l, b = ops.gather_dets(boxes, score, label, idx, count)
         counts = count.tolist()                                  # the one device->host sync (the reference syncs too)
-        if ops.MODEL_ARITH[self.f32_arith][2] == 'f16x3' and not torch.cuda.is_current_stream_capturing():
+        if f16x3 and not torch.cuda.is_current_stream_capturing():
             ops.check_range_flag(s.device)                       # (a sigmoid turns an inf logit into a plausible score: make overflow an error)
         return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
 

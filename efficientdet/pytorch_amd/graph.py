@@ -179,7 +179,11 @@ class GraphedDetect:
         self.images = images.clone()
         H, W = int(images.shape[2]), int(images.shape[3])
 
+        f16x3 = ops.MODEL_ARITH[getattr(model, 'f32_arith', 'f32')][2] == 'f16x3'
+
         def run():
+            if f16x3:
+                ops.clear_range_flag(self.images.device)       # (a kernel node of the graph: every replay reports its own overflow only)
             with torch.no_grad():
                 cls, reg, anc = model.forward_raw(self.images)
                 boxes, score, label = ops.decode_score(anc, reg, cls, H, W)

@@ -113,6 +113,13 @@ def range_flag(device):
     return t
 
 
+def clear_range_flag(device):
+    """Start a guarded call (detect(), a GraphedDetect replay) with a clean watch: what the next check reports is then that call's own
+    overflow, not one left by a training step in between.  fill_ is an elementwise kernel on the current stream, so it is captured into a
+    graph as a kernel node (a memset node did not hold inside captured graphs here, loss.hip zero_stat)."""
+    range_flag(device).fill_(0)
+
+
 def check_range_flag(device, what='f16x3'):
     """Host-side read of the watch (synchronises the current stream): raises -- and clears the flag -- if a value left fp16's range since
     the last check."""

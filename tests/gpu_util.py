@@ -43,3 +43,27 @@ def unmatched_detections(got, ref, score_tol, box_tol=1e-2):
         else:
             missing += 1
     return missing, int(free.sum())
+
+
+def assert_nonfinite_match(got, ref, tol, exact=True, what=''):
+    """Non-finite parity, then assert_close on the rest.  exact=True: the NaN masks are equal and the +inf / -inf masks are equal sign for
+    sign.  exact=False: only the isfinite masks are equal -- for sums of products through the x3 split forms, where inf - inf inside the
+    split may turn an inf into a NaN.  The finite elements of both then pass assert_close at `tol` (the op's own parity tolerance)."""
+    got = got.detach().double().cpu(); ref = ref.detach().double().cpu()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+
+    def same(mg, mr, kind):
+        if not torch.equal(mg, mr):
+            bad = torch.nonzero((mg != mr).reshape(-1)).reshape(-1)
+            i = int(bad[0])
+            raise AssertionError('%s: %s mask differs at %d/%d elements (first at %d: got %g ref %g)' % (
+                what, kind, bad.numel(), mg.numel(), i, float(got.reshape(-1)[i]), float(ref.reshape(-1)[i])))
+    if exact:
+        same(torch.isnan(got), torch.isnan(ref), 'NaN')
+        same(got == float('inf'), ref == float('inf'), '+inf')
+        same(got == float('-inf'), ref == float('-inf'), '-inf')
+    else:
+        same(torch.isfinite(got), torch.isfinite(ref), 'isfinite')
+    fin = torch.isfinite(ref)
+    if bool(fin.any()):
+        assert_close(got[fin], ref[fin], tol, what)
