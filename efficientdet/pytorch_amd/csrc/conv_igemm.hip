@@ -1163,33 +1163,81 @@ static bool pw_eligible(const effdet_conv_t* p) {
   return (long long)p->B * g.H * g.W >= 65536;
 }
 
-// tile_start of every segment in units of BM-row tiles; returns the total
-static int retile(ConvK& k, int bm) {
-  int tiles = 0;
-  for (int s = 0; s < k.nseg; ++s) { k.seg[s].tile_start = tiles; tiles += (k.seg[s].M + bm - 1) / bm; }
-  for (int s = k.nseg; s < EFFDET_MAX_CONV_SEG; ++s) k.seg[s].tile_start = 0x7fffffff;
-  k.mtiles = tiles;
-  return tiles;
+// What effdet_conv2d launches for one descriptor, decided by plan_conv without a HIP runtime call
+struct ConvPlan {
+  int id;                      // the public kernel id (effdet_conv2d_kernel)
+  ConvK k;                     // the final kernel arguments
+  int (*launch)(const ConvPlan&, hipStream_t);     // the one template instance that runs it
+  unsigned grid;               // workgroups (the persistent kernel: its tile count, capped at the device's CUs by its launcher)
+  size_t lds;                  // dynamic LDS bytes
+  int pw_G, pw_NPS, pw_ppw;    // conv_pw_f32_kernel: channel groups, pixel slots per workgroup, pixels per workgroup
+};
+
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT, int NS, int M32>
+int launch_igemm(const ConvPlan& c, hipStream_t st) {
+  if (c.lds > 48 * 1024) EFFDET_SET_MAX_LDS((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>), c.lds);
+  hipLaunchKernelGGL((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>), dim3(c.grid), dim3(NWAVES * 64), c.lds, st, c.k);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0>
+int use_igemm(ConvPlan& c, int id) {
+  c.k.ntiles = (c.k.Cout + BN - 1) / BN;
+  c.grid = (unsigned)(c.k.mtiles * c.k.ntiles);
+  c.lds = (size_t)NS * (BM + BN) * 8 * sizeof(uint4);                    // NS-stage operand tiles
+  c.launch = launch_igemm<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>;
+  return c.id = id;
 }
 
+template <int WM, int WN, int NS, int X3>
+int launch_pers(const ConvPlan& c, hipStream_t st) {
+  EFFDET_SET_MAX_LDS((conv_igemm_pers_kernel<WM, WN, NS, X3>), c.lds);
+  static unsigned ncu = 0;                              // CUs of the current device (all devices of a node are alike)
+  if (ncu == 0) { int dev = 0; hipDeviceProp_t pr; ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
+  const unsigned grid = c.grid < ncu ? c.grid : ncu;   // one workgroup per CU (the LDS footprint allows no second one)
+  hipLaunchKernelGGL((conv_igemm_pers_kernel<WM, WN, NS, X3>), dim3(grid), dim3(WM * WN * 64), c.lds, st, c.k);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
 template <int WM, int WN, int NS, int X3 = 0>
-int launch_pers(ConvK& k, hipStream_t st) {
+int use_pers(ConvPlan& c, int id) {
   constexpr int TM = 64 * WM, TN = 64 * WN;
-  retile(k, TM);
+  ConvK& k = c.k;
+  k.mtiles = 0;       // tile_start of every segment in units of TM-row tiles
+  for (int s = 0; s < k.nseg; ++s) { k.seg[s].tile_start = k.mtiles; k.mtiles += (k.seg[s].M + TM - 1) / TM; }
   k.ntiles = (k.Cout + TN - 1) / TN;
-  const size_t lds = (size_t)NS * (TM + TN) * 128;
   if (X3) {           // input side into the bf16 VIEW of the split layout (see the kernel): element = 2 bytes, twice the counts
     k.ldx *= 2;       // (cpt / Kc count 16-byte chunks: the same in both views)
     for (int s = 0; s < k.nseg; ++s) { k.seg[s].in_off *= 2; k.seg[s].in_bs *= 2; }
   }
-  EFFDET_SET_MAX_LDS((conv_igemm_pers_kernel<WM, WN, NS, X3>), lds);
-  static int ncu = 0;                                   // CUs of the current device (all devices of a node are alike)
-  if (ncu == 0) { int dev = 0; hipDeviceProp_t pr; ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
-  const int total = k.mtiles * k.ntiles;
-  const int grid = total < ncu ? total : ncu;          // one workgroup per CU (the LDS footprint allows no second one)
-  hipLaunchKernelGGL((conv_igemm_pers_kernel<WM, WN, NS, X3>), dim3(grid), dim3(WM * WN * 64), lds, st, k);
+  c.grid = (unsigned)(k.mtiles * k.ntiles);
+  c.lds = (size_t)NS * (TM + TN) * 128;
+  c.launch = launch_pers<WM, WN, NS, X3>;
+  return c.id = id;
+}
+// persistent big-tile variant by kernel id (10 + v, see plan_conv)
+static int use_big(ConvPlan& c, int id) {
+  switch (id) {
+    case 10 + 442: return use_pers<4, 4, 2>(c, id);
+    case 10 + 242: return use_pers<2, 4, 2>(c, id);
+    case 10 + 243: return use_pers<2, 4, 3>(c, id);
+    case 10 + 4220: return use_pers<4, 2, 2>(c, id);
+    default: return use_pers<4, 2, 3>(c, id);        // 10 + 423 | 10 + 4230
+  }
+}
+
+template <int CIN>
+int launch_pw(const ConvPlan& c, hipStream_t st) {
+  hipLaunchKernelGGL(conv_pw_f32_kernel<CIN>, dim3(c.grid), dim3(256), 0, st, c.k, c.k.seg[0].M, c.pw_G, c.pw_NPS, c.pw_ppw);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
+}
+static int use_pw(ConvPlan& c) {
+  c.pw_G = c.k.Cout / 4; c.pw_NPS = 256 / c.pw_G; c.pw_ppw = 1024;      // 16 tiles of 64 pixels per workgroup
+  c.grid = (unsigned)((c.k.seg[0].M + c.pw_ppw - 1) / c.pw_ppw);
+  c.lds = 0;
+  c.launch = c.k.Cin == 16 ? launch_pw<16> : launch_pw<24>;
+  return c.id = 20;
 }
 
 // Tuning knobs (effdet_tuning_set; A/B experiments and tests): which persistent big-tile shape serves an eligible conv
@@ -1202,47 +1250,33 @@ static int big_variant() {
   return g_tuning[EFFDET_TUNE_IGEMM_BIG];
 }
 
-template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0>
-int launch(const ConvK& k, hipStream_t st) {
-  const size_t lds = (size_t)NS * (BM + BN) * 8 * sizeof(uint4);                    // NS-stage operand tiles
-  const int grid = k.mtiles * k.ntiles;
-  if (lds > 48 * 1024) EFFDET_SET_MAX_LDS((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>), lds);
-  hipLaunchKernelGGL((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>), dim3(grid), dim3(NWAVES * 64), lds, st, k);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-template <typename T, int SPLIT = 0>
-int dispatch(ConvK& k, hipStream_t st) {
-  int bn;
-  if (k.Cout > 64) bn = 128; else if (k.Cout > 32) bn = 64; else if (k.Cout > 16) bn = 32; else bn = 16;
-  k.ntiles = (k.Cout + bn - 1) / bn;
-  {
-    // at most one tile per CU and a K loop worth pipelining: deep staging (see the kernel's NS note).  (EFFDET_IGEMM_DEEP: 0 off,
-    // 1 exact-fp32 / bf16 only, 2 (default) also the bf16x3 register-split form -- the 8x8 / 4x4 stages of the backbone and the
-    // coarse BiFPN levels are 16..144 workgroups walking 18..36 K-steps at one DMA round trip each)
-    static const int deep_env = getenv("EFFDET_IGEMM_DEEP") ? atoi(getenv("EFFDET_IGEMM_DEEP")) : 2;      // A/B switch
-    if ((SPLIT ? deep_env >= 2 : deep_env >= 1) && (long long)k.mtiles * k.ntiles <= 256 && k.Kc >= 6 * 8) {
-      // a handful of 128-wide tiles with a long K loop (the project convs of the 8x8 / 4x4 stages: 16 x 2 tiles, 36 K-steps) are bound
-      // by the MFMA work of their few CUs (0.66 us per K-step on 32 of 256 CUs): narrower tiles spread the same work over 4x the CUs
-      // A/B switch: up to how many 128/64-wide tiles (0 = off).  Round 3: 64 took the D0 step from 27.91 to 27.61 ms, 128 / 256 measured the
-      // same THERE.  Round 5: 128 -- the 224 -> 224 BiFPN convs of D4 at M = 8192 (64 x 2 wide tiles on 256 CUs, 63 K-steps each) go from
-      // 1.78 to 1.05 ms per forward (49.8 -> 84.9 TFLOP/s, 12 launches); configs[4] forward 4.758 -> 4.627 ms/img, D0 train / inference +-0
-      static const int narrow = getenv("EFFDET_IGEMM_NARROW") ? atoi(getenv("EFFDET_IGEMM_NARROW")) : 128;
-      static const int narrow_k = getenv("EFFDET_IGEMM_NARROW_K") ? atoi(getenv("EFFDET_IGEMM_NARROW_K")) : 16;
-      if (narrow && bn >= 64 && (long long)k.mtiles * k.ntiles <= narrow && k.Kc >= narrow_k * 8) {
-        k.ntiles = (k.Cout + 31) / 32;
-        return launch<T, 32, 1, 4, SPLIT, 4>(k, st);
-      }
-      if (bn == 128) return launch<T, 128, 2, 8, SPLIT, 4>(k, st);
-      if (bn == 64) return launch<T, 64, 1, 4, SPLIT, 4>(k, st);
-    }
+// Block tile (bt = 0..3: 128 / 64 / 32 / 16 channels) and staging depth of the 128-pixel-tile kernel: ids 0..3, 4..7 with SPLIT = 1
+template <typename T, int SPLIT>
+int use_tile(ConvPlan& c, int bt) {
+  const ConvK& k = c.k;
+  const int id = bt + (SPLIT ? 4 : 0), bn = 128 >> bt;
+  const long long tiles = (long long)k.mtiles * ((k.Cout + bn - 1) / bn);
+  // at most one tile per CU and a K loop worth pipelining: deep staging (see the kernel's NS note).  (EFFDET_IGEMM_DEEP: 0 off,
+  // 1 exact-fp32 / bf16 only, 2 (default) also the bf16x3 register-split form -- the 8x8 / 4x4 stages of the backbone and the
+  // coarse BiFPN levels are 16..144 workgroups walking 18..36 K-steps at one DMA round trip each)
+  static const int deep_env = getenv("EFFDET_IGEMM_DEEP") ? atoi(getenv("EFFDET_IGEMM_DEEP")) : 2;      // A/B switch
+  if ((SPLIT ? deep_env >= 2 : deep_env >= 1) && tiles <= 256 && k.Kc >= 6 * 8) {
+    // a handful of 128-wide tiles with a long K loop (the project convs of the 8x8 / 4x4 stages: 16 x 2 tiles, 36 K-steps) are bound
+    // by the MFMA work of their few CUs (0.66 us per K-step on 32 of 256 CUs): narrower tiles spread the same work over 4x the CUs
+    // A/B switch: up to how many 128/64-wide tiles (0 = off).  Round 3: 64 took the D0 step from 27.91 to 27.61 ms, 128 / 256 measured the
+    // same THERE.  Round 5: 128 -- the 224 -> 224 BiFPN convs of D4 at M = 8192 (64 x 2 wide tiles on 256 CUs, 63 K-steps each) go from
+    // 1.78 to 1.05 ms per forward (49.8 -> 84.9 TFLOP/s, 12 launches); configs[4] forward 4.758 -> 4.627 ms/img, D0 train / inference +-0
+    static const int narrow = getenv("EFFDET_IGEMM_NARROW") ? atoi(getenv("EFFDET_IGEMM_NARROW")) : 128;
+    static const int narrow_k = getenv("EFFDET_IGEMM_NARROW_K") ? atoi(getenv("EFFDET_IGEMM_NARROW_K")) : 16;
+    if (narrow && bt <= 1 && tiles <= narrow && k.Kc >= narrow_k * 8) return use_igemm<T, 32, 1, 4, SPLIT, 4>(c, id);
+    if (bt == 0) return use_igemm<T, 128, 2, 8, SPLIT, 4>(c, id);
+    if (bt == 1) return use_igemm<T, 64, 1, 4, SPLIT, 4>(c, id);
   }
-  switch (bn) {
-    case 128: return launch<T, 128, 2, 8, SPLIT>(k, st);
-    case 64: return launch<T, 64, 1, 4, SPLIT>(k, st);
-    case 32: return launch<T, 32, 1, 4, SPLIT>(k, st);
-    default: return launch<T, 16, 1, 4, SPLIT>(k, st);
+  switch (bt) {
+    case 0: return use_igemm<T, 128, 2, 8, SPLIT>(c, id);
+    case 1: return use_igemm<T, 64, 1, 4, SPLIT>(c, id);
+    case 2: return use_igemm<T, 32, 1, 4, SPLIT>(c, id);
+    default: return use_igemm<T, 16, 1, 4, SPLIT>(c, id);
   }
 }
 
@@ -1256,10 +1290,9 @@ extern "C" int effdet_tuning_set(int key, int value) {
   return old;
 }
 
-// Validates the descriptor, fills the kernel arguments and picks the kernel: -> EFFDET_E* (< 0), or the kernel id
-// 0..3 = conv_igemm_kernel with a 128 / 64 / 32 / 16-channel block tile, 10 + v = persistent big-tile variant v
-// (v = 442 | 242 | 243 | 423; 4420 / 4220 = their <= 128-channel forms).
-static int plan_conv(const effdet_conv_t* p, ConvK& k) {
+// Validates the descriptor and fills the plan: -> EFFDET_E* (< 0), or the kernel id (the list at effdet_conv2d_kernel in the header).
+static int plan_conv(const effdet_conv_t* p, ConvPlan& c) {
+  ConvK& k = c.k;
   if (!p || !p->x || !p->w || !p->y) return EFFDET_EINVAL;
   if (p->nseg < 1 || p->nseg > EFFDET_MAX_CONV_SEG) return EFFDET_EINVAL;
   if (p->dtype != EFFDET_F32 && p->dtype != EFFDET_BF16 && p->dtype != EFFDET_F32_BF16X3 && p->dtype != EFFDET_F32_SPLIT && p->dtype != EFFDET_F32_HSPLIT) return EFFDET_EINVAL;
@@ -1347,99 +1380,65 @@ static int plan_conv(const effdet_conv_t* p, ConvK& k) {
   k.w_bytes = (unsigned)wb;
   if (hfmt) {
     k.scale = (const float*)((const char*)p->w + wb);        // [Cout] x 1 / S_n, written by the pack right behind the rows
-    return p->Cout > 64 ? 30 : 31;                           // conv_igemm_kernel<float, 128 | 64, ..., SPLIT = 3>
+    return p->Cout > 64 ? use_igemm<float, 128, 2, 8, 3>(c, 30) : use_igemm<float, 64, 1, 4, 3>(c, 31);
   }
-  if (p->dtype == EFFDET_BF16 && !per_seg && !p->bc_scale && !p->w_image_stride && p->Cin % 64 == 0 && p->KH * p->KW <= 32 && p->Cout >= 128 && big_variant() != 0 && wb < 0x40000000LL) {
-    long long mtot = 0;
-    bool fits = true;        // offsets + the tap walk's SGPR offset must stay below the 2-GiB sentinel
-    for (int s = 0; s < p->nseg; ++s) {
-      mtot += k.seg[s].M;
-      if ((long long)k.seg[s].x_bytes + 2LL * ((long long)p->KH * p->seg[s].W + p->KW) * p->ldx * 2 >= 0x70000000LL) fits = false;
-    }
-    if (fits && mtot >= g_tuning[EFFDET_TUNE_IGEMM_BIG_MIN_M]) {
-      const int v = big_variant();
-      if (v == 1) {
-        // measured on the RetinaHead shapes (tools/kbench2.py, B = 32 @512): the persistent 256x256 kernel wins where the K
-        // loop is long enough to amortise its exposed epilogue -- tower forward 885 vs 797 TFLOP/s, d(cls) data gradient
-        // 1005-1036 vs 957 -- and loses where the epilogue reads a residual behind a short K loop (tower data gradient
-        // 726 vs 866) or K is short (first tower layer 560 vs 658): those stay on the two-workgroups-per-CU kernel
-        const long long K = (long long)k.Kc * 8;
-        if (p->Cout >= 192 && mtot >= 65536 && ((p->res_mode == EFFDET_RES_NONE && K >= 2304) || K >= 4608)) return 10 + 442;
-      } else if (v == 442 || v == 242 || v == 243 || v == 423) {
-        return 10 + ((p->Cout > 128 || v == 423) ? v : (v == 243 ? 4230 : 4220));
-      }
+  long long mtot = 0;
+  bool fits = true;          // persistent kernels: offsets + the tap walk's SGPR offset must stay below the 2-GiB sentinel
+  for (int s = 0; s < p->nseg; ++s) {
+    mtot += k.seg[s].M;
+    if ((long long)k.seg[s].x_bytes + 2LL * ((long long)p->KH * p->seg[s].W + p->KW) * p->ldx * es >= 0x70000000LL) fits = false;
+  }
+  if (p->dtype == EFFDET_BF16 && !per_seg && !p->bc_scale && !p->w_image_stride && p->Cin % 64 == 0 && p->KH * p->KW <= 32 && p->Cout >= 128 && big_variant() != 0 && wb < 0x40000000LL &&
+      fits && mtot >= g_tuning[EFFDET_TUNE_IGEMM_BIG_MIN_M]) {
+    const int v = big_variant();
+    if (v == 1) {
+      // measured on the RetinaHead shapes (tools/kbench2.py, B = 32 @512): the persistent 256x256 kernel wins where the K
+      // loop is long enough to amortise its exposed epilogue -- tower forward 885 vs 797 TFLOP/s, d(cls) data gradient
+      // 1005-1036 vs 957 -- and loses where the epilogue reads a residual behind a short K loop (tower data gradient
+      // 726 vs 866) or K is short (first tower layer 560 vs 658): those stay on the two-workgroups-per-CU kernel
+      const long long K = (long long)k.Kc * 8;
+      if (p->Cout >= 192 && mtot >= 65536 && ((p->res_mode == EFFDET_RES_NONE && K >= 2304) || K >= 4608)) return use_big(c, 10 + 442);
+    } else if (v == 442 || v == 242 || v == 243 || v == 423) {
+      return use_big(c, 10 + ((p->Cout > 128 || v == 423) ? v : (v == 243 ? 4230 : 4220)));
     }
   }
-  if (!per_seg && !p->w_image_stride && !p->y_split && pw_eligible(p)) return 20;
+  if (!per_seg && !p->w_image_stride && !p->y_split && pw_eligible(p)) return use_pw(c);
   const int bt = k.Cout > 64 ? 0 : k.Cout > 32 ? 1 : k.Cout > 16 ? 2 : 3;
-  if (p->dtype == EFFDET_F32_BF16X3) return (k.Kc % 8) ? EFFDET_EUNSUPPORTED : 4 + bt;   // K-step = one [hi|lo] weight group
+  if (p->dtype == EFFDET_F32_BF16X3) {
+    if (k.Kc % 8) return EFFDET_EUNSUPPORTED;                // K-step = one [hi|lo] weight group
+    k.kord = 0;
+    return use_tile<float, 1>(c, bt);
+  }
   if (p->dtype == EFFDET_F32_SPLIT) {
     // persistent 256 x 256 / 32x32x16 form for the long-K head convs (tuning knob EFFDET_TUNE_SPLIT_PERS / env EFFDET_SPLIT_PERS).
     // In-step A/B on the D0 train step (same box, ms/step): off 27.83 | all eligible 27.57 | forward convs only (default) 27.33 |
     // residual-epilogue convs only 27.94 -- the exposed epilogue of the persistent form costs more where it also reads the ReLU mask.
     if (g_tuning[EFFDET_TUNE_SPLIT_PERS] < 0) g_tuning[EFFDET_TUNE_SPLIT_PERS] = getenv("EFFDET_SPLIT_PERS") ? atoi(getenv("EFFDET_SPLIT_PERS")) : 2;
     if (g_tuning[EFFDET_TUNE_SPLIT_PERS] > 0 && !per_seg && !p->bc_scale && p->KH * p->KW <= 32 && p->Cout >= 192 && wb < 0x40000000LL) {
-      long long mtot = 0;
-      bool fits = true;
-      for (int s = 0; s < p->nseg; ++s) {
-        mtot += k.seg[s].M;
-        if ((long long)k.seg[s].x_bytes + 2LL * ((long long)p->KH * p->seg[s].W + p->KW) * p->ldx * 4 >= 0x70000000LL) fits = false;
-      }
       // knob values: 1 = every eligible conv, 2 = only those without a residual epilogue (forward convs), 3 = only those WITH one
       const int pv = g_tuning[EFFDET_TUNE_SPLIT_PERS];
       const bool pick = pv == 1 || (pv == 2 && p->res_mode == EFFDET_RES_NONE) || (pv == 3 && p->res_mode != EFFDET_RES_NONE);
-      if (pick && fits && mtot >= g_tuning[EFFDET_TUNE_IGEMM_BIG_MIN_M] && (long long)k.Kc * 4 >= 1152) return 10000 + 442;
+      if (pick && fits && mtot >= g_tuning[EFFDET_TUNE_IGEMM_BIG_MIN_M] && (long long)k.Kc * 4 >= 1152) return use_pers<4, 4, 2, 1>(c, 10000 + 442);
     }
-    return 8 + (bt > 1 ? 1 : bt);                        // (block tiles of 128 / 64 output channels)
+    // block tiles of 128 / 64 output channels; A/B switch: 32x32x16 tiles (measured 342-360 TFLOP/s) vs 16x16x32 (370-390)
+    static const int m32 = getenv("EFFDET_SPLIT_M32") ? atoi(getenv("EFFDET_SPLIT_M32")) : 0;
+    if (bt == 0) return m32 ? use_igemm<float, 128, 2, 8, 2, 2, 1>(c, 8) : use_igemm<float, 128, 2, 8, 2>(c, 8);
+    return m32 ? use_igemm<float, 64, 1, 4, 2, 2, 1>(c, 9) : use_igemm<float, 64, 1, 4, 2>(c, 9);
   }
-  return bt;
+  // K walk of the plain 128-pixel-tile kernels: tap-major, or (exact fp32, 3x3, whole 32-channel groups; env EFFDET_F32_KORD, A/B)
+  // channel-group-major like the split-layout convs -- same products, another summation order, fewer L2 -> fabric re-fetches
+  static const int f32_kord = getenv("EFFDET_F32_KORD") ? atoi(getenv("EFFDET_F32_KORD")) : 0;
+  k.kord = (f32_kord && p->dtype == EFFDET_F32 && p->KH * p->KW > 1 && k.cpt % 8 == 0 && p->Cin >= f32_kord) ? 1 : 0;
+  return p->dtype == EFFDET_BF16 ? use_tile<bf16_t, 0>(c, bt) : use_tile<float, 0>(c, bt);
 }
 
 extern "C" int effdet_conv2d_kernel(const effdet_conv_t* p) {
-  ConvK k;
-  return plan_conv(p, k);
+  ConvPlan c;
+  return plan_conv(p, c);
 }
 
 extern "C" int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream) {
-  ConvK k;
-  const int id = plan_conv(p, k);
-  if (id < 0) return id;
-  hipStream_t st = (hipStream_t)stream;
-  switch (id) {
-    case 10 + 442: return launch_pers<4, 4, 2>(k, st);
-    case 10 + 242: return launch_pers<2, 4, 2>(k, st);
-    case 10 + 243: return launch_pers<2, 4, 3>(k, st);
-    case 10 + 423: return launch_pers<4, 2, 3>(k, st);
-    case 10 + 4220: return launch_pers<4, 2, 2>(k, st);
-    case 10 + 4230: return launch_pers<4, 2, 3>(k, st);
-    case 10000 + 442: return launch_pers<4, 4, 2, 1>(k, st);
-    default: break;
-  }
-  if (id < 8) {
-    // K walk of the plain 128-pixel-tile kernels: tap-major, or (exact fp32, 3x3, whole 32-channel groups; env EFFDET_F32_KORD, A/B)
-    // channel-group-major like the split-layout convs -- same products, another summation order, fewer L2 -> fabric re-fetches
-    static const int f32_kord = getenv("EFFDET_F32_KORD") ? atoi(getenv("EFFDET_F32_KORD")) : 0;
-    k.kord = (id < 4 && f32_kord && p->dtype == EFFDET_F32 && p->KH * p->KW > 1 && k.cpt % 8 == 0 && p->Cin >= f32_kord) ? 1 : 0;
-  }
-  if (id >= 4 && id < 8) return dispatch<float, 1>(k, st);
-  if (id == 20) {
-    const int M = k.seg[0].M;
-    const int G = k.Cout / 4, NPS = 256 / G, ppw = 1024;               // 16 tiles of 64 pixels per workgroup
-    const unsigned grid = (unsigned)((M + ppw - 1) / ppw);
-    if (k.Cin == 16) hipLaunchKernelGGL(conv_pw_f32_kernel<16>, dim3(grid), dim3(256), 0, st, k, M, G, NPS, ppw);
-    else hipLaunchKernelGGL(conv_pw_f32_kernel<24>, dim3(grid), dim3(256), 0, st, k, M, G, NPS, ppw);
-    EFFDET_CHECK_LAUNCH();
-    return EFFDET_OK;
-  }
-  if (id == 30 || id == 31) {
-    k.ntiles = (k.Cout + (id == 30 ? 127 : 63)) / (id == 30 ? 128 : 64);
-    return id == 30 ? launch<float, 128, 2, 8, 3>(k, st) : launch<float, 64, 1, 4, 3>(k, st);
-  }
-  if (id == 8 || id == 9) {
-    k.ntiles = (k.Cout + (id == 8 ? 127 : 63)) / (id == 8 ? 128 : 64);
-    static const int m32 = getenv("EFFDET_SPLIT_M32") ? atoi(getenv("EFFDET_SPLIT_M32")) : 0;      // A/B switch: 32x32x16 tiles (measured 342-360 TFLOP/s) vs 16x16x32 (370-390)
-    if (m32) return id == 8 ? launch<float, 128, 2, 8, 2, 2, 1>(k, st) : launch<float, 64, 1, 4, 2, 2, 1>(k, st);
-    return id == 8 ? launch<float, 128, 2, 8, 2>(k, st) : launch<float, 64, 1, 4, 2>(k, st);
-  }
-  return p->dtype == EFFDET_BF16 ? dispatch<bf16_t>(k, st) : dispatch<float>(k, st);
+  ConvPlan c;
+  const int id = plan_conv(p, c);
+  return id < 0 ? id : c.launch(c, (hipStream_t)stream);
 }

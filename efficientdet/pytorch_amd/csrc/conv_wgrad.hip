@@ -1184,75 +1184,6 @@ int plan(const effdet_wgrad_t* p, WgradK& k, int& splits, int tile = 128) {
 }
 }  // namespace
 
-// EFFDET_F32_BF16X3 (fp32 storage, split-bf16 products): same storage geometry as EFFDET_F32.
-// EFFDET_F32_SPLIT (both operands in the split layout): planned and staged as the bf16 tensor of twice the channel count it is
-// byte for byte (the VIEW: channel counts, pitches, offsets x 2; the dz width is its whole padded pitch); q##_alg keeps the
-// algorithmic Cout / Cin for the slab layout and the epilogue.
-#define WGRAD_NORMALISE_DTYPE(p, q) effdet_wgrad_t q; bool q##_x3 = false, q##_split = false; int q##_cout = 0, q##_cin = 0; \
-  if (p) { q = *p; q##_cout = q.Cout; q##_cin = q.Cin; \
-    if (q.dtype == EFFDET_F32_BF16X3) { q.dtype = EFFDET_F32; q##_x3 = true; } \
-    else if (q.dtype == EFFDET_F32_SPLIT) { \
-      q##_split = true; q.dtype = EFFDET_BF16; \
-      if (q.Cin % 32 || q.ldx % 32 || q.lddz % 32 || q.Cout > q.lddz || q.nseg < 1 || q.nseg > EFFDET_MAX_SEG) q.nseg = 0;   /* -> EFFDET_EINVAL in plan() */ \
-      q.Cin *= 2; q.ldx *= 2; q.Cout = 2 * q.lddz; q.lddz *= 2; \
-      for (int s_ = 0; s_ < q.nseg; ++s_) { q.seg[s_].in_off *= 2; q.seg[s_].in_bstride *= 2; q.seg[s_].out_off *= 2; q.seg[s_].out_bstride *= 2; } \
-    } \
-    p = &q; } (void)q##_x3; (void)q##_split; (void)q##_cout; (void)q##_cin
-
-namespace { bool tr_eligible(const effdet_wgrad_t* p, const WgradK& k, int s); }
-// every pyramid level of a split-layout launch must qualify for the DMA + transpose-read kernel (there is no other split kernel)
-static bool split_all_eligible(const effdet_wgrad_t* pv, const WgradK& k) {
-  for (int s = 0; s < pv->nseg; ++s) if (!tr_eligible(pv, k, s)) return false;
-  return true;
-}
-
-// (Cout / 16, Cin / 16) tile shapes conv_wgrad_thin_kernel is built for: EfficientNet-B0..B2's high-resolution 1x1 convs
-static int thin_combo(int nta, int ntb) {
-  static const int combos[][2] = {{1, 2}, {6, 1}, {2, 6}, {9, 2}, {2, 9}, {3, 9}, {1, 1}, {2, 1}, {1, 3}, {2, 2}};
-  for (int i = 0; i < (int)(sizeof(combos) / sizeof(combos[0])); ++i) if (combos[i][0] == nta && combos[i][1] == ntb) return i;
-  return -1;
-}
-// Does the (normalised) descriptor go to conv_wgrad_thin_kernel?  1 = one contiguous pointwise level, few channels, many pixels;
-// 2 = the stem's geometry (3x3 stride 2 on a 4-channel NHWC image, <= 32 output channels, pad 0 / 1); 0 = no.
-static int thin_eligible(const effdet_wgrad_t* p, bool splitfmt) {
-  static const int on = getenv("EFFDET_WGRAD_THIN") ? atoi(getenv("EFFDET_WGRAD_THIN")) : 1;      // A/B switch (2: pointwise form only)
-  if (!on || splitfmt || !p || p->dtype != EFFDET_F32 || p->nseg != 1) return 0;
-  const effdet_seg_t& g = p->seg[0];
-  if (p->lddz != p->Cout || (p->Cout & 3) || (g.out_off & 3) || g.out_bstride != (long long)g.Ho * g.Wo * p->lddz) return 0;
-  if ((long long)p->B * g.Ho * g.Wo < 32768) return 0;
-  if (p->KH == 3 && p->KW == 3 && p->stride == 2) {
-    if (on == 2 || p->Cin != 4 || p->ldx != 4 || p->Cout <= 16 || p->Cout > 32 || (g.in_off & 3) || g.in_bstride != (long long)g.H * g.W * 4) return 0;
-    if (p->pad_t < 0 || p->pad_t > 1 || p->pad_l < 0 || p->pad_l > 1) return 0;
-    if (2 * (g.Ho - 1) - p->pad_t >= g.H || 2 * (g.Wo - 1) - p->pad_l >= g.W) return 0;       // every output pixel has its centre tap row/column start inside
-    return 2;
-  }
-  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad_t || p->pad_l) return 0;
-  if (g.Ho != g.H || g.Wo != g.W || p->ldx != p->Cin || (p->Cin & 3)) return 0;
-  if (g.in_bstride != (long long)g.H * g.W * p->ldx) return 0;
-  if ((g.in_off & 3) || p->Cin + p->Cout > 192) return 0;
-  return thin_combo((p->Cout + 15) / 16, (p->Cin + 15) / 16) < 0 ? 0 : 1;
-}
-#define WGRAD_TILE(p, q) (q##_split ? 256 : (thin_eligible(p, q##_split) ? 256 : 128))
-
-extern "C" long long effdet_conv2d_wgrad_workspace_bytes(const effdet_wgrad_t* p) {
-  WGRAD_NORMALISE_DTYPE(p, pn);
-  WgradK k; int splits = 0;
-  if (plan(p, k, splits, WGRAD_TILE(p, pn)) != EFFDET_OK) return -1;
-  if (pn_split) {
-    if (!split_all_eligible(p, k)) return -1;
-    return (long long)splits * pn_cout * ((long long)(k.K / 2) + 1) * (long long)sizeof(float);
-  }
-  return (long long)splits * p->Cout * (k.K + 1) * (long long)sizeof(float);      // slabs + the [splits][Cout] bias partials
-}
-
-extern "C" int effdet_conv2d_wgrad_splits(const effdet_wgrad_t* p) {
-  WGRAD_NORMALISE_DTYPE(p, pn);
-  WgradK k; int splits = 0;
-  if (plan(p, k, splits, WGRAD_TILE(p, pn)) != EFFDET_OK) return -1;
-  if (pn_split && !split_all_eligible(p, k)) return -1;
-  return splits;
-}
-
 namespace {
 // Does pyramid level s qualify for the DMA + transpose-read kernel?  (see the eligibility note at that kernel)
 bool tr_eligible(const effdet_wgrad_t* p, const WgradK& k, int s) {
@@ -1295,217 +1226,235 @@ constexpr int F32_NW = EFFDET_WGRAD_F32_WAVES;
 #define EFFDET_WGRAD_X3_WAVES 4
 #endif
 constexpr int X3_NW = EFFDET_WGRAD_X3_WAVES;
-}  // namespace
 
-// Slab range [first, first + count) of every pyramid level, in the order effdet_conv2d_wgrad lays the slabs out: the levels the
-// DMA-staged kernels take first, then the register-transpose kernel's (each launch numbers its own splits from 0 and owns a
-// contiguous range; the split-layout kernel takes every level in order).  -> number of slabs of the fast launch.
-static int seg_slab_ranges(const effdet_wgrad_t* p, const WgradK& k, bool x3, bool splitfmt, int* first, int* count, bool* fast) {
-  static const int f32dma = getenv("EFFDET_WGRAD_F32DMA") ? atoi(getenv("EFFDET_WGRAD_F32DMA")) : 1;      // A/B switch
-  int sf = 0, ss = 0;
-  for (int s = 0; s < p->nseg; ++s) {
-    count[s] = (int)((k.seg[s].M + k.mchunk - 1) / k.mchunk);
-    fast[s] = splitfmt || tr_eligible(p, k, s) || (f32dma && f32dma_eligible(p, k, s, x3));
-    if (fast[s]) { first[s] = sf; sf += count[s]; }
+// What effdet_conv2d_wgrad launches for one descriptor, decided by plan_wgrad without a HIP runtime call
+enum { WG_TILED = 0, WG_THIN = 1, WG_SPLIT = 2, WG_STEM = 3 };      // (effdet_conv2d_wgrad_kernel reports the stem's form as 1)
+struct WgradPlan;
+typedef void (*ThinLaunch)(const WgradPlan&, const WgradK&, hipStream_t);
+struct WgradPlan {
+  // the normalised descriptor: EFFDET_F32_BF16X3 as EFFDET_F32 (x3 set); EFFDET_F32_SPLIT (split set) as the bf16 tensor of twice the
+  // channel count it is byte for byte (the VIEW: channel counts, pitches, offsets x 2; the dz width is its whole padded pitch)
+  effdet_wgrad_t d;
+  bool x3, split;
+  int cout;                    // the algorithmic Cout (slab layout, bias rows, epilogue)
+  int path;                    // WG_*
+  WgradK k;                    // kernel arguments but the workspace pointers; WG_TILED: the fast (DMA-staged) launch's ...
+  WgradK ks;                   // ... and the register-transpose launch's
+  int splits, nfast;           // slabs in all / of the fast launch
+  int first[EFFDET_MAX_SEG], count[EFFDET_MAX_SEG];                  // slab range of every level (effdet_conv2d_wgrad_seg_slabs)
+  int P, NS, pps;              // thin kernel: pixels per stage, ring slots, DMA instructions per wave and stage
+  ThinLaunch thin;             // thin kernel: the instance for the (Cout / 16, Cin / 16) tile shape
+  size_t lds;                  // dynamic LDS bytes of the main launch
+  int allr;                    // split kernel: all fragment reads of a K-step issued ahead of its MFMAs
+  long long slab_floats;       // floats per slab (cout x algorithmic K)
+  long long workspace_bytes;   // slabs + the [splits][cout] bias partial rows
+};
+
+template <int NTA, int NTB, bool STEM = false>
+void launch_thin(const WgradPlan& w, const WgradK& k, hipStream_t st) {
+  EFFDET_SET_MAX_LDS((conv_wgrad_thin_kernel<NTA, NTB, STEM>), w.lds);
+  hipLaunchKernelGGL((conv_wgrad_thin_kernel<NTA, NTB, STEM>), dim3((unsigned)w.splits), dim3(256), w.lds, st, k, w.P, w.pps, w.NS);
+}
+// (Cout / 16, Cin / 16) tile shapes conv_wgrad_thin_kernel is built for: EfficientNet-B0..B2's high-resolution 1x1 convs
+const struct { int nta, ntb; ThinLaunch launch; } thin_shapes[] = {
+  {1, 2, launch_thin<1, 2>}, {6, 1, launch_thin<6, 1>}, {2, 6, launch_thin<2, 6>}, {9, 2, launch_thin<9, 2>}, {2, 9, launch_thin<2, 9>},
+  {3, 9, launch_thin<3, 9>}, {1, 1, launch_thin<1, 1>}, {2, 1, launch_thin<2, 1>}, {1, 3, launch_thin<1, 3>}, {2, 2, launch_thin<2, 2>}};
+ThinLaunch thin_launch(int nta, int ntb) {
+  for (const auto& t : thin_shapes) if (t.nta == nta && t.ntb == ntb) return t.launch;
+  return nullptr;
+}
+// Does the (normalised) descriptor go to conv_wgrad_thin_kernel?  1 = one contiguous pointwise level, few channels, many pixels;
+// 2 = the stem's geometry (3x3 stride 2 on a 4-channel NHWC image, <= 32 output channels, pad 0 / 1); 0 = no.
+int thin_eligible(const effdet_wgrad_t* p, bool splitfmt) {
+  static const int on = getenv("EFFDET_WGRAD_THIN") ? atoi(getenv("EFFDET_WGRAD_THIN")) : 1;      // A/B switch (2: pointwise form only)
+  if (!on || splitfmt || !p || p->dtype != EFFDET_F32 || p->nseg != 1) return 0;
+  const effdet_seg_t& g = p->seg[0];
+  if (p->lddz != p->Cout || (p->Cout & 3) || (g.out_off & 3) || g.out_bstride != (long long)g.Ho * g.Wo * p->lddz) return 0;
+  if ((long long)p->B * g.Ho * g.Wo < 32768) return 0;
+  if (p->KH == 3 && p->KW == 3 && p->stride == 2) {
+    if (on == 2 || p->Cin != 4 || p->ldx != 4 || p->Cout <= 16 || p->Cout > 32 || (g.in_off & 3) || g.in_bstride != (long long)g.H * g.W * 4) return 0;
+    if (p->pad_t < 0 || p->pad_t > 1 || p->pad_l < 0 || p->pad_l > 1) return 0;
+    if (2 * (g.Ho - 1) - p->pad_t >= g.H || 2 * (g.Wo - 1) - p->pad_l >= g.W) return 0;       // every output pixel has its centre tap row/column start inside
+    return 2;
   }
-  for (int s = 0; s < p->nseg; ++s) if (!fast[s]) { first[s] = sf + ss; ss += count[s]; }
-  return sf;
+  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad_t || p->pad_l) return 0;
+  if (g.Ho != g.H || g.Wo != g.W || p->ldx != p->Cin || (p->Cin & 3)) return 0;
+  if (g.in_bstride != (long long)g.H * g.W * p->ldx) return 0;
+  if ((g.in_off & 3) || p->Cin + p->Cout > 192) return 0;
+  return thin_launch((p->Cout + 15) / 16, (p->Cin + 15) / 16) ? 1 : 0;
 }
 
-extern "C" int effdet_conv2d_wgrad_kernel(const effdet_wgrad_t* p) {
+// Validates the descriptor and fills the plan: -> EFFDET_OK or EFFDET_E* (< 0).
+int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w) {
   if (!p) return EFFDET_EINVAL;
-  WGRAD_NORMALISE_DTYPE(p, pn);
-  if (pn_split) return 2;
-  return thin_eligible(p, false) ? 1 : 0;      // (the stem's form of the thin kernel reports 1 too)
-}
-
-extern "C" int effdet_conv2d_wgrad_seg_slabs(const effdet_wgrad_t* p, int* first, int* count) {
-  if (!p || !first || !count) return EFFDET_EINVAL;
-  WGRAD_NORMALISE_DTYPE(p, pn);
-  WgradK k; int splits = 0;
-  const int rc = plan(p, k, splits, WGRAD_TILE(p, pn));
+  effdet_wgrad_t& q = w.d;
+  q = *p; w.cout = q.Cout; w.x3 = w.split = false;
+  if (q.dtype == EFFDET_F32_BF16X3) { q.dtype = EFFDET_F32; w.x3 = true; }
+  else if (q.dtype == EFFDET_F32_SPLIT) {
+    w.split = true; q.dtype = EFFDET_BF16;
+    if (q.Cin % 32 || q.ldx % 32 || q.lddz % 32 || q.Cout > q.lddz || q.nseg < 1 || q.nseg > EFFDET_MAX_SEG) return EFFDET_EINVAL;
+    q.Cin *= 2; q.ldx *= 2; q.Cout = 2 * q.lddz; q.lddz *= 2;
+    for (int s = 0; s < q.nseg; ++s) { q.seg[s].in_off *= 2; q.seg[s].in_bstride *= 2; q.seg[s].out_off *= 2; q.seg[s].out_bstride *= 2; }
+  }
+  const int thin = thin_eligible(&q, w.split);
+  WgradK& k = w.k;
+  const int rc = plan(&q, k, w.splits, w.split || thin ? 256 : 128);      // (tile 256 of the bf16 VIEW for the split-layout kernel)
   if (rc != EFFDET_OK) return rc;
-  if (pn_split && !split_all_eligible(p, k)) return EFFDET_EUNSUPPORTED;
+  // slab ranges, in the order of the launches: the levels the DMA-staged kernels take first, then the register-transpose kernel's
+  // (each launch numbers its own splits from 0 and owns a contiguous range; the split-layout kernel takes every level in order)
+  static const int f32dma = getenv("EFFDET_WGRAD_F32DMA") ? atoi(getenv("EFFDET_WGRAD_F32DMA")) : 1;      // A/B switch
   bool fast[EFFDET_MAX_SEG];
-  (void)seg_slab_ranges(p, k, pn_x3, pn_split, first, count, fast);
-  return splits;
-}
-
-extern "C" int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes,
-                                   effdet_stream_t stream) {
-  if (!p || !p->x || !p->dz || !workspace) return EFFDET_EINVAL;
-  WGRAD_NORMALISE_DTYPE(p, pn);
-  WgradK k; int splits = 0;
-  const int rc = plan(p, k, splits, WGRAD_TILE(p, pn));
-  if (rc != EFFDET_OK) return rc;
-  if (pn_split) {
-    // split-layout operands: one launch of the transpose-read kernel in its three-product form (k = the bf16 VIEW for staging;
-    // Cout / K back to algorithmic for the [Cout][K] fp32 slabs, the bias partial rows and the epilogue)
-    if (!split_all_eligible(p, k)) return EFFDET_EUNSUPPORTED;
-    const long long Kalg = k.K / 2, nalg = (long long)pn_cout * Kalg;
-    if (workspace_bytes < (long long)splits * (nalg + pn_cout) * (long long)sizeof(float)) return EFFDET_EINVAL;
-    k.slab = (float*)workspace;
-    k.dbp = p->dbias ? (float*)workspace + (long long)splits * nalg : nullptr;
-    k.Cout = pn_cout; k.K = (int)Kalg;
-    for (int s = 0; s < p->nseg; ++s) {
-      WSeg& d = k.seg[s];
-      if (p->KH == 1 && p->KW == 1 && d.in_bs == (long long)d.H * d.W * p->ldx && d.out_bs == (long long)d.Ho * d.Wo * p->lddz) {
-        d.H = d.Ho = 1; d.W = d.Wo = d.M;
-      }
-    }
-    const size_t lds4 = (size_t)4 * 128 * 8 * sizeof(uint4);      // 2 stages x (dz 16 KiB + x 16 KiB)
-    hipStream_t st4 = (hipStream_t)stream;
+  int sf = 0, ss = 0;
+  for (int s = 0; s < q.nseg; ++s) {
+    w.count[s] = (int)((k.seg[s].M + k.mchunk - 1) / k.mchunk);
+    fast[s] = tr_eligible(&q, k, s) || (f32dma && f32dma_eligible(&q, k, s, w.x3));
+    if (fast[s]) { w.first[s] = sf; sf += w.count[s]; }
+    else if (w.split) return EFFDET_EUNSUPPORTED;     // every level of a split-layout launch must qualify (there is no other split kernel)
+  }
+  for (int s = 0; s < q.nseg; ++s) if (!fast[s]) { w.first[s] = sf + ss; ss += w.count[s]; }
+  w.nfast = sf;
+  auto flatten = [&](WSeg& d) {      // contiguous pointwise level: one long image row, no wrap, no borders
+    if (q.KH == 1 && q.KW == 1 && d.in_bs == (long long)d.H * d.W * q.ldx && d.out_bs == (long long)d.Ho * d.Wo * q.lddz) { d.H = d.Ho = 1; d.W = d.Wo = d.M; }
+  };
+  if (w.split) {
+    // one launch of the transpose-read kernel in its three-product form (k = the bf16 VIEW for staging; Cout / K back to algorithmic
+    // for the [Cout][K] fp32 slabs, the bias partial rows and the epilogue)
+    w.path = WG_SPLIT;
+    k.Cout = w.cout; k.K /= 2;
+    for (int s = 0; s < q.nseg; ++s) flatten(k.seg[s]);
     // all fragment reads of a K-step ahead of its MFMAs (122 VGPRs instead of 106, still 4 waves / SIMD): +2.5 .. 3.5 % on the
     // 256-channel head shapes (342 -> 355, 353 -> 362 TFLOP/s standalone), -2.5 % on 64 -> 256 -- so by input width (A/B: env 0 / 1)
     static const int allr_env = getenv("EFFDET_WGRAD_SPLIT_ALLR") ? atoi(getenv("EFFDET_WGRAD_SPLIT_ALLR")) : -1;
-    const int allr = allr_env >= 0 ? allr_env : (p->Cin >= 128 ? 1 : 0);
-    EFFDET_SET_MAX_LDS(conv_wgrad_split_kernel<0>, lds4);
-    EFFDET_SET_MAX_LDS(conv_wgrad_split_kernel<1>, lds4);
-    if (allr) hipLaunchKernelGGL(conv_wgrad_split_kernel<1>, dim3((unsigned)(k.ntiles * k.jtiles * splits)), dim3(512), lds4, st4, k);
-    else hipLaunchKernelGGL(conv_wgrad_split_kernel<0>, dim3((unsigned)(k.ntiles * k.jtiles * splits)), dim3(512), lds4, st4, k);
-    EFFDET_CHECK_LAUNCH();
-    if (p->dw) {
-      long long g = (nalg / 4 + 255) / 256; if (g < 1) g = 1; if (g > 4096) g = 4096;
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st4, (const float*)workspace, p->dw, nalg, splits);
-      EFFDET_CHECK_LAUNCH();
-      if (p->dbias) {
-        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((pn_cout + 255) / 256)), dim3(256), 0, st4, (const float*)k.dbp, p->dbias,
-                           pn_cout, splits);
-        EFFDET_CHECK_LAUNCH();
-      }
-    }
-    return EFFDET_OK;
-  }
-  const long long n = (long long)p->Cout * k.K;
-  if (workspace_bytes < (long long)splits * (n + p->Cout) * (long long)sizeof(float)) return EFFDET_EINVAL;
-  k.slab = (float*)workspace;
-  k.dbp = p->dbias ? (float*)workspace + (long long)splits * n : nullptr;
-  const size_t lds = (size_t)4 * 128 * 8 * sizeof(uint4);
-  hipStream_t st = (hipStream_t)stream;
-  const int thin = thin_eligible(p, false);
-  if (thin == 2) {
+    w.allr = allr_env >= 0 ? allr_env : (q.Cin >= 128 ? 1 : 0);
+    w.lds = (size_t)4 * 128 * 8 * sizeof(uint4);                       // 2 stages x (dz 16 KiB + x 16 KiB)
+  } else if (thin == 2) {
     // the stem: 64 output pixels per stage = 9 KiB of gathered taps + 8 KiB of dz rows, 3 slots (two workgroups per CU)
-    const int P = 64, np = P * (36 + p->Cout) * 4 / 1024, pps = (np + 3) / 4, NS = 3;
-    const size_t ldt = (size_t)NS * ((size_t)P * (36 + p->Cout) * 4 + 1024);
-    if ((P * p->Cout * 4) & 1023) return EFFDET_EUNSUPPORTED;
-    EFFDET_SET_MAX_LDS((conv_wgrad_thin_kernel<2, 3, true>), ldt);
-    hipLaunchKernelGGL((conv_wgrad_thin_kernel<2, 3, true>), dim3((unsigned)splits), dim3(256), ldt, st, k, P, pps, NS);
-    EFFDET_CHECK_LAUNCH();
-    if (p->dw) {
-      long long g = (n / 4 + 255) / 256; if (g < 1) g = 1; if (g > 4096) g = 4096;
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, (const float*)workspace, p->dw, n, splits);
-      EFFDET_CHECK_LAUNCH();
-      if (p->dbias) {
-        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((p->Cout + 255) / 256)), dim3(256), 0, st, (const float*)k.dbp, p->dbias,
-                           p->Cout, splits);
-        EFFDET_CHECK_LAUNCH();
-      }
-    }
-    return EFFDET_OK;
-  }
-  if (thin == 1) {
+    w.path = WG_STEM; w.P = 64; w.NS = 3; w.pps = (w.P * (36 + q.Cout) * 4 / 1024 + 3) / 4;
+    w.lds = (size_t)w.NS * ((size_t)w.P * (36 + q.Cout) * 4 + 1024);
+    if ((w.P * q.Cout * 4) & 1023) return EFFDET_EUNSUPPORTED;
+    w.thin = launch_thin<2, 3, true>;
+  } else if (thin == 1) {
     // Stage size P (pixels) and ring depth NS, measured per channel budget (tools/wgrad_thin_bench.py, B = 32): the kernel is bound by
     // its LDS-read + fp32-MFMA loop (knock-outs: DMA alone streams at 5.2-6.1 TB/s, the loop alone at 3.6-4.8), so what pays is TWO
     // workgroups per CU taking turns -- slots small enough for that -- not a deeper ring in one workgroup:
     //   <= 64 channels  P 128 x 3 slots   32 -> 16: 79 us (tiled kernel 264)
     //   <= 128          P 64 x 2          16 -> 96: 229 (292), 96 -> 24: 69 (81)
     //   wider           P 32 x 3          24 -> 144: 99 (138), 144 -> 24: 78 (134), 144 -> 40: 35 (41)
-    const int ch = p->Cin + p->Cout;
-    int P = ch <= 64 ? 128 : (ch <= 128 || (p->Cin & 7) || (p->Cout & 7)) ? 64 : 32;
-    int NS = (ch > 64 && ch <= 128) ? 2 : 3;
-    if (getenv("EFFDET_THIN_P")) P = atoi(getenv("EFFDET_THIN_P"));                         // tuning overrides (P % 64 == 0, or 32 with channels % 8 == 0)
-    if (getenv("EFFDET_THIN_NS")) NS = atoi(getenv("EFFDET_THIN_NS"));
-    if (P < 32 || (P & 31) || ((P * p->Cin) & 255) || ((P * p->Cout) & 255) || NS < 2 || NS > 6) return EFFDET_EINVAL;
-    const int np = P * ch * 4 / 1024, pps = (np + 3) / 4;                                   // 1-KiB DMA pieces per stage / per wave
-    const int nta = (p->Cout + 15) / 16, ntb = (p->Cin + 15) / 16;
-    const size_t slot = (size_t)P * ch * 4 + 1024;
-    while (NS > 2 && (NS - 2) * pps > 48) --NS;                                              // (the vmcnt immediates the kernel has)
-    size_t ldt = (size_t)NS * slot;
-    if (ldt < 32 * 1024) ldt = 32 * 1024;                                                   // the final cross-wave reduction (8 tiles x 4 waves)
-#define THIN_LAUNCH(A, B) do { EFFDET_SET_MAX_LDS((conv_wgrad_thin_kernel<A, B>), ldt); \
-      hipLaunchKernelGGL((conv_wgrad_thin_kernel<A, B>), dim3((unsigned)splits), dim3(256), ldt, st, k, P, pps, NS); } while (0)
-    switch (thin_combo(nta, ntb)) {
-      case 0: THIN_LAUNCH(1, 2); break;
-      case 1: THIN_LAUNCH(6, 1); break;
-      case 2: THIN_LAUNCH(2, 6); break;
-      case 3: THIN_LAUNCH(9, 2); break;
-      case 4: THIN_LAUNCH(2, 9); break;
-      case 5: THIN_LAUNCH(3, 9); break;
-      case 6: THIN_LAUNCH(1, 1); break;
-      case 7: THIN_LAUNCH(2, 1); break;
-      case 8: THIN_LAUNCH(1, 3); break;
-      default: THIN_LAUNCH(2, 2); break;
+    w.path = WG_THIN;
+    const int ch = q.Cin + q.Cout;
+    w.P = ch <= 64 ? 128 : (ch <= 128 || (q.Cin & 7) || (q.Cout & 7)) ? 64 : 32;
+    w.NS = (ch > 64 && ch <= 128) ? 2 : 3;
+    if (getenv("EFFDET_THIN_P")) w.P = atoi(getenv("EFFDET_THIN_P"));                       // tuning overrides (P % 64 == 0, or 32 with channels % 8 == 0)
+    if (getenv("EFFDET_THIN_NS")) w.NS = atoi(getenv("EFFDET_THIN_NS"));
+    if (w.P < 32 || (w.P & 31) || ((w.P * q.Cin) & 255) || ((w.P * q.Cout) & 255) || w.NS < 2 || w.NS > 6) return EFFDET_EINVAL;
+    w.pps = (w.P * ch * 4 / 1024 + 3) / 4;                                                   // 1-KiB DMA pieces per stage / per wave
+    while (w.NS > 2 && (w.NS - 2) * w.pps > 48) --w.NS;                                       // (the vmcnt immediates the kernel has)
+    w.lds = (size_t)w.NS * ((size_t)w.P * ch * 4 + 1024);
+    if (w.lds < 32 * 1024) w.lds = 32 * 1024;                                                 // the final cross-wave reduction (8 tiles x 4 waves)
+    w.thin = thin_launch((q.Cout + 15) / 16, (q.Cin + 15) / 16);
+  } else {
+    // the levels split between the DMA-staged kernel (fast) and the register-transpose kernel
+    w.path = WG_TILED;
+    w.ks = k;
+    int nf = 0, ns = 0;
+    for (int s = 0; s < q.nseg; ++s) {
+      WSeg d = w.ks.seg[s];
+      if (fast[s]) { d.split_start = w.first[s]; flatten(d); k.seg[nf++] = d; }
+      else { d.split_start = w.first[s] - sf; w.ks.seg[ns++] = d; }
     }
-#undef THIN_LAUNCH
-    EFFDET_CHECK_LAUNCH();
-    if (p->dw) {
-      long long g = (n / 4 + 255) / 256; if (g < 1) g = 1; if (g > 4096) g = 4096;
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, (const float*)workspace, p->dw, n, splits);
-      EFFDET_CHECK_LAUNCH();
-      if (p->dbias) {
-        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((p->Cout + 255) / 256)), dim3(256), 0, st, (const float*)k.dbp, p->dbias,
-                           p->Cout, splits);
-        EFFDET_CHECK_LAUNCH();
-      }
-    }
-    return EFFDET_OK;
+    for (int s = nf; s < EFFDET_MAX_SEG; ++s) { k.seg[s] = k.seg[0]; k.seg[s].split_start = 0x7fffffff; }
+    for (int s = ns; s < EFFDET_MAX_SEG; ++s) { w.ks.seg[s] = w.ks.seg[0]; w.ks.seg[s].split_start = 0x7fffffff; }
+    k.nseg = nf; w.ks.nseg = ns;
+    w.lds = (size_t)4 * 128 * 8 * sizeof(uint4);
   }
-  // Partition the pyramid levels between the two kernels; each launch numbers its own splits from 0 and owns a
-  // contiguous range of slabs (the slab order is irrelevant to the reduction).
-  WgradK kf = k, ks = k;            // fast (DMA staging: bf16 LDS-transpose-read / fp32 direct-operand) / slow (register transpose)
-  int first[EFFDET_MAX_SEG], count[EFFDET_MAX_SEG]; bool fast[EFFDET_MAX_SEG];
-  const int sf = seg_slab_ranges(p, k, pn_x3, false, first, count, fast);
-  int nf = 0, ns = 0, ss = 0;
-  for (int s = 0; s < p->nseg; ++s) {
-    if (fast[s]) {
-      WSeg d = k.seg[s]; d.split_start = first[s];
-      if (p->KH == 1 && p->KW == 1 && d.in_bs == (long long)d.H * d.W * p->ldx && d.out_bs == (long long)d.Ho * d.Wo * p->lddz) {
-        d.H = d.Ho = 1; d.W = d.Wo = d.M;           // contiguous pointwise: one long image row, no wrap, no borders
-      }
-      kf.seg[nf++] = d;
-    } else {
-      WSeg d = k.seg[s]; d.split_start = first[s] - sf; ss += count[s];
-      ks.seg[ns++] = d;
-    }
-  }
-  for (int s = nf; s < EFFDET_MAX_SEG; ++s) { kf.seg[s] = kf.seg[0]; kf.seg[s].split_start = 0x7fffffff; }
-  for (int s = ns; s < EFFDET_MAX_SEG; ++s) { ks.seg[s] = ks.seg[0]; ks.seg[s].split_start = 0x7fffffff; }
-  kf.nseg = nf; ks.nseg = ns;
-  ks.slab = k.slab + (long long)sf * n;
-  if (k.dbp) ks.dbp = k.dbp + (long long)sf * p->Cout;
-  if (nf > 0 && p->dtype == EFFDET_F32 && pn_x3) {
-    EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<X3_NW, 1>), lds);
-    hipLaunchKernelGGL((conv_wgrad_f32dma_kernel<X3_NW, 1>), dim3((unsigned)(k.ntiles * k.jtiles * sf)), dim3(X3_NW * 64), lds, st, kf);
+  w.slab_floats = (long long)w.cout * k.K;
+  w.workspace_bytes = (long long)w.splits * (w.slab_floats + w.cout) * (long long)sizeof(float);
+  return EFFDET_OK;
+}
+
+// dw += the slabs and dbias += the bias partial rows, in slab order (with dw == NULL the caller reduces them while unpacking)
+int reduce_slabs(const effdet_wgrad_t* p, const WgradPlan& w, const float* slab, const float* dbp, hipStream_t st) {
+  if (!p->dw) return EFFDET_OK;
+  const long long n = w.slab_floats;
+  long long g = (n / 4 + 255) / 256; if (g < 1) g = 1; if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, slab, p->dw, n, w.splits);
+  EFFDET_CHECK_LAUNCH();
+  if (p->dbias) {
+    hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((w.cout + 255) / 256)), dim3(256), 0, st, dbp, p->dbias, w.cout, w.splits);
     EFFDET_CHECK_LAUNCH();
-  } else if (nf > 0 && p->dtype == EFFDET_F32) {
-    EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<F32_NW>), lds);
-    hipLaunchKernelGGL(conv_wgrad_f32dma_kernel<F32_NW>, dim3((unsigned)(k.ntiles * k.jtiles * sf)), dim3(F32_NW * 64), lds, st, kf);
-    EFFDET_CHECK_LAUNCH();
-  } else if (nf > 0) {
-    EFFDET_SET_MAX_LDS((conv_wgrad_tr_kernel<TR_NW>), lds);
-    hipLaunchKernelGGL(conv_wgrad_tr_kernel<TR_NW>, dim3((unsigned)(k.ntiles * k.jtiles * sf)), dim3(TR_NW * 64), lds, st, kf);
-    EFFDET_CHECK_LAUNCH();
-  }
-  if (ns > 0) {
-    dim3 grid((unsigned)(k.ntiles * k.jtiles * ss));
-    if (p->dtype == EFFDET_F32) {
-      EFFDET_SET_MAX_LDS((conv_wgrad_kernel<float>), lds);
-      hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), lds, st, ks);
-    } else {
-      EFFDET_SET_MAX_LDS((conv_wgrad_kernel<bf16_t>), lds);
-      hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(256), lds, st, ks);
-    }
-    EFFDET_CHECK_LAUNCH();
-  }
-  if (p->dw) {   // optional packed accumulate; with dw == NULL the caller reduces the slabs in effdet_unpack_conv_wgrad
-    long long g = (n / 4 + 255) / 256; if (g < 1) g = 1; if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, (const float*)workspace, p->dw, n, splits);
-    EFFDET_CHECK_LAUNCH();
-    if (p->dbias) {
-      hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((p->Cout + 255) / 256)), dim3(256), 0, st, (const float*)k.dbp, p->dbias,
-                         p->Cout, splits);
-      EFFDET_CHECK_LAUNCH();
-    }
   }
   return EFFDET_OK;
+}
+}  // namespace
+
+extern "C" long long effdet_conv2d_wgrad_workspace_bytes(const effdet_wgrad_t* p) {
+  WgradPlan w;
+  return plan_wgrad(p, w) == EFFDET_OK ? w.workspace_bytes : -1;
+}
+
+extern "C" int effdet_conv2d_wgrad_splits(const effdet_wgrad_t* p) {
+  WgradPlan w;
+  return plan_wgrad(p, w) == EFFDET_OK ? w.splits : -1;
+}
+
+extern "C" int effdet_conv2d_wgrad_kernel(const effdet_wgrad_t* p) {
+  WgradPlan w;
+  const int rc = plan_wgrad(p, w);
+  return rc != EFFDET_OK ? rc : w.path == WG_STEM ? WG_THIN : w.path;
+}
+
+extern "C" int effdet_conv2d_wgrad_seg_slabs(const effdet_wgrad_t* p, int* first, int* count) {
+  if (!p || !first || !count) return EFFDET_EINVAL;
+  WgradPlan w;
+  const int rc = plan_wgrad(p, w);
+  if (rc != EFFDET_OK) return rc;
+  for (int s = 0; s < p->nseg; ++s) { first[s] = w.first[s]; count[s] = w.count[s]; }
+  return w.splits;
+}
+
+extern "C" int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes,
+                                   effdet_stream_t stream) {
+  if (!p || !p->x || !p->dz || !workspace) return EFFDET_EINVAL;
+  WgradPlan w;
+  const int rc = plan_wgrad(p, w);
+  if (rc != EFFDET_OK) return rc;
+  if (workspace_bytes < w.workspace_bytes) return EFFDET_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  WgradK k = w.k;
+  k.slab = (float*)workspace;
+  k.dbp = p->dbias ? k.slab + (long long)w.splits * w.slab_floats : nullptr;
+  const unsigned tiles = (unsigned)(k.ntiles * k.jtiles);
+  if (w.path == WG_SPLIT && w.allr) {
+    EFFDET_SET_MAX_LDS(conv_wgrad_split_kernel<1>, w.lds);
+    hipLaunchKernelGGL(conv_wgrad_split_kernel<1>, dim3(tiles * w.splits), dim3(512), w.lds, st, k);
+  } else if (w.path == WG_SPLIT) {
+    EFFDET_SET_MAX_LDS(conv_wgrad_split_kernel<0>, w.lds);
+    hipLaunchKernelGGL(conv_wgrad_split_kernel<0>, dim3(tiles * w.splits), dim3(512), w.lds, st, k);
+  } else if (w.path != WG_TILED) {
+    w.thin(w, k, st);
+  } else {
+    WgradK ks = w.ks;
+    ks.slab = k.slab + (long long)w.nfast * w.slab_floats;
+    ks.dbp = k.dbp ? k.dbp + (long long)w.nfast * w.cout : nullptr;
+    if (w.nfast > 0 && w.d.dtype == EFFDET_F32 && w.x3) {
+      EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<X3_NW, 1>), w.lds);
+      hipLaunchKernelGGL((conv_wgrad_f32dma_kernel<X3_NW, 1>), dim3(tiles * w.nfast), dim3(X3_NW * 64), w.lds, st, k);
+    } else if (w.nfast > 0 && w.d.dtype == EFFDET_F32) {
+      EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<F32_NW>), w.lds);
+      hipLaunchKernelGGL(conv_wgrad_f32dma_kernel<F32_NW>, dim3(tiles * w.nfast), dim3(F32_NW * 64), w.lds, st, k);
+    } else if (w.nfast > 0) {
+      EFFDET_SET_MAX_LDS((conv_wgrad_tr_kernel<TR_NW>), w.lds);
+      hipLaunchKernelGGL(conv_wgrad_tr_kernel<TR_NW>, dim3(tiles * w.nfast), dim3(TR_NW * 64), w.lds, st, k);
+    }
+    EFFDET_CHECK_LAUNCH();
+    if (w.splits > w.nfast && w.d.dtype == EFFDET_F32) {
+      EFFDET_SET_MAX_LDS((conv_wgrad_kernel<float>), w.lds);
+      hipLaunchKernelGGL(conv_wgrad_kernel<float>, dim3(tiles * (w.splits - w.nfast)), dim3(256), w.lds, st, ks);
+    } else if (w.splits > w.nfast) {
+      EFFDET_SET_MAX_LDS((conv_wgrad_kernel<bf16_t>), w.lds);
+      hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, dim3(tiles * (w.splits - w.nfast)), dim3(256), w.lds, st, ks);
+    }
+  }
+  EFFDET_CHECK_LAUNCH();
+  return reduce_slabs(p, w, k.slab, k.dbp, st);
 }

@@ -120,9 +120,15 @@ int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream);
  * w: fp32 [Cout][Cin] (an OIHW 1x1 weight as is), gate: fp32 [B][Cin].  Image stride of `out` = Cout * Cin * (2 for bf16, else 4) bytes. */
 int effdet_scale_pack_weight(const float* w, const float* gate, void* out, int dtype, int B, int Cout, int Cin, effdet_stream_t stream);
 
-/* Which kernel effdet_conv2d would launch for this descriptor (no device work): a negative EFFDET_E* code, 0..3 = the
- * implicit-GEMM kernel with a 128 / 64 / 32 / 16-channel block tile, 4..7 = the same tiles in the bf16x3 form
- * (EFFDET_F32_BF16X3), >= 10 = 10 + the persistent big-tile variant. */
+/* Which kernel effdet_conv2d would launch for this descriptor (no device work): a negative EFFDET_E* code, or
+ *   0..3       the implicit-GEMM kernel with a 128 / 64 / 32 / 16-channel block tile (EFFDET_F32, EFFDET_BF16), 4..7 the same
+ *              tiles in the bf16x3 form (EFFDET_F32_BF16X3); a short grid with a long K loop may run them with deep staging,
+ *              128 / 64 on a 32-channel tile
+ *   8, 9       EFFDET_F32_SPLIT, 128 / 64-channel block tile          30, 31  EFFDET_F32_HSPLIT (f16x3), 128 / 64-channel block tile
+ *   20         the skinny pointwise fp32 kernel (1x1, Cin 16 or 24)
+ *   10 + v     the persistent big-tile bf16 variant v = 442 | 242 | 243 | 423, or 4220 / 4230 (the <= 128-channel forms of 442 and
+ *              242 / of 243)
+ *   10000 + 442  the persistent 256 x 256 form of EFFDET_F32_SPLIT */
 int effdet_conv2d_kernel(const effdet_conv_t* p);
 
 /* Kernel-selection knobs (speed only -- every setting computes the same values; process-wide, meant for A/B runs and
@@ -172,7 +178,8 @@ int effdet_conv2d_wgrad_splits(const effdet_wgrad_t* p);
 int effdet_conv2d_wgrad_seg_slabs(const effdet_wgrad_t* p, int* first, int* count);
 /* Which kernel serves the descriptor: 0 = the 128 x 128-tile kernels (DMA-staged / register-transpose, per level), 1 = the thin
  * pointwise kernel (one contiguous 1x1 level, Cin + Cout <= 192, >= 32768 pixels: exact fp32 MFMA on linearly staged pixel
- * rows -- also in the EFFDET_F32_BF16X3 mode), 2 = the split-layout kernel. */
+ * rows -- also in the EFFDET_F32_BF16X3 mode), 2 = the split-layout kernel; the planner's negative EFFDET_E* code for a
+ * descriptor effdet_conv2d_wgrad would refuse. */
 int effdet_conv2d_wgrad_kernel(const effdet_wgrad_t* p);
 int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes, effdet_stream_t stream);
 

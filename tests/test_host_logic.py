@@ -225,6 +225,7 @@ def test_weight_gradient_planning_entry_points():
     assert kid(_wgrad_desc(L.BF16, 32, 16, 96, [(256, 256)])) == 0        # bf16 storage
     assert kid(_wgrad_desc(L.F32, 32, 8, 32, [(512, 512)], k=3, stride=2)) == 0     # not the stem's 4-channel image
     assert kid(_wgrad_desc(L.F32_SPLIT, 32, 256, 256, [(64, 64), (32, 32)], k=3, pad=1)) == 2
+    assert kid(_wgrad_desc(L.F32_SPLIT, 32, 48, 256, [(64, 64)], k=3, pad=1)) == -1     # Cin % 32: the launch refuses it too
     # per-image splits on the thin kernel: B * q slabs, q | image pixels
     d = _wgrad_desc(L.F32_BF16X3, 32, 96, 24, [(128, 128)], image_splits=1)
     splits = int(lib.effdet_conv2d_wgrad_splits(C.byref(d)))
