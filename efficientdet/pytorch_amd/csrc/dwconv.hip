@@ -1032,34 +1032,37 @@ __global__ __launch_bounds__(256) void dw_wgrad_reduce_kernel(const float* __res
   }
 }
 
-bool extent(DwK& k, long long elems, int dtype) {
-  const long long bytes = elems * (dtype == EFFDET_F32 ? 4 : 2);
-  if (bytes >= 0xFFFF0000LL) return false;
-  k.x_bytes = (unsigned)bytes;
+// ---------------------------------------------------------------- host: one plan per launch
+// What an entry point launches, decided by its planner without a HIP runtime call.  The workspace and pool-group queries
+// read the same plan (or, for the pool groups, the same tile walk), so they cannot disagree with the launch.
+struct DwPlan {
+  DwFuseK f;                   // the final kernel arguments: f.d is the DwK of every kernel, the rest only the fused forward's
+  void (*launch)(const DwPlan&, hipStream_t);     // the one template instance that runs it
+  dim3 grid;
+  size_t lds;                  // dynamic LDS of this launch
+  size_t max_lds;              // attribute of the instance: set once per device, so the largest request, not this launch's
+  int groups;                  // tile groups over all images (the weight gradients: slab rows, one per group)
+  long long workspace_bytes;   // weight gradients: one [k*k + 1][C] fp32 row set per slab row
+};
+
+// Byte extent of a tensor the kernels address with 32-bit buffer offsets: refused from 4 GB up (EFFDET_EUNSUPPORTED)
+bool extent(unsigned& bytes, long long elems, int dtype) {
+  const long long b = elems * (dtype == EFFDET_F32 ? 4 : 2);
+  if (b >= 0xFFFF0000LL) return false;
+  bytes = (unsigned)b;
   return true;
 }
 
-int fill(DwK& k, int dtype, int B, int H, int W, int C, int kk, int stride, int pad_t, int pad_l, int Ho, int Wo,
-         int group, int npix, dim3& grid) {
+// The shape fields of DwK, checked in the same order for every entry point; ce channels per 16-byte chunk
+int shape(DwK& k, int dtype, int B, int H, int W, int C, int kk, int stride, int pad_t, int pad_l, int Ho, int Wo, int ce) {
   if (dtype != EFFDET_F32 && dtype != EFFDET_BF16) return EFFDET_EINVAL;
   if ((kk != 3 && kk != 5) || (stride != 1 && stride != 2)) return EFFDET_EUNSUPPORTED;
-  if (C % group) return EFFDET_EUNSUPPORTED;
+  if (C % ce) return EFFDET_EUNSUPPORTED;
   k.B = B; k.H = H; k.W = W; k.C = C; k.k = kk; k.stride = stride; k.pad_t = pad_t; k.pad_l = pad_l; k.Ho = Ho; k.Wo = Wo;
-  k.nch = C / group;
-  int tx = pow2_ge(k.nch); if (tx > 64) tx = 64;
-  k.tx = tx;
-  const int TY = 256 / tx;
-  // pixels per thread: enough work per block to amortise the reduction, but keep >= ~1024 blocks
-  int ppt = 8;
-  while (ppt > 1 && (long long)B * ((npix + TY * ppt - 1) / (TY * ppt)) * ((k.nch + tx - 1) / tx) < 1024) ppt >>= 1;
-  k.ppt = ppt;
-  grid = dim3(B * ((npix + TY * ppt - 1) / (TY * ppt)), (k.nch + tx - 1) / tx);
+  k.nch = C / ce;
   return EFFDET_OK;
 }
 
-}  // namespace
-
-namespace {
 // Slab width: 8 channel chunks (128-B pixel rows) unless that leaves >= 15 % of the lanes on channel padding, in which
 // case 4 chunks (C = 32: 4 of 8 chunk lanes live, C = 96: 12 of 16, C = 144: 18 of 24 -- the three largest maps of
 // EfficientNet-B0..B2).  Half-width slabs read 64-B pixel rows, so they are not the default.
@@ -1070,185 +1073,154 @@ inline int slab_chunks(int nch) {
   return (p8 - p4) * 100 >= 15 * p8 ? 4 : 8;
 }
 // 1-D grid of (tile groups x slabs) with the slab fastest (see slab_block); EFFDET_DW_ORDER=0 restores the 2-D grid for A/B
-inline dim3 slab_grid(DwK& a, int groups, int nslab) {
+inline void slab_grid(DwPlan& p, int groups, int nslab) {
   static const int legacy = getenv("EFFDET_DW_ORDER") ? atoi(getenv("EFFDET_DW_ORDER")) == 0 : 0;
-  if (legacy || nslab == 1) { a.nslab = 0; return dim3(groups, nslab); }
-  a.nslab = nslab;
-  return dim3((unsigned)groups * nslab);
+  const bool two_d = legacy || nslab == 1;
+  p.groups = groups;
+  p.f.d.nslab = two_d ? 0 : nslab;
+  p.grid = two_d ? dim3(groups, nslab) : dim3((unsigned)groups * nslab);
 }
-// tiles per workgroup of the pipelined forward / data-gradient kernels: >= ~2048 workgroups first, then up to 16 tiles each
-inline int tiles_per_wg(long long total_tiles) {
-  long long ppt = total_tiles / 2048;
+// tiles per workgroup: >= ~wgs workgroups first, then up to 16 tiles each
+inline int tiles_per_wg(long long total_tiles, int wgs) {
+  long long ppt = total_tiles / wgs;
   return ppt < 1 ? 1 : (ppt > 16 ? 16 : (int)ppt);
 }
-// tiles per workgroup / tile groups per image of the forward launch (shared by the launcher and effdet_dwconv_fwd_pool_groups)
-inline int fwd_tiles(int B, int nch, int stride, int Ho, int Wo, int& ppt) {
-  const int th = stride == 1 ? 16 : 8, tw = 8;               // DwTile<K, S>::TH / TW
-  const int cq = slab_chunks(nch), nslab = (nch + cq - 1) / cq;
-  const int tpi = ((Ho + th - 1) / th) * ((Wo + tw - 1) / tw);
-  ppt = tiles_per_wg((long long)tpi * B * nslab);
-  if (ppt > tpi) ppt = tpi;
-  return (tpi + ppt - 1) / ppt;
+// Tile walk of an LDS kernel (TL = DwTile / DgTile / BwTile) over an h x w map in slabs of cq chunks, with the tiles per
+// workgroup of the forward / data-gradient kernels (>= ~2048 workgroups); the weight gradients choose their own ppt.
+struct Walk {
+  int tpi, nslab, ppt;
+  int groups() const { return (tpi + ppt - 1) / ppt; }          // tile groups per image
+};
+template <typename TL>
+Walk walk(int B, int h, int w, int nch, int cq) {
+  Walk t{((h + TL::TH - 1) / TL::TH) * ((w + TL::TW - 1) / TL::TW), (nch + cq - 1) / cq, 0};
+  t.ppt = tiles_per_wg((long long)t.tpi * B * t.nslab, 2048);
+  if (t.ppt > t.tpi) t.ppt = t.tpi;
+  return t;
 }
-template <typename T, int K, int S, int CQ>
-int launch_fwd_lds(const DwK& a0, hipStream_t st) {
-  typedef DwTile<K, S> TL;
-  DwK a = a0;
-  const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, wb = (size_t)K * K * CQ * Elem<T>::CE * 4;
-  const int tpi = ((a.Ho + TL::TH - 1) / TL::TH) * ((a.Wo + TL::TW - 1) / TL::TW), nslab = (a.nch + CQ - 1) / CQ;
-  (void)fwd_tiles(a.B, a.nch, S, a.Ho, a.Wo, a.ppt);
+// tile groups per image of the plain and the fused forward: their tile does not depend on k, so the queries take none
+int fwd_groups(int B, int stride, int Ho, int Wo, int nch, int cq) {
+  return (stride == 1 ? walk<DwTile<3, 1>>(B, Ho, Wo, nch, cq) : walk<DwTile<3, 2>>(B, Ho, Wo, nch, cq)).groups();
+}
+
+// ---- kernel families: use<T, K, S, CQ> fills the instance-dependent fields of a plan and sets its launcher
+template <void (*KER)(DwK)>
+void launch_lds(const DwPlan& p, hipStream_t st) {
+  EFFDET_SET_MAX_LDS(KER, p.max_lds);
+  hipLaunchKernelGGL(KER, p.grid, dim3(256), p.lds, st, p.f.d);
+}
+// pipelined forward / data gradient: the next tile of a run is prefetched into a second buffer when two fit
+template <typename TL, int K, int CQ, int CE, void (*KER)(DwK)>
+void use_pipelined(DwPlan& p, int h, int w) {
+  DwK& a = p.f.d;
+  const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, wb = (size_t)K * K * CQ * CE * 4;
+  const Walk t = walk<TL>(a.B, h, w, a.nch, CQ);
+  a.ppt = t.ppt;
   static const int nb_env = getenv("EFFDET_DW_NBUF") ? atoi(getenv("EFFDET_DW_NBUF")) : 0;    // A/B switch
   a.nbuf = (a.ppt > 1 && 2 * tile + wb <= 80 * 1024 && nb_env != 1) ? 2 : 1;                  // keep >= 2 workgroups per CU
-  const size_t lds = a.nbuf * tile + wb;
-  dim3 grid = slab_grid(a, a.B * ((tpi + a.ppt - 1) / a.ppt), nslab);
-  EFFDET_SET_MAX_LDS((dw_fwd_lds_kernel<T, K, S, CQ>), (2 * tile + wb));
-  hipLaunchKernelGGL((dw_fwd_lds_kernel<T, K, S, CQ>), grid, dim3(256), lds, st, a);
-  return EFFDET_OK;
+  p.lds = a.nbuf * tile + wb;
+  p.max_lds = 2 * tile + wb;
+  slab_grid(p, a.B * t.groups(), t.nslab);
+  p.launch = launch_lds<KER>;
 }
-template <typename T, int K, int S, int CQ>
-int launch_dgrad_lds(const DwK& a0, hipStream_t st) {
-  typedef DgTile<K, S> TL;
-  DwK a = a0;
-  const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, wb = (size_t)K * K * CQ * Elem<T>::CE * 4;
-  const int tpi = ((a.H + TL::TH - 1) / TL::TH) * ((a.W + TL::TW - 1) / TL::TW), nslab = (a.nch + CQ - 1) / CQ;
-  a.ppt = tiles_per_wg((long long)tpi * a.B * nslab);
-  if (a.ppt > tpi) a.ppt = tpi;
-  static const int nb_env = getenv("EFFDET_DW_NBUF") ? atoi(getenv("EFFDET_DW_NBUF")) : 0;
-  a.nbuf = (a.ppt > 1 && 2 * tile + wb <= 80 * 1024 && nb_env != 1) ? 2 : 1;
-  const size_t lds = a.nbuf * tile + wb;
-  dim3 grid = slab_grid(a, a.B * ((tpi + a.ppt - 1) / a.ppt), nslab);
-  EFFDET_SET_MAX_LDS((dw_dgrad_lds_kernel<T, K, S, CQ>), (2 * tile + wb));
-  hipLaunchKernelGGL((dw_dgrad_lds_kernel<T, K, S, CQ>), grid, dim3(256), lds, st, a);
-  return EFFDET_OK;
+struct Fwd {
+  template <typename T, int K, int S, int CQ> static void use(DwPlan& p) {
+    use_pipelined<DwTile<K, S>, K, CQ, Elem<T>::CE, dw_fwd_lds_kernel<T, K, S, CQ>>(p, p.f.d.Ho, p.f.d.Wo);
+  }
+};
+struct Dgrad {
+  template <typename T, int K, int S, int CQ> static void use(DwPlan& p) {
+    use_pipelined<DgTile<K, S>, K, CQ, Elem<T>::CE, dw_dgrad_lds_kernel<T, K, S, CQ>>(p, p.f.d.H, p.f.d.W);
+  }
+};
+struct Wgrad {
+  template <typename T, int K, int S, int CQ> static void use(DwPlan& p) {
+    typedef DwTile<K, S> TL;
+    DwK& a = p.f.d;
+    Walk t = walk<TL>(a.B, a.Ho, a.Wo, a.nch, CQ);
+    // forward tiles walked `ppt` at a time by one workgroup: fat workgroups (each ends in a reduction + a slab row that the
+    // reduce kernel has to sum), but at least ~768 of them
+    t.ppt = a.ppt = tiles_per_wg((long long)t.tpi * a.B * t.nslab, 768);
+    const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, red = (size_t)4 * (K * K + 1) * CQ * Elem<T>::CE * 4;
+    p.lds = p.max_lds = red > tile ? red : tile;
+    slab_grid(p, a.B * t.groups(), t.nslab);
+    p.launch = launch_lds<dw_wgrad_lds_kernel<T, K, S, CQ>>;
+  }
+};
+struct Bwd {       // fp32 only (bwd_fused_ok): the element type is not a parameter of the kernel
+  template <typename, int K, int S, int CQ> static void use(DwPlan& p) {
+    typedef BwTile<K, S, CQ> TL;
+    DwK& a = p.f.d;
+    const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, wb = (size_t)K * K * CQ * 4 * 4, red = (size_t)4 * (K * K + 1) * CQ * 4 * 4;
+    Walk t = walk<TL>(a.B, a.H, a.W, a.nch, CQ);
+    // Tiles per workgroup.  ~140 VGPRs = 3 workgroups per CU = 768 resident workgroups, each ending in a reduction + a slab row worth
+    // ~1.5 tiles of time: pick the run length whose ROUNDS of resident workgroups cost least (block 0 of D0 at B = 32: 32 768 tiles ->
+    // 43 per workgroup = exactly one round of 768; the ">= 1536 workgroups" rule of the other kernels gave 3.25 rounds, 4 paid)
+    static const int slots_env = getenv("EFFDET_DWB_SLOTS") ? atoi(getenv("EFFDET_DWB_SLOTS")) : 0;
+    const int slots = slots_env > 0 ? slots_env : (K == 5 ? 512 : 768);            // (k = 5: 100 weight-gradient accumulators, ~200 VGPRs, 2 workgroups per CU)
+    int best = 1; double best_cost = 1e30;
+    for (int ppt = 1; ppt <= 64 && ppt <= t.tpi; ++ppt) {
+      const long long nwg = (long long)a.B * ((t.tpi + ppt - 1) / ppt) * t.nslab;
+      const double cost = (double)((nwg + slots - 1) / slots) * (ppt + 1.5);
+      if (cost < best_cost - 1e-9) { best_cost = cost; best = ppt; }
+    }
+    t.ppt = a.ppt = best;
+    a.nbuf = (a.ppt > 1 && 2 * tile + wb <= 80 * 1024) ? 2 : 1;
+    p.lds = a.nbuf * tile + wb > red ? a.nbuf * tile + wb : red;
+    p.max_lds = 2 * tile + wb > red ? 2 * tile + wb : red;
+    slab_grid(p, a.B * t.groups(), t.nslab);
+    p.launch = launch_lds<dw_bwd_lds_kernel<K, S, CQ>>;
+  }
+};
+// The instance of family F for (k, stride, CQ): one table per family and element type
+template <class F, typename T>
+void pick(DwPlan& p, int k, int stride) {
+  static void (*const tab[8])(DwPlan&) = {
+      F::template use<T, 3, 1, 4>, F::template use<T, 3, 1, 8>, F::template use<T, 3, 2, 4>, F::template use<T, 3, 2, 8>,
+      F::template use<T, 5, 1, 4>, F::template use<T, 5, 1, 8>, F::template use<T, 5, 2, 4>, F::template use<T, 5, 2, 8>};
+  tab[(k == 5) * 4 + (stride == 2) * 2 + (slab_chunks(p.f.d.nch) != 4)](p);
 }
-template <typename T, int K, int S, int CQ>
-int launch_wgrad_lds(const DwK& a0, hipStream_t st) {
-  typedef DwTile<K, S> TL;
-  size_t lds = (size_t)TL::npiece(64 / CQ) * 1024;
-  const size_t red = (size_t)4 * (K * K + 1) * CQ * Elem<T>::CE * 4;
-  if (red > lds) lds = red;
-  const int tpi = ((a0.Ho + TL::TH - 1) / TL::TH) * ((a0.Wo + TL::TW - 1) / TL::TW);
-  DwK a = a0;
-  dim3 grid = slab_grid(a, a.B * ((tpi + a.ppt - 1) / a.ppt), (a.nch + CQ - 1) / CQ);
-  EFFDET_SET_MAX_LDS((dw_wgrad_lds_kernel<T, K, S, CQ>), lds);
-  hipLaunchKernelGGL((dw_wgrad_lds_kernel<T, K, S, CQ>), grid, dim3(256), lds, st, a);
-  return EFFDET_OK;
-}
-#define DW_DISPATCH_Q(FN, T, k, s, a, st)                                                               \
-  do {                                                                                                  \
-    if (slab_chunks((a).nch) == 4) {                                                                    \
-      if ((k) == 3) { if ((s) == 1) FN<T, 3, 1, 4>(a, st); else FN<T, 3, 2, 4>(a, st); }                \
-      else { if ((s) == 1) FN<T, 5, 1, 4>(a, st); else FN<T, 5, 2, 4>(a, st); }                         \
-    } else {                                                                                            \
-      if ((k) == 3) { if ((s) == 1) FN<T, 3, 1, 8>(a, st); else FN<T, 3, 2, 8>(a, st); }                \
-      else { if ((s) == 1) FN<T, 5, 1, 8>(a, st); else FN<T, 5, 2, 8>(a, st); }                         \
-    }                                                                                                   \
-  } while (0)
-#define DW_DISPATCH(FN, dtype, k, s, a, st)                                                    \
-  do {                                                                                         \
-    if ((dtype) == EFFDET_F32) DW_DISPATCH_Q(FN, float, k, s, a, st);                          \
-    else DW_DISPATCH_Q(FN, bf16_t, k, s, a, st);                                               \
-  } while (0)
-}  // namespace
-
-extern "C" int effdet_dwconv_fwd_pool_groups(int dtype, int B, int C, int stride, int Ho, int Wo) {
-  if ((dtype != EFFDET_F32 && dtype != EFFDET_BF16) || B < 1 || C < 1 || (stride != 1 && stride != 2)) return EFFDET_EINVAL;
-  const int ce = dtype == EFFDET_F32 ? 4 : 8;
-  int ppt;
-  return fwd_tiles(B, C / ce, stride, Ho, Wo, ppt);
-}
-
-extern "C" int effdet_dwconv_fwd(const void* x, const float* w, const float* scale, const float* shift, void* y,
-                                 void* z, float* pool, int dtype, int B, int H, int W, int C, int k, int stride,
-                                 int pad_t, int pad_l, int Ho, int Wo, int in_act, effdet_stream_t stream) {
-  if (!x || !w || (!y && !z) || (in_act != EFFDET_ACT_NONE && in_act != EFFDET_ACT_SWISH)) return EFFDET_EINVAL;
-  DwK a{}; dim3 grid;
-  const int ce = dtype == EFFDET_F32 ? 4 : 8;
-  int rc = fill(a, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, ce, Ho * Wo, grid);
+// Planner of the LDS forward, data gradient and weight gradient: chunks of the element type, F's instance for (dtype, k, stride, CQ)
+template <class F>
+int plan(DwPlan& p, int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l, int Ho, int Wo) {
+  const int rc = shape(p.f.d, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, dtype == EFFDET_F32 ? 4 : 8);
   if (rc) return rc;
-  a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.y = y; a.z = z; a.pool = pool; a.in_act = in_act;
-  if (!extent(a, (long long)B * H * W * C, dtype)) return EFFDET_EUNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  DW_DISPATCH(launch_fwd_lds, dtype, k, stride, a, st);
-  EFFDET_CHECK_LAUNCH();
+  if (dtype == EFFDET_F32) pick<F, float>(p, k, stride); else pick<F, bf16_t>(p, k, stride);
   return EFFDET_OK;
 }
 
-
-namespace {
-// tile groups per image / tiles per workgroup of the fused expand -> depthwise forward (always 32-channel slabs)
-inline int fused_tiles(int B, int Cexp, int stride, int Ho, int Wo, int& ppt) {
-  const int th = stride == 1 ? 16 : 8, tw = 8;
-  const int nslab = (Cexp / 4 + 7) / 8;
-  const int tpi = ((Ho + th - 1) / th) * ((Wo + tw - 1) / tw);
-  ppt = tiles_per_wg((long long)tpi * B * nslab);
-  if (ppt > tpi) ppt = tpi;
-  return (tpi + ppt - 1) / ppt;
+// fused expand -> depthwise forward (fp32, always 32-channel slabs), KS = Cin / 4 MFMA k-steps
+template <int K, int S, int KS>
+void launch_fused(const DwPlan& p, hipStream_t st) {
+  EFFDET_SET_MAX_LDS((dw_fwd_fused_kernel<K, S, KS>), p.max_lds);
+  hipLaunchKernelGGL((dw_fwd_fused_kernel<K, S, KS>), p.grid, dim3(256), p.lds, st, p.f);
 }
 template <int K, int S, int KS>
-int launch_fused(const DwFuseK& f0, hipStream_t st) {
-  typedef DwTile<K, S> TL;
-  DwFuseK f = f0;
-  constexpr int NPIECE = TL::npiece(8), NSLOT = NPIECE * 8, NPT = (NSLOT + 15) / 16, NXP = ((NPT * 16) * KS + 63) / 64;
-  const size_t lds = (size_t)NPIECE * 1024 + (size_t)K * K * 32 * 4 + (size_t)32 * KS * 16 + (size_t)NXP * 1024;
-  (void)fused_tiles(f.d.B, f.d.C, S, f.d.Ho, f.d.Wo, f.d.ppt);
-  f.d.nbuf = 1;
-  const int tpi = ((f.d.Ho + TL::TH - 1) / TL::TH) * ((f.d.Wo + TL::TW - 1) / TL::TW), nslab = (f.d.nch + 7) / 8;
-  dim3 grid = slab_grid(f.d, f.d.B * ((tpi + f.d.ppt - 1) / f.d.ppt), nslab);
-  EFFDET_SET_MAX_LDS((dw_fwd_fused_kernel<K, S, KS>), lds);
-  hipLaunchKernelGGL((dw_fwd_fused_kernel<K, S, KS>), grid, dim3(256), lds, st, f);
-  return EFFDET_OK;
+void use_fused(DwPlan& p) {
+  constexpr int NPIECE = DwTile<K, S>::npiece(8), NSLOT = NPIECE * 8, NPT = (NSLOT + 15) / 16, NXP = ((NPT * 16) * KS + 63) / 64;
+  p.lds = p.max_lds = (size_t)NPIECE * 1024 + (size_t)K * K * 32 * 4 + (size_t)32 * KS * 16 + (size_t)NXP * 1024;
+  DwK& a = p.f.d;
+  const Walk t = walk<DwTile<K, S>>(a.B, a.Ho, a.Wo, a.nch, 8);
+  a.ppt = t.ppt;
+  a.nbuf = 1;
+  slab_grid(p, a.B * t.groups(), t.nslab);
+  p.launch = launch_fused<K, S, KS>;
 }
-}  // namespace
-
-extern "C" int effdet_mbconv_expand_dw_pool_groups(int B, int Cexp, int stride, int Ho, int Wo) {
-  if (B < 1 || Cexp < 4 || (Cexp & 3) || (stride != 1 && stride != 2)) return EFFDET_EINVAL;
-  int ppt;
-  return fused_tiles(B, Cexp, stride, Ho, Wo, ppt);
-}
-
-extern "C" int effdet_mbconv_expand_dw_fwd(const float* x, const float* w_expand, const float* scale0, const float* shift0,
-                                           const float* w_dw, const float* scale1, const float* shift1, float* y, float* pool,
-                                           int B, int H, int W, int Cin, int Cexp, int k, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                                           effdet_stream_t stream) {
-  if (!x || !w_expand || !scale0 || !shift0 || !w_dw || !y) return EFFDET_EINVAL;
+int plan_fused(DwPlan& p, int B, int H, int W, int Cin, int Cexp, int k, int stride, int pad_t, int pad_l, int Ho, int Wo) {
   if (Cin != 16 && Cin != 24 && Cin != 32 && Cin != 40) return EFFDET_EUNSUPPORTED;      // MFMA k-steps are compile-time
-  DwFuseK f{}; dim3 grid;
-  int rc = fill(f.d, EFFDET_F32, B, H, W, Cexp, k, stride, pad_t, pad_l, Ho, Wo, 4, Ho * Wo, grid);
+  const int rc = shape(p.f.d, EFFDET_F32, B, H, W, Cexp, k, stride, pad_t, pad_l, Ho, Wo, 4);
   if (rc) return rc;
-  f.d.w = w_dw; f.d.scale = scale1; f.d.shift = shift1; f.d.y = y; f.d.pool = pool;
-  f.xin = x; f.we = w_expand; f.s0 = scale0; f.t0 = shift0; f.Cin = Cin;
-  const long long xb = (long long)B * H * W * Cin * 4;
-  if (xb >= 0xFFFF0000LL) return EFFDET_EUNSUPPORTED;
-  f.xin_bytes = (unsigned)xb;
-  hipStream_t st = (hipStream_t)stream;
-#define FUSED_KS(KSV) do { \
-    if (k == 3) { if (stride == 1) launch_fused<3, 1, KSV>(f, st); else launch_fused<3, 2, KSV>(f, st); } \
-    else { if (stride == 1) launch_fused<5, 1, KSV>(f, st); else launch_fused<5, 2, KSV>(f, st); } } while (0)
-  switch (Cin) { case 16: FUSED_KS(4); break; case 24: FUSED_KS(6); break; case 32: FUSED_KS(8); break; default: FUSED_KS(10); break; }
-#undef FUSED_KS
-  EFFDET_CHECK_LAUNCH();
+  p.f.Cin = Cin;
+  static void (*const tab[16])(DwPlan&) = {
+      use_fused<3, 1, 4>, use_fused<3, 1, 6>, use_fused<3, 1, 8>, use_fused<3, 1, 10>, use_fused<3, 2, 4>, use_fused<3, 2, 6>,
+      use_fused<3, 2, 8>, use_fused<3, 2, 10>, use_fused<5, 1, 4>, use_fused<5, 1, 6>, use_fused<5, 1, 8>, use_fused<5, 1, 10>,
+      use_fused<5, 2, 4>, use_fused<5, 2, 6>, use_fused<5, 2, 8>, use_fused<5, 2, 10>};
+  tab[(k == 5) * 8 + (stride == 2) * 4 + Cin / 8 - 2](p);
   return EFFDET_OK;
 }
 
-extern "C" int effdet_dwconv_dgrad(const void* dz, const float* w, const float* scale, const void* zprev, void* dx,
-                                   int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l,
-                                   int Ho, int Wo, effdet_stream_t stream) {
-  if (!dz || !w || !dx) return EFFDET_EINVAL;
-  DwK a{}; dim3 grid;
-  const int ce = dtype == EFFDET_F32 ? 4 : 8;
-  int rc = fill(a, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, ce, H * W, grid);
-  if (rc) return rc;
-  a.x = dz; a.w = w; a.scale = scale; a.aux = zprev; a.y = dx;
-  if (!extent(a, (long long)B * Ho * Wo * C, dtype)) return EFFDET_EUNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  DW_DISPATCH(launch_dgrad_lds, dtype, k, stride, a, st);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-namespace {
-// ---- fused data + weight gradient (dw_bwd_lds_kernel): fp32, k = 3 ----
+// ---- fused data + weight gradient (dw_bwd_lds_kernel): fp32, maps of >= 64 pixels; k = 3, and k = 5 from H * W >= 1024 at
+// stride 1 / >= 4096 at stride 2 (EFFDET_DW_BWD_FUSED_K5: 0 never, 2 at every map size)
 inline bool bwd_fused_ok(int dtype, int k, int stride, int H, int W) {
   static const int off = getenv("EFFDET_DW_BWD_FUSED") ? atoi(getenv("EFFDET_DW_BWD_FUSED")) == 0 : 0;       // A/B switch
   static const int k5 = getenv("EFFDET_DW_BWD_FUSED_K5") ? atoi(getenv("EFFDET_DW_BWD_FUSED_K5")) : 1;
@@ -1257,149 +1229,152 @@ inline bool bwd_fused_ok(int dtype, int k, int stride, int H, int W) {
   const bool k5ok = k5 == 2 || (k5 == 1 && H * W >= (stride == 1 ? 1024 : 4096));
   return !off && dtype == EFFDET_F32 && (k == 3 || (k == 5 && k5ok)) && H * W >= 64;
 }
-template <int K, int S, int CQ>
-int bwd_geometry(DwK& a, dim3& grid, size_t& lds) {
-  typedef BwTile<K, S, CQ> TL;
-  const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, wb = (size_t)K * K * CQ * 4 * 4, red = (size_t)4 * (K * K + 1) * CQ * 4 * 4;
-  const int tpi = ((a.H + TL::TH - 1) / TL::TH) * ((a.W + TL::TW - 1) / TL::TW), nslab = (a.nch + CQ - 1) / CQ;
-  // Tiles per workgroup.  ~140 VGPRs = 3 workgroups per CU = 768 resident workgroups, each ending in a reduction + a slab row worth
-  // ~1.5 tiles of time: pick the run length whose ROUNDS of resident workgroups cost least (block 0 of D0 at B = 32: 32 768 tiles ->
-  // 43 per workgroup = exactly one round of 768; the ">= 1536 workgroups" rule of the other kernels gave 3.25 rounds, 4 paid)
-  static const int slots_env = getenv("EFFDET_DWB_SLOTS") ? atoi(getenv("EFFDET_DWB_SLOTS")) : 0;
-  const int slots = slots_env > 0 ? slots_env : (K == 5 ? 512 : 768);            // (k = 5: 100 weight-gradient accumulators, ~200 VGPRs, 2 workgroups per CU)
-  int best = 1; double best_cost = 1e30;
-  for (int ppt = 1; ppt <= 64 && ppt <= tpi; ++ppt) {
-    const long long nwg = (long long)a.B * ((tpi + ppt - 1) / ppt) * nslab;
-    const double cost = (double)((nwg + slots - 1) / slots) * (ppt + 1.5);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best = ppt; }
-  }
-  a.ppt = best;
-  a.nbuf = (a.ppt > 1 && 2 * tile + wb <= 80 * 1024) ? 2 : 1;
-  lds = a.nbuf * tile + wb;
-  if (lds < red) lds = red;
-  grid = slab_grid(a, a.B * ((tpi + a.ppt - 1) / a.ppt), nslab);
-  return a.B * ((tpi + a.ppt - 1) / a.ppt);            // slab rows
-}
-template <int K, int S, int CQ>
-int launch_bwd_lds(const DwK& a0, hipStream_t st, bool launch) {
-  DwK a = a0; dim3 grid; size_t lds;
-  const int rows = bwd_geometry<K, S, CQ>(a, grid, lds);
-  if (!launch) return rows;
-  {  // (the attribute is set once per device: the largest request of this instantiation, not the first launch's)
-    typedef BwTile<K, S, CQ> TL;
-    const size_t mx = (size_t)2 * TL::npiece(64 / CQ) * 1024 + (size_t)K * K * CQ * 16, red = (size_t)4 * (K * K + 1) * CQ * 16;
-    EFFDET_SET_MAX_LDS((dw_bwd_lds_kernel<K, S, CQ>), (mx > red ? mx : red));
-  }
-  hipLaunchKernelGGL((dw_bwd_lds_kernel<K, S, CQ>), grid, dim3(256), lds, st, a);
-  return rows;
-}
-int bwd_dispatch(const DwK& a, int stride, hipStream_t st, bool launch) {
-  if (a.k == 5) {
-    if (slab_chunks(a.nch) == 4) return stride == 1 ? launch_bwd_lds<5, 1, 4>(a, st, launch) : launch_bwd_lds<5, 2, 4>(a, st, launch);
-    return stride == 1 ? launch_bwd_lds<5, 1, 8>(a, st, launch) : launch_bwd_lds<5, 2, 8>(a, st, launch);
-  }
-  if (slab_chunks(a.nch) == 4) return stride == 1 ? launch_bwd_lds<3, 1, 4>(a, st, launch) : launch_bwd_lds<3, 2, 4>(a, st, launch);
-  return stride == 1 ? launch_bwd_lds<3, 1, 8>(a, st, launch) : launch_bwd_lds<3, 2, 8>(a, st, launch);
-}
-}  // namespace
-
-extern "C" long long effdet_dwconv_bwd_workspace_bytes(int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l,
-                                                        int Ho, int Wo) {
-  if (!bwd_fused_ok(dtype, k, stride, H, W)) return 0;             // 0 = not available for this geometry: use the two separate entry points
-  DwK a{}; dim3 grid;
-  if (fill(a, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, 4, H * W, grid)) return -1;
-  return (long long)bwd_dispatch(a, stride, nullptr, false) * (k * k + 1) * C * (long long)sizeof(float);
-}
-
-extern "C" int effdet_dwconv_bwd(const void* dz, const float* w, const float* scale, const void* zprev, void* dx, float* g, float* dsum,
-                                 void* workspace, long long workspace_bytes, int dtype, int B, int H, int W, int C, int k, int stride,
-                                 int pad_t, int pad_l, int Ho, int Wo, effdet_stream_t stream) {
-  if (!dz || !w || !zprev || !dx || !g || !workspace) return EFFDET_EINVAL;
+inline long long slab_bytes(const DwPlan& p) { return (long long)p.groups * (p.f.d.k * p.f.d.k + 1) * p.f.d.C * (long long)sizeof(float); }
+int plan_bwd(DwPlan& p, int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l, int Ho, int Wo) {
   if (!bwd_fused_ok(dtype, k, stride, H, W)) return EFFDET_EUNSUPPORTED;
-  DwK a{}; dim3 grid;
-  int rc = fill(a, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, 4, H * W, grid);
+  const int rc = shape(p.f.d, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, 4);
   if (rc) return rc;
-  a.x = dz; a.w = w; a.scale = scale; a.aux = zprev; a.y = dx; a.z = workspace;
-  if (!extent(a, (long long)B * Ho * Wo * C, dtype)) return EFFDET_EUNSUPPORTED;
-  const int rows = k * k + 1;
-  if (workspace_bytes < (long long)bwd_dispatch(a, stride, nullptr, false) * rows * C * (long long)sizeof(float)) return EFFDET_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const int nrows = bwd_dispatch(a, stride, st, true);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((rows * C + 63) / 64), dim3(256), 0, st, (const float*)workspace, g, dsum, nrows, rows, C);
-  EFFDET_CHECK_LAUNCH();
+  pick<Bwd, float>(p, k, stride);
+  p.workspace_bytes = slab_bytes(p);
   return EFFDET_OK;
 }
 
-namespace {
 // tiny maps (<= 4x4 outputs): a 16x8 tile is mostly halo and padding -- the direct kernel is faster there.  (8x8 maps were on the direct
 // kernel too until the k5 LDS form got its registers down: C1152 8x8 k5 28-30 us direct, 24 us on the LDS kernel incl. its Swish pass.)
 inline bool wgrad_direct(int Ho, int Wo) {
   static const int lim = getenv("EFFDET_DW_WGRAD_DIRECT") ? atoi(getenv("EFFDET_DW_WGRAD_DIRECT")) : 16;      // A/B switch: largest map on the direct kernel
   return Ho * Wo <= lim;
 }
-
-int wgrad_plan(DwK& a, dim3& grid, int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l, int Ho, int Wo) {
-  if (wgrad_direct(Ho, Wo)) {
-    int rc = fill(a, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, 4, Ho * Wo, grid);
+template <typename T, int K>
+void launch_wgrad_direct(const DwPlan& p, hipStream_t st) {
+  hipLaunchKernelGGL((dw_wgrad_kernel<T, K>), p.grid, dim3(256), 0, st, p.f.d);
+}
+int plan_wgrad(DwPlan& p, int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l, int Ho, int Wo) {
+  if (!wgrad_direct(Ho, Wo)) {
+    const int rc = plan<Wgrad>(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo);
     if (rc) return rc;
-    const int TY = 256 / a.tx;
-    int ppt = 64;
-    while (ppt > 1 && (long long)B * ((Ho * Wo + TY * ppt - 1) / (TY * ppt)) * ((a.nch + a.tx - 1) / a.tx) < 512) ppt >>= 1;
-    a.ppt = ppt;
-    grid = dim3(B * ((Ho * Wo + TY * ppt - 1) / (TY * ppt)), (a.nch + a.tx - 1) / a.tx);
-    return EFFDET_OK;
+  } else {               // direct kernel: tx lanes of 4-channel groups x 256 / tx pixel rows, ppt pixels per thread
+    DwK& a = p.f.d;
+    const int rc = shape(a, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, 4);
+    if (rc) return rc;
+    a.tx = pow2_ge(a.nch) < 64 ? pow2_ge(a.nch) : 64;
+    const int TY = 256 / a.tx, npix = Ho * Wo, cgroups = (a.nch + a.tx - 1) / a.tx;
+    a.ppt = 64;
+    while (a.ppt > 1 && (long long)B * ((npix + TY * a.ppt - 1) / (TY * a.ppt)) * cgroups < 512) a.ppt >>= 1;
+    p.groups = B * ((npix + TY * a.ppt - 1) / (TY * a.ppt));
+    p.grid = dim3(p.groups, cgroups);
+    static void (*const tab[4])(const DwPlan&, hipStream_t) = {
+        launch_wgrad_direct<float, 3>, launch_wgrad_direct<float, 5>, launch_wgrad_direct<bf16_t, 3>, launch_wgrad_direct<bf16_t, 5>};
+    p.launch = tab[(dtype != EFFDET_F32) * 2 + (k == 5)];
   }
-  const int ce = dtype == EFFDET_F32 ? 4 : 8;
-  int rc = fill(a, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo, ce, Ho * Wo, grid);
-  if (rc) return rc;
-  // forward tiles (16x8 at stride 1, 8x8 at stride 2) walked `ppt` at a time by one workgroup: fat workgroups (each
-  // ends in a reduction + a slab row that the reduce kernel has to sum), but at least ~768 of them
-  const int th = stride == 1 ? 16 : 8, tw = 8;
-  const int tpi = ((Ho + th - 1) / th) * ((Wo + tw - 1) / tw), cq = slab_chunks(a.nch), nslab = (a.nch + cq - 1) / cq;
-  long long ppt = (long long)tpi * B * nslab / 768;
-  if (ppt < 1) ppt = 1;
-  if (ppt > 16) ppt = 16;
-  a.ppt = (int)ppt;
-  grid = dim3(B * ((tpi + a.ppt - 1) / a.ppt), nslab);
+  p.workspace_bytes = slab_bytes(p);
   return EFFDET_OK;
 }
+
+// Launch a plan; the weight gradients then add their slab rows in `slabs` into g / dsum in a fixed order
+int run(const DwPlan& p, effdet_stream_t stream, const void* slabs = nullptr, float* g = nullptr, float* dsum = nullptr) {
+  hipStream_t st = (hipStream_t)stream;
+  p.launch(p, st);
+  EFFDET_CHECK_LAUNCH();
+  if (!slabs) return EFFDET_OK;
+  const int rows = p.f.d.k * p.f.d.k + 1, C = p.f.d.C;
+  hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((rows * C + 63) / 64), dim3(256), 0, st, (const float*)slabs, g, dsum, p.groups, rows, C);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
 }  // namespace
+
+extern "C" int effdet_dwconv_fwd_pool_groups(int dtype, int B, int C, int stride, int Ho, int Wo) {
+  if ((dtype != EFFDET_F32 && dtype != EFFDET_BF16) || B < 1 || C < 1 || (stride != 1 && stride != 2)) return EFFDET_EINVAL;
+  const int nch = C / (dtype == EFFDET_F32 ? 4 : 8);
+  return fwd_groups(B, stride, Ho, Wo, nch, slab_chunks(nch));
+}
+
+extern "C" int effdet_dwconv_fwd(const void* x, const float* w, const float* scale, const float* shift, void* y,
+                                 void* z, float* pool, int dtype, int B, int H, int W, int C, int k, int stride,
+                                 int pad_t, int pad_l, int Ho, int Wo, int in_act, effdet_stream_t stream) {
+  if (!x || !w || (!y && !z) || (in_act != EFFDET_ACT_NONE && in_act != EFFDET_ACT_SWISH)) return EFFDET_EINVAL;
+  DwPlan p{};
+  DwK& a = p.f.d;
+  const int rc = plan<Fwd>(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo);
+  if (rc) return rc;
+  if (!extent(a.x_bytes, (long long)B * H * W * C, dtype)) return EFFDET_EUNSUPPORTED;
+  a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.y = y; a.z = z; a.pool = pool; a.in_act = in_act;
+  return run(p, stream);
+}
+
+extern "C" int effdet_mbconv_expand_dw_pool_groups(int B, int Cexp, int stride, int Ho, int Wo) {
+  if (B < 1 || Cexp < 4 || (Cexp & 3) || (stride != 1 && stride != 2)) return EFFDET_EINVAL;
+  return fwd_groups(B, stride, Ho, Wo, Cexp / 4, 8);
+}
+
+extern "C" int effdet_mbconv_expand_dw_fwd(const float* x, const float* w_expand, const float* scale0, const float* shift0,
+                                           const float* w_dw, const float* scale1, const float* shift1, float* y, float* pool,
+                                           int B, int H, int W, int Cin, int Cexp, int k, int stride, int pad_t, int pad_l, int Ho, int Wo,
+                                           effdet_stream_t stream) {
+  if (!x || !w_expand || !scale0 || !shift0 || !w_dw || !y) return EFFDET_EINVAL;
+  DwPlan p{};
+  DwFuseK& f = p.f;
+  const int rc = plan_fused(p, B, H, W, Cin, Cexp, k, stride, pad_t, pad_l, Ho, Wo);
+  if (rc) return rc;
+  if (!extent(f.xin_bytes, (long long)B * H * W * Cin, EFFDET_F32)) return EFFDET_EUNSUPPORTED;
+  f.d.w = w_dw; f.d.scale = scale1; f.d.shift = shift1; f.d.y = y; f.d.pool = pool;
+  f.xin = x; f.we = w_expand; f.s0 = scale0; f.t0 = shift0;
+  return run(p, stream);
+}
+
+extern "C" int effdet_dwconv_dgrad(const void* dz, const float* w, const float* scale, const void* zprev, void* dx,
+                                   int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l,
+                                   int Ho, int Wo, effdet_stream_t stream) {
+  if (!dz || !w || !dx) return EFFDET_EINVAL;
+  DwPlan p{};
+  DwK& a = p.f.d;
+  const int rc = plan<Dgrad>(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo);
+  if (rc) return rc;
+  if (!extent(a.x_bytes, (long long)B * Ho * Wo * C, dtype)) return EFFDET_EUNSUPPORTED;
+  a.x = dz; a.w = w; a.scale = scale; a.aux = zprev; a.y = dx;
+  return run(p, stream);
+}
+
+extern "C" long long effdet_dwconv_bwd_workspace_bytes(int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l,
+                                                        int Ho, int Wo) {
+  if (!bwd_fused_ok(dtype, k, stride, H, W)) return 0;             // 0 = not available for this geometry: use the two separate entry points
+  DwPlan p{};
+  return plan_bwd(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo) ? -1 : p.workspace_bytes;
+}
+
+extern "C" int effdet_dwconv_bwd(const void* dz, const float* w, const float* scale, const void* zprev, void* dx, float* g, float* dsum,
+                                 void* workspace, long long workspace_bytes, int dtype, int B, int H, int W, int C, int k, int stride,
+                                 int pad_t, int pad_l, int Ho, int Wo, effdet_stream_t stream) {
+  if (!dz || !w || !zprev || !dx || !g || !workspace) return EFFDET_EINVAL;
+  DwPlan p{};
+  DwK& a = p.f.d;
+  const int rc = plan_bwd(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo);
+  if (rc) return rc;
+  if (!extent(a.x_bytes, (long long)B * Ho * Wo * C, dtype)) return EFFDET_EUNSUPPORTED;
+  if (workspace_bytes < p.workspace_bytes) return EFFDET_EINVAL;
+  a.x = dz; a.w = w; a.scale = scale; a.aux = zprev; a.y = dx; a.z = workspace;
+  return run(p, stream, workspace, g, dsum);
+}
 
 extern "C" long long effdet_dwconv_wgrad_workspace_bytes(int dtype, int B, int H, int W, int C, int k, int stride, int pad_t,
                                                           int pad_l, int Ho, int Wo) {
-  DwK a{}; dim3 grid;
-  if (wgrad_plan(a, grid, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo)) return -1;
-  return (long long)grid.x * (k * k + 1) * C * (long long)sizeof(float);     // one slab row set per workgroup (both kernels)
+  DwPlan p{};
+  return plan_wgrad(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo) ? -1 : p.workspace_bytes;
 }
 
 extern "C" int effdet_dwconv_wgrad(const void* x, const void* dz, float* g, float* dsum, void* workspace,
                                    long long workspace_bytes, int dtype, int B, int H, int W, int C, int k, int stride,
                                    int pad_t, int pad_l, int Ho, int Wo, int in_act, effdet_stream_t stream) {
   if (!x || !dz || !g || !workspace || (in_act != EFFDET_ACT_NONE && in_act != EFFDET_ACT_SWISH)) return EFFDET_EINVAL;
-  DwK a{}; dim3 grid;
-  int rc = wgrad_plan(a, grid, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo);
+  DwPlan p{};
+  DwK& a = p.f.d;
+  const int rc = plan_wgrad(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo);
   if (rc) return rc;
-  if (workspace_bytes < (long long)grid.x * (k * k + 1) * C * (long long)sizeof(float)) return EFFDET_EINVAL;
-  a.x = x; a.aux = dz; a.y = workspace; a.in_act = in_act;
-  if (!extent(a, (long long)B * H * W * C, dtype)) return EFFDET_EUNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if ((long long)B * Ho * Wo * C * (dtype == EFFDET_F32 ? 4 : 2) >= 0xFFFF0000LL) return EFFDET_EUNSUPPORTED;
-  if (wgrad_direct(Ho, Wo)) {
-    if (dtype == EFFDET_F32) {
-      if (k == 3) hipLaunchKernelGGL((dw_wgrad_kernel<float, 3>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((dw_wgrad_kernel<float, 5>), grid, dim3(256), 0, st, a);
-    } else {
-      if (k == 3) hipLaunchKernelGGL((dw_wgrad_kernel<bf16_t, 3>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((dw_wgrad_kernel<bf16_t, 5>), grid, dim3(256), 0, st, a);
-    }
-  } else {
-    DW_DISPATCH(launch_wgrad_lds, dtype, k, stride, a, st);  // a.y = the slabs: [grid.x = B * tile groups][k*k + 1][C]
-  }
-  EFFDET_CHECK_LAUNCH();
-  const int rows = k * k + 1;
-  hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((rows * C + 63) / 64), dim3(256), 0, st, (const float*)workspace, g, dsum,
-                     (int)grid.x, rows, C);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
+  if (workspace_bytes < p.workspace_bytes) return EFFDET_EINVAL;
+  unsigned dz_bytes;                           // (dz is addressed with 32-bit offsets too)
+  if (!extent(a.x_bytes, (long long)B * H * W * C, dtype) || !extent(dz_bytes, (long long)B * Ho * Wo * C, dtype)) return EFFDET_EUNSUPPORTED;
+  a.x = x; a.aux = dz; a.y = workspace; a.in_act = in_act;     // a.y = the slabs: [groups][k*k + 1][C]
+  return run(p, stream, workspace, g, dsum);
 }

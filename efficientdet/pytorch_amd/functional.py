@@ -21,7 +21,7 @@ DW_SAVE_Y = os.environ.get('EFFDET_DW_SAVE_Y', '0') == '1'      # A/B switch: al
 BIFPN_WGRAD_GROUP = os.environ.get('EFFDET_BIFPN_WGRAD_GROUP', '1') != '0'     # A/B switch: grouped BiFPN weight gradients
 EXPAND_Z_ONLY = os.environ.get('EFFDET_EXPAND_Z_ONLY', '1') == '1'   # training: the expand conv stores its pre-activation only
 SE_FUSED = os.environ.get('EFFDET_SE_FUSED', '1') == '1'             # squeeze-excite backward fused into the project conv's gradients
-DW_BWD_FUSED = os.environ.get('EFFDET_DW_BWD_FUSED', '1') == '1'       # training, fp32, k = 3: depthwise data + weight gradient in one kernel
+DW_BWD_FUSED = os.environ.get('EFFDET_DW_BWD_FUSED', '1') == '1'       # training, fp32, k = 3, or k = 5 at H*W >= 1024 (stride 1) / 4096 (stride 2), EFFDET_DW_BWD_FUSED_K5 overrides: depthwise data + weight gradient in one kernel
 PW_BWD_FUSED = os.environ.get('EFFDET_PW_BWD_FUSED', '1') == '1'       # training, fp32, Cin 16 / 24 / 32: expand conv data + weight gradient in one kernel
 PW_DGRAD_SE = os.environ.get('EFFDET_PW_DGRAD_SE', '1') == '1'         # training, fp32, Co 16 / 24 / 40: project-conv data gradient + SE backward epilogue as a streaming MFMA kernel
 FUSE_EXPAND_DW = os.environ.get('EFFDET_FUSE_EXPAND_DW', '1') == '1'  # inference, fp32 storage: expand conv inside the depthwise kernel

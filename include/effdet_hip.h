@@ -330,7 +330,8 @@ int effdet_dwconv_wgrad(const void* x, const void* dz, float* g_kkc, float* dsum
 /* Data gradient AND weight gradient of the depthwise conv in one pass over dz and zprev (models/efficientnet.py:85-88 backward; replaces
  * the two entry points above when the conv's input was stored as its producer's PRE-activation only, i.e. x = swish(zprev)):
  *   dx = (sum_taps dz * w * scale) * swish'(zprev)      g[tap][c] = sum dz * swish(zprev)(tap)      dsum[c] = sum dz
- * fp32, k = 3.  effdet_dwconv_bwd_workspace_bytes returns 0 when the fused form does not serve the geometry (use the two separate
+ * fp32, H*W >= 64; k = 3, and k = 5 from H*W >= 1024 at stride 1 / >= 4096 at stride 2 (env EFFDET_DW_BWD_FUSED_K5: 0 never, 2 at
+ * every map size).  effdet_dwconv_bwd_workspace_bytes returns 0 when the fused form does not serve the geometry (use the two separate
  * entry points), < 0 on invalid arguments, else the bytes of the slab workspace (one [k*k + 1][C] row set per workgroup, added in a
  * fixed order by a reduce pass: no float atomics).  g_kkc / dsum are OVERWRITTEN. */
 long long effdet_dwconv_bwd_workspace_bytes(int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l,

@@ -245,6 +245,57 @@ def test_weight_gradient_planning_entry_points():
     assert int(lib.effdet_conv2d_wgrad_seg_slabs(None, None, None)) == -1
 
 
+def test_depthwise_planning_entry_points():
+    """effdet_dwconv_fwd_pool_groups / effdet_mbconv_expand_dw_pool_groups / effdet_dwconv_{wgrad,bwd}_workspace_bytes (host planning
+    only) for the depthwise convs of a D0 step (B = 32 @ 512), and the codes of calls every entry point refuses before launching."""
+    import ctypes as C
+    from efficientdet.pytorch_amd import _lib as L
+    from efficientdet.pytorch_amd.config import backbone_plan, conv_out
+    lib = L.lib()
+    pads = {(b.k, b.stride): b.pad for b in backbone_plan('efficientnet-b0')[2]}
+
+    def geo(dtype, k, s, H, C_, B=32):
+        p = pads[(k, s)]
+        Ho = conv_out(H, k, s, p)
+        return (dtype, B, H, H, C_, k, s, p[0], p[0], Ho, Ho)
+    # (k, s, H, Cexp): fwd pool groups f32 / bf16, fused pool groups, wgrad / bwd workspace bytes (f32)
+    for (k, s, H, Ce), (gf, gb, gx, wws, bws) in [
+            ((3, 1, 256, 32), (64, 64, 64, 1310720, 983040)), ((3, 2, 256, 96), (22, 22, 22, 1966080, 983040)),
+            ((3, 1, 128, 144), (13, 13, 13, 1474560, 1658880)), ((5, 2, 128, 144), (13, 13, 13, 2396160, 1437696)),
+            ((5, 1, 64, 240), (8, 16, 8, 3194880, 1597440)), ((3, 2, 64, 240), (8, 16, 8, 1228800, 921600)),
+            ((3, 1, 32, 480), (8, 8, 8, 1228800, 1843200)), ((5, 2, 32, 480), (4, 4, 4, 3194880, 0)),
+            ((5, 1, 16, 672), (2, 2, 2, 4472832, 0)), ((5, 2, 16, 672), (1, 1, 1, 2236416, 0)),
+            ((5, 1, 8, 1152), (1, 1, 1, 3833856, 0)), ((3, 2, 8, 1152), (1, 1, 1, 5898240, 1474560))]:      # (last: direct wgrad)
+        g = geo(L.F32, k, s, H, Ce)
+        Ho = g[-1]
+        got = (int(lib.effdet_dwconv_fwd_pool_groups(L.F32, 32, Ce, s, Ho, Ho)), int(lib.effdet_dwconv_fwd_pool_groups(L.BF16, 32, Ce, s, Ho, Ho)),
+               int(lib.effdet_mbconv_expand_dw_pool_groups(32, Ce, s, Ho, Ho)),
+               int(lib.effdet_dwconv_wgrad_workspace_bytes(*g)), int(lib.effdet_dwconv_bwd_workspace_bytes(*g)))
+        assert got == (gf, gb, gx, wws, bws), ((k, s, H, Ce), got)
+    assert int(lib.effdet_dwconv_wgrad_workspace_bytes(*geo(L.BF16, 3, 1, 64, 240))) == 2150400
+    assert int(lib.effdet_dwconv_wgrad_workspace_bytes(*geo(L.BF16, 5, 1, 32, 480))) == 6389760
+    assert int(lib.effdet_dwconv_bwd_workspace_bytes(*geo(L.BF16, 3, 1, 64, 240))) == 0          # fused backward: fp32 only
+    # invalid arguments (EFFDET_EINVAL = -1, EFFDET_EUNSUPPORTED = -3); none of these calls reaches a launch
+    assert int(lib.effdet_dwconv_fwd_pool_groups(7, 32, 32, 1, 64, 64)) == -1
+    assert int(lib.effdet_dwconv_fwd_pool_groups(L.F32, 32, 32, 3, 64, 64)) == -1
+    assert int(lib.effdet_mbconv_expand_dw_pool_groups(32, 30, 1, 64, 64)) == -1
+    assert int(lib.effdet_dwconv_wgrad_workspace_bytes(*geo(2, 3, 1, 64, 240))) == -1
+    assert int(lib.effdet_dwconv_wgrad_workspace_bytes(*geo(L.F32, 3, 1, 64, 30))) == -1          # C % 4
+    assert int(lib.effdet_dwconv_bwd_workspace_bytes(L.F32, 32, 64, 64, 240, 3, 3, 0, 0, 22, 22)) == -1    # stride 3
+    P, N = C.c_void_p(0x1000), None
+    g = geo(L.F32, 3, 1, 64, 240)
+    assert int(lib.effdet_dwconv_fwd(N, P, P, P, P, P, P, *g, L.ACT_NONE, N)) == -1
+    assert int(lib.effdet_dwconv_fwd(P, P, P, P, P, P, P, *geo(2, 3, 1, 64, 240), L.ACT_NONE, N)) == -1
+    assert int(lib.effdet_dwconv_fwd(P, P, P, P, P, P, P, *geo(L.BF16, 3, 1, 64, 36), L.ACT_NONE, N)) == -3       # C % 8
+    assert int(lib.effdet_dwconv_fwd(P, P, P, P, P, P, P, *geo(L.F32, 3, 1, 512, 1152), L.ACT_NONE, N)) == -3      # 38 GB input
+    assert int(lib.effdet_dwconv_dgrad(P, P, P, P, P, L.F32, 32, 64, 64, 240, 7, 1, 3, 3, 64, 64, N)) == -3        # k = 7
+    assert int(lib.effdet_mbconv_expand_dw_fwd(P, P, P, P, P, P, P, P, P, 32, 64, 64, 48, 288, 3, 1, 1, 1, 64, 64, N)) == -3    # Cin
+    ws = int(lib.effdet_dwconv_wgrad_workspace_bytes(*g))
+    assert int(lib.effdet_dwconv_wgrad(P, P, P, P, P, C.c_longlong(ws - 1), *g, L.ACT_SWISH, N)) == -1
+    ws = int(lib.effdet_dwconv_bwd_workspace_bytes(*g))
+    assert int(lib.effdet_dwconv_bwd(P, P, P, P, P, P, P, P, C.c_longlong(ws - 1), *g, N)) == -1
+
+
 def test_tail_batch_context_records_and_joins(monkeypatch):
     """ops.unpack_batch (host logic of effdet_backward_tail): jobs issued inside are recorded, an inner block joins the outer one,
     the launch happens once at the outermost exit, and an exception inside drops the batch instead of launching half a node."""
