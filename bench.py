@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- EfficientDet-D0 512px train step (fwd + focal/smooth-L1 loss + bwd + clip + AdamW) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps of the headline leg, writes --dump-outputs if asked and prints the result line: nothing
+else.  --full adds, after the headline leg, everything else the benchmark measures: the instrumented roofline step and the extra objects
+listed below.  The captured step's replay-vs-eager self-check stays in a plain run: it decides whether the timed steps replay the graph,
+and it leaves the model one step further on, so the dumped outputs depend on it.
 
 Works by itself for every N: with N > 1 and no WORLD_SIZE in the environment it re-launches itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (the reference self-spawns too,
@@ -18,7 +23,7 @@ product ~2^-22, inside the rounding noise of the fp32 accumulation (against a fl
 head's, tests/test_gpu_model.py::test_f16x3_head_is_fp32_equivalent_at_model_level; every complete-detection-list golden of the real
 reference incl. D4 @1024 holds); only the GRADIENT convolutions run on bf16 hi + lo operand splits (3 bf16 MFMAs per product, ~1e-5 per
 product).  Losses / outputs / all parameter-gradient norms are gated at 1e-3 (+ the reference's own measured instability s_k) against the
-real reference's goldens on EVERY model family D0..D6 (profiles/r06_parity_errors.txt).  Extra objects in the same line:
+real reference's goldens on EVERY model family D0..D6 (profiles/r06_parity_errors.txt).  Extra objects in the same line (--full only):
   exact_forward_mode_f32fwd_bf16x3bwd   round 5's headline: the whole forward bit for bit the f32 mode's, bf16x3 gradient convs;
   strict_mode_f32        the SAME step with exact-fp32 products in the backward too;
   fast_mode_bf16x3       bf16x3 products in the forward as well: faster, but NOT parity-qualified -- its box deltas / neck taps measure
@@ -30,7 +35,7 @@ real reference's goldens on EVERY model family D0..D6 (profiles/r06_parity_error
   cpu_baseline           the oracle = torch-CPU restatement of the reference, bounded sample, thread sweep + configs[0].
 The headline leg times exactly --steps steps; every extra-mode leg --extra-steps (default 20).
 
---dump-outputs DIR writes what the headline's timed step computed in its LAST timed step (before the instrumented roofline step):
+--dump-outputs DIR writes what the headline's timed step computed in its LAST timed step (before --full's instrumented roofline step):
 DIR/cls_loss.npy and DIR/reg_loss.npy (what the step returns) and DIR/parameters.npy (every trainable parameter after the optimizer
 update, flattened in named_parameters() order), float32, at most 64 MB in all (a larger output is cut to a fixed, seeded sample of its
 elements).  Weights (torch.manual_seed(0)), the synthetic batch and the drop_connect stream are seeded, so the same arguments give the
@@ -94,6 +99,9 @@ def parse(argv=None):
     ap.add_argument('--dtype', default='f32_hf16x3_bwd_bf16x3', choices=['bf16', 'f32', 'f32_bf16x3', 'f32_bwd_bf16x3', 'f32_hf16x3_bwd_bf16x3'],
                     help='arithmetic mode of the headline leg (default: exact-fp32 trunk + fp32-equivalent f16x3 RetinaHead forward, bf16x3 gradient '
                          'convs -- the fastest mode that meets the 1e-3 parity gates and reproduces every complete-detection-list golden)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline leg, also run the instrumented roofline step, the other arithmetic modes, the inference legs '
+                         '(configs[1], configs[4]) and the CPU baseline; the --no-* switches below leave single parts out of a --full run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-inference', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
@@ -118,6 +126,8 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.steps < 1 or a.extra_steps < 1:
         ap.error('--steps and --extra-steps must be >= 1')
+    if not a.full:      # a plain run does what the headline line needs and nothing after it
+        a.no_roofline = a.no_extra_modes = a.no_inference = a.no_d4 = a.no_cpu_baseline = True
     if a.dump_outputs:
         a.dump_outputs = os.path.abspath(a.dump_outputs)       # (DDP legs run in child processes started with cwd=ROOT)
     return a
@@ -550,7 +560,8 @@ def result_line(a, world, leg, cfg, ddp_note=None):
 
 
 def single_gpu_main(a):
-    """N = 1: the headline leg, the other arithmetic modes, inference (configs[1], configs[4]) and the CPU baseline, in one process."""
+    """N = 1, in one process: the headline leg; with --full also the other arithmetic modes, inference (configs[1], configs[4]) and the
+    CPU baseline."""
     import torch
     from efficientdet.pytorch_amd import EFFICIENTDET
     torch.cuda.set_device(0)

@@ -3,7 +3,7 @@
 TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-B1="python bench.py --no-cpu-baseline --no-extra-modes --no-d4 --no-inference"
+B1="python bench.py --full --no-cpu-baseline --no-extra-modes --no-d4 --no-inference"
 for s in "$@"; do
   t0=$(date +%s)
   case $s in
@@ -15,7 +15,7 @@ for s in "$@"; do
     mfma)     hipcc --offload-arch=gfx950 -O3 -o /tmp/mfma_peak tools/probe/mfma_peak.hip > /dev/null 2>&1 && timeout 120 /tmp/mfma_peak > $OUT/mfma_peak.txt 2>&1; cat $OUT/mfma_peak.txt ;;
     chunk)    timeout 300 python tools/chunk_probe.py 4 > $OUT/chunk_probe.txt 2>&1; tail -8 $OUT/chunk_probe.txt ;;
     ddp1)     timeout 600 python bench.py --ddp-single --no-cpu-baseline --no-extra-modes --no-d4 --no-inference --no-roofline > $OUT/bench_ddp1.log 2> $OUT/bench_ddp1.err; echo "ddp1 rc=$?" | tee -a $OUT/rc.txt; tail -c 1500 $OUT/bench_ddp1.log; tail -5 $OUT/bench_ddp1.err ;;
-    bench)    timeout 900 python bench.py > $OUT/bench.log 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/rc.txt; tail -c 3000 $OUT/bench.log; tail -3 $OUT/bench.err ;;
+    bench)    timeout 900 python bench.py --full > $OUT/bench.log 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/rc.txt; tail -c 3000 $OUT/bench.log; tail -3 $OUT/bench.err ;;
     bench1)   timeout 300 $B1 > $OUT/bench1.log 2> $OUT/bench1.err; echo "bench1 rc=$?" | tee -a $OUT/rc.txt; tail -c 1200 $OUT/bench1.log ;;
     hostc)    timeout 400 python tools/host_contention.py > $OUT/host_contention.txt 2>&1; tail -8 $OUT/host_contention.txt ;;
     *)        if [ -f "tools/r4_steps/$s.sh" ]; then OUT=$OUT bash tools/r4_steps/$s.sh; else echo "unknown step $s"; fi ;;
