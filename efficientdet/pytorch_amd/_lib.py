@@ -92,7 +92,8 @@ SYMBOLS = [
     'effdet_anchors', 'effdet_num_anchors', 'effdet_decode_score', 'effdet_nms_workspace_bytes', 'effdet_nms',
     'effdet_gather_dets', 'effdet_loss_workspace_bytes', 'effdet_focal_loss_fwd', 'effdet_focal_loss_bwd', 'effdet_focal_loss_bwd_pix', 'effdet_focal_loss_fwd_grad', 'effdet_focal_loss_bwd_reg',
     'effdet_clip_adamw_step', 'effdet_opt_chunk',
-    'effdet_drop_connect_scales', 'effdet_philox4x32_10', 'effdet_preprocess_batch', 'effdet_finalize_dets', 'effdet_voc_match', 'effdet_voc_ap', 'effdet_voc_ap_workspace_bytes', 'effdet_head_out_bwd',
+    'effdet_drop_connect_scales', 'effdet_philox4x32_10', 'effdet_preprocess_batch', 'effdet_finalize_dets', 'effdet_voc_match', 'effdet_voc_ap', 'effdet_voc_ap_workspace_bytes',
+    'effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes', 'effdet_head_out_bwd',
     'effdet_nhwc_to_nchw_f32', 'effdet_nchw_f32_to_nhwc', 'effdet_pad_rows', 'effdet_to_split', 'effdet_to_split2', 'effdet_version', 'effdet_abi_version',
 ]
 
@@ -115,10 +116,22 @@ def lib():
         _lib.effdet_version.restype = C.c_char_p
         for name in ('effdet_num_anchors', 'effdet_nms_workspace_bytes', 'effdet_loss_workspace_bytes',
                      'effdet_conv2d_wgrad_workspace_bytes', 'effdet_dwconv_wgrad_workspace_bytes', 'effdet_dwconv_bwd_workspace_bytes',
-                     'effdet_se_gate_bwd_workspace_floats', 'effdet_voc_ap_workspace_bytes'):
+                     'effdet_se_gate_bwd_workspace_floats', 'effdet_voc_ap_workspace_bytes', 'effdet_coco_slots',
+                     'effdet_coco_accumulate_workspace_bytes'):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_longlong
     return _lib
+
+
+def require(*names):
+    """-> lib(), after checking that it exports every one of names: a library built before an additive entry point (same ABI
+    generation, fewer symbols) is refused with the rebuild message instead of a ctypes AttributeError at the call."""
+    L = lib()
+    missing = [n for n in names if not hasattr(L, n)]
+    if missing:
+        raise RuntimeError('%s does not export %s: it predates this binding, rebuild it (`python -m efficientdet.pytorch_amd.build`)'
+                           % (LIB_PATH, ', '.join(missing)))
+    return L
 
 
 def check(status, what):

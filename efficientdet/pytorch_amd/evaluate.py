@@ -7,7 +7,8 @@ MS-COCO result dicts {'image_id', 'category_id', 'score', 'bbox': [x, y, w, h]}.
 
 The VOC metric itself (eval.py:165-257 `evaluate` after `_get_detections`) runs on the device too: ``VOCMeanAP`` keeps one record per
 detection slot on the GPU across the dataset (csrc/voc_map.hip) and the host receives the per-class APs once, in ``compute``;
-``evaluate_voc`` is the drop-in for ``evaluate(generator, model)``."""
+``evaluate_voc`` is the drop-in for ``evaluate(generator, model)``.  The COCO box metric (pycocotools' ``COCOeval`` as eval.py:260-338
+`evaluate_coco` runs it) is on the device the same way: ``COCOMeanAP`` (csrc/coco_map.hip) and the drop-in ``evaluate_coco``."""
 import numpy as np
 import torch
 
@@ -238,3 +239,210 @@ def evaluate_voc(generator, model, iou_threshold=0.5, score_threshold=0.05, max_
         print('{}: {}'.format(generator.label_to_name(label), average_precisions[label][0]))
     print('avg mAP: {}'.format(mean))
     return mean, average_precisions
+
+
+# ------------------------------------------------------------------------------------------------ COCO box metric
+# COCOeval's default Params for iouType='bbox', computed the way COCOeval computes them (np.linspace: iouThrs[8] is
+# 0.8999999999999999, and 10 of the 101 recThrs differ from i / 100)
+COCO_IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+COCO_REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+COCO_AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], dtype=np.float64)
+COCO_AREA_LBL = ['all', 'small', 'medium', 'large']
+COCO_MAX_DETS = [1, 10, 100]
+# summarize()'s 12 rows: (ap, iouThr or None, area label, index into maxDets)
+_COCO_SUMMARY = [(1, None, 'all', 2), (1, .5, 'all', 2), (1, .75, 'all', 2), (1, None, 'small', 2), (1, None, 'medium', 2),
+                 (1, None, 'large', 2), (0, None, 'all', 0), (0, None, 'all', 1), (0, None, 'all', 2), (0, None, 'small', 2),
+                 (0, None, 'medium', 2), (0, None, 'large', 2)]
+
+
+def summarize_lines(stats):
+    """The 12 lines COCOeval.summarize() prints for these stats (default Params)."""
+    lines = []
+    for (ap, thr, area, mi), v in zip(_COCO_SUMMARY, stats):
+        iou = '{:0.2f}:{:0.2f}'.format(COCO_IOU_THRS[0], COCO_IOU_THRS[-1]) if thr is None else '{:0.2f}'.format(thr)
+        lines.append(' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'.format(
+            'Average Precision' if ap else 'Average Recall', '(AP)' if ap else '(AR)', iou, area, COCO_MAX_DETS[mi], v))
+    return lines
+
+
+class COCOMeanAP:
+    """pycocotools' COCOeval (iouType='bbox', default Params, useCats=1) accumulated on the device.
+
+    ``add(dets, counts, image_ids, gt)`` matches one batch of finalize_dets' xywh rows (category index in column 5, rows of an image
+    score-descending) against its ground truth and appends the records of the detections COCOeval would keep (the first 100 per
+    image and category) to a device buffer -- no device->host transfer.  ``image_ids`` are host integers in [0, 2^31), each seen
+    once per accumulation.  ``gt`` is either a list of per-image [g, 7] arrays (x, y, w, h, category index, iscrowd, annotation
+    area; annotation order) or a device tensor [B, G, 7] fp64 whose rows with a category outside [0, num_categories) are padding.
+    ``compute()`` returns ``stats`` (np.float64[12], summarize()'s order); ``compute(full=True)`` also returns
+    ``{'precision': [T, R, K, A, M], 'recall': [T, K, A, M]}`` as ``COCOeval.eval`` holds them.
+
+    Deviations from COCOeval: a matched detection is flagged rather than labelled with the matched GT's annotation id (COCOeval
+    reads id 0 as "no match", which COCO's positive ids never produce); no ``eval['scores']``; the category list is the
+    ``num_categories`` indices (evaluate_coco maps the dataset's sorted category ids onto them)."""
+
+    INITIAL_CAPACITY = 1 << 16            # records; the buffers double when a batch does not fit
+
+    def __init__(self, num_categories, device=None):
+        num_categories = int(num_categories)
+        if not 1 <= num_categories <= ops.COCO_MAX_CATEGORIES:
+            raise ValueError('num_categories must be in [1, %d], got %d' % (ops.COCO_MAX_CATEGORIES, num_categories))
+        self.num_categories = num_categories
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.reset()
+
+    def reset(self):
+        self.num_records = 0
+        self.max_image_id = 0
+        self._seen = set()
+        self._rec = self._alloc(self.INITIAL_CAPACITY)
+        self._npig = torch.zeros((self.num_categories, len(COCO_AREA_RNG)), dtype=torch.int32, device=self.device)
+
+    def _alloc(self, n):
+        return tuple(torch.empty(n, dtype=dt, device=self.device)
+                     for dt in (torch.int64, torch.int32, torch.uint8, torch.int64, torch.int64))   # key, image, rank, match, ignore
+
+    @property
+    def capacity(self):
+        return self._rec[0].numel()
+
+    def _reserve(self, need):
+        cap = self.capacity
+        if need <= cap:
+            return
+        while cap < need:
+            cap *= 2
+        rec = self._alloc(cap)
+        for new, old in zip(rec, self._rec):
+            new[:self.num_records].copy_(old[:self.num_records])          # device to device, stream-ordered
+        self._rec = rec
+
+    def _image_ids(self, image_ids, B):
+        if torch.is_tensor(image_ids) and image_ids.device.type != 'cpu':
+            raise ValueError('image_ids must be host integers (the meter checks them for duplicates)')
+        ids = np.asarray(image_ids).reshape(-1)
+        if ids.shape[0] != B:
+            raise ValueError('%d image ids for %d images' % (ids.shape[0], B))
+        if ids.size and (ids.dtype.kind not in 'iu' and not np.all(ids == np.floor(ids))):
+            raise ValueError('image ids must be integers')
+        ids = ids.astype(np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= 2 ** 31):
+            raise ValueError('image ids must be in [0, 2^31)')
+        if len(set(ids.tolist())) != B or self._seen.intersection(ids.tolist()):
+            raise ValueError('an image id was added twice')
+        return ids
+
+    def _ground_truth(self, gt, B):
+        K = self.num_categories
+        if torch.is_tensor(gt):
+            if gt.dim() != 3 or gt.shape[0] != B or gt.shape[2] != 7:
+                raise ValueError('device ground truth must be [B, G, 7], got %s' % (tuple(gt.shape),))
+            if gt.dtype != torch.float64:
+                raise ValueError('device ground truth must be float64')
+            g = gt.to(self.device).contiguous()
+        else:
+            if len(gt) != B:
+                raise ValueError('%d ground-truth arrays for %d images' % (len(gt), B))
+            rows = []
+            for a in gt:
+                a = np.asarray(a, dtype=np.float64)
+                if a.size == 0:
+                    a = a.reshape(0, 7)
+                if a.ndim != 2 or a.shape[1] != 7:
+                    raise ValueError('ground truth per image must be [n, 7] (x, y, w, h, category, iscrowd, area), got %s' % (a.shape,))
+                c = a[:, 4]
+                if not np.all((c >= 0) & (c < K) & (c == np.floor(c))):
+                    raise ValueError('ground-truth category out of range [0, %d)' % K)
+                rows.append(a)
+            G = max([1] + [len(a) for a in rows])
+            if G > ops.COCO_MAX_GT:
+                raise ValueError('at most %d ground-truth rows per image, got %d' % (ops.COCO_MAX_GT, G))
+            h = np.zeros((B, G, 7), dtype=np.float64)
+            h[:, :, 4] = -1
+            for i, a in enumerate(rows):
+                h[i, :len(a)] = a
+            g = torch.from_numpy(h).to(self.device)
+        if g.shape[1] > ops.COCO_MAX_GT:
+            raise ValueError('at most %d ground-truth rows per image, got %d' % (ops.COCO_MAX_GT, g.shape[1]))
+        if g.shape[1] == 0:                                         # (the kernel wants G >= 1: one padding row)
+            g = torch.zeros((B, 1, 7), dtype=torch.float64, device=self.device)
+            g[:, :, 4] = -1
+        return g
+
+    def add(self, dets, counts, image_ids, gt):
+        """dets [B, max_det, 6] fp32 (x, y, w, h, score, category index) and counts [B] (device tensors); image_ids: B host ints;
+        gt: see the class docstring."""
+        dets = torch.as_tensor(dets).to(self.device, torch.float32).contiguous()
+        counts = torch.as_tensor(counts).to(self.device, torch.int32).contiguous()
+        if dets.dim() != 3 or dets.shape[2] != 6 or counts.dim() != 1 or counts.shape[0] != dets.shape[0]:
+            raise ValueError('dets must be [B, max_det, 6] with counts [B], got %s and %s' % (tuple(dets.shape), tuple(counts.shape)))
+        B, M = int(dets.shape[0]), int(dets.shape[1])
+        ids = self._image_ids(image_ids, B)
+        g = self._ground_truth(gt, B)
+        if B == 0:
+            return
+        if M == 0:                                                  # no detection rows: the ground truth still counts
+            dets = torch.zeros((B, 1, 6), dtype=torch.float32, device=self.device)
+            counts = torch.zeros(B, dtype=torch.int32, device=self.device)
+            M = 1
+        S = ops.coco_slots(M, self.num_categories, COCO_MAX_DETS[-1])
+        self._reserve(self.num_records + B * S)
+        n = self.num_records
+        ops.coco_match(dets, counts, torch.from_numpy(ids.astype(np.int32)).to(self.device), g, self.num_categories, COCO_IOU_THRS,
+                       COCO_AREA_RNG, COCO_MAX_DETS[-1], tuple(t[n:] for t in self._rec), self._npig)
+        self.num_records = n + B * S
+        self._seen.update(ids.tolist())
+        self.max_image_id = max(self.max_image_id, int(ids.max()))
+
+    def compute(self, full=False):
+        """-> stats (np.float64[12]); with full=True -> (stats, {'precision', 'recall'}) in COCOeval.eval's shapes."""
+        precision, recall, stats = ops.coco_accumulate(self._rec, self.num_records, self.max_image_id, self._npig, self.num_categories,
+                                                       COCO_IOU_THRS, COCO_REC_THRS, len(COCO_AREA_RNG), COCO_MAX_DETS)
+        host = stats.cpu().numpy()                                  # the one device->host copy: 12 doubles
+        if not full:
+            return host
+        return host, {'precision': precision.cpu().numpy(), 'recall': recall.cpu().numpy()}
+
+
+def evaluate_coco(dataset, model, threshold=0.05, batch_size=1):
+    """Drop-in for eval.py:260-338 `evaluate_coco(dataset, model, threshold)`: the same dataset protocol (len, [i] -> {'img' HWC,
+    'scale'}, image_ids, label_to_coco_label, coco) and the same 12 summary lines; detections, matching, accumulation and the
+    summary on the device.  Returns the 12 stats (the reference returns None), or None without a summary when no image has a
+    detection, as the reference does.  The ground truth is read through coco.getCatIds / getAnnIds(imgIds=[id]) / loadAnns:
+    every annotation (crowd and sub-pixel boxes included) with its bbox, category_id, iscrowd and area.  No results JSON is
+    written: a submission still goes through detections_batched(..., xywh=True) and coco_results.  batch_size > 1 batches
+    consecutive images of the same size."""
+    model.eval()
+    p = next(model.parameters(), None)
+    device = p.device if p is not None else torch.device('cuda', torch.cuda.current_device())
+    coco = dataset.coco
+    cat_ids = sorted(coco.getCatIds())
+    cat_index = {c: i for i, c in enumerate(cat_ids)}
+    meter = COCOMeanAP(len(cat_ids), device)
+    lut, total = None, torch.zeros((), dtype=torch.int64, device=device)
+    with torch.no_grad():
+        for batch in _image_batches(dataset, max(1, int(batch_size))):
+            x = torch.stack([img.permute(2, 0, 1) for _, img, _ in batch]).to(device).float().contiguous()
+            cls, reg, anc = model.forward_raw(x)
+            if lut is None:                                         # model label -> index into the sorted category ids (-1: none)
+                lut = torch.tensor([cat_index.get(dataset.label_to_coco_label(c), -1) for c in range(int(cls.shape[-1]))],
+                                   dtype=torch.float32, device=device)
+            s, l, b, count = postprocess(model, cls, reg, anc, int(x.shape[2]), int(x.shape[3]))
+            sc = torch.as_tensor(np.asarray([sc for _, _, sc in batch], dtype=np.float32), device=device)
+            dets, counts = ops.finalize_dets(s, l, b, count, sc, threshold, int(s.shape[1]), True)     # uncapped, as the reference
+            lab = dets[:, :, 5]
+            dets[:, :, 5] = torch.where(lab >= 0, lut[lab.clamp(min=0).long()], lab)
+            total += counts.sum()
+            ids = [int(dataset.image_ids[i]) for i, _, _ in batch]
+            gts = []
+            for iid in ids:
+                rows = [[*a['bbox'], cat_index[a['category_id']], a['iscrowd'], a['area']]
+                        for a in coco.loadAnns(coco.getAnnIds(imgIds=[iid])) if a['category_id'] in cat_index]
+                gts.append(np.asarray(rows, dtype=np.float64).reshape(-1, 7))
+            meter.add(dets, counts, ids, gts)
+    if int(total) == 0:
+        return None
+    stats = meter.compute()
+    for line in summarize_lines(stats):
+        print(line)
+    model.train()
+    return stats

@@ -7,6 +7,7 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1253,6 +1254,66 @@ def voc_ap(rec_key, rec_tp, num_records, gt_count, num_classes):
                                   C.c_longlong(ws.numel()), L.ptr(out[0]), L.ptr(out[1]), L.ptr(recall), L.ptr(precision), L.ptr(seg),
                                   L.stream_ptr()), 'effdet_voc_ap')
     return out, recall[:N], precision[:N], seg
+
+
+COCO_MAX_GT = 2048                 # GT rows per image effdet_coco_match stages in LDS
+COCO_MAX_CATEGORIES = 1024
+_COCO = ('effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes')
+
+
+def coco_slots(max_det, num_categories, max_dets_last=100):
+    """Records effdet_coco_match writes per image: min(max_det, max_dets_last * num_categories)."""
+    return int(L.require(*_COCO).effdet_coco_slots(int(max_det), int(num_categories), int(max_dets_last)))
+
+
+def coco_match(dets, counts, image_ids, gt, num_categories, iou_thrs, area_rng, max_dets_last, rec, npig):
+    """COCO matching of one batch: dets [B,max_det,6] fp32 (x, y, w, h, score, category index) + counts [B] int32, image_ids [B] int32,
+    gt [B,G,7] fp64 (x, y, w, h, category index (-1 = pad), iscrowd, area); iou_thrs [T] / area_rng [A,2] fp64 numpy arrays.
+    rec: (key int64, image int32, rank uint8, match int64, ignore int64) views of at least B * coco_slots(...) records each;
+    adds to npig [num_categories, A] int32."""
+    Lb = L.require(*_COCO)
+    B, max_det = int(dets.shape[0]), int(dets.shape[1])
+    G = int(gt.shape[1])
+    it = np.ascontiguousarray(iou_thrs, dtype=np.float64)
+    ar = np.ascontiguousarray(area_rng, dtype=np.float64).reshape(-1, 2)
+    S = coco_slots(max_det, num_categories, max_dets_last)
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.shape[2] == 6
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == B
+    assert image_ids.dtype == torch.int32 and image_ids.is_contiguous() and image_ids.numel() == B
+    assert gt.dtype == torch.float64 and gt.is_contiguous() and tuple(gt.shape) == (B, G, 7)
+    key, img, rank, match, ignore = rec
+    assert key.dtype == torch.int64 and img.dtype == torch.int32 and rank.dtype == torch.uint8
+    assert match.dtype == torch.int64 and ignore.dtype == torch.int64
+    assert min(t.numel() for t in rec) >= B * S and all(t.is_contiguous() for t in rec)
+    assert npig.dtype == torch.int32 and npig.is_contiguous() and npig.numel() == num_categories * len(ar)
+    L.check(Lb.effdet_coco_match(L.ptr(dets), L.ptr(counts), L.ptr(image_ids), L.ptr(gt), B, max_det, G, int(num_categories),
+                                 it.ctypes.data_as(C.POINTER(C.c_double)), len(it), ar.ctypes.data_as(C.POINTER(C.c_double)), len(ar),
+                                 int(max_dets_last), L.ptr(key), L.ptr(img), L.ptr(rank), L.ptr(match), L.ptr(ignore), L.ptr(npig),
+                                 L.stream_ptr()), 'effdet_coco_match')
+    return B * S
+
+
+def coco_accumulate(rec, num_records, max_image_id, npig, num_categories, iou_thrs, rec_thrs, num_areas, max_dets):
+    """accumulate + summarize over the first num_records records -> (precision [T,R,K,A,M] fp64, recall [T,K,A,M] fp64, stats [12]
+    fp64), all on the device."""
+    Lb = L.require(*_COCO)
+    dev = npig.device
+    N, K = int(num_records), int(num_categories)
+    it = np.ascontiguousarray(iou_thrs, dtype=np.float64)
+    rt = np.ascontiguousarray(rec_thrs, dtype=np.float64)
+    md = np.ascontiguousarray(max_dets, dtype=np.int32)
+    T, R, A, M = len(it), len(rt), int(num_areas), len(md)
+    ws = torch.empty(int(Lb.effdet_coco_accumulate_workspace_bytes(C.c_longlong(N), K)), dtype=torch.uint8, device=dev)
+    precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+    stats = torch.empty(12, dtype=torch.float64, device=dev)
+    key, img, rank, match, ignore = rec
+    L.check(Lb.effdet_coco_accumulate(L.ptr(key), L.ptr(img), L.ptr(rank), L.ptr(match), L.ptr(ignore), C.c_longlong(N),
+                                      C.c_uint(int(max_image_id)), L.ptr(npig), K, it.ctypes.data_as(C.POINTER(C.c_double)), T,
+                                      rt.ctypes.data_as(C.POINTER(C.c_double)), R, A, md.ctypes.data_as(C.POINTER(C.c_int)), M,
+                                      L.ptr(ws), C.c_longlong(ws.numel()), L.ptr(precision), L.ptr(recall), L.ptr(stats),
+                                      L.stream_ptr()), 'effdet_coco_accumulate')
+    return precision, recall, stats
 
 
 def head_out_bwd(dprob, prob, dreg, dtype):

@@ -634,6 +634,41 @@ int effdet_voc_ap(const unsigned long long* rec_key, const unsigned char* rec_tp
                   int num_classes, void* workspace, long long workspace_bytes, double* ap, double* num_annotations,
                   double* recall, double* precision, int* seg, effdet_stream_t stream);
 
+/* Device-side COCO box mean AP (pycocotools' COCOeval, iouType='bbox', useCats=1), matching half (evaluate / evaluateImg), over
+ * effdet_finalize_dets' xywh rows of a batch:
+ *   dets [B][max_det][6] fp32 (x, y, w, h, score, label = category index) + counts [B] (the first counts[b] rows of image b,
+ *   score-descending); image_ids [B] in [0, 2^31), distinct across everything one accumulation sees;
+ *   gt [B][G][7] fp64 (x, y, w, h, category index, iscrowd, annotation area; a category outside [0, num_categories) = padding),
+ *   1 <= G <= 2048, in annotation order; iou_thrs [T] (T <= 16) and area_rng [A][2] (A <= 4, both ends inclusive) are HOST arrays.
+ * A detection row is kept when its label is a category index and its rank among the image's rows of that category, in row
+ * order, is < max_dets_last (<= 100).  Matching is evaluateImg's greedy walk per (threshold t, area a) with maskApi.c's fp64
+ * IoU (x + w recomputed in fp64, a crowd GT's union = the detection's area); a matched detection is flagged, not labelled with
+ * the GT's annotation id.  Image b owns records [b * S, (b + 1) * S), S = effdet_coco_slots(max_det, num_categories,
+ * max_dets_last): its kept rows in (category, rank) order -- rec_key = (category << 32) | descending-score key, rec_image,
+ * rec_rank, rec_match / rec_ignore bit (a * T + t) -- then padding records (category num_categories, rank 255).  ADDS the
+ * image's non-ignored GTs to npig[num_categories][A] (integer atomics).  No workspace. */
+long long effdet_coco_slots(int max_det, int num_categories, int max_dets_last);
+int effdet_coco_match(const float* dets, const int* counts, const int* image_ids, const double* gt, int B, int max_det, int G,
+                      int num_categories, const double* iou_thrs, int num_iou_thrs, const double* area_rng, int num_areas,
+                      int max_dets_last, unsigned long long* rec_key, unsigned* rec_image, unsigned char* rec_rank,
+                      unsigned long long* rec_match, unsigned long long* rec_ignore, int* npig, effdet_stream_t stream);
+
+/* Device-side COCO box mean AP, scoring half (accumulate and summarize) over num_records records of effdet_coco_match:
+ * a stable sort by (category, descending score, image id) -- ties within one image keep record (= rank) order; max_image_id
+ * bounds every record's image id --, then per (category k, area a, max_dets[m], threshold t) the records of rank < max_dets[m]:
+ * exact integer TP / FP cumsums, recall = tp / npig, precision = tp / ((fp + tp) + 2^-52), the envelope from the right and the
+ * rec_thrs lookups (searchsorted 'left', 0 past the end).  Writes precision [T][R][K][A][M] and recall [T][K][A][M] fp64 in
+ * COCOeval.eval's layout (-1 where npig[k][a] == 0) and stats[12] (summarize's means over the entries > -1, -1 when none,
+ * reduced in a fixed order).  iou_thrs [T <= 16], rec_thrs [R <= 128] and max_dets [M <= 3] are HOST arrays; num_categories
+ * <= 1024.  workspace: effdet_coco_accumulate_workspace_bytes(num_records, num_categories) bytes. */
+long long effdet_coco_accumulate_workspace_bytes(long long num_records, int num_categories);
+int effdet_coco_accumulate(const unsigned long long* rec_key, const unsigned* rec_image, const unsigned char* rec_rank,
+                           const unsigned long long* rec_match, const unsigned long long* rec_ignore, long long num_records,
+                           unsigned max_image_id, const int* npig, int num_categories, const double* iou_thrs, int num_iou_thrs,
+                           const double* rec_thrs, int num_rec_thrs, int num_areas, const int* max_dets, int num_max_dets,
+                           void* workspace, long long workspace_bytes, double* precision, double* recall, double* stats,
+                           effdet_stream_t stream);
+
 /* Gradient of the head outputs (models/retinahead.py:119-127 under autograd):  dlogit = dprob * p * (1 - p) and dreg,
  * both stored in `dtype` for the head's data-gradient convs.  ncls / nreg: element counts. */
 int effdet_head_out_bwd(const float* dprob, const float* prob, const float* dreg, void* dlogit, void* dreg_out, int dtype,
