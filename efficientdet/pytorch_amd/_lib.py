@@ -94,6 +94,7 @@ SYMBOLS = [
     'effdet_clip_adamw_step', 'effdet_opt_chunk',
     'effdet_drop_connect_scales', 'effdet_philox4x32_10', 'effdet_preprocess_batch', 'effdet_finalize_dets', 'effdet_voc_match', 'effdet_voc_ap', 'effdet_voc_ap_workspace_bytes',
     'effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes', 'effdet_head_out_bwd',
+    'effdet_augment_train', 'effdet_augment_resize', 'effdet_augment_boxes',
     'effdet_nhwc_to_nchw_f32', 'effdet_nchw_f32_to_nhwc', 'effdet_pad_rows', 'effdet_to_split', 'effdet_to_split2', 'effdet_version', 'effdet_abi_version',
 ]
 

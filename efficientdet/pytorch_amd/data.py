@@ -6,6 +6,8 @@ one async H2D copy; bilinear resize to the common size, /255, mean/std normalisa
 NHWC / compute-dtype / channel-padded pack the stem conv reads, and the annotation rescale all happen on the GPU
 (csrc/pipeline.hip::preprocess_kernel).  The float64 512x512x3 canvas of augmentation.py:111, the NCHW permute of the
 collater and the model-side NCHW -> NHWC repack disappear.  There is no CPU fallback: the collater needs the GPU."""
+import math
+
 import numpy as np
 import torch
 
@@ -40,12 +42,12 @@ class DeviceCollater:
             self._stage[s] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
         return s, self._stage[s]
 
-    def __call__(self, samples):
-        B = len(samples)
+    def _stage_images(self, samples):
+        """Concatenate the decoded images into a pinned staging buffer -> (pinned bytes, slot, offsets [B+1] int64, hw [B,2] int32)."""
         imgs = [np.ascontiguousarray(s['img']) for s in samples]
         for im in imgs:
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError('DeviceCollater takes decoded uint8 HWC RGB images')
+                raise ValueError('%s takes decoded uint8 HWC RGB images' % type(self).__name__)
         sizes = [im.size for im in imgs]
         offs = np.concatenate([[0], np.cumsum([(n + 15) // 16 * 16 for n in sizes])]).astype(np.int64)
         slot, stage = self._pinned(int(offs[-1]))
@@ -53,18 +55,170 @@ class DeviceCollater:
         for im, o, n in zip(imgs, offs[:-1], sizes):
             view[o:o + n] = im.reshape(-1)
         hw = np.array([[im.shape[0], im.shape[1]] for im in imgs], dtype=np.int32)
-        flips = (self.rng.rand(B) < self.flip_x).astype(np.uint8) if self.flip_x > 0 else None
-        M = max(1, max((len(s['annot']) for s in samples), default=0))
-        ann = np.full((B, M, 5), -1.0, dtype=np.float32)                    # collater's padding (augmentation.py:78-86)
-        for b, s in enumerate(samples):
-            a = np.asarray(s['annot'], dtype=np.float32).reshape(-1, 5)
-            ann[b, :len(a)] = a
+        return stage, slot, offs, hw
+
+    def _upload_images(self, stage, slot, offs, hw):
+        """One async H2D copy of the staged bytes (the slot's event guards its reuse) -> (src, src_off, src_hw) on the device."""
         dev = self.device
         src = stage[:int(offs[-1])].to(dev, non_blocking=True)
         ev = torch.cuda.Event(); ev.record(); self._evt[slot] = ev
         d_off = torch.from_numpy(offs[:-1].copy()).to(dev, non_blocking=True)
         d_hw = torch.from_numpy(hw).to(dev, non_blocking=True)
+        return src, d_off, d_hw
+
+    @staticmethod
+    def _padded_annots(samples):
+        M = max(1, max((len(s['annot']) for s in samples), default=0))
+        ann = np.full((len(samples), M, 5), -1.0, dtype=np.float32)         # collater's padding (augmentation.py:78-86)
+        for b, s in enumerate(samples):
+            a = np.asarray(s['annot'], dtype=np.float32).reshape(-1, 5)
+            ann[b, :len(a)] = a
+        return ann
+
+    def __call__(self, samples):
+        B = len(samples)
+        stage, slot, offs, hw = self._stage_images(samples)
+        flips = (self.rng.rand(B) < self.flip_x).astype(np.uint8) if self.flip_x > 0 else None
+        ann = self._padded_annots(samples)
+        dev = self.device
+        src, d_off, d_hw = self._upload_images(stage, slot, offs, hw)
         d_flip = torch.from_numpy(flips).to(dev, non_blocking=True) if flips is not None else None
         d_ann = torch.from_numpy(ann).to(dev, non_blocking=True)
         m, scale = ops.preprocess_batch(src, d_off, d_hw, self.S, self.dtype, chunk_elems(self.dtype), MEAN, STD, d_flip, d_ann)
         return PackedImages(m), d_ann, scale
+
+
+# ------------------------------------------------------------------------------------------------ get_augumentation on the device
+# Columns of the per-image parameter table (include/effdet_hip.h, EFFDET_AUG_P).
+AUG_COLUMNS = ('rrc', 'crop_y', 'crop_x', 'crop_h', 'crop_w', 'flip', 'flip_code', 'transpose', 'color', 'alpha', 'beta', 'gamma',
+               'shift', 'r_shift', 'g_shift', 'b_shift', 'hue_shift', 'sat_shift', 'val_shift', 'clahe', 'clip_limit', 'hflip', 'vflip')
+AUG = {n: i for i, n in enumerate(AUG_COLUMNS)}
+COLOR_BRIGHTNESS_CONTRAST, COLOR_GAMMA, COLOR_NOOP = 1, 2, 3       # 'color' column (0: the OneOf did not fire)
+SHIFT_RGB, SHIFT_HSV, SHIFT_NOOP = 1, 2, 3                         # 'shift' column
+
+
+def _one_of(rng, member_p=(0.5, 0.5, 0.5), p=0.5):
+    """albumentations OneOf: fires with probability p, then picks a member by its normalised probability -> 0 or 1 + member."""
+    if rng.rand() >= p:
+        return 0
+    q = np.asarray(member_p, dtype=np.float64)
+    return 1 + int(rng.choice(len(q), p=q / q.sum()))
+
+
+def sample_augment_table(rng, B, S):
+    """Draw the 'train' parameters of B images on an S x S canvas from rng (np.random.RandomState) -> [B, len(AUG_COLUMNS)] fp32.
+
+    Order per image: RandomResizedCrop (p 0.3; up to 10 attempts with area scale U(0.08, 1) and log-uniform ratio in (3/4, 4/3),
+    then the centre-crop fallback, which on the square canvas is the whole canvas), Flip (p 0.5, code U{-1, 0, 1}), Transpose
+    (p 0.5), OneOf[RandomBrightnessContrast(0.5, 0.4), RandomGamma(50, 150), NoOp] (p 0.5, members 1/3 each; alpha = 1 + U(-0.4,
+    0.4), beta = U(-0.5, 0.5), gamma = U(50, 150) / 100), OneOf[RGBShift(20, 15, 15), HueSaturationValue(5, 5, 20), NoOp] (same
+    rule), CLAHE (p 0.8, clip U(1, 4)), HorizontalFlip (p 0.5), VerticalFlip (p 0.5).  A parameter is drawn only when its
+    transform fires.  This is not albumentations' random stream (matching it is a non-goal), only its distributions."""
+    t = np.zeros((B, len(AUG_COLUMNS)), dtype=np.float32)
+    for b in range(B):
+        r = t[b]
+        if rng.rand() < 0.3:
+            area = float(S * S)
+            y = x = 0; h = w = S
+            for _ in range(10):
+                target = rng.uniform(0.08, 1.0) * area
+                ratio = math.exp(rng.uniform(math.log(3 / 4), math.log(4 / 3)))
+                cw, ch = int(round(math.sqrt(target * ratio))), int(round(math.sqrt(target / ratio)))
+                if 0 < cw <= S and 0 < ch <= S:
+                    h, w = ch, cw
+                    y, x = rng.randint(0, S - h + 1), rng.randint(0, S - w + 1)
+                    break
+            r[[AUG['rrc'], AUG['crop_y'], AUG['crop_x'], AUG['crop_h'], AUG['crop_w']]] = (1, y, x, h, w)
+        if rng.rand() < 0.5:
+            r[AUG['flip']], r[AUG['flip_code']] = 1, rng.randint(-1, 2)
+        if rng.rand() < 0.5:
+            r[AUG['transpose']] = 1
+        c = r[AUG['color']] = _one_of(rng)
+        if c == COLOR_BRIGHTNESS_CONTRAST:
+            r[AUG['alpha']] = 1.0 + rng.uniform(-0.4, 0.4)
+            r[AUG['beta']] = rng.uniform(-0.5, 0.5)
+        elif c == COLOR_GAMMA:
+            r[AUG['gamma']] = rng.uniform(50, 150) / 100.0
+        s = r[AUG['shift']] = _one_of(rng)
+        if s == SHIFT_RGB:
+            r[AUG['r_shift']], r[AUG['g_shift']], r[AUG['b_shift']] = rng.uniform(-20, 20), rng.uniform(-15, 15), rng.uniform(-15, 15)
+        elif s == SHIFT_HSV:
+            r[AUG['hue_shift']], r[AUG['sat_shift']], r[AUG['val_shift']] = rng.uniform(-5, 5), rng.uniform(-5, 5), rng.uniform(-20, 20)
+        if rng.rand() < 0.8:
+            r[AUG['clahe']], r[AUG['clip_limit']] = 1, rng.uniform(1, 4)
+        r[AUG['hflip']] = rng.rand() < 0.5
+        r[AUG['vflip']] = rng.rand() < 0.5
+    return t
+
+
+def check_augment_table(table, B, S):
+    """Refuse a table the chain cannot mean: wrong shape, or a crop that is not an integer box inside the S x S canvas."""
+    t = np.asarray(table, dtype=np.float32)
+    if t.shape != (B, len(AUG_COLUMNS)):
+        raise ValueError('augmentation table must be [%d, %d], got %s' % (B, len(AUG_COLUMNS), t.shape))
+    crop = t[t[:, AUG['rrc']] != 0][:, [AUG['crop_y'], AUG['crop_x'], AUG['crop_h'], AUG['crop_w']]]
+    if len(crop) and (np.any(crop != np.round(crop)) or np.any(crop[:, 2:] < 1) or np.any(crop[:, :2] < 0)
+                      or np.any(crop[:, 0] + crop[:, 2] > S) or np.any(crop[:, 1] + crop[:, 3] > S)):
+        raise ValueError('RandomResizedCrop boxes must be integer windows inside the %d x %d canvas' % (S, S))
+    codes = t[t[:, AUG['flip']] != 0][:, AUG['flip_code']]
+    if np.any(~np.isin(codes, (-1, 0, 1))):
+        raise ValueError('Flip codes are -1, 0 or 1')
+    return t
+
+
+class DeviceAugmentation(DeviceCollater):
+    """get_augumentation(phase, width, height, min_area, min_visibility) + detection_collate (datasets/augmentation.py:8-67) on the
+    device: ``images, annotations, params = aug(samples)``.
+
+    samples: as for DeviceCollater ({'img': uint8 [H,W,3] RGB, 'annot': [n,5] pascal_voc boxes + label}).  Returns
+    PackedImages (NHWC, `dtype`, the stem conv's layout), annotations [B,M,5] fp32 with each image's kept boxes first in their
+    input order and -1 rows after (None for 'test'), and params: for 'train' the device table [B, len(AUG_COLUMNS)] that drove
+    the chain, for 'valid' / 'test' the per-axis scales [B,2] = (width / w, height / h) (boxes / scale map back to the image).
+    M = max(1, most boxes kept by one image); trim=False keeps M = max(1, longest input list) instead, which spares the
+    device-to-host read of the kept counts.  The reference's detection_collate can return M = 0; this never does.
+    ``aug(samples, table=...)`` runs 'train' with an explicit table (numpy or tensor, columns AUG_COLUMNS).
+
+    The host draws the table (sample_augment_table) and copies the uint8 bytes; every pixel and box operation runs in
+    csrc/augment.hip.  'train' needs width == height (the reference's transpose and crop assume a square output)."""
+
+    PHASES = ('train', 'valid', 'test')
+
+    def __init__(self, phase='train', width=512, height=512, min_area=0., min_visibility=0., dtype=torch.bfloat16, device='cuda',
+                 seed=0, trim=True):
+        if phase not in self.PHASES:
+            raise ValueError('phase must be one of %s' % (self.PHASES,))
+        if phase == 'train' and (width != height or width < 8):
+            raise ValueError("the 'train' chain needs width == height >= 8 (got %d x %d)" % (width, height))
+        super().__init__(common_size=width, dtype=dtype, device=device, seed=seed)
+        self.phase, self.W, self.H = phase, int(width), int(height)
+        self.min_area, self.min_visibility, self.trim = float(min_area), float(min_visibility), bool(trim)
+
+    def __call__(self, samples, table=None, stages=None):
+        """stages: optional dict that receives the uint8 intermediates of ops.augment_train / ops.augment_resize (tests)."""
+        B = len(samples)
+        stage, slot, offs, hw = self._stage_images(samples)
+        if self.phase == 'train':
+            if table is None:
+                table = sample_augment_table(self.rng, B, self.S)
+            elif not torch.is_tensor(table) or table.device.type == 'cpu':
+                table = check_augment_table(table.numpy() if torch.is_tensor(table) else table, B, self.S)
+        elif table is not None:
+            raise ValueError("an explicit table only applies to the 'train' phase")
+        ann = self._padded_annots(samples) if self.phase != 'test' else None
+        dev = self.device
+        src, d_off, d_hw = self._upload_images(stage, slot, offs, hw)
+        if self.phase == 'train':
+            params = (table if torch.is_tensor(table) else torch.from_numpy(table)).to(dev, torch.float32, non_blocking=True).contiguous()
+            m = ops.augment_train(src, d_off, d_hw, params, self.S, self.dtype, chunk_elems(self.dtype), MEAN, STD, stages)
+        else:
+            scale = np.stack([self.W / hw[:, 1].astype(np.float64), self.H / hw[:, 0].astype(np.float64)], 1).astype(np.float32)
+            params = torch.from_numpy(scale).to(dev, non_blocking=True)
+            m = ops.augment_resize(src, d_off, d_hw, self.H, self.W, self.dtype, chunk_elems(self.dtype), MEAN, STD, stages)
+        if ann is None:
+            return PackedImages(m), None, params
+        d_ann = torch.from_numpy(ann).to(dev, non_blocking=True)
+        out, counts = ops.augment_boxes(d_hw, params if self.phase == 'train' else None, self.H, self.W, d_ann, self.min_area,
+                                        self.min_visibility)
+        if self.trim:
+            out = out[:, :max(1, int(counts.max()))].contiguous()
+        return PackedImages(m), out, params

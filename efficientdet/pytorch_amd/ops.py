@@ -1328,3 +1328,62 @@ def head_out_bwd(dprob, prob, dreg, dtype):
 def tuning_set(key, value):
     """Kernel-selection knob of the library (speed only; see effdet_tuning_set in include/effdet_hip.h) -> previous value."""
     return int(L.lib().effdet_tuning_set(int(key), int(value)))
+
+
+_AUG = ('effdet_augment_train', 'effdet_augment_resize', 'effdet_augment_boxes')
+AUG_P = 23                         # EFFDET_AUG_P: columns of the per-image augmentation table
+
+
+def _norm_consts(mean, std):
+    """albumentations' Normalize constants: mean * 255 and 1 / (std * 255), each step in fp32."""
+    m = np.asarray(mean, dtype=np.float32) * np.float32(255.0)
+    inv = np.reciprocal(np.asarray(std, dtype=np.float32) * np.float32(255.0), dtype=np.float32)
+    return (C.c_float * 3)(*[float(v) for v in m]), (C.c_float * 3)(*[float(v) for v in inv])
+
+
+def augment_train(src_u8, src_off, src_hw, table, S, dtype, cpad, mean, std, stages=None):
+    """'train' chain of get_augumentation: uint8 HWC images (concatenated, device) + table [B, AUG_P] fp32 (device) ->
+    Map [B,S,S,cpad].  stages: optional dict that receives the uint8 intermediates 'a' (LongestMaxSize + pad) and 'b'
+    (crop / flips / transpose / colour, 4th byte = CLAHE's L) as [B,S,S,4] tensors and the CLAHE LUTs 'lut' [B,64,256]."""
+    B = int(src_hw.shape[0])
+    dev = src_u8.device
+    assert table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (B, AUG_P)
+    out = Map.new(B, S, S, cpad, dtype, dev)
+    sa = torch.empty((B, S, S, 4), dtype=torch.uint8, device=dev)
+    sb = torch.empty((B, S, S, 4), dtype=torch.uint8, device=dev)
+    lut = torch.empty((B, 64, 256), dtype=torch.uint8, device=dev)
+    m, inv = _norm_consts(mean, std)
+    L.check(L.require(*_AUG).effdet_augment_train(L.ptr(src_u8), L.ptr(src_off), L.ptr(src_hw), L.ptr(table), B, int(S), L.ptr(sa),
+                                                  L.ptr(sb), L.ptr(lut), L.ptr(out.t), L.dtype_code(dtype), cpad, m, inv,
+                                                  L.stream_ptr()), 'effdet_augment_train')
+    if stages is not None:
+        stages.update(a=sa, b=sb, lut=lut)
+    return out
+
+
+def augment_resize(src_u8, src_off, src_hw, H, W, dtype, cpad, mean, std, stages=None):
+    """'valid' / 'test' chain: Resize(H, W) + Normalize -> Map [B,H,W,cpad]; stages['a'] = the resized uint8 [B,H,W,4] if asked."""
+    B = int(src_hw.shape[0])
+    dev = src_u8.device
+    out = Map.new(B, H, W, cpad, dtype, dev)
+    sa = torch.empty((B, H, W, 4), dtype=torch.uint8, device=dev) if stages is not None else None
+    m, inv = _norm_consts(mean, std)
+    L.check(L.require(*_AUG).effdet_augment_resize(L.ptr(src_u8), L.ptr(src_off), L.ptr(src_hw), B, int(H), int(W), L.ptr(sa),
+                                                   L.ptr(out.t), L.dtype_code(dtype), cpad, m, inv, L.stream_ptr()),
+            'effdet_augment_resize')
+    if stages is not None:
+        stages.update(a=sa)
+    return out
+
+
+def augment_boxes(src_hw, table, H, W, annots, min_area=0.0, min_visibility=0.0):
+    """Boxes [B,M,5] fp32 (label -1 = padding) through the chain's geometry (table None: the stretch resize to H x W), clipped and
+    filtered -> (annots_out [B,M,5] with the kept rows first and -1 after, counts [B] int32)."""
+    B, M = int(annots.shape[0]), int(annots.shape[1])
+    assert annots.dtype == torch.float32 and annots.is_contiguous() and annots.shape[2] == 5
+    out = torch.empty_like(annots)
+    counts = torch.empty(B, dtype=torch.int32, device=annots.device)
+    L.check(L.require(*_AUG).effdet_augment_boxes(L.ptr(src_hw), L.ptr(table), B, int(H), int(W), L.ptr(annots), M,
+                                                  C.c_double(min_area), C.c_double(min_visibility), L.ptr(out), L.ptr(counts),
+                                                  L.stream_ptr()), 'effdet_augment_boxes')
+    return out, counts

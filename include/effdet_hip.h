@@ -669,6 +669,31 @@ int effdet_coco_accumulate(const unsigned long long* rec_key, const unsigned* re
                            void* workspace, long long workspace_bytes, double* precision, double* recall, double* stats,
                            effdet_stream_t stream);
 
+/* Device-side get_augumentation (datasets/augmentation.py:8-50), on the input layout of effdet_preprocess_batch (uint8 RGB HWC
+ * images of mixed sizes, concatenated, src_off / src_hw).  Every random decision of the 'train' chain is a column of a per-image
+ * fp32 table [B][EFFDET_AUG_P] drawn on the host:
+ *   0 RRC (0 / 1), 1-4 crop y, x, height, width (integers, inside the S x S canvas), 5 Flip (0 / 1), 6 its cv2 code (-1 / 0 / 1),
+ *   7 Transpose, 8 colour op (0 off, 1 brightness / contrast, 2 gamma, 3 NoOp), 9 alpha, 10 beta, 11 gamma,
+ *   12 shift op (0 off, 1 RGB shift, 2 HSV shift, 3 NoOp), 13-15 r / g / b shift, 16-18 hue / sat / val shift,
+ *   19 CLAHE (0 / 1), 20 its clip limit, 21 HorizontalFlip, 22 VerticalFlip.
+ * effdet_augment_train: LongestMaxSize(S) + centred PadIfNeeded into stage_a, crop resample + Flip + Transpose + colour LUTs /
+ * HSV shift into stage_b (R, G, B, L of the CLAHE input), CLAHE tile LUTs into clahe_lut, then CLAHE + LAB -> RGB +
+ * HorizontalFlip + VerticalFlip + (v - mean255) * inv_std255 packed into out_nhwc [B][S][S][Cpad] (`dtype`, channels >= 3 zero).
+ * stage_a / stage_b: [B][S][S][4] uint8, clahe_lut: [B][64][256] uint8.  S >= 8.
+ * effdet_augment_resize ('valid' / 'test'): Resize(H, W) + Normalize + pack; stage_a (may be NULL): [B][H][W][4] uint8 copy.
+ * effdet_augment_boxes: annots [B][M][5] (label -1 = padding row) through the geometric steps of `table` (NULL: the stretch
+ * resize to H x W), clipped to the image, dropped when the unclipped area is 0, clipped / unclipped < min_visibility or the
+ * clipped area <= min_area; kept rows keep their order at the front of annots_out [B][M][5], the rest -1; counts [B] int32. */
+#define EFFDET_AUG_P 23
+int effdet_augment_train(const unsigned char* src, const long long* src_off, const int* src_hw, const float* table, int B, int S,
+                         unsigned char* stage_a, unsigned char* stage_b, unsigned char* clahe_lut, void* out_nhwc, int dtype, int Cpad,
+                         const float mean255[3], const float inv_std255[3], effdet_stream_t stream);
+int effdet_augment_resize(const unsigned char* src, const long long* src_off, const int* src_hw, int B, int H, int W,
+                          unsigned char* stage_a, void* out_nhwc, int dtype, int Cpad, const float mean255[3], const float inv_std255[3],
+                          effdet_stream_t stream);
+int effdet_augment_boxes(const int* src_hw, const float* table, int B, int H, int W, const float* annots, int M, double min_area,
+                         double min_visibility, float* annots_out, int* counts, effdet_stream_t stream);
+
 /* Gradient of the head outputs (models/retinahead.py:119-127 under autograd):  dlogit = dprob * p * (1 - p) and dreg,
  * both stored in `dtype` for the head's data-gradient convs.  ncls / nreg: element counts. */
 int effdet_head_out_bwd(const float* dprob, const float* prob, const float* dreg, void* dlogit, void* dreg_out, int dtype,
