@@ -222,8 +222,6 @@ __global__ __launch_bounds__(256) void fuse_weight_bwd_kernel(const float* wraw,
     if (relu_bwd_(wraw[i * wcols + col], 1.f) != 0.f) dwraw[i * wcols + col] += ti * (d[i] - dot);
 }
 
-inline int grid_for(long long n, int cap = 4096) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > cap ? cap : g)); }
-
 }  // namespace
 
 extern "C" int effdet_bifpn_fuse_fwd2(const void* a, const void* b, const void* c, void* out, void* out_hsplit, const float* wraw, int wrows,

@@ -20,6 +20,7 @@
 //     from the right) and, at each point where recall steps, the recThrs it answers (searchsorted 'left').  A last launch reduces
 //     the 12 summary statistics in a fixed order.  Every launch geometry follows from the arguments alone.
 #include "common.h"
+#include "block_scan.h"
 #include "radix_sort.h"
 #include <limits.h>
 #include <math.h>
@@ -27,6 +28,7 @@
 namespace {
 
 constexpr int COCO_MAX_GT = 2048;           // GT rows per image staged in LDS (as VOC_MAX_GT)
+constexpr size_t COCO_GT_LDS = 4 * sizeof(double) + sizeof(unsigned long long) + sizeof(int);     // bytes per GT row: box, gtm, gflag
 constexpr int COCO_MAX_CATEGORIES = 1024;   // categories; the category occupies 10 bits of the sort key (2 passes above 255)
 constexpr int COCO_MAX_T = 16, COCO_MAX_A = 4, COCO_MAX_M = 3, COCO_MAX_R = 128, COCO_MAX_DETS = 100;
 
@@ -42,13 +44,6 @@ struct CocoAccParams {
   int max_dets[COCO_MAX_M];
   int T, R, A, M;
 };
-
-// descending-score key of an fp32 score (voc_score_key / nms_keys32_kernel's transform)
-__device__ __forceinline__ unsigned coco_score_key(float s) {
-  unsigned u = __float_as_uint(s);
-  u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
-  return ~u;
-}
 
 __device__ __forceinline__ bool coco_label(float lf, int K, int& c) {
   c = (int)lf;
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(256) void coco_match_kernel(const float* __restrict
         const unsigned long long bm = __ballot(active && matched), bi = __ballot(active && ignored);
         if (lane == 0) {
           const long long o = out0 + rank;
-          rec_key[o] = ((unsigned long long)c << 32) | coco_score_key(row[4]);
+          rec_key[o] = ((unsigned long long)c << 32) | rs_score_key(row[4]);
           rec_image[o] = iid;
           rec_rank[o] = (unsigned char)rank;
           rec_match[o] = bm;
@@ -201,15 +196,6 @@ __global__ __launch_bounds__(256) void coco_match_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ accumulate
-__global__ __launch_bounds__(256) void coco_sort_init_kernel(const unsigned* __restrict__ rec_image, unsigned* __restrict__ ka,
-                                                             unsigned* __restrict__ va, long long N, int* __restrict__ seg, int K) {
-  const long long n = N > 2LL * K ? N : 2LL * K;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    if (i < N) { ka[i] = rec_image[i]; va[i] = (unsigned)i; }
-    if (i < 2LL * K) seg[i] = 0;
-  }
-}
-
 // the (category, score) key of every record in image-id order
 __global__ __launch_bounds__(256) void coco_key_gather_kernel(const unsigned long long* __restrict__ rec_key, const unsigned* __restrict__ v,
                                                               unsigned long long* __restrict__ k64, long long N) {
@@ -226,38 +212,8 @@ __global__ __launch_bounds__(256) void coco_segments_kernel(const unsigned long 
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
     const unsigned r = v[i];
     s_rank[i] = rec_rank[r]; s_match[i] = rec_match[r]; s_ignore[i] = rec_ignore[r];
-    const unsigned c = (unsigned)(skey[i] >> 32);
-    if (c >= (unsigned)K) continue;
-    if (i == 0 || (unsigned)(skey[i - 1] >> 32) != c) seg[2 * c] = (int)i;
-    if (i == N - 1 || (unsigned)(skey[i + 1] >> 32) != c) seg[2 * c + 1] = (int)(i + 1);
+    rs_segment_bounds(skey, i, N, K, seg);
   }
-}
-
-// block-wide inclusive scans over threadIdx order (256 threads = 4 waves); *total = the whole block's result
-__device__ __forceinline__ unsigned long long coco_scan_sum(unsigned long long x, unsigned long long* wtot, unsigned long long* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = __shfl_up(x, o, 64); if (lane >= o) x += t; }
-  if (lane == 63) wtot[wave] = x;
-  __syncthreads();
-  unsigned long long pre = 0;
-  for (int w = 0; w < wave; ++w) pre += wtot[w];
-  *total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-  __syncthreads();
-  return x + pre;
-}
-
-__device__ __forceinline__ double coco_scan_max(double x, double* wtot, double* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const double t = __shfl_up(x, o, 64); if (lane >= o) x = fmax(x, t); }
-  if (lane == 63) wtot[wave] = x;
-  __syncthreads();
-  double pre = 0.0;                                              // (every value is >= 0)
-  for (int w = 0; w < wave; ++w) pre = fmax(pre, wtot[w]);
-  *total = fmax(fmax(wtot[0], wtot[1]), fmax(wtot[2], wtot[3]));
-  __syncthreads();
-  return fmax(x, pre);
 }
 
 // first index r of the sorted x[0..R) with x[r] > v
@@ -338,14 +294,14 @@ __global__ __launch_bounds__(256) void coco_accumulate_kernel(const int* __restr
         if (!ig) v = mt ? (1ull << 32) : 1ull;
       }
       unsigned long long ctot;
-      const unsigned long long suf = carry + coco_scan_sum(v, itot, &ctot);     // sum over positions >= i
+      const unsigned long long suf = carry + block_scan_sum(v, itot, &ctot);    // sum over positions >= i
       const unsigned long long after = suf - v;                                  // sum over positions > i
       const long long tp = TP - (long long)(after >> 32);
       const long long fp = (long long)(tot & 0xffffffffull) - (long long)(after & 0xffffffffull);
       const double dtp = (double)tp;
       const double pr = incl ? dtp / (((double)fp + dtp) + 2.220446049250313e-16) : 0.0;
       double mtot;
-      const double e = fmax(coco_scan_max(pr, dtot, &mtot), env);
+      const double e = fmax(block_scan_max(pr, dtot, &mtot), env);
       if (incl) {
         const double rc = dtp / np_;
         const int r_lo = (i == (long long)first) ? 0 : coco_upper(rthr, R, (double)(tp - (long long)(v >> 32)) / np_);
@@ -406,37 +362,21 @@ __global__ __launch_bounds__(256) void coco_stats_kernel(const double* __restric
   if (tid == 0) stats[s] = scnt[0] ? ssum[0] / (double)scnt[0] : -1.0;
 }
 
-inline int coco_grid(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-inline size_t coco_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct CocoWs {
-  unsigned long long *ka, *kb, *s_match, *s_ignore;
-  unsigned *va, *vb, *hist;
+  RsBufs<unsigned long long> rs;
+  unsigned long long *s_match, *s_ignore;
   unsigned char* s_rank;
   int* seg;
-  int T;
 };
 
 size_t coco_carve(CocoWs& w, void* base, long long N, int K) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* p = base ? (char*)base + off : nullptr; off += coco_al(bytes); return p; };
+  Carver c(base);
   const size_t n = (size_t)(N > 0 ? N : 1);
-  w.T = (int)((n + RS_TILE - 1) / RS_TILE);
-  w.ka = (unsigned long long*)take(n * 8); w.kb = (unsigned long long*)take(n * 8);
-  w.va = (unsigned*)take(n * 4); w.vb = (unsigned*)take(n * 4);
-  w.hist = (unsigned*)take((size_t)256 * w.T * 4);
-  w.s_match = (unsigned long long*)take(n * 8); w.s_ignore = (unsigned long long*)take(n * 8);
-  w.s_rank = (unsigned char*)take(n);
-  w.seg = (int*)take((size_t)2 * (K > 0 ? K : 1) * 4);
-  return off;
-}
-
-template <typename Key>
-void coco_sort_pass(Key* ki, unsigned* vi, Key* ko, unsigned* vo, unsigned* hist, long long N, int T, int shift, hipStream_t st) {
-  hipLaunchKernelGGL((rs_hist_kernel<Key>), dim3(T, 1), dim3(256), 0, st, (const Key*)ki, hist, N, T, shift);
-  hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(256), 0, st, hist, T);
-  hipLaunchKernelGGL((rs_scatter_kernel<Key>), dim3(T, 1), dim3(256), 0, st, (const Key*)ki, (const unsigned*)vi, ko, vo,
-                     (const unsigned*)hist, N, T, shift);
+  rs_carve(w.rs, c, 1, n);
+  w.s_match = c.take<unsigned long long>(n); w.s_ignore = c.take<unsigned long long>(n);
+  w.s_rank = c.take<unsigned char>(n);
+  w.seg = c.take<int>((size_t)2 * (K > 0 ? K : 1));
+  return c.off;
 }
 
 }  // namespace
@@ -457,8 +397,8 @@ extern "C" int effdet_coco_match(const float* dets, const int* counts, const int
   for (int a = 0; a < 2 * num_areas; ++a) P.rng[a] = area_rng[a];
   P.T = num_iou_thrs; P.A = num_areas; P.max_det_last = max_dets_last;
   const long long S = effdet_coco_slots(max_det, K, max_dets_last);
-  const size_t lds = (size_t)G * (4 * sizeof(double) + sizeof(unsigned long long) + sizeof(int)) + (size_t)(5 * K + 3) * sizeof(int);
-  EFFDET_SET_MAX_LDS(coco_match_kernel, (size_t)COCO_MAX_GT * 44 + (size_t)(5 * COCO_MAX_CATEGORIES + 3) * sizeof(int));
+  const size_t lds = (size_t)G * COCO_GT_LDS + (size_t)(5 * K + 3) * sizeof(int);
+  EFFDET_SET_MAX_LDS(coco_match_kernel, (size_t)COCO_MAX_GT * COCO_GT_LDS + (size_t)(5 * COCO_MAX_CATEGORIES + 3) * sizeof(int));
   hipLaunchKernelGGL(coco_match_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dets, counts, image_ids, gt, max_det, G, K, (int)S, P,
                      rec_key, rec_image, rec_rank, rec_match, rec_ignore, npig);
   EFFDET_CHECK_LAUNCH();
@@ -501,32 +441,22 @@ extern "C" int effdet_coco_accumulate(const unsigned long long* rec_key, const u
   }
   P.T = num_iou_thrs; P.R = num_rec_thrs; P.A = num_areas; P.M = num_max_dets;
   hipStream_t st = (hipStream_t)stream;
-  unsigned* ia = (unsigned*)w.ka;                                // the image-id passes use the key buffers as 32-bit keys
-  unsigned* ib = (unsigned*)w.kb;
-  hipLaunchKernelGGL(coco_sort_init_kernel, dim3(coco_grid(N > 2LL * K ? N : 2LL * K)), dim3(256), 0, st, rec_image, ia, w.va, N,
+  unsigned* ia = (unsigned*)w.rs.ka;                             // the image-id passes use the key buffers as 32-bit keys
+  unsigned* ib = (unsigned*)w.rs.kb;
+  hipLaunchKernelGGL(rs_init_kernel<unsigned>, dim3(grid_for(N > 2LL * K ? N : 2LL * K)), dim3(256), 0, st, rec_image, ia, w.rs.va, N,
                      w.seg, K);
   EFFDET_CHECK_LAUNCH();
-  unsigned *vi = w.va, *vo = w.vb;
+  unsigned *vi = w.rs.va, *vo = w.rs.vb;
   if (N > 0) {
     const int id_passes = max_image_id == 0u ? 0 : (max_image_id < 0x100u ? 1 : (max_image_id < 0x10000u ? 2 : (max_image_id < 0x1000000u ? 3 : 4)));
-    for (int pass = 0; pass < id_passes; ++pass) {
-      coco_sort_pass<unsigned>(ia, vi, ib, vo, w.hist, N, w.T, pass * 8, st);
-      EFFDET_CHECK_LAUNCH();
-      unsigned* t = ia; ia = ib; ib = t;
-      unsigned* u = vi; vi = vo; vo = u;
-    }
+    if (const int rc = rs_sort(ia, vi, ib, vo, w.rs.hist, 1, N, w.rs.T, 0, id_passes, st)) return rc;
     // (category, score) keys in image-id order (only the permutation vi of the image-id passes is still needed)
-    unsigned long long *ki = w.ka, *ko = w.kb;
-    hipLaunchKernelGGL(coco_key_gather_kernel, dim3(coco_grid(N)), dim3(256), 0, st, rec_key, (const unsigned*)vi, ki, N);
+    unsigned long long *ki = w.rs.ka, *ko = w.rs.kb;
+    hipLaunchKernelGGL(coco_key_gather_kernel, dim3(grid_for(N)), dim3(256), 0, st, rec_key, (const unsigned*)vi, ki, N);
     EFFDET_CHECK_LAUNCH();
     const int passes = 4 + (K <= 255 ? 1 : 2);                   // category values 0..K (K = padding record)
-    for (int pass = 0; pass < passes; ++pass) {
-      coco_sort_pass<unsigned long long>(ki, vi, ko, vo, w.hist, N, w.T, pass * 8, st);
-      EFFDET_CHECK_LAUNCH();
-      unsigned long long* t = ki; ki = ko; ko = t;
-      unsigned* u = vi; vi = vo; vo = u;
-    }
-    hipLaunchKernelGGL(coco_segments_kernel, dim3(coco_grid(N)), dim3(256), 0, st, (const unsigned long long*)ki, (const unsigned*)vi,
+    if (const int rc = rs_sort(ki, vi, ko, vo, w.rs.hist, 1, N, w.rs.T, 0, passes, st)) return rc;
+    hipLaunchKernelGGL(coco_segments_kernel, dim3(grid_for(N)), dim3(256), 0, st, (const unsigned long long*)ki, (const unsigned*)vi,
                        rec_rank, rec_match, rec_ignore, N, K, w.seg, w.s_rank, w.s_match, w.s_ignore);
     EFFDET_CHECK_LAUNCH();
   }

@@ -29,6 +29,21 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     }                                                                                                               \
   } while (0)
 
+// workgroups of 256 threads for a grid-stride loop over n elements: at least 1, at most cap
+inline int grid_for(long long n, int cap = 4096) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > cap ? cap : g)); }
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Hands out 256-byte aligned buffers of one workspace in call order; base == nullptr only adds up the sizes (`off` = bytes needed).
+struct Carver {
+  char* base; size_t off;
+  explicit Carver(void* b) : base((char*)b), off(0) {}
+  template <typename T> T* take(size_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += al256(count * sizeof(T));
+    return p;
+  }
+};
+
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // fp32 -> bf16, round-to-nearest-even, through the native v_cvt_pk_bf16_f32 (one instruction per PAIR; the software
 // rounding sequence was ~6 VALU per value and made the conv epilogues VALU-bound)

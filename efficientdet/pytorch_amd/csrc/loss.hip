@@ -350,26 +350,26 @@ inline void zero_stat(const LossK& k, int B, hipStream_t st) {
   hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((B * SS + 255) / 256)), dim3(256), 0, st, k.stat, B * SS);
 }
 
-inline int grid_for(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // workgroups per image of the assign pass / upper bound of the class pass (either kernel: dld <= 9*nc + 63)
 static inline long long assign_blocks(long long A) { return (A + 255) / 256; }
 static inline long long cls_blocks_max(long long A, int nc) { return ((A * nc + 3) / 4 + (A / 9 + 1) * 16 + 1023) / 1024 + 1; }
 
-extern "C" long long effdet_loss_workspace_bytes(int B, long long A, int num_classes) {
-  return (long long)(al((size_t)B * A * 4) + al((size_t)B * SS * 4) + al((size_t)B * assign_blocks(A) * 4) +
-                     al((size_t)B * cls_blocks_max(A, num_classes) * 4));
+// assign [B][A], stat [B][SS], part_reg [B][na], part_cls [B][cls_blocks_max] -> bytes (num_classes only sizes the last buffer)
+static size_t carve_loss(LossK& k, void* ws, int B, long long A, int num_classes = 0) {
+  Carver c(ws);
+  k.assign = c.take<int>((size_t)B * A);
+  k.stat = c.take<float>((size_t)B * SS);
+  k.part_reg = c.take<float>((size_t)B * assign_blocks(A));
+  k.part_cls = c.take<float>((size_t)B * cls_blocks_max(A, num_classes));
+  k.na = (int)assign_blocks(A);
+  return c.off;
 }
 
-static void carve_loss(LossK& k, void* ws, int B, long long A) {
-  k.assign = (int*)ws;
-  k.stat = (float*)((char*)ws + al((size_t)B * A * 4));
-  k.part_reg = (float*)((char*)k.stat + al((size_t)B * SS * 4));
-  k.part_cls = (float*)((char*)k.part_reg + al((size_t)B * assign_blocks(A) * 4));
-  k.na = (int)assign_blocks(A);
+extern "C" long long effdet_loss_workspace_bytes(int B, long long A, int num_classes) {
+  LossK k{};
+  return (long long)carve_loss(k, nullptr, B, A, num_classes);
 }
 
 extern "C" int effdet_focal_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots,

@@ -210,7 +210,8 @@ __global__ void to_split_kernel(const float* __restrict__ src, split_t* __restri
     store4(dst + i * 4, *(const f32x4*)(src + i * 4));
 }
 
-inline int grid_for(long long n, int block = 256) {
+// (as common.h's grid_for with a clamp of 2048 workgroups)
+inline int pack_grid(long long n, int block = 256) {
   long long g = (n + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
@@ -232,12 +233,12 @@ extern "C" int effdet_pack_conv_weight(const float* w, const float* scale, void*
   const long long n = mode == 0 ? (long long)Cout * Cin_pad * KH * KW : (long long)Cin * Cin_pad * KH * KW;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == EFFDET_F32)
-    hipLaunchKernelGGL(pack_w_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, w, scale, (float*)out, mode, Cout, Cin, KH, KW, Cin_pad);
+    hipLaunchKernelGGL(pack_w_kernel<float>, dim3(pack_grid(n)), dim3(256), 0, st, w, scale, (float*)out, mode, Cout, Cin, KH, KW, Cin_pad);
   else if (dtype == EFFDET_BF16)
-    hipLaunchKernelGGL(pack_w_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, w, scale, (bf16_t*)out, mode, Cout, Cin, KH, KW, Cin_pad);
+    hipLaunchKernelGGL(pack_w_kernel<bf16_t>, dim3(pack_grid(n)), dim3(256), 0, st, w, scale, (bf16_t*)out, mode, Cout, Cin, KH, KW, Cin_pad);
   else if (dtype == EFFDET_F32_BF16X3) {
     if (((long long)Cin_pad * KH * KW) % 32) return EFFDET_EUNSUPPORTED;
-    hipLaunchKernelGGL((pack_w_kernel<float, true>), dim3(grid_for(n)), dim3(256), 0, st, w, scale, (float*)out, mode, Cout, Cin, KH, KW, Cin_pad);
+    hipLaunchKernelGGL((pack_w_kernel<float, true>), dim3(pack_grid(n)), dim3(256), 0, st, w, scale, (float*)out, mode, Cout, Cin, KH, KW, Cin_pad);
   } else if (dtype == EFFDET_F32_HSPLIT) {
     // f16x3 forward operand: f16 hi | lo pairs of the row-scaled weights + the row scales (see pack_h3_slice)
     const long long K = (long long)Cin_pad * KH * KW;
@@ -339,8 +340,8 @@ extern "C" int effdet_unpack_conv_wgrad_bn(const float* g, const float* scale, c
 extern "C" int effdet_nhwc_to_nchw_f32(const void* x, float* y, int dtype, int B, int H, int W, int C, effdet_stream_t stream) {
   const long long n = (long long)B * H * W * C;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EFFDET_F32) hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)x, y, B, H * W, C);
-  else hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, (const bf16_t*)x, y, B, H * W, C);
+  if (dtype == EFFDET_F32) hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(pack_grid(n)), dim3(256), 0, st, (const float*)x, y, B, H * W, C);
+  else hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(pack_grid(n)), dim3(256), 0, st, (const bf16_t*)x, y, B, H * W, C);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
@@ -351,13 +352,13 @@ extern "C" int effdet_nchw_f32_to_nhwc(const float* x, void* y, int dtype, int B
   const int ce = dtype == EFFDET_F32 ? 4 : 8;
   if (Cpad == ce && C <= ce) {
     const long long np = (long long)B * H * W;
-    if (dtype == EFFDET_F32) hipLaunchKernelGGL(nchw_to_nhwc_chunk_kernel<float>, dim3(grid_for(np)), dim3(256), 0, st, x, (float*)y, B, H * W, C);
-    else hipLaunchKernelGGL(nchw_to_nhwc_chunk_kernel<bf16_t>, dim3(grid_for(np)), dim3(256), 0, st, x, (bf16_t*)y, B, H * W, C);
+    if (dtype == EFFDET_F32) hipLaunchKernelGGL(nchw_to_nhwc_chunk_kernel<float>, dim3(pack_grid(np)), dim3(256), 0, st, x, (float*)y, B, H * W, C);
+    else hipLaunchKernelGGL(nchw_to_nhwc_chunk_kernel<bf16_t>, dim3(pack_grid(np)), dim3(256), 0, st, x, (bf16_t*)y, B, H * W, C);
     EFFDET_CHECK_LAUNCH();
     return EFFDET_OK;
   }
-  if (dtype == EFFDET_F32) hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, x, (float*)y, B, H * W, C, Cpad);
-  else hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, x, (bf16_t*)y, B, H * W, C, Cpad);
+  if (dtype == EFFDET_F32) hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(pack_grid(n)), dim3(256), 0, st, x, (float*)y, B, H * W, C, Cpad);
+  else hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(pack_grid(n)), dim3(256), 0, st, x, (bf16_t*)y, B, H * W, C, Cpad);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
@@ -367,8 +368,8 @@ extern "C" int effdet_pad_rows(const void* src, void* dst, int dtype, long long 
   if (!src || !dst || Cpad < C) return EFFDET_EINVAL;
   const long long n = (long long)B * HW * Cpad;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EFFDET_F32) hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)src, (float*)dst, src_off, src_bstride, src_ld, HW, C, Cpad, n);
-  else if (dtype == EFFDET_BF16) hipLaunchKernelGGL(pad_rows_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, src_off, src_bstride, src_ld, HW, C, Cpad, n);
+  if (dtype == EFFDET_F32) hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(pack_grid(n)), dim3(256), 0, st, (const float*)src, (float*)dst, src_off, src_bstride, src_ld, HW, C, Cpad, n);
+  else if (dtype == EFFDET_BF16) hipLaunchKernelGGL(pad_rows_kernel<bf16_t>, dim3(pack_grid(n)), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, src_off, src_bstride, src_ld, HW, C, Cpad, n);
   else return EFFDET_EINVAL;
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;

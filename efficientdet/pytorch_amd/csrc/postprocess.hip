@@ -94,10 +94,10 @@ struct KeptGrid { int* kcount; float4* kcell; int* kover_n; float4* kover; int H
 constexpr int KG_CAP = 8;                 // boxes per cell (NMS keeps same-size boxes in one cell sparse); more go to the overflow list
 
 struct NmsWs {
-  unsigned* vals_in; int* nvalid; int* kept; unsigned* dead; float4* sbox; float4* kbox;
+  int* nvalid; int* kept; unsigned* dead; float4* sbox; float4* kbox;
   KeptGrid kg;                                      // spatial hash of the kept boxes (cross phase, iou_threshold >= 0.5)
-  // round 4: in-tree radix sort (32-bit keys per image, ping-pong) + the multi-workgroup round
-  unsigned *k32a, *k32b, *v32b, *hist; int T;
+  // round 4: in-tree radix sort (32-bit keys per image, ping-pong; rs.va is the first buffer of the workspace) + the multi-workgroup round
+  RsBufs<unsigned> rs;
   unsigned long long* rowbits; float4* surv_box; unsigned* surv_idx; int* surv_n; int RND, NW;
 };
 
@@ -331,10 +331,8 @@ __global__ __launch_bounds__(256) void nms_keys32_kernel(const float* __restrict
     const float s = score[i];
     unsigned k = 0xffffffffu;
     if (s > thr) {
-      unsigned u = __float_as_uint(s);
-      u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;     // ascending-orderable
-      k = ~u;                                         // descending score
-      if (k == 0xffffffffu) k = 0xfffffffeu;
+      k = rs_score_key(s);
+      if (k == 0xffffffffu) k = 0xfffffffeu;          // (0xffffffff is the key of the invalid ones)
       ++mine;
     }
     keys[i] = k; vals[i] = (unsigned)a; dead[i] = 0u;
@@ -528,9 +526,6 @@ __global__ void gather_dets_kernel(const float* __restrict__ boxes, const float*
   }
 }
 
-inline int grid_for(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // candidates per round of the multi-workgroup form: 2048 (D0 @512: 24 rounds), 4096 above 64 k anchors (D4 @1024: 48 rounds);
 // EFFDET_NMS_ROUND overrides (A/B)
 inline int nms_round_size(long long A) {
@@ -541,24 +536,21 @@ inline int nms_round_size(long long A) {
 
 size_t carve(NmsWs& w, void* base, int B, long long A) {
   const size_t n = (size_t)B * A;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* p = base ? (char*)base + off : nullptr; off += al(bytes); return p; };
-  w.vals_in = (unsigned*)take(n * 4);
-  w.dead = (unsigned*)take(n * 4);
-  w.sbox = (float4*)take(n * 16); w.kbox = (float4*)take(n * 16);
-  w.nvalid = (int*)take((size_t)B * 4); w.kept = (int*)take((size_t)B * 4);
+  Carver c(base);
+  w.rs.va = c.take<unsigned>(n);
+  w.dead = c.take<unsigned>(n);
+  w.sbox = c.take<float4>(n); w.kbox = c.take<float4>(n);
+  w.nvalid = c.take<int>(B); w.kept = c.take<int>(B);
   int ht = 1024; while (ht < A / 2) ht <<= 1;      // hash slots per image (kept boxes are a fraction of the candidates), a power of two
   w.kg.HT = ht;
-  w.kg.kcount = (int*)take((size_t)B * ht * 4); w.kg.kover_n = (int*)take((size_t)B * 4);
-  w.kg.kcell = (float4*)take((size_t)B * ht * KG_CAP * 16); w.kg.kover = (float4*)take(n * 16);
+  w.kg.kcount = c.take<int>((size_t)B * ht); w.kg.kover_n = c.take<int>(B);
+  w.kg.kcell = c.take<float4>((size_t)B * ht * KG_CAP); w.kg.kover = c.take<float4>(n);
   // in-tree radix sort (32-bit keys per image, ping-pong) + the multi-workgroup round
-  w.T = (int)((A + RS_TILE - 1) / RS_TILE);
-  w.k32a = (unsigned*)take(n * 4); w.k32b = (unsigned*)take(n * 4); w.v32b = (unsigned*)take(n * 4);
-  w.hist = (unsigned*)take((size_t)B * 256 * w.T * 4);
+  rs_carve(w.rs, c, B, A, false);
   w.RND = nms_round_size(A); w.NW = w.RND / 64;
-  w.rowbits = (unsigned long long*)take((size_t)B * w.NW * w.RND * 8);
-  w.surv_box = (float4*)take((size_t)B * w.RND * 16); w.surv_idx = (unsigned*)take((size_t)B * w.RND * 4); w.surv_n = (int*)take((size_t)B * 4);
-  return off;
+  w.rowbits = c.take<unsigned long long>((size_t)B * w.NW * w.RND);
+  w.surv_box = c.take<float4>((size_t)B * w.RND); w.surv_idx = c.take<unsigned>((size_t)B * w.RND); w.surv_n = c.take<int>(B);
+  return c.off;
 }
 
 }  // namespace
@@ -640,17 +632,10 @@ extern "C" int effdet_nms(const float* boxes, const float* score, float threshol
   // ---- keys, in-tree stable radix sort per image (4 x 8 bits), boxes in sorted order ----
   {
     { long long gx = (A + 2047) / 2048; if (gx > 64) gx = 64;      // (one atomic per workgroup onto nvalid[b]: 32 counters in ONE cache line serialise at ~8 ns each)
-      hipLaunchKernelGGL(nms_keys32_kernel, dim3((unsigned)gx, B), dim3(256), 0, st, score, threshold, w.k32a, w.vals_in, w.nvalid, w.kept, w.dead, A); }
+      hipLaunchKernelGGL(nms_keys32_kernel, dim3((unsigned)gx, B), dim3(256), 0, st, score, threshold, w.rs.ka, w.rs.va, w.nvalid, w.kept, w.dead, A); }
     EFFDET_CHECK_LAUNCH();
-    unsigned *ki = w.k32a, *vi = w.vals_in, *ko = w.k32b, *vo = w.v32b;
-    for (int pass = 0; pass < 4; ++pass) {
-      hipLaunchKernelGGL(rs_hist_kernel<unsigned>, dim3(w.T, B), dim3(256), 0, st, (const unsigned*)ki, w.hist, A, w.T, pass * 8);
-      hipLaunchKernelGGL(rs_scan_kernel, dim3(B), dim3(256), 0, st, w.hist, w.T);
-      hipLaunchKernelGGL(rs_scatter_kernel<unsigned>, dim3(w.T, B), dim3(256), 0, st, (const unsigned*)ki, (const unsigned*)vi, ko, vo, (const unsigned*)w.hist, A, w.T, pass * 8);
-      EFFDET_CHECK_LAUNCH();
-      unsigned* t = ki; ki = ko; ko = t; t = vi; vi = vo; vo = t;
-    }
-    // (4 passes: the sorted pairs are back in k32a / vals_in)
+    unsigned *ki = w.rs.ka, *vi = w.rs.va, *ko = w.rs.kb, *vo = w.rs.vb;
+    if (const int rc = rs_sort(ki, vi, ko, vo, w.rs.hist, B, A, w.rs.T, 0, 4, st)) return rc;
     hipLaunchKernelGGL(nms_gather_kernel, dim3(grid_for(n)), dim3(256), 0, st, boxes, (const unsigned*)vi, w.nvalid, w.sbox, A, B);
     EFFDET_CHECK_LAUNCH();
     // ---- rounds: cross phase (whole GPU) -> survivors + bit-matrix (G workgroups per image) -> greedy resolve (one wave per image) ----

@@ -1,14 +1,23 @@
 // Stable LSD radix sort of (key, uint32 value) pairs in B independent segments of A elements, 8 bits per pass; used by the NMS
-// (32-bit score keys per image, postprocess.hip) and by the VOC metric (64-bit (class, score) keys, one segment, voc_map.hip).
+// (32-bit score keys per image, postprocess.hip), the VOC metric (64-bit (class, score) keys, one segment, voc_map.hip) and the
+// COCO metric (32-bit image ids, then 64-bit (category, score) keys, one segment, coco_map.hip).
 // A pass is three launches: rs_hist_kernel (per-tile digit counts), rs_scan_kernel (per-segment exclusive scan over (digit, tile)
 // in digit-major order) and rs_scatter_kernel (tile-ordered, rank-within-wave ordered stores: stable).  The grid depends on B and
-// A only.
+// A only.  rs_sort drives the passes over the buffers of an RsBufs; rs_score_key makes the score part of a key; the two metrics
+// also share the sort input (rs_init_kernel) and the segment bounds of their sorted 64-bit keys (rs_segment_bounds).
 #pragma once
 #include "common.h"
 
 namespace {
 
 constexpr int RS_TILE = 2048;                    // keys per workgroup and pass
+
+// descending-score key of an fp32 score: ascending radix order of the keys = descending order of the scores
+__device__ __forceinline__ unsigned rs_score_key(float s) {
+  unsigned u = __float_as_uint(s);
+  u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;     // ascending-orderable
+  return ~u;                                      // descending
+}
 
 // hist[b][digit][tile]
 template <typename K>
@@ -78,6 +87,55 @@ __global__ __launch_bounds__(256) void rs_scatter_kernel(const K* __restrict__ k
     cur[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
     __syncthreads();                                                   // (the next chunk zeroes wcnt)
   }
+}
+
+// ping-pong (key, value) buffers, hist [B][256][T] and the tiles per segment
+template <typename K> struct RsBufs { K *ka, *kb; unsigned *va, *vb, *hist; int T; };
+
+// takes ka, kb, (va,) vb, hist in this order; with own_va = false the caller has taken va elsewhere in its workspace
+template <typename K> void rs_carve(RsBufs<K>& s, Carver& c, size_t B, size_t A, bool own_va = true) {
+  s.T = (int)((A + RS_TILE - 1) / RS_TILE);
+  s.ka = c.take<K>(B * A); s.kb = c.take<K>(B * A);
+  if (own_va) s.va = c.take<unsigned>(B * A);
+  s.vb = c.take<unsigned>(B * A);
+  s.hist = c.take<unsigned>(B * 256 * s.T);
+}
+
+// `passes` passes over bits [shift, shift + 8 * passes) of the B segments of A keys; (ki, vi) ends on the sorted pairs and
+// (ko, vo) on the other half of the ping-pong.  -> EFFDET_OK or EFFDET_ELAUNCH
+template <typename K> int rs_sort(K*& ki, unsigned*& vi, K*& ko, unsigned*& vo, unsigned* hist, int B, long long A, int T, int shift,
+                                  int passes, hipStream_t st) {
+  for (int pass = 0; pass < passes; ++pass, shift += 8) {
+    hipLaunchKernelGGL((rs_hist_kernel<K>), dim3(T, B), dim3(256), 0, st, (const K*)ki, hist, A, T, shift);
+    hipLaunchKernelGGL(rs_scan_kernel, dim3(B), dim3(256), 0, st, hist, T);
+    hipLaunchKernelGGL((rs_scatter_kernel<K>), dim3(T, B), dim3(256), 0, st, (const K*)ki, (const unsigned*)vi, ko, vo,
+                       (const unsigned*)hist, A, T, shift);
+    EFFDET_CHECK_LAUNCH();
+    K* t = ki; ki = ko; ko = t;
+    unsigned* u = vi; vi = vo; vo = u;
+  }
+  return EFFDET_OK;
+}
+
+// sort input of the metrics: keys = src, values = record index; and the reset of the per-class segment bounds seg[2 * C]
+template <typename K>
+__global__ __launch_bounds__(256) void rs_init_kernel(const K* __restrict__ src, K* __restrict__ ka, unsigned* __restrict__ va, long long N,
+                                                      int* __restrict__ seg, int C) {
+  const long long n = N > 2LL * C ? N : 2LL * C;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    if (i < N) { ka[i] = src[i]; va[i] = (unsigned)i; }
+    if (i < 2LL * C) seg[i] = 0;
+  }
+}
+
+// sorted position i of N 64-bit keys whose high word is the class: seg[2c], seg[2c + 1] = [first, last + 1) position of class c < C
+// (left at 0, 0 when the class has no records)
+__device__ __forceinline__ void rs_segment_bounds(const unsigned long long* __restrict__ skey, long long i, long long N, int C,
+                                                  int* __restrict__ seg) {
+  const unsigned c = (unsigned)(skey[i] >> 32);
+  if (c >= (unsigned)C) return;
+  if (i == 0 || (unsigned)(skey[i - 1] >> 32) != c) seg[2 * c] = (int)i;
+  if (i == N - 1 || (unsigned)(skey[i + 1] >> 32) != c) seg[2 * c + 1] = (int)(i + 1);
 }
 
 }  // namespace

@@ -5,11 +5,6 @@
 
 namespace {
 
-inline int grid_for(long long n, int block = 256) {
-  long long g = (n + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
-
 // ---- gate = sigmoid(W2 * swish(W1 * mean + b1) + b2); one 1024-thread workgroup per image ----
 // Latency-bound (a few KB of data per image): the win is the LENGTH OF THE DEPENDENT CHAIN, so every stage
 // issues all of its loads before the first use (16 waves, squeezed channels unrolled x3).

@@ -16,21 +16,16 @@
 //     (precision envelope = running max from the right, AP terms (r_k - r_{k-1}) * env_k at the TP positions k), and a fixed
 //     LDS tree over the per-thread partial sums.  Every launch geometry follows from (B, max_det, G, C, N) alone.
 #include "common.h"
+#include "block_scan.h"
 #include "radix_sort.h"
 #include <float.h>
 #include <limits.h>
 
 namespace {
 
-constexpr int VOC_MAX_GT = 2048;              // GT rows per image staged in LDS: 40 bytes each (4 fp64 box, label, claim)
+constexpr int VOC_MAX_GT = 2048;              // GT rows per image staged in LDS
+constexpr size_t VOC_GT_LDS = 4 * sizeof(double) + 2 * sizeof(int);     // bytes per GT row: 4 fp64 box, label, claim
 constexpr int VOC_MAX_CLASSES = 65535;        // class values 0..C fit the two class passes of the sort
-
-// descending-score key of a positive fp32 score (nms_keys32_kernel's transform)
-__device__ __forceinline__ unsigned voc_score_key(float s) {
-  unsigned u = __float_as_uint(s);
-  u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;     // ascending-orderable
-  return ~u;                                      // descending
-}
 
 // compute_overlap(d, gts of class c) and np.argmax, in the reference's fp64 operation order
 __device__ __forceinline__ int voc_assign(const double a0, const double a1, const double a2, const double a3, int c,
@@ -99,7 +94,7 @@ __global__ __launch_bounds__(256) void voc_match_kernel(const float* __restrict_
         double best;
         const int a = voc_assign(r[0], r[1], r[2], r[3], c, gb, gl, G, best);
         tp = (a >= 0 && best >= thr && claim[a] == k) ? 1 : 0;
-        key = ((unsigned long long)c << 32) | voc_score_key(r[4]);
+        key = ((unsigned long long)c << 32) | rs_score_key(r[4]);
       }
     }
     rec_key[o] = key;
@@ -107,51 +102,9 @@ __global__ __launch_bounds__(256) void voc_match_kernel(const float* __restrict_
   }
 }
 
-// sort input (keys + record index) and the reset of the per-class segment bounds
-__global__ __launch_bounds__(256) void voc_sort_init_kernel(const unsigned long long* __restrict__ rec_key, unsigned long long* __restrict__ ka,
-                                                            unsigned* __restrict__ va, long long N, int* __restrict__ seg, int C) {
-  const long long n = N > 2LL * C ? N : 2LL * C;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    if (i < N) { ka[i] = rec_key[i]; va[i] = (unsigned)i; }
-    if (i < 2LL * C) seg[i] = 0;
-  }
-}
-
 // seg[2c], seg[2c + 1] = [first, last + 1) sorted position of class c (0, 0 when the class has no records)
 __global__ __launch_bounds__(256) void voc_segments_kernel(const unsigned long long* __restrict__ skey, long long N, int C, int* __restrict__ seg) {
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
-    const unsigned c = (unsigned)(skey[i] >> 32);
-    if (c >= (unsigned)C) continue;
-    if (i == 0 || (unsigned)(skey[i - 1] >> 32) != c) seg[2 * c] = (int)i;
-    if (i == N - 1 || (unsigned)(skey[i + 1] >> 32) != c) seg[2 * c + 1] = (int)(i + 1);
-  }
-}
-
-// block-wide inclusive scan (sum for int, max for double) over threadIdx order; *total = the whole block's result
-__device__ __forceinline__ int block_scan_sum(int x, int* wtot, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(x, o, 64); if (lane >= o) x += t; }
-  if (lane == 63) wtot[wave] = x;
-  __syncthreads();
-  int pre = 0;
-  for (int w = 0; w < wave; ++w) pre += wtot[w];
-  *total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-  __syncthreads();
-  return x + pre;
-}
-
-__device__ __forceinline__ double block_scan_max(double x, double* wtot, double* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const double t = __shfl_up(x, o, 64); if (lane >= o) x = fmax(x, t); }
-  if (lane == 63) wtot[wave] = x;
-  __syncthreads();
-  double pre = 0.0;                                  // (every value is >= 0)
-  for (int w = 0; w < wave; ++w) pre = fmax(pre, wtot[w]);
-  *total = fmax(fmax(wtot[0], wtot[1]), fmax(wtot[2], wtot[3]));
-  __syncthreads();
-  return fmax(x, pre);
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < N; i += (long long)gridDim.x * 256) rs_segment_bounds(skey, i, N, C, seg);
 }
 
 // one workgroup per class: eval.py:225-241 + _compute_ap on the class's sorted records [seg[2c], seg[2c+1])
@@ -206,20 +159,12 @@ __global__ __launch_bounds__(256) void voc_ap_kernel(const unsigned* __restrict_
   if (tid == 0) { ap[c] = red[0]; num_ann[c] = n; }
 }
 
-inline int voc_grid(long long n) { long long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-inline size_t voc_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct VocWs { unsigned long long *ka, *kb; unsigned *va, *vb, *hist; int T; };
+typedef RsBufs<unsigned long long> VocWs;     // the workspace is the sort's buffers for one segment of max(N, 1) keys
 
 size_t voc_carve(VocWs& w, void* base, long long N) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* p = base ? (char*)base + off : nullptr; off += voc_al(bytes); return p; };
-  const size_t n = (size_t)(N > 0 ? N : 1);
-  w.T = (int)((n + RS_TILE - 1) / RS_TILE);
-  w.ka = (unsigned long long*)take(n * 8); w.kb = (unsigned long long*)take(n * 8);
-  w.va = (unsigned*)take(n * 4); w.vb = (unsigned*)take(n * 4);
-  w.hist = (unsigned*)take((size_t)256 * w.T * 4);
-  return off;
+  Carver c(base);
+  rs_carve(w, c, 1, (size_t)(N > 0 ? N : 1));
+  return c.off;
 }
 
 }  // namespace
@@ -231,8 +176,8 @@ extern "C" int effdet_voc_match(const float* dets, const int* counts, const doub
       num_classes < 1 || num_classes > VOC_MAX_CLASSES)
     return EFFDET_EINVAL;
   if (G > VOC_MAX_GT) return EFFDET_EUNSUPPORTED;
-  const size_t lds = (size_t)G * (4 * sizeof(double) + 2 * sizeof(int));
-  EFFDET_SET_MAX_LDS(voc_match_kernel, (size_t)VOC_MAX_GT * (4 * sizeof(double) + 2 * sizeof(int)));
+  const size_t lds = (size_t)G * VOC_GT_LDS;
+  EFFDET_SET_MAX_LDS(voc_match_kernel, (size_t)VOC_MAX_GT * VOC_GT_LDS);
   hipLaunchKernelGGL(voc_match_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dets, counts, gt_boxes, gt_labels, max_det, G,
                      num_classes, iou_threshold, rec_key, rec_tp, gt_count);
   EFFDET_CHECK_LAUNCH();
@@ -255,22 +200,15 @@ extern "C" int effdet_voc_ap(const unsigned long long* rec_key, const unsigned c
   if ((long long)voc_carve(w, workspace, N) > workspace_bytes) return EFFDET_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int C = num_classes;
-  hipLaunchKernelGGL(voc_sort_init_kernel, dim3(voc_grid(N > 2LL * C ? N : 2LL * C)), dim3(256), 0, st, rec_key, w.ka, w.va, N, seg, C);
+  hipLaunchKernelGGL(rs_init_kernel<unsigned long long>, dim3(grid_for(N > 2LL * C ? N : 2LL * C)), dim3(256), 0, st, rec_key, w.ka, w.va, N,
+                     seg, C);
   EFFDET_CHECK_LAUNCH();
   unsigned long long *ki = w.ka, *ko = w.kb;
   unsigned *vi = w.va, *vo = w.vb;
   if (N > 0) {
     const int passes = 4 + (C <= 255 ? 1 : 2);       // class values 0..C (C = empty slot)
-    for (int pass = 0; pass < passes; ++pass) {
-      hipLaunchKernelGGL((rs_hist_kernel<unsigned long long>), dim3(w.T, 1), dim3(256), 0, st, (const unsigned long long*)ki, w.hist, N, w.T, pass * 8);
-      hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(256), 0, st, w.hist, w.T);
-      hipLaunchKernelGGL((rs_scatter_kernel<unsigned long long>), dim3(w.T, 1), dim3(256), 0, st, (const unsigned long long*)ki,
-                         (const unsigned*)vi, ko, vo, (const unsigned*)w.hist, N, w.T, pass * 8);
-      EFFDET_CHECK_LAUNCH();
-      unsigned long long* t = ki; ki = ko; ko = t;
-      unsigned* u = vi; vi = vo; vo = u;
-    }
-    hipLaunchKernelGGL(voc_segments_kernel, dim3(voc_grid(N)), dim3(256), 0, st, (const unsigned long long*)ki, N, C, seg);
+    if (const int rc = rs_sort(ki, vi, ko, vo, w.hist, 1, N, w.T, 0, passes, st)) return rc;
+    hipLaunchKernelGGL(voc_segments_kernel, dim3(grid_for(N)), dim3(256), 0, st, (const unsigned long long*)ki, N, C, seg);
     EFFDET_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(256), 0, st, (const unsigned*)vi, rec_tp, (const int*)seg, gt_count, recall, precision,

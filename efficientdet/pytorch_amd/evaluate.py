@@ -88,7 +88,79 @@ def coco_results(dets_xywh, counts, image_ids, label_to_coco_label=lambda c: c):
     return res
 
 
-class VOCMeanAP:
+def _check_dets(dets, counts, device):
+    """dets [B, max_det, 6] and counts [B] of finalize_dets -> (fp32 dets, int32 counts), contiguous on device."""
+    dets = torch.as_tensor(dets).to(device, torch.float32).contiguous()
+    counts = torch.as_tensor(counts).to(device, torch.int32).contiguous()
+    if dets.dim() != 3 or dets.shape[2] != 6 or counts.dim() != 1 or counts.shape[0] != dets.shape[0]:
+        raise ValueError('dets must be [B, max_det, 6] with counts [B], got %s and %s' % (tuple(dets.shape), tuple(counts.shape)))
+    return dets, counts
+
+
+def _check_gt_rows(G, max_gt):
+    if G > max_gt:
+        raise ValueError('at most %d ground-truth rows per image, got %d' % (max_gt, G))
+
+
+def _pad_ground_truth(rows, B, cols, what, max_gt, check=None):
+    """B per-image [n, cols] arrays (label in column 4; an empty one counts as (0, cols)) -> fp64 [B, G, cols] with G >= 1 (the
+    kernels want a row: all empty gives one padding row), padding rows zero with label -1.  check(a) sees each image's array."""
+    if len(rows) != B:
+        raise ValueError('%d ground-truth arrays for %d images' % (len(rows), B))
+    arrays = []
+    for a in rows:
+        a = np.asarray(a, dtype=np.float64)
+        if a.size == 0:
+            a = a.reshape(0, cols)
+        if a.ndim != 2 or a.shape[1] != cols:
+            raise ValueError('ground truth per image must be [n, %d] %s, got %s' % (cols, what, a.shape))
+        if check is not None:
+            check(a)
+        arrays.append(a)
+    G = max([1] + [len(a) for a in arrays])
+    _check_gt_rows(G, max_gt)
+    h = np.zeros((B, G, cols), dtype=np.float64)
+    h[:, :, 4] = -1
+    for i, a in enumerate(arrays):
+        h[i, :len(a)] = a
+    return h
+
+
+class _RecordMeter:
+    """What the two meters share: one record per detection slot, held in the 1-D device tensors `_rec` (one per entry of
+    RECORD_DTYPES) that grow by doubling; `num_records` of their `capacity` are filled.  A subclass extends reset()."""
+
+    INITIAL_CAPACITY = 1 << 16            # records; the buffers double when a batch does not fit
+    RECORD_DTYPES = ()
+
+    def __init__(self, device):
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.reset()
+
+    def reset(self):
+        self.num_records = 0
+        self._rec = self._alloc(self.INITIAL_CAPACITY)
+
+    def _alloc(self, n):
+        return tuple(torch.empty(n, dtype=dt, device=self.device) for dt in self.RECORD_DTYPES)
+
+    @property
+    def capacity(self):
+        return self._rec[0].numel()
+
+    def _reserve(self, need):
+        cap = self.capacity
+        if need <= cap:
+            return
+        while cap < need:
+            cap *= 2
+        rec = self._alloc(cap)
+        for new, old in zip(rec, self._rec):
+            new[:self.num_records].copy_(old[:self.num_records])          # device to device, stream-ordered
+        self._rec = rec
+
+
+class VOCMeanAP(_RecordMeter):
     """The reference's VOC metric (eval.py:185-257) accumulated on the device.
 
     ``add(dets, counts, gt)`` matches one batch of finalize_device's rows against its ground truth and appends one record per detection
@@ -99,7 +171,7 @@ class VOCMeanAP:
     ``gt`` is either a list of per-image [n, 5] arrays (x1, y1, x2, y2, label; the generator's load_annotations, (0, 5) allowed) or a
     pair of device tensors (boxes fp64 [B, G, 4], labels int32 [B, G], -1 = pad)."""
 
-    INITIAL_CAPACITY = 1 << 16            # records; the buffer doubles when a batch does not fit
+    RECORD_DTYPES = (torch.int64, torch.uint8)                     # sort key (class << 32 | score key), TP byte
 
     def __init__(self, num_classes, iou_threshold=0.5, device=None):
         num_classes = int(num_classes)
@@ -107,30 +179,11 @@ class VOCMeanAP:
             raise ValueError('num_classes must be in [1, 65535], got %d' % num_classes)
         self.num_classes = num_classes
         self.iou_threshold = float(iou_threshold)
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        self.reset()
+        super().__init__(device)
 
     def reset(self):
-        self.num_records = 0
-        self._key = torch.empty(self.INITIAL_CAPACITY, dtype=torch.int64, device=self.device)
-        self._tp = torch.empty(self.INITIAL_CAPACITY, dtype=torch.uint8, device=self.device)
+        super().reset()
         self._gt_count = torch.zeros(self.num_classes, dtype=torch.int32, device=self.device)
-
-    @property
-    def capacity(self):
-        return self._key.numel()
-
-    def _reserve(self, need):
-        cap = self._key.numel()
-        if need <= cap:
-            return
-        while cap < need:
-            cap *= 2
-        key = torch.empty(cap, dtype=torch.int64, device=self.device)
-        tp = torch.empty(cap, dtype=torch.uint8, device=self.device)
-        key[:self.num_records].copy_(self._key[:self.num_records])          # device to device, stream-ordered
-        tp[:self.num_records].copy_(self._tp[:self.num_records])
-        self._key, self._tp = key, tp
 
     def _ground_truth(self, gt, B):
         if isinstance(gt, tuple) and len(gt) == 2 and torch.is_tensor(gt[0]) and torch.is_tensor(gt[1]) and gt[0].dim() == 3:
@@ -140,55 +193,34 @@ class VOCMeanAP:
                                  % (tuple(boxes.shape), tuple(labels.shape)))
             if boxes.dtype != torch.float64 or labels.dtype != torch.int32:
                 raise ValueError('device ground truth must be float64 boxes and int32 labels')
-            boxes, labels = boxes.to(self.device).contiguous(), labels.to(self.device).contiguous()
-        else:
-            if len(gt) != B:
-                raise ValueError('%d ground-truth arrays for %d images' % (len(gt), B))
-            rows = []
-            for a in gt:
-                a = np.asarray(a, dtype=np.float64)
-                if a.size == 0:
-                    a = a.reshape(0, 5)
-                if a.ndim != 2 or a.shape[1] != 5:
-                    raise ValueError('ground truth per image must be [n, 5] (x1, y1, x2, y2, label), got %s' % (a.shape,))
-                rows.append(a)
-            G = max([1] + [len(a) for a in rows])
-            hb = np.zeros((B, G, 4), dtype=np.float64)
-            hl = np.full((B, G), -1, dtype=np.int32)
-            for i, a in enumerate(rows):
-                lab = a[:, 4]
-                # eval.py:157 selects rows by `annotations[:, 4] == label` for label in range(num_classes): any other value is no row
-                ok = (lab >= 0) & (lab < self.num_classes) & (lab == np.floor(lab))
-                hb[i, :len(a)] = a[:, :4]
-                hl[i, :len(a)] = np.where(ok, lab, -1).astype(np.int32)
-            boxes = torch.from_numpy(hb).to(self.device)
-            labels = torch.from_numpy(hl).to(self.device)
-        if boxes.shape[1] > ops.VOC_MAX_GT:
-            raise ValueError('at most %d ground-truth rows per image, got %d' % (ops.VOC_MAX_GT, boxes.shape[1]))
-        if boxes.shape[1] == 0:                                     # (the kernel wants G >= 1: one padding row)
-            boxes = torch.zeros((B, 1, 4), dtype=torch.float64, device=self.device)
-            labels = torch.full((B, 1), -1, dtype=torch.int32, device=self.device)
-        return boxes, labels
+            _check_gt_rows(boxes.shape[1], ops.VOC_MAX_GT)
+            if boxes.shape[1] > 0:
+                return boxes.to(self.device).contiguous(), labels.to(self.device).contiguous()
+            gt = [()] * B                                               # G = 0: one padding row
+        h = _pad_ground_truth(gt, B, 5, '(x1, y1, x2, y2, label)', ops.VOC_MAX_GT)
+        lab = h[:, :, 4]
+        # eval.py:157 selects rows by `annotations[:, 4] == label` for label in range(num_classes): any other value is no row
+        ok = (lab >= 0) & (lab < self.num_classes) & (lab == np.floor(lab))
+        return (torch.from_numpy(np.ascontiguousarray(h[:, :, :4])).to(self.device),
+                torch.from_numpy(np.where(ok, lab, -1).astype(np.int32)).to(self.device))
 
     def add(self, dets, counts, gt):
         """dets [B, max_det, 6] fp32 and counts [B] of finalize_device (device tensors); gt: see the class docstring."""
-        dets = torch.as_tensor(dets).to(self.device, torch.float32).contiguous()
-        counts = torch.as_tensor(counts).to(self.device, torch.int32).contiguous()
-        if dets.dim() != 3 or dets.shape[2] != 6 or counts.dim() != 1 or counts.shape[0] != dets.shape[0]:
-            raise ValueError('dets must be [B, max_det, 6] with counts [B], got %s and %s' % (tuple(dets.shape), tuple(counts.shape)))
+        dets, counts = _check_dets(dets, counts, self.device)
         B, M = int(dets.shape[0]), int(dets.shape[1])
         if B == 0 or M == 0:
             return
         boxes, labels = self._ground_truth(gt, B)
         self._reserve(self.num_records + B * M)
         n = self.num_records
-        ops.voc_match(dets, counts, boxes, labels, self.num_classes, self.iou_threshold, self._key[n:], self._tp[n:], self._gt_count)
+        ops.voc_match(dets, counts, boxes, labels, self.num_classes, self.iou_threshold, self._rec[0][n:], self._rec[1][n:],
+                      self._gt_count)
         self.num_records = n + B * M
 
     def compute(self, curves=False):
         """-> (mean AP, {label: (ap, num_annotations)}) as eval.py:243-257 returns them; with curves=True also
         {label: (recall, precision)}: the sorted fp64 arrays eval.py:241 hands to _compute_ap (labels without ground truth: absent)."""
-        out, recall, precision, seg = ops.voc_ap(self._key, self._tp, self.num_records, self._gt_count, self.num_classes)
+        out, recall, precision, seg = ops.voc_ap(*self._rec, self.num_records, self._gt_count, self.num_classes)
         host = out.cpu().numpy()                                    # the one device->host copy: 2 x num_classes doubles
         average_precisions = {}
         for c in range(self.num_classes):
@@ -218,19 +250,29 @@ def _image_batches(generator, batch_size):
         yield batch
 
 
+def _model_device(model):
+    p = next(model.parameters(), None)
+    return p.device if p is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def _detect_batch(model, batch, device):
+    """One batch of _image_batches (HWC images of one size) through forward_raw + postprocess
+    -> (scores, labels, boxes, count, number of classes of the head)."""
+    x = torch.stack([img.permute(2, 0, 1) for _, img, _ in batch]).to(device).float().contiguous()
+    cls, reg, anc = model.forward_raw(x)
+    return postprocess(model, cls, reg, anc, int(x.shape[2]), int(x.shape[3])) + (int(cls.shape[-1]),)
+
+
 def evaluate_voc(generator, model, iou_threshold=0.5, score_threshold=0.05, max_detections=100, batch_size=1):
     """Drop-in for eval.py:165-257 `evaluate(generator, retinanet)`: the same generator protocol (len, [i] -> {'img' HWC, 'scale'},
     load_annotations, num_classes, label_to_name), the same summary lines and return value; detections, matching, sort and AP on
     the device.  batch_size > 1 batches consecutive images of the same size."""
     model.eval()
-    p = next(model.parameters(), None)
-    device = p.device if p is not None else torch.device('cuda', torch.cuda.current_device())
+    device = _model_device(model)
     meter = VOCMeanAP(generator.num_classes(), iou_threshold, device)
     with torch.no_grad():
         for batch in _image_batches(generator, max(1, int(batch_size))):
-            x = torch.stack([img.permute(2, 0, 1) for _, img, _ in batch]).to(device).float().contiguous()
-            cls, reg, anc = model.forward_raw(x)
-            s, l, b, count = postprocess(model, cls, reg, anc, int(x.shape[2]), int(x.shape[3]))
+            s, l, b, count, _ = _detect_batch(model, batch, device)
             dets, counts = finalize_device(s, l, b, count, [sc for _, _, sc in batch], score_threshold, max_detections)
             meter.add(dets, counts, [generator.load_annotations(i) for i, _, _ in batch])
     mean, average_precisions = meter.compute()
@@ -265,7 +307,7 @@ def summarize_lines(stats):
     return lines
 
 
-class COCOMeanAP:
+class COCOMeanAP(_RecordMeter):
     """pycocotools' COCOeval (iouType='bbox', default Params, useCats=1) accumulated on the device.
 
     ``add(dets, counts, image_ids, gt)`` matches one batch of finalize_dets' xywh rows (category index in column 5, rows of an image
@@ -280,41 +322,20 @@ class COCOMeanAP:
     reads id 0 as "no match", which COCO's positive ids never produce); no ``eval['scores']``; the category list is the
     ``num_categories`` indices (evaluate_coco maps the dataset's sorted category ids onto them)."""
 
-    INITIAL_CAPACITY = 1 << 16            # records; the buffers double when a batch does not fit
+    RECORD_DTYPES = (torch.int64, torch.int32, torch.uint8, torch.int64, torch.int64)      # key, image, rank, match, ignore
 
     def __init__(self, num_categories, device=None):
         num_categories = int(num_categories)
         if not 1 <= num_categories <= ops.COCO_MAX_CATEGORIES:
             raise ValueError('num_categories must be in [1, %d], got %d' % (ops.COCO_MAX_CATEGORIES, num_categories))
         self.num_categories = num_categories
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        self.reset()
+        super().__init__(device)
 
     def reset(self):
-        self.num_records = 0
+        super().reset()
         self.max_image_id = 0
         self._seen = set()
-        self._rec = self._alloc(self.INITIAL_CAPACITY)
         self._npig = torch.zeros((self.num_categories, len(COCO_AREA_RNG)), dtype=torch.int32, device=self.device)
-
-    def _alloc(self, n):
-        return tuple(torch.empty(n, dtype=dt, device=self.device)
-                     for dt in (torch.int64, torch.int32, torch.uint8, torch.int64, torch.int64))   # key, image, rank, match, ignore
-
-    @property
-    def capacity(self):
-        return self._rec[0].numel()
-
-    def _reserve(self, need):
-        cap = self.capacity
-        if need <= cap:
-            return
-        while cap < need:
-            cap *= 2
-        rec = self._alloc(cap)
-        for new, old in zip(rec, self._rec):
-            new[:self.num_records].copy_(old[:self.num_records])          # device to device, stream-ordered
-        self._rec = rec
 
     def _image_ids(self, image_ids, B):
         if torch.is_tensor(image_ids) and image_ids.device.type != 'cpu':
@@ -338,43 +359,22 @@ class COCOMeanAP:
                 raise ValueError('device ground truth must be [B, G, 7], got %s' % (tuple(gt.shape),))
             if gt.dtype != torch.float64:
                 raise ValueError('device ground truth must be float64')
-            g = gt.to(self.device).contiguous()
-        else:
-            if len(gt) != B:
-                raise ValueError('%d ground-truth arrays for %d images' % (len(gt), B))
-            rows = []
-            for a in gt:
-                a = np.asarray(a, dtype=np.float64)
-                if a.size == 0:
-                    a = a.reshape(0, 7)
-                if a.ndim != 2 or a.shape[1] != 7:
-                    raise ValueError('ground truth per image must be [n, 7] (x, y, w, h, category, iscrowd, area), got %s' % (a.shape,))
-                c = a[:, 4]
-                if not np.all((c >= 0) & (c < K) & (c == np.floor(c))):
-                    raise ValueError('ground-truth category out of range [0, %d)' % K)
-                rows.append(a)
-            G = max([1] + [len(a) for a in rows])
-            if G > ops.COCO_MAX_GT:
-                raise ValueError('at most %d ground-truth rows per image, got %d' % (ops.COCO_MAX_GT, G))
-            h = np.zeros((B, G, 7), dtype=np.float64)
-            h[:, :, 4] = -1
-            for i, a in enumerate(rows):
-                h[i, :len(a)] = a
-            g = torch.from_numpy(h).to(self.device)
-        if g.shape[1] > ops.COCO_MAX_GT:
-            raise ValueError('at most %d ground-truth rows per image, got %d' % (ops.COCO_MAX_GT, g.shape[1]))
-        if g.shape[1] == 0:                                         # (the kernel wants G >= 1: one padding row)
-            g = torch.zeros((B, 1, 7), dtype=torch.float64, device=self.device)
-            g[:, :, 4] = -1
-        return g
+            _check_gt_rows(gt.shape[1], ops.COCO_MAX_GT)
+            if gt.shape[1] > 0:
+                return gt.to(self.device).contiguous()
+            gt = [()] * B                                               # G = 0: one padding row
+
+        def in_range(a):
+            c = a[:, 4]
+            if not np.all((c >= 0) & (c < K) & (c == np.floor(c))):
+                raise ValueError('ground-truth category out of range [0, %d)' % K)
+        h = _pad_ground_truth(gt, B, 7, '(x, y, w, h, category, iscrowd, area)', ops.COCO_MAX_GT, in_range)
+        return torch.from_numpy(h).to(self.device)
 
     def add(self, dets, counts, image_ids, gt):
         """dets [B, max_det, 6] fp32 (x, y, w, h, score, category index) and counts [B] (device tensors); image_ids: B host ints;
         gt: see the class docstring."""
-        dets = torch.as_tensor(dets).to(self.device, torch.float32).contiguous()
-        counts = torch.as_tensor(counts).to(self.device, torch.int32).contiguous()
-        if dets.dim() != 3 or dets.shape[2] != 6 or counts.dim() != 1 or counts.shape[0] != dets.shape[0]:
-            raise ValueError('dets must be [B, max_det, 6] with counts [B], got %s and %s' % (tuple(dets.shape), tuple(counts.shape)))
+        dets, counts = _check_dets(dets, counts, self.device)
         B, M = int(dets.shape[0]), int(dets.shape[1])
         ids = self._image_ids(image_ids, B)
         g = self._ground_truth(gt, B)
@@ -412,8 +412,7 @@ def evaluate_coco(dataset, model, threshold=0.05, batch_size=1):
     written: a submission still goes through detections_batched(..., xywh=True) and coco_results.  batch_size > 1 batches
     consecutive images of the same size."""
     model.eval()
-    p = next(model.parameters(), None)
-    device = p.device if p is not None else torch.device('cuda', torch.cuda.current_device())
+    device = _model_device(model)
     coco = dataset.coco
     cat_ids = sorted(coco.getCatIds())
     cat_index = {c: i for i, c in enumerate(cat_ids)}
@@ -421,12 +420,10 @@ def evaluate_coco(dataset, model, threshold=0.05, batch_size=1):
     lut, total = None, torch.zeros((), dtype=torch.int64, device=device)
     with torch.no_grad():
         for batch in _image_batches(dataset, max(1, int(batch_size))):
-            x = torch.stack([img.permute(2, 0, 1) for _, img, _ in batch]).to(device).float().contiguous()
-            cls, reg, anc = model.forward_raw(x)
+            s, l, b, count, nc = _detect_batch(model, batch, device)
             if lut is None:                                         # model label -> index into the sorted category ids (-1: none)
-                lut = torch.tensor([cat_index.get(dataset.label_to_coco_label(c), -1) for c in range(int(cls.shape[-1]))],
+                lut = torch.tensor([cat_index.get(dataset.label_to_coco_label(c), -1) for c in range(nc)],
                                    dtype=torch.float32, device=device)
-            s, l, b, count = postprocess(model, cls, reg, anc, int(x.shape[2]), int(x.shape[3]))
             sc = torch.as_tensor(np.asarray([sc for _, _, sc in batch], dtype=np.float32), device=device)
             dets, counts = ops.finalize_dets(s, l, b, count, sc, threshold, int(s.shape[1]), True)     # uncapped, as the reference
             lab = dets[:, :, 5]
