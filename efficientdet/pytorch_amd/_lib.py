@@ -78,6 +78,17 @@ class TailJob(C.Structure):      # effdet_tail_job_t
     _fields_ = [('kind', C.c_int), ('u', _TailUnion)]
 
 
+class JpegInfo(C.Structure):     # effdet_jpeg_info_t
+    _fields_ = [(n, C.c_int) for n in ('width', 'height', 'ncomp', 'sampling', 'restart_interval', 'mcus_x', 'mcus_y')] + \
+               [('blocks_w', C.c_int * 3), ('blocks_h', C.c_int * 3), ('reason', C.c_int), ('coef_bytes', C.c_longlong)]
+
+
+class JpegDesc(C.Structure):     # effdet_jpeg_desc_t
+    _fields_ = [(n, C.c_int) for n in ('width', 'height', 'ncomp', 'sampling', 'status')] + \
+               [('blocks_w', C.c_int * 3), ('blocks_h', C.c_int * 3), ('idct_wg0', C.c_int), ('rgb_wg0', C.c_int), ('reserved', C.c_int),
+                ('coef_off', C.c_longlong * 3), ('qt', (C.c_ushort * 64) * 3)]
+
+
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
 
 _lib = None
@@ -95,6 +106,7 @@ SYMBOLS = [
     'effdet_drop_connect_scales', 'effdet_philox4x32_10', 'effdet_preprocess_batch', 'effdet_finalize_dets', 'effdet_voc_match', 'effdet_voc_ap', 'effdet_voc_ap_workspace_bytes',
     'effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes', 'effdet_head_out_bwd',
     'effdet_augment_train', 'effdet_augment_resize', 'effdet_augment_boxes',
+    'effdet_jpeg_probe', 'effdet_jpeg_entropy_batch', 'effdet_jpeg_reconstruct',
     'effdet_nhwc_to_nchw_f32', 'effdet_nchw_f32_to_nhwc', 'effdet_pad_rows', 'effdet_to_split', 'effdet_to_split2', 'effdet_version', 'effdet_abi_version',
 ]
 

@@ -5,7 +5,11 @@ The host only concatenates the decoded uint8 HWC images into a pinned staging bu
 one async H2D copy; bilinear resize to the common size, /255, mean/std normalisation, horizontal flip, zero padding, the
 NHWC / compute-dtype / channel-padded pack the stem conv reads, and the annotation rescale all happen on the GPU
 (csrc/pipeline.hip::preprocess_kernel).  The float64 512x512x3 canvas of augmentation.py:111, the NCHW permute of the
-collater and the model-side NCHW -> NHWC repack disappear.  There is no CPU fallback: the collater needs the GPU."""
+collater and the model-side NCHW -> NHWC repack disappear.  There is no CPU fallback: the collater needs the GPU.
+
+Samples may carry the file itself ({'jpeg': bytes}) instead of decoded pixels: decode_jpeg_batch then replaces the staging of the
+pixels -- Huffman decode on host threads inside the library, coefficients over the same pinned double buffer, and the rest of the
+decoder as two HIP launches (csrc/jpeg.hip) that write the uint8 HWC layout the kernels above read."""
 import math
 
 import numpy as np
@@ -19,15 +23,115 @@ MEAN = (0.485, 0.456, 0.406)       # datasets/augmentation.py:141-142
 STD = (0.229, 0.224, 0.225)
 
 
+class UnsupportedJPEG(ValueError):
+    """A valid JPEG outside what csrc/jpeg.hip decodes (one-scan 8-bit baseline, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0), met without a
+    fallback decoder.  index: position in the batch; reason: ops.JPEG_REASONS code."""
+
+    def __init__(self, index, reason):
+        super().__init__('JPEG %d of the batch is not baseline (%s) and no decode_fallback was given'
+                         % (index, ops.JPEG_REASONS.get(reason, 'reason %d' % reason)))
+        self.index, self.reason = index, reason
+
+
+def _align(n, a=128):
+    return (int(n) + a - 1) // a * a
+
+
+def _decode_jpeg_batch(streams, stager, threads, fallback):
+    """decode_jpeg_batch on `stager`'s pinned double buffer -> (src, src_off, src_hw, host hw [B,2] int32)."""
+    dev = stager.device
+    B = len(streams)
+    infos, fb = [], {}
+    for b, st in enumerate(streams):                               # 1. probe (host): every refusal is raised before anything is staged
+        status, info = ops.jpeg_probe(st)
+        if status == -3 and fallback is not None:
+            px = np.ascontiguousarray(fallback(st))
+            if px.dtype != np.uint8 or px.ndim != 3 or px.shape[2] != 3:
+                raise ValueError('decode_fallback must return uint8 [H,W,3] RGB (JPEG %d of the batch)' % b)
+            fb[b] = px
+        elif status == -3:
+            raise UnsupportedJPEG(b, info.reason)
+        elif status != 0:
+            raise ValueError('JPEG %d of the batch is corrupt: not a JPEG, or its header is cut short' % b)
+        infos.append(info)
+    dec = [b for b in range(B) if b not in fb]
+    hw = np.array([fb[b].shape[:2] if b in fb else (infos[b].height, infos[b].width) for b in range(B)], dtype=np.int32).reshape(B, 2)
+    nd = len(dec)
+    # one staging block = one H2D copy: [descriptors | planes_off | dst_off | src_off | src_hw | coefficients | fallback pixels]; the
+    # device buffer continues with the decoded images, and src starts at the fallback pixels
+    o_desc = 0
+    o_poff = _align(o_desc + nd * ops.JPEG_DESC_BYTES)
+    o_doff = _align(o_poff + 8 * nd)
+    o_soff = _align(o_doff + 8 * nd)
+    o_shw = _align(o_soff + 8 * B)
+    o_coef = _align(o_shw + 8 * B)
+    coef_off = o_coef + np.concatenate([[0], np.cumsum([infos[b].coef_bytes for b in dec])]).astype(np.int64)    # whole blocks: 128 B each
+    o_fb = _align(coef_off[-1])
+    src_off = np.zeros(B, dtype=np.int64)
+    end = o_fb
+    for b in fb:
+        src_off[b] = end - o_fb
+        end += _align(fb[b].size, 16)
+    n_stage = _align(end)
+    for b in dec:
+        src_off[b] = end - o_fb
+        end += _align(int(hw[b, 0]) * int(hw[b, 1]) * 3, 16)
+    slot, stage = stager._pinned(n_stage)
+    view = stage.numpy()
+    wgs = (0, 0)
+    if nd:                                                         # 2. entropy decode (host threads) straight into the pinned block
+        status, wgs = ops.jpeg_entropy_batch([streams[b] for b in dec], view[:o_fb], coef_off[:-1], view[o_desc:o_poff], threads)
+        if status != 0:
+            bad = [b for b, d in zip(dec, ops.jpeg_descs(view[o_desc:o_poff], nd)) if d.status != 0]
+            raise ValueError('JPEG %d of the batch is corrupt: its scan is truncated or damaged' % bad[0])
+        view[o_poff:o_poff + 8 * nd].view(np.int64)[:] = (coef_off[:-1] - o_coef) // 2
+        view[o_doff:o_doff + 8 * nd].view(np.int64)[:] = src_off[dec]
+    view[o_soff:o_soff + 8 * B].view(np.int64)[:] = src_off
+    view[o_shw:o_shw + 8 * B].view(np.int32)[:] = hw.reshape(-1)
+    for b, px in fb.items():
+        view[o_fb + src_off[b]:o_fb + src_off[b] + px.size] = px.reshape(-1)
+    buf = torch.empty(int(end), dtype=torch.uint8, device=dev)
+    buf[:n_stage].copy_(stage[:n_stage], non_blocking=True)       # 3. the one async H2D copy; the slot's event guards its reuse
+    ev = torch.cuda.Event(); ev.record(); stager._evt[slot] = ev
+    src = buf[o_fb:]
+    if nd:                                                         # 4. two launches for the whole batch
+        planes = torch.empty(max(int(coef_off[-1] - o_coef) // 2, 16), dtype=torch.uint8, device=dev)
+        ops.jpeg_reconstruct(buf, buf[o_desc:o_poff], nd, wgs, planes, buf[o_poff:o_poff + 8 * nd].view(torch.int64), src,
+                             buf[o_doff:o_doff + 8 * nd].view(torch.int64))
+    return src, buf[o_soff:o_soff + 8 * B].view(torch.int64), buf[o_shw:o_shw + 8 * B].view(torch.int32).view(B, 2), hw
+
+
+_default_stagers = {}
+
+
+def decode_jpeg_batch(streams, device='cuda', threads=8, fallback=None):
+    """Baseline JPEG streams (list of bytes) -> (src uint8, src_off [B] int64, src_hw [B,2] int32) on the device: RGB HWC pixels of
+    image b at src[src_off[b]:], rows tightly packed -- the input of ops.preprocess_batch / augment_train / augment_resize.
+
+    The host probes the headers and Huffman-decodes the batch on `threads` workers into a pinned double buffer; one async copy
+    carries coefficients and descriptors over; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB are two HIP launches
+    (csrc/jpeg.hip).  The pixels are libjpeg's (islow IDCT, fancy upsampling) bit for bit; EXIF orientation is not applied.
+    A stream outside the baseline subset goes through fallback(bytes) -> uint8 [H,W,3] RGB when given (its pixels ride the same
+    copy), else UnsupportedJPEG is raised; a corrupt stream raises ValueError.  Nothing is launched for a batch that raises."""
+    dev = torch.device(device)
+    if dev not in _default_stagers:
+        _default_stagers[dev] = DeviceCollater(device=dev)
+    src, d_off, d_hw, _ = _decode_jpeg_batch(list(streams), _default_stagers[dev], threads, fallback)
+    return src, d_off, d_hw
+
+
 class DeviceCollater:
     """collate_fn replacement: ``batch = collater(samples)`` -> (PackedImages, annotations [B,M,5] fp32 device, scales [B]).
 
     samples: list of dicts {'img': uint8 ndarray [H,W,3] RGB, 'annot': float ndarray [n,5]} -- what the reference's
     datasets yield BEFORE its transform chain (the chain runs here, on the device).  flip_x: probability of the
-    Augmenter's horizontal flip (0 disables; eval pipelines have none)."""
+    Augmenter's horizontal flip (0 disables; eval pipelines have none).
+    A batch may carry {'jpeg': bytes} in place of 'img' in EVERY sample: the files are then decoded by decode_jpeg_batch
+    (decode_threads host workers for the entropy stage, decode_fallback for streams that are not baseline)."""
 
-    def __init__(self, common_size=512, dtype=torch.bfloat16, device='cuda', flip_x=0.0, seed=0):
+    def __init__(self, common_size=512, dtype=torch.bfloat16, device='cuda', flip_x=0.0, seed=0, decode_threads=8, decode_fallback=None):
         self.S, self.dtype, self.device = int(common_size), dtype, torch.device(device)
+        self.decode_threads, self.decode_fallback = int(decode_threads), decode_fallback
         self.flip_x = float(flip_x)
         self.rng = np.random.RandomState(seed)
         self._stage = [None, None]      # two pinned staging buffers: batch k+1 is assembled while batch k's copy is in flight
@@ -41,6 +145,20 @@ class DeviceCollater:
         if self._stage[s] is None or self._stage[s].numel() < nbytes:
             self._stage[s] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
         return s, self._stage[s]
+
+    def _stage_batch(self, samples):
+        """-> None for a batch of {'jpeg': bytes} samples (decoded in _upload), else _stage_images(samples)."""
+        n_jpeg = sum('jpeg' in s for s in samples)
+        if n_jpeg and (n_jpeg != len(samples) or any('img' in s for s in samples)):
+            raise ValueError("a batch carries either 'img' or 'jpeg' in every sample, not a mix")
+        return None if n_jpeg else self._stage_images(samples)
+
+    def _upload(self, samples, staged):
+        """-> (src, src_off, src_hw on the device, host hw [B,2]): the staged pixels' H2D copy, or the JPEG decode."""
+        if staged is None:
+            return _decode_jpeg_batch([s['jpeg'] for s in samples], self, self.decode_threads, self.decode_fallback)
+        stage, slot, offs, hw = staged
+        return self._upload_images(stage, slot, offs, hw) + (hw,)
 
     def _stage_images(self, samples):
         """Concatenate the decoded images into a pinned staging buffer -> (pinned bytes, slot, offsets [B+1] int64, hw [B,2] int32)."""
@@ -77,11 +195,11 @@ class DeviceCollater:
 
     def __call__(self, samples):
         B = len(samples)
-        stage, slot, offs, hw = self._stage_images(samples)
+        staged = self._stage_batch(samples)
         flips = (self.rng.rand(B) < self.flip_x).astype(np.uint8) if self.flip_x > 0 else None
         ann = self._padded_annots(samples)
         dev = self.device
-        src, d_off, d_hw = self._upload_images(stage, slot, offs, hw)
+        src, d_off, d_hw, _ = self._upload(samples, staged)
         d_flip = torch.from_numpy(flips).to(dev, non_blocking=True) if flips is not None else None
         d_ann = torch.from_numpy(ann).to(dev, non_blocking=True)
         m, scale = ops.preprocess_batch(src, d_off, d_hw, self.S, self.dtype, chunk_elems(self.dtype), MEAN, STD, d_flip, d_ann)
@@ -170,7 +288,7 @@ class DeviceAugmentation(DeviceCollater):
     """get_augumentation(phase, width, height, min_area, min_visibility) + detection_collate (datasets/augmentation.py:8-67) on the
     device: ``images, annotations, params = aug(samples)``.
 
-    samples: as for DeviceCollater ({'img': uint8 [H,W,3] RGB, 'annot': [n,5] pascal_voc boxes + label}).  Returns
+    samples: as for DeviceCollater ({'img': uint8 [H,W,3] RGB or 'jpeg': bytes, 'annot': [n,5] pascal_voc boxes + label}).  Returns
     PackedImages (NHWC, `dtype`, the stem conv's layout), annotations [B,M,5] fp32 with each image's kept boxes first in their
     input order and -1 rows after (None for 'test'), and params: for 'train' the device table [B, len(AUG_COLUMNS)] that drove
     the chain, for 'valid' / 'test' the per-axis scales [B,2] = (width / w, height / h) (boxes / scale map back to the image).
@@ -184,19 +302,20 @@ class DeviceAugmentation(DeviceCollater):
     PHASES = ('train', 'valid', 'test')
 
     def __init__(self, phase='train', width=512, height=512, min_area=0., min_visibility=0., dtype=torch.bfloat16, device='cuda',
-                 seed=0, trim=True):
+                 seed=0, trim=True, decode_threads=8, decode_fallback=None):
         if phase not in self.PHASES:
             raise ValueError('phase must be one of %s' % (self.PHASES,))
         if phase == 'train' and (width != height or width < 8):
             raise ValueError("the 'train' chain needs width == height >= 8 (got %d x %d)" % (width, height))
-        super().__init__(common_size=width, dtype=dtype, device=device, seed=seed)
+        super().__init__(common_size=width, dtype=dtype, device=device, seed=seed, decode_threads=decode_threads,
+                         decode_fallback=decode_fallback)
         self.phase, self.W, self.H = phase, int(width), int(height)
         self.min_area, self.min_visibility, self.trim = float(min_area), float(min_visibility), bool(trim)
 
     def __call__(self, samples, table=None, stages=None):
         """stages: optional dict that receives the uint8 intermediates of ops.augment_train / ops.augment_resize (tests)."""
         B = len(samples)
-        stage, slot, offs, hw = self._stage_images(samples)
+        staged = self._stage_batch(samples)
         if self.phase == 'train':
             if table is None:
                 table = sample_augment_table(self.rng, B, self.S)
@@ -206,7 +325,7 @@ class DeviceAugmentation(DeviceCollater):
             raise ValueError("an explicit table only applies to the 'train' phase")
         ann = self._padded_annots(samples) if self.phase != 'test' else None
         dev = self.device
-        src, d_off, d_hw = self._upload_images(stage, slot, offs, hw)
+        src, d_off, d_hw, hw = self._upload(samples, staged)
         if self.phase == 'train':
             params = (table if torch.is_tensor(table) else torch.from_numpy(table)).to(dev, torch.float32, non_blocking=True).contiguous()
             m = ops.augment_train(src, d_off, d_hw, params, self.S, self.dtype, chunk_elems(self.dtype), MEAN, STD, stages)

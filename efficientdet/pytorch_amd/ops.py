@@ -1387,3 +1387,61 @@ def augment_boxes(src_hw, table, H, W, annots, min_area=0.0, min_visibility=0.0)
                                                   C.c_double(min_area), C.c_double(min_visibility), L.ptr(out), L.ptr(counts),
                                                   L.stream_ptr()), 'effdet_augment_boxes')
     return out, counts
+
+
+# ----------------------------------------------------------------------------- JPEG decode (csrc/jpeg.hip)
+_JPEG = ('effdet_jpeg_probe', 'effdet_jpeg_entropy_batch', 'effdet_jpeg_reconstruct')
+JPEG_GREY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3
+JPEG_REASONS = {1: 'progressive frame', 2: 'extended, lossless or arithmetic-coded frame', 3: 'sample precision other than 8 bits',
+                4: '16-bit quantisation table', 5: 'component count other than 1 or 3', 6: 'sampling other than 4:4:4, 4:2:2 or 4:2:0',
+                7: 'more than one scan', 8: 'three components that are not YCbCr'}
+JPEG_DESC_BYTES = C.sizeof(L.JpegDesc)
+
+
+def _as_u8(stream):
+    return np.frombuffer(stream, dtype=np.uint8)
+
+
+def jpeg_probe(stream):
+    """Host only.  bytes -> (status, JpegInfo): 0, or _lib's EFFDET_EUNSUPPORTED (-3, info.reason says why) / EFFDET_EINVAL (-1)."""
+    a = _as_u8(stream)
+    info = L.JpegInfo()
+    st = L.require(*_JPEG).effdet_jpeg_probe(C.c_void_p(a.ctypes.data), C.c_longlong(a.size), C.byref(info))
+    return int(st), info
+
+
+def jpeg_entropy_batch(streams, coef_out, coef_off, desc_out, threads=8):
+    """Host only.  Huffman-decode the streams (list of bytes) into coef_out (uint8 numpy view of the caller's staging buffer; image
+    b at byte coef_off[b], a multiple of 16) and desc_out (uint8 numpy view, len(streams) * JPEG_DESC_BYTES) on `threads` workers
+    -> (status of the first image that failed or 0, (launch-1 workgroups, launch-2 workgroups)).  Per-image statuses are in the
+    descriptors (jpeg_descs)."""
+    B = len(streams)
+    arrs = [_as_u8(s) for s in streams]
+    ptrs = (C.c_void_p * B)(*[a.ctypes.data for a in arrs])
+    lens = (C.c_longlong * B)(*[a.size for a in arrs])
+    offs = (C.c_longlong * B)(*[int(o) for o in coef_off])
+    assert coef_out.dtype == np.uint8 and coef_out.flags['C_CONTIGUOUS'] and coef_out.flags['WRITEABLE']
+    assert desc_out.dtype == np.uint8 and desc_out.flags['C_CONTIGUOUS'] and desc_out.size >= B * JPEG_DESC_BYTES
+    totals = (C.c_int * 2)()
+    st = L.require(*_JPEG).effdet_jpeg_entropy_batch(ptrs, lens, B, C.c_void_p(coef_out.ctypes.data), C.c_longlong(coef_out.size), offs,
+                                                     C.c_void_p(desc_out.ctypes.data), int(threads), totals)
+    return int(st), (int(totals[0]), int(totals[1]))
+
+
+def jpeg_descs(desc_out, B):
+    """The B descriptor records of a jpeg_entropy_batch buffer as a ctypes array (a view, not a copy)."""
+    return (L.JpegDesc * B).from_buffer(desc_out)
+
+
+def jpeg_reconstruct(coef, desc, B, wgs, planes, planes_off, dst, dst_off):
+    """Device: the two launches of effdet_jpeg_reconstruct on torch's current stream.  coef / desc: the staged coefficient bytes and
+    descriptor records on the device (uint8 tensors, 16-byte aligned); wgs: the workgroup totals jpeg_entropy_batch returned;
+    planes: uint8 workspace, image b's component planes at byte planes_off[b]; dst: uint8, image b's RGB HWC pixels at dst_off[b]
+    (both int64 device tensors, multiples of 16)."""
+    for t in (coef, desc, planes, dst):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+    assert planes_off.dtype == torch.int64 and dst_off.dtype == torch.int64 and planes_off.numel() >= B and dst_off.numel() >= B
+    assert desc.numel() >= B * JPEG_DESC_BYTES
+    L.check(L.require(*_JPEG).effdet_jpeg_reconstruct(L.ptr(coef), L.ptr(desc), int(B), int(wgs[0]), int(wgs[1]), L.ptr(planes),
+                                                      L.ptr(planes_off), L.ptr(dst), L.ptr(dst_off), L.stream_ptr()),
+            'effdet_jpeg_reconstruct')

@@ -694,6 +694,74 @@ int effdet_augment_resize(const unsigned char* src, const long long* src_off, co
 int effdet_augment_boxes(const int* src_hw, const float* table, int B, int H, int W, const float* annots, int M, double min_area,
                          double min_visibility, float* annots_out, int* counts, effdet_stream_t stream);
 
+/* Baseline JPEG decode in front of the input pipeline (the cv2.imread of datasets/voc0712.py and datasets/coco.py), cut at the
+ * coefficient buffer: the serial entropy decode runs on the HOST (the two calls below take no stream and touch no GPU), and
+ * everything after the coefficients is two batched launches (effdet_jpeg_reconstruct).
+ *
+ * Accepted: one-scan 8-bit baseline (SOF0) streams, Huffman coded, 1 component or 3 components (YCbCr) sampled 4:4:4, 4:2:2
+ * (luma 2x1) or 4:2:0 (luma 2x2), with or without restart intervals.  EXIF orientation is not applied.
+ *
+ * effdet_jpeg_probe parses SOI, APPn, COM, DQT, SOF0, DHT, DRI and SOS up to the scan and fills `info`.  Returns EFFDET_OK,
+ * EFFDET_EUNSUPPORTED (a valid JPEG outside the accepted set; info->reason says why) or EFFDET_EINVAL (not a JPEG, or the header
+ * is cut short or inconsistent).
+ *
+ * effdet_jpeg_entropy_batch Huffman-decodes B streams (DC prediction, byte unstuffing, RSTn resynchronisation, fill bytes) on
+ * `threads` std::thread workers (clamped to [1, 16]; the machine's CPU count is never read).  Image b's int16 coefficients go to
+ * coef_out + coef_off[b] (BYTES, a multiple of 16), component-major [component][block_row][block_col][64], each block in natural
+ * (de-zigzagged, row-major) order, block grids rounded up to whole MCUs; the image owns info.coef_bytes bytes there and nothing
+ * outside them is written under any input (coef_bytes_total bounds the whole buffer).  desc[b] receives the image's record.
+ * A scan that is truncated or corrupt (data ends or a marker arrives before the last MCU, an undefined Huffman code, a
+ * coefficient index past 63, a DC value outside int16, a missing or out-of-order RSTn) FAILS that image alone: desc[b].status =
+ * EFFDET_EINVAL, its coefficient range is zero, and it gets no workgroups.  A stream the probe refuses gets the probe's status
+ * and no write at all.  wg_totals[0], [1]: the grid sizes of the two launches over the images with status EFFDET_OK.  Returns EFFDET_OK
+ * when every image decoded, else the status of the first image that did not; EFFDET_EINVAL for bad arguments (nothing is written).
+ *
+ * effdet_jpeg_reconstruct (device; enqueues two kernels, no allocation, no synchronisation, capture-safe) takes the coefficient
+ * buffer and the descriptor table as the host stage wrote them, both copied to the device:
+ *   1. dequantise + 8x8 inverse DCT (the 13-bit "slow integer" transform, two passes, each rounded once) + level shift + clamp:
+ *      int16 coefficients -> uint8 component planes at planes + planes_off[b] (components in order, each blocks_h * 8 rows of
+ *      blocks_w * 8 bytes; info.coef_bytes / 2 bytes per image);
+ *   2. triangle-filter ("fancy") chroma upsampling with the edges replicated from the last real sample of the downsampled plane
+ *      + YCbCr -> RGB through 16-bit fixed-point constants (grey: R = G = B): uint8 RGB HWC, rows tightly packed, at
+ *      dst + dst_off[b] -- with (desc[b].height, desc[b].width) as src_hw this is the src / src_off / src_hw input of
+ *      effdet_preprocess_batch, effdet_augment_train and effdet_augment_resize.  planes_off and dst_off are multiples of 16.
+ * All arithmetic is int32.  The kernels read addresses from the descriptor table only, never from stream bytes. */
+enum { EFFDET_JPEG_GREY = 0, EFFDET_JPEG_444 = 1, EFFDET_JPEG_422 = 2, EFFDET_JPEG_420 = 3 };
+enum {
+  EFFDET_JPEG_OK = 0,
+  EFFDET_JPEG_PROGRESSIVE = 1,     /* SOF2 */
+  EFFDET_JPEG_FRAME_TYPE = 2,      /* extended sequential, lossless, differential or arithmetic-coded frames (any other SOF, DAC) */
+  EFFDET_JPEG_PRECISION = 3,       /* sample precision other than 8 bits */
+  EFFDET_JPEG_QUANT16 = 4,         /* 16-bit quantisation table */
+  EFFDET_JPEG_COMPONENTS = 5,      /* component count other than 1 or 3 */
+  EFFDET_JPEG_SAMPLING = 6,        /* a sampling combination outside 4:4:4 / 4:2:2 / 4:2:0 (4:4:0, 4:1:1, ...) */
+  EFFDET_JPEG_MULTISCAN = 7,       /* the first scan does not carry every component */
+  EFFDET_JPEG_COLORSPACE = 8       /* 3 components that are not YCbCr (Adobe transform 0, or component ids 'R' 'G' 'B') */
+};
+typedef struct {
+  int width, height, ncomp, sampling, restart_interval;
+  int mcus_x, mcus_y;              /* MCU grid */
+  int blocks_w[3], blocks_h[3];    /* 8x8 blocks per component row / column, whole MCUs */
+  int reason;                      /* EFFDET_JPEG_* when the call returns EFFDET_EUNSUPPORTED */
+  long long coef_bytes;            /* coefficient space of the image: 128 * sum(blocks_w * blocks_h) */
+} effdet_jpeg_info_t;
+typedef struct {
+  int width, height, ncomp, sampling;
+  int status;                      /* EFFDET_OK, or why the image has no coefficients */
+  int blocks_w[3], blocks_h[3];
+  int idct_wg0, rgb_wg0;           /* first workgroup of the image in launch 1 / launch 2 (prefix over the batch) */
+  int reserved;
+  long long coef_off[3];           /* BYTE offset of each component's coefficients from coef_out */
+  unsigned short qt[3][64];        /* quantisation table per component, natural order */
+} effdet_jpeg_desc_t;
+int effdet_jpeg_probe(const unsigned char* bytes, long long nbytes, effdet_jpeg_info_t* info);
+int effdet_jpeg_entropy_batch(const unsigned char* const* streams, const long long* nbytes, int B, short* coef_out,
+                              long long coef_bytes_total, const long long* coef_off, effdet_jpeg_desc_t* desc, int threads,
+                              int wg_totals[2]);
+int effdet_jpeg_reconstruct(const short* coef, const effdet_jpeg_desc_t* desc, int B, int idct_wgs, int rgb_wgs,
+                            unsigned char* planes, const long long* planes_off, unsigned char* dst, const long long* dst_off,
+                            effdet_stream_t stream);
+
 /* Gradient of the head outputs (models/retinahead.py:119-127 under autograd):  dlogit = dprob * p * (1 - p) and dreg,
  * both stored in `dtype` for the head's data-gradient convs.  ncls / nreg: element counts. */
 int effdet_head_out_bwd(const float* dprob, const float* prob, const float* dreg, void* dlogit, void* dreg_out, int dtype,
