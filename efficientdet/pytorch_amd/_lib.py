@@ -89,6 +89,10 @@ class JpegDesc(C.Structure):     # effdet_jpeg_desc_t
                 ('coef_off', C.c_longlong * 3), ('qt', (C.c_ushort * 64) * 3)]
 
 
+class TrainCtl(C.Structure):     # effdet_train_ctl_t
+    _fields_ = [(n, C.c_int) for n in ('skip', 'pending', 'applied', 'skipped')] + [('loss_count', C.c_longlong), ('loss_sum', C.c_double)]
+
+
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
 
 _lib = None
@@ -102,7 +106,7 @@ SYMBOLS = [
     'effdet_act_bwd', 'effdet_add_inplace', 'effdet_colsum', 'effdet_bifpn_fuse_fwd', 'effdet_bifpn_fuse_fwd2', 'effdet_bifpn_fuse_bwd',
     'effdet_anchors', 'effdet_num_anchors', 'effdet_decode_score', 'effdet_nms_workspace_bytes', 'effdet_nms',
     'effdet_gather_dets', 'effdet_loss_workspace_bytes', 'effdet_focal_loss_fwd', 'effdet_focal_loss_bwd', 'effdet_focal_loss_bwd_pix', 'effdet_focal_loss_fwd_grad', 'effdet_focal_loss_bwd_reg',
-    'effdet_clip_adamw_step', 'effdet_opt_chunk',
+    'effdet_clip_adamw_step', 'effdet_opt_chunk', 'effdet_train_gate', 'effdet_grad_accumulate', 'effdet_clip_adamw_step_gated',
     'effdet_drop_connect_scales', 'effdet_philox4x32_10', 'effdet_preprocess_batch', 'effdet_finalize_dets', 'effdet_voc_match', 'effdet_voc_ap', 'effdet_voc_ap_workspace_bytes',
     'effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes', 'effdet_head_out_bwd',
     'effdet_augment_train', 'effdet_augment_resize', 'effdet_augment_boxes',

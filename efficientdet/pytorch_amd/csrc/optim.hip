@@ -6,6 +6,17 @@
 //                   p -= (lr/(1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)                    (torch.optim.AdamW)
 // HBM-bound: reads g twice, p/m/v once, writes p/m/v: 7 x 4 bytes per parameter (275 MB per D0 step).  The clipped
 // gradient is not written back (p.grad keeps the unclipped values) unless write_grad is set.
+//
+// Training-loop control on the device (reference train.py:104-120: `if bool(loss == 0): continue`, gradient accumulation over
+// grad_accumulation_steps micro-batches, total_loss.append(loss.item())): a 32-byte control block (effdet_train_ctl_t) written by
+// one-thread launches and read by the multi-tensor passes, so a captured loop needs no host decision that depends on data:
+//   train_gate_kernel       skip = (loss == 0); otherwise the fp64 loss meter advances
+//   grad_accumulate_kernel  unless skip: acc = g (pending == 0) or acc += g over the optimizer's block table; then
+//   train_pending_kernel    unless skip: pending += 1                    (single writer, ordered behind every reader)
+//   the GATED instantiations of the three step kernels do nothing unless (!skip && pending != 0); they read acc as the gradient; then
+//   train_release_kernel    if the step ran: pending = 0, applied += 1   (single writer, ordered behind every reader)
+// No kernel both reads a control word from many workgroups and writes it.  Accumulate moves 12 bytes per parameter (8 on the first
+// micro-batch of a window, which writes instead of adding: the arena never needs a zeroing pass).
 #include "common.h"
 
 namespace {
@@ -20,7 +31,14 @@ struct OptK {
   int nblocks, ntensors, write_grad;
   const float* hyper;      // optional DEVICE copy of {max_norm, lr, beta1, beta2, eps, wd}: read at run time, so a captured
                            // step (hipGraph replay) follows a learning-rate schedule instead of the values frozen at capture
+  // GATED instantiations only: g is the accumulation arena's table, `has` the micro-step's gradient table (has[i] == 0: tensor i has
+  // no gradient) and ctl the control block that says whether the step runs at all
+  const unsigned long long* has; const effdet_train_ctl_t* ctl;
 };
+
+static_assert(sizeof(effdet_train_ctl_t) == 32, "effdet_train_ctl_t is read back as 32 bytes by the binding");
+
+__device__ __forceinline__ bool gate_open(const effdet_train_ctl_t* c) { return c->skip == 0 && c->pending != 0; }
 
 struct Hyper { float max_norm, lr, beta1, beta2, eps, wd; };
 __device__ __forceinline__ Hyper hyper_of(const OptK& k) {
@@ -46,9 +64,10 @@ __device__ __forceinline__ f32x4 load4_any(const float* q, bool al) {
   return f32x4{q[0], q[1], q[2], q[3]};
 }
 
-__global__ __launch_bounds__(256) void opt_norm_kernel(const OptK k) {
+template <bool GATED> __global__ __launch_bounds__(256) void opt_norm_kernel(const OptK k) {
+  if (GATED && !gate_open(k.ctl)) return;                    // (the whole grid takes the same branch: partial[] stays untouched)
   const int ti = k.block_tensor[blockIdx.x];
-  const float* g = (const float*)k.g[ti];
+  const float* g = (const float*)(GATED && !k.has[ti] ? 0ull : k.g[ti]);
   float s = 0.f;
   if (g) {
     const long long n = k.n[ti], off = (long long)(blockIdx.x - k.block_first[ti]) * OPT_CHUNK;
@@ -66,9 +85,12 @@ __global__ __launch_bounds__(256) void opt_norm_kernel(const OptK k) {
 
 // one workgroup: finishes the norm and advances the per-tensor AdamW step counters (torch keeps one per parameter: a
 // parameter without gradient in some step is skipped and its bias correction lags behind)
+template <bool GATED>
 __global__ __launch_bounds__(1024) void opt_norm_final_kernel(const float* __restrict__ partial, int nb, float* __restrict__ norm,
-                                                              const unsigned long long* __restrict__ g, int* __restrict__ steps, int nt) {
+                                                              const unsigned long long* __restrict__ g, int* __restrict__ steps, int nt,
+                                                              const effdet_train_ctl_t* __restrict__ ctl) {
   __shared__ float red[16];
+  if (GATED && !gate_open(ctl)) return;
   for (int i = threadIdx.x; i < nt; i += 1024) if (g[i]) steps[i] += 1;
   float s = 0.f;
   for (int i = threadIdx.x; i < nb; i += 1024) s += partial[i];
@@ -85,10 +107,11 @@ __device__ __forceinline__ void adamw1(float& p, float& m, float& v, float g, co
   p -= step_size * m / (sqrtf(v) / bc2_sqrt + k.eps);
 }
 
-__global__ __launch_bounds__(256) void opt_adamw_kernel(const OptK kk) {
+template <bool GATED> __global__ __launch_bounds__(256) void opt_adamw_kernel(const OptK kk) {
+  if (GATED && !gate_open(kk.ctl)) return;
   const Hyper k = hyper_of(kk);
   const int ti = kk.block_tensor[blockIdx.x];
-  float* g = (float*)kk.g[ti];
+  float* g = (float*)(GATED && !kk.has[ti] ? 0ull : kk.g[ti]);
   if (!g) return;
   float* p = (float*)kk.p[ti]; float* m = (float*)kk.m[ti]; float* v = (float*)kk.v[ti];
   // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)) with torch.clamp's NaN rule -- a NaN norm turns every gradient into NaN
@@ -128,6 +151,66 @@ __global__ __launch_bounds__(256) void opt_adamw_kernel(const OptK kk) {
   }
 }
 
+// ---- the loop's control block: one-thread launches are its only writers ----
+__global__ void train_gate_kernel(const float* __restrict__ loss, effdet_train_ctl_t* __restrict__ ctl) {
+  const float l = loss[0];
+  if (l == 0.0f) { ctl->skip = 1; ctl->skipped += 1; }       // train.py:110 `if bool(loss == 0): continue` (-0.0 skips; NaN / Inf do not)
+  else { ctl->skip = 0; ctl->loss_sum += (double)l; ctl->loss_count += 1; }
+}
+
+__global__ void train_pending_kernel(effdet_train_ctl_t* __restrict__ ctl) {
+  if (!ctl->skip) ctl->pending += 1;
+}
+
+__global__ void train_release_kernel(effdet_train_ctl_t* __restrict__ ctl) {
+  if (gate_open(ctl)) { ctl->pending = 0; ctl->applied += 1; }
+}
+
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const unsigned long long* __restrict__ grads,
+                                                              const unsigned long long* __restrict__ acc, const long long* __restrict__ numel,
+                                                              const int* __restrict__ block_tensor, const int* __restrict__ block_first,
+                                                              const effdet_train_ctl_t* __restrict__ ctl) {
+  if (ctl->skip) return;                                     // a skipped micro-step: its gradients (NaN included) are never read
+  const int ti = block_tensor[blockIdx.x];
+  const float* g = (const float*)grads[ti];
+  if (!g) return;
+  float* a = (float*)acc[ti];
+  const bool first = ctl->pending == 0;                      // the first micro-batch of a window WRITES: no zeroing pass
+  const long long n = numel[ti], off = (long long)(blockIdx.x - block_first[ti]) * OPT_CHUNK;
+  const long long end = off + OPT_CHUNK < n ? off + OPT_CHUNK : n;
+  const bool alg = (((unsigned long long)(g + off)) & 15ull) == 0, ala = (((unsigned long long)(a + off)) & 15ull) == 0;
+  for (long long i = off + threadIdx.x * 4; i < end; i += 1024) {
+    if (i + 3 < end) {
+      f32x4 gv = load4_any(g + i, alg);
+      if (!first) {
+        const f32x4 av = load4_any(a + i, ala);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gv[e] = av[e] + gv[e];
+      }
+      if (ala) *(f32x4*)(a + i) = gv;
+      else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[i + e] = gv[e];
+      }
+    } else {
+      for (long long j = i; j < end; ++j) a[j] = first ? g[j] : a[j] + g[j];
+    }
+  }
+}
+
+template <bool GATED> int launch_step(const OptK& k, float max_norm, hipStream_t st) {
+  if (max_norm > 0.f) {
+    hipLaunchKernelGGL(opt_norm_kernel<GATED>, dim3(k.nblocks), dim3(256), 0, st, k);
+    EFFDET_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(opt_norm_final_kernel<GATED>, dim3(1), dim3(1024), 0, st, (const float*)k.partial, max_norm > 0.f ? k.nblocks : 0, k.norm,
+                     GATED ? k.has : k.g, k.steps, k.ntensors, k.ctl);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(opt_adamw_kernel<GATED>, dim3(k.nblocks), dim3(256), 0, st, k);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
 }  // namespace
 
 extern "C" int effdet_clip_adamw_step(const unsigned long long* params, const unsigned long long* grads, const unsigned long long* exp_avg,
@@ -143,15 +226,46 @@ extern "C" int effdet_clip_adamw_step(const unsigned long long* params, const un
   k.norm = scratch; k.partial = scratch + 64;                       // scratch: 64 + nblocks floats
   k.max_norm = max_norm; k.lr = lr; k.beta1 = beta1; k.beta2 = beta2; k.eps = eps; k.wd = weight_decay;
   k.steps = steps; k.nblocks = nblocks; k.ntensors = ntensors; k.write_grad = write_grad; k.hyper = hyper_dev;
-  hipStream_t st = (hipStream_t)stream;
-  if (max_norm > 0.f) {
-    hipLaunchKernelGGL(opt_norm_kernel, dim3(nblocks), dim3(256), 0, st, k);
-    EFFDET_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(opt_norm_final_kernel, dim3(1), dim3(1024), 0, st, (const float*)k.partial, max_norm > 0.f ? nblocks : 0, k.norm,
-                     grads, steps, ntensors);
+  return launch_step<false>(k, max_norm, (hipStream_t)stream);
+}
+
+extern "C" int effdet_train_gate(const float* loss, effdet_train_ctl_t* ctl, effdet_stream_t stream) {
+  if (!loss || !ctl) return EFFDET_EINVAL;
+  hipLaunchKernelGGL(train_gate_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, loss, ctl);
   EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(opt_adamw_kernel, dim3(nblocks), dim3(256), 0, st, k);
+  return EFFDET_OK;
+}
+
+extern "C" int effdet_grad_accumulate(const unsigned long long* grads, const unsigned long long* acc, const long long* numel,
+                                      const int* block_tensor, const int* block_first, int ntensors, int nblocks, effdet_train_ctl_t* ctl,
+                                      effdet_stream_t stream) {
+  if (!grads || !acc || !numel || !block_tensor || !block_first || !ctl || nblocks < 1 || ntensors < 1) return EFFDET_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3(nblocks), dim3(256), 0, st, grads, acc, numel, block_tensor, block_first,
+                     (const effdet_train_ctl_t*)ctl);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(train_pending_kernel, dim3(1), dim3(1), 0, st, ctl);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+extern "C" int effdet_clip_adamw_step_gated(const unsigned long long* params, const unsigned long long* grads, const unsigned long long* acc,
+                                            const unsigned long long* exp_avg, const unsigned long long* exp_avg_sq, const long long* numel,
+                                            const int* block_tensor, const int* block_first, int ntensors, int nblocks, float* scratch,
+                                            int* steps, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                            const float* hyper_dev, effdet_train_ctl_t* ctl, effdet_stream_t stream) {
+  if (!params || !grads || !acc || !exp_avg || !exp_avg_sq || !numel || !block_tensor || !block_first || !scratch || !steps || !ctl ||
+      nblocks < 1 || ntensors < 1)
+    return EFFDET_EINVAL;
+  OptK k{};
+  k.p = params; k.g = acc; k.has = grads; k.m = exp_avg; k.v = exp_avg_sq; k.n = numel; k.block_tensor = block_tensor; k.block_first = block_first;
+  k.norm = scratch; k.partial = scratch + 64;
+  k.max_norm = max_norm; k.lr = lr; k.beta1 = beta1; k.beta2 = beta2; k.eps = eps; k.wd = weight_decay;
+  k.steps = steps; k.nblocks = nblocks; k.ntensors = ntensors; k.write_grad = 0; k.hyper = hyper_dev; k.ctl = ctl;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch_step<true>(k, max_norm, st);
+  if (rc != EFFDET_OK) return rc;
+  hipLaunchKernelGGL(train_release_kernel, dim3(1), dim3(1), 0, st, ctl);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }

@@ -109,6 +109,104 @@ class GraphedTrainStep:
         return [sorted((k, repr(v)) for k, v in g.items() if k != 'params') for g in self.optimizer.param_groups]
 
 
+class GraphedTrainLoop:
+    """One iteration of the reference's loop body (train.py:104-120) per call, with no host sync:
+
+        loss = cls.mean() + reg.mean()
+        if bool(loss == 0): continue                      # skips backward, the boundary check below and total_loss.append
+        loss.backward()                                   # into the same .grad: no zero_grad between micro-batches
+        if (idx + 1) % grad_accumulation_steps == 0:
+            clip_grad_norm_(model.parameters(), 0.1); optimizer.step(); optimizer.zero_grad()
+        total_loss.append(loss.item())
+
+    Two captured hipGraphs over an optim.ClipAdamW(accumulate=True):
+      micro  zero_grad(set_to_none=True) -> forward -> loss scalar -> backward -> gate -> accumulate
+      tail   the gated clip + AdamW + release of the accumulation arena
+    __call__ replays micro, and tail as well when (idx + 1) % accumulation_steps == 0.  The host's control flow depends on idx alone;
+    everything that depends on data (loss == 0, whether anything is pending) is decided by the device gates of csrc/optim.hip.
+
+        loop = GraphedTrainLoop(model, optimizer, images, annotations, accumulation_steps=4)     # warm-up + capture
+        for epoch in ...:
+            loop.reset_epoch()                                   # optimizer.zero_grad() at the top of train(), idx = 0
+            for batch in loader:
+                loop.images.copy_(batch_images); loop.annotations.copy_(batch_annots)
+                cls_loss, reg_loss = loop()                      # device tensors, valid until the next call
+            scheduler.step(loop.epoch_mean())                    # np.mean(total_loss): the epoch's one device-to-host read
+
+    The warm-up iterations are whole steps (micro + tail) on the static batch, like GraphedTrainStep's; the constructor ends with
+    reset_epoch(), so they leave no trace in the meter.
+
+    A quirk of the reference that is reproduced, not fixed: a zero loss on a boundary idx skips the optimizer step AND the zero_grad,
+    so the gradients pending at that point ride into the next window and are applied together with it (with accumulation_steps = 2
+    and micro-batches D, Z, E, F from idx 4 on, the step at idx 7 applies D + E + F).
+
+    Not covered: DistributedDataParallel / DataParallel (the reference's own `continue` would leave the ranks with different numbers
+    of collectives; refused), and a checkpoint in the middle of a window (the arena is not part of state_dict)."""
+
+    def __init__(self, model, optimizer, images, annotations, accumulation_steps=1, warmup=2):
+        if isinstance(model, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)):
+            raise NotImplementedError('GraphedTrainLoop: %s is not supported -- a rank whose loss is 0 would skip collectives the other '
+                                      'ranks wait for (the reference has the same hazard); use GraphedTrainStep' % type(model).__name__)
+        if not getattr(optimizer, 'accumulate', False):
+            raise RuntimeError('GraphedTrainLoop needs optim.ClipAdamW(accumulate=True): the skip gate, the accumulation arena and the '
+                               'loss meter live in the optimizer')
+        if int(accumulation_steps) < 1:
+            raise ValueError('accumulation_steps must be >= 1')
+        if not images.is_cuda:
+            raise RuntimeError('GraphedTrainLoop needs GPU-resident batches')
+        self.model, self.optimizer, self.accumulation_steps = model, optimizer, int(accumulation_steps)
+        self.images, self.annotations = images.clone(), annotations.clone()      # static input buffers of the micro graph
+        self.idx = 0
+        side = torch.cuda.Stream()
+        self.stream = side
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):           # (the same warm-up and side-stream discipline as GraphedTrainStep)
+            optimizer.reset_epoch()
+            for _ in range(max(1, warmup)):
+                self._micro()
+                self._tail()
+            optimizer.reset_epoch()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        _build_pending_tables(model)
+        self.micro, self.tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.micro, stream=side):
+            self.losses = self._micro()
+        with torch.cuda.graph(self.tail, stream=side, pool=self.micro.pool()):
+            self._tail()
+        torch.cuda.synchronize()
+        ops.bump_param_generation()
+
+    def _micro(self):
+        self.optimizer.zero_grad(set_to_none=True)
+        cl, rl = self.model([self.images, self.annotations])
+        loss = cl.mean() + rl.mean()
+        loss.backward()
+        self.optimizer.accumulate_grads(loss)
+        return cl, rl
+
+    def _tail(self):
+        self.optimizer.step()
+
+    def __call__(self):
+        self.optimizer.sync_hyper()             # the lr schedule (train.py:133,269) reaches the captured update through the device buffer
+        self.micro.replay()
+        self.idx += 1
+        if self.idx % self.accumulation_steps == 0:
+            self.tail.replay()
+        ops.bump_param_generation()             # a replay may have rewritten the parameters through raw pointers (no Tensor._version bump)
+        self.optimizer._table['g_last'] = None  # the micro graph's memcpy node re-installed ITS gradient-pointer table (see GraphedTrainStep)
+        return self.losses
+
+    def epoch_mean(self):
+        """np.mean(total_loss) over the calls since reset_epoch() that were not skipped (NaN when there were none)."""
+        return self.optimizer.loss_meter()[0]
+
+    def reset_epoch(self):
+        self.idx = 0
+        self.optimizer.reset_epoch()
+
+
 def replay_vs_eager(graphed, eager_step=None):
     """Is a replay of `graphed` (a GraphedTrainStep over optim.ClipAdamW) the eager step?  From ONE saved state -- parameters, Adam
     moments + per-tensor step counters, the drop_connect counter, all restored IN PLACE so the graph's pointers stay valid -- run the eager

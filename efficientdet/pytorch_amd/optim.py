@@ -9,7 +9,18 @@ with `ClipAdamW(params, lr=..., max_norm=0.1).step()`: same arithmetic (clip coe
 clamped to 1; decoupled weight decay; bias-corrected moments), one pass for the norm and one for the update over a
 device-resident pointer table instead of ~17 foreach / multi-tensor launches.  Only the gradient pointers change from
 step to step (fresh tensors after zero_grad(set_to_none=True)); they are refreshed through a pinned staging buffer.
-fp32 parameters on one GPU; moments live in two flat arenas.  There is no CPU fallback."""
+fp32 parameters on one GPU; moments live in two flat arenas.  There is no CPU fallback.
+
+`ClipAdamW(..., accumulate=True)` adds the rest of the reference's loop body (train.py:104-120) as device-side gates, so that a
+captured loop (graph.GraphedTrainLoop) takes no host decision that depends on data:
+
+    loss = cls.mean() + reg.mean(); loss.backward()
+    opt.accumulate_grads(loss)          # `if bool(loss == 0): continue` + the sum over micro-batches + total_loss.append(loss.item())
+    if (idx + 1) % grad_accumulation_steps == 0:
+        opt.step()                      # clip + AdamW on the sum; a no-op when the micro-step just run was skipped or nothing is pending
+
+A third arena holds the sum, a 32-byte device control block (effdet_train_ctl_t) the skip flag, the number of pending micro-batches,
+the counters and the fp64 loss meter; loss_meter() reads it back (one device-to-host copy), reset_epoch() clears it."""
 import ctypes as C
 
 import numpy as np
@@ -20,12 +31,18 @@ from . import ops as ops_mod
 
 
 class ClipAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=0.0, write_clipped_grads=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=0.0, write_clipped_grads=False,
+                 accumulate=False):
+        if accumulate and write_clipped_grads:
+            raise ValueError('ClipAdamW: write_clipped_grads=True cannot be combined with accumulate=True (the step clips the sum held in '
+                             'the accumulation arena; p.grad holds one micro-batch and is not what was clipped)')
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm)
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise ValueError('ClipAdamW supports a single parameter group (the reference uses one, train.py:268)')
         self.write_clipped_grads = bool(write_clipped_grads)
+        self.accumulate = bool(accumulate)
+        self._grad_mask = None               # accumulate: which tensors had a gradient in the epoch's first micro-step
         self._table = None
         self._step = 0
         self._captured = False               # a step() ran under stream capture (its launch sequence is frozen in a hipGraph)
@@ -71,6 +88,13 @@ class ClipAdamW(torch.optim.Optimizer):
             'hyper': torch.zeros(6, dtype=torch.float32, device=dev), 'hyper_host': torch.zeros(6, dtype=torch.float32).pin_memory(),
             'hyper_last': None, 'hyper_evt': None,
         }
+        if self.accumulate:
+            # the sum over a window's micro-batches (same offsets as the moments; written, not added to, by the first micro-batch of a
+            # window, so it is never zeroed) and the control block (effdet_train_ctl_t, 32 bytes; zero = start of an epoch)
+            self.grad_acc = torch.zeros(int(offs[-1]), dtype=torch.float32, device=dev)
+            t['a_ptr'] = i64([self.grad_acc.data_ptr() + 4 * int(o) for o in offs[:-1]])
+            t['ctl'] = torch.zeros(C.sizeof(L.TrainCtl) // 8, dtype=torch.int64, device=dev)
+            self._grad_mask = None
         for i, p in enumerate(ps):                                     # per-parameter views for state_dict()
             self.state[p] = {'step': torch.tensor(0.0),                # refreshed from the device counters in state_dict()
                              'exp_avg': self.exp_avg[int(offs[i]):int(offs[i]) + numel[i]].view_as(p),
@@ -80,7 +104,8 @@ class ClipAdamW(torch.optim.Optimizer):
     # ---- checkpointing (train.py:279-291 saves only the model; resuming needs the moments + per-tensor step counters) ----
     def state_dict(self):
         """torch.optim.AdamW-compatible: per-parameter {'step', 'exp_avg', 'exp_avg_sq'}; 'step' is read back from the
-        device-resident counters (they advance on the GPU), the moments are views of the two arenas."""
+        device-resident counters (they advance on the GPU), the moments are views of the two arenas.  accumulate=True adds nothing:
+        a checkpoint is an epoch boundary, where nothing is pending, so the accumulation arena and the control block are not saved."""
         if self._table is not None:
             steps = self._table['steps'].cpu()
             for i, p in enumerate(self._table['params']):
@@ -133,20 +158,17 @@ class ClipAdamW(torch.optim.Optimizer):
         ev = torch.cuda.Event(); ev.record()
         t['hyper_evt'], t['hyper_last'] = ev, hv
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        if len(self.param_groups) != 1:         # (before anything is uploaded or counted: a refused step leaves no trace)
-            raise RuntimeError('ClipAdamW honours ONE parameter group (the reference builds one, train.py:266); got %d -- other '
-                               "groups' lr / weight_decay would be silently ignored" % len(self.param_groups))
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _ensure_table(self):
         if self._table is None or self._table['p_sig'] != [p.data_ptr() for p in self._table['params']]:
+            if self.accumulate and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('ClipAdamW: the device tables are not built (or a parameter moved) and the stream is capturing: '
+                                   'building them allocates and uploads; run one eager accumulate_grads() + step() before capturing')
             self._build()
-        t, g = self._table, self.param_groups[0]
+        return self._table
+
+    def _grad_ptrs(self):
         ptrs = []
-        for p in t['params']:
+        for p in self._table['params']:
             gr = p.grad
             if gr is None:
                 ptrs.append(0)
@@ -154,6 +176,10 @@ class ClipAdamW(torch.optim.Optimizer):
             if gr.dtype != torch.float32 or not gr.is_contiguous():
                 gr = gr.float().contiguous(); p.grad = gr
             ptrs.append(gr.data_ptr())
+        return ptrs
+
+    def _upload_grad_ptrs(self, ptrs):
+        t = self._table
         if ptrs != t['g_last']:                                        # (DDP bucket views keep their addresses: no upload)
             if torch.cuda.is_current_stream_capturing():
                 # hipGraph capture: the memcpy node keeps reading this pinned buffer on every replay, so it gets a buffer of
@@ -170,8 +196,9 @@ class ClipAdamW(torch.optim.Optimizer):
                 ev = torch.cuda.Event(); ev.record()
                 t['g_evt'][slot] = ev
                 t['g_last'] = ptrs
-        self._step += 1
-        b1, b2 = g['betas']
+
+    def _hyper_ready(self):
+        t = self._table
         if torch.cuda.is_current_stream_capturing():
             self._captured = True
             if t['hyper_last'] is None:
@@ -181,7 +208,37 @@ class ClipAdamW(torch.optim.Optimizer):
                                    'the stream is capturing (no upload possible); call sync_hyper() before capturing')
         else:
             self.sync_hyper()
+
+    def _one_group(self):
+        if len(self.param_groups) != 1:         # (before anything is uploaded or counted: a refused step leaves no trace)
+            raise RuntimeError('ClipAdamW honours ONE parameter group (the reference builds one, train.py:266); got %d -- other '
+                               "groups' lr / weight_decay would be silently ignored" % len(self.param_groups))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        self._one_group()
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        t, g = self._ensure_table(), self.param_groups[0]
+        if not self.accumulate:
+            self._upload_grad_ptrs(self._grad_ptrs())
+        self._step += 1
+        b1, b2 = g['betas']
+        self._hyper_ready()
         ops_mod.bump_param_generation()      # parameters are rewritten through raw pointers: Tensor._version does not move
+        if self.accumulate:
+            # the gated form: the sum in the arena is the gradient; which tensors have one is what the last accumulate_grads() uploaded.
+            # Nothing moves when the micro-step just run was skipped or nothing is pending (decided on the device).
+            Lb = L.require('effdet_clip_adamw_step_gated')
+            L.check(Lb.effdet_clip_adamw_step_gated(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['a_ptr']), L.ptr(t['m_ptr']), L.ptr(t['v_ptr']),
+                                                    L.ptr(t['numel']), L.ptr(t['block_tensor']), L.ptr(t['block_first']), t['n'], t['nblocks'],
+                                                    L.ptr(t['scratch']), L.ptr(t['steps']), C.c_float(g['max_norm'] or 0.0),
+                                                    C.c_float(g['lr']), C.c_float(b1), C.c_float(b2), C.c_float(g['eps']),
+                                                    C.c_float(g['weight_decay']), L.ptr(t['hyper']), L.ptr(t['ctl']), L.stream_ptr()),
+                    'effdet_clip_adamw_step_gated')
+            return loss
         L.check(L.lib().effdet_clip_adamw_step(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['m_ptr']), L.ptr(t['v_ptr']), L.ptr(t['numel']),
                                                L.ptr(t['block_tensor']), L.ptr(t['block_first']), t['n'], t['nblocks'],
                                                L.ptr(t['scratch']), L.ptr(t['steps']), C.c_float(g['max_norm'] or 0.0),
@@ -189,6 +246,69 @@ class ClipAdamW(torch.optim.Optimizer):
                                                C.c_float(g['weight_decay']), int(self.write_clipped_grads), L.ptr(t['hyper']), L.stream_ptr()),
                 'effdet_clip_adamw_step')
         return loss
+
+    # ---- the reference's loop body around the step (train.py:104-120), accumulate=True only ----
+    def _need_accumulate(self, what):
+        if not self.accumulate:
+            raise RuntimeError('ClipAdamW.%s needs ClipAdamW(accumulate=True)' % what)
+
+    @torch.no_grad()
+    def accumulate_grads(self, loss):
+        """Call after loss.backward() with the micro-step's fp32 DEVICE scalar loss.  Device side, no host sync: loss == 0 (the
+        reference's `if bool(loss == 0): continue`; -0.0 skips, NaN and Inf do not) marks the micro-step skipped and nothing else
+        happens; otherwise the loss enters the meter and the current p.grad tensors are added into the accumulation arena (the first
+        micro-batch of a window is copied, not added).
+        The tensors that have a gradient must be the same ones in every micro-step from reset_epoch() to reset_epoch(): a window's first
+        micro-batch overwrites the arena only where it has a gradient, and the host cannot see whether the device skipped a boundary
+        step and let pending gradients ride into the next window (train.py's own behaviour), so a window never ends for certain
+        before the epoch does."""
+        self._need_accumulate('accumulate_grads')
+        self._one_group()
+        if not (isinstance(loss, torch.Tensor) and loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+            raise ValueError('ClipAdamW.accumulate_grads needs the loss as a one-element fp32 GPU tensor (it is read on the device)')
+        t = self._ensure_table()
+        ptrs = self._grad_ptrs()
+        mask = [x != 0 for x in ptrs]
+        if self._grad_mask is not None and mask != self._grad_mask:
+            changed = [i for i, (a, b) in enumerate(zip(mask, self._grad_mask)) if a != b]
+            raise RuntimeError('ClipAdamW.accumulate_grads: the set of tensors that have a gradient changed between micro-steps '
+                               '(%d tensors, first: parameter %d); the accumulation arena would mix windows' % (len(changed), changed[0]))
+        self._grad_mask = mask
+        self._upload_grad_ptrs(ptrs)
+        if torch.cuda.is_current_stream_capturing():
+            self._captured = True
+        Lb = L.require('effdet_train_gate', 'effdet_grad_accumulate')
+        L.check(Lb.effdet_train_gate(L.ptr(loss.detach()), L.ptr(t['ctl']), L.stream_ptr()), 'effdet_train_gate')
+        L.check(Lb.effdet_grad_accumulate(L.ptr(t['g_ptr']), L.ptr(t['a_ptr']), L.ptr(t['numel']), L.ptr(t['block_tensor']),
+                                          L.ptr(t['block_first']), t['n'], t['nblocks'], L.ptr(t['ctl']), L.stream_ptr()),
+                'effdet_grad_accumulate')
+
+    def _ctl(self):
+        return L.TrainCtl.from_buffer_copy(self._table['ctl'].cpu().numpy().tobytes())       # the one device-to-host read
+
+    def loss_meter(self):
+        """-> (mean, count, skipped, applied): np.mean(total_loss) of train.py:133 over the micro-steps since reset_epoch() that were not
+        skipped (a sequential fp64 sum of the fp32 losses; NaN for count 0, as np.mean([]) is), their number, the number of skipped
+        micro-steps and the number of optimizer steps applied.  One device-to-host read."""
+        self._need_accumulate('loss_meter')
+        if self._table is None:
+            return float('nan'), 0, 0, 0
+        c = self._ctl()
+        return (c.loss_sum / c.loss_count if c.loss_count else float('nan')), int(c.loss_count), int(c.skipped), int(c.applied)
+
+    def pending(self):
+        """Micro-batches summed in the arena and not yet applied (one device-to-host read)."""
+        self._need_accumulate('pending')
+        return 0 if self._table is None else int(self._ctl().pending)
+
+    def reset_epoch(self):
+        """optimizer.zero_grad() at the top of train() (train.py:97): pending gradients are dropped, the meter and the counters cleared."""
+        self._need_accumulate('reset_epoch')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ClipAdamW.reset_epoch under stream capture: an epoch boundary is a host event, not part of a captured step')
+        if self._table is not None:
+            self._table['ctl'].zero_()
+        self._grad_mask = None
 
     def grad_norm(self):
         """Total gradient norm measured by the last step() (device scalar; clipping enabled only)."""

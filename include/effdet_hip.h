@@ -556,6 +556,45 @@ int effdet_clip_adamw_step(const unsigned long long* params, const unsigned long
                            int* steps, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
                            int write_grad, const float* hyper_dev, effdet_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The reference's loop body around that tail (train.py:104-120) as device-side gates, so that a captured loop takes no
+ * host decision that depends on data: `if bool(loss == 0): continue`, gradient accumulation over grad_accumulation_steps
+ * micro-batches, and total_loss.append(loss.item()).  Additive entry points (same ABI generation); all of them only
+ * enqueue kernels (no allocation, no synchronisation, no memset node: capture-safe) and return EFFDET_EINVAL, without
+ * launching anything, for a null table, nblocks < 1 or ntensors < 1.
+ *
+ * effdet_train_ctl_t is a DEVICE control block (32 bytes, zero = start of an epoch), written only by one-thread launches
+ * that are ordered behind every reader.
+ *
+ * effdet_train_gate: loss is the micro-step's fp32 DEVICE scalar.  skip = (loss == 0.0f) -- the reference's predicate: -0.0
+ *   skips, NaN and Inf do not.  Skipped: skipped += 1.  Otherwise loss_sum += (double)loss and loss_count += 1.
+ * effdet_grad_accumulate: over the optimizer's block table.  skip: nothing is read or written (the gradient buffers may hold
+ *   anything).  Otherwise, for every tensor with grads[i] != 0, acc[i] = grads[i] when pending == 0 and acc[i] += grads[i]
+ *   when it is not (the first micro-batch of a window writes, so the arena is never zeroed); then pending += 1.  acc is a
+ *   table of ntensors device pointers like grads; 16-byte accesses where the addresses allow, the same values where not.
+ * effdet_clip_adamw_step_gated: when skip is set or pending == 0, parameters, both moments, the step counters, the norm
+ *   scratch and the arena stay untouched bit for bit.  Otherwise effdet_clip_adamw_step's arithmetic with acc[i] as the
+ *   gradient of every tensor with grads[i] != 0 (write_grad = 0); then pending = 0 and applied += 1.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int skip;             /* the micro-step just gated is skipped */
+  int pending;          /* micro-batches summed in the accumulation arena */
+  int applied;          /* optimizer steps applied */
+  int skipped;          /* micro-steps skipped */
+  long long loss_count; /* the meter: non-skipped micro-steps ... */
+  double loss_sum;      /* ... and the sequential fp64 sum of their fp32 losses */
+} effdet_train_ctl_t;
+int effdet_train_gate(const float* loss, effdet_train_ctl_t* ctl, effdet_stream_t stream);
+int effdet_grad_accumulate(const unsigned long long* grads, const unsigned long long* acc, const long long* numel,
+                           const int* block_tensor, const int* block_first, int ntensors, int nblocks,
+                           effdet_train_ctl_t* ctl, effdet_stream_t stream);
+int effdet_clip_adamw_step_gated(const unsigned long long* params, const unsigned long long* grads,
+                                 const unsigned long long* acc, const unsigned long long* exp_avg,
+                                 const unsigned long long* exp_avg_sq, const long long* numel, const int* block_tensor,
+                                 const int* block_first, int ntensors, int nblocks, float* scratch, int* steps,
+                                 float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                 const float* hyper_dev, effdet_train_ctl_t* ctl, effdet_stream_t stream);
+
 /* Row repack with zero channel padding: dst[b][pix][0..Cpad) = src[src_off + b*src_bstride + pix*src_ld + c]
  * for c < C, 0 beyond (makes an unaligned-channel gradient map consumable by effdet_conv2d). */
 int effdet_pad_rows(const void* src, void* dst, int dtype, long long src_off, long long src_bstride, int src_ld,
