@@ -2,6 +2,10 @@
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
+
+``SIGNATURES`` declares every entry point's return and parameter types once; ``lib()`` binds them (``restype`` / ``argtypes``) at
+load, so no call site casts an argument: ints, floats and addresses (``ptr()``, ``stream_ptr()``, ``ndarray.ctypes.data``) are passed
+as they are.  A new entry point is one line in that table.
 """
 import ctypes as C
 import os
@@ -97,22 +101,108 @@ TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
 
 _lib = None
 
-# every symbol include/effdet_hip.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    'effdet_conv2d', 'effdet_conv2d_kernel', 'effdet_tuning_set', 'effdet_conv2d_wgrad', 'effdet_conv2d_wgrad_workspace_bytes', 'effdet_conv2d_wgrad_splits', 'effdet_conv2d_wgrad_seg_slabs', 'effdet_conv2d_wgrad_kernel', 'effdet_pack_conv_weight', 'effdet_scale_pack_weight', 'effdet_unpack_conv_wgrad', 'effdet_unpack_conv_wgrad_bn', 'effdet_unpack_conv_wgrad_batch', 'effdet_backward_tail', 'effdet_dw_unpack_wgrad_bn', 'effdet_prepare_params',
-    'effdet_bn_fold', 'effdet_bn_param_grad', 'effdet_dw_pack_weight', 'effdet_dw_unpack_wgrad', 'effdet_bifpn_weight_bwd',
-    'effdet_dwconv_fwd', 'effdet_dwconv_fwd_pool_groups', 'effdet_mbconv_expand_dw_fwd', 'effdet_mbconv_expand_dw_pool_groups', 'effdet_dwconv_dgrad', 'effdet_dwconv_wgrad', 'effdet_dwconv_wgrad_workspace_bytes', 'effdet_dwconv_bwd', 'effdet_dwconv_bwd_workspace_bytes', 'effdet_pw_bwd', 'effdet_pw_bwd_slabs', 'effdet_pw_dgrad_se', 'effdet_pw_dgrad_se_supported',
-    'effdet_se_gate_fwd', 'effdet_se_gate_fwd_split', 'effdet_channel_scale', 'effdet_se_dgate', 'effdet_se_dgate_slabs', 'effdet_se_dgate_from_wgrad', 'effdet_se_gate_bwd', 'effdet_se_gate_bwd_workspace_floats', 'effdet_se_bwd_apply',
-    'effdet_act_bwd', 'effdet_add_inplace', 'effdet_colsum', 'effdet_bifpn_fuse_fwd', 'effdet_bifpn_fuse_fwd2', 'effdet_bifpn_fuse_bwd',
-    'effdet_anchors', 'effdet_num_anchors', 'effdet_decode_score', 'effdet_nms_workspace_bytes', 'effdet_nms',
-    'effdet_gather_dets', 'effdet_loss_workspace_bytes', 'effdet_focal_loss_fwd', 'effdet_focal_loss_bwd', 'effdet_focal_loss_bwd_pix', 'effdet_focal_loss_fwd_grad', 'effdet_focal_loss_bwd_reg',
-    'effdet_clip_adamw_step', 'effdet_opt_chunk', 'effdet_train_gate', 'effdet_grad_accumulate', 'effdet_clip_adamw_step_gated',
-    'effdet_drop_connect_scales', 'effdet_philox4x32_10', 'effdet_preprocess_batch', 'effdet_finalize_dets', 'effdet_voc_match', 'effdet_voc_ap', 'effdet_voc_ap_workspace_bytes',
-    'effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes', 'effdet_head_out_bwd',
-    'effdet_augment_train', 'effdet_augment_resize', 'effdet_augment_boxes',
-    'effdet_jpeg_probe', 'effdet_jpeg_entropy_batch', 'effdet_jpeg_reconstruct',
-    'effdet_nhwc_to_nchw_f32', 'effdet_nchw_f32_to_nhwc', 'effdet_pad_rows', 'effdet_to_split', 'effdet_to_split2', 'effdet_version', 'effdet_abi_version',
-]
+# The one place where the C signatures of include/effdet_hip.h live: '<return>:<parameters>' per entry point, in the header's order,
+# one letter per C type.  lib() turns each entry into restype / argtypes, so a call site passes plain Python ints and floats and ctypes
+# converts (or refuses) them by the declared type; tests/test_abi.py parses the header's prototypes and compares them with this table.
+#   i int    q long long    I unsigned    Q unsigned long long    f float    d double    s effdet_stream_t
+#   p any pointer (typed or void*, struct, scalar or array): c_void_p takes an int address, None, byref(struct), a ctypes array
+#   returns: i, q, z const char*, v void
+_CTYPE = {'i': C.c_int, 'q': C.c_longlong, 'I': C.c_uint, 'Q': C.c_ulonglong, 'f': C.c_float, 'd': C.c_double,
+          'p': C.c_void_p, 's': C.c_void_p, 'z': C.c_char_p, 'v': None}
+SIGNATURES = {
+    'effdet_conv2d': 'i:ps',
+    'effdet_scale_pack_weight': 'i:pppiiiis',
+    'effdet_conv2d_kernel': 'i:p',
+    'effdet_tuning_set': 'i:ii',
+    'effdet_conv2d_wgrad_workspace_bytes': 'q:p',
+    'effdet_conv2d_wgrad_splits': 'i:p',
+    'effdet_conv2d_wgrad_seg_slabs': 'i:ppp',
+    'effdet_conv2d_wgrad_kernel': 'i:p',
+    'effdet_conv2d_wgrad': 'i:ppqs',
+    'effdet_pack_conv_weight': 'i:pppiiiiiiis',
+    'effdet_unpack_conv_wgrad': 'i:pppppiiiiiiipppis',
+    'effdet_unpack_conv_wgrad_bn': 'i:pppppppppiiiiiipis',
+    'effdet_unpack_conv_wgrad_batch': 'i:pis',
+    'effdet_backward_tail': 'i:pis',
+    'effdet_prepare_params': 'i:pppis',
+    'effdet_bn_fold': 'i:ppppfpppis',
+    'effdet_bn_param_grad': 'i:ppppppis',
+    'effdet_dwconv_fwd_pool_groups': 'i:iiiiii',
+    'effdet_dwconv_fwd': 'i:pppppppiiiiiiiiiiiis',
+    'effdet_mbconv_expand_dw_pool_groups': 'i:iiiii',
+    'effdet_mbconv_expand_dw_fwd': 'i:pppppppppiiiiiiiiiiis',
+    'effdet_dwconv_dgrad': 'i:pppppiiiiiiiiiiis',
+    'effdet_dwconv_wgrad_workspace_bytes': 'q:iiiiiiiiiii',
+    'effdet_dwconv_wgrad': 'i:pppppqiiiiiiiiiiiis',
+    'effdet_dwconv_bwd_workspace_bytes': 'q:iiiiiiiiiii',
+    'effdet_dwconv_bwd': 'i:ppppppppqiiiiiiiiiiis',
+    'effdet_pw_bwd_slabs': 'i:qii',
+    'effdet_pw_bwd': 'i:ppppppppqiis',
+    'effdet_pw_dgrad_se_supported': 'i:qii',
+    'effdet_pw_dgrad_se': 'i:ppppppppqiiiis',
+    'effdet_dw_pack_weight': 'i:ppiis',
+    'effdet_dw_unpack_wgrad': 'i:pppppiis',
+    'effdet_dw_unpack_wgrad_bn': 'i:pppppppppiis',
+    'effdet_se_gate_fwd': 'i:pipppppppiiifs',
+    'effdet_se_gate_fwd_split': 'i:pippppppppiiifs',
+    'effdet_channel_scale': 'i:pppiiiqis',
+    'effdet_se_dgate_slabs': 'i:q',
+    'effdet_se_dgate_from_wgrad': 'i:pppppiiiis',
+    'effdet_se_dgate': 'i:pppiiiqis',
+    'effdet_se_gate_bwd_workspace_floats': 'q:iii',
+    'effdet_se_gate_bwd': 'i:piippppppppppppiiifs',
+    'effdet_se_bwd_apply': 'i:pppppiiqis',
+    'effdet_act_bwd': 'i:ppppiiiqs',
+    'effdet_add_inplace': 'i:ppiqs',
+    'effdet_colsum': 'i:ppiqiis',
+    'effdet_bifpn_fuse_fwd': 'i:pppppiiiiiiiiis',
+    'effdet_bifpn_fuse_fwd2': 'i:ppppppiiiiiiiiips',
+    'effdet_bifpn_fuse_bwd': 'i:pppppppiiippiiiiiiiiis',
+    'effdet_bifpn_weight_bwd': 'i:pppiis',
+    'effdet_anchors': 'i:piis',
+    'effdet_num_anchors': 'q:ii',
+    'effdet_decode_score': 'i:ppppppiqiffs',
+    'effdet_nms_workspace_bytes': 'q:iq',
+    'effdet_nms': 'i:ppffpppqiqs',
+    'effdet_gather_dets': 'i:ppppppppiqs',
+    'effdet_loss_workspace_bytes': 'q:iqi',
+    'effdet_focal_loss_fwd': 'i:ppppppqiqiis',
+    'effdet_focal_loss_bwd': 'i:ppppppppiiqiis',
+    'effdet_focal_loss_bwd_pix': 'i:pppppppipiiqiis',
+    'effdet_focal_loss_fwd_grad': 'i:ppppppqpiiiqiis',
+    'effdet_focal_loss_bwd_reg': 'i:ppppppiiiqis',
+    'effdet_opt_chunk': 'i:',
+    'effdet_clip_adamw_step': 'i:pppppppiippffffffips',
+    'effdet_train_gate': 'i:pps',
+    'effdet_grad_accumulate': 'i:pppppiips',
+    'effdet_clip_adamw_step_gated': 'i:ppppppppiippffffffpps',
+    'effdet_pad_rows': 'i:ppiqqiiiiis',
+    'effdet_to_split': 'i:ppqs',
+    'effdet_to_split2': 'i:pppqps',
+    'effdet_nhwc_to_nchw_f32': 'i:ppiiiiis',
+    'effdet_nchw_f32_to_nhwc': 'i:ppiiiiiis',
+    'effdet_drop_connect_scales': 'i:ppiiQQps',
+    'effdet_philox4x32_10': 'v:ppp',
+    'effdet_preprocess_batch': 'i:pppppppiiiiipps',
+    'effdet_finalize_dets': 'i:pppppfiippiqs',
+    'effdet_voc_match': 'i:ppppiiiidppps',
+    'effdet_voc_ap_workspace_bytes': 'q:q',
+    'effdet_voc_ap': 'i:ppqpipqppppps',
+    'effdet_coco_slots': 'q:iii',
+    'effdet_coco_match': 'i:ppppiiiipipiipppppps',
+    'effdet_coco_accumulate_workspace_bytes': 'q:qi',
+    'effdet_coco_accumulate': 'i:pppppqIpipipiipipqppps',
+    'effdet_augment_train': 'i:ppppiippppiipps',
+    'effdet_augment_resize': 'i:pppiiippiipps',
+    'effdet_augment_boxes': 'i:ppiiipiddpps',
+    'effdet_jpeg_probe': 'i:pqp',
+    'effdet_jpeg_entropy_batch': 'i:ppipqppip',
+    'effdet_jpeg_reconstruct': 'i:ppiiipppps',
+    'effdet_head_out_bwd': 'i:pppppiqqs',
+    'effdet_version': 'z:',
+    'effdet_abi_version': 'i:',
+}
+SYMBOLS = list(SIGNATURES)
 
 
 def lib():
@@ -130,13 +220,10 @@ def lib():
             raise RuntimeError('%s has ABI generation %d, this binding needs %d: rebuild it (`python -m efficientdet.pytorch_amd.build`)'
                                % (LIB_PATH, got, ABI_VERSION))
         _lib = cand
-        _lib.effdet_version.restype = C.c_char_p
-        for name in ('effdet_num_anchors', 'effdet_nms_workspace_bytes', 'effdet_loss_workspace_bytes',
-                     'effdet_conv2d_wgrad_workspace_bytes', 'effdet_dwconv_wgrad_workspace_bytes', 'effdet_dwconv_bwd_workspace_bytes',
-                     'effdet_se_gate_bwd_workspace_floats', 'effdet_voc_ap_workspace_bytes', 'effdet_coco_slots',
-                     'effdet_coco_accumulate_workspace_bytes'):
-            if hasattr(_lib, name):
-                getattr(_lib, name).restype = C.c_longlong
+        for name, sig in SIGNATURES.items():
+            f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
+            if f is not None:
+                f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]
     return _lib
 
 
@@ -163,12 +250,13 @@ def stream_ptr():
     """hipStream_t of torch's current stream on the current device (every launch asks: the raw-handle query is ~0.3 us, the
     torch.cuda.current_stream() object ~9 us -- 1.2 ms of host time per eager D0 train step)."""
     if _raw_stream is not None:
-        return C.c_void_p(_raw_stream(torch.cuda.current_device()))
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _raw_stream(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
 
 
 def ptr(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
+    """Device address of tensor t as an int (None for no tensor: a null pointer)."""
+    return None if t is None else t.data_ptr()
 
 
 def dtype_code(t):

@@ -328,7 +328,6 @@ class ParamPrep:
             self.dirty = True
 
     def _build(self):
-        import numpy as np
         keys = list(self.jobs)
         dev = self.jobs[keys[0]][1][0].device
         offs, total = [], 0
@@ -546,7 +545,7 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
            ('conv_wgrad_split_kernel' if split else
             ('conv_wgrad_thin_kernel' if int(L.lib().effdet_conv2d_wgrad_kernel(C.byref(d))) == 1 else
              ('conv_wgrad_f32dma_kernel<4,bf16x3>' if d.dtype == L.F32_BF16X3 else 'conv_wgrad_f32dma_kernel<8>'))), flops,
-           lambda: L.check(L.lib().effdet_conv2d_wgrad(C.byref(d), L.ptr(ws), C.c_longlong(nbytes), L.stream_ptr()),
+           lambda: L.check(L.lib().effdet_conv2d_wgrad(C.byref(d), L.ptr(ws), nbytes, L.stream_ptr()),
                            'effdet_conv2d_wgrad'),
            'k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, sum(z.B * z.H * z.W for z in dzs)),
            nbytes=float(x0.t.element_size() * Cin * sum(x.B * x.H * x.W for x in xs) +
@@ -709,8 +708,18 @@ def to_split(t):
     """plain fp32 tensor (rows of whole 32-channel groups) -> the same shape in the split layout (out of place)."""
     assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() % 32 == 0
     out = torch.empty_like(t)
-    L.check(L.lib().effdet_to_split(L.ptr(t), L.ptr(out), C.c_longlong(t.numel()), L.stream_ptr()), 'effdet_to_split')
+    L.check(L.lib().effdet_to_split(L.ptr(t), L.ptr(out), t.numel(), L.stream_ptr()), 'effdet_to_split')
     return out
+
+
+def to_split2(src, dst_split, dst_hsplit, n, flag=None):
+    """The first n elements of the plain fp32 tensor src -> the split layout at address dst_split and / or the H-split layout at address
+    dst_hsplit (ints; None = that form is not wanted), out of place, in one pass.  flag (range_flag(device) or None): the watch word a
+    value that does not fit the H-split layout sets.  Without an H-split destination this is the single-layout pass of to_split."""
+    if dst_hsplit is None:
+        L.check(L.lib().effdet_to_split(L.ptr(src), dst_split, n, L.stream_ptr()), 'effdet_to_split')
+    else:
+        L.check(L.lib().effdet_to_split2(L.ptr(src), dst_split, dst_hsplit, n, L.ptr(flag), L.stream_ptr()), 'effdet_to_split2')
 
 
 def nhwc_to_nchw(m):
@@ -741,7 +750,7 @@ def bn_fold(gamma, beta, mean, var, eps=1e-3):
             return hit[0], hit[1], hit[2]
         PREP.record(key, PREP_BNFOLD, (gamma, beta, mean, var), (C_,), torch.float32, (3, C_), eps)
     out = torch.empty((3, C_), dtype=torch.float32, device=gamma.device)     # scale | shift | invstd
-    L.check(L.lib().effdet_bn_fold(L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(var), C.c_float(eps),
+    L.check(L.lib().effdet_bn_fold(L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(var), float(eps),
                                    L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), C_, L.stream_ptr()), 'effdet_bn_fold')
     if PREP is not None:
         PREP.bn_src[out[0].data_ptr()] = (gamma, var, eps)
@@ -857,7 +866,7 @@ def dwconv_wgrad(x, dz, k, stride, pad_t, pad_l, in_act=ACT_NONE):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.t.device)
     traffic = x.t.element_size() * x.B * x.C * (x.H * x.W + dz.H * dz.W)
     _timed('dw_wgrad_lds_kernel', traffic, lambda: L.check(L.lib().effdet_dwconv_wgrad(
-        L.ptr(x.tensor()), L.ptr(dz.tensor()), L.ptr(g), L.ptr(g[k * k]), L.ptr(ws), C.c_longlong(nbytes), *geo, in_act, L.stream_ptr()),
+        L.ptr(x.tensor()), L.ptr(dz.tensor()), L.ptr(g), L.ptr(g[k * k]), L.ptr(ws), nbytes, *geo, in_act, L.stream_ptr()),
         'effdet_dwconv_wgrad'), 'BYTES k%d s%d C%d %dx%d' % (k, stride, x.C, x.H, x.W))
     return g[:k * k], g[k * k]
 
@@ -878,7 +887,7 @@ def dwconv_bwd(dz, w_kkc, scale, zprev, k, stride, pad_t, pad_l):
     traffic = dz.t.element_size() * dz.B * dz.C * (dz.H * dz.W + 2 * H * W)
     _timed('dw_bwd_lds_kernel', traffic, lambda: L.check(L.lib().effdet_dwconv_bwd(
         L.ptr(dz.tensor()), L.ptr(w_kkc), L.ptr(scale), L.ptr(zprev.tensor()), L.ptr(dx.t), L.ptr(g), L.ptr(g[k * k]), L.ptr(ws),
-        C.c_longlong(nbytes), *geo, L.stream_ptr()), 'effdet_dwconv_bwd'), 'BYTES k%d s%d C%d %dx%d' % (k, stride, dz.C, H, W))
+        nbytes, *geo, L.stream_ptr()), 'effdet_dwconv_bwd'), 'BYTES k%d s%d C%d %dx%d' % (k, stride, dz.C, H, W))
     return dx, g[:k * k], g[k * k]
 
 
@@ -888,7 +897,7 @@ def pw_bwd(dz, x, w_expand, scale, res=None):
     Cexp, Cin = w_expand.shape[0], w_expand.shape[1]
     M = dz.B * dz.H * dz.W
     dense = all(m is None or (m.ld == m.C and m.off == 0 and m.bstride == m.H * m.W * m.C and m.dtype == torch.float32) for m in (dz, x, res))
-    S = int(L.lib().effdet_pw_bwd_slabs(C.c_longlong(M), Cin, Cexp)) if dense and dz.C == Cexp and x.C == Cin else 0
+    S = int(L.lib().effdet_pw_bwd_slabs(M, Cin, Cexp)) if dense and dz.C == Cexp and x.C == Cin else 0
     if S < 1:
         return None
     dx = Map.new(x.B, x.H, x.W, Cin, torch.float32, x.t.device)
@@ -896,7 +905,7 @@ def pw_bwd(dz, x, w_expand, scale, res=None):
     slabs, parts = ws[:S * Cexp * Cin].view(S, Cexp, 1, Cin), ws[S * Cexp * Cin:].view(S, Cexp)
     _timed('conv_pw_bwd_kernel', 4.0 * Cin * Cexp * M, lambda: L.check(L.lib().effdet_pw_bwd(
         L.ptr(dz.tensor()), L.ptr(x.tensor()), L.ptr(w_expand.detach()), L.ptr(scale), L.ptr(res.tensor() if res is not None else None), L.ptr(dx.t),
-        L.ptr(slabs), L.ptr(parts), C.c_longlong(M), Cin, Cexp, L.stream_ptr()), 'effdet_pw_bwd'), 'Cin%d Cexp%d M%d' % (Cin, Cexp, M),
+        L.ptr(slabs), L.ptr(parts), M, Cin, Cexp, L.stream_ptr()), 'effdet_pw_bwd'), 'Cin%d Cexp%d M%d' % (Cin, Cexp, M),
         nbytes=4.0 * M * (Cexp + (3 if res is not None else 2) * Cin))
     return dx, slabs, parts
 
@@ -907,12 +916,12 @@ def pw_dgrad_se(dy, w_project, scale, rowscale, gate, dpool, zd):
     Cout, Cexp = w_project.shape[0], w_project.shape[1]
     M = dy.B * dy.H * dy.W
     dense = all(m.ld == m.C and m.off == 0 and m.bstride == m.H * m.W * m.C and m.dtype == torch.float32 for m in (dy, zd))
-    if not dense or dy.C != Cout or zd.C != Cexp or not int(L.lib().effdet_pw_dgrad_se_supported(C.c_longlong(M), Cout, Cexp)):
+    if not dense or dy.C != Cout or zd.C != Cexp or not int(L.lib().effdet_pw_dgrad_se_supported(M, Cout, Cexp)):
         return None
     dz = Map.new(zd.B, zd.H, zd.W, Cexp, torch.float32, zd.t.device)
     _timed('conv_pw_dgrad_se_kernel', 2.0 * Cout * Cexp * M, lambda: L.check(L.lib().effdet_pw_dgrad_se(
         L.ptr(dy.tensor()), L.ptr(w_project.detach()), L.ptr(scale), L.ptr(rowscale), L.ptr(gate), L.ptr(dpool), L.ptr(zd.tensor()), L.ptr(dz.t),
-        C.c_longlong(M), dy.H * dy.W, dy.B, Cout, Cexp, L.stream_ptr()), 'effdet_pw_dgrad_se'), 'Cout%d Cexp%d M%d' % (Cout, Cexp, M),
+        M, dy.H * dy.W, dy.B, Cout, Cexp, L.stream_ptr()), 'effdet_pw_dgrad_se'), 'Cout%d Cexp%d M%d' % (Cout, Cexp, M),
         nbytes=4.0 * M * (Cout + 2 * Cexp))
     return dz
 
@@ -930,7 +939,7 @@ def se_gate_fwd(pool_part, w1, b1, w2, b2, inv_hw, save_mid=False):
     mid = torch.empty((B, Cse), dtype=torch.float32, device=pool_part.device) if save_mid else None
     ws = torch.empty((B, Cse), dtype=torch.float32, device=pool_part.device)
     L.check(L.lib().effdet_se_gate_fwd_split(L.ptr(pool_part), G, L.ptr(pool), L.ptr(w1.detach()), L.ptr(b1.detach()), L.ptr(w2.detach()),
-                                             L.ptr(b2.detach()), L.ptr(gate), L.ptr(mid), L.ptr(ws), B, Cc, Cse, C.c_float(inv_hw),
+                                             L.ptr(b2.detach()), L.ptr(gate), L.ptr(mid), L.ptr(ws), B, Cc, Cse, float(inv_hw),
                                              L.stream_ptr()), 'effdet_se_gate_fwd_split')
     return gate, mid, pool
 
@@ -939,15 +948,15 @@ def channel_scale(x, gate, act=ACT_NONE):
     """act(x) * gate[b][c]; act=ACT_SWISH when x is the depthwise pre-activation (z-only storage)."""
     y = Map.new(x.B, x.H, x.W, x.C, x.dtype, x.t.device)
     L.check(L.lib().effdet_channel_scale(L.ptr(x.tensor()), L.ptr(gate), L.ptr(y.t), act, L.dtype_code(x.dtype), x.B,
-                                         C.c_longlong(x.H * x.W), x.C, L.stream_ptr()), 'effdet_channel_scale')
+                                         x.H * x.W, x.C, L.stream_ptr()), 'effdet_channel_scale')
     return y
 
 
 def se_dgate(dy, x, act=ACT_NONE):
     """-> dgate_part [B][slabs][C]: per-pixel-slab partial sums (added in slab order by se_gate_bwd)."""
-    dg = torch.empty((x.B, int(L.lib().effdet_se_dgate_slabs(C.c_longlong(x.H * x.W))), x.C), dtype=torch.float32, device=x.t.device)
+    dg = torch.empty((x.B, int(L.lib().effdet_se_dgate_slabs(x.H * x.W)), x.C), dtype=torch.float32, device=x.t.device)
     L.check(L.lib().effdet_se_dgate(L.ptr(dy.tensor()), L.ptr(x.tensor()), L.ptr(dg), act, L.dtype_code(x.dtype), x.B,
-                                    C.c_longlong(x.H * x.W), x.C, L.stream_ptr()), 'effdet_se_dgate')
+                                    x.H * x.W, x.C, L.stream_ptr()), 'effdet_se_dgate')
     return dg
 
 
@@ -984,7 +993,7 @@ def se_gate_bwd(dgate, gate, mid, pool, w1, b1, w2, inv_hw, times_gate=False):
     L.check(L.lib().effdet_se_gate_bwd(L.ptr(dgate), dgate.shape[1], int(times_gate), L.ptr(gate), L.ptr(mid), L.ptr(pool), L.ptr(w1d), L.ptr(b1d),
                                        L.ptr(w2d), L.ptr(dpool), L.ptr(None if defer else dw1), L.ptr(None if defer else db1),
                                        L.ptr(None if defer else dw2), L.ptr(None if defer else db2), L.ptr(ws),
-                                       B, Cc, Cse, C.c_float(inv_hw), L.stream_ptr()), 'effdet_se_gate_bwd')
+                                       B, Cc, Cse, float(inv_hw), L.stream_ptr()), 'effdet_se_gate_bwd')
     if defer:
         j = L.SeParamJob()
         j.du, j.dmid, j.sw = ws.data_ptr(), ws.data_ptr() + 4 * B * Cc, ws.data_ptr() + 4 * B * (Cc + Cse)
@@ -997,14 +1006,14 @@ def se_gate_bwd(dgate, gate, mid, pool, w1, b1, w2, inv_hw, times_gate=False):
 def se_bwd_apply(dy, gate, dpool, z):
     out = Map.new(z.B, z.H, z.W, z.C, z.dtype, z.t.device)
     L.check(L.lib().effdet_se_bwd_apply(L.ptr(dy.tensor()), L.ptr(gate), L.ptr(dpool), L.ptr(z.tensor()), L.ptr(out.t),
-                                        L.dtype_code(z.dtype), z.B, C.c_longlong(z.H * z.W), z.C, L.stream_ptr()), 'effdet_se_bwd_apply')
+                                        L.dtype_code(z.dtype), z.B, z.H * z.W, z.C, L.stream_ptr()), 'effdet_se_bwd_apply')
     return out
 
 
 def act_bwd(dy, aux, act, rowscale=None, out=None):
     out = out or Map.new(dy.B, dy.H, dy.W, dy.C, dy.dtype, dy.t.device)
     L.check(L.lib().effdet_act_bwd(L.ptr(dy.tensor()), L.ptr(aux.tensor() if aux is not None else None), L.ptr(rowscale),
-                                   L.ptr(out.t), L.dtype_code(dy.dtype), act, dy.B, C.c_longlong(dy.H * dy.W * dy.C),
+                                   L.ptr(out.t), L.dtype_code(dy.dtype), act, dy.B, dy.H * dy.W * dy.C,
                                    L.stream_ptr()), 'effdet_act_bwd')
     return out
 
@@ -1014,13 +1023,13 @@ def add_inplace(y, x):
     ty = y.tensor() if isinstance(y, Map) else y
     tx = x.tensor() if isinstance(x, Map) else x
     assert ty.numel() == tx.numel() and ty.dtype == tx.dtype
-    L.check(L.lib().effdet_add_inplace(L.ptr(ty), L.ptr(tx), L.dtype_code(ty.dtype), C.c_longlong(ty.numel()), L.stream_ptr()),
+    L.check(L.lib().effdet_add_inplace(L.ptr(ty), L.ptr(tx), L.dtype_code(ty.dtype), ty.numel(), L.stream_ptr()),
             'effdet_add_inplace')
 
 
 def colsum(t2d, out):
     rows, Cc = t2d.shape
-    L.check(L.lib().effdet_colsum(L.ptr(t2d), L.ptr(out), L.dtype_code(t2d.dtype), C.c_longlong(rows), Cc, Cc, L.stream_ptr()),
+    L.check(L.lib().effdet_colsum(L.ptr(t2d), L.ptr(out), L.dtype_code(t2d.dtype), rows, Cc, Cc, L.stream_ptr()),
             'effdet_colsum')
 
 
@@ -1080,7 +1089,7 @@ def decode_score(anc, reg, cls, img_h, img_w):
     # algorithmic bytes: probabilities + box deltas read once, boxes / score / label written once (anchors: one [A,4] table for the batch)
     nbytes = 4 * (B * A * (nc + 4) + A * 4 + B * A * 6)
     _timed('decode_score_kernel', nbytes, lambda: L.check(L.lib().effdet_decode_score(
-        L.ptr(anc), L.ptr(reg), L.ptr(cls), L.ptr(boxes), L.ptr(score), L.ptr(label), B, C.c_longlong(A), nc, C.c_float(img_w), C.c_float(img_h),
+        L.ptr(anc), L.ptr(reg), L.ptr(cls), L.ptr(boxes), L.ptr(score), L.ptr(label), B, A, nc, float(img_w), float(img_h),
         L.stream_ptr()), 'effdet_decode_score'), 'BYTES B%d A%d nc%d' % (B, A, nc))
     return boxes, score, label
 
@@ -1088,7 +1097,7 @@ def decode_score(anc, reg, cls, img_h, img_w):
 def nms(boxes, score, threshold, iou_threshold):
     """-> (idx [B][A] int32 kept anchor indices in order, count [B] int32); all on device, no sync."""
     B, A = score.shape
-    nbytes = int(L.lib().effdet_nms_workspace_bytes(B, C.c_longlong(A)))
+    nbytes = int(L.lib().effdet_nms_workspace_bytes(B, A))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=score.device)
     idx = torch.empty((B, A), dtype=torch.int32, device=score.device)
     count = torch.empty((B,), dtype=torch.int32, device=score.device)
@@ -1096,8 +1105,8 @@ def nms(boxes, score, threshold, iou_threshold):
     # written once -- the O(K^2) suppression work is latency / ALU, not bytes, so the GB/s of this entry says how far from a streaming
     # pass the greedy algorithm is, not how well a kernel streams
     _timed('nms (radix sort + cross / matrix / resolve rounds)', 4 * B * A * 6, lambda: L.check(L.lib().effdet_nms(
-        L.ptr(boxes), L.ptr(score), C.c_float(threshold), C.c_float(iou_threshold), L.ptr(idx), L.ptr(count),
-        L.ptr(ws), C.c_longlong(nbytes), B, C.c_longlong(A), L.stream_ptr()), 'effdet_nms'), 'BYTES B%d A%d' % (B, A))
+        L.ptr(boxes), L.ptr(score), float(threshold), float(iou_threshold), L.ptr(idx), L.ptr(count),
+        L.ptr(ws), nbytes, B, A, L.stream_ptr()), 'effdet_nms'), 'BYTES B%d A%d' % (B, A))
     return idx, count
 
 
@@ -1107,7 +1116,7 @@ def gather_dets(boxes, score, label, idx, count):
     ol = torch.empty((B, A), dtype=torch.int64, device=score.device)
     ob = torch.empty((B, A, 4), dtype=torch.float32, device=score.device)
     L.check(L.lib().effdet_gather_dets(L.ptr(boxes), L.ptr(score), L.ptr(label), L.ptr(idx), L.ptr(count), L.ptr(os_), L.ptr(ol),
-                                       L.ptr(ob), B, C.c_longlong(A), L.stream_ptr()), 'effdet_gather_dets')
+                                       L.ptr(ob), B, A, L.stream_ptr()), 'effdet_gather_dets')
     return os_, ol, ob
 
 
@@ -1115,11 +1124,11 @@ def gather_dets(boxes, score, label, idx, count):
 def focal_loss_fwd(cls, reg, anc, annots):
     B, A, nc = cls.shape
     N = annots.shape[1]
-    nbytes = int(L.lib().effdet_loss_workspace_bytes(B, C.c_longlong(A), nc))
+    nbytes = int(L.lib().effdet_loss_workspace_bytes(B, A, nc))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
     losses = torch.empty(2, dtype=torch.float32, device=cls.device)
     L.check(L.lib().effdet_focal_loss_fwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws),
-                                          C.c_longlong(nbytes), B, C.c_longlong(A), nc, N, L.stream_ptr()), 'effdet_focal_loss_fwd')
+                                          nbytes, B, A, nc, N, L.stream_ptr()), 'effdet_focal_loss_fwd')
     return losses, ws
 
 
@@ -1128,7 +1137,7 @@ def focal_loss_bwd(cls, reg, anc, annots, gscale, ws, dtype):
     dcls = torch.empty((B, A, nc), dtype=dtype, device=cls.device)
     dreg = torch.empty((B, A, 4), dtype=dtype, device=cls.device)
     L.check(L.lib().effdet_focal_loss_bwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls),
-                                          L.ptr(dreg), L.dtype_code(dtype), B, C.c_longlong(A), nc, annots.shape[1], L.stream_ptr()),
+                                          L.ptr(dreg), L.dtype_code(dtype), B, A, nc, annots.shape[1], L.stream_ptr()),
             'effdet_focal_loss_bwd')
     return dcls, dreg
 
@@ -1139,7 +1148,7 @@ def focal_loss_bwd_pix(cls, reg, anc, annots, gscale, ws, dtype, dld):
     dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
     dreg = torch.empty((B, A, 4), dtype=dtype, device=cls.device)
     L.check(L.lib().effdet_focal_loss_bwd_pix(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls),
-                                              dld, L.ptr(dreg), L.dtype_code(dtype), B, C.c_longlong(A), nc, annots.shape[1],
+                                              dld, L.ptr(dreg), L.dtype_code(dtype), B, A, nc, annots.shape[1],
                                               L.stream_ptr()), 'effdet_focal_loss_bwd_pix')
     return dcls, dreg
 
@@ -1148,12 +1157,12 @@ def focal_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False):
     """Training fast path: -> (losses [2], ws, dcls_pix [B, A/9, dld]) in one pass over cls; dcls_pix is the gradient wrt the
     logits for an upstream gradient of ONE (the caller scales downstream, see effdet_hip.h)."""
     B, A, nc = cls.shape
-    nbytes = int(L.lib().effdet_loss_workspace_bytes(B, C.c_longlong(A), nc))
+    nbytes = int(L.lib().effdet_loss_workspace_bytes(B, A, nc))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
     losses = torch.empty(2, dtype=torch.float32, device=cls.device)
     dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
     L.check(L.lib().effdet_focal_loss_fwd_grad(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws),
-                                               C.c_longlong(nbytes), L.ptr(dcls), dld, L.F32_SPLIT if split else L.dtype_code(dtype), B, C.c_longlong(A), nc,
+                                               nbytes, L.ptr(dcls), dld, L.F32_SPLIT if split else L.dtype_code(dtype), B, A, nc,
                                                annots.shape[1], L.stream_ptr()), 'effdet_focal_loss_fwd_grad')
     return losses, ws, dcls
 
@@ -1163,7 +1172,7 @@ def focal_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=Fals
     B, A, _ = reg.shape
     dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
     L.check(L.lib().effdet_focal_loss_bwd_reg(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld,
-                                              L.F32_SPLIT if split else L.dtype_code(dtype), B, C.c_longlong(A), annots.shape[1],
+                                              L.F32_SPLIT if split else L.dtype_code(dtype), B, A, annots.shape[1],
                                               L.stream_ptr()), 'effdet_focal_loss_bwd_reg')
     return dreg
 
@@ -1172,7 +1181,7 @@ def pad_rows(src_map, cpad):
     """Level map with unaligned channel count -> fresh contiguous [B,H,W,cpad] map, zero padded."""
     m = src_map
     dst = Map.new(m.B, m.H, m.W, cpad, m.dtype, m.t.device)
-    L.check(L.lib().effdet_pad_rows(L.ptr(m.t), L.ptr(dst.t), L.dtype_code(m.dtype), C.c_longlong(m.off), C.c_longlong(m.bstride),
+    L.check(L.lib().effdet_pad_rows(L.ptr(m.t), L.ptr(dst.t), L.dtype_code(m.dtype), m.off, m.bstride,
                                     m.ld, m.B, m.H * m.W, m.C, cpad, L.stream_ptr()), 'effdet_pad_rows')
     return dst
 
@@ -1183,17 +1192,15 @@ def drop_connect_scales(keep_dev, B, seed, step, step_dev=None):
     step_dev (int64 device tensor [1]): the step counter lives on the device and is advanced by the kernel (hipGraph replay)."""
     n = keep_dev.numel()
     out = torch.empty((n, B), dtype=torch.float32, device=keep_dev.device)
-    L.check(L.lib().effdet_drop_connect_scales(L.ptr(out), L.ptr(keep_dev), n, B, C.c_ulonglong(seed & (2 ** 64 - 1)),
-                                               C.c_ulonglong(step), L.ptr(step_dev), L.stream_ptr()), 'effdet_drop_connect_scales')
+    L.check(L.lib().effdet_drop_connect_scales(L.ptr(out), L.ptr(keep_dev), n, B, seed & (2 ** 64 - 1), int(step), L.ptr(step_dev),
+                                               L.stream_ptr()), 'effdet_drop_connect_scales')
     return out
 
 
 def philox_host(ctr, key):
     """Host twin of the device generator (Philox4x32-10): -> 4 uint32 words."""
     c = (C.c_uint * 4)(*ctr); k = (C.c_uint * 2)(*key); o = (C.c_uint * 4)()
-    f = L.lib().effdet_philox4x32_10
-    f.restype = None
-    f(c, k, o)
+    L.lib().effdet_philox4x32_10(c, k, o)
     return [int(x) for x in o]
 
 
@@ -1216,7 +1223,7 @@ def finalize_dets(score, label, boxes, count, scale, score_threshold, max_det, x
     out = torch.empty((B, max_det, 6), dtype=torch.float32, device=score.device)
     oc = torch.empty(B, dtype=torch.int32, device=score.device)
     L.check(L.lib().effdet_finalize_dets(L.ptr(score), L.ptr(label), L.ptr(boxes), L.ptr(count), L.ptr(scale),
-                                         C.c_float(score_threshold), max_det, int(xywh), L.ptr(out), L.ptr(oc), B, C.c_longlong(A),
+                                         float(score_threshold), max_det, int(xywh), L.ptr(out), L.ptr(oc), B, A,
                                          L.stream_ptr()), 'effdet_finalize_dets')
     return out, oc
 
@@ -1236,7 +1243,7 @@ def voc_match(dets, counts, gt_boxes, gt_labels, num_classes, iou_threshold, rec
     assert rec_key.dtype == torch.int64 and rec_tp.dtype == torch.uint8 and rec_key.numel() >= B * max_det and rec_tp.numel() >= B * max_det
     assert gt_count.dtype == torch.int32 and gt_count.numel() == num_classes
     L.check(L.lib().effdet_voc_match(L.ptr(dets), L.ptr(counts), L.ptr(gt_boxes), L.ptr(gt_labels), B, max_det, G, int(num_classes),
-                                     C.c_double(iou_threshold), L.ptr(rec_key), L.ptr(rec_tp), L.ptr(gt_count), L.stream_ptr()),
+                                     float(iou_threshold), L.ptr(rec_key), L.ptr(rec_tp), L.ptr(gt_count), L.stream_ptr()),
             'effdet_voc_match')
 
 
@@ -1245,13 +1252,13 @@ def voc_ap(rec_key, rec_tp, num_records, gt_count, num_classes):
     fp64 in sorted order, seg [C, 2] int32 = each class's [start, end) in that order)."""
     dev = gt_count.device
     N = int(num_records)
-    ws = torch.empty(int(L.lib().effdet_voc_ap_workspace_bytes(C.c_longlong(N))), dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(L.lib().effdet_voc_ap_workspace_bytes(N)), dtype=torch.uint8, device=dev)
     out = torch.empty((2, num_classes), dtype=torch.float64, device=dev)
     recall = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
     precision = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
     seg = torch.empty((num_classes, 2), dtype=torch.int32, device=dev)
-    L.check(L.lib().effdet_voc_ap(L.ptr(rec_key), L.ptr(rec_tp), C.c_longlong(N), L.ptr(gt_count), int(num_classes), L.ptr(ws),
-                                  C.c_longlong(ws.numel()), L.ptr(out[0]), L.ptr(out[1]), L.ptr(recall), L.ptr(precision), L.ptr(seg),
+    L.check(L.lib().effdet_voc_ap(L.ptr(rec_key), L.ptr(rec_tp), N, L.ptr(gt_count), int(num_classes), L.ptr(ws),
+                                  ws.numel(), L.ptr(out[0]), L.ptr(out[1]), L.ptr(recall), L.ptr(precision), L.ptr(seg),
                                   L.stream_ptr()), 'effdet_voc_ap')
     return out, recall[:N], precision[:N], seg
 
@@ -1287,7 +1294,7 @@ def coco_match(dets, counts, image_ids, gt, num_categories, iou_thrs, area_rng, 
     assert min(t.numel() for t in rec) >= B * S and all(t.is_contiguous() for t in rec)
     assert npig.dtype == torch.int32 and npig.is_contiguous() and npig.numel() == num_categories * len(ar)
     L.check(Lb.effdet_coco_match(L.ptr(dets), L.ptr(counts), L.ptr(image_ids), L.ptr(gt), B, max_det, G, int(num_categories),
-                                 it.ctypes.data_as(C.POINTER(C.c_double)), len(it), ar.ctypes.data_as(C.POINTER(C.c_double)), len(ar),
+                                 it.ctypes.data, len(it), ar.ctypes.data, len(ar),
                                  int(max_dets_last), L.ptr(key), L.ptr(img), L.ptr(rank), L.ptr(match), L.ptr(ignore), L.ptr(npig),
                                  L.stream_ptr()), 'effdet_coco_match')
     return B * S
@@ -1303,15 +1310,15 @@ def coco_accumulate(rec, num_records, max_image_id, npig, num_categories, iou_th
     rt = np.ascontiguousarray(rec_thrs, dtype=np.float64)
     md = np.ascontiguousarray(max_dets, dtype=np.int32)
     T, R, A, M = len(it), len(rt), int(num_areas), len(md)
-    ws = torch.empty(int(Lb.effdet_coco_accumulate_workspace_bytes(C.c_longlong(N), K)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(Lb.effdet_coco_accumulate_workspace_bytes(N, K)), dtype=torch.uint8, device=dev)
     precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
     recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
     stats = torch.empty(12, dtype=torch.float64, device=dev)
     key, img, rank, match, ignore = rec
-    L.check(Lb.effdet_coco_accumulate(L.ptr(key), L.ptr(img), L.ptr(rank), L.ptr(match), L.ptr(ignore), C.c_longlong(N),
-                                      C.c_uint(int(max_image_id)), L.ptr(npig), K, it.ctypes.data_as(C.POINTER(C.c_double)), T,
-                                      rt.ctypes.data_as(C.POINTER(C.c_double)), R, A, md.ctypes.data_as(C.POINTER(C.c_int)), M,
-                                      L.ptr(ws), C.c_longlong(ws.numel()), L.ptr(precision), L.ptr(recall), L.ptr(stats),
+    L.check(Lb.effdet_coco_accumulate(L.ptr(key), L.ptr(img), L.ptr(rank), L.ptr(match), L.ptr(ignore), N,
+                                      int(max_image_id), L.ptr(npig), K, it.ctypes.data, T,
+                                      rt.ctypes.data, R, A, md.ctypes.data, M,
+                                      L.ptr(ws), ws.numel(), L.ptr(precision), L.ptr(recall), L.ptr(stats),
                                       L.stream_ptr()), 'effdet_coco_accumulate')
     return precision, recall, stats
 
@@ -1321,7 +1328,7 @@ def head_out_bwd(dprob, prob, dreg, dtype):
     dl = torch.empty(prob.shape, dtype=dtype, device=prob.device)
     dr = torch.empty(dreg.shape, dtype=dtype, device=prob.device)
     L.check(L.lib().effdet_head_out_bwd(L.ptr(dprob), L.ptr(prob), L.ptr(dreg), L.ptr(dl), L.ptr(dr), L.dtype_code(dtype),
-                                        C.c_longlong(prob.numel()), C.c_longlong(dreg.numel()), L.stream_ptr()), 'effdet_head_out_bwd')
+                                        prob.numel(), dreg.numel(), L.stream_ptr()), 'effdet_head_out_bwd')
     return dl, dr
 
 
@@ -1384,7 +1391,7 @@ def augment_boxes(src_hw, table, H, W, annots, min_area=0.0, min_visibility=0.0)
     out = torch.empty_like(annots)
     counts = torch.empty(B, dtype=torch.int32, device=annots.device)
     L.check(L.require(*_AUG).effdet_augment_boxes(L.ptr(src_hw), L.ptr(table), B, int(H), int(W), L.ptr(annots), M,
-                                                  C.c_double(min_area), C.c_double(min_visibility), L.ptr(out), L.ptr(counts),
+                                                  float(min_area), float(min_visibility), L.ptr(out), L.ptr(counts),
                                                   L.stream_ptr()), 'effdet_augment_boxes')
     return out, counts
 
@@ -1406,7 +1413,7 @@ def jpeg_probe(stream):
     """Host only.  bytes -> (status, JpegInfo): 0, or _lib's EFFDET_EUNSUPPORTED (-3, info.reason says why) / EFFDET_EINVAL (-1)."""
     a = _as_u8(stream)
     info = L.JpegInfo()
-    st = L.require(*_JPEG).effdet_jpeg_probe(C.c_void_p(a.ctypes.data), C.c_longlong(a.size), C.byref(info))
+    st = L.require(*_JPEG).effdet_jpeg_probe(a.ctypes.data, a.size, C.byref(info))
     return int(st), info
 
 
@@ -1423,8 +1430,8 @@ def jpeg_entropy_batch(streams, coef_out, coef_off, desc_out, threads=8):
     assert coef_out.dtype == np.uint8 and coef_out.flags['C_CONTIGUOUS'] and coef_out.flags['WRITEABLE']
     assert desc_out.dtype == np.uint8 and desc_out.flags['C_CONTIGUOUS'] and desc_out.size >= B * JPEG_DESC_BYTES
     totals = (C.c_int * 2)()
-    st = L.require(*_JPEG).effdet_jpeg_entropy_batch(ptrs, lens, B, C.c_void_p(coef_out.ctypes.data), C.c_longlong(coef_out.size), offs,
-                                                     C.c_void_p(desc_out.ctypes.data), int(threads), totals)
+    st = L.require(*_JPEG).effdet_jpeg_entropy_batch(ptrs, lens, B, coef_out.ctypes.data, coef_out.size, offs,
+                                                     desc_out.ctypes.data, int(threads), totals)
     return int(st), (int(totals[0]), int(totals[1]))
 
 

@@ -234,16 +234,16 @@ class ClipAdamW(torch.optim.Optimizer):
             Lb = L.require('effdet_clip_adamw_step_gated')
             L.check(Lb.effdet_clip_adamw_step_gated(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['a_ptr']), L.ptr(t['m_ptr']), L.ptr(t['v_ptr']),
                                                     L.ptr(t['numel']), L.ptr(t['block_tensor']), L.ptr(t['block_first']), t['n'], t['nblocks'],
-                                                    L.ptr(t['scratch']), L.ptr(t['steps']), C.c_float(g['max_norm'] or 0.0),
-                                                    C.c_float(g['lr']), C.c_float(b1), C.c_float(b2), C.c_float(g['eps']),
-                                                    C.c_float(g['weight_decay']), L.ptr(t['hyper']), L.ptr(t['ctl']), L.stream_ptr()),
+                                                    L.ptr(t['scratch']), L.ptr(t['steps']), float(g['max_norm'] or 0.0),
+                                                    float(g['lr']), float(b1), float(b2), float(g['eps']),
+                                                    float(g['weight_decay']), L.ptr(t['hyper']), L.ptr(t['ctl']), L.stream_ptr()),
                     'effdet_clip_adamw_step_gated')
             return loss
         L.check(L.lib().effdet_clip_adamw_step(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['m_ptr']), L.ptr(t['v_ptr']), L.ptr(t['numel']),
                                                L.ptr(t['block_tensor']), L.ptr(t['block_first']), t['n'], t['nblocks'],
-                                               L.ptr(t['scratch']), L.ptr(t['steps']), C.c_float(g['max_norm'] or 0.0),
-                                               C.c_float(g['lr']), C.c_float(b1), C.c_float(b2), C.c_float(g['eps']),
-                                               C.c_float(g['weight_decay']), int(self.write_clipped_grads), L.ptr(t['hyper']), L.stream_ptr()),
+                                               L.ptr(t['scratch']), L.ptr(t['steps']), float(g['max_norm'] or 0.0),
+                                               float(g['lr']), float(b1), float(b2), float(g['eps']),
+                                               float(g['weight_decay']), int(self.write_clipped_grads), L.ptr(t['hyper']), L.stream_ptr()),
                 'effdet_clip_adamw_step')
         return loss
 

@@ -29,6 +29,52 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert int(L.effdet_num_anchors(512, 512)) == 49104 and int(L.effdet_num_anchors(1024, 1024)) == 196416
 
 
+def _prototypes():
+    """{name: (return kind, [parameter kinds])} of every prototype of the header, comments stripped as in _declared().  Kinds are
+    _lib.SIGNATURES' letters, with effdet_stream_t counted as a pointer."""
+    h = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'effdet_hip.h')).read(), flags=re.S)
+    scalar = {'int': 'i', 'long long': 'q', 'unsigned': 'I', 'unsigned long long': 'Q', 'float': 'f', 'double': 'd', 'effdet_stream_t': 'p'}
+    ret = {'int': 'i', 'long long': 'q', 'const char*': 'z', 'void': 'v'}
+    out = {}
+    for r, name, params in re.findall(r'^([a-z][a-z ]*?\*?)\s*\b(effdet_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', h, flags=re.M):
+        kinds = []
+        for p in ([] if params.strip() == 'void' else params.split(',')):
+            p = ' '.join(p.split())
+            kinds.append('p' if '*' in p or '[' in p else scalar[p.rsplit(' ', 1)[0]])      # KeyError: a type outside the vocabulary
+        assert name not in out, name
+        out[name] = (ret[' '.join(r.split())], kinds)
+    return out
+
+
+def test_signature_table_matches_the_header_prototypes():
+    """_lib.SIGNATURES (what lib() binds as restype / argtypes) against the prototypes of include/effdet_hip.h: per function the same
+    return kind, parameter count and parameter kinds in order -- int, 64-bit int, unsigned, 64-bit unsigned, float, double,
+    pointer / stream."""
+    import ctypes as C
+    from efficientdet.pytorch_amd import build, _lib
+    protos = _prototypes()
+    assert sorted(protos) == _declared() and len(protos) == 91
+    assert sorted(_lib.SIGNATURES) == sorted(protos), set(_lib.SIGNATURES) ^ set(protos)
+    for name, (r, kinds) in protos.items():
+        sig = _lib.SIGNATURES[name]
+        assert sig[1] == ':' and sig[0] == r, (name, sig, r)
+        got = sig[2:].replace('s', 'p')
+        assert len(got) == len(kinds), (name, len(got), len(kinds))
+        assert list(got) == kinds, (name, got, ''.join(kinds))
+    # the letters mean what the table's comment says
+    assert [_lib._CTYPE[c] for c in 'iqIQfdpszv'] == [C.c_int, C.c_longlong, C.c_uint, C.c_ulonglong, C.c_float, C.c_double, C.c_void_p,
+                                                      C.c_void_p, C.c_char_p, None]
+    # and lib() binds every exported symbol of the table with them
+    build.build(verbose=False)
+    L = _lib.lib()
+    for name, sig in _lib.SIGNATURES.items():
+        if hasattr(L, name):
+            f = getattr(L, name)
+            assert f.restype is _lib._CTYPE[sig[0]], name
+            assert f.argtypes is not None and len(f.argtypes) == len(protos[name][1]), name
+            assert list(f.argtypes) == [_lib._CTYPE[c] for c in sig[2:]], name
+
+
 def test_stale_library_is_refused(tmp_path, monkeypatch):
     """A library with another ABI generation (stale build, foreign EFFDET_HIP_LIB) must not be bound: ctypes would call it with
     shifted arguments."""

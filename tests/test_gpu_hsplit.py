@@ -42,10 +42,9 @@ def from_split(t):
 
 def to_split2(x, bf=True):
     from efficientdet.pytorch_amd import ops
-    L, C = ops.L, ops.C
     s = torch.empty_like(x) if bf else None
     h = torch.empty_like(x)
-    L.check(L.lib().effdet_to_split2(L.ptr(x), L.ptr(s), L.ptr(h), C.c_longlong(x.numel()), L.ptr(ops.range_flag(x.device)), L.stream_ptr()), 'effdet_to_split2')
+    ops.to_split2(x, ops.L.ptr(s), h.data_ptr(), x.numel(), ops.range_flag(x.device))
     return s, h
 
 

@@ -229,7 +229,6 @@ def test_weight_gradient_planning_entry_points():
 def test_depthwise_planning_entry_points():
     """effdet_dwconv_fwd_pool_groups / effdet_mbconv_expand_dw_pool_groups / effdet_dwconv_{wgrad,bwd}_workspace_bytes (host planning
     only) for the depthwise convs of a D0 step (B = 32 @ 512), and the codes of calls every entry point refuses before launching."""
-    import ctypes as C
     from efficientdet.pytorch_amd import _lib as L
     from efficientdet.pytorch_amd.config import backbone_plan, conv_out
     lib = L.lib()
@@ -263,7 +262,7 @@ def test_depthwise_planning_entry_points():
     assert int(lib.effdet_dwconv_wgrad_workspace_bytes(*geo(2, 3, 1, 64, 240))) == -1
     assert int(lib.effdet_dwconv_wgrad_workspace_bytes(*geo(L.F32, 3, 1, 64, 30))) == -1          # C % 4
     assert int(lib.effdet_dwconv_bwd_workspace_bytes(L.F32, 32, 64, 64, 240, 3, 3, 0, 0, 22, 22)) == -1    # stride 3
-    P, N = C.c_void_p(0x1000), None
+    P, N = 0x1000, None
     g = geo(L.F32, 3, 1, 64, 240)
     assert int(lib.effdet_dwconv_fwd(N, P, P, P, P, P, P, *g, L.ACT_NONE, N)) == -1
     assert int(lib.effdet_dwconv_fwd(P, P, P, P, P, P, P, *geo(2, 3, 1, 64, 240), L.ACT_NONE, N)) == -1
@@ -272,9 +271,9 @@ def test_depthwise_planning_entry_points():
     assert int(lib.effdet_dwconv_dgrad(P, P, P, P, P, L.F32, 32, 64, 64, 240, 7, 1, 3, 3, 64, 64, N)) == -3        # k = 7
     assert int(lib.effdet_mbconv_expand_dw_fwd(P, P, P, P, P, P, P, P, P, 32, 64, 64, 48, 288, 3, 1, 1, 1, 64, 64, N)) == -3    # Cin
     ws = int(lib.effdet_dwconv_wgrad_workspace_bytes(*g))
-    assert int(lib.effdet_dwconv_wgrad(P, P, P, P, P, C.c_longlong(ws - 1), *g, L.ACT_SWISH, N)) == -1
+    assert int(lib.effdet_dwconv_wgrad(P, P, P, P, P, ws - 1, *g, L.ACT_SWISH, N)) == -1
     ws = int(lib.effdet_dwconv_bwd_workspace_bytes(*g))
-    assert int(lib.effdet_dwconv_bwd(P, P, P, P, P, P, P, P, C.c_longlong(ws - 1), *g, N)) == -1
+    assert int(lib.effdet_dwconv_bwd(P, P, P, P, P, P, P, P, ws - 1, *g, N)) == -1
 
 
 def test_tail_batch_context_records_and_joins(monkeypatch):

@@ -19,7 +19,6 @@ a = ap.parse_args()
 dev, dt = 'cuda', torch.float32
 sizes = [(int(v), int(v)) for v in os.environ.get('KB_SIZES', '64,32,16,8,4').split(',')]
 M = sum(a.B * h * w for h, w in sizes)
-L, C = ops.L, ops.C
 
 
 def timeit(fn):
@@ -42,7 +41,7 @@ def pyr(Cc, fill=None, kind='plain'):
             v = ops.to_split(v)
         elif kind == 'h':
             o = torch.empty_like(v)
-            L.check(L.lib().effdet_to_split2(L.ptr(v), None, L.ptr(o), C.c_longlong(v.numel()), None, L.stream_ptr()), 'to_split2')
+            ops.to_split2(v, None, o.data_ptr(), v.numel())
             v = o
         flat.copy_(v)
     return maps
