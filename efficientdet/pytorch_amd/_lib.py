@@ -1,4 +1,4 @@
-"""ctypes binding of libeffdet_hip.so (include/effdet_hip.h).
+"""ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -203,6 +203,13 @@ SIGNATURES = {
     'effdet_abi_version': 'i:',
 }
 SYMBOLS = list(SIGNATURES)
+# Entry points added within ABI generation 11, declared in include/effdet_soft_nms.h (same letters; tests/test_soft_nms_host.py compares
+# this table with that header's prototypes).  A library of the generation built before them lacks the symbols: callers go through
+# require().
+ADDED_SIGNATURES = {
+    'effdet_soft_nms_workspace_bytes': 'q:iqi',
+    'effdet_soft_nms': 'i:pppffifiiippppqiqs',
+}
 
 
 def lib():
@@ -220,7 +227,7 @@ def lib():
             raise RuntimeError('%s has ABI generation %d, this binding needs %d: rebuild it (`python -m efficientdet.pytorch_amd.build`)'
                                % (LIB_PATH, got, ABI_VERSION))
         _lib = cand
-        for name, sig in SIGNATURES.items():
+        for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -39,7 +39,7 @@ def _digest(paths):
 
 def build(force=False, verbose=True):
     srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip')))
-    deps = srcs + glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', '..', 'include', 'effdet_hip.h')]
+    deps = srcs + glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(HERE, '..', '..', 'include', '*.h'))
     deps = [os.path.abspath(d) for d in deps]
     stamp = os.path.join(CSRC, 'build', 'stamp')
     dig = _digest(deps)

@@ -16,6 +16,7 @@
 //   All loops are bounded by device-side counts; the host launches ceil(A / round) rounds blindly; every
 //   launch geometry depends on shapes only and the call consists of kernel nodes only: capture-safe.
 #include "common.h"
+#include "../../../include/effdet_soft_nms.h"
 #include "radix_sort.h"
 #include <stdlib.h>
 
@@ -101,14 +102,22 @@ struct NmsWs {
   unsigned long long* rowbits; float4* surv_box; unsigned* surv_idx; int* surv_n; int RND, NW;
 };
 
-__device__ __forceinline__ bool suppresses(const float4& a, float aa, const float4& b, float ab, float thr) {
+// THE IoU arithmetic of the file (greedy and rescoring NMS): f(iou) of the IoU from the stored fp32 areas, f's zero (false / 0.f)
+// for boxes that do not overlap
+template <typename F> __device__ __forceinline__ auto with_iou(const float4& a, float aa, const float4& b, float ab, F f) -> decltype(f(0.f)) {
   const float iw = fminf(a.z, b.z) - fmaxf(a.x, b.x);
   const float ih = fminf(a.w, b.w) - fmaxf(a.y, b.y);
-  if (iw <= 0.f || ih <= 0.f) return false;
+  if (iw <= 0.f || ih <= 0.f) return decltype(f(0.f))(0);
   const float inter = iw * ih;
   // (division-free forms -- bracketing products, or the exact f64 midpoint compare -- measured no faster: the phases that
   //  call this are LDS/latency-bound, not VALU-bound)
-  return inter / (aa + ab - inter) > thr;
+  return f(inter / (aa + ab - inter));
+}
+__device__ __forceinline__ bool suppresses(const float4& a, float aa, const float4& b, float ab, float thr) {
+  return with_iou(a, aa, b, ab, [thr](float iou) { return iou > thr; });
+}
+__device__ __forceinline__ float box_iou(const float4& a, float aa, const float4& b, float ab) {
+  return with_iou(a, aa, b, ab, [](float iou) { return iou; });
 }
 
 // `me` against n kept boxes staged in LDS (tb / ta, padded to a multiple of 8 with boxes that suppress nothing).
@@ -526,6 +535,80 @@ __global__ void gather_dets_kernel(const float* __restrict__ boxes, const float*
   }
 }
 
+// ------------------------------------------------------------------ rescoring NMS (Soft-NMS; hard / per-class suppression as special cases)
+// Same keys and sort as the greedy path; then ONE workgroup per image keeps the first n = min(candidates, top_n) sorted candidates in
+// LDS (box 16 B, area, running score, label: 28 B each, 112 KB at the 4096 cap) and runs the sequential pick loop: pick the live
+// candidate with the largest running score (ties: smallest sorted position), emit it, rescore the live candidates (of its class).
+// A thread owns the candidates q = tid, tid + 1024, ..: it alone reads and writes their running scores, and while it rescores them for
+// pick k it already keeps its best for pick k + 1 -- so a pick is one sweep, one wave + cross-wave arg-max and ONE barrier (the
+// reduction slots ping-pong; boxes, areas and labels are never written after the load).  A dead candidate's score is -inf, so
+// "live" is `s > threshold` everywhere.  Degenerate boxes (area not positive and finite) neither rescore nor are rescored.
+constexpr int SN_T = 1024, SN_MAX = 4096;
+constexpr float SN_DEAD = -__builtin_huge_valf();
+
+struct SoftNms {
+  const float* boxes; const float* score; const int* label; const unsigned* sidx; const int* nvalid;
+  int* out_idx; float* out_score; int* out_count; long long A;
+  float thr, iou_thr, sigma; int method, top_n, max_det;
+};
+
+__device__ __forceinline__ bool area_ok(float a) { return a > 0.f && a < __builtin_huge_valf(); }
+// (s, position) arg-max order: larger score first, then the smaller position; dead entries are (-inf, INT_MAX)
+__device__ __forceinline__ void sn_better(float& s, int& q, float os, int oq) { if (os > s || (os == s && oq < q)) { s = os; q = oq; } }
+
+__global__ __launch_bounds__(SN_T) void soft_nms_kernel(const SoftNms p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float4* tb = (float4*)smem_raw;                                      // [top_n] boxes in sorted order
+  float* ta = (float*)(tb + p.top_n);                                  // [top_n] areas
+  float* ts = ta + p.top_n;                                            // [top_n] running scores (owner thread only)
+  int* tl = (int*)(ts + p.top_n);                                      // [top_n] labels (0 when class-agnostic)
+  __shared__ float red_s[2][SN_T / 64];
+  __shared__ int red_q[2][SN_T / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long base = (long long)b * p.A;
+  const int n = min(p.nvalid[b], p.top_n);
+  float bs = SN_DEAD; int bq = 0x7fffffff;
+  for (int q = tid; q < n; q += SN_T) {
+    const long long src = base + p.sidx[base + q];
+    const float4 bx = ((const float4*)p.boxes)[src];
+    const float s = p.score[src];                                      // (> thr: it is a candidate)
+    tb[q] = bx; ta[q] = box_area(bx); ts[q] = s; tl[q] = p.label ? p.label[src] : 0;
+    sn_better(bs, bq, s, q);
+  }
+  int k = 0;
+  for (; k < p.max_det; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sn_better(bs, bq, __shfl_xor(bs, o, 64), __shfl_xor(bq, o, 64));
+    if (lane == 0) { red_s[k & 1][wave] = bs; red_q[k & 1][wave] = bq; }
+    __syncthreads();                                                   // (also publishes the loads above before pick 0 reads a box)
+    float ws = red_s[k & 1][lane & 15]; int wq = red_q[k & 1][lane & 15];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) sn_better(ws, wq, __shfl_xor(ws, o, 64), __shfl_xor(wq, o, 64));
+    if (!(ws > p.thr)) break;                                          // nothing live (block-uniform: every thread reduced the same 16 slots)
+    if (tid == 0) { p.out_idx[base + k] = (int)p.sidx[base + wq]; p.out_score[base + k] = ws; }
+    const float4 pb = tb[wq]; const float pa = ta[wq]; const int pl = tl[wq];
+    const bool pick_ok = area_ok(pa);
+    bs = SN_DEAD; bq = 0x7fffffff;
+    for (int q = tid; q < n; q += SN_T) {
+      float s = ts[q];
+      if (q == wq) { s = SN_DEAD; ts[q] = s; }
+      else if (s > p.thr && pick_ok && tl[q] == pl) {
+        const float a = ta[q];
+        if (area_ok(a)) {
+          const float iou = box_iou(pb, pa, tb[q], a);
+          if (p.method == 0) { if (iou > p.iou_thr) s = SN_DEAD; }
+          else if (p.method == 1) { if (iou > p.iou_thr) s = s * (1.f - iou); }
+          else s = s * expf(-(iou * iou) / p.sigma);
+          if (!(s > p.thr)) s = SN_DEAD;
+          ts[q] = s;
+        }
+      }
+      sn_better(bs, bq, s, q);
+    }
+  }
+  if (tid == 0) p.out_count[b] = k;
+}
+
 // candidates per round of the multi-workgroup form: 2048 (D0 @512: 24 rounds), 4096 above 64 k anchors (D4 @1024: 48 rounds);
 // EFFDET_NMS_ROUND overrides (A/B)
 inline int nms_round_size(long long A) {
@@ -550,6 +633,17 @@ size_t carve(NmsWs& w, void* base, int B, long long A) {
   w.RND = nms_round_size(A); w.NW = w.RND / 64;
   w.rowbits = c.take<unsigned long long>((size_t)B * w.NW * w.RND);
   w.surv_box = c.take<float4>((size_t)B * w.RND); w.surv_idx = c.take<unsigned>((size_t)B * w.RND); w.surv_n = c.take<int>(B);
+  return c.off;
+}
+
+// workspace of the rescoring NMS: the sort's ping-pong pairs and histograms, and what nms_keys32_kernel writes besides the keys
+struct SoftNmsWs { RsBufs<unsigned> rs; unsigned* dead; int* nvalid; int* kept; };
+
+size_t carve(SoftNmsWs& w, void* base, int B, long long A) {
+  Carver c(base);
+  rs_carve(w.rs, c, B, A);
+  w.dead = c.take<unsigned>((size_t)B * A);
+  w.nvalid = c.take<int>(B); w.kept = c.take<int>(B);
   return c.off;
 }
 
@@ -658,6 +752,43 @@ extern "C" int effdet_nms(const float* boxes, const float* score, float threshol
     }
     return EFFDET_OK;
   }
+}
+
+extern "C" long long effdet_soft_nms_workspace_bytes(int B, long long A, int pre_nms_top_n) {
+  (void)pre_nms_top_n;                                 // (the top-N candidates live in LDS; the workspace is the sort's)
+  if (B < 1 || A < 1) return 0;
+  SoftNmsWs w;
+  return (long long)carve(w, nullptr, B, A);
+}
+
+extern "C" int effdet_soft_nms(const float* boxes, const float* score, const int* label, float threshold, float iou_threshold,
+                               int method, float sigma, int class_aware, int pre_nms_top_n, int max_det, int* out_idx,
+                               float* out_score, int* out_count, void* workspace, long long workspace_bytes, int B, long long A,
+                               effdet_stream_t stream) {
+  if (!boxes || !score || !out_idx || !out_score || !out_count || !workspace || B < 1 || A < 1) return EFFDET_EINVAL;
+  if ((label != nullptr) != (class_aware != 0)) return EFFDET_EINVAL;
+  if (method < 0 || method > 2 || pre_nms_top_n < 1 || pre_nms_top_n > SN_MAX || max_det < 1 || max_det > pre_nms_top_n || !(sigma > 0.f))
+    return EFFDET_EUNSUPPORTED;
+  SoftNmsWs w;
+  const size_t need = carve(w, workspace, B, A);
+  if ((long long)need > workspace_bytes) return EFFDET_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  // resets as a kernel (no memset nodes): nvalid [B], and the output rows -- rows past the count stay index 0, score 0 (+0.f is all-zero bits)
+  hipLaunchKernelGGL(nms_reset_kernel, dim3(512), dim3(256), 0, st, w.nvalid, (long long)B, out_idx, (long long)B * A, (int*)out_score, (long long)B * A);
+  EFFDET_CHECK_LAUNCH();
+  { long long gx = (A + 2047) / 2048; if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(nms_keys32_kernel, dim3((unsigned)gx, B), dim3(256), 0, st, score, threshold, w.rs.ka, w.rs.va, w.nvalid, w.kept, w.dead, A); }
+  EFFDET_CHECK_LAUNCH();
+  unsigned *ki = w.rs.ka, *vi = w.rs.va, *ko = w.rs.kb, *vo = w.rs.vb;
+  if (const int rc = rs_sort(ki, vi, ko, vo, w.rs.hist, B, A, w.rs.T, 0, 4, st)) return rc;
+  SoftNms p;
+  p.boxes = boxes; p.score = score; p.label = label; p.sidx = vi; p.nvalid = w.nvalid;
+  p.out_idx = out_idx; p.out_score = out_score; p.out_count = out_count; p.A = A;
+  p.thr = threshold; p.iou_thr = iou_threshold; p.sigma = sigma; p.method = method; p.top_n = pre_nms_top_n; p.max_det = max_det;
+  EFFDET_SET_MAX_LDS(soft_nms_kernel, (size_t)SN_MAX * 28);          // (the cap: the attribute is set once per device)
+  hipLaunchKernelGGL(soft_nms_kernel, dim3(B), dim3(SN_T), (size_t)pre_nms_top_n * 28, st, p);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
 }
 
 extern "C" int effdet_gather_dets(const float* boxes, const float* score, const int* label, const int* idx, const int* count,

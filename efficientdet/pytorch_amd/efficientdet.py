@@ -368,6 +368,7 @@ class EfficientDet(nn.Module):
         self.anchors = Anchors()
         self.threshold = threshold
         self.iou_threshold = iou_threshold
+        self.nms_options = None                                 # set_nms(): None = the reference's class-agnostic greedy NMS
         self.num_classes = num_classes
         self.compute_dtype = compute_dtype
         # MFMA arithmetic on fp32 storage: 'f32' = exact fp32 products (v_mfma_f32_16x16x4_f32), 'bf16x3' = operands split into
@@ -400,6 +401,14 @@ class EfficientDet(nn.Module):
     def set_compute_dtype(self, dtype):
         assert dtype in (torch.float32, torch.bfloat16)
         self.compute_dtype = dtype
+        return self
+
+    def set_nms(self, options):
+        """NMS of the detection paths (detect, evaluate.*, graph.GraphedDetect): None = the reference's class-agnostic greedy NMS
+        (the default), an ops.NMSOptions = the device-side rescoring NMS (Soft-NMS, per-class suppression, top-N cap)."""
+        if options is not None and not isinstance(options, ops.NMSOptions):
+            raise TypeError('set_nms takes an NMSOptions or None, not %r' % (options,))
+        self.nms_options = options
         return self
 
     def live_parameters(self):
@@ -535,8 +544,7 @@ class EfficientDet(nn.Module):
             cls, reg, anc = self.forward_raw(img)
         H, W = int(img.shape[2]), int(img.shape[3])
         boxes, score, label = ops.decode_score(anc, reg, cls, H, W)
-        idx, count = ops.nms(boxes, score, float(self.threshold), float(self.iou_threshold))
-        s, l, b = ops.gather_dets(boxes, score, label, idx, count)
+        s, l, b, count = ops.model_nms(self, boxes, score, label)
         counts = count.tolist()                                  # the one device->host sync (the reference syncs too)
         if f16x3 and not torch.cuda.is_current_stream_capturing():
             ops.check_range_flag(s.device)                       # (a sigmoid turns an inf logit into a plausible score: make overflow an error)

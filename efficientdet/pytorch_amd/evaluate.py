@@ -19,9 +19,7 @@ def postprocess(model, cls, reg, anc, H, W):
     """models/efficientdet.py:69-86 for every image of the batch, on the device: decode + clip + class max + threshold + NMS.
     -> (scores [B,A], labels [B,A] int64, boxes [B,A,4], count [B] int32): score-descending rows, count[b] of them valid."""
     boxes, score, label = ops.decode_score(anc, reg, cls, H, W)
-    idx, count = ops.nms(boxes, score, float(model.threshold), float(model.iou_threshold))
-    s, l, b = ops.gather_dets(boxes, score, label, idx, count)
-    return s, l, b, count
+    return ops.model_nms(model, boxes, score, label)
 
 
 def default_max_detections(xywh, A, num_classes=None):

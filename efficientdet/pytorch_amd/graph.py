@@ -285,9 +285,7 @@ class GraphedDetect:
             with torch.no_grad():
                 cls, reg, anc = model.forward_raw(self.images)
                 boxes, score, label = ops.decode_score(anc, reg, cls, H, W)
-                idx, count = ops.nms(boxes, score, float(model.threshold), float(model.iou_threshold))
-                s, l, b = ops.gather_dets(boxes, score, label, idx, count)
-                return s, l, b, count
+                return ops.model_nms(model, boxes, score, label)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -298,6 +296,7 @@ class GraphedDetect:
         _build_pending_tables(model)
         self.graph = torch.cuda.CUDAGraph()
         self.thresholds = (float(model.threshold), float(model.iou_threshold))       # baked into the captured launches
+        self.nms_options = getattr(model, 'nms_options', None)                       # and so is which NMS runs, with what arguments
         # (inside a torch.distributed job the process group's watchdog thread polls events while this capture is open: 'thread_local'
         #  confines the unsafe-call check to this thread, as in GraphedTrainStep)
         dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -310,6 +309,9 @@ class GraphedDetect:
         if (float(m.threshold), float(m.iou_threshold)) != self.thresholds:
             raise RuntimeError('GraphedDetect: model.threshold / iou_threshold changed after capture (they are kernel arguments of the '
                                'captured NMS); build a new GraphedDetect')
+        if getattr(m, 'nms_options', None) != self.nms_options:
+            raise RuntimeError('GraphedDetect: model.nms_options changed after capture (%r was captured; the NMS and its arguments are '
+                               'part of the graph); build a new GraphedDetect' % (self.nms_options,))
         self.graph.replay()
         counts = self.count.tolist()                       # the one device->host sync (the reference syncs too)
         if ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3':

@@ -1120,6 +1120,83 @@ def gather_dets(boxes, score, label, idx, count):
     return os_, ol, ob
 
 
+NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}
+SOFT_NMS_MAX_TOP_N = 4096          # the kernel holds the top-N candidates of an image in one workgroup's LDS
+
+
+class NMSOptions:
+    """The rescoring NMS of EfficientDet.set_nms (effdet_soft_nms): method 'hard' | 'linear' | 'gaussian', gaussian sigma,
+    per-class suppression, the top-N candidates per image that take part (<= 4096) and the picks per image."""
+
+    def __init__(self, method='hard', sigma=0.5, class_aware=False, pre_nms_top_n=1000, max_det=100):
+        if method not in NMS_METHODS:
+            raise ValueError('NMSOptions: method must be one of %s, not %r' % (sorted(NMS_METHODS), method))
+        if not float(sigma) > 0.0:
+            raise ValueError('NMSOptions: sigma must be > 0')
+        if not 1 <= int(pre_nms_top_n) <= SOFT_NMS_MAX_TOP_N:
+            raise ValueError('NMSOptions: pre_nms_top_n must be in 1..%d' % SOFT_NMS_MAX_TOP_N)
+        if not 1 <= int(max_det) <= int(pre_nms_top_n):
+            raise ValueError('NMSOptions: max_det must be in 1..pre_nms_top_n')
+        self.method, self.sigma, self.class_aware = method, float(sigma), bool(class_aware)
+        self.pre_nms_top_n, self.max_det = int(pre_nms_top_n), int(max_det)
+
+    def key(self):
+        return (self.method, self.sigma, self.class_aware, self.pre_nms_top_n, self.max_det)
+
+    def __eq__(self, other):
+        return isinstance(other, NMSOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'NMSOptions(method=%r, sigma=%r, class_aware=%r, pre_nms_top_n=%d, max_det=%d)' % self.key()
+
+
+_soft_nms_ws = {}      # (device, B, A, top_n) -> workspace of eager calls (a capture allocates its own, from the graph's pool)
+
+
+def soft_nms(boxes, score, label, threshold, iou_threshold, method, sigma=0.5, class_aware=False, pre_nms_top_n=1000, max_det=100):
+    """Rescoring NMS (include/effdet_soft_nms.h: effdet_soft_nms) -> (idx [B,A] int32 picked anchor indices in pick order,
+    new_score [B,A] fp32 their scores when picked, count [B] int32); all on device, no sync.  label is read with class_aware only."""
+    lib = L.require('effdet_soft_nms', 'effdet_soft_nms_workspace_bytes')
+    B, A = score.shape
+    dev = score.device
+    nbytes = int(lib.effdet_soft_nms_workspace_bytes(B, A, int(pre_nms_top_n)))
+    if torch.cuda.is_current_stream_capturing():
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    else:
+        k = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), B, A, int(pre_nms_top_n))
+        ws = _soft_nms_ws.get(k)
+        if ws is None:
+            ws = _soft_nms_ws[k] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    idx = torch.empty((B, A), dtype=torch.int32, device=dev)
+    new_score = torch.empty((B, A), dtype=torch.float32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    m = NMS_METHODS[method] if isinstance(method, str) else int(method)
+    # algorithmic bytes as for nms: the sort's traffic + one box / score / label per top-N candidate; the pick loop is LDS / latency
+    _timed('soft_nms (radix sort + per-image pick loop)', 4 * B * A * 6, lambda: L.check(lib.effdet_soft_nms(
+        L.ptr(boxes), L.ptr(score), L.ptr(label) if class_aware else None, float(threshold), float(iou_threshold), m, float(sigma),
+        1 if class_aware else 0, int(pre_nms_top_n), int(max_det), L.ptr(idx), L.ptr(new_score), L.ptr(count), L.ptr(ws), nbytes, B, A,
+        L.stream_ptr()), 'effdet_soft_nms'), 'BYTES B%d A%d' % (B, A))
+    return idx, new_score, count
+
+
+def model_nms(model, boxes, score, label):
+    """The NMS stage of every detection path (EfficientDet.detect, evaluate.postprocess, graph.GraphedDetect) on decode_score's
+    outputs -> (scores [B,A], labels [B,A] int64, boxes [B,A,4], count [B] int32): score-descending rows, count[b] of them valid.
+    model.nms_options None: the reference's class-agnostic greedy NMS; an NMSOptions: the rescoring NMS, scores = the rescored ones."""
+    opt = getattr(model, 'nms_options', None)
+    if opt is None:
+        idx, count = nms(boxes, score, float(model.threshold), float(model.iou_threshold))
+        s, l, b = gather_dets(boxes, score, label, idx, count)
+        return s, l, b, count
+    idx, new_score, count = soft_nms(boxes, score, label, float(model.threshold), float(model.iou_threshold), opt.method, opt.sigma,
+                                     opt.class_aware, opt.pre_nms_top_n, opt.max_det)
+    _, l, b = gather_dets(boxes, score, label, idx, count)
+    return new_score, l, b, count
+
+
 # ----------------------------------------------------------------------------- loss
 def focal_loss_fwd(cls, reg, anc, annots):
     B, A, nc = cls.shape

@@ -488,6 +488,33 @@ long long effdet_nms_workspace_bytes(int B, long long A);
 int effdet_nms(const float* boxes, const float* score, float threshold, float iou_threshold, int* out_idx,
                int* out_count, void* workspace, long long workspace_bytes, int B, long long A,
                effdet_stream_t stream);
+/* Rescoring NMS on the device: Soft-NMS (linear / gaussian) and hard suppression, class-agnostic or per class.  The reference has
+ * none (its README lists Soft-NMS as to do), so the semantics are fixed here:
+ *   candidates  anchors with score > threshold (a NaN score is none), by descending score, ties by anchor index -- the keys and the
+ *               in-tree radix sort of effdet_nms -- of which only the first min(n, pre_nms_top_n) take part (the cap: 4096);
+ *   pick loop   running score s_i = score_i (fp32).  For k = 0 .. max_det-1: pick the live candidate with the largest s (ties: the
+ *               smallest sorted position; stop when none is live), write its anchor index to out_idx[b][k] and its CURRENT s to
+ *               out_score[b][k], then rescore every other live candidate j (class_aware: only those with the picked box's label):
+ *                 method 0 hard      iou > iou_threshold: j is dead
+ *                 method 1 linear    iou > iou_threshold: s_j = s_j * (1.f - iou)
+ *                 method 2 gaussian  s_j = s_j * expf(-(iou * iou) / sigma) for every j (iou_threshold unused)
+ *               and a rescored j with !(s_j > threshold) is dead.  iou is effdet_nms' fp32 value, inter / (aa + ab - inter) from the
+ *               stored areas (no fused multiply-add), 0 for boxes that do not overlap; a box whose area is not positive and finite
+ *               neither rescores anything nor is rescored;
+ *   outputs     out_idx [B][A], out_score [B][A] (emitted scores never increase), out_count [B]; rows past the count are index 0,
+ *               score 0.  effdet_gather_dets takes out_idx / out_count as they are.
+ * label [B][A] is required with class_aware and must be NULL without (else EFFDET_EINVAL).  Limits: method in 0..2,
+ * 1 <= pre_nms_top_n <= 4096, 1 <= max_det <= pre_nms_top_n, sigma > 0 (whatever the method): anything else is EFFDET_EUNSUPPORTED and
+ * nothing is launched.  workspace: effdet_soft_nms_workspace_bytes(B, A, pre_nms_top_n) = the sort's buffers (~20 B per anchor).
+ * After the sort ONE workgroup per image holds the top-N in LDS (28 B each).  Kernel nodes only, launch geometry a function of B, A
+ * and pre_nms_top_n alone, every loop bounded by a device-side count: capture-safe like effdet_nms.
+ * The pair is additive within this ABI generation (a binding asks the library for the two symbols by name), and its declarations
+ * live in the companion header effdet_soft_nms.h, which includes this one:
+ *   long long effdet_soft_nms_workspace_bytes(int B, long long A, int pre_nms_top_n);
+ *   int effdet_soft_nms(const float* boxes, const float* score, const int* label, float threshold, float iou_threshold,
+ *                       int method, float sigma, int class_aware, int pre_nms_top_n, int max_det, int* out_idx,
+ *                       float* out_score, int* out_count, void* workspace, long long workspace_bytes, int B, long long A,
+ *                       effdet_stream_t stream); */
 /* gather kept rows: scores [B][A], labels [B][A] (int64), boxes [B][A][4] for the first count[b] rows */
 int effdet_gather_dets(const float* boxes, const float* score, const int* label, const int* idx,
                        const int* count, float* out_scores, long long* out_labels, float* out_boxes, int B,
