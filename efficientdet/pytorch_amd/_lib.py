@@ -1,4 +1,4 @@
-"""ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h).
+"""ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -95,6 +95,10 @@ class JpegDesc(C.Structure):     # effdet_jpeg_desc_t
 
 class TrainCtl(C.Structure):     # effdet_train_ctl_t
     _fields_ = [(n, C.c_int) for n in ('skip', 'pending', 'applied', 'skipped')] + [('loss_count', C.c_longlong), ('loss_sum', C.c_double)]
+
+
+class EmaCtl(C.Structure):       # effdet_ema_ctl_t (include/effdet_ema.h)
+    _fields_ = [('updates', C.c_int), ('reserved', C.c_int * 3)]
 
 
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
@@ -210,6 +214,13 @@ ADDED_SIGNATURES = {
     'effdet_soft_nms_workspace_bytes': 'q:iqi',
     'effdet_soft_nms': 'i:pppffifiiippppqiqs',
 }
+# The parameter EMA of the clip + AdamW step and the in-place weight swap, declared in include/effdet_ema.h (same generation, same
+# letters, same rule: callers go through require(); tests/test_ema_host.py compares this table with that header's prototypes).
+EMA_SIGNATURES = {
+    'effdet_clip_adamw_step_ema': 'i:ppppppppiippffffffifipps',
+    'effdet_clip_adamw_step_gated_ema': 'i:pppppppppiippfffffffippps',
+    'effdet_ema_swap': 'i:pppppiis',
+}
 
 
 def lib():
@@ -227,7 +238,7 @@ def lib():
             raise RuntimeError('%s has ABI generation %d, this binding needs %d: rebuild it (`python -m efficientdet.pytorch_amd.build`)'
                                % (LIB_PATH, got, ABI_VERSION))
         _lib = cand
-        for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -4,6 +4,9 @@
   nn.DataParallel, so its DDP checkpoints carry a ``module.`` prefix that its own ``load_state_dict`` then rejects).
 * ``save_checkpoint`` / ``load_checkpoint`` -- the dict of train.py:279-291 ({'epoch', 'parser', 'state_dict'}) plus the
   optimizer state the reference forgets, ``module.``-prefix tolerant on load (train.py:212-236).
+* ``ema_state_dict`` -- the model's state dict with the averaged weights kept by ``optim.ClipAdamW(ema_decay=...)`` (beyond the
+  reference, which keeps no average); the optimizer's own state dict carries the average and its counter through
+  ``save_checkpoint`` / ``load_checkpoint``.
 * ``load_pretrained_backbone`` -- models/utils.py:305-328 (``load_pretrained_weights``) without the network: the
   ``efficientnet-b*.pth`` file named by ``url_map`` is looked up in a local directory; same key handling (drop ``_fc.*``
   unless load_fc, and insist that nothing else is missing)."""
@@ -29,6 +32,14 @@ def unwrap(model):
 
 def get_state_dict(model):
     return unwrap(model).state_dict()
+
+
+def ema_state_dict(model, optimizer):
+    """The model's state dict with the AVERAGED weights of optim.ClipAdamW(ema_decay=...): swap the average in, clone, swap back (also
+    when the clone raises).  Buffers (BatchNorm running statistics, frozen on the training path) are the model's own.  This is the
+    file to publish: `torch.save(ema_state_dict(model, opt), path)` loads into a plain model."""
+    with optimizer.ema_weights():
+        return {k: v.detach().clone() for k, v in get_state_dict(model).items()}
 
 
 def strip_module_prefix(sd):

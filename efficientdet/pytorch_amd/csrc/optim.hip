@@ -17,7 +17,15 @@
 //   train_release_kernel    if the step ran: pending = 0, applied += 1   (single writer, ordered behind every reader)
 // No kernel both reads a control word from many workgroups and writes it.  Accumulate moves 12 bytes per parameter (8 on the first
 // micro-batch of a window, which writes instead of adding: the arena never needs a zeroing pass).
+//
+// Parameter EMA (include/effdet_ema.h; the EMA instantiations): the update kernel has every new parameter value in registers, so the
+// average is one more stream of it -- e += om * (p - e), 8 more bytes per parameter, no second read of p -- and a tensor without a
+// gradient takes an EMA-only pass over its chunk.  om = 1 - min(decay, (1 + t) / (10 + t)) is computed ONCE per step by thread 0 of
+// opt_norm_final_kernel (one workgroup) from the counter `updates` of effdet_ema_ctl_t, stored next to the norm (scratch[1]) and read
+// from there by the update kernel's workgroups; the same thread then advances `updates`: it is the word's only reader and only writer,
+// so no launch is added.  ema_swap_kernel exchanges p and e in place over the same block table (evaluation with the averaged weights).
 #include "common.h"
+#include "../../../include/effdet_ema.h"
 
 namespace {
 
@@ -34,9 +42,13 @@ struct OptK {
   // GATED instantiations only: g is the accumulation arena's table, `has` the micro-step's gradient table (has[i] == 0: tensor i has
   // no gradient) and ctl the control block that says whether the step runs at all
   const unsigned long long* has; const effdet_train_ctl_t* ctl;
+  // EMA instantiations only: the average's table (the moments' offsets), its control block, the by-value decay (used when hyper is
+  // null; hyper[6] otherwise) and the warm-up switch.  om lives in norm[1].
+  const unsigned long long* e; effdet_ema_ctl_t* ectl; float ema_decay; int ema_warmup;
 };
 
 static_assert(sizeof(effdet_train_ctl_t) == 32, "effdet_train_ctl_t is read back as 32 bytes by the binding");
+static_assert(sizeof(effdet_ema_ctl_t) == 16, "effdet_ema_ctl_t is read back as 16 bytes by the binding");
 
 __device__ __forceinline__ bool gate_open(const effdet_train_ctl_t* c) { return c->skip == 0 && c->pending != 0; }
 
@@ -64,6 +76,29 @@ __device__ __forceinline__ f32x4 load4_any(const float* q, bool al) {
   return f32x4{q[0], q[1], q[2], q[3]};
 }
 
+// The EMA recurrence: subtract, multiply, add -- three fp32 operations, each rounded to nearest, never contracted into an FMA (a
+// contracted e + om * d rounds once and differs from the restatement in the last bit).  This toolchain's __fsub_rn / __fmul_rn /
+// __fadd_rn / __fdiv_rn are the plain operators and inherit the translation unit's contraction, so the functions below switch
+// contraction off for their own statements instead; adamw1 keeps the file's default.
+__device__ __forceinline__ float ema1(float e, float p, float om) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  const float q = om * d;
+  return e + q;
+}
+
+// 1 - d, d = decay or, during the warm-up, min(decay, (1 + t) / (10 + t)) with t the updates made so far (0 on the first)
+__device__ __forceinline__ float ema_one_minus_decay(float decay, int warmup, int updates) {
+#pragma clang fp contract(off)
+  float d = decay;
+  if (warmup) {
+    const float t = (float)updates;
+    const float num = 1.0f + t, den = 10.0f + t;
+    d = fminf(d, num / den);                                 // (hipcc's fp32 division is correctly rounded by default)
+  }
+  return 1.0f - d;
+}
+
 template <bool GATED> __global__ __launch_bounds__(256) void opt_norm_kernel(const OptK k) {
   if (GATED && !gate_open(k.ctl)) return;                    // (the whole grid takes the same branch: partial[] stays untouched)
   const int ti = k.block_tensor[blockIdx.x];
@@ -85,12 +120,19 @@ template <bool GATED> __global__ __launch_bounds__(256) void opt_norm_kernel(con
 
 // one workgroup: finishes the norm and advances the per-tensor AdamW step counters (torch keeps one per parameter: a
 // parameter without gradient in some step is skipped and its bias correction lags behind)
-template <bool GATED>
+struct EmaStep { effdet_ema_ctl_t* ectl; const float* hyper; float decay; int warmup; };
+
+template <bool GATED, bool EMA>
 __global__ __launch_bounds__(1024) void opt_norm_final_kernel(const float* __restrict__ partial, int nb, float* __restrict__ norm,
                                                               const unsigned long long* __restrict__ g, int* __restrict__ steps, int nt,
-                                                              const effdet_train_ctl_t* __restrict__ ctl) {
+                                                              const effdet_train_ctl_t* __restrict__ ctl, const EmaStep es) {
   __shared__ float red[16];
   if (GATED && !gate_open(ctl)) return;
+  if (EMA && threadIdx.x == 0) {                             // this step's om, then the counter: one thread reads and writes `updates`
+    const int u = es.ectl->updates;
+    norm[1] = ema_one_minus_decay(es.hyper ? es.hyper[6] : es.decay, es.warmup, u);
+    es.ectl->updates = u + 1;
+  }
   for (int i = threadIdx.x; i < nt; i += 1024) if (g[i]) steps[i] += 1;
   float s = 0.f;
   for (int i = threadIdx.x; i < nb; i += 1024) s += partial[i];
@@ -107,13 +149,41 @@ __device__ __forceinline__ void adamw1(float& p, float& m, float& v, float g, co
   p -= step_size * m / (sqrtf(v) / bc2_sqrt + k.eps);
 }
 
-template <bool GATED> __global__ __launch_bounds__(256) void opt_adamw_kernel(const OptK kk) {
+// a tensor without a gradient in this step: AdamW leaves it alone, its average still follows the unchanged p
+__device__ __forceinline__ void ema_only_chunk(const OptK& kk, int ti, float om) {
+  const float* p = (const float*)kk.p[ti]; float* e = (float*)kk.e[ti];
+  const long long n = kk.n[ti], off = (long long)(blockIdx.x - kk.block_first[ti]) * OPT_CHUNK;
+  const long long end = off + OPT_CHUNK < n ? off + OPT_CHUNK : n;
+  const bool alp = (((unsigned long long)(p + off)) & 15ull) == 0, ale = (((unsigned long long)(e + off)) & 15ull) == 0;
+  for (long long i = off + threadIdx.x * 4; i < end; i += 1024) {
+    if (i + 3 < end) {
+      const f32x4 pv = load4_any(p + i, alp);
+      f32x4 ev = load4_any(e + i, ale);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) ev[c] = ema1(ev[c], pv[c], om);
+      if (ale) *(f32x4*)(e + i) = ev;
+      else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[i + c] = ev[c];
+      }
+    } else {
+      for (long long j = i; j < end; ++j) e[j] = ema1(e[j], p[j], om);
+    }
+  }
+}
+
+template <bool GATED, bool EMA> __global__ __launch_bounds__(256) void opt_adamw_kernel(const OptK kk) {
   if (GATED && !gate_open(kk.ctl)) return;
   const Hyper k = hyper_of(kk);
   const int ti = kk.block_tensor[blockIdx.x];
   float* g = (float*)(GATED && !kk.has[ti] ? 0ull : kk.g[ti]);
-  if (!g) return;
+  const float om = EMA ? kk.norm[1] : 0.f;                   // written by opt_norm_final_kernel of this step
+  if (!g) {
+    if (EMA) ema_only_chunk(kk, ti, om);
+    return;
+  }
   float* p = (float*)kk.p[ti]; float* m = (float*)kk.m[ti]; float* v = (float*)kk.v[ti];
+  float* ea = EMA ? (float*)kk.e[ti] : nullptr;
   // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)) with torch.clamp's NaN rule -- a NaN norm turns every gradient into NaN
   const float coef = k.max_norm > 0.f ? nan_min(1.0f, k.max_norm / (kk.norm[0] + 1e-6f)) : 1.0f;
   const float t = (float)kk.steps[ti];                       // already advanced by opt_norm_final_kernel
@@ -122,21 +192,32 @@ template <bool GATED> __global__ __launch_bounds__(256) void opt_adamw_kernel(co
   const long long end = off + OPT_CHUNK < n ? off + OPT_CHUNK : n;
   const bool alg = (((unsigned long long)(g + off)) & 15ull) == 0;
   const bool alp = ((((unsigned long long)(p + off)) | ((unsigned long long)(m + off)) | ((unsigned long long)(v + off))) & 15ull) == 0;
+  const bool ale = EMA && (((unsigned long long)(ea + off)) & 15ull) == 0;
   // one code path for the arithmetic (see load4_any): vector or scalar memory operations, identical values
   for (long long i = off + threadIdx.x * 4; i < end; i += 1024) {
     if (i + 3 < end) {
       f32x4 gv = load4_any(g + i, alg), pv = load4_any(p + i, alp), mv = load4_any(m + i, alp), vv = load4_any(v + i, alp);
+      f32x4 ev{};
+      if (EMA) ev = load4_any(ea + i, ale);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pv[e], me = mv[e], ve = vv[e];
         const float ge = gv[e] * coef;
         adamw1(pe, me, ve, ge, k, step_size, bc2_sqrt);
         pv[e] = pe; mv[e] = me; vv[e] = ve; gv[e] = ge;
+        if (EMA) ev[e] = ema1(ev[e], pe, om);
       }
       if (alp) { *(f32x4*)(p + i) = pv; *(f32x4*)(m + i) = mv; *(f32x4*)(v + i) = vv; }
       else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) { p[i + e] = pv[e]; m[i + e] = mv[e]; v[i + e] = vv[e]; }
+      }
+      if (EMA) {
+        if (ale) *(f32x4*)(ea + i) = ev;
+        else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ea[i + e] = ev[e];
+        }
       }
       if (kk.write_grad) {
         if (alg) *(f32x4*)(g + i) = gv;
@@ -147,6 +228,7 @@ template <bool GATED> __global__ __launch_bounds__(256) void opt_adamw_kernel(co
       }
     } else {
       for (long long j = i; j < end; ++j) { const float gj = g[j] * coef; adamw1(p[j], m[j], v[j], gj, k, step_size, bc2_sqrt); if (kk.write_grad) g[j] = gj; }
+      if (EMA) for (long long j = i; j < end; ++j) ea[j] = ema1(ea[j], p[j], om);       // (a loop of its own: the one above stays the EMA-less kernel's, instruction for instruction)
     }
   }
 }
@@ -198,15 +280,43 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const unsigned lon
   }
 }
 
-template <bool GATED> int launch_step(const OptK& k, float max_norm, hipStream_t st) {
+// in-place exchange of p and e over the optimizer's block table (one launch; no control word is read)
+__global__ __launch_bounds__(256) void ema_swap_kernel(const unsigned long long* __restrict__ params, const unsigned long long* __restrict__ ema,
+                                                       const long long* __restrict__ numel, const int* __restrict__ block_tensor,
+                                                       const int* __restrict__ block_first) {
+  const int ti = block_tensor[blockIdx.x];
+  float* p = (float*)params[ti]; float* e = (float*)ema[ti];
+  const long long n = numel[ti], off = (long long)(blockIdx.x - block_first[ti]) * OPT_CHUNK;
+  const long long end = off + OPT_CHUNK < n ? off + OPT_CHUNK : n;
+  const bool alp = (((unsigned long long)(p + off)) & 15ull) == 0, ale = (((unsigned long long)(e + off)) & 15ull) == 0;
+  for (long long i = off + threadIdx.x * 4; i < end; i += 1024) {
+    if (i + 3 < end) {
+      const f32x4 pv = load4_any(p + i, alp), ev = load4_any(e + i, ale);
+      if (alp) *(f32x4*)(p + i) = ev;
+      else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) p[i + c] = ev[c];
+      }
+      if (ale) *(f32x4*)(e + i) = pv;
+      else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[i + c] = pv[c];
+      }
+    } else {
+      for (long long j = i; j < end; ++j) { const float x = p[j]; p[j] = e[j]; e[j] = x; }
+    }
+  }
+}
+
+template <bool GATED, bool EMA = false> int launch_step(const OptK& k, float max_norm, hipStream_t st) {
   if (max_norm > 0.f) {
     hipLaunchKernelGGL(opt_norm_kernel<GATED>, dim3(k.nblocks), dim3(256), 0, st, k);
     EFFDET_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(opt_norm_final_kernel<GATED>, dim3(1), dim3(1024), 0, st, (const float*)k.partial, max_norm > 0.f ? k.nblocks : 0, k.norm,
-                     GATED ? k.has : k.g, k.steps, k.ntensors, k.ctl);
+  hipLaunchKernelGGL((opt_norm_final_kernel<GATED, EMA>), dim3(1), dim3(1024), 0, st, (const float*)k.partial, max_norm > 0.f ? k.nblocks : 0,
+                     k.norm, GATED ? k.has : k.g, k.steps, k.ntensors, k.ctl, EmaStep{k.ectl, k.hyper, k.ema_decay, k.ema_warmup});
   EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(opt_adamw_kernel<GATED>, dim3(k.nblocks), dim3(256), 0, st, k);
+  hipLaunchKernelGGL((opt_adamw_kernel<GATED, EMA>), dim3(k.nblocks), dim3(256), 0, st, k);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
@@ -266,6 +376,59 @@ extern "C" int effdet_clip_adamw_step_gated(const unsigned long long* params, co
   const int rc = launch_step<true>(k, max_norm, st);
   if (rc != EFFDET_OK) return rc;
   hipLaunchKernelGGL(train_release_kernel, dim3(1), dim3(1), 0, st, ctl);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// ---- include/effdet_ema.h: the two steps with the parameter average as one more stream, and the in-place weight swap ----
+extern "C" int effdet_clip_adamw_step_ema(const unsigned long long* params, const unsigned long long* grads, const unsigned long long* exp_avg,
+                                          const unsigned long long* exp_avg_sq, const unsigned long long* ema, const long long* numel,
+                                          const int* block_tensor, const int* block_first, int ntensors, int nblocks, float* scratch,
+                                          int* steps, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                          int write_grad, float ema_decay, int ema_warmup, const float* hyper_dev, effdet_ema_ctl_t* ema_ctl,
+                                          effdet_stream_t stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !ema || !numel || !block_tensor || !block_first || !scratch || !steps || !ema_ctl ||
+      nblocks < 1 || ntensors < 1)
+    return EFFDET_EINVAL;
+  if (!hyper_dev && !(ema_decay >= 0.f && ema_decay < 1.f)) return EFFDET_EINVAL;
+  OptK k{};
+  k.p = params; k.g = grads; k.m = exp_avg; k.v = exp_avg_sq; k.n = numel; k.block_tensor = block_tensor; k.block_first = block_first;
+  k.norm = scratch; k.partial = scratch + 64;
+  k.max_norm = max_norm; k.lr = lr; k.beta1 = beta1; k.beta2 = beta2; k.eps = eps; k.wd = weight_decay;
+  k.steps = steps; k.nblocks = nblocks; k.ntensors = ntensors; k.write_grad = write_grad; k.hyper = hyper_dev;
+  k.e = ema; k.ectl = ema_ctl; k.ema_decay = ema_decay; k.ema_warmup = ema_warmup;
+  return launch_step<false, true>(k, max_norm, (hipStream_t)stream);
+}
+
+extern "C" int effdet_clip_adamw_step_gated_ema(const unsigned long long* params, const unsigned long long* grads,
+                                                const unsigned long long* acc, const unsigned long long* exp_avg,
+                                                const unsigned long long* exp_avg_sq, const unsigned long long* ema, const long long* numel,
+                                                const int* block_tensor, const int* block_first, int ntensors, int nblocks, float* scratch,
+                                                int* steps, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                                float ema_decay, int ema_warmup, const float* hyper_dev, effdet_train_ctl_t* ctl,
+                                                effdet_ema_ctl_t* ema_ctl, effdet_stream_t stream) {
+  if (!params || !grads || !acc || !exp_avg || !exp_avg_sq || !ema || !numel || !block_tensor || !block_first || !scratch || !steps || !ctl ||
+      !ema_ctl || nblocks < 1 || ntensors < 1)
+    return EFFDET_EINVAL;
+  if (!hyper_dev && !(ema_decay >= 0.f && ema_decay < 1.f)) return EFFDET_EINVAL;
+  OptK k{};
+  k.p = params; k.g = acc; k.has = grads; k.m = exp_avg; k.v = exp_avg_sq; k.n = numel; k.block_tensor = block_tensor; k.block_first = block_first;
+  k.norm = scratch; k.partial = scratch + 64;
+  k.max_norm = max_norm; k.lr = lr; k.beta1 = beta1; k.beta2 = beta2; k.eps = eps; k.wd = weight_decay;
+  k.steps = steps; k.nblocks = nblocks; k.ntensors = ntensors; k.write_grad = 0; k.hyper = hyper_dev; k.ctl = ctl;
+  k.e = ema; k.ectl = ema_ctl; k.ema_decay = ema_decay; k.ema_warmup = ema_warmup;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch_step<true, true>(k, max_norm, st);
+  if (rc != EFFDET_OK) return rc;
+  hipLaunchKernelGGL(train_release_kernel, dim3(1), dim3(1), 0, st, ctl);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+extern "C" int effdet_ema_swap(const unsigned long long* params, const unsigned long long* ema, const long long* numel,
+                               const int* block_tensor, const int* block_first, int ntensors, int nblocks, effdet_stream_t stream) {
+  if (!params || !ema || !numel || !block_tensor || !block_first || nblocks < 1 || ntensors < 1) return EFFDET_EINVAL;
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, params, ema, numel, block_tensor, block_first);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }

@@ -215,6 +215,9 @@ def replay_vs_eager(graphed, eager_step=None):
     restore complete), and replay vs eager differs at most by what a collective's summation order may change under DDP.
     -> {'replay_vs_eager', 'eager_vs_eager', 'replay_vs_replay'} (norm of the parameter difference / norm of the step's own update),
        'update_norm', 'finite', 'losses_replay', 'losses_eager'.   Leaves the model one replayed step past the state it found.
+    With a parameter average (ClipAdamW(ema_decay=...)) the EMA arena and its update counter are saved, restored and compared along with
+    the moments: 'ema_replay_vs_eager', 'ema_eager_vs_eager', 'ema_replay_vs_replay' (norm of the arena difference / norm of the step's own
+    EMA update), 'ema_update_norm' and 'ema_updates' (the counter after the eager run, the replay, and the saved value: +1, +1).
     (Round 5: this is the check that found the captured step training on ~1e-7 of its gradients -- a hipMemsetAsync node inside the loss
     did not hold in the graph -- while every 'losses track, parameters within AdamW's sign noise' test stayed green.)"""
     opt = graphed.optimizer
@@ -232,6 +235,9 @@ def replay_vs_eager(graphed, eager_step=None):
     torch.cuda.synchronize()
     p0, m0, v0, s0 = flat(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), t['steps'].clone()
     dc0 = [d.clone() for d in dc]
+    ema = bool(getattr(opt, 'ema', False))
+    if ema:
+        e0, u0 = opt.ema_avg.clone(), t['ectl'].clone()
     side = graphed.stream
 
     def run(replay):
@@ -240,6 +246,8 @@ def replay_vs_eager(graphed, eager_step=None):
             for p in ps:
                 n = p.numel(); p.copy_(p0[o:o + n].view_as(p)); o += n
             opt.exp_avg.copy_(m0); opt.exp_avg_sq.copy_(v0); t['steps'].copy_(s0)
+            if ema:
+                opt.ema_avg.copy_(e0); t['ectl'].copy_(u0)
             for d, d0 in zip(dc, dc0):
                 d.copy_(d0)
         torch.cuda.synchronize()
@@ -249,12 +257,22 @@ def replay_vs_eager(graphed, eager_step=None):
             with torch.cuda.stream(side):
                 cl, rl = (graphed._step if eager_step is None else eager_step)()
         torch.cuda.synchronize()
+        if ema:
+            emas.append((opt.ema_avg.clone(), int(t['ectl'][0])))
         return flat(), (float(cl.detach().reshape(-1)[0]), float(rl.detach().reshape(-1)[0]))
+    emas = []
     pe, le = run(False); pe2, _ = run(False)
     pg, lg = run(True); pg2, _ = run(True)
     upd = float((pe - p0).norm())
     rel = lambda a, b: float((a - b).norm()) / max(upd, 1e-30)
-    return {'replay_vs_eager': rel(pg, pe), 'eager_vs_eager': rel(pe2, pe), 'replay_vs_replay': rel(pg2, pg), 'update_norm': upd,
+    extra = {}
+    if ema:
+        (ee, ue), (ee2, _), (eg, ug), (eg2, _) = emas
+        eupd = float((ee - e0).norm())
+        erel = lambda a, b: float((a - b).norm()) / max(eupd, 1e-30)
+        extra = {'ema_replay_vs_eager': erel(eg, ee), 'ema_eager_vs_eager': erel(ee2, ee), 'ema_replay_vs_replay': erel(eg2, eg),
+                 'ema_update_norm': eupd, 'ema_updates': (ue, ug, int(u0[0]))}
+    return {**extra, 'replay_vs_eager': rel(pg, pe), 'eager_vs_eager': rel(pe2, pe), 'replay_vs_replay': rel(pg2, pg), 'update_norm': upd,
             'finite': bool(torch.isfinite(pg).all()), 'losses_replay': lg, 'losses_eager': le}
 
 

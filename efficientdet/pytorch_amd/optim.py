@@ -20,8 +20,20 @@ captured loop (graph.GraphedTrainLoop) takes no host decision that depends on da
         opt.step()                      # clip + AdamW on the sum; a no-op when the micro-step just run was skipped or nothing is pending
 
 A third arena holds the sum, a 32-byte device control block (effdet_train_ctl_t) the skip flag, the number of pending micro-batches,
-the counters and the fp64 loss meter; loss_meter() reads it back (one device-to-host copy), reset_epoch() clears it."""
+the counters and the fp64 loss meter; loss_meter() reads it back (one device-to-host copy), reset_epoch() clears it.
+
+`ClipAdamW(..., ema_decay=0.9998)` keeps an exponential moving average of the parameters (the EfficientDet paper trains and evaluates
+with one) as one more stream of the update kernel: an fp32 arena with the moments' offsets and a device counter of the updates made.
+On every step that is APPLIED (the gated form decides that on the device), for every tensor of the table, with p the value after AdamW:
+
+    d = min(decay, (1 + updates) / (10 + updates)) if ema_warmup else decay;   e += (1 - d) * (p - e);   updates += 1
+
+No second pass over the parameters, nothing extra to capture (GraphedTrainStep / GraphedTrainLoop call step()), and the decay travels
+in the device hyper buffer like lr.  swap_ema() exchanges parameters and average in place; `with opt.ema_weights():` evaluates with the
+averaged weights and swaps back; checkpoint.ema_state_dict(model, opt) is the file to publish."""
+import contextlib
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -32,11 +44,16 @@ from . import ops as ops_mod
 
 class ClipAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=0.0, write_clipped_grads=False,
-                 accumulate=False):
+                 accumulate=False, ema_decay=None, ema_warmup=True):
         if accumulate and write_clipped_grads:
             raise ValueError('ClipAdamW: write_clipped_grads=True cannot be combined with accumulate=True (the step clips the sum held in '
                              'the accumulation arena; p.grad holds one micro-batch and is not what was clipped)')
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm)
+        self.ema = ema_decay is not None
+        if self.ema:                         # (the key exists only with the average on: param_groups of a plain ClipAdamW stay as they were)
+            defaults['ema_decay'] = self._checked_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._swapped = False                # swap_ema(): the parameters hold the average and the arena the trained weights
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise ValueError('ClipAdamW supports a single parameter group (the reference uses one, train.py:268)')
@@ -46,6 +63,17 @@ class ClipAdamW(torch.optim.Optimizer):
         self._table = None
         self._step = 0
         self._captured = False               # a step() ran under stream capture (its launch sequence is frozen in a hipGraph)
+
+    @staticmethod
+    def _checked_decay(d):
+        """0 <= decay < 1 as the fp32 value the kernel reads (a decay that rounds to 1.0f would freeze the average); NaN is refused."""
+        try:
+            d = float(d)
+        except (TypeError, ValueError):
+            raise ValueError('ClipAdamW: ema_decay must be a number in [0, 1), got %r' % (d,))
+        if math.isnan(d) or not (0.0 <= d < 1.0) or not float(np.float32(d)) < 1.0:
+            raise ValueError('ClipAdamW: ema_decay must satisfy 0 <= decay < 1 (as fp32), got %r' % (d,))
+        return d
 
     # ---- the device tables (built once; parameter and moment storage is stable) ----
     def _build(self):
@@ -85,9 +113,21 @@ class ClipAdamW(torch.optim.Optimizer):
             'steps': torch.zeros(n, dtype=torch.int32, device=dev), 'p_sig': [p.data_ptr() for p in ps],
             # hyper-parameters live on the device (read by the update kernel at run time): a captured step follows the
             # schedule of param_groups[0] -- sync_hyper() refreshes them ahead of a graph replay
-            'hyper': torch.zeros(6, dtype=torch.float32, device=dev), 'hyper_host': torch.zeros(6, dtype=torch.float32).pin_memory(),
+            # (a seventh float carries the EMA decay; the six the kernels without the average read stay where they are)
+            'hyper': torch.zeros(7 if self.ema else 6, dtype=torch.float32, device=dev),
+            'hyper_host': torch.zeros(7 if self.ema else 6, dtype=torch.float32).pin_memory(),
             'hyper_last': None, 'hyper_evt': None,
         }
+        if self.ema:
+            # the average (same offsets as the moments; e = p to begin with) and its control block (effdet_ema_ctl_t: the update counter)
+            self.ema_avg = torch.zeros(int(offs[-1]), dtype=torch.float32, device=dev)
+            t['e_ptr'] = i64([self.ema_avg.data_ptr() + 4 * int(o) for o in offs[:-1]])
+            t['ectl'] = torch.zeros(C.sizeof(L.EmaCtl) // 4, dtype=torch.int32, device=dev)
+            t['e_views'] = [self.ema_avg[int(offs[i]):int(offs[i]) + numel[i]].view_as(p) for i, p in enumerate(ps)]
+            with torch.no_grad():
+                for e, p in zip(t['e_views'], ps):
+                    e.copy_(p)
+            self._swapped = False
         if self.accumulate:
             # the sum over a window's micro-batches (same offsets as the moments; written, not added to, by the first micro-batch of a
             # window, so it is never zeroed) and the control block (effdet_train_ctl_t, 32 bytes; zero = start of an epoch)
@@ -99,6 +139,8 @@ class ClipAdamW(torch.optim.Optimizer):
             self.state[p] = {'step': torch.tensor(0.0),                # refreshed from the device counters in state_dict()
                              'exp_avg': self.exp_avg[int(offs[i]):int(offs[i]) + numel[i]].view_as(p),
                              'exp_avg_sq': self.exp_avg_sq[int(offs[i]):int(offs[i]) + numel[i]].view_as(p)}
+            if self.ema:
+                self.state[p]['ema'] = t['e_views'][i]
         self._table = t
 
     # ---- checkpointing (train.py:279-291 saves only the model; resuming needs the moments + per-tensor step counters) ----
@@ -110,17 +152,37 @@ class ClipAdamW(torch.optim.Optimizer):
             steps = self._table['steps'].cpu()
             for i, p in enumerate(self._table['params']):
                 self.state[p]['step'] = torch.tensor(float(steps[i]))
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.ema:
+            # the average travels as 'ema' per parameter (views of the arena) and the counter as 'ema_updates', read from the device.
+            # Save outside ema_weights(): while swapped in, 'ema' holds the trained weights and the model the average.
+            sd['ema_updates'] = self.ema_updates()
+        return sd
 
     def load_state_dict(self, state_dict):
         """Loads a state_dict of this class or of torch.optim.AdamW over the same parameter list: moments are copied INTO
         the arenas and the step counters into the device array (super() alone would leave self.state pointing at fresh
         tensors the kernels never see)."""
+        if self._swapped:
+            raise RuntimeError('ClipAdamW.load_state_dict while the averaged weights are swapped in; call swap_ema() (or leave ema_weights()) first')
+        decay = self.param_groups[0].get('ema_decay')
         super().load_state_dict(state_dict)
+        g = self.param_groups[0]                                       # (now the loaded group: the average is on or off by construction)
+        if not self.ema:
+            g.pop('ema_decay', None)
+        else:
+            g['ema_decay'] = self._checked_decay(decay if g.get('ema_decay') is None else g['ema_decay'])
         loaded = {p: dict(st) for p, st in self.state.items()}
         self.state.clear()
-        self._build()
+        self._build()                                                  # (with the average on: e = the current p, updates = 0)
         t = self._table
+        if self.ema:
+            have = [i for i, p in enumerate(t['params']) if (loaded.get(p) or {}).get('ema') is not None]
+            for i in have:
+                p = t['params'][i]
+                t['e_views'][i].copy_(loaded[p]['ema'].to(p.device, torch.float32).view_as(p))
+            # a state without the average (torch's AdamW, or this class with it off) starts one at the current parameters
+            t['ectl'][0] = int(state_dict.get('ema_updates', 0)) if have else 0
         steps = torch.zeros(t['n'], dtype=torch.int32)
         for i, p in enumerate(t['params']):
             st = loaded.get(p)
@@ -135,10 +197,11 @@ class ClipAdamW(torch.optim.Optimizer):
     def _hyper_values(self):
         g = self.param_groups[0]
         b1, b2 = g['betas']
-        return (float(g['max_norm'] or 0.0), float(g['lr']), float(b1), float(b2), float(g['eps']), float(g['weight_decay']))
+        hv = (float(g['max_norm'] or 0.0), float(g['lr']), float(b1), float(b2), float(g['eps']), float(g['weight_decay']))
+        return hv + (self._checked_decay(g['ema_decay']),) if self.ema else hv
 
     def sync_hyper(self):
-        """Upload param_groups[0]'s {max_norm, lr, betas, eps, weight_decay} to the device buffer the update kernel reads, if
+        """Upload param_groups[0]'s {max_norm, lr, betas, eps, weight_decay} (and ema_decay) to the device buffer the update kernel reads, if
         they changed since the last upload.  step() calls it; graph.GraphedTrainStep calls it before every replay, so an lr
         scheduler (train.py:133,269: ReduceLROnPlateau) drives captured steps exactly like eager ones."""
         if self._table is None:
@@ -214,9 +277,15 @@ class ClipAdamW(torch.optim.Optimizer):
             raise RuntimeError('ClipAdamW honours ONE parameter group (the reference builds one, train.py:266); got %d -- other '
                                "groups' lr / weight_decay would be silently ignored" % len(self.param_groups))
 
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError('ClipAdamW.%s while the averaged weights are swapped in: the step would train the average; call swap_ema() '
+                               '(or leave ema_weights()) first' % what)
+
     @torch.no_grad()
     def step(self, closure=None):
         self._one_group()
+        self._not_swapped('step')
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -231,6 +300,17 @@ class ClipAdamW(torch.optim.Optimizer):
         if self.accumulate:
             # the gated form: the sum in the arena is the gradient; which tensors have one is what the last accumulate_grads() uploaded.
             # Nothing moves when the micro-step just run was skipped or nothing is pending (decided on the device).
+            if self.ema:
+                Lb = L.require('effdet_clip_adamw_step_gated_ema')
+                L.check(Lb.effdet_clip_adamw_step_gated_ema(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['a_ptr']), L.ptr(t['m_ptr']),
+                                                            L.ptr(t['v_ptr']), L.ptr(t['e_ptr']), L.ptr(t['numel']), L.ptr(t['block_tensor']),
+                                                            L.ptr(t['block_first']), t['n'], t['nblocks'], L.ptr(t['scratch']),
+                                                            L.ptr(t['steps']), float(g['max_norm'] or 0.0), float(g['lr']), float(b1),
+                                                            float(b2), float(g['eps']), float(g['weight_decay']), float(g['ema_decay']),
+                                                            int(self.ema_warmup), L.ptr(t['hyper']), L.ptr(t['ctl']), L.ptr(t['ectl']),
+                                                            L.stream_ptr()),
+                        'effdet_clip_adamw_step_gated_ema')
+                return loss
             Lb = L.require('effdet_clip_adamw_step_gated')
             L.check(Lb.effdet_clip_adamw_step_gated(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['a_ptr']), L.ptr(t['m_ptr']), L.ptr(t['v_ptr']),
                                                     L.ptr(t['numel']), L.ptr(t['block_tensor']), L.ptr(t['block_first']), t['n'], t['nblocks'],
@@ -238,6 +318,16 @@ class ClipAdamW(torch.optim.Optimizer):
                                                     float(g['lr']), float(b1), float(b2), float(g['eps']),
                                                     float(g['weight_decay']), L.ptr(t['hyper']), L.ptr(t['ctl']), L.stream_ptr()),
                     'effdet_clip_adamw_step_gated')
+            return loss
+        if self.ema:
+            Lb = L.require('effdet_clip_adamw_step_ema')
+            L.check(Lb.effdet_clip_adamw_step_ema(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['m_ptr']), L.ptr(t['v_ptr']), L.ptr(t['e_ptr']),
+                                                  L.ptr(t['numel']), L.ptr(t['block_tensor']), L.ptr(t['block_first']), t['n'], t['nblocks'],
+                                                  L.ptr(t['scratch']), L.ptr(t['steps']), float(g['max_norm'] or 0.0), float(g['lr']),
+                                                  float(b1), float(b2), float(g['eps']), float(g['weight_decay']),
+                                                  int(self.write_clipped_grads), float(g['ema_decay']), int(self.ema_warmup),
+                                                  L.ptr(t['hyper']), L.ptr(t['ectl']), L.stream_ptr()),
+                    'effdet_clip_adamw_step_ema')
             return loss
         L.check(L.lib().effdet_clip_adamw_step(L.ptr(t['p_ptr']), L.ptr(t['g_ptr']), L.ptr(t['m_ptr']), L.ptr(t['v_ptr']), L.ptr(t['numel']),
                                                L.ptr(t['block_tensor']), L.ptr(t['block_first']), t['n'], t['nblocks'],
@@ -264,6 +354,7 @@ class ClipAdamW(torch.optim.Optimizer):
         before the epoch does."""
         self._need_accumulate('accumulate_grads')
         self._one_group()
+        self._not_swapped('accumulate_grads')
         if not (isinstance(loss, torch.Tensor) and loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
             raise ValueError('ClipAdamW.accumulate_grads needs the loss as a one-element fp32 GPU tensor (it is read on the device)')
         t = self._ensure_table()
@@ -313,3 +404,45 @@ class ClipAdamW(torch.optim.Optimizer):
     def grad_norm(self):
         """Total gradient norm measured by the last step() (device scalar; clipping enabled only)."""
         return self._table['scratch'][0] if self._table is not None else None
+
+    # ---- the parameter average (ema_decay=...) ----
+    def _need_ema(self, what):
+        if not self.ema:
+            raise RuntimeError('ClipAdamW.%s needs ClipAdamW(ema_decay=...)' % what)
+
+    def ema_params(self):
+        """The average, one view of the arena per trainable parameter, in the optimizer's order (while swapped in by swap_ema() these
+        hold the trained weights and the parameters the average)."""
+        self._need_ema('ema_params')
+        return list(self._ensure_table()['e_views'])
+
+    def ema_updates(self):
+        """EMA updates applied so far: the device counter (one device-to-host read)."""
+        self._need_ema('ema_updates')
+        return 0 if self._table is None else int(self._table['ectl'][:1].cpu()[0])
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange parameters and average in place (one launch over the optimizer's block table).  After an odd number of calls the
+        model computes with the averaged weights, and step() / accumulate_grads() are refused; a second call restores both bit for bit."""
+        self._need_ema('swap_ema')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ClipAdamW.swap_ema under stream capture: every replay would exchange the weights again; swap outside the graph')
+        t = self._ensure_table()
+        Lb = L.require('effdet_ema_swap')
+        L.check(Lb.effdet_ema_swap(L.ptr(t['p_ptr']), L.ptr(t['e_ptr']), L.ptr(t['numel']), L.ptr(t['block_tensor']), L.ptr(t['block_first']),
+                                   t['n'], t['nblocks'], L.stream_ptr()), 'effdet_ema_swap')
+        self._swapped = not self._swapped
+        ops_mod.bump_param_generation()      # parameters were rewritten through raw pointers: packed-weight caches must refresh
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights(): evaluate(model)`: the averaged weights are swapped in for the block and the trained ones are back
+        after it, also when the block raises."""
+        self._need_ema('ema_weights')
+        self._not_swapped('ema_weights')
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
