@@ -1,4 +1,4 @@
-"""ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h).
+"""ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -221,6 +221,13 @@ EMA_SIGNATURES = {
     'effdet_clip_adamw_step_gated_ema': 'i:pppppppppiippfffffffippps',
     'effdet_ema_swap': 'i:pppppiis',
 }
+# The host-only query of the depthwise launch plans, declared in include/effdet_dwconv_plan.h (same generation, same letters, same
+# rule; tests/test_dwconv_cases_host.py compares this table with that header's prototype).
+PLAN_SIGNATURES = {
+    'effdet_dwconv_plan_info': 'i:iiiiiiiiiiiiip',
+}
+DW_PLAN_FWD, DW_PLAN_DGRAD, DW_PLAN_WGRAD, DW_PLAN_BWD, DW_PLAN_EXPAND_FWD = 0, 1, 2, 3, 4      # EFFDET_DW_PLAN_*
+DW_INFO = ('cq', 'tpi', 'ppt', 'nbuf', 'groups', 'nslab', 'direct')                              # EFFDET_DW_INFO_* in order
 
 
 def lib():
@@ -238,7 +245,8 @@ def lib():
             raise RuntimeError('%s has ABI generation %d, this binding needs %d: rebuild it (`python -m efficientdet.pytorch_amd.build`)'
                                % (LIB_PATH, got, ABI_VERSION))
         _lib = cand
-        for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
+                list(PLAN_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

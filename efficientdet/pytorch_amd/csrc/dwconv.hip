@@ -9,6 +9,7 @@
 // at ~1-2 TB/s of algorithmic bytes).  Only weight gradients of <= 8x8 maps still use the direct kernel.
 #include <stdlib.h>
 #include "common.h"
+#include "../../../include/effdet_dwconv_plan.h"
 
 namespace {
 
@@ -1043,6 +1044,7 @@ struct DwPlan {
   size_t max_lds;              // attribute of the instance: set once per device, so the largest request, not this launch's
   int groups;                  // tile groups over all images (the weight gradients: slab rows, one per group)
   long long workspace_bytes;   // weight gradients: one [k*k + 1][C] fp32 row set per slab row
+  int cq, tpi, nslab;          // the tile walk the instance was planned with (slab chunks, tiles per image, slabs): effdet_dwconv_plan_info
 };
 
 // Byte extent of a tensor the kernels address with 32-bit buffer offsets: refused from 4 GB up (EFFDET_EUNSUPPORTED)
@@ -1077,6 +1079,7 @@ inline void slab_grid(DwPlan& p, int groups, int nslab) {
   static const int legacy = getenv("EFFDET_DW_ORDER") ? atoi(getenv("EFFDET_DW_ORDER")) == 0 : 0;
   const bool two_d = legacy || nslab == 1;
   p.groups = groups;
+  p.nslab = nslab;
   p.f.d.nslab = two_d ? 0 : nslab;
   p.grid = two_d ? dim3(groups, nslab) : dim3((unsigned)groups * nslab);
 }
@@ -1116,6 +1119,7 @@ void use_pipelined(DwPlan& p, int h, int w) {
   const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, wb = (size_t)K * K * CQ * CE * 4;
   const Walk t = walk<TL>(a.B, h, w, a.nch, CQ);
   a.ppt = t.ppt;
+  p.cq = CQ; p.tpi = t.tpi;
   static const int nb_env = getenv("EFFDET_DW_NBUF") ? atoi(getenv("EFFDET_DW_NBUF")) : 0;    // A/B switch
   a.nbuf = (a.ppt > 1 && 2 * tile + wb <= 80 * 1024 && nb_env != 1) ? 2 : 1;                  // keep >= 2 workgroups per CU
   p.lds = a.nbuf * tile + wb;
@@ -1141,6 +1145,7 @@ struct Wgrad {
     // forward tiles walked `ppt` at a time by one workgroup: fat workgroups (each ends in a reduction + a slab row that the
     // reduce kernel has to sum), but at least ~768 of them
     t.ppt = a.ppt = tiles_per_wg((long long)t.tpi * a.B * t.nslab, 768);
+    p.cq = CQ; p.tpi = t.tpi;
     const size_t tile = (size_t)TL::npiece(64 / CQ) * 1024, red = (size_t)4 * (K * K + 1) * CQ * Elem<T>::CE * 4;
     p.lds = p.max_lds = red > tile ? red : tile;
     slab_grid(p, a.B * t.groups(), t.nslab);
@@ -1165,6 +1170,7 @@ struct Bwd {       // fp32 only (bwd_fused_ok): the element type is not a parame
       if (cost < best_cost - 1e-9) { best_cost = cost; best = ppt; }
     }
     t.ppt = a.ppt = best;
+    p.cq = CQ; p.tpi = t.tpi;
     a.nbuf = (a.ppt > 1 && 2 * tile + wb <= 80 * 1024) ? 2 : 1;
     p.lds = a.nbuf * tile + wb > red ? a.nbuf * tile + wb : red;
     p.max_lds = 2 * tile + wb > red ? 2 * tile + wb : red;
@@ -1203,6 +1209,7 @@ void use_fused(DwPlan& p) {
   const Walk t = walk<DwTile<K, S>>(a.B, a.Ho, a.Wo, a.nch, 8);
   a.ppt = t.ppt;
   a.nbuf = 1;
+  p.cq = 8; p.tpi = t.tpi;
   slab_grid(p, a.B * t.groups(), t.nslab);
   p.launch = launch_fused<K, S, KS>;
 }
@@ -1377,4 +1384,34 @@ extern "C" int effdet_dwconv_wgrad(const void* x, const void* dz, float* g, floa
   if (!extent(a.x_bytes, (long long)B * H * W * C, dtype) || !extent(dz_bytes, (long long)B * Ho * Wo * C, dtype)) return EFFDET_EUNSUPPORTED;
   a.x = x; a.aux = dz; a.y = workspace; a.in_act = in_act;     // a.y = the slabs: [groups][k*k + 1][C]
   return run(p, stream, workspace, g, dsum);
+}
+
+// include/effdet_dwconv_plan.h: what the entry point of `kind` would launch for this geometry, read from the plan its own planner
+// makes -- no HIP call, nothing restated
+extern "C" int effdet_dwconv_plan_info(int kind, int dtype, int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l,
+                                       int Ho, int Wo, int Cin, int* info) {
+  if (!info || B < 1 || H < 1 || W < 1 || C < 1 || Ho < 1 || Wo < 1) return EFFDET_EINVAL;
+  DwPlan p{};
+  int rc;
+  switch (kind) {
+    case EFFDET_DW_PLAN_FWD: rc = plan<Fwd>(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo); break;
+    case EFFDET_DW_PLAN_DGRAD: rc = plan<Dgrad>(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo); break;
+    case EFFDET_DW_PLAN_WGRAD: rc = plan_wgrad(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo); break;
+    case EFFDET_DW_PLAN_BWD: rc = plan_bwd(p, dtype, B, H, W, C, k, stride, pad_t, pad_l, Ho, Wo); break;
+    case EFFDET_DW_PLAN_EXPAND_FWD:
+      rc = dtype != EFFDET_F32 ? EFFDET_EINVAL : plan_fused(p, B, H, W, Cin, C, k, stride, pad_t, pad_l, Ho, Wo);
+      break;
+    default: return EFFDET_EINVAL;
+  }
+  if (rc) return rc;
+  const bool direct = p.cq == 0;             // only the direct weight-gradient kernel walks no tiles
+  info[EFFDET_DW_INFO_CQ] = p.cq;
+  info[EFFDET_DW_INFO_TPI] = p.tpi;
+  info[EFFDET_DW_INFO_PPT] = p.f.d.ppt;
+  // the weight-gradient kernel has one tile buffer and no field for it; the direct kernel stages nothing
+  info[EFFDET_DW_INFO_NBUF] = direct ? 0 : (p.f.d.nbuf ? p.f.d.nbuf : 1);
+  info[EFFDET_DW_INFO_GROUPS] = p.groups / B;
+  info[EFFDET_DW_INFO_NSLAB] = direct ? (int)p.grid.y : p.nslab;
+  info[EFFDET_DW_INFO_DIRECT] = direct;
+  return EFFDET_OK;
 }

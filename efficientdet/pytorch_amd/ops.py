@@ -891,6 +891,22 @@ def dwconv_bwd(dz, w_kkc, scale, zprev, k, stride, pad_t, pad_l):
     return dx, g[:k * k], g[k * k]
 
 
+DW_PLAN_KINDS = {'fwd': L.DW_PLAN_FWD, 'dgrad': L.DW_PLAN_DGRAD, 'wgrad': L.DW_PLAN_WGRAD, 'bwd': L.DW_PLAN_BWD, 'expand_fwd': L.DW_PLAN_EXPAND_FWD}
+
+
+def dwconv_plan_info(kind, dtype, B, H, W, Cch, k, stride, pad_t, pad_l, Ho, Wo, Cin=0):
+    """What the depthwise entry point of `kind` ('fwd', 'dgrad', 'wgrad', 'bwd', 'expand_fwd': Cch = Cexp) plans for a geometry, asked of
+    the library's own planner without device work (effdet_dwconv_plan_info) -> dict of cq, tpi, ppt, nbuf, groups (per image), nslab,
+    direct; or None where the entry point answers EFFDET_EUNSUPPORTED (e.g. the fused backward at a geometry it does not serve)."""
+    info = (C.c_int * len(L.DW_INFO))()
+    rc = int(L.require('effdet_dwconv_plan_info').effdet_dwconv_plan_info(
+        DW_PLAN_KINDS[kind], L.dtype_code(dtype), B, H, W, Cch, k, stride, pad_t, pad_l, Ho, Wo, Cin, info))
+    if rc == -3:
+        return None
+    L.check(rc, 'effdet_dwconv_plan_info')
+    return dict(zip(L.DW_INFO, (int(v) for v in info)))
+
+
 def pw_bwd(dz, x, w_expand, scale, res=None):
     """Data + weight gradient of the MBConv expand conv in one pass over the expanded gradient ``dz`` (effdet_pw_bwd).
     -> (dx Map, slabs [S][Cexp][1][Cin], dsum parts [S][Cexp]) for unpack_wgrad_bn, or None when the fused kernel does not serve the geometry."""

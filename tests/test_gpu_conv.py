@@ -304,7 +304,8 @@ def test_thin_pointwise_wgrad_kernel():
     dev = 'cuda'
     g = torch.Generator().manual_seed(21)
     for (B, H, W, Cin, Cout) in [(8, 64, 64, 16, 96), (8, 64, 64, 32, 16), (8, 64, 64, 24, 144), (8, 64, 64, 144, 24), (9, 60, 64, 144, 40),
-                                 (8, 64, 64, 96, 24), (3, 128, 128, 16, 16)]:
+                                 (8, 64, 64, 96, 24), (3, 128, 128, 16, 16),
+                                 (8, 64, 64, 16, 32), (8, 64, 64, 48, 16), (8, 64, 64, 32, 32)]:     # (last three: instances (2,1), (1,3), (2,2))
         x = torch.randn(B, H, W, Cin, generator=g).to(dev); dz = torch.randn(B, H, W, Cout, generator=g).to(dev)
         xm, zm = Map.of(x), Map.of(dz)
         assert ops.conv2d_wgrad_kernel_id(xm, zm, Cin=Cin, Cout=Cout, KH=1, KW=1) == 1
