@@ -24,6 +24,7 @@
 //   * 1-D grid with a bijective XCD remap: the 8 blocks that land on one XCD walk neighbouring
 //     tiles (n fastest), so the activation tile is fetched into one private L2 only.
 #include "common.h"
+#include "../../../include/effdet_live_tiles.h"
 #include <stdlib.h>
 
 #ifndef EFFDET_IGEMM_BIG_DEFAULT
@@ -56,6 +57,8 @@ struct ConvK {
   unsigned w_bytes;            // extent of the packed weights for the bounds-checked buffer loads
   int kord;                    // K walk of the persistent kernel: 0 tap-major, 1 channel-group-major
   long long w_img_bytes;       // != 0: image b reads its own packed weights at w + b * w_img_bytes (one segment, Ho*Wo % BM == 0)
+  const unsigned char* live;   // SPLIT == 2 only, may be NULL: live[mt - live_tile0] == 0 = every input tap of pixel tile mt is zero (effdet_conv2d_live)
+  int live_tile0;              // pixel tiles below it carry no flag and are live
   SegD seg[EFFDET_MAX_CONV_SEG];
 };
 
@@ -141,7 +144,20 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   const int lane = tid & 63, wave = tid >> 6;
   const int wm0 = (wave / WAVES_N) * WTM, wn0 = (wave % WAVES_N) * WTN;
 
-  const int tile = xcd_remap(blockIdx.x, gridDim.x);
+  int tile = xcd_remap(blockIdx.x, gridDim.x);
+  if constexpr (SPLIT == 2) {
+    // Flagged launch: the live tiles cluster (the coarse levels at the end of the tile range are mostly live, whole images of the fine
+    // ones dead), and the remap above hands each XCD one contiguous eighth of the range -- one XCD would get most of the work.  Deal
+    // the pixel tiles out round-robin instead (pixel tile 8 j + x to XCD x, its channel tiles back to back on it, so the activation
+    // tile is still fetched into one L2); the blocks past the last whole group of eight keep their own index.  Speed only.
+    if (p.live) {
+      const int b = blockIdx.x, whole = (p.mtiles >> 3) << 3;
+      if (b < whole * p.ntiles) {
+        const int i = b >> 3, j = i / p.ntiles;
+        tile = (j * 8 + (b & 7)) * p.ntiles + (i - j * p.ntiles);
+      } else tile = b;
+    }
+  }
   const int mt = tile / p.ntiles, nt = tile - mt * p.ntiles;
   int si = 0;
 #pragma unroll
@@ -151,6 +167,32 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   const int m_base = (mt - sg.tile_start) * BM;
   const int n_base = nt * BN;
   const int HoWo = sg.Ho * sg.Wo;
+
+  if constexpr (SPLIT == 2) {
+    // Dead tile (workgroup-uniform, ahead of every barrier and DMA): all its input taps are exact zeros and the launch has no bias /
+    // affine / activation (the host passes flags only then), so the dense loop would produce +0 everywhere -- zeros after a ReLU mask
+    // too, and the unchanged value under an in-place RES_ADD.  Write the tile's rows (split layout or fp32: the same zero bytes, the
+    // tile's channels are contiguous in either) and leave.
+    if (p.live && mt >= p.live_tile0 && p.live[mt - p.live_tile0] == 0) {
+      if (p.res_mode == EFFDET_RES_ADD) return;
+      const int rows = min(BM, sg.M - m_base), nch = min(BN, p.Cout - n_base);
+      if (p.vec_ok) {
+        const int q4 = nch >> 2;
+        for (int i = tid; i < rows * q4; i += NTHREADS) {
+          const int row = i / q4, c = i - row * q4;
+          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
+          *(uint4*)((float*)p.y + sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + 4 * c) = make_uint4(0u, 0u, 0u, 0u);
+        }
+      } else {
+        for (int i = tid; i < rows * nch; i += NTHREADS) {
+          const int row = i / nch, c = i - row * nch;
+          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
+          ((float*)p.y)[sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + c] = 0.f;
+        }
+      }
+      return;
+    }
+  }
 
   // ---- per-thread staging bookkeeping: LDS position (row tid/8 + 32*j, slot tid&7) ----
   // Staging is direct-to-LDS DMA: `buffer_load_dwordx4 ... lds` through a bounds-checked SRD.  A wave's 64 lanes
@@ -1341,6 +1383,7 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c) {
   }
   k.nseg = p->nseg;
   k.w_img_bytes = p->w_image_stride;
+  k.live = nullptr; k.live_tile0 = 0;
   if (p->w_image_stride) {
     // per-image weights: one level whose images are whole numbers of 128-pixel tiles, on the implicit-GEMM kernels only
     if (p->w_image_stride < 0 || (p->w_image_stride & 15) || p->nseg != 1 || splitfmt || (p->seg[0].Ho * p->seg[0].Wo) % BM) return EFFDET_EUNSUPPORTED;
@@ -1441,4 +1484,21 @@ extern "C" int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream) {
   ConvPlan c;
   const int id = plan_conv(p, c);
   return id < 0 ? id : c.launch(c, (hipStream_t)stream);
+}
+
+// effdet_conv2d with per-tile liveness flags (include/effdet_live_tiles.h).  The flags are per call, like x and y, and only a hint: they
+// reach the kernel where a dead tile's dense result is known to be zero bytes (or, adding in place, no change) -- the split-layout
+// 128-pixel-tile kernels without bias, affine, row scale, activation, second output or per-image weights -- and are dropped elsewhere.
+extern "C" int effdet_conv2d_live(const effdet_conv_t* p, const unsigned char* live, int live_tile0, effdet_stream_t stream) {
+  ConvPlan c;
+  const int id = plan_conv(p, c);
+  if (id < 0) return id;
+  if (live_tile0 < 0) return EFFDET_EINVAL;
+  const bool plain = !p->scale && !p->shift && !p->rowscale && !p->bc_scale && !p->z && !p->y_split && p->act == EFFDET_ACT_NONE && !p->w_image_stride;
+  bool no_shift = true;
+  for (int s = 0; s < p->nseg; ++s) if (p->seg_shift[s]) no_shift = false;
+  const bool res_ok = p->out_f32 ? (p->res_mode == EFFDET_RES_NONE || (p->res_mode == EFFDET_RES_ADD && p->res == p->y))
+                                 : (p->res_mode == EFFDET_RES_NONE || p->res_mode == EFFDET_RES_RELU_MASK);
+  if (live && (id == 8 || id == 9) && plain && no_shift && res_ok) { c.k.live = live; c.k.live_tile0 = live_tile0; }
+  return c.launch(c, (hipStream_t)stream);
 }

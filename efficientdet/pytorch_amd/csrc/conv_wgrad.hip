@@ -22,6 +22,7 @@
 //     operand (blocks of j-tile 0 only); every split stores its partial row [Cout] next to its slab, and the
 //     consumer sums the rows in slab order -- no float atomics anywhere: two runs are bitwise equal.
 #include "common.h"
+#include "../../../include/effdet_live_tiles.h"
 #include <stdlib.h>
 
 #ifndef EFFDET_WGRAD_TR_WAVES
@@ -34,6 +35,7 @@ struct WSeg {
   int H, W, Ho, Wo, M, split_start;
   long long in_off, in_bs, out_off, out_bs;
   unsigned x_bytes, dz_bytes;   // per-segment SRD extents (32-bit offsets span one tensor only)
+  int step0;                    // first 32-pixel step of the level in WgradK::live32 (levels in order, each rounded up to whole steps)
 };
 struct WgradK {
   const void* x; const void* dz; float* dw; float* dbias; float* slab;
@@ -45,6 +47,7 @@ struct WgradK {
   int K;            // taps*Cin
   int mchunk;       // pixels per split (multiple of the K-step)
   int nseg, ntiles, jtiles, vec_a;
+  const unsigned char* live32;  // conv_wgrad_split_kernel<., 1> only: live32[step] == 0 = the 32 dz pixels of the step are all zero
   WSeg seg[EFFDET_MAX_SEG];
 };
 
@@ -487,7 +490,11 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_tr_kernel(const WgradK p) 
 //   Stage = 32 pixels: dz [4 row groups][4 pieces] + x [4][4] pieces of 8 pixels x 128 B = 32 KiB, two stages, two workgroups per
 //   CU (4 waves / SIMD).  Waves 0-3 stage dz (row group w, its four 64-wide pieces), waves 4-7 stage x: one scalar pixel cursor per
 //   wave, four DMA instructions per stage.  LDS image of a piece and the fragment addressing are those of conv_wgrad_tr_kernel.
-template <int ALLR>     // 1: all 24 fragment reads of a K-step issued before its first MFMA (A/B knob EFFDET_WGRAD_SPLIT_ALLR)
+// LIVE = 1 (effdet_conv2d_wgrad_live; launched only with flags): a split walks only the 32-pixel steps of its range whose flag
+// p.live32 is set, in order, through the same two-stage pipeline -- a skipped step would have added +-0 to every accumulator and bias
+// sum.  The flags of up to 64 steps are fetched as one ballot (every wave reads the same bytes: the walk is workgroup-uniform) and
+// stage() gets a seek() that recomputes the scalar pixel cursor on a jump.  A range without a live step takes the zero-slab branch.
+template <int ALLR, int LIVE = 0>     // ALLR = 1: all 24 fragment reads of a K-step issued before its first MFMA (A/B knob EFFDET_WGRAD_SPLIT_ALLR)
 __global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
   constexpr unsigned OPB = 16384, BUFB = 2 * OPB, RG = 4096;     // operand / stage / row-group (8 pixels x 4 pieces) bytes
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
@@ -544,6 +551,27 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
   int cm = m_begin + 8 * rgi;                                      // scalar pixel cursor of this wave's row group
   int cb = cm / HoWo, crem = cm - cb * HoWo;
   int cho = crem / sg.Wo, cwo = crem - cho * sg.Wo;
+  auto seek = [&](int step) {                                      // LIVE: put the cursor on 32-pixel step `step` of the split's range
+    cm = m_begin + 32 * step + 8 * rgi;
+    cb = cm / HoWo; crem = cm - cb * HoWo;
+    cho = crem / sg.Wo; cwo = crem - cho * sg.Wo;
+  };
+  // LIVE: first live step >= s of the range (nsteps: none).  The flags of the 64-step window around s are held as a lane mask.
+  const unsigned char* const lv = LIVE ? p.live32 + sg.step0 + m_begin / 32 : nullptr;
+  int lwin = -1; unsigned long long lmask = 0ull;
+  auto next_live = [&](int s) -> int {
+    while (s < nsteps) {
+      if ((s >> 6) != lwin) {
+        lwin = s >> 6;
+        const int i = lwin * 64 + lane;
+        lmask = __ballot(i < nsteps && lv[i] != 0);
+      }
+      const unsigned long long rest = lmask >> (s & 63);
+      if (rest) return s + __builtin_ctzll(rest);
+      s = (s | 63) + 1;
+    }
+    return nsteps;
+  };
   auto stage = [&](int buf) {
     // scalar: which flag bits invalidate a lane for THIS row group (bit 0 always; past the split's end: every lane)
     const bool all_out = cm >= m_end;
@@ -590,13 +618,21 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
   float* slab = p.slab + (long long)split * p.Cout * p.K;
   const int n_alg0 = nt * 128 + wn * 64, j_alg0 = jt * 128 + wj * 32;
 
-  if (nsteps > 0) {
+  int nxt = LIVE ? next_live(0) : 0;                                // (LIVE: the step staged next; else unused past this test)
+  if (nxt < nsteps) {
+    if constexpr (LIVE) { if (nxt != 0) seek(nxt); }
     stage(0);
-    for (int kt = 0; kt < nsteps; ++kt) {
+    for (int kt = 0; LIVE ? nxt < nsteps : kt < nsteps; ++kt) {
       const unsigned cur = (unsigned)(kt & 1) * BUFB;
       dma_wait_all();
       __syncthreads();
-      if (kt + 1 < nsteps) stage((kt & 1) ^ 1);
+      if constexpr (LIVE) {
+        const int at = nxt + 1;                                     // (stage() left the cursor on the step after the one it staged)
+        nxt = next_live(at);
+        if (nxt < nsteps) { if (nxt != at) seek(nxt); stage((kt & 1) ^ 1); }
+      } else {
+        if (kt + 1 < nsteps) stage((kt & 1) ^ 1);
+      }
       uint4 bh[2], bl[2];
 #pragma unroll
       for (int b = 0; b < 2; ++b) { bh[b] = frag(b_addr[b] + cur); bl[b] = frag(b_addr[2 + b] + cur); }
@@ -1098,7 +1134,7 @@ int plan(const effdet_wgrad_t* p, WgradK& k, int& splits, int tile = 128) {
   if (p->dtype != EFFDET_F32 && p->dtype != EFFDET_BF16) return EFFDET_EINVAL;
   const int ce = p->dtype == EFFDET_F32 ? 4 : 8;
   if (p->Cin % ce || p->ldx % ce) return EFFDET_EUNSUPPORTED;
-  k.x = p->x; k.dz = p->dz; k.dw = p->dw; k.dbias = p->dbias; k.slab = nullptr; k.dbp = nullptr;
+  k.x = p->x; k.dz = p->dz; k.dw = p->dw; k.dbias = p->dbias; k.slab = nullptr; k.dbp = nullptr; k.live32 = nullptr;
   k.Cin = p->Cin; k.Cout = p->Cout; k.KW = p->KW; k.stride = p->stride; k.pad_t = p->pad_t; k.pad_l = p->pad_l;
   k.ldx = p->ldx; k.lddz = p->lddz; k.B = p->B;
   k.cpt = p->Cin / ce; k.Kc = p->KH * p->KW * k.cpt; k.K = p->KH * p->KW * p->Cin;
@@ -1158,6 +1194,7 @@ int plan(const effdet_wgrad_t* p, WgradK& k, int& splits, int tile = 128) {
   }
   k.mchunk = (int)mchunk;
   splits = 0;
+  int step0 = 0;
   for (int s = 0; s < p->nseg; ++s) {
     const effdet_seg_t& gsg = p->seg[s];
     WSeg& d = k.seg[s];
@@ -1167,6 +1204,7 @@ int plan(const effdet_wgrad_t* p, WgradK& k, int& splits, int tile = 128) {
     if (gsg.in_off % ce || gsg.in_bstride % ce) return EFFDET_EUNSUPPORTED;
     if (gsg.out_off % ce || gsg.out_bstride % ce) k.vec_a = 0;
     d.split_start = splits;
+    d.step0 = step0; step0 += (d.M + 31) / 32;
     d.in_off = gsg.in_off; d.in_bs = gsg.in_bstride; d.out_off = gsg.out_off; d.out_bs = gsg.out_bstride;
     splits += (int)((d.M + mchunk - 1) / mchunk);
   }
@@ -1412,8 +1450,9 @@ extern "C" int effdet_conv2d_wgrad_seg_slabs(const effdet_wgrad_t* p, int* first
   return w.splits;
 }
 
-extern "C" int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes,
-                                   effdet_stream_t stream) {
+// live32 (effdet_conv2d_wgrad_live, include/effdet_live_tiles.h; NULL: the dense launch): per-call flags of the split-layout kernel
+static int wgrad_launch(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes, const unsigned char* live32,
+                        effdet_stream_t stream) {
   if (!p || !p->x || !p->dz || !workspace) return EFFDET_EINVAL;
   WgradPlan w;
   const int rc = plan_wgrad(p, w);
@@ -1424,7 +1463,18 @@ extern "C" int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, lon
   k.slab = (float*)workspace;
   k.dbp = p->dbias ? k.slab + (long long)w.splits * w.slab_floats : nullptr;
   const unsigned tiles = (unsigned)(k.ntiles * k.jtiles);
-  if (w.path == WG_SPLIT && w.allr) {
+  if (live32) {
+    if (w.path != WG_SPLIT) return EFFDET_EUNSUPPORTED;
+    if (k.mchunk % 32) return EFFDET_EINVAL;              // a split must start on a step of the flag array
+    k.live32 = live32;
+    if (w.allr) {
+      EFFDET_SET_MAX_LDS((conv_wgrad_split_kernel<1, 1>), w.lds);
+      hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1>), dim3(tiles * w.splits), dim3(512), w.lds, st, k);
+    } else {
+      EFFDET_SET_MAX_LDS((conv_wgrad_split_kernel<0, 1>), w.lds);
+      hipLaunchKernelGGL((conv_wgrad_split_kernel<0, 1>), dim3(tiles * w.splits), dim3(512), w.lds, st, k);
+    }
+  } else if (w.path == WG_SPLIT && w.allr) {
     EFFDET_SET_MAX_LDS(conv_wgrad_split_kernel<1>, w.lds);
     hipLaunchKernelGGL(conv_wgrad_split_kernel<1>, dim3(tiles * w.splits), dim3(512), w.lds, st, k);
   } else if (w.path == WG_SPLIT) {
@@ -1457,4 +1507,15 @@ extern "C" int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, lon
   }
   EFFDET_CHECK_LAUNCH();
   return reduce_slabs(p, w, k.slab, k.dbp, st);
+}
+
+extern "C" int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes,
+                                   effdet_stream_t stream) {
+  return wgrad_launch(p, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int effdet_conv2d_wgrad_live(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes,
+                                        const unsigned char* live32, effdet_stream_t stream) {
+  if (!live32) return EFFDET_EINVAL;
+  return wgrad_launch(p, workspace, workspace_bytes, live32, stream);
 }

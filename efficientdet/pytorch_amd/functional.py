@@ -475,6 +475,11 @@ class _Fork:
 
 HEAD_PAIR_TOWERS = os.environ.get('EFFDET_HEAD_PAIR_TOWERS', '1') == '1'     # A/B switch: layer t of both towers as one launch (f16x3 forward, split-layout data gradients)
 HEAD_SPLIT = os.environ.get('EFFDET_HEAD_SPLIT', '1') == '1'     # A/B switch: split-layout head activations in the bf16x3 arithmetic
+# A/B switch: the regression tower's backward pass skips the tiles / steps its gradient cannot reach (head_bwd).  The smooth-L1 gradient
+# is an exact zero everywhere but at the positive anchors and every layer behind it is a 3x3 conv without bias, so after k data-gradient
+# layers the gradient is confined to Chebyshev distance k of those pixels: ops.live_tiles flags the units, the split-layout kernels skip
+# the rest.  Bit for bit the dense pass (DESIGN.md section 3 names the one exception: non-finite weights / activations under a zero gradient).
+HEAD_SPARSE_REG = os.environ.get('EFFDET_HEAD_SPARSE_REG', '1') == '1'
 _split_ok = {}
 
 
@@ -611,6 +616,15 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
     g = {}
     apix = sum(h * w for (h, w) in sizes)
     last = {}
+    # liveness flags of the regression tower (row r: units within distance r of a non-zero d(reg) pixel), from the pixel-major rows
+    # the loss kernel wrote; retina_reg's gradients read d(reg) itself (r = 0 / 1), layer t of the tower is 4 - t / 5 - t layers on
+    live = None
+    if HEAD_SPARSE_REG and split and dreg_ld and (in_split or dreg.dtype == torch.float32):
+        live = ops.live_tiles(dreg, B, sizes, dreg_ld, in_split)
+    ntile = sum((B * h * w + 127) // 128 for (h, w) in sizes)
+
+    def lv(tower, kind, r):
+        return live[kind][r] if (live is not None and tower == 'reg') else None
 
     def tower_final(tower, dout, per, pix_ld):
         """retina_cls / retina_reg: weight gradient + data gradient back into the tower (ReLU mask of its last layer fused) -> dz maps"""
@@ -633,7 +647,7 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
                 dzmaps = _split_rows(dzmaps, Cfp, dtype)
             elif Cfp != Cf:          # 9*num_classes (or 36) channels are not whole 16-byte chunks: zero-pad the rows
                 dzmaps = [ops.pad_rows(m, Cfp) for m in dzmaps]
-        G, dbp = ops.conv2d_wgrad(acts[tower][3], dzmaps, Cin=256, Cout=Cf, KH=3, KW=3, pad_t=1, pad_l=1, split=split)
+        G, dbp = ops.conv2d_wgrad(acts[tower][3], dzmaps, Cin=256, Cout=Cf, KH=3, KW=3, pad_t=1, pad_l=1, split=split, live32=lv(tower, 0, 0))
         # (cls_gscale: the class-loss gradient was written for an upstream gradient of one -- the upstream scalar multiplies the
         #  slabs and bias partial rows inside the unpack, and the rows of the data gradient)
         gs = cls_gscale if tower == 'cls' else None
@@ -643,13 +657,13 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
         # data gradient with the ReLU mask of the producing tower layer fused into the epilogue
         _, dz = pyramid_alloc(B, sizes, 256, dtype, dev)
         ops.conv2d(dzmaps, ops.pack_weight(wf, dtype, mode=1, cin_pad=Cfp, x3=split), dz, Cin=Cfp, Cout=256, KH=3, KW=3, pad_t=1,
-                   pad_l=1, res=acts[tower][3], res_mode=RES_RELU_MASK, rowscale=rows, split=split)
+                   pad_l=1, res=acts[tower][3], res_mode=RES_RELU_MASK, rowscale=rows, split=split, live=lv(tower, 1, 1))
         return dz
 
     def layer_wgrad(tower, t, dz):
         w = HP[f'{tower}_convs.{t}.weight']
         xin = acts[tower][t - 1] if t > 0 else p
-        G, dbp = ops.conv2d_wgrad(xin, dz, Cin=w.shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1, split=split)
+        G, dbp = ops.conv2d_wgrad(xin, dz, Cin=w.shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1, split=split, live32=lv(tower, 0, 4 - t))
         dw = torch.empty_like(w); db = ops.unpack_wgrad(G, dw, dbias_part=dbp)
         g[f'{tower}_convs.{t}.weight'], g[f'{tower}_convs.{t}.bias'] = dw, db
 
@@ -661,7 +675,7 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
             if t > 0:
                 _, nz = pyramid_alloc(B, sizes, 256, dtype, dev)
                 ops.conv2d(dz, wd, nz, Cin=256, Cout=256, KH=3, KW=3, pad_t=1, pad_l=1, res=acts[tower][t - 1],
-                           res_mode=RES_RELU_MASK, split=split)
+                           res_mode=RES_RELU_MASK, split=split, live=lv(tower, 1, 5 - t))
                 dz = nz
             else:
                 last[tower] = (dz, wd)                  # 256 -> Wc back to the neck: after the join (the towers' sum)
@@ -679,7 +693,7 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
                 _, na, nb = pyramid_alloc_pair(B, sizes, 256, dtype, dev)
                 ops.conv2d(dzs['cls'] + dzs['reg'], wd2[0], na + nb, Cin=256, Cout=256, KH=3, KW=3, pad_t=1, pad_l=1,
                            res=acts['cls'][t - 1] + acts['reg'][t - 1], res_mode=RES_RELU_MASK, split=split,
-                           seg_w=[wd2[0]] * L5 + [wd2[1]] * L5)
+                           seg_w=[wd2[0]] * L5 + [wd2[1]] * L5, live=lv('reg', 1, 5 - t), live_tile0=ntile if live is not None else 0)
                 dzs = {'cls': na, 'reg': nb}
             else:
                 last['cls'], last['reg'] = (dzs['cls'], wd2[0]), (dzs['reg'], wd2[1])
@@ -700,5 +714,6 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
     dz, wd = last['cls']
     ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, KH=3, KW=3, pad_t=1, pad_l=1, split=split, out_f32=split)
     dz, wd = last['reg']
-    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, KH=3, KW=3, pad_t=1, pad_l=1, res=dp_maps, res_mode=RES_ADD, split=split, out_f32=split)
+    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, KH=3, KW=3, pad_t=1, pad_l=1, res=dp_maps, res_mode=RES_ADD, split=split, out_f32=split,
+               live=lv('reg', 1, 5))
     return dp_maps, g

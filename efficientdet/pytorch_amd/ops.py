@@ -437,7 +437,7 @@ def scale_pack_weight(w_oihw, gate, dtype):
 
 def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
            res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
-           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None):
+           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0):
     """Grouped implicit-GEMM conv: xs/ys (and optional zs/res) are lists of Map, one per pyramid level.
     split=True (EFFDET_F32_SPLIT): xs hold the split layout ([32 x bf16 hi | 32 x bf16 lo] per 32 channels, 4 B per element), wp
     is packed for bf16x3; ys are written split too unless out_f32 (then plain fp32; res, if any, is plain and ADDed).
@@ -445,7 +445,10 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     hsplit=True (EFFDET_F32_HSPLIT, the f16x3 forward arithmetic): xs hold the H-split layout ([32 x f16 hi | 32 x f16 lo * 2^11] per 32
     channels), wp = pack_weight(..., h3=True); ys are written H-split too unless out_f32; no scale / res / rowscale.
     seg_w / seg_shift (lists, one entry per map, None = wp / shift): the maps are INDEPENDENT convs of one geometry with their own packed
-    weights / bias rows -- the same layer of the head's two towers in one launch (<= 10 maps).  Same values as separate launches."""
+    weights / bias rows -- the same layer of the head's two towers in one launch (<= 10 maps).  Same values as separate launches.
+    live (uint8 tensor, one byte per 128-pixel tile from tile live_tile0 on: live_tiles()[1][r]): a 0 marks a tile whose every input
+    tap is zero; the split-layout kernels without bias / affine / activation skip it (zeros out, or nothing under an in-place RES_ADD),
+    every other launch ignores the flags.  Same values as without, but 0 where the dense launch would give 0 * Inf = NaN."""
     if isinstance(xs, Map):
         xs, ys = [xs], [ys]
         zs = [zs] if zs is not None else None
@@ -493,8 +496,16 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     # algorithmic bytes: the input map, the packed weights, every output stream (y, the pre-activation copy, the split copy), the residual
     nbytes = isx * Cin * sum(x.B * x.H * x.W for x in xs) + wp.numel() * wp.element_size() + \
         (4 if out_f32 else isy) * Cout * sum(y.B * y.H * y.W for y in ys) * (1 + (zs is not None) + (ysplit is not None) + (res is not None))
-    _timed(_igemm_symbol(x0.dtype, d) if PROFILE is not None else '', flops,
-           lambda: L.check(L.lib().effdet_conv2d(C.byref(d), L.stream_ptr()), 'effdet_conv2d'),
+    if live is not None:
+        assert live.dtype == torch.uint8 and live.is_contiguous()
+        ntile = sum((y.B * y.H * y.W + 127) // 128 for y in ys)
+        assert 0 <= live_tile0 <= ntile and live.numel() == ntile - live_tile0, (live.numel(), ntile, live_tile0)
+        run = lambda: L.check(L.require('effdet_conv2d_live').effdet_conv2d_live(C.byref(d), live.data_ptr(), int(live_tile0), L.stream_ptr()),
+                              'effdet_conv2d_live')
+    else:
+        run = lambda: L.check(L.lib().effdet_conv2d(C.byref(d), L.stream_ptr()), 'effdet_conv2d')
+    # (flops stay those of the dense launch: a flagged launch reports an EFFECTIVE rate)
+    _timed(_igemm_symbol(x0.dtype, d) if PROFILE is not None else '', flops, run,
            'k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, sum(y.B * y.H * y.W for y in ys)), nbytes=float(nbytes))
 
 
@@ -523,12 +534,14 @@ def conv2d_wgrad_kernel_id(x, dz, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l
 
 
 def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, split=False,
-                 image_splits=False, group=False):
+                 image_splits=False, group=False, live32=None):
     """Weight gradient -> (slabs [splits][Cout][taps][Cin] fp32, bias partial rows [splits][Cout] fp32 or None): the UNREDUCED
     split-K partials for unpack_wgrad / unpack_wgrad_bn to sum, in slab order, while unpacking (no float atomics anywhere: two
     runs are bitwise equal).  With dw given (packed [Cout][taps][Cin] fp32) the library reduces itself: dw += ..., dbias += ...
     group=True (dw None, <= 5 maps): the maps are INDEPENDENT problems of the same conv geometry (different tensors, different
-    weights) sharing one launch -> a list of (slabs_i, parts_i), one per map (effdet_conv2d_wgrad_seg_slabs)."""
+    weights) sharing one launch -> a list of (slabs_i, parts_i), one per map (effdet_conv2d_wgrad_seg_slabs).
+    live32 (split only; uint8 tensor, one byte per 32-pixel step of dzs: live_tiles()[0][r]): a 0 marks a step whose dz pixels are all
+    zero; every split-K block walks only its live steps.  Same slabs and bias rows as without."""
     if isinstance(xs, Map):
         xs, dzs = [xs], [dzs]
     x0 = xs[0]
@@ -540,13 +553,19 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     n = Cout * KH * KW * Cin
     ws = torch.empty(splits * (n + Cout), dtype=torch.float32, device=x0.t.device)
     nbytes = ws.numel() * 4
+    if live32 is not None:
+        assert split and live32.dtype == torch.uint8 and live32.is_contiguous()
+        assert live32.numel() == sum((z.B * z.H * z.W + 31) // 32 for z in dzs)
+        run = lambda: L.check(L.require('effdet_conv2d_wgrad_live').effdet_conv2d_wgrad_live(C.byref(d), L.ptr(ws), nbytes, live32.data_ptr(),
+                                                                                             L.stream_ptr()), 'effdet_conv2d_wgrad_live')
+    else:
+        run = lambda: L.check(L.lib().effdet_conv2d_wgrad(C.byref(d), L.ptr(ws), nbytes, L.stream_ptr()), 'effdet_conv2d_wgrad')
     # (bf16: DMA + LDS-transpose-read kernel, fp32: DMA + direct-operand kernel; levels neither can take use the register-transpose kernel)
     _timed('conv_wgrad_tr_kernel<8>' if x0.dtype == torch.bfloat16 else
            ('conv_wgrad_split_kernel' if split else
             ('conv_wgrad_thin_kernel' if int(L.lib().effdet_conv2d_wgrad_kernel(C.byref(d))) == 1 else
              ('conv_wgrad_f32dma_kernel<4,bf16x3>' if d.dtype == L.F32_BF16X3 else 'conv_wgrad_f32dma_kernel<8>'))), flops,
-           lambda: L.check(L.lib().effdet_conv2d_wgrad(C.byref(d), L.ptr(ws), nbytes, L.stream_ptr()),
-                           'effdet_conv2d_wgrad'),
+           run,
            'k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, sum(z.B * z.H * z.W for z in dzs)),
            nbytes=float(x0.t.element_size() * Cin * sum(x.B * x.H * x.W for x in xs) +
                         dzs[0].t.element_size() * Cout * sum(z.B * z.H * z.W for z in dzs) + 4.0 * splits * (n + Cout)))
@@ -702,6 +721,27 @@ def wgrad_split_supported(B, sizes, Cin, Cout, lddz, KH=3, KW=3, pad=1):
         s.in_off, s.in_bstride, s.out_off, s.out_bstride = ox, h * w * Cin, oz, h * w * lddz
         ox += B * h * w * Cin; oz += B * h * w * lddz
     return int(L.lib().effdet_conv2d_wgrad_splits(C.byref(d))) >= 1
+
+
+def live_tiles(dreg, B, sizes, reg_ld, split):
+    """Liveness flags of the regression tower's backward pass (include/effdet_live_tiles.h) from d(reg) as focal_loss_bwd_reg leaves
+    it with reg_ld: [B][sum H*W][reg_ld] rows, fp32 or (split) the split layout.  -> (live32 [6][steps], live128 [6][tiles]) uint8:
+    row r flags the 32-pixel steps / 128-pixel tiles (per level over its (b, h, w) pixel index, levels concatenated) that hold a pixel
+    within Chebyshev distance r of a non-zero d(reg) pixel of the same image and level.  Three kernel launches, nothing else."""
+    lib_ = L.require(*L.LIVE_SIGNATURES)
+    n = len(sizes)
+    Hs, Ws = (C.c_int * n)(*[h for h, _ in sizes]), (C.c_int * n)(*[w for _, w in sizes])
+    steps, tiles = C.c_longlong(), C.c_longlong()
+    pixels = int(lib_.effdet_live_tiles_counts(B, n, Hs, Ws, C.byref(steps), C.byref(tiles)))
+    if pixels < 0:
+        L.check(pixels, 'effdet_live_tiles_counts')
+    assert dreg.is_contiguous() and dreg.element_size() == 4 and dreg.numel() == pixels * reg_ld
+    S, T, R = steps.value, tiles.value, L.LIVE_RADII
+    buf = torch.empty(R * S + R * T + 2 * pixels, dtype=torch.uint8, device=dreg.device)
+    l32, l128, scratch = buf[:R * S].view(R, S), buf[R * S:R * (S + T)].view(R, T), buf[R * (S + T):]
+    L.check(lib_.effdet_live_tiles(dreg.data_ptr(), L.F32_SPLIT if split else L.F32, reg_ld, B, n, Hs, Ws, scratch.data_ptr(),
+                                   l32.data_ptr(), l128.data_ptr(), L.stream_ptr()), 'effdet_live_tiles')
+    return l32, l128
 
 
 def to_split(t):
