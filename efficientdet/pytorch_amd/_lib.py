@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h).
+include/effdet_live_tiles.h, include/effdet_box_loss.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -236,6 +236,13 @@ LIVE_SIGNATURES = {
     'effdet_conv2d_live': 'i:ppis',
     'effdet_conv2d_wgrad_live': 'i:ppqps',
 }
+# The IoU-family box regression losses, declared in include/effdet_box_loss.h (same generation, same letters, same rule;
+# tests/test_box_loss_host.py compares this table with that header's prototypes).
+BOX_LOSS_SIGNATURES = {
+    'effdet_box_loss_fwd': 'i:ppppppqiqiiifs',
+    'effdet_box_loss_fwd_grad': 'i:ppppppqpiiiqiiifs',
+    'effdet_box_loss_bwd_reg': 'i:ppppppiiiqiifs',
+}
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
 DW_PLAN_FWD, DW_PLAN_DGRAD, DW_PLAN_WGRAD, DW_PLAN_BWD, DW_PLAN_EXPAND_FWD = 0, 1, 2, 3, 4      # EFFDET_DW_PLAN_*
 DW_INFO = ('cq', 'tpi', 'ppt', 'nbuf', 'groups', 'nslab', 'direct')                              # EFFDET_DW_INFO_* in order
@@ -257,7 +264,7 @@ def lib():
                                % (LIB_PATH, got, ABI_VERSION))
         _lib = cand
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
-                list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()):
+                list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

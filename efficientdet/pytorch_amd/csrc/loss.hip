@@ -16,6 +16,7 @@
 //            data-gradient convs consume.
 // HBM-bound: reads cls once per pass (15.7 MB / image fp32 at 80 classes).
 #include "common.h"
+#include "../../../include/effdet_box_loss.h"
 
 namespace {
 
@@ -479,6 +480,190 @@ extern "C" int effdet_focal_loss_bwd_reg(const float* reg, const float* anchors,
   if (dtype == EFFDET_F32) hipLaunchKernelGGL(loss_bwd_reg_kernel<float>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
   else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(loss_bwd_reg_kernel<split_t>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
   else hipLaunchKernelGGL(loss_bwd_reg_kernel<bf16_t>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// IoU-family box regression losses (include/effdet_box_loss.h fixes the semantics): IoU / GIoU / DIoU / CIoU between the DECODED
+// prediction and the assigned annotation, over the positives of loss_assign_kernel, in place of its smooth-L1 term.  The forward
+// entry points run their smooth-L1 twins unchanged (assignment, focal term, losses[0]) and then two more kernels: one thread per
+// anchor re-reads assign[] and puts the per-workgroup sum of the positives' losses into the same part_reg[b][block] slots, and a
+// final kernel adds them per image in a fixed pattern and overwrites losses[1].  Kernel launches only, no float atomics.
+namespace {
+
+constexpr float BOX_EPS = 1e-7f;
+constexpr float BOX_4_PI2 = 0.40528473456935109f;    // 4 / pi^2
+
+// d min(a, b) / d a (= d max(b, a) / d b) the way autograd splits it: 1 where a is selected, 0.5 on a tie
+__device__ __forceinline__ float sel_lt(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
+
+// loss of one positive anchor; with GRAD its gradient wrt the regression row r (not yet scaled) in gr[4]
+template <bool GRAD>
+__device__ __forceinline__ float box_loss_elem(int kind, float4 an, const float* __restrict__ g, float4 r, float* gr) {
+  const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
+  const float pcx = acx + 0.1f * r.x * aw, pcy = acy + 0.1f * r.y * ah;
+  const float dwr = 0.2f * r.z, dhr = 0.2f * r.w;
+  const float pw = expf(fminf(dwr, EFFDET_BOX_LOSS_DW_MAX)) * aw, ph = expf(fminf(dhr, EFFDET_BOX_LOSS_DW_MAX)) * ah;
+  const float px1 = pcx - 0.5f * pw, px2 = pcx + 0.5f * pw, py1 = pcy - 0.5f * ph, py2 = pcy + 0.5f * ph;
+  const float gx1 = g[0], gy1 = g[1], gx2 = g[2], gy2 = g[3], gw = gx2 - gx1, gh = gy2 - gy1;
+  const float iwr = fminf(px2, gx2) - fmaxf(px1, gx1), ihr = fminf(py2, gy2) - fmaxf(py1, gy1);
+  const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
+  const float I = iw * ih, U = pw * ph + gw * gh - I, D = U + BOX_EPS, iou = I / D;
+  const float cw = fmaxf(px2, gx2) - fminf(px1, gx1), ch = fmaxf(py2, gy2) - fminf(py1, gy1);
+  float L = 1.f - iou;
+  // gradients of L wrt the intermediate quantities, accumulated term by term
+  float gI = -(D + I) / (D * D), gAp = I / (D * D);              // I and the predicted area pw * ph (U = pw ph + gw gh - I)
+  float gcw = 0.f, gch = 0.f, gpcx = 0.f, gpcy = 0.f, gpw = 0.f, gph = 0.f;
+  if (kind == EFFDET_BOX_LOSS_GIOU) {
+    const float C = cw * ch, CE = C + BOX_EPS;
+    L += (C - U) / CE;
+    if (GRAD) { const float gC = D / (CE * CE); gcw = gC * ch; gch = gC * cw; gI += 1.f / CE; gAp -= 1.f / CE; }
+  }
+  if (kind >= EFFDET_BOX_LOSS_DIOU) {
+    const float dx = pcx - (gx1 + gx2) * 0.5f, dy = pcy - (gy1 + gy2) * 0.5f;
+    const float rho2 = dx * dx + dy * dy, K = cw * cw + ch * ch + BOX_EPS;
+    L += rho2 / K;
+    if (GRAD) { const float t = -2.f * rho2 / (K * K); gcw = t * cw; gch = t * ch; gpcx = 2.f * dx / K; gpcy = 2.f * dy / K; }
+  }
+  if (kind == EFFDET_BOX_LOSS_CIOU) {
+    const float q = pw / ph, da = atanf(gw / gh) - atanf(q);
+    const float v = BOX_4_PI2 * da * da, alpha = v / (1.f - iou + v + BOX_EPS);       // alpha: a constant of the gradient
+    L += alpha * v;
+    if (GRAD) { const float dvdq = -2.f * BOX_4_PI2 * da / (1.f + q * q); gpw = alpha * dvdq / ph; gph = -alpha * dvdq * q / ph; }
+  }
+  if (GRAD) {
+    const float giw = iwr >= 0.f ? gI * ih : 0.f, gih = ihr >= 0.f ? gI * iw : 0.f;   // the clamp at 0 passes at exactly 0
+    const float gpx2 = giw * sel_lt(px2, gx2) + gcw * sel_lt(gx2, px2), gpx1 = -giw * sel_lt(gx1, px1) - gcw * sel_lt(px1, gx1);
+    const float gpy2 = gih * sel_lt(py2, gy2) + gch * sel_lt(gy2, py2), gpy1 = -gih * sel_lt(gy1, py1) - gch * sel_lt(py1, gy1);
+    gpcx += gpx1 + gpx2; gpcy += gpy1 + gpy2;
+    gpw += 0.5f * (gpx2 - gpx1) + gAp * ph; gph += 0.5f * (gpy2 - gpy1) + gAp * pw;
+    gr[0] = gpcx * (0.1f * aw); gr[1] = gpcy * (0.1f * ah);
+    gr[2] = dwr <= EFFDET_BOX_LOSS_DW_MAX ? gpw * pw * 0.2f : 0.f;                    // the cap passes at equality
+    gr[3] = dhr <= EFFDET_BOX_LOSS_DW_MAX ? gph * ph * 0.2f : 0.f;
+  }
+  return L;
+}
+
+// the grid of loss_assign_kernel: one thread per (image, anchor), one partial per workgroup into part_reg[b][block]
+__global__ __launch_bounds__(256) void box_loss_fwd_kernel(const LossK p, const int kind) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  __shared__ float red[4];
+  float l = 0.f;
+  if (a < p.A) {
+    const int code = p.assign[(long long)b * p.A + a];
+    if (code >= 0)
+      l = box_loss_elem<false>(kind, ((const float4*)p.anchors)[a], p.annots + ((long long)b * p.N + code) * 5,
+                               ((const float4*)p.reg)[(long long)b * p.A + a], nullptr);
+  }
+  l = wave_sum(l);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l;
+  __syncthreads();
+  if (threadIdx.x == 0) p.part_reg[(long long)b * p.na + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// one workgroup: wave w adds part_reg of images w, w + 16, ... (lane-strided, then the fixed shuffle tree) into stat[b][1]; thread 0
+// then losses[1] = weight * mean_b sum_b / num_pos_b (models/losses.py:148-152 with the per-anchor loss in place of the 4 deltas)
+__global__ __launch_bounds__(1024) void box_loss_final_kernel(const LossK p, const float weight) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int b = wave; b < p.B; b += 16) {
+    const float* q = p.part_reg + (long long)b * p.na;
+    float s = 0.f;
+    for (int i = lane; i < p.na; i += 64) s += q[i];
+    s = wave_sum(s);
+    if (lane == 0) p.stat[b * SS + 1] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float rl = 0.f;
+  for (int b = 0; b < p.B; ++b) {
+    const float* s = p.stat + b * SS;
+    if (s[3] > 0.f && npos(s) > 0.f) rl += s[1] / npos(s);
+  }
+  p.losses[1] = weight * (rl / (float)p.B);
+}
+
+// loss_bwd_reg_kernel's grid, output layouts and pad zeroing with the analytic gradient of box_loss_elem
+template <typename T>
+__global__ void box_loss_bwd_reg_kernel(const LossK p, const int kind, const float weight) {
+  const long long total = (long long)p.B * p.A;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / p.A, a = i - b * p.A;
+    const int code = p.assign[i];
+    const float* st = p.stat + b * SS;
+    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (code >= 0 && st[3] > 0.f && npos(st) > 0.f) {
+      const float gs = p.gscale[1] * weight / ((float)p.B * npos(st));
+      float gr[4];
+      (void)box_loss_elem<true>(kind, ((const float4*)p.anchors)[a], p.annots + (b * p.N + code) * 5, ((const float4*)p.reg)[i], gr);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) g[q] = gs * gr[q];
+    }
+    if (p.reg_ld) {
+      const long long pix = a / 9; const int an = (int)(a - pix * 9);
+      T* row = (T*)p.dreg + (b * (p.A / 9) + pix) * p.reg_ld;
+      store4(row + an * 4, g);
+      if (an == 8) for (int c = 36; c < p.reg_ld; c += 4) store4(row + c, f32x4{0.f, 0.f, 0.f, 0.f});
+    } else {
+      store4((T*)p.dreg + i * 4, g);
+    }
+  }
+}
+
+inline bool box_loss_args_ok(int kind, float weight) {
+  return kind >= EFFDET_BOX_LOSS_IOU && kind <= EFFDET_BOX_LOSS_CIOU && weight >= 0.f && weight <= 3.402823466e38f;   // (false for a NaN)
+}
+
+// after the smooth-L1 twin has been enqueued: the per-workgroup IoU-loss partials over its assignment, then losses[1]
+int box_loss_finish(const float* reg, const float* anchors, const float* annots, float* losses, void* workspace, int B, long long A,
+                    int N, int kind, float weight, hipStream_t st) {
+  LossK k{}; k.reg = reg; k.anchors = anchors; k.annots = annots; k.losses = losses; k.B = B; k.N = N; k.A = A;
+  carve_loss(k, workspace, B, A);
+  hipLaunchKernelGGL(box_loss_fwd_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, kind);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(box_loss_final_kernel, dim3(1), dim3(1024), 0, st, k, weight);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+}  // namespace
+
+extern "C" int effdet_box_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                   void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N, int kind,
+                                   float weight, effdet_stream_t stream) {
+  if (!box_loss_args_ok(kind, weight)) return EFFDET_EINVAL;
+  const int rc = effdet_focal_loss_fwd(cls, reg, anchors, annots, losses, workspace, workspace_bytes, B, A, num_classes, N, stream);
+  if (rc != EFFDET_OK) return rc;
+  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, kind, weight, (hipStream_t)stream);
+}
+
+extern "C" int effdet_box_loss_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                        void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
+                                        long long A, int num_classes, int N, int kind, float weight, effdet_stream_t stream) {
+  if (!box_loss_args_ok(kind, weight)) return EFFDET_EINVAL;
+  const int rc = effdet_focal_loss_fwd_grad(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, B, A,
+                                            num_classes, N, stream);
+  if (rc != EFFDET_OK) return rc;
+  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, kind, weight, (hipStream_t)stream);
+}
+
+extern "C" int effdet_box_loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
+                                       const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N, int kind,
+                                       float weight, effdet_stream_t stream) {
+  if (!reg || !anchors || !annots || !gscale || !workspace || !dreg) return EFFDET_EINVAL;
+  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
+  if (reg_ld && (reg_ld < 36 || reg_ld % 4 || A % 9)) return EFFDET_EINVAL;
+  if (dtype == EFFDET_F32_SPLIT && (!reg_ld || reg_ld % 32 || ((unsigned long long)dreg & 127ull))) return EFFDET_EINVAL;
+  if (!box_loss_args_ok(kind, weight)) return EFFDET_EINVAL;
+  LossK k{}; k.reg = reg; k.anchors = anchors; k.annots = annots; k.gscale = gscale; k.dreg = dreg;
+  k.B = B; k.N = N; k.A = A; k.reg_ld = reg_ld;
+  carve_loss(k, const_cast<void*>(workspace), B, A);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(grid_for((long long)B * A));
+  if (dtype == EFFDET_F32) hipLaunchKernelGGL(box_loss_bwd_reg_kernel<float>, grid, dim3(256), 0, st, k, kind, weight);
+  else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(box_loss_bwd_reg_kernel<split_t>, grid, dim3(256), 0, st, k, kind, weight);
+  else hipLaunchKernelGGL(box_loss_bwd_reg_kernel<bf16_t>, grid, dim3(256), 0, st, k, kind, weight);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }

@@ -115,11 +115,17 @@ class Anchors(nn.Module):
 
 
 class FocalLoss(nn.Module):
-    """models/losses.py:29-152 as two HIP passes; forward only (training uses the fused head+loss node)."""
+    """models/losses.py:29-152 as two HIP passes; forward only (training uses the fused head+loss node).  box_loss: an
+    ops.BoxLossOptions puts an IoU-family loss in the place of smooth-L1 (None: the reference's term)."""
+
+    def __init__(self, box_loss=None):
+        super().__init__()
+        ops._box_loss_args(box_loss)                            # (TypeError on anything but BoxLossOptions / None)
+        self.box_loss = box_loss
 
     def forward(self, classifications, regressions, anchors, annotations):
-        losses, _ = ops.focal_loss_fwd(classifications.contiguous(), regressions.contiguous(), anchors.contiguous(),
-                                       annotations.contiguous().float())
+        losses, _ = ops.box_loss_fwd(classifications.contiguous(), regressions.contiguous(), anchors.contiguous(),
+                                     annotations.contiguous().float(), self.box_loss)
         return losses[0:1], losses[1:2]
 
 
@@ -307,11 +313,13 @@ LOSS_FWD_GRAD = os.environ.get('EFFDET_LOSS_FWD_GRAD', '1') == '1'    # A/B swit
 
 class _HeadLossFn(torch.autograd.Function):
     """RetinaHead + focal / smooth-L1 loss as ONE node: the loss kernel hands the head's data-gradient convs
-    d(logit) and d(reg) directly in the activation dtype (no fp32 gradient tensor round trip)."""
+    d(logit) and d(reg) directly in the activation dtype (no fp32 gradient tensor round trip).  box: None = smooth-L1 (the
+    ops.focal_loss_* calls), an ops.BoxLossOptions of an IoU kind = the ops.box_loss_* calls, which keep the output contract of
+    d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them)."""
 
     @staticmethod
-    def forward(ctx, dtype, num_classes, anchors, annots, train, *args):
-        ctx.prep, ctx.arith = ops.get_prep(), ops.F32_ARITH_BWD
+    def forward(ctx, dtype, num_classes, anchors, annots, train, box, *args):
+        ctx.prep, ctx.arith, ctx.box = ops.get_prep(), ops.F32_ARITH_BWD, box
         p = [Map.of(t) for t in args[:5]]
         HP = dict(zip(_HEAD_KEYS, args[5:]))
         cls, reg, saved = Fn.head_fwd(p, HP, num_classes, dtype, train)
@@ -320,10 +328,13 @@ class _HeadLossFn(torch.autograd.Function):
             # ONE pass over the 15.7 MB/image of probabilities: losses + d(logits) for an upstream gradient of one, already in
             # the pixel-major, 64-channel-padded rows the head's gradient convs read; cls itself is not kept for backward
             dld = (9 * nc + 63) // 64 * 64
-            losses, ws, dpix = ops.focal_loss_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5])    # (split-layout head: see functional.head_uses_split)
+            if box is None:
+                losses, ws, dpix = ops.focal_loss_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5])    # (split-layout head: see functional.head_uses_split)
+            else:
+                losses, ws, dpix = ops.box_loss_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], options=box)
             ctx.saved = (saved, None, reg, anchors, annots, ws, dtype, dpix, dld)
         else:
-            losses, ws = ops.focal_loss_fwd(cls, reg, anchors, annots)
+            losses, ws = ops.focal_loss_fwd(cls, reg, anchors, annots) if box is None else ops.box_loss_fwd(cls, reg, anchors, annots, box)
             ctx.saved = (saved, cls, reg, anchors, annots, ws, dtype, None, 0) if train else None
         return losses[0:1].clone(), losses[1:2].clone()
 
@@ -339,7 +350,10 @@ class _HeadLossFn(torch.autograd.Function):
         if dpix is not None:
             split = saved[5]
             rld = 64 if split else 0                # split layout: d(reg) pixel-major, 36 -> 64 channels (two [hi|lo] groups)
-            dreg = ops.focal_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split)
+            if ctx.box is None:
+                dreg = ops.focal_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split)
+            else:
+                dreg = ops.box_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, options=ctx.box)
             with ops.unpack_batch():                               # the head's 10 weight-gradient unpacks: one launch
                 dp, g = Fn.head_bwd(saved, dpix, dreg, dtype, dcls_ld=dld, cls_gscale=gscale[0:1], dreg_ld=rld, in_split=split)
         else:
@@ -350,10 +364,12 @@ class _HeadLossFn(torch.autograd.Function):
             else:
                 dld = 0
                 dcls, dreg = ops.focal_loss_bwd(cls, reg, anchors, annots, gscale, ws, dtype)
+            if ctx.box is not None:      # (the class gradient above is the focal term's either way; its smooth-L1 d(reg) is replaced)
+                dreg = ops.box_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, options=ctx.box)
             with ops.unpack_batch():
                 dp, g = Fn.head_bwd(saved, dcls, dreg, dtype, dcls_ld=dld)
         ctx.saved = None
-        return (None, None, None, None, None) + tuple(Fn.level_tensor(m) for m in dp) + tuple(g[k] for k in _HEAD_KEYS)
+        return (None, None, None, None, None, None) + tuple(Fn.level_tensor(m) for m in dp) + tuple(g[k] for k in _HEAD_KEYS)
 
 
 # --------------------------------------------------------------------------- the model
@@ -369,6 +385,7 @@ class EfficientDet(nn.Module):
         self.threshold = threshold
         self.iou_threshold = iou_threshold
         self.nms_options = None                                 # set_nms(): None = the reference's class-agnostic greedy NMS
+        self.box_loss = None                                    # set_box_loss(): None = the reference's smooth-L1 on encoded deltas
         self.num_classes = num_classes
         self.compute_dtype = compute_dtype
         # MFMA arithmetic on fp32 storage: 'f32' = exact fp32 products (v_mfma_f32_16x16x4_f32), 'bf16x3' = operands split into
@@ -409,6 +426,18 @@ class EfficientDet(nn.Module):
         if options is not None and not isinstance(options, ops.NMSOptions):
             raise TypeError('set_nms takes an NMSOptions or None, not %r' % (options,))
         self.nms_options = options
+        return self
+
+    def set_box_loss(self, options):
+        """Box regression term of the training loss: None (the default) or ops.BoxLossOptions('smooth_l1') = the reference's smooth-L1
+        on encoded deltas, through the same calls as ever; BoxLossOptions('iou' | 'giou' | 'diou' | 'ciou', weight) = that loss
+        between the decoded prediction and the assigned annotation IN PLACE of smooth-L1 (include/effdet_box_loss.h).  The kind and
+        the weight are launch arguments: a graph.GraphedTrainStep / GraphedTrainLoop captured before a change keeps the old term
+        until it is captured again."""
+        if options is not None and not isinstance(options, ops.BoxLossOptions):
+            raise TypeError('set_box_loss takes a BoxLossOptions or None, not %r' % (options,))
+        self.box_loss = options
+        self.criterion.box_loss = options
         return self
 
     def live_parameters(self):
@@ -556,8 +585,10 @@ class EfficientDet(nn.Module):
             self._check(inputs)
             p = self._neck(self._backbone(inputs.float())[-5:])
             anc = self.anchors(inputs)
+            box = getattr(self, 'box_loss', None)                # (a model pickled before the option existed has no such attribute)
+            box = None if (box is None or box.is_default()) else box
             return _HeadLossFn.apply(self.compute_dtype, self.num_classes, anc, annotations.float().contiguous(),
-                                     torch.is_grad_enabled(), *p, *self._head_params())
+                                     torch.is_grad_enabled(), box, *p, *self._head_params())
         dets = self.detect(inputs)
         s, l, b = dets[0]
         if s.numel() == 0:

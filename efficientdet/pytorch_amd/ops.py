@@ -1310,6 +1310,96 @@ def focal_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=Fals
     return dreg
 
 
+BOX_LOSS_KINDS = {'smooth_l1': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}     # EFFDET_BOX_LOSS_* (0: the effdet_focal_loss_* calls)
+
+
+class BoxLossOptions:
+    """The box regression term of EfficientDet.set_box_loss / FocalLoss(box_loss=) (include/effdet_box_loss.h): kind 'smooth_l1' (the
+    reference's, on the encoded deltas) or 'iou' | 'giou' | 'diou' | 'ciou' between the decoded prediction and the assigned annotation,
+    in place of smooth-L1; weight multiplies the IoU kinds' loss (and gradient).  smooth_l1 is the reference's term as it is: it takes
+    no weight other than 1."""
+
+    def __init__(self, kind='smooth_l1', weight=1.0):
+        if kind not in BOX_LOSS_KINDS:
+            raise ValueError('BoxLossOptions: kind must be one of %s, not %r' % (sorted(BOX_LOSS_KINDS), kind))
+        w = float(weight)
+        if not 0.0 <= w < float('inf'):
+            raise ValueError('BoxLossOptions: weight must be finite and >= 0')
+        if kind == 'smooth_l1' and w != 1.0:
+            raise ValueError("BoxLossOptions: kind 'smooth_l1' is the reference's unweighted term (weight 1.0)")
+        self.kind, self.weight = kind, w
+
+    def key(self):
+        return (self.kind, self.weight)
+
+    def is_default(self):
+        return self.kind == 'smooth_l1'
+
+    def __eq__(self, other):
+        return isinstance(other, BoxLossOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'BoxLossOptions(kind=%r, weight=%r)' % self.key()
+
+
+def _box_loss_args(options):
+    """-> None for the smooth-L1 path (options None or kind 'smooth_l1'), else (kind code, weight)."""
+    if options is None:
+        return None
+    if not isinstance(options, BoxLossOptions):
+        raise TypeError('box loss options must be a BoxLossOptions or None, not %r' % (options,))
+    return None if options.is_default() else (BOX_LOSS_KINDS[options.kind], options.weight)
+
+
+def box_loss_fwd(cls, reg, anc, annots, options=None):
+    """focal_loss_fwd with the box term of options (None / 'smooth_l1': focal_loss_fwd itself) -> (losses [2], ws)."""
+    kw = _box_loss_args(options)
+    if kw is None:
+        return focal_loss_fwd(cls, reg, anc, annots)
+    lib = L.require('effdet_box_loss_fwd')
+    B, A, nc = cls.shape
+    nbytes = int(lib.effdet_loss_workspace_bytes(B, A, nc))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
+    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
+    L.check(lib.effdet_box_loss_fwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes, B, A, nc,
+                                    annots.shape[1], kw[0], kw[1], L.stream_ptr()), 'effdet_box_loss_fwd')
+    return losses, ws
+
+
+def box_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, options=None):
+    """focal_loss_fwd_grad with the box term of options -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
+    kw = _box_loss_args(options)
+    if kw is None:
+        return focal_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=split)
+    lib = L.require('effdet_box_loss_fwd_grad')
+    B, A, nc = cls.shape
+    nbytes = int(lib.effdet_loss_workspace_bytes(B, A, nc))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
+    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
+    dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
+    L.check(lib.effdet_box_loss_fwd_grad(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes,
+                                         L.ptr(dcls), dld, L.F32_SPLIT if split else L.dtype_code(dtype), B, A, nc, annots.shape[1],
+                                         kw[0], kw[1], L.stream_ptr()), 'effdet_box_loss_fwd_grad')
+    return losses, ws, dcls
+
+
+def box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, options=None):
+    """focal_loss_bwd_reg with the box term of options: d(reg) in the same three layouts, from the workspace of any forward call."""
+    kw = _box_loss_args(options)
+    if kw is None:
+        return focal_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=reg_ld, split=split)
+    lib = L.require('effdet_box_loss_bwd_reg')
+    B, A, _ = reg.shape
+    dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
+    L.check(lib.effdet_box_loss_bwd_reg(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld,
+                                        L.F32_SPLIT if split else L.dtype_code(dtype), B, A, annots.shape[1], kw[0], kw[1],
+                                        L.stream_ptr()), 'effdet_box_loss_bwd_reg')
+    return dreg
+
+
 def pad_rows(src_map, cpad):
     """Level map with unaligned channel count -> fresh contiguous [B,H,W,cpad] map, zero padded."""
     m = src_map
