@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h, include/effdet_box_loss.h).
+include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -100,6 +100,11 @@ class TrainCtl(C.Structure):     # effdet_train_ctl_t
 
 class EmaCtl(C.Structure):       # effdet_ema_ctl_t (include/effdet_ema.h)
     _fields_ = [('updates', C.c_int), ('reserved', C.c_int * 3)]
+
+
+class LossOpts(C.Structure):     # effdet_loss_opts_t (include/effdet_loss_opts.h)
+    _fields_ = [(n, C.c_float) for n in ('alpha', 'gamma', 'label_smoothing', 'beta', 'reg_weight', 'pos_iou', 'neg_iou')] + \
+               [('low_quality', C.c_int), ('box_kind', C.c_int), ('box_weight', C.c_float)]
 
 
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
@@ -243,6 +248,16 @@ BOX_LOSS_SIGNATURES = {
     'effdet_box_loss_fwd_grad': 'i:ppppppqpiiiqiiifs',
     'effdet_box_loss_bwd_reg': 'i:ppppppiiiqiifs',
 }
+# The options of the detection loss (focal alpha / gamma, label smoothing, smooth-L1 knee and weight, matcher bands, low-quality
+# matches), declared in include/effdet_loss_opts.h (same generation, same letters, same rule; tests/test_loss_options_host.py compares
+# this table with that header's prototypes).  The options travel as a LossOpts struct in host memory (byref).
+LOSS_OPTS_SIGNATURES = {
+    'effdet_loss_opts_workspace_bytes': 'q:iqii',
+    'effdet_loss_opts_fwd': 'i:ppppppqiqiips',
+    'effdet_loss_opts_fwd_grad': 'i:ppppppqpiiiqiips',
+    'effdet_loss_opts_bwd_cls': 'i:pppppiiiqiips',
+    'effdet_loss_opts_bwd_reg': 'i:ppppppiiiqips',
+}
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
 DW_PLAN_FWD, DW_PLAN_DGRAD, DW_PLAN_WGRAD, DW_PLAN_BWD, DW_PLAN_EXPAND_FWD = 0, 1, 2, 3, 4      # EFFDET_DW_PLAN_*
 DW_INFO = ('cq', 'tpi', 'ppt', 'nbuf', 'groups', 'nslab', 'direct')                              # EFFDET_DW_INFO_* in order
@@ -264,7 +279,8 @@ def lib():
                                % (LIB_PATH, got, ABI_VERSION))
         _lib = cand
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
-                list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()):
+                list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
+                list(LOSS_OPTS_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

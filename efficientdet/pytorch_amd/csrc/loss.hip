@@ -17,6 +17,7 @@
 // HBM-bound: reads cls once per pass (15.7 MB / image fp32 at 80 classes).
 #include "common.h"
 #include "../../../include/effdet_box_loss.h"
+#include "../../../include/effdet_loss_opts.h"
 
 namespace {
 
@@ -664,6 +665,491 @@ extern "C" int effdet_box_loss_bwd_reg(const float* reg, const float* anchors, c
   if (dtype == EFFDET_F32) hipLaunchKernelGGL(box_loss_bwd_reg_kernel<float>, grid, dim3(256), 0, st, k, kind, weight);
   else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(box_loss_bwd_reg_kernel<split_t>, grid, dim3(256), 0, st, k, kind, weight);
   else hipLaunchKernelGGL(box_loss_bwd_reg_kernel<bf16_t>, grid, dim3(256), 0, st, k, kind, weight);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Loss options (include/effdet_loss_opts.h fixes the semantics): focal alpha / gamma, label smoothing, the smooth-L1 knee and weight,
+// the matcher's IoU bands and low-quality matches, as launch arguments.  The kernels above are not edited: these are their twins.
+//   opts_iou_kernel     one thread per (image, anchor): loss_assign_kernel's IoU loop -> best[b][a], barg[b][a]; with low_quality also
+//                       gtmax[b][n] = max over the anchors, as an INTEGER atomicMax on the bit pattern of the non-negative IoU (order-
+//                       independent, exact), first per workgroup in LDS, then one global atomic per (workgroup, row)
+//   opts_assign_kernel  the same grid: bands on best; with low_quality the IoU loop once more, promoting an anchor whose IoU with any row
+//                       equals that row's gtmax (> 0); assign[], the smooth-L1 partials with the knee beta, the integer num_pos
+//   opts_cls_* / opts_bwd_cls_*  the class passes with focal_elem_opts in the place of focal_elem
+//   opts_final_kernel   loss_final_kernel with reg_weight on losses[1];  opts_bwd_reg_kernel  loss_bwd_reg_kernel with beta, reg_weight
+// An IoU-family box term (box_kind 1..4) is box_loss_fwd / box_loss_final / box_loss_bwd_reg_kernel as they are, over this assignment.
+namespace {
+
+struct FocalP { float alpha, gamma, eps; };
+struct OptsK {
+  FocalP f; float beta, reg_weight, pos_iou, neg_iou; int low_quality;
+  int* gtmax; float* best; int* barg;         // [B][N] bit patterns, [B][A], [B][A]
+};
+
+// loss_assign_kernel's IoU of anchor `an` (area aarea) with the box at r[0..3], statement for statement: both passes of the matcher
+// evaluate THIS function, so the equality test of the second pass compares a value with a maximum over the same values (no
+// contraction: whether a multiply-add is fused must not depend on the kernel the function is inlined into; loss_assign_kernel's
+// gfx950 code has none in this expression either)
+__device__ __forceinline__ float assign_iou(const float4 an, const float aarea, const float* r) {
+#pragma clang fp contract(off)
+  const float bx1 = r[0], by1 = r[1], bx2 = r[2], by2 = r[3];
+  const float barea = (bx2 - bx1) * (by2 - by1);
+  float iw = fminf(an.z, bx2) - fmaxf(an.x, bx1); float ih = fminf(an.w, by2) - fmaxf(an.y, by1);
+  iw = fmaxf(iw, 0.f); ih = fmaxf(ih, 0.f);
+  const float ua = fmaxf(aarea + barea - iw * ih, 1e-8f);
+  const float iou = iw * ih / ua;
+  return iou;
+}
+
+// thread 0 compacts the valid rows of chunk [n0, n0 + 64) of image b into ann[] (loss_assign_kernel's order and format) -> their number
+__device__ __forceinline__ int compact_chunk(const LossK& p, int b, int n0, float* ann) {
+  int c = 0;
+  for (int n = n0; n < min(p.N, n0 + 64); ++n) {
+    const float* r = p.annots + ((long long)b * p.N + n) * 5;
+    if (r[4] != -1.0f) { for (int q = 0; q < 5; ++q) ann[c * 5 + q] = r[q]; ann[c * 5 + 4] = (float)n; ++c; }
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(256) void opts_zero_kernel(float* __restrict__ stat, int n, int* __restrict__ gtmax, int m) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) stat[i] = 0.f;
+  else if (i - n < m) gtmax[i - n] = 0;
+}
+
+__global__ __launch_bounds__(256) void opts_iou_kernel(const LossK p, const OptsK o) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  __shared__ float ann[64 * 5];
+  __shared__ int gm[64];
+  __shared__ int nvalid_s;
+  float best = -1.0f; int barg = -1;
+  float4 an = make_float4(0, 0, 0, 0);
+  const bool ok = a < p.A;
+  if (ok) an = ((const float4*)p.anchors)[a];
+  const float aarea = (an.z - an.x) * (an.w - an.y);
+  int total_valid = 0;
+  for (int n0 = 0; n0 < p.N; n0 += 64) {
+    __syncthreads();
+    if (threadIdx.x == 0) nvalid_s = compact_chunk(p, b, n0, ann);
+    if (threadIdx.x < 64) gm[threadIdx.x] = 0;
+    __syncthreads();
+    const int c = nvalid_s;
+    total_valid += c;
+    if (ok) {
+      for (int j = 0; j < c; ++j) {
+        const float iou = assign_iou(an, aarea, ann + j * 5);
+        if (iou > best) { best = iou; barg = (int)ann[j * 5 + 4]; }     // strict > keeps the FIRST max
+        if (o.low_quality && iou > 0.f && __float_as_int(iou) > *(volatile int*)&gm[j]) atomicMax(&gm[j], __float_as_int(iou));
+      }
+    }
+    if (o.low_quality) {
+      __syncthreads();
+      if ((int)threadIdx.x < c && gm[threadIdx.x] > 0) atomicMax(o.gtmax + (long long)b * p.N + (int)ann[threadIdx.x * 5 + 4], gm[threadIdx.x]);
+    }
+  }
+  if (ok) { o.best[(long long)b * p.A + a] = best; o.barg[(long long)b * p.A + a] = barg; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
+}
+
+__global__ __launch_bounds__(256) void opts_assign_kernel(const LossK p, const OptsK o) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  __shared__ float ann[64 * 5];
+  __shared__ float gmf[64];
+  __shared__ int nvalid_s;
+  __shared__ float red[2][4];
+  const bool ok = a < p.A;
+  float4 an = make_float4(0, 0, 0, 0);
+  float best = -1.0f; int barg = -1;
+  if (ok) { an = ((const float4*)p.anchors)[a]; best = o.best[(long long)b * p.A + a]; barg = o.barg[(long long)b * p.A + a]; }
+  const bool any_valid = p.stat[b * SS + 3] > 0.f;
+  bool promoted = false;
+  if (o.low_quality && any_valid) {
+    const float aarea = (an.z - an.x) * (an.w - an.y);
+    for (int n0 = 0; n0 < p.N; n0 += 64) {
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const int c = compact_chunk(p, b, n0, ann);
+        for (int j = 0; j < c; ++j) gmf[j] = __int_as_float(o.gtmax[(long long)b * p.N + (int)ann[j * 5 + 4]]);
+        nvalid_s = c;
+      }
+      __syncthreads();
+      const int c = nvalid_s;
+      if (ok) {
+        for (int j = 0; j < c; ++j) {
+          const float iou = assign_iou(an, aarea, ann + j * 5);
+          promoted = promoted || (iou == gmf[j] && gmf[j] > 0.f);
+        }
+      }
+    }
+  }
+  float regl = 0.f, pos = 0.f;
+  int code = -2;                       // -2 ignore, -1 negative, >= 0 positive (annotation row)
+  if (ok && any_valid) {
+    if (best < o.neg_iou) code = -1;
+    if ((best >= o.pos_iou || promoted) && barg >= 0) {
+      code = barg; pos = 1.f;
+      const float* g = p.annots + ((long long)b * p.N + barg) * 5;
+      const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
+      float gw = g[2] - g[0], gh = g[3] - g[1];
+      const float gcx = g[0] + 0.5f * gw, gcy = g[1] + 0.5f * gh;
+      gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
+      const float t[4] = {(gcx - acx) / aw / 0.1f, (gcy - acy) / ah / 0.1f, logf(gw / aw) / 0.2f, logf(gh / ah) / 0.2f};
+      const float4 r = ((const float4*)p.reg)[(long long)b * p.A + a];
+      const float rv[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { const float d = fabsf(t[q] - rv[q]); regl += (d <= o.beta) ? 0.5f * d * d / o.beta : d - 0.5f * o.beta; }
+    }
+  }
+  if (ok) p.assign[(long long)b * p.A + a] = code;
+  regl = wave_sum(regl); pos = wave_sum(pos);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { red[0][wave] = regl; red[1][wave] = pos; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    p.part_reg[(long long)b * p.na + blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    atomicAdd((int*)(p.stat + b * SS + 2), (int)(red[1][0] + red[1][1] + red[1][2] + red[1][3]));    // num_pos is kept as an INTEGER (npos())
+  }
+}
+
+// focal_elem with the options: per-element term and its derivative wrt the (unclamped) probability p
+// (no contraction: every kernel and layout computes the same bits)
+__device__ __forceinline__ float focal_elem_opts(const FocalP f, float praw, bool target_one, float& dldp) {
+#pragma clang fp contract(off)
+  const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);
+  const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);
+  const float h = target_one ? 1.f : 0.f;
+  const float t = h * (1.f - f.eps) + 0.5f * f.eps;
+  const float u = target_one ? 1.f - pc : pc, aw = target_one ? f.alpha : 1.f - f.alpha;
+  const float pw = exp2f(f.gamma * log2f(u));
+  const float ce = -(t * logf(pc) + (1.f - t) * logf(1.f - pc));
+  const float dce = (1.f - t) / (1.f - pc) - t / pc;
+  const float dpw = f.gamma * pw / u;                               // d pw / d u; du / dp = -1 for a target of one
+  dldp = pass ? aw * ((target_one ? -dpw : dpw) * ce + pw * dce) : 0.f;
+  return aw * pw * ce;
+}
+
+__device__ __forceinline__ int label_of(const LossK& p, int b, int code) {
+  return code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
+}
+
+// loss_cls_kernel with the options
+__global__ __launch_bounds__(256) void opts_cls_kernel(const LossK p, const FocalP f) {
+  const int b = blockIdx.y;
+  const int per = (int)(p.A * p.nc);
+  float s = 0.f;
+  if (p.stat[b * SS + 3] > 0.f) {
+    const float* c = p.cls + (long long)b * per;
+    const int* asg = p.assign + (long long)b * p.A;
+#pragma unroll
+    for (int it = 0; it < CLS_IT; ++it) {
+      const int e0 = ((blockIdx.x * CLS_IT + it) * 256 + threadIdx.x) * 4;
+      if (e0 >= per) break;
+      float v[4]; const int cnt = min(4, per - e0);
+      const bool vec = cnt == 4 && ((per & 3) == 0);
+      if (vec) { const f32x4 t = *(const f32x4*)(c + e0); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+      else for (int q = 0; q < cnt; ++q) v[q] = c[e0 + q];
+      int a = e0 / p.nc, k = e0 - a * p.nc;
+      int code = asg[a];
+      int lab = label_of(p, b, code);
+      for (int q = 0; q < cnt; ++q) {
+        if (code != -2) { float d; s += focal_elem_opts(f, v[q], lab == k, d); }
+        if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
+      }
+    }
+  }
+  __shared__ float red[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) p.part_cls[(long long)b * p.ncb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// loss_final_kernel with reg_weight on losses[1]
+__global__ __launch_bounds__(1024) void opts_final_kernel(const LossK p, const float reg_weight) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto lane_sum = [&](const float* q, int n) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int i = lane;
+    for (; i + 192 < n; i += 256) { s0 += q[i]; s1 += q[i + 64]; s2 += q[i + 128]; s3 += q[i + 192]; }
+    for (; i < n; i += 64) s0 += q[i];
+    return wave_sum((s0 + s1) + (s2 + s3));
+  };
+  for (int b = wave; b < p.B; b += 16) {
+    const float c = lane_sum(p.part_cls + (long long)b * p.ncb, p.ncb), r = lane_sum(p.part_reg + (long long)b * p.na, p.na);
+    if (lane == 0) { p.stat[b * SS + 0] = c; p.stat[b * SS + 1] = r; }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float cl = 0.f, rl = 0.f;
+  for (int b = 0; b < p.B; ++b) {
+    const float* s = p.stat + b * SS;
+    if (s[3] > 0.f) {
+      cl += s[0] / fmaxf(npos(s), 1.0f);
+      if (npos(s) > 0.f) rl += s[1] / (npos(s) * 4.0f);
+    }
+  }
+  p.losses[0] = cl / (float)p.B; p.losses[1] = reg_weight * (rl / (float)p.B);
+}
+
+// loss_bwd_cls_kernel with the options
+template <typename T>
+__global__ __launch_bounds__(256) void opts_bwd_cls_kernel(const LossK p, const FocalP f) {
+  const int b = blockIdx.y;
+  const int per = (int)(p.A * p.nc);
+  const int e0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (e0 >= per) return;
+  const float* st = p.stat + b * SS;
+  const bool active = st[3] > 0.f;
+  const float gs = active ? p.gscale[0] / ((float)p.B * fmaxf(npos(st), 1.0f)) : 0.f;
+  const float* c = p.cls + (long long)b * per;
+  const int* asg = p.assign + (long long)b * p.A;
+  T* out = (T*)p.dcls + (long long)b * per;
+  const int cnt = min(4, per - e0);
+  const bool vec = cnt == 4 && ((per & 3) == 0);
+  float v[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
+  if (vec) { const f32x4 t = *(const f32x4*)(c + e0); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+  else for (int q = 0; q < cnt; ++q) v[q] = c[e0 + q];
+  int a = e0 / p.nc, k = e0 - a * p.nc;
+  int code = asg[a];
+  int lab = label_of(p, b, code);
+  for (int q = 0; q < cnt; ++q) {
+    if (active && code != -2) {
+      float d; (void)focal_elem_opts(f, v[q], lab == k, d);
+      g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
+    } else {
+      g[q] = nan_zero(v[q]);
+    }
+    if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
+  }
+  if (vec) store4(out + e0, f32x4{g[0], g[1], g[2], g[3]});
+  else for (int q = 0; q < cnt; ++q) Elem<T>::st(out + e0 + q, g[q]);
+}
+
+// loss_bwd_cls_pix_kernel (GRAD_ONLY: the upstream gradient gscale[0] applied, no partial) and loss_cls_grad_pix_kernel (forward and
+// gradient for an upstream gradient of one in ONE pass over cls) with the options; IT 4-element groups per thread
+template <typename T, bool GRAD_ONLY, int IT>
+__global__ __launch_bounds__(256) void opts_cls_pix_kernel(const LossK p, const FocalP f) {
+  const int b = blockIdx.y;
+  const int apix = (int)(p.A / 9), perp = apix * p.dld, cmax = 9 * p.nc;
+  const float* st = p.stat + b * SS;
+  const bool active = st[3] > 0.f;
+  const float gs = (GRAD_ONLY ? p.gscale[0] : 1.0f) / ((float)p.B * fmaxf(npos(st), 1.0f));
+  float s = 0.f;
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int e0 = ((blockIdx.x * IT + it) * 256 + threadIdx.x) * 4;
+    if (e0 >= perp) break;
+    const int pix = e0 / p.dld, ch = e0 - pix * p.dld;
+    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (ch < cmax) {
+      const int an = ch / p.nc, k = ch - an * p.nc, a = pix * 9 + an;
+      const int code = active ? p.assign[(long long)b * p.A + a] : -2;
+      const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
+      if (code != -2) {
+        const int lab = label_of(p, b, code);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float d; s += focal_elem_opts(f, v[q], lab == k + q, d);
+          g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = nan_zero(v[q]);
+      }
+    }
+    store4((T*)p.dcls + (long long)b * perp + e0, g);
+  }
+  if (GRAD_ONLY) return;
+  __shared__ float red[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) p.part_cls[(long long)b * p.ncb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// loss_bwd_reg_kernel with the knee beta and reg_weight: the same grid, layouts and pad zeroing
+template <typename T>
+__global__ void opts_bwd_reg_kernel(const LossK p, const float beta, const float reg_weight) {
+  const long long total = (long long)p.B * p.A;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / p.A, a = i - b * p.A;
+    const int code = p.assign[i];
+    const float* st = p.stat + b * SS;
+    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (code >= 0 && st[3] > 0.f && npos(st) > 0.f) {
+      const float gs = p.gscale[1] * reg_weight / ((float)p.B * npos(st) * 4.0f);
+      const float4 an = ((const float4*)p.anchors)[a];
+      const float* gt = p.annots + (b * p.N + code) * 5;
+      const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
+      float gw = gt[2] - gt[0], gh = gt[3] - gt[1];
+      const float gcx = gt[0] + 0.5f * gw, gcy = gt[1] + 0.5f * gh;
+      gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
+      const float t[4] = {(gcx - acx) / aw / 0.1f, (gcy - acy) / ah / 0.1f, logf(gw / aw) / 0.2f, logf(gh / ah) / 0.2f};
+      const float4 r = ((const float4*)p.reg)[i];
+      const float rv[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float diff = rv[q] - t[q], d = fabsf(diff);
+        const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
+        g[q] = gs * ((d <= beta) ? diff / beta : sgn + 0.f * d);      // (0 * d: see loss_bwd_reg_kernel)
+      }
+    }
+    if (p.reg_ld) {
+      const long long pix = a / 9; const int an = (int)(a - pix * 9);
+      T* row = (T*)p.dreg + (b * (p.A / 9) + pix) * p.reg_ld;
+      store4(row + an * 4, g);
+      if (an == 8) for (int c = 36; c < p.reg_ld; c += 4) store4(row + c, f32x4{0.f, 0.f, 0.f, 0.f});
+    } else {
+      store4((T*)p.dreg + i * 4, g);
+    }
+  }
+}
+
+// carve_loss's layout, then gtmax [B][N], best [B][A], barg [B][A] -> bytes
+size_t carve_loss_opts(LossK& k, OptsK& o, void* ws, int B, long long A, int num_classes, int N) {
+  const size_t head = carve_loss(k, ws, B, A, num_classes);
+  Carver c(ws ? (char*)ws + head : nullptr);
+  o.gtmax = c.take<int>((size_t)B * N);
+  o.best = c.take<float>((size_t)B * A);
+  o.barg = c.take<int>((size_t)B * A);
+  return head + c.off;
+}
+
+inline bool finite_ge0(float v) { return v >= 0.f && v <= 3.402823466e38f; }      // (false for a NaN)
+
+bool loss_opts_ok(const effdet_loss_opts_t* o) {
+  if (!o) return false;
+  if (!(o->alpha > 0.f && o->alpha < 1.f) || !(o->gamma >= 0.f && o->gamma <= 8.f)) return false;
+  if (!(o->label_smoothing >= 0.f && o->label_smoothing < 1.f)) return false;
+  if (!(o->beta > 0.f && o->beta <= 3.402823466e38f) || !finite_ge0(o->reg_weight) || !finite_ge0(o->box_weight)) return false;
+  if (!(o->neg_iou >= 0.f && o->neg_iou <= o->pos_iou && o->pos_iou <= 1.f)) return false;
+  if (o->low_quality != 0 && o->low_quality != 1) return false;
+  return o->box_kind >= 0 && o->box_kind <= EFFDET_BOX_LOSS_CIOU;
+}
+
+OptsK opts_args(const effdet_loss_opts_t* o) {
+  OptsK k{};
+  k.f = FocalP{o->alpha, o->gamma, o->label_smoothing};
+  k.beta = o->beta; k.reg_weight = o->reg_weight; k.pos_iou = o->pos_iou; k.neg_iou = o->neg_iou; k.low_quality = o->low_quality;
+  return k;
+}
+
+// both forward entry points: dcls_pix == nullptr is effdet_loss_opts_fwd
+int loss_opts_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
+                      long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
+                      int N, const effdet_loss_opts_t* opts, effdet_stream_t stream) {
+  if (!cls || !reg || !anchors || !annots || !losses || !workspace || (grad && !dcls_pix)) return EFFDET_EINVAL;
+  if (!loss_opts_ok(opts) || B < 1 || B > 65535 || N < 1 || A < 1 || num_classes < 1) return EFFDET_EINVAL;
+  if (workspace_bytes < effdet_loss_opts_workspace_bytes(B, A, num_classes, N)) return EFFDET_EINVAL;
+  if (grad) {
+    if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
+    if (dld <= 0 || A % 9 || num_classes % 4 || dld % 4 || dld < 9 * num_classes) return EFFDET_EINVAL;
+    if (dtype == EFFDET_F32_SPLIT && (dld % 32 || ((unsigned long long)dcls_pix & 127ull))) return EFFDET_EINVAL;
+    if ((A / 9) * dld >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
+  }
+  if (A * num_classes >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
+  LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.losses = losses;
+  k.dcls = dcls_pix; k.dld = dld; k.B = B; k.nc = num_classes; k.N = N; k.A = A;
+  OptsK o = opts_args(opts);
+  carve_loss_opts(k, o, workspace, B, A, num_classes, N);
+  hipStream_t st = (hipStream_t)stream;
+  const int nz = B * SS, mz = B * N;
+  hipLaunchKernelGGL(opts_zero_kernel, dim3((unsigned)((nz + mz + 255) / 256)), dim3(256), 0, st, k.stat, nz, o.gtmax, mz);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(opts_iou_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(opts_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o);
+  EFFDET_CHECK_LAUNCH();
+  if (grad) {
+    const long long groups = (A / 9) * dld / 4;
+    k.ncb = (int)((groups + 256 * FG_IT - 1) / (256 * FG_IT));
+    if (k.ncb > cls_blocks_max(A, num_classes)) return EFFDET_EINVAL;
+    dim3 g1((unsigned)k.ncb, B);
+    if (dtype == EFFDET_F32) hipLaunchKernelGGL((opts_cls_pix_kernel<float, false, FG_IT>), g1, dim3(256), 0, st, k, o.f);
+    else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL((opts_cls_pix_kernel<split_t, false, FG_IT>), g1, dim3(256), 0, st, k, o.f);
+    else hipLaunchKernelGGL((opts_cls_pix_kernel<bf16_t, false, FG_IT>), g1, dim3(256), 0, st, k, o.f);
+  } else {
+    const long long groups = (A * num_classes + 3) / 4;
+    k.ncb = (int)((groups + 256 * CLS_IT - 1) / (256 * CLS_IT));
+    if (k.ncb > cls_blocks_max(A, num_classes)) return EFFDET_EINVAL;
+    hipLaunchKernelGGL(opts_cls_kernel, dim3((unsigned)k.ncb, B), dim3(256), 0, st, k, o.f);
+  }
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(opts_final_kernel, dim3(1), dim3(1024), 0, st, k, o.reg_weight);
+  EFFDET_CHECK_LAUNCH();
+  if (opts->box_kind == 0) return EFFDET_OK;
+  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
+}
+
+}  // namespace
+
+extern "C" long long effdet_loss_opts_workspace_bytes(int B, long long A, int num_classes, int N) {
+  LossK k{}; OptsK o{};
+  return (long long)carve_loss_opts(k, o, nullptr, B, A, num_classes, N);
+}
+
+extern "C" int effdet_loss_opts_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                    void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
+                                    const effdet_loss_opts_t* opts, effdet_stream_t stream) {
+  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
+                           num_classes, N, opts, stream);
+}
+
+extern "C" int effdet_loss_opts_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                         void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
+                                         long long A, int num_classes, int N, const effdet_loss_opts_t* opts, effdet_stream_t stream) {
+  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
+                           num_classes, N, opts, stream);
+}
+
+extern "C" int effdet_loss_opts_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls,
+                                        int dld, int dtype, int B, long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
+                                        effdet_stream_t stream) {
+  if (!cls || !annots || !gscale || !workspace || !dcls) return EFFDET_EINVAL;
+  if (!loss_opts_ok(opts) || B < 1 || B > 65535 || N < 1 || A < 1 || num_classes < 1 || dld < 0) return EFFDET_EINVAL;
+  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16) return EFFDET_EINVAL;
+  if (dld && (A % 9 || num_classes % 4 || dld % 4 || dld < 9 * num_classes)) return EFFDET_EINVAL;
+  if (A * num_classes >= 0x7fffffffLL || (dld && (A / 9) * dld >= 0x7fffffffLL)) return EFFDET_EUNSUPPORTED;
+  LossK k{}; k.cls = cls; k.annots = annots; k.gscale = gscale; k.dcls = dcls; k.B = B; k.nc = num_classes; k.N = N; k.A = A; k.dld = dld;
+  carve_loss(k, const_cast<void*>(workspace), B, A);
+  const FocalP f{opts->alpha, opts->gamma, opts->label_smoothing};
+  hipStream_t st = (hipStream_t)stream;
+  const long long groups = dld ? (A / 9) * dld / 4 : (A * num_classes + 3) / 4;
+  dim3 g1((unsigned)((groups + 255) / 256), B);
+  if (dtype == EFFDET_F32) {
+    if (dld) hipLaunchKernelGGL((opts_cls_pix_kernel<float, true, 1>), g1, dim3(256), 0, st, k, f);
+    else hipLaunchKernelGGL(opts_bwd_cls_kernel<float>, g1, dim3(256), 0, st, k, f);
+  } else {
+    if (dld) hipLaunchKernelGGL((opts_cls_pix_kernel<bf16_t, true, 1>), g1, dim3(256), 0, st, k, f);
+    else hipLaunchKernelGGL(opts_bwd_cls_kernel<bf16_t>, g1, dim3(256), 0, st, k, f);
+  }
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+extern "C" int effdet_loss_opts_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
+                                        const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N,
+                                        const effdet_loss_opts_t* opts, effdet_stream_t stream) {
+  if (!loss_opts_ok(opts)) return EFFDET_EINVAL;
+  if (opts->box_kind != 0)
+    return effdet_box_loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, opts->box_kind,
+                                   opts->box_weight, stream);
+  if (!reg || !anchors || !annots || !gscale || !workspace || !dreg || B < 1 || N < 1 || A < 1) return EFFDET_EINVAL;
+  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
+  if (reg_ld && (reg_ld < 36 || reg_ld % 4 || A % 9)) return EFFDET_EINVAL;
+  if (dtype == EFFDET_F32_SPLIT && (!reg_ld || reg_ld % 32 || ((unsigned long long)dreg & 127ull))) return EFFDET_EINVAL;
+  LossK k{}; k.reg = reg; k.anchors = anchors; k.annots = annots; k.gscale = gscale; k.dreg = dreg;
+  k.B = B; k.N = N; k.A = A; k.reg_ld = reg_ld;
+  carve_loss(k, const_cast<void*>(workspace), B, A);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(grid_for((long long)B * A));
+  if (dtype == EFFDET_F32) hipLaunchKernelGGL(opts_bwd_reg_kernel<float>, grid, dim3(256), 0, st, k, opts->beta, opts->reg_weight);
+  else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(opts_bwd_reg_kernel<split_t>, grid, dim3(256), 0, st, k, opts->beta, opts->reg_weight);
+  else hipLaunchKernelGGL(opts_bwd_reg_kernel<bf16_t>, grid, dim3(256), 0, st, k, opts->beta, opts->reg_weight);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }

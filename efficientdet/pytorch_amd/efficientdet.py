@@ -116,16 +116,19 @@ class Anchors(nn.Module):
 
 class FocalLoss(nn.Module):
     """models/losses.py:29-152 as two HIP passes; forward only (training uses the fused head+loss node).  box_loss: an
-    ops.BoxLossOptions puts an IoU-family loss in the place of smooth-L1 (None: the reference's term)."""
+    ops.BoxLossOptions puts an IoU-family loss in the place of smooth-L1 (None: the reference's term); loss: an ops.LossOptions sets
+    focal alpha / gamma, label smoothing, the smooth-L1 knee and weight and the matcher's rules (None: the reference's constants)."""
 
-    def __init__(self, box_loss=None):
+    def __init__(self, box_loss=None, loss=None):
         super().__init__()
         ops._box_loss_args(box_loss)                            # (TypeError on anything but BoxLossOptions / None)
+        ops._loss_opts_struct(loss)                             # (TypeError on anything but LossOptions / None)
         self.box_loss = box_loss
+        self.loss = loss
 
     def forward(self, classifications, regressions, anchors, annotations):
-        losses, _ = ops.box_loss_fwd(classifications.contiguous(), regressions.contiguous(), anchors.contiguous(),
-                                     annotations.contiguous().float(), self.box_loss)
+        losses, _ = ops.loss_opts_fwd(classifications.contiguous(), regressions.contiguous(), anchors.contiguous(),
+                                      annotations.contiguous().float(), getattr(self, 'loss', None), self.box_loss)
         return losses[0:1], losses[1:2]
 
 
@@ -315,11 +318,13 @@ class _HeadLossFn(torch.autograd.Function):
     """RetinaHead + focal / smooth-L1 loss as ONE node: the loss kernel hands the head's data-gradient convs
     d(logit) and d(reg) directly in the activation dtype (no fp32 gradient tensor round trip).  box: None = smooth-L1 (the
     ops.focal_loss_* calls), an ops.BoxLossOptions of an IoU kind = the ops.box_loss_* calls, which keep the output contract of
-    d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them)."""
+    d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them).  loss: None =
+    the reference's constants (the calls above), a non-default ops.LossOptions = the ops.loss_opts_* calls with box inside them; they
+    keep the same contracts for d(logit) and d(reg)."""
 
     @staticmethod
-    def forward(ctx, dtype, num_classes, anchors, annots, train, box, *args):
-        ctx.prep, ctx.arith, ctx.box = ops.get_prep(), ops.F32_ARITH_BWD, box
+    def forward(ctx, dtype, num_classes, anchors, annots, train, box, loss, *args):
+        ctx.prep, ctx.arith, ctx.box, ctx.loss = ops.get_prep(), ops.F32_ARITH_BWD, box, loss
         p = [Map.of(t) for t in args[:5]]
         HP = dict(zip(_HEAD_KEYS, args[5:]))
         cls, reg, saved = Fn.head_fwd(p, HP, num_classes, dtype, train)
@@ -328,13 +333,18 @@ class _HeadLossFn(torch.autograd.Function):
             # ONE pass over the 15.7 MB/image of probabilities: losses + d(logits) for an upstream gradient of one, already in
             # the pixel-major, 64-channel-padded rows the head's gradient convs read; cls itself is not kept for backward
             dld = (9 * nc + 63) // 64 * 64
-            if box is None:
+            if loss is not None:
+                losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], loss=loss, box=box)
+            elif box is None:
                 losses, ws, dpix = ops.focal_loss_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5])    # (split-layout head: see functional.head_uses_split)
             else:
                 losses, ws, dpix = ops.box_loss_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], options=box)
             ctx.saved = (saved, None, reg, anchors, annots, ws, dtype, dpix, dld)
         else:
-            losses, ws = ops.focal_loss_fwd(cls, reg, anchors, annots) if box is None else ops.box_loss_fwd(cls, reg, anchors, annots, box)
+            if loss is not None:
+                losses, ws = ops.loss_opts_fwd(cls, reg, anchors, annots, loss, box)
+            else:
+                losses, ws = ops.focal_loss_fwd(cls, reg, anchors, annots) if box is None else ops.box_loss_fwd(cls, reg, anchors, annots, box)
             ctx.saved = (saved, cls, reg, anchors, annots, ws, dtype, None, 0) if train else None
         return losses[0:1].clone(), losses[1:2].clone()
 
@@ -350,7 +360,9 @@ class _HeadLossFn(torch.autograd.Function):
         if dpix is not None:
             split = saved[5]
             rld = 64 if split else 0                # split layout: d(reg) pixel-major, 36 -> 64 channels (two [hi|lo] groups)
-            if ctx.box is None:
+            if ctx.loss is not None:
+                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, loss=ctx.loss, box=ctx.box)
+            elif ctx.box is None:
                 dreg = ops.focal_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split)
             else:
                 dreg = ops.box_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, options=ctx.box)
@@ -358,18 +370,20 @@ class _HeadLossFn(torch.autograd.Function):
                 dp, g = Fn.head_bwd(saved, dpix, dreg, dtype, dcls_ld=dld, cls_gscale=gscale[0:1], dreg_ld=rld, in_split=split)
         else:
             nc = cls.shape[2]
-            if nc % 4 == 0:      # d(logits) straight into the pixel-major, 64-channel-padded rows the head's gradient convs read
-                dld = (9 * nc + 63) // 64 * 64
+            dld = (9 * nc + 63) // 64 * 64 if nc % 4 == 0 else 0      # d(logits) straight into the pixel-major, 64-channel-padded rows the head's gradient convs read
+            if ctx.loss is not None:
+                dcls = ops.loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, ctx.loss, dld=dld)
+                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, loss=ctx.loss, box=ctx.box)
+            elif dld:
                 dcls, dreg = ops.focal_loss_bwd_pix(cls, reg, anchors, annots, gscale, ws, dtype, dld)
             else:
-                dld = 0
                 dcls, dreg = ops.focal_loss_bwd(cls, reg, anchors, annots, gscale, ws, dtype)
-            if ctx.box is not None:      # (the class gradient above is the focal term's either way; its smooth-L1 d(reg) is replaced)
+            if ctx.loss is None and ctx.box is not None:      # (the class gradient above is the focal term's either way; its smooth-L1 d(reg) is replaced)
                 dreg = ops.box_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, options=ctx.box)
             with ops.unpack_batch():
                 dp, g = Fn.head_bwd(saved, dcls, dreg, dtype, dcls_ld=dld)
         ctx.saved = None
-        return (None, None, None, None, None, None) + tuple(Fn.level_tensor(m) for m in dp) + tuple(g[k] for k in _HEAD_KEYS)
+        return (None, None, None, None, None, None, None) + tuple(Fn.level_tensor(m) for m in dp) + tuple(g[k] for k in _HEAD_KEYS)
 
 
 # --------------------------------------------------------------------------- the model
@@ -386,6 +400,7 @@ class EfficientDet(nn.Module):
         self.iou_threshold = iou_threshold
         self.nms_options = None                                 # set_nms(): None = the reference's class-agnostic greedy NMS
         self.box_loss = None                                    # set_box_loss(): None = the reference's smooth-L1 on encoded deltas
+        self.loss_options = None                                # set_loss(): None = the reference's focal / smooth-L1 / matcher constants
         self.num_classes = num_classes
         self.compute_dtype = compute_dtype
         # MFMA arithmetic on fp32 storage: 'f32' = exact fp32 products (v_mfma_f32_16x16x4_f32), 'bf16x3' = operands split into
@@ -438,6 +453,18 @@ class EfficientDet(nn.Module):
             raise TypeError('set_box_loss takes a BoxLossOptions or None, not %r' % (options,))
         self.box_loss = options
         self.criterion.box_loss = options
+        return self
+
+    def set_loss(self, options):
+        """Options of the training loss: None (the default) or an ops.LossOptions equal to the defaults = the reference's constants
+        (alpha 0.25, gamma 2, no label smoothing, smooth-L1 knee 1/9 with weight 1, bands 0.4 / 0.5, no low-quality matches), through
+        the same calls as ever; any other LossOptions = the effdet_loss_opts_* entry points (include/effdet_loss_opts.h), with the box
+        term of set_box_loss inside them.  The values are launch arguments: a graph.GraphedTrainStep / GraphedTrainLoop captured
+        before a change keeps the old loss until it is captured again."""
+        if options is not None and not isinstance(options, ops.LossOptions):
+            raise TypeError('set_loss takes a LossOptions or None, not %r' % (options,))
+        self.loss_options = options
+        self.criterion.loss = options
         return self
 
     def live_parameters(self):
@@ -587,8 +614,10 @@ class EfficientDet(nn.Module):
             anc = self.anchors(inputs)
             box = getattr(self, 'box_loss', None)                # (a model pickled before the option existed has no such attribute)
             box = None if (box is None or box.is_default()) else box
+            loss = getattr(self, 'loss_options', None)           # (likewise)
+            loss = None if (loss is None or loss.is_default()) else loss
             return _HeadLossFn.apply(self.compute_dtype, self.num_classes, anc, annotations.float().contiguous(),
-                                     torch.is_grad_enabled(), box, *p, *self._head_params())
+                                     torch.is_grad_enabled(), box, loss, *p, *self._head_params())
         dets = self.detect(inputs)
         s, l, b = dets[0]
         if s.numel() == 0:

@@ -1400,6 +1400,138 @@ def box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False,
     return dreg
 
 
+def _f32(v):
+    return C.c_float(float(v)).value
+
+
+LOSS_BETA_DEFAULT = _f32(1.0 / 9.0)                  # the reference's smooth-L1 knee as the fp32 the kernels compare with
+
+
+class LossOptions:
+    """The options of the training loss of EfficientDet.set_loss / FocalLoss(loss=) (include/effdet_loss_opts.h): focal alpha and gamma,
+    label smoothing eps (soft target h (1 - eps) + eps / 2), the smooth-L1 knee beta (Huber delta) and its weight reg_weight, the
+    matcher's bands (positive at IoU >= pos_iou, negative below neg_iou, ignored between) and low_quality (every annotation's best
+    anchor(s) become positive, torchvision's allow_low_quality_matches).  Values are kept as the fp32 the kernels receive.  The
+    defaults are the reference's constants: a LossOptions equal to them is the existing ops.focal_loss_* / box_loss_* calls."""
+
+    _FIELDS = ('alpha', 'gamma', 'label_smoothing', 'beta', 'reg_weight', 'pos_iou', 'neg_iou', 'low_quality')
+
+    def __init__(self, alpha=0.25, gamma=2.0, label_smoothing=0.0, beta=LOSS_BETA_DEFAULT, reg_weight=1.0, pos_iou=0.5, neg_iou=0.4,
+                 low_quality=False):
+        a, g, e, b, w, hi, lo = (_f32(v) for v in (alpha, gamma, label_smoothing, beta, reg_weight, pos_iou, neg_iou))
+        inf = float('inf')
+        if not 0.0 < a < 1.0:
+            raise ValueError('LossOptions: alpha must lie in (0, 1), not %r' % (alpha,))
+        if not 0.0 <= g <= 8.0:
+            raise ValueError('LossOptions: gamma must lie in [0, 8], not %r' % (gamma,))
+        if not 0.0 <= e < 1.0:
+            raise ValueError('LossOptions: label_smoothing must lie in [0, 1), not %r' % (label_smoothing,))
+        if not 0.0 < b < inf:
+            raise ValueError('LossOptions: beta must be finite and > 0, not %r' % (beta,))
+        if not 0.0 <= w < inf:
+            raise ValueError('LossOptions: reg_weight must be finite and >= 0, not %r' % (reg_weight,))
+        if not 0.0 <= lo <= hi <= 1.0:
+            raise ValueError('LossOptions: need 0 <= neg_iou <= pos_iou <= 1, not neg_iou %r, pos_iou %r' % (neg_iou, pos_iou))
+        if low_quality not in (False, True, 0, 1):
+            raise ValueError('LossOptions: low_quality must be a bool, not %r' % (low_quality,))
+        self.alpha, self.gamma, self.label_smoothing, self.beta, self.reg_weight, self.pos_iou, self.neg_iou = a, g, e, b, w, hi, lo
+        self.low_quality = bool(low_quality)
+
+    def key(self):
+        return tuple(getattr(self, f) for f in self._FIELDS)
+
+    def is_default(self):
+        return self.key() == _LOSS_DEFAULT_KEY
+
+    def __eq__(self, other):
+        return isinstance(other, LossOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'LossOptions(%s)' % ', '.join('%s=%r' % (f, getattr(self, f)) for f in self._FIELDS)
+
+
+_LOSS_DEFAULT_KEY = LossOptions().key()
+
+
+def _loss_opts_struct(loss, box=None):
+    """-> None where the existing calls apply (loss None or equal to the defaults), else the effdet_loss_opts_t of (loss, box)."""
+    if loss is None:
+        return None
+    if not isinstance(loss, LossOptions):
+        raise TypeError('loss options must be a LossOptions or None, not %r' % (loss,))
+    if loss.is_default():
+        return None
+    kw = _box_loss_args(box)
+    kind, weight = (0, 1.0) if kw is None else kw
+    return L.LossOpts(loss.alpha, loss.gamma, loss.label_smoothing, loss.beta, loss.reg_weight, loss.pos_iou, loss.neg_iou,
+                      1 if loss.low_quality else 0, kind, weight)
+
+
+def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None):
+    """box_loss_fwd with the options of loss (None / the defaults: box_loss_fwd itself) -> (losses [2], ws)."""
+    o = _loss_opts_struct(loss, box)
+    if o is None:
+        return box_loss_fwd(cls, reg, anc, annots, box)
+    lib = L.require('effdet_loss_opts_fwd', 'effdet_loss_opts_workspace_bytes')
+    B, A, nc = cls.shape
+    N = annots.shape[1]
+    nbytes = int(lib.effdet_loss_opts_workspace_bytes(B, A, nc, N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
+    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
+    L.check(lib.effdet_loss_opts_fwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes, B, A, nc, N,
+                                     C.byref(o), L.stream_ptr()), 'effdet_loss_opts_fwd')
+    return losses, ws
+
+
+def loss_opts_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, loss=None, box=None):
+    """box_loss_fwd_grad with the options of loss -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
+    o = _loss_opts_struct(loss, box)
+    if o is None:
+        return box_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=split, options=box)
+    lib = L.require('effdet_loss_opts_fwd_grad', 'effdet_loss_opts_workspace_bytes')
+    B, A, nc = cls.shape
+    N = annots.shape[1]
+    nbytes = int(lib.effdet_loss_opts_workspace_bytes(B, A, nc, N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
+    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
+    dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
+    L.check(lib.effdet_loss_opts_fwd_grad(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes,
+                                          L.ptr(dcls), dld, L.F32_SPLIT if split else L.dtype_code(dtype), B, A, nc, N, C.byref(o),
+                                          L.stream_ptr()), 'effdet_loss_opts_fwd_grad')
+    return losses, ws, dcls
+
+
+def loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, loss, dld=0):
+    """d(logits) of the class term with the (non-default) options of loss, from the workspace of a forward call with them:
+    [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld]."""
+    o = _loss_opts_struct(loss)
+    if o is None:
+        raise ValueError('loss_opts_bwd_cls is the non-default path: the defaults are focal_loss_bwd / focal_loss_bwd_pix')
+    lib = L.require('effdet_loss_opts_bwd_cls')
+    B, A, nc = cls.shape
+    dcls = torch.empty((B, A // 9, dld) if dld else (B, A, nc), dtype=dtype, device=cls.device)
+    L.check(lib.effdet_loss_opts_bwd_cls(L.ptr(cls), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls), dld, L.dtype_code(dtype), B, A,
+                                         nc, annots.shape[1], C.byref(o), L.stream_ptr()), 'effdet_loss_opts_bwd_cls')
+    return dcls
+
+
+def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, loss=None, box=None):
+    """box_loss_bwd_reg with the options of loss: d(reg) in the same three layouts."""
+    o = _loss_opts_struct(loss, box)
+    if o is None:
+        return box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=reg_ld, split=split, options=box)
+    lib = L.require('effdet_loss_opts_bwd_reg')
+    B, A, _ = reg.shape
+    dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
+    L.check(lib.effdet_loss_opts_bwd_reg(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld,
+                                         L.F32_SPLIT if split else L.dtype_code(dtype), B, A, annots.shape[1], C.byref(o),
+                                         L.stream_ptr()), 'effdet_loss_opts_bwd_reg')
+    return dreg
+
+
 def pad_rows(src_map, cpad):
     """Level map with unaligned channel count -> fresh contiguous [B,H,W,cpad] map, zero padded."""
     m = src_map
