@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h).
+include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_conv_plan.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -105,6 +105,11 @@ class EmaCtl(C.Structure):       # effdet_ema_ctl_t (include/effdet_ema.h)
 class LossOpts(C.Structure):     # effdet_loss_opts_t (include/effdet_loss_opts.h)
     _fields_ = [(n, C.c_float) for n in ('alpha', 'gamma', 'label_smoothing', 'beta', 'reg_weight', 'pos_iou', 'neg_iou')] + \
                [('low_quality', C.c_int), ('box_kind', C.c_int), ('box_weight', C.c_float)]
+
+
+class ConvPlanInfo(C.Structure):   # effdet_conv_plan_info_t (include/effdet_conv_plan.h)
+    _fields_ = [(n, C.c_int) for n in ('id', 'form', 'persistent', 'tile_m', 'tile_n', 'stages', 'threads', 'mtiles', 'ntiles', 'grid',
+                                       'ksteps', 'kord', 'lds_bytes', 'm32')] + [('reserved', C.c_int * 2)]
 
 
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
@@ -258,6 +263,12 @@ LOSS_OPTS_SIGNATURES = {
     'effdet_loss_opts_bwd_cls': 'i:pppppiiiqiips',
     'effdet_loss_opts_bwd_reg': 'i:ppppppiiiqips',
 }
+# The host-only query of the dense-conv launch plan, declared in include/effdet_conv_plan.h (same generation, same letters, same rule;
+# tests/test_conv_plan_cases_host.py compares this table and ConvPlanInfo with that header).
+CONV_PLAN_SIGNATURES = {
+    'effdet_conv2d_plan_info': 'i:pp',
+}
+CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
 DW_PLAN_FWD, DW_PLAN_DGRAD, DW_PLAN_WGRAD, DW_PLAN_BWD, DW_PLAN_EXPAND_FWD = 0, 1, 2, 3, 4      # EFFDET_DW_PLAN_*
 DW_INFO = ('cq', 'tpi', 'ppt', 'nbuf', 'groups', 'nslab', 'direct')                              # EFFDET_DW_INFO_* in order
@@ -280,7 +291,7 @@ def lib():
         _lib = cand
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
-                list(LOSS_OPTS_SIGNATURES.items()):
+                list(LOSS_OPTS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -25,6 +25,7 @@
 //     tiles (n fastest), so the activation tile is fetched into one private L2 only.
 #include "common.h"
 #include "../../../include/effdet_live_tiles.h"
+#include "../../../include/effdet_conv_plan.h"
 #include <stdlib.h>
 
 #ifndef EFFDET_IGEMM_BIG_DEFAULT
@@ -1213,6 +1214,10 @@ struct ConvPlan {
   unsigned grid;               // workgroups (the persistent kernel: its tile count, capped at the device's CUs by its launcher)
   size_t lds;                  // dynamic LDS bytes
   int pw_G, pw_NPS, pw_ppw;    // conv_pw_f32_kernel: channel groups, pixel slots per workgroup, pixels per workgroup
+  // the template instance behind `launch`, recorded by the use_* helper that picks it (effdet_conv2d_plan_info copies these out)
+  int form, pers;              // EFFDET_CONV_FORM_*; 1 = conv_igemm_pers_kernel
+  int tile_m, tile_n, stages, threads, m32;      // workgroup tile (pixels x channels), LDS stages of the K loop, threads per workgroup, 32x32x16 tiles
+  int ksteps;                  // trips of the K loop
 };
 
 template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT, int NS, int M32>
@@ -1228,6 +1233,10 @@ int use_igemm(ConvPlan& c, int id) {
   c.grid = (unsigned)(c.k.mtiles * c.k.ntiles);
   c.lds = (size_t)NS * (BM + BN) * 8 * sizeof(uint4);                    // NS-stage operand tiles
   c.launch = launch_igemm<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>;
+  static_assert(EFFDET_CONV_FORM_PLAIN == 0 && EFFDET_CONV_FORM_BF16X3 == 1 && EFFDET_CONV_FORM_SPLIT == 2 && EFFDET_CONV_FORM_HSPLIT == 3,
+                "the kernel's SPLIT parameter is the public form code");
+  c.form = SPLIT; c.pers = 0; c.tile_m = BM; c.tile_n = BN; c.stages = NS; c.threads = NWAVES * 64; c.m32 = M32;
+  c.ksteps = (c.k.Kc + 7) >> 3;
   return c.id = id;
 }
 
@@ -1255,6 +1264,8 @@ int use_pers(ConvPlan& c, int id) {
   c.grid = (unsigned)(k.mtiles * k.ntiles);
   c.lds = (size_t)NS * (TM + TN) * 128;
   c.launch = launch_pers<WM, WN, NS, X3>;
+  c.form = X3 ? EFFDET_CONV_FORM_SPLIT : EFFDET_CONV_FORM_PLAIN; c.pers = 1; c.tile_m = TM; c.tile_n = TN; c.stages = NS; c.threads = WM * WN * 64; c.m32 = 1;
+  c.ksteps = (k.Kc / k.cpt) * (k.cpt >> 3);
   return c.id = id;
 }
 // persistent big-tile variant by kernel id (10 + v, see plan_conv)
@@ -1279,6 +1290,9 @@ static int use_pw(ConvPlan& c) {
   c.grid = (unsigned)((c.k.seg[0].M + c.pw_ppw - 1) / c.pw_ppw);
   c.lds = 0;
   c.launch = c.k.Cin == 16 ? launch_pw<16> : launch_pw<24>;
+  // (no MFMA tile: a workgroup walks its pixels in LDS tiles of 64, all channels at once, two LDS buffers)
+  c.form = EFFDET_CONV_FORM_SKINNY; c.pers = 0; c.tile_m = 64; c.tile_n = c.k.Cout; c.stages = 2; c.threads = 256; c.m32 = 0;
+  c.k.mtiles = (int)c.grid; c.k.ntiles = 1; c.ksteps = 1;
   return c.id = 20;
 }
 
@@ -1478,6 +1492,20 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c) {
 extern "C" int effdet_conv2d_kernel(const effdet_conv_t* p) {
   ConvPlan c;
   return plan_conv(p, c);
+}
+
+// The decision effdet_conv2d launches from, copied out of the same ConvPlan (include/effdet_conv_plan.h): no device work, no HIP runtime call
+extern "C" int effdet_conv2d_plan_info(const effdet_conv_t* p, effdet_conv_plan_info_t* info) {
+  ConvPlan c;
+  const int id = plan_conv(p, c);
+  if (id < 0) return id;
+  if (!info) return EFFDET_EINVAL;
+  info->id = c.id; info->form = c.form; info->persistent = c.pers;
+  info->tile_m = c.tile_m; info->tile_n = c.tile_n; info->stages = c.stages; info->threads = c.threads;
+  info->mtiles = c.k.mtiles; info->ntiles = c.k.ntiles; info->grid = (int)c.grid;
+  info->ksteps = c.ksteps; info->kord = c.k.kord; info->lds_bytes = (int)c.lds; info->m32 = c.m32;
+  info->reserved[0] = info->reserved[1] = 0;
+  return id;
 }
 
 extern "C" int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream) {

@@ -107,7 +107,7 @@ _range_flags = {}
 
 def range_flag(device):
     device = torch.device(device)
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = device.index if (device.index is not None or device.type != 'cuda') else torch.cuda.current_device()
     t = _range_flags.get(key)
     if t is None:
         t = _range_flags[key] = torch.zeros(1, dtype=torch.int32, device=device)
@@ -435,20 +435,11 @@ def scale_pack_weight(w_oihw, gate, dtype):
     return out, Cout * Cin * out.element_size()
 
 
-def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
-           res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
-           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0):
-    """Grouped implicit-GEMM conv: xs/ys (and optional zs/res) are lists of Map, one per pyramid level.
-    split=True (EFFDET_F32_SPLIT): xs hold the split layout ([32 x bf16 hi | 32 x bf16 lo] per 32 channels, 4 B per element), wp
-    is packed for bf16x3; ys are written split too unless out_f32 (then plain fp32; res, if any, is plain and ADDed).
-    ysplit (exact-fp32 and f16x3 convs only): Maps addressed like ys that receive the output a second time in the split layout.
-    hsplit=True (EFFDET_F32_HSPLIT, the f16x3 forward arithmetic): xs hold the H-split layout ([32 x f16 hi | 32 x f16 lo * 2^11] per 32
-    channels), wp = pack_weight(..., h3=True); ys are written H-split too unless out_f32; no scale / res / rowscale.
-    seg_w / seg_shift (lists, one entry per map, None = wp / shift): the maps are INDEPENDENT convs of one geometry with their own packed
-    weights / bias rows -- the same layer of the head's two towers in one launch (<= 10 maps).  Same values as separate launches.
-    live (uint8 tensor, one byte per 128-pixel tile from tile live_tile0 on: live_tiles()[1][r]): a 0 marks a tile whose every input
-    tap is zero; the split-layout kernels without bias / affine / activation skip it (zeros out, or nothing under an in-place RES_ADD),
-    every other launch ignores the flags.  Same values as without, but 0 where the dense launch would give 0 * Inf = NaN."""
+def _conv_desc(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
+               res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
+               w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0):
+    """The effdet_conv_t of a conv2d(...) call -> (descriptor, xs, ys as lists).  The one place it is built: conv2d launches from it and
+    conv2d_plan_info asks the planner about it, so the query describes the launch conv2d makes."""
     if isinstance(xs, Map):
         xs, ys = [xs], [ys]
         zs = [zs] if zs is not None else None
@@ -492,14 +483,38 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     d.act, d.res_mode = act, res_mode
     d.w_image_stride = int(w_image_stride)       # bytes; image b reads its own packed weights (scale_pack_weight)
     _segs(d, xs, ys, base_x, base_y, isx, isy)
+    if live is not None:
+        assert live.dtype == torch.uint8 and live.is_contiguous()
+        ntile = sum((y.B * y.H * y.W + 127) // 128 for y in ys)
+        assert 0 <= live_tile0 <= ntile and live.numel() == ntile - live_tile0, (live.numel(), ntile, live_tile0)
+    return d, xs, ys
+
+
+def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
+           res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
+           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0):
+    """Grouped implicit-GEMM conv: xs/ys (and optional zs/res) are lists of Map, one per pyramid level.
+    split=True (EFFDET_F32_SPLIT): xs hold the split layout ([32 x bf16 hi | 32 x bf16 lo] per 32 channels, 4 B per element), wp
+    is packed for bf16x3; ys are written split too unless out_f32 (then plain fp32; res, if any, is plain and ADDed).
+    ysplit (exact-fp32 and f16x3 convs only): Maps addressed like ys that receive the output a second time in the split layout.
+    hsplit=True (EFFDET_F32_HSPLIT, the f16x3 forward arithmetic): xs hold the H-split layout ([32 x f16 hi | 32 x f16 lo * 2^11] per 32
+    channels), wp = pack_weight(..., h3=True); ys are written H-split too unless out_f32; no scale / res / rowscale.
+    seg_w / seg_shift (lists, one entry per map, None = wp / shift): the maps are INDEPENDENT convs of one geometry with their own packed
+    weights / bias rows -- the same layer of the head's two towers in one launch (<= 10 maps).  Same values as separate launches.
+    live (uint8 tensor, one byte per 128-pixel tile from tile live_tile0 on: live_tiles()[1][r]): a 0 marks a tile whose every input
+    tap is zero; the split-layout kernels without bias / affine / activation skip it (zeros out, or nothing under an in-place RES_ADD),
+    every other launch ignores the flags.  Same values as without, but 0 where the dense launch would give 0 * Inf = NaN."""
+    d, xs, ys = _conv_desc(xs, wp, ys, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad_t=pad_t, pad_l=pad_l, scale=scale, shift=shift,
+                           act=act, res=res, res_mode=res_mode, rowscale=rowscale, zs=zs, out_f32=out_f32, split=split, bc_scale=bc_scale,
+                           bc_shift=bc_shift, w_image_stride=w_image_stride, ysplit=ysplit, hsplit=hsplit, seg_w=seg_w, seg_shift=seg_shift,
+                           live=live, live_tile0=live_tile0)
+    x0, y0 = xs[0], ys[0]
+    isx, isy = x0.t.element_size(), y0.t.element_size()
     flops = 2.0 * KH * KW * Cin * Cout * sum(y.B * y.H * y.W for y in ys)
     # algorithmic bytes: the input map, the packed weights, every output stream (y, the pre-activation copy, the split copy), the residual
     nbytes = isx * Cin * sum(x.B * x.H * x.W for x in xs) + wp.numel() * wp.element_size() + \
         (4 if out_f32 else isy) * Cout * sum(y.B * y.H * y.W for y in ys) * (1 + (zs is not None) + (ysplit is not None) + (res is not None))
     if live is not None:
-        assert live.dtype == torch.uint8 and live.is_contiguous()
-        ntile = sum((y.B * y.H * y.W + 127) // 128 for y in ys)
-        assert 0 <= live_tile0 <= ntile and live.numel() == ntile - live_tile0, (live.numel(), ntile, live_tile0)
         run = lambda: L.check(L.require('effdet_conv2d_live').effdet_conv2d_live(C.byref(d), live.data_ptr(), int(live_tile0), L.stream_ptr()),
                               'effdet_conv2d_live')
     else:
@@ -507,6 +522,22 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     # (flops stay those of the dense launch: a flagged launch reports an EFFECTIVE rate)
     _timed(_igemm_symbol(x0.dtype, d) if PROFILE is not None else '', flops, run,
            'k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, sum(y.B * y.H * y.W for y in ys)), nbytes=float(nbytes))
+
+
+def conv2d_plan_info(xs, wp, ys, **kw):
+    """What conv2d(xs, wp, ys, **kw) would launch, asked of the library's own planner without device work (effdet_conv2d_plan_info) on the
+    descriptor conv2d builds (_conv_desc; the tensors only lend their addresses and may live on the host) -> dict of id, form ('plain',
+    'bf16x3', 'split', 'hsplit', 'skinny'), persistent, tile_m, tile_n, stages, threads, mtiles, ntiles, grid (a persistent kernel: its
+    tile count before the cap at the device's compute units), ksteps, kord, lds_bytes, m32.  Raises where conv2d would."""
+    d, _, _ = _conv_desc(xs, wp, ys, **kw)
+    info = L.ConvPlanInfo()
+    rc = int(L.require('effdet_conv2d_plan_info').effdet_conv2d_plan_info(C.byref(d), C.byref(info)))
+    if rc < 0:
+        L.check(rc, 'effdet_conv2d_plan_info')
+    out = {n: int(getattr(info, n)) for n, _ in L.ConvPlanInfo._fields_ if n != 'reserved'}
+    out['form'] = L.CONV_FORMS[out['form']]
+    out['persistent'], out['m32'] = bool(out['persistent']), bool(out['m32'])
+    return out
 
 
 def _wgrad_desc(xs, dzs, dw, dbias, Cin, Cout, KH, KW, stride, pad_t, pad_l, want_bias, split, image_splits):

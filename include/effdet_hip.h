@@ -128,7 +128,8 @@ int effdet_scale_pack_weight(const float* w, const float* gate, void* out, int d
  *   20         the skinny pointwise fp32 kernel (1x1, Cin 16 or 24)
  *   10 + v     the persistent big-tile bf16 variant v = 442 | 242 | 243 | 423, or 4220 / 4230 (the <= 128-channel forms of 442 and
  *              242 / of 243)
- *   10000 + 442  the persistent 256 x 256 form of EFFDET_F32_SPLIT */
+ *   10000 + 442  the persistent 256 x 256 form of EFFDET_F32_SPLIT
+ * (An id names a kernel, not a template instance: effdet_conv2d_plan_info of effdet_conv_plan.h reports tile, stages, tiles and K-steps.) */
 int effdet_conv2d_kernel(const effdet_conv_t* p);
 
 /* Kernel-selection knobs (speed only -- every setting computes the same values; process-wide, meant for A/B runs and
