@@ -1,19 +1,33 @@
-// Focal + smooth-L1 detection loss on device (reference models/losses.py:32-152), batched over the
-// images with no host loop and no device->host sync.
+// Focal + box-regression detection loss on device (reference models/losses.py:32-152), batched over the images with no host loop
+// and no device->host sync.  ONE family of kernels serves the reference's constants, the IoU-family box terms
+// (include/effdet_box_loss.h) and the loss options (include/effdet_loss_opts.h); what differs is a compile-time policy:
 //
-//   kernel 1 (assign): one thread per (image, anchor): IoU against the image's valid annotations
-//            (pad rows label == -1 skipped), max / first-argmax, state = positive (IoU >= 0.5) /
-//            negative (< 0.4) / ignored, smooth-L1 on the positives; stat[b] = {cls_sum, reg_sum, num_pos,
-//            num_valid_annotations} (one 128-byte line per image).  num_pos is an INTEGER count (int atomics: exact whatever
-//            the order); the smooth-L1 partial of every workgroup goes to its own slot part_reg[b][block].
-//   kernel 2 (cls):    one thread per 4 class probabilities (16-byte loads): focal BCE with the
-//            reference's clamp to [1e-4, 1-1e-4], one partial per workgroup in part_cls[b][block].
-//   kernel 3 (final):  adds every image's partials in a fixed pattern (one wave per image), then
-//            losses[0] = mean_b cls_sum/max(npos,1), losses[1] = mean_b reg_sum/(4*npos).
+//   focal policy  FocalDefault: alpha 0.25, gamma 2 as q * q, __logf, contraction left to the compiler (the reference's constants)
+//                 FocalP:       alpha / gamma / label smoothing as launch arguments, exp2f(gamma log2f(u)), no contraction
+//   knee policy   KneeDefault:  the smooth-L1 knee 1/9 with the literals 0.5f * 9.0f, 0.5f / 9.0f, 9.0f spelled out
+//                 KneeBeta:     the knee beta as a launch argument (0.5 d^2 / beta, d - 0.5 beta, diff / beta)
+//   The default path is NOT the option kernels with default values: its arithmetic (and its single assign pass) stays as it was.
+//
+//   assign   one thread per (image, anchor): IoU against the image's valid annotations (pad rows label == -1 skipped), max /
+//            first-argmax, state = positive / negative / ignored, smooth-L1 on the positives; stat[b] = {cls_sum, reg_sum, num_pos,
+//            num_valid_annotations} (one 128-byte line per image).  num_pos is an INTEGER count (int atomics: exact whatever the
+//            order); the smooth-L1 partial of every workgroup goes to its own slot part_reg[b][block].
+//              loss_assign_kernel                    bands 0.5 / 0.4 as constants, IoU loop and tail in one pass
+//              opts_iou_kernel, opts_assign_kernel   the IoU loop -> best[b][a], barg[b][a]; with low_quality also gtmax[b][n] = max
+//                       over the anchors, as an INTEGER atomicMax on the bit pattern of the non-negative IoU (order-independent,
+//                       exact), first per workgroup in LDS, then one global atomic per (workgroup, row).  Then the same grid: bands
+//                       on best; with low_quality the IoU loop once more, promoting an anchor whose IoU with any row equals that
+//                       row's gtmax (> 0); then the same tail (assign_tail)
+//   cls      loss_cls_kernel<F>: one thread per 4 class probabilities (16-byte loads): focal BCE with the reference's clamp to
+//            [1e-4, 1-1e-4], one partial per workgroup in part_cls[b][block].  loss_cls_pix_kernel<T, F, GRAD_ONLY, IT>: the same
+//            sum AND d/d(logit) in one pass, or the gradient alone, written pixel-major (see there)
+//   final    loss_final_kernel: adds every image's partials in a fixed pattern (one wave per image), then
+//            losses[0] = mean_b cls_sum/max(npos,1), losses[1] = reg_weight * mean_b reg_sum/(4*npos)
+//   backward loss_bwd_cls_kernel<T, F> / loss_cls_pix_kernel<T, F, true, 1>: d/d(logit) of the class term (through clamp and
+//            sigmoid); loss_bwd_reg_kernel<T, Knee>: d/d(reg); scaled by the upstream scalar grads, written in the activation
+//            dtype that the head's data-gradient convs consume
+//   box_*    an IoU-family box term over the same assignment, in place of smooth-L1 (second half of the file)
 //   No float atomics on anything but exact integer counts: two runs give bitwise-equal losses.
-//   backward: d/d(logit) of the class term (through clamp and sigmoid) and d/d(reg), scaled by
-//            the upstream scalar grads, written in the activation dtype that the head's
-//            data-gradient convs consume.
 // HBM-bound: reads cls once per pass (15.7 MB / image fp32 at 80 classes).
 #include "common.h"
 #include "../../../include/effdet_box_loss.h"
@@ -21,9 +35,9 @@
 
 namespace {
 
-constexpr float ALPHA = 0.25f;
 constexpr int SS = 32;        // floats per image in stat[] (one cache line)
 constexpr int CLS_IT = 8;     // 4-element groups per thread in the class pass (fewer blocks -> fewer atomics)
+constexpr int FG_IT = 4;      // ... in the forward+gradient pass: keeps the per-workgroup partials (summed by loss_final_kernel) few
 
 struct LossK {
   const float* cls; const float* reg; const float* anchors; const float* annots; const float* gscale;
@@ -35,63 +49,137 @@ struct LossK {
   int reg_ld;        // channel pitch of a pixel-major dreg layout [B][A/9][reg_ld] (channel = anchor*4 + k, zeros beyond 36); 0 = [B][A][4]
 };
 
+// the matcher of the options path: bands, low-quality matches and the buffers between its two passes
+struct OptsK {
+  float pos_iou, neg_iou; int low_quality;
+  int* gtmax; float* best; int* barg;         // [B][N] bit patterns, [B][A], [B][A]
+};
+
 // stat[b][2] holds the number of positive anchors as an int32 bit pattern (integer atomics: exact, order-independent)
 __device__ __forceinline__ float npos(const float* st) { return (float)__float_as_int(st[2]); }
 
-__global__ __launch_bounds__(256) void loss_assign_kernel(const LossK p) {
-  const int b = blockIdx.y;
-  const long long a = blockIdx.x * 256LL + threadIdx.x;
-  __shared__ float ann[64 * 5];
-  __shared__ int nvalid_s;
-  __shared__ float red[2][4];
-  // compact this image's valid annotations into LDS (order preserved), in chunks of 64
-  float best = -1.0f; int barg = -1;
-  float4 an = make_float4(0, 0, 0, 0);
-  const bool ok = a < p.A;
-  if (ok) an = ((const float4*)p.anchors)[a];
-  const float aarea = (an.z - an.x) * (an.w - an.y);
-  int total_valid = 0;
-  for (int n0 = 0; n0 < p.N; n0 += 64) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int c = 0;
-      for (int n = n0; n < min(p.N, n0 + 64); ++n) {
-        const float* r = p.annots + ((long long)b * p.N + n) * 5;
-        if (r[4] != -1.0f) { for (int q = 0; q < 5; ++q) ann[c * 5 + q] = r[q]; ann[c * 5 + 4] = (float)n; ++c; }
-      }
-      nvalid_s = c;
+// d(loss)/d(logit) where the class term does not reach p (ignored anchor, image without annotations): 0 -- but NaN for a NaN (or inf)
+// p, because autograd's sigmoid backward still multiplies that zero by p (1 - p) (models/losses.py:53-57, :96)
+__device__ __forceinline__ float nan_zero(float p) { return p - p; }
+
+__device__ __forceinline__ int label_of(const LossK& p, int b, int code) {
+  return code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
+}
+
+// ---- focal policies: f(praw, target_one, dldp) -> the per-element focal term; dldp its derivative wrt the (unclamped) probability
+struct FocalDefault {
+  __device__ __forceinline__ float operator()(float praw, bool target_one, float& dldp) const {
+    constexpr float ALPHA = 0.25f;
+    const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);         // (torch.clamp keeps a NaN: so does the loss)
+    const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);   // clamp passes the gradient inside the range
+    float l, d;
+    if (target_one) {
+      const float q = 1.f - pc, lg = __logf(pc);
+      l = -ALPHA * q * q * lg;
+      d = ALPHA * (2.f * q * lg - q * q / pc);
+    } else {
+      const float lg = __logf(1.f - pc);
+      l = -(1.f - ALPHA) * pc * pc * lg;
+      d = (1.f - ALPHA) * (pc * pc / (1.f - pc) - 2.f * pc * lg);
     }
-    __syncthreads();
-    const int c = nvalid_s;
-    total_valid += c;
-    if (ok) {
-      for (int j = 0; j < c; ++j) {
-        const float bx1 = ann[j * 5], by1 = ann[j * 5 + 1], bx2 = ann[j * 5 + 2], by2 = ann[j * 5 + 3];
-        const float barea = (bx2 - bx1) * (by2 - by1);
-        float iw = fminf(an.z, bx2) - fmaxf(an.x, bx1); float ih = fminf(an.w, by2) - fmaxf(an.y, by1);
-        iw = fmaxf(iw, 0.f); ih = fmaxf(ih, 0.f);
-        const float ua = fmaxf(aarea + barea - iw * ih, 1e-8f);
-        const float iou = iw * ih / ua;
-        if (iou > best) { best = iou; barg = (int)ann[j * 5 + 4]; }     // strict > keeps the FIRST max
-      }
-    }
+    dldp = pass ? d : 0.f;
+    return l;
   }
+};
+
+// (no contraction: every kernel and layout computes the same bits)
+struct FocalP {
+  float alpha, gamma, eps;
+  __device__ __forceinline__ float operator()(float praw, bool target_one, float& dldp) const {
+#pragma clang fp contract(off)
+    const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);
+    const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);
+    const float h = target_one ? 1.f : 0.f;
+    const float t = h * (1.f - eps) + 0.5f * eps;
+    const float u = target_one ? 1.f - pc : pc, aw = target_one ? alpha : 1.f - alpha;
+    const float pw = exp2f(gamma * log2f(u));
+    const float ce = -(t * logf(pc) + (1.f - t) * logf(1.f - pc));
+    const float dce = (1.f - t) / (1.f - pc) - t / pc;
+    const float dpw = gamma * pw / u;                                 // d pw / d u; du / dp = -1 for a target of one
+    dldp = pass ? aw * ((target_one ? -dpw : dpw) * ce + pw * dce) : 0.f;
+    return aw * pw * ce;
+  }
+};
+
+// ---- knee policies of smooth-L1 on d = |diff|: the term, and its derivative wrt diff (sgn = sign(diff)).
+// (0 * d: autograd of the reference's where(d <= 1/9, 4.5 d^2, d - 1/18) sends 0 * 9d into the branch not taken -- NaN when d is
+//  NaN or inf, and the gradient with it)
+struct KneeDefault {
+  __device__ __forceinline__ float term(float d) const { return (d <= 1.0f / 9.0f) ? 0.5f * 9.0f * d * d : d - 0.5f / 9.0f; }
+  __device__ __forceinline__ float grad(float diff, float d, float sgn) const { return (d <= 1.0f / 9.0f) ? 9.0f * d * sgn : sgn + 0.f * d; }
+};
+struct KneeBeta {
+  float beta;
+  __device__ __forceinline__ float term(float d) const { return (d <= beta) ? 0.5f * d * d / beta : d - 0.5f * beta; }
+  __device__ __forceinline__ float grad(float diff, float d, float sgn) const { return (d <= beta) ? diff / beta : sgn + 0.f * d; }
+};
+
+// ---- shared device functions
+// the sum of s over the workgroup (4 waves) -> *out, by thread 0, in a fixed association order (part of the bitwise-determinism contract)
+__device__ __forceinline__ void block_partial(float s, float* out) {
+  __shared__ float red[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// IoU of anchor `an` (area aarea) with the box at r[0..3].  Every pass of either matcher evaluates THIS function, so the equality test
+// of the promotion pass compares a value with a maximum over the same values (no contraction: whether a multiply-add is fused must not
+// depend on the kernel the function is inlined into)
+__device__ __forceinline__ float assign_iou(const float4 an, const float aarea, const float* r) {
+#pragma clang fp contract(off)
+  const float bx1 = r[0], by1 = r[1], bx2 = r[2], by2 = r[3];
+  const float barea = (bx2 - bx1) * (by2 - by1);
+  float iw = fminf(an.z, bx2) - fmaxf(an.x, bx1); float ih = fminf(an.w, by2) - fmaxf(an.y, by1);
+  iw = fmaxf(iw, 0.f); ih = fmaxf(ih, 0.f);
+  const float ua = fmaxf(aarea + barea - iw * ih, 1e-8f);
+  const float iou = iw * ih / ua;
+  return iou;
+}
+
+// thread 0 compacts the valid rows of chunk [n0, n0 + 64) of image b into ann[] (order preserved; ann[c][4] = the row index) -> their number
+__device__ __forceinline__ int compact_chunk(const LossK& p, int b, int n0, float* ann) {
+  int c = 0;
+  for (int n = n0; n < min(p.N, n0 + 64); ++n) {
+    const float* r = p.annots + ((long long)b * p.N + n) * 5;
+    if (r[4] != -1.0f) { for (int q = 0; q < 5; ++q) ann[c * 5 + q] = r[q]; ann[c * 5 + 4] = (float)n; ++c; }
+  }
+  return c;
+}
+
+// the regression target of anchor `an` for the annotation at g[0..3] (models/losses.py:119-137)
+__device__ __forceinline__ void encode_target(const float4 an, const float* g, float* t) {
+  const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
+  float gw = g[2] - g[0], gh = g[3] - g[1];
+  const float gcx = g[0] + 0.5f * gw, gcy = g[1] + 0.5f * gh;
+  gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
+  t[0] = (gcx - acx) / aw / 0.1f; t[1] = (gcy - acy) / ah / 0.1f; t[2] = logf(gw / aw) / 0.2f; t[3] = logf(gh / ah) / 0.2f;
+}
+
+// the end of an assign pass.  live: a valid anchor of an image with annotations; negative / positive: the band decisions on its best
+// IoU (two ifs, not else-if: with neg_iou == pos_iou the second wins).  -> assign[], the workgroup's smooth-L1 partial, num_pos
+template <typename Knee>
+__device__ __forceinline__ void assign_tail(const LossK& p, int b, long long a, bool ok, bool live, bool negative, bool positive,
+                                            int barg, const float4 an, const Knee knee) {
+  __shared__ float red[2][4];
   float regl = 0.f, pos = 0.f;
   int code = -2;                       // -2 ignore, -1 negative, >= 0 positive (annotation row)
-  if (ok && total_valid > 0) {
-    if (best < 0.4f) code = -1;
-    if (best >= 0.5f) {
+  if (live) {
+    if (negative) code = -1;
+    if (positive) {
       code = barg; pos = 1.f;
-      const float* g = p.annots + ((long long)b * p.N + barg) * 5;
-      const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
-      float gw = g[2] - g[0], gh = g[3] - g[1];
-      const float gcx = g[0] + 0.5f * gw, gcy = g[1] + 0.5f * gh;
-      gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
-      const float t[4] = {(gcx - acx) / aw / 0.1f, (gcy - acy) / ah / 0.1f, logf(gw / aw) / 0.2f, logf(gh / ah) / 0.2f};
+      float t[4];
+      encode_target(an, p.annots + ((long long)b * p.N + barg) * 5, t);
       const float4 r = ((const float4*)p.reg)[(long long)b * p.A + a];
       const float rv[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { const float d = fabsf(t[q] - rv[q]); regl += (d <= 1.0f / 9.0f) ? 0.5f * 9.0f * d * d : d - 0.5f / 9.0f; }
+      for (int q = 0; q < 4; ++q) regl += knee.term(fabsf(t[q] - rv[q]));
     }
   }
   if (ok) p.assign[(long long)b * p.A + a] = code;
@@ -102,35 +190,141 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const LossK p) {
   if (threadIdx.x == 0) {
     p.part_reg[(long long)b * p.na + blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
     atomicAdd((int*)(p.stat + b * SS + 2), (int)(red[1][0] + red[1][1] + red[1][2] + red[1][3]));    // num_pos is kept as an INTEGER (npos())
-    if (blockIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
   }
 }
 
-// d(loss)/d(logit) where the class term does not reach p (ignored anchor, image without annotations): 0 -- but NaN for a NaN (or inf)
-// p, because autograd's sigmoid backward still multiplies that zero by p (1 - p) (models/losses.py:53-57, :96)
-__device__ __forceinline__ float nan_zero(float p) { return p - p; }
-
-// per-element focal term and its derivative wrt the (unclamped) probability p
-__device__ __forceinline__ float focal_elem(float praw, bool target_one, float& dldp) {
-  const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);         // (torch.clamp keeps a NaN: so does the loss)
-  const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);   // clamp passes the gradient inside the range
-  float l, d;
-  if (target_one) {
-    const float q = 1.f - pc, lg = __logf(pc);
-    l = -ALPHA * q * q * lg;
-    d = ALPHA * (2.f * q * lg - q * q / pc);
+// d(reg) of anchor a of image b (i = b * A + a) -> [B][A][4], or with reg_ld the pixel-major rows with a padded pitch (the layout the
+// head's data-gradient conv reads; pad channels zeroed here)
+template <typename T>
+__device__ __forceinline__ void store_dreg_row(const LossK& p, long long b, long long a, long long i, f32x4 g) {
+  if (p.reg_ld) {
+    const long long pix = a / 9; const int an = (int)(a - pix * 9);
+    T* row = (T*)p.dreg + (b * (p.A / 9) + pix) * p.reg_ld;
+    store4(row + an * 4, g);
+    if (an == 8) for (int c = 36; c < p.reg_ld; c += 4) store4(row + c, f32x4{0.f, 0.f, 0.f, 0.f});
   } else {
-    const float lg = __logf(1.f - pc);
-    l = -(1.f - ALPHA) * pc * pc * lg;
-    d = (1.f - ALPHA) * (pc * pc / (1.f - pc) - 2.f * pc * lg);
+    store4((T*)p.dreg + i * 4, g);
   }
-  dldp = pass ? d : 0.f;
-  return l;
 }
 
-__global__ __launch_bounds__(256) void loss_cls_kernel(const LossK p) {
-  // 32-bit index arithmetic (A*nc < 2^31 is checked by the host): the 64-bit divisions per element of the first
-  // version made this HBM pass ALU-bound.  When nc % 4 == 0 a 4-element group never straddles two anchors.
+// ---- kernels
+// stat[] starts every pass at zero (num_pos is an integer atomic count).  A KERNEL, not hipMemsetAsync: captured into a hipGraph the
+// memset node did not hold -- replays of the captured train step ran the assign pass on whatever the recycled workspace contained
+// (num_pos ~ 1e9 from a float bit pattern: losses and every gradient scaled by ~1e-7; found in round 5 by comparing one replay with one
+// eager step from the same state).  Kernel nodes only, like the NMS (postprocess.hip).
+__global__ __launch_bounds__(256) void loss_zero_stat_kernel(float* __restrict__ stat, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) stat[i] = 0.f;
+}
+
+// ... and gtmax[] with it on the options path
+__global__ __launch_bounds__(256) void opts_zero_kernel(float* __restrict__ stat, int n, int* __restrict__ gtmax, int m) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) stat[i] = 0.f;
+  else if (i - n < m) gtmax[i - n] = 0;
+}
+
+__global__ __launch_bounds__(256) void loss_assign_kernel(const LossK p) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  __shared__ float ann[64 * 5];
+  __shared__ int nvalid_s;
+  float best = -1.0f; int barg = -1;
+  float4 an = make_float4(0, 0, 0, 0);
+  const bool ok = a < p.A;
+  if (ok) an = ((const float4*)p.anchors)[a];
+  const float aarea = (an.z - an.x) * (an.w - an.y);
+  int total_valid = 0;
+  for (int n0 = 0; n0 < p.N; n0 += 64) {       // the image's valid annotations through LDS, in chunks of 64
+    __syncthreads();
+    if (threadIdx.x == 0) nvalid_s = compact_chunk(p, b, n0, ann);
+    __syncthreads();
+    const int c = nvalid_s;
+    total_valid += c;
+    if (ok) {
+      for (int j = 0; j < c; ++j) {
+        const float iou = assign_iou(an, aarea, ann + j * 5);
+        if (iou > best) { best = iou; barg = (int)ann[j * 5 + 4]; }     // strict > keeps the FIRST max
+      }
+    }
+  }
+  assign_tail(p, b, a, ok, ok && total_valid > 0, best < 0.4f, best >= 0.5f, barg, an, KneeDefault{});
+  if (blockIdx.x == 0 && threadIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
+}
+
+__global__ __launch_bounds__(256) void opts_iou_kernel(const LossK p, const OptsK o) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  __shared__ float ann[64 * 5];
+  __shared__ int gm[64];
+  __shared__ int nvalid_s;
+  float best = -1.0f; int barg = -1;
+  float4 an = make_float4(0, 0, 0, 0);
+  const bool ok = a < p.A;
+  if (ok) an = ((const float4*)p.anchors)[a];
+  const float aarea = (an.z - an.x) * (an.w - an.y);
+  int total_valid = 0;
+  for (int n0 = 0; n0 < p.N; n0 += 64) {
+    __syncthreads();
+    if (threadIdx.x == 0) nvalid_s = compact_chunk(p, b, n0, ann);
+    if (threadIdx.x < 64) gm[threadIdx.x] = 0;
+    __syncthreads();
+    const int c = nvalid_s;
+    total_valid += c;
+    if (ok) {
+      for (int j = 0; j < c; ++j) {
+        const float iou = assign_iou(an, aarea, ann + j * 5);
+        if (iou > best) { best = iou; barg = (int)ann[j * 5 + 4]; }     // (the first max, as above)
+        if (o.low_quality && iou > 0.f && __float_as_int(iou) > *(volatile int*)&gm[j]) atomicMax(&gm[j], __float_as_int(iou));
+      }
+    }
+    if (o.low_quality) {
+      __syncthreads();
+      if ((int)threadIdx.x < c && gm[threadIdx.x] > 0) atomicMax(o.gtmax + (long long)b * p.N + (int)ann[threadIdx.x * 5 + 4], gm[threadIdx.x]);
+    }
+  }
+  if (ok) { o.best[(long long)b * p.A + a] = best; o.barg[(long long)b * p.A + a] = barg; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
+}
+
+__global__ __launch_bounds__(256) void opts_assign_kernel(const LossK p, const OptsK o, const KneeBeta knee) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  __shared__ float ann[64 * 5];
+  __shared__ float gmf[64];
+  __shared__ int nvalid_s;
+  const bool ok = a < p.A;
+  float4 an = make_float4(0, 0, 0, 0);
+  float best = -1.0f; int barg = -1;
+  if (ok) { an = ((const float4*)p.anchors)[a]; best = o.best[(long long)b * p.A + a]; barg = o.barg[(long long)b * p.A + a]; }
+  const bool any_valid = p.stat[b * SS + 3] > 0.f;
+  bool promoted = false;
+  if (o.low_quality && any_valid) {
+    const float aarea = (an.z - an.x) * (an.w - an.y);
+    for (int n0 = 0; n0 < p.N; n0 += 64) {
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const int c = compact_chunk(p, b, n0, ann);
+        for (int j = 0; j < c; ++j) gmf[j] = __int_as_float(o.gtmax[(long long)b * p.N + (int)ann[j * 5 + 4]]);
+        nvalid_s = c;
+      }
+      __syncthreads();
+      const int c = nvalid_s;
+      if (ok) {
+        for (int j = 0; j < c; ++j) {
+          const float iou = assign_iou(an, aarea, ann + j * 5);
+          promoted = promoted || (iou == gmf[j] && gmf[j] > 0.f);
+        }
+      }
+    }
+  }
+  assign_tail(p, b, a, ok, ok && any_valid, best < o.neg_iou, (best >= o.pos_iou || promoted) && barg >= 0, barg, an, knee);
+}
+
+// 32-bit index arithmetic (A*nc < 2^31 is checked by the host): the 64-bit divisions per element of the first version made this HBM
+// pass ALU-bound.  When nc % 4 == 0 a 4-element group never straddles two anchors.
+template <typename F>
+__global__ __launch_bounds__(256) void loss_cls_kernel(const LossK p, const F f) {
   const int b = blockIdx.y;
   const int per = (int)(p.A * p.nc);
   float s = 0.f;
@@ -147,22 +341,95 @@ __global__ __launch_bounds__(256) void loss_cls_kernel(const LossK p) {
       else for (int q = 0; q < cnt; ++q) v[q] = c[e0 + q];
       int a = e0 / p.nc, k = e0 - a * p.nc;
       int code = asg[a];
-      int lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
+      int lab = label_of(p, b, code);
       for (int q = 0; q < cnt; ++q) {
-        if (code != -2) { float d; s += focal_elem(v[q], lab == k, d); }
-        if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1; }
+        if (code != -2) { float d; s += f(v[q], lab == k, d); }
+        if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
       }
     }
   }
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) p.part_cls[(long long)b * p.ncb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  block_partial(s, p.part_cls + (long long)b * p.ncb + blockIdx.x);
+}
+
+template <typename T, typename F>
+__global__ __launch_bounds__(256) void loss_bwd_cls_kernel(const LossK p, const F f) {
+  const int b = blockIdx.y;
+  const int per = (int)(p.A * p.nc);
+  const int e0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (e0 >= per) return;
+  const float* st = p.stat + b * SS;
+  const bool active = st[3] > 0.f;
+  const float gs = active ? p.gscale[0] / ((float)p.B * fmaxf(npos(st), 1.0f)) : 0.f;
+  const float* c = p.cls + (long long)b * per;
+  const int* asg = p.assign + (long long)b * p.A;
+  T* out = (T*)p.dcls + (long long)b * per;
+  const int cnt = min(4, per - e0);
+  const bool vec = cnt == 4 && ((per & 3) == 0);
+  float v[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
+  if (vec) { const f32x4 t = *(const f32x4*)(c + e0); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+  else for (int q = 0; q < cnt; ++q) v[q] = c[e0 + q];
+  int a = e0 / p.nc, k = e0 - a * p.nc;
+  int code = asg[a];
+  int lab = label_of(p, b, code);
+  for (int q = 0; q < cnt; ++q) {
+    if (active && code != -2) {
+      float d; (void)f(v[q], lab == k, d);
+      g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
+    } else {
+      g[q] = nan_zero(v[q]);
+    }
+    if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
+  }
+  if (vec) store4(out + e0, f32x4{g[0], g[1], g[2], g[3]});
+  else for (int q = 0; q < cnt; ++q) Elem<T>::st(out + e0 + q, g[q]);
+}
+
+// The class gradient written PIXEL-major with a padded channel pitch: dcls[b][pixel][dld], channel = anchor*nc + class,
+// zeros in [9*nc, dld).  That is the layout the head's data-gradient conv reads as its input rows: with dld a multiple
+// of 64 every 128-byte K-slice of a row is one aligned cache line (the natural 720-channel pitch = 1440 B straddles two
+// lines for 3 pixels out of 4, and that conv is bound by its L2->LDS path).  Requires nc % 4 == 0.  IT 4-element groups per thread.
+//   GRAD_ONLY:  backward -- the upstream gradient gscale[0] applied, no partial
+//   otherwise:  forward AND gradient in ONE pass over cls (training): the focal sum goes to part_cls as in loss_cls_kernel, and the
+//               gradient is written for an upstream gradient of 1.  The upstream scalar is applied downstream (it multiplies a LINEAR
+//               chain: the head's data-gradient conv takes it as its per-image output scale, the retina_cls parameter gradients are
+//               scaled after unpacking), so backward never re-reads the 15.7 MB/image of probabilities.
+template <typename T, typename F, bool GRAD_ONLY, int IT>
+__global__ __launch_bounds__(256) void loss_cls_pix_kernel(const LossK p, const F f) {
+  const int b = blockIdx.y;
+  const int apix = (int)(p.A / 9), perp = apix * p.dld, cmax = 9 * p.nc;
+  const float* st = p.stat + b * SS;
+  const bool active = st[3] > 0.f;
+  const float gs = (GRAD_ONLY ? p.gscale[0] : 1.0f) / ((float)p.B * fmaxf(npos(st), 1.0f));
+  float s = 0.f;
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int e0 = ((blockIdx.x * IT + it) * 256 + threadIdx.x) * 4;
+    if (e0 >= perp) break;
+    const int pix = e0 / p.dld, ch = e0 - pix * p.dld;
+    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (ch < cmax) {
+      const int an = ch / p.nc, k = ch - an * p.nc, a = pix * 9 + an;
+      const int code = active ? p.assign[(long long)b * p.A + a] : -2;
+      const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
+      if (code != -2) {
+        const int lab = label_of(p, b, code);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float d; s += f(v[q], lab == k + q, d);
+          g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = nan_zero(v[q]);
+      }
+    }
+    store4((T*)p.dcls + (long long)b * perp + e0, g);
+  }
+  if constexpr (!GRAD_ONLY) block_partial(s, p.part_cls + (long long)b * p.ncb + blockIdx.x);
 }
 
 // one workgroup: wave w adds the partials of images w, w + 16, ... (lane-strided, then the fixed shuffle tree), thread 0 the images
-__global__ __launch_bounds__(1024) void loss_final_kernel(const LossK p) {
+__global__ __launch_bounds__(1024) void loss_final_kernel(const LossK p, const float reg_weight) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // fixed summation pattern (lane-strided with four chains in flight -- the loop is pure L2 latency -- then the shuffle tree)
   auto lane_sum = [&](const float* q, int n) {
@@ -186,123 +453,11 @@ __global__ __launch_bounds__(1024) void loss_final_kernel(const LossK p) {
       if (npos(s) > 0.f) rl += s[1] / (npos(s) * 4.0f);
     }
   }
-  p.losses[0] = cl / (float)p.B; p.losses[1] = rl / (float)p.B;
+  p.losses[0] = cl / (float)p.B; p.losses[1] = reg_weight * (rl / (float)p.B);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void loss_bwd_cls_kernel(const LossK p) {
-  const int b = blockIdx.y;
-  const int per = (int)(p.A * p.nc);
-  const int e0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (e0 >= per) return;
-  const float* st = p.stat + b * SS;
-  const bool active = st[3] > 0.f;
-  const float gs = active ? p.gscale[0] / ((float)p.B * fmaxf(npos(st), 1.0f)) : 0.f;
-  const float* c = p.cls + (long long)b * per;
-  const int* asg = p.assign + (long long)b * p.A;
-  T* out = (T*)p.dcls + (long long)b * per;
-  const int cnt = min(4, per - e0);
-  const bool vec = cnt == 4 && ((per & 3) == 0);
-  float v[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
-  if (vec) { const f32x4 t = *(const f32x4*)(c + e0); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
-  else for (int q = 0; q < cnt; ++q) v[q] = c[e0 + q];
-  int a = e0 / p.nc, k = e0 - a * p.nc;
-  int code = asg[a];
-  int lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
-  for (int q = 0; q < cnt; ++q) {
-    if (active && code != -2) {
-      float d; (void)focal_elem(v[q], lab == k, d);
-      g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
-    } else {
-      g[q] = nan_zero(v[q]);
-    }
-    if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1; }
-  }
-  if (vec) store4(out + e0, f32x4{g[0], g[1], g[2], g[3]});
-  else for (int q = 0; q < cnt; ++q) Elem<T>::st(out + e0 + q, g[q]);
-}
-
-// The same gradient written PIXEL-major with a padded channel pitch: dcls[b][pixel][dld], channel = anchor*nc + class,
-// zeros in [9*nc, dld).  That is the layout the head's data-gradient conv reads as its input rows: with dld a multiple
-// of 64 every 128-byte K-slice of a row is one aligned cache line (the natural 720-channel pitch = 1440 B straddles two
-// lines for 3 pixels out of 4, and that conv is bound by its L2->LDS path).  Requires nc % 4 == 0.
-template <typename T>
-__global__ __launch_bounds__(256) void loss_bwd_cls_pix_kernel(const LossK p) {
-  const int b = blockIdx.y;
-  const int apix = (int)(p.A / 9), perp = apix * p.dld, cmax = 9 * p.nc;
-  const int e0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (e0 >= perp) return;
-  const int pix = e0 / p.dld, ch = e0 - pix * p.dld;
-  T* out = (T*)p.dcls + (long long)b * perp + e0;
-  f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
-  const float* st = p.stat + b * SS;
-  if (ch < cmax) {
-    const int an = ch / p.nc, k = ch - an * p.nc, a = pix * 9 + an;
-    const int code = st[3] > 0.f ? p.assign[(long long)b * p.A + a] : -2;
-    const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
-    if (code != -2) {
-      const float gs = p.gscale[0] / ((float)p.B * fmaxf(npos(st), 1.0f));
-      const int lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float d; (void)focal_elem(v[q], lab == k + q, d);
-        g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[q] = nan_zero(v[q]);
-    }
-  }
-  store4(out, g);
-}
-
-// Forward AND gradient of the class term in ONE pass over cls (training): the focal sum goes to stat[b].cls_sum as in
-// loss_cls_kernel, and d(loss)/d(logit) for an upstream gradient of 1 is written in the pixel-major padded layout above.
-// The upstream scalar is applied downstream (it multiplies a LINEAR chain: the head's data-gradient conv takes it as its
-// per-image output scale, the retina_cls parameter gradients are scaled after unpacking), so backward never re-reads
-// the 15.7 MB/image of probabilities.  FG_IT 4-element groups per thread keep the per-workgroup partials (summed by loss_final_kernel) few.
-constexpr int FG_IT = 4;
-template <typename T>
-__global__ __launch_bounds__(256) void loss_cls_grad_pix_kernel(const LossK p) {
-  const int b = blockIdx.y;
-  const int apix = (int)(p.A / 9), perp = apix * p.dld, cmax = 9 * p.nc;
-  const float* st = p.stat + b * SS;
-  const bool active = st[3] > 0.f;
-  const float gs = 1.0f / ((float)p.B * fmaxf(npos(st), 1.0f));
-  float s = 0.f;
-#pragma unroll
-  for (int it = 0; it < FG_IT; ++it) {
-    const int e0 = ((blockIdx.x * FG_IT + it) * 256 + threadIdx.x) * 4;
-    if (e0 >= perp) break;
-    const int pix = e0 / p.dld, ch = e0 - pix * p.dld;
-    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (ch < cmax) {
-      const int an = ch / p.nc, k = ch - an * p.nc, a = pix * 9 + an;
-      const int code = active ? p.assign[(long long)b * p.A + a] : -2;
-      const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
-      if (code != -2) {
-        const int lab = code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float d; s += focal_elem(v[q], lab == k + q, d);
-          g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = nan_zero(v[q]);
-      }
-    }
-    store4((T*)p.dcls + (long long)b * perp + e0, g);
-  }
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) p.part_cls[(long long)b * p.ncb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-template <typename T>
-__global__ void loss_bwd_reg_kernel(const LossK p) {
+template <typename T, typename Knee>
+__global__ void loss_bwd_reg_kernel(const LossK p, const Knee knee, const float reg_weight) {
   const long long total = (long long)p.B * p.A;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long b = i / p.A, a = i - b * p.A;
@@ -310,189 +465,28 @@ __global__ void loss_bwd_reg_kernel(const LossK p) {
     const float* st = p.stat + b * SS;
     f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
     if (code >= 0 && st[3] > 0.f && npos(st) > 0.f) {
-      const float gs = p.gscale[1] / ((float)p.B * npos(st) * 4.0f);
-      const float4 an = ((const float4*)p.anchors)[a];
-      const float* gt = p.annots + (b * p.N + code) * 5;
-      const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
-      float gw = gt[2] - gt[0], gh = gt[3] - gt[1];
-      const float gcx = gt[0] + 0.5f * gw, gcy = gt[1] + 0.5f * gh;
-      gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
-      const float t[4] = {(gcx - acx) / aw / 0.1f, (gcy - acy) / ah / 0.1f, logf(gw / aw) / 0.2f, logf(gh / ah) / 0.2f};
+      const float gs = p.gscale[1] * reg_weight / ((float)p.B * npos(st) * 4.0f);
+      float t[4];
+      encode_target(((const float4*)p.anchors)[a], p.annots + (b * p.N + code) * 5, t);
       const float4 r = ((const float4*)p.reg)[i];
       const float rv[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float diff = rv[q] - t[q], d = fabsf(diff);
         const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-        // (0 * d: autograd of the reference's where(d <= 1/9, 4.5 d^2, d - 1/18) sends 0 * 9d into the branch not taken -- NaN when d is
-        //  NaN or inf, and the gradient with it)
-        g[q] = gs * ((d <= 1.0f / 9.0f) ? 9.0f * d * sgn : sgn + 0.f * d);
+        g[q] = gs * knee.grad(diff, d, sgn);
       }
     }
-    if (p.reg_ld) {       // pixel-major rows with a padded pitch (the layout the head's data-gradient conv reads; pad channels zeroed here)
-      const long long pix = a / 9; const int an = (int)(a - pix * 9);
-      T* row = (T*)p.dreg + (b * (p.A / 9) + pix) * p.reg_ld;
-      store4(row + an * 4, g);
-      if (an == 8) for (int c = 36; c < p.reg_ld; c += 4) store4(row + c, f32x4{0.f, 0.f, 0.f, 0.f});
-    } else {
-      store4((T*)p.dreg + i * 4, g);
-    }
+    store_dreg_row<T>(p, b, a, i, g);
   }
-}
-
-// stat[] starts every pass at zero (num_pos is an integer atomic count).  A KERNEL, not hipMemsetAsync: captured into a hipGraph the
-// memset node did not hold -- replays of the captured train step ran the assign pass on whatever the recycled workspace contained
-// (num_pos ~ 1e9 from a float bit pattern: losses and every gradient scaled by ~1e-7; found in round 5 by comparing one replay with one
-// eager step from the same state).  Kernel nodes only, like the NMS (postprocess.hip).
-__global__ __launch_bounds__(256) void loss_zero_stat_kernel(float* __restrict__ stat, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) stat[i] = 0.f;
-}
-inline void zero_stat(const LossK& k, int B, hipStream_t st) {
-  hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((B * SS + 255) / 256)), dim3(256), 0, st, k.stat, B * SS);
-}
-
-}  // namespace
-
-// workgroups per image of the assign pass / upper bound of the class pass (either kernel: dld <= 9*nc + 63)
-static inline long long assign_blocks(long long A) { return (A + 255) / 256; }
-static inline long long cls_blocks_max(long long A, int nc) { return ((A * nc + 3) / 4 + (A / 9 + 1) * 16 + 1023) / 1024 + 1; }
-
-// assign [B][A], stat [B][SS], part_reg [B][na], part_cls [B][cls_blocks_max] -> bytes (num_classes only sizes the last buffer)
-static size_t carve_loss(LossK& k, void* ws, int B, long long A, int num_classes = 0) {
-  Carver c(ws);
-  k.assign = c.take<int>((size_t)B * A);
-  k.stat = c.take<float>((size_t)B * SS);
-  k.part_reg = c.take<float>((size_t)B * assign_blocks(A));
-  k.part_cls = c.take<float>((size_t)B * cls_blocks_max(A, num_classes));
-  k.na = (int)assign_blocks(A);
-  return c.off;
-}
-
-extern "C" long long effdet_loss_workspace_bytes(int B, long long A, int num_classes) {
-  LossK k{};
-  return (long long)carve_loss(k, nullptr, B, A, num_classes);
-}
-
-extern "C" int effdet_focal_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots,
-                                     float* losses, void* workspace, long long workspace_bytes, int B, long long A,
-                                     int num_classes, int N, effdet_stream_t stream) {
-  if (!cls || !reg || !anchors || !annots || !losses || !workspace) return EFFDET_EINVAL;
-  if (workspace_bytes < effdet_loss_workspace_bytes(B, A, num_classes) || B > 65535 || N < 1) return EFFDET_EINVAL;
-  if (A * num_classes >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
-  LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.losses = losses;
-  k.B = B; k.nc = num_classes; k.N = N; k.A = A;
-  carve_loss(k, workspace, B, A);
-  hipStream_t st = (hipStream_t)stream;
-  zero_stat(k, B, st);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(loss_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k);
-  EFFDET_CHECK_LAUNCH();
-  const long long groups = (A * num_classes + 3) / 4;
-  k.ncb = (int)((groups + 256 * CLS_IT - 1) / (256 * CLS_IT));
-  if (k.ncb > cls_blocks_max(A, num_classes)) return EFFDET_EINVAL;
-  hipLaunchKernelGGL(loss_cls_kernel, dim3((unsigned)k.ncb, B), dim3(256), 0, st, k);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, st, k);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-static int loss_bwd(const float* cls, const float* reg, const float* anchors, const float* annots, const float* gscale,
-                    const void* workspace, void* dcls_logit, int dld, void* dreg, int dtype, int B, long long A, int num_classes,
-                    int N, effdet_stream_t stream) {
-  if (!cls || !reg || !anchors || !annots || !gscale || !workspace || !dcls_logit || !dreg) return EFFDET_EINVAL;
-  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16) return EFFDET_EINVAL;
-  if (dld && (A % 9 || num_classes % 4 || dld % 4 || dld < 9 * num_classes)) return EFFDET_EINVAL;
-  if (dld && (A / 9) * dld >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
-  LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.gscale = gscale;
-  k.dcls = dcls_logit; k.dreg = dreg; k.B = B; k.nc = num_classes; k.N = N; k.A = A; k.dld = dld;
-  carve_loss(k, const_cast<void*>(workspace), B, A);
-  hipStream_t st = (hipStream_t)stream;
-  const long long groups = dld ? (A / 9) * dld / 4 : (A * num_classes + 3) / 4;
-  dim3 g1((unsigned)((groups + 255) / 256), B);
-  if (dtype == EFFDET_F32) {
-    if (dld) hipLaunchKernelGGL(loss_bwd_cls_pix_kernel<float>, g1, dim3(256), 0, st, k);
-    else hipLaunchKernelGGL(loss_bwd_cls_kernel<float>, g1, dim3(256), 0, st, k);
-    hipLaunchKernelGGL(loss_bwd_reg_kernel<float>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
-  } else {
-    if (dld) hipLaunchKernelGGL(loss_bwd_cls_pix_kernel<bf16_t>, g1, dim3(256), 0, st, k);
-    else hipLaunchKernelGGL(loss_bwd_cls_kernel<bf16_t>, g1, dim3(256), 0, st, k);
-    hipLaunchKernelGGL(loss_bwd_reg_kernel<bf16_t>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
-  }
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-extern "C" int effdet_focal_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* annots,
-                                     const float* gscale, const void* workspace, void* dcls_logit, void* dreg, int dtype,
-                                     int B, long long A, int num_classes, int N, effdet_stream_t stream) {
-  return loss_bwd(cls, reg, anchors, annots, gscale, workspace, dcls_logit, 0, dreg, dtype, B, A, num_classes, N, stream);
-}
-
-extern "C" int effdet_focal_loss_bwd_pix(const float* cls, const float* reg, const float* anchors, const float* annots,
-                                         const float* gscale, const void* workspace, void* dcls_pix, int dld, void* dreg,
-                                         int dtype, int B, long long A, int num_classes, int N, effdet_stream_t stream) {
-  if (dld <= 0) return EFFDET_EINVAL;
-  return loss_bwd(cls, reg, anchors, annots, gscale, workspace, dcls_pix, dld, dreg, dtype, B, A, num_classes, N, stream);
-}
-
-extern "C" int effdet_focal_loss_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots,
-                                          float* losses, void* workspace, long long workspace_bytes, void* dcls_pix, int dld,
-                                          int dtype, int B, long long A, int num_classes, int N, effdet_stream_t stream) {
-  if (!cls || !reg || !anchors || !annots || !losses || !workspace || !dcls_pix) return EFFDET_EINVAL;
-  if (workspace_bytes < effdet_loss_workspace_bytes(B, A, num_classes) || B > 65535 || N < 1) return EFFDET_EINVAL;
-  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
-  if (dld <= 0 || A % 9 || num_classes % 4 || dld % 4 || dld < 9 * num_classes) return EFFDET_EINVAL;
-  if (dtype == EFFDET_F32_SPLIT && (dld % 32 || ((unsigned long long)dcls_pix & 127ull))) return EFFDET_EINVAL;     // whole [hi|lo] groups, aligned rows
-  if (A * num_classes >= 0x7fffffffLL || (A / 9) * dld >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
-  LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.losses = losses;
-  k.dcls = dcls_pix; k.dld = dld; k.B = B; k.nc = num_classes; k.N = N; k.A = A;
-  carve_loss(k, workspace, B, A);
-  hipStream_t st = (hipStream_t)stream;
-  zero_stat(k, B, st);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(loss_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k);
-  EFFDET_CHECK_LAUNCH();
-  const long long groups = (A / 9) * dld / 4;
-  k.ncb = (int)((groups + 256 * FG_IT - 1) / (256 * FG_IT));
-  if (k.ncb > cls_blocks_max(A, num_classes)) return EFFDET_EINVAL;
-  dim3 g1((unsigned)k.ncb, B);
-  if (dtype == EFFDET_F32) hipLaunchKernelGGL(loss_cls_grad_pix_kernel<float>, g1, dim3(256), 0, st, k);
-  else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(loss_cls_grad_pix_kernel<split_t>, g1, dim3(256), 0, st, k);
-  else hipLaunchKernelGGL(loss_cls_grad_pix_kernel<bf16_t>, g1, dim3(256), 0, st, k);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, st, k);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-extern "C" int effdet_focal_loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
-                                         const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N,
-                                         effdet_stream_t stream) {
-  if (!reg || !anchors || !annots || !gscale || !workspace || !dreg) return EFFDET_EINVAL;
-  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
-  if (reg_ld && (reg_ld < 36 || reg_ld % 4 || A % 9)) return EFFDET_EINVAL;
-  if (dtype == EFFDET_F32_SPLIT && (!reg_ld || reg_ld % 32 || ((unsigned long long)dreg & 127ull))) return EFFDET_EINVAL;
-  LossK k{}; k.reg = reg; k.anchors = anchors; k.annots = annots; k.gscale = gscale; k.dreg = dreg;
-  k.B = B; k.N = N; k.A = A; k.reg_ld = reg_ld;
-  carve_loss(k, const_cast<void*>(workspace), B, A);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == EFFDET_F32) hipLaunchKernelGGL(loss_bwd_reg_kernel<float>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
-  else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(loss_bwd_reg_kernel<split_t>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
-  else hipLaunchKernelGGL(loss_bwd_reg_kernel<bf16_t>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // IoU-family box regression losses (include/effdet_box_loss.h fixes the semantics): IoU / GIoU / DIoU / CIoU between the DECODED
-// prediction and the assigned annotation, over the positives of loss_assign_kernel, in place of its smooth-L1 term.  The forward
-// entry points run their smooth-L1 twins unchanged (assignment, focal term, losses[0]) and then two more kernels: one thread per
+// prediction and the assigned annotation, over the positives of the assign pass, in place of its smooth-L1 term.  The forward
+// entry points run the smooth-L1 forward unchanged (assignment, focal term, losses[0]) and then two more kernels: one thread per
 // anchor re-reads assign[] and puts the per-workgroup sum of the positives' losses into the same part_reg[b][block] slots, and a
 // final kernel adds them per image in a fixed pattern and overwrites losses[1].  Kernel launches only, no float atomics.
-namespace {
-
 constexpr float BOX_EPS = 1e-7f;
 constexpr float BOX_4_PI2 = 0.40528473456935109f;    // 4 / pi^2
 
@@ -546,11 +540,10 @@ __device__ __forceinline__ float box_loss_elem(int kind, float4 an, const float*
   return L;
 }
 
-// the grid of loss_assign_kernel: one thread per (image, anchor), one partial per workgroup into part_reg[b][block]
+// the grid of the assign pass: one thread per (image, anchor), one partial per workgroup into part_reg[b][block]
 __global__ __launch_bounds__(256) void box_loss_fwd_kernel(const LossK p, const int kind) {
   const int b = blockIdx.y;
   const long long a = blockIdx.x * 256LL + threadIdx.x;
-  __shared__ float red[4];
   float l = 0.f;
   if (a < p.A) {
     const int code = p.assign[(long long)b * p.A + a];
@@ -558,10 +551,7 @@ __global__ __launch_bounds__(256) void box_loss_fwd_kernel(const LossK p, const 
       l = box_loss_elem<false>(kind, ((const float4*)p.anchors)[a], p.annots + ((long long)b * p.N + code) * 5,
                                ((const float4*)p.reg)[(long long)b * p.A + a], nullptr);
   }
-  l = wave_sum(l);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l;
-  __syncthreads();
-  if (threadIdx.x == 0) p.part_reg[(long long)b * p.na + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  block_partial(l, p.part_reg + (long long)b * p.na + blockIdx.x);
 }
 
 // one workgroup: wave w adds part_reg of images w, w + 16, ... (lane-strided, then the fixed shuffle tree) into stat[b][1]; thread 0
@@ -585,7 +575,7 @@ __global__ __launch_bounds__(1024) void box_loss_final_kernel(const LossK p, con
   p.losses[1] = weight * (rl / (float)p.B);
 }
 
-// loss_bwd_reg_kernel's grid, output layouts and pad zeroing with the analytic gradient of box_loss_elem
+// loss_bwd_reg_kernel's grid and output layouts with the analytic gradient of box_loss_elem
 template <typename T>
 __global__ void box_loss_bwd_reg_kernel(const LossK p, const int kind, const float weight) {
   const long long total = (long long)p.B * p.A;
@@ -601,25 +591,136 @@ __global__ void box_loss_bwd_reg_kernel(const LossK p, const int kind, const flo
 #pragma unroll
       for (int q = 0; q < 4; ++q) g[q] = gs * gr[q];
     }
-    if (p.reg_ld) {
-      const long long pix = a / 9; const int an = (int)(a - pix * 9);
-      T* row = (T*)p.dreg + (b * (p.A / 9) + pix) * p.reg_ld;
-      store4(row + an * 4, g);
-      if (an == 8) for (int c = 36; c < p.reg_ld; c += 4) store4(row + c, f32x4{0.f, 0.f, 0.f, 0.f});
-    } else {
-      store4((T*)p.dreg + i * 4, g);
-    }
+    store_dreg_row<T>(p, b, a, i, g);
   }
 }
 
-inline bool box_loss_args_ok(int kind, float weight) {
-  return kind >= EFFDET_BOX_LOSS_IOU && kind <= EFFDET_BOX_LOSS_CIOU && weight >= 0.f && weight <= 3.402823466e38f;   // (false for a NaN)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host side
+
+// workgroups per image of the assign pass / upper bound of the class pass (either kernel: dld <= 9*nc + 63)
+inline long long assign_blocks(long long A) { return (A + 255) / 256; }
+inline long long cls_blocks_max(long long A, int nc) { return ((A * nc + 3) / 4 + (A / 9 + 1) * 16 + 1023) / 1024 + 1; }
+
+// assign [B][A], stat [B][SS], part_reg [B][na], part_cls [B][cls_blocks_max] -> bytes (num_classes only sizes the last buffer)
+size_t carve_loss(LossK& k, void* ws, int B, long long A, int num_classes = 0) {
+  Carver c(ws);
+  k.assign = c.take<int>((size_t)B * A);
+  k.stat = c.take<float>((size_t)B * SS);
+  k.part_reg = c.take<float>((size_t)B * assign_blocks(A));
+  k.part_cls = c.take<float>((size_t)B * cls_blocks_max(A, num_classes));
+  k.na = (int)assign_blocks(A);
+  return c.off;
 }
 
-// after the smooth-L1 twin has been enqueued: the per-workgroup IoU-loss partials over its assignment, then losses[1]
+// carve_loss's layout, then gtmax [B][N], best [B][A], barg [B][A] -> bytes
+size_t carve_loss_opts(LossK& k, OptsK& o, void* ws, int B, long long A, int num_classes, int N) {
+  const size_t head = carve_loss(k, ws, B, A, num_classes);
+  Carver c(ws ? (char*)ws + head : nullptr);
+  o.gtmax = c.take<int>((size_t)B * N);
+  o.best = c.take<float>((size_t)B * A);
+  o.barg = c.take<int>((size_t)B * A);
+  return head + c.off;
+}
+
+LossK loss_args(const float* cls, const float* reg, const float* anchors, const float* annots, int B, long long A, int nc, int N) {
+  LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.B = B; k.nc = nc; k.N = N; k.A = A;
+  return k;
+}
+
+// ---- argument checks, each written once.  Every entry point makes all its EFFDET_EINVAL checks before the first
+// EFFDET_EUNSUPPORTED one; check_dcls ends with the latter, so it comes last among an entry point's EINVAL checks.
+inline bool finite_ge0(float v) { return v >= 0.f && v <= 3.402823466e38f; }      // (false for a NaN)
+
+inline bool box_loss_args_ok(int kind, float weight) {
+  return kind >= EFFDET_BOX_LOSS_IOU && kind <= EFFDET_BOX_LOSS_CIOU && finite_ge0(weight);
+}
+
+bool loss_opts_ok(const effdet_loss_opts_t* o) {
+  if (!o) return false;
+  if (!(o->alpha > 0.f && o->alpha < 1.f) || !(o->gamma >= 0.f && o->gamma <= 8.f)) return false;
+  if (!(o->label_smoothing >= 0.f && o->label_smoothing < 1.f)) return false;
+  if (!(o->beta > 0.f && o->beta <= 3.402823466e38f) || !finite_ge0(o->reg_weight) || !finite_ge0(o->box_weight)) return false;
+  if (!(o->neg_iou >= 0.f && o->neg_iou <= o->pos_iou && o->pos_iou <= 1.f)) return false;
+  if (o->low_quality != 0 && o->low_quality != 1) return false;
+  return o->box_kind >= 0 && o->box_kind <= EFFDET_BOX_LOSS_CIOU;
+}
+
+inline bool dtype_ok(int dtype, bool split) { return dtype == EFFDET_F32 || dtype == EFFDET_BF16 || (split && dtype == EFFDET_F32_SPLIT); }
+
+// the d(cls) output: dtype, then with dld the pixel-major padded layout (split: whole [hi|lo] groups, aligned rows) and its extent
+int check_dcls(const void* dcls, int dld, int dtype, bool split, long long A, int nc) {
+  if (!dtype_ok(dtype, split)) return EFFDET_EINVAL;
+  if (dld && (A % 9 || nc % 4 || dld % 4 || dld < 9 * nc)) return EFFDET_EINVAL;
+  if (dtype == EFFDET_F32_SPLIT && (dld % 32 || ((unsigned long long)dcls & 127ull))) return EFFDET_EINVAL;
+  if (dld && (A / 9) * dld >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
+  return EFFDET_OK;
+}
+
+// the d(reg) output: dtype and layout (the split layout exists pixel-major only)
+int check_dreg(const void* dreg, int reg_ld, int dtype, long long A) {
+  if (!dtype_ok(dtype, true)) return EFFDET_EINVAL;
+  if (reg_ld && (reg_ld < 36 || reg_ld % 4 || A % 9)) return EFFDET_EINVAL;
+  if (dtype == EFFDET_F32_SPLIT && (!reg_ld || reg_ld % 32 || ((unsigned long long)dreg & 127ull))) return EFFDET_EINVAL;
+  return EFFDET_OK;
+}
+
+// ---- the one place where a dtype code becomes an element type: fn(Tag<T>{}).  SPLIT: the entry point also takes EFFDET_F32_SPLIT
+// (the callers have checked the code with dtype_ok)
+template <typename T> struct Tag { using type = T; };
+template <bool SPLIT, typename Fn>
+inline void by_dtype(int dtype, Fn&& fn) {
+  if (dtype == EFFDET_F32) return fn(Tag<float>{});
+  if constexpr (SPLIT) if (dtype == EFFDET_F32_SPLIT) return fn(Tag<split_t>{});
+  fn(Tag<bf16_t>{});
+}
+
+// ---- drivers
+// Every forward entry point.  assign(k): carves the workspace into k and enqueues the zero and assign kernels of its path.  Then the
+// class pass (grad: forward + gradient into k.dcls, pixel-major) and the final reduction.
+template <typename F, typename Assign>
+int loss_forward(LossK k, const F f, float reg_weight, const void* workspace, long long workspace_bytes, long long need, bool grad,
+                 int dtype, hipStream_t st, Assign&& assign) {
+  if (!k.cls || !k.reg || !k.anchors || !k.annots || !k.losses || !workspace || (grad && !k.dcls)) return EFFDET_EINVAL;
+  if (workspace_bytes < need || k.B > 65535 || k.N < 1) return EFFDET_EINVAL;
+  if (grad) {
+    if (k.dld <= 0) return EFFDET_EINVAL;
+    if (const int rc = check_dcls(k.dcls, k.dld, dtype, true, k.A, k.nc)) return rc;
+  }
+  if (k.A * k.nc >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
+  if (const int rc = assign(k)) return rc;
+  const long long groups = grad ? (k.A / 9) * k.dld / 4 : (k.A * k.nc + 3) / 4;
+  const int it = grad ? FG_IT : CLS_IT;
+  k.ncb = (int)((groups + 256 * it - 1) / (256 * it));
+  if (k.ncb > cls_blocks_max(k.A, k.nc)) return EFFDET_EINVAL;
+  const dim3 g1((unsigned)k.ncb, k.B);
+  if (grad) by_dtype<true>(dtype, [&](auto t) {
+    hipLaunchKernelGGL((loss_cls_pix_kernel<typename decltype(t)::type, F, false, FG_IT>), g1, dim3(256), 0, st, k, f);
+  });
+  else hipLaunchKernelGGL(loss_cls_kernel<F>, g1, dim3(256), 0, st, k, f);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, st, k, reg_weight);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+int loss_forward_default(const LossK& k0, void* workspace, long long workspace_bytes, bool grad, int dtype, effdet_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  return loss_forward(k0, FocalDefault{}, 1.0f, workspace, workspace_bytes, effdet_loss_workspace_bytes(k0.B, k0.A, k0.nc), grad, dtype,
+                      st, [&](LossK& k) -> int {
+    carve_loss(k, workspace, k.B, k.A);
+    hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((k.B * SS + 255) / 256)), dim3(256), 0, st, k.stat, k.B * SS);
+    EFFDET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(loss_assign_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k);
+    EFFDET_CHECK_LAUNCH();
+    return EFFDET_OK;
+  });
+}
+
+// after a forward driver has been enqueued with an IoU-family box term: the per-workgroup partials over its assignment, then losses[1]
 int box_loss_finish(const float* reg, const float* anchors, const float* annots, float* losses, void* workspace, int B, long long A,
                     int N, int kind, float weight, hipStream_t st) {
-  LossK k{}; k.reg = reg; k.anchors = anchors; k.annots = annots; k.losses = losses; k.B = B; k.N = N; k.A = A;
+  LossK k = loss_args(nullptr, reg, anchors, annots, B, A, 0, N); k.losses = losses;
   carve_loss(k, workspace, B, A);
   hipLaunchKernelGGL(box_loss_fwd_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, kind);
   EFFDET_CHECK_LAUNCH();
@@ -628,7 +729,121 @@ int box_loss_finish(const float* reg, const float* anchors, const float* annots,
   return EFFDET_OK;
 }
 
+// both forward entry points of the options: dcls_pix == nullptr is effdet_loss_opts_fwd
+int loss_opts_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
+                      long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
+                      int N, const effdet_loss_opts_t* opts, effdet_stream_t stream) {
+  if (!loss_opts_ok(opts) || B < 1 || N < 1 || A < 1 || num_classes < 1) return EFFDET_EINVAL;
+  LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = loss_forward(k0, FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, opts->reg_weight, workspace, workspace_bytes,
+                              effdet_loss_opts_workspace_bytes(B, A, num_classes, N), grad, dtype, st, [&](LossK& k) -> int {
+    OptsK o{opts->pos_iou, opts->neg_iou, opts->low_quality};
+    carve_loss_opts(k, o, workspace, B, A, num_classes, N);
+    const int nz = B * SS, mz = B * N;
+    hipLaunchKernelGGL(opts_zero_kernel, dim3((unsigned)((nz + mz + 255) / 256)), dim3(256), 0, st, k.stat, nz, o.gtmax, mz);
+    EFFDET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(opts_iou_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o);
+    EFFDET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(opts_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o, KneeBeta{opts->beta});
+    EFFDET_CHECK_LAUNCH();
+    return EFFDET_OK;
+  });
+  if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
+  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
+}
+
+// d(logits) into k.dcls, flat or (k.dld) pixel-major, with the upstream gradient applied.  No launch check: the caller's follows.
+template <typename F>
+void launch_bwd_cls(const LossK& k, const F f, int dtype, hipStream_t st) {
+  const long long groups = k.dld ? (k.A / 9) * k.dld / 4 : (k.A * k.nc + 3) / 4;
+  const dim3 g1((unsigned)((groups + 255) / 256), k.B);
+  by_dtype<false>(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (k.dld) hipLaunchKernelGGL((loss_cls_pix_kernel<T, F, true, 1>), g1, dim3(256), 0, st, k, f);
+    else hipLaunchKernelGGL((loss_bwd_cls_kernel<T, F>), g1, dim3(256), 0, st, k, f);
+  });
+}
+
+template <typename Knee>
+void launch_bwd_reg(const LossK& k, const Knee knee, float reg_weight, int dtype, hipStream_t st) {
+  by_dtype<true>(dtype, [&](auto t) {
+    hipLaunchKernelGGL((loss_bwd_reg_kernel<typename decltype(t)::type, Knee>), dim3(grid_for((long long)k.B * k.A)), dim3(256), 0, st, k,
+                       knee, reg_weight);
+  });
+}
+
+int loss_bwd(const float* cls, const float* reg, const float* anchors, const float* annots, const float* gscale,
+             const void* workspace, void* dcls_logit, int dld, void* dreg, int dtype, int B, long long A, int num_classes,
+             int N, effdet_stream_t stream) {
+  if (!cls || !reg || !anchors || !annots || !gscale || !workspace || !dcls_logit || !dreg) return EFFDET_EINVAL;
+  if (const int rc = check_dcls(dcls_logit, dld, dtype, false, A, num_classes)) return rc;
+  LossK k = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k.gscale = gscale; k.dcls = dcls_logit; k.dreg = dreg; k.dld = dld;
+  carve_loss(k, const_cast<void*>(workspace), B, A);
+  launch_bwd_cls(k, FocalDefault{}, dtype, (hipStream_t)stream);
+  launch_bwd_reg(k, KneeDefault{}, 1.0f, dtype, (hipStream_t)stream);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// every d(reg) entry point: launch(k, st) enqueues its kernel
+template <typename Launch>
+int loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale, const void* workspace, void* dreg,
+                 int reg_ld, int dtype, int B, long long A, int N, effdet_stream_t stream, Launch&& launch) {
+  if (!reg || !anchors || !annots || !gscale || !workspace || !dreg) return EFFDET_EINVAL;
+  if (const int rc = check_dreg(dreg, reg_ld, dtype, A)) return rc;
+  LossK k = loss_args(nullptr, reg, anchors, annots, B, A, 0, N); k.gscale = gscale; k.dreg = dreg; k.reg_ld = reg_ld;
+  carve_loss(k, const_cast<void*>(workspace), B, A);
+  launch(k, (hipStream_t)stream);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
 }  // namespace
+
+extern "C" long long effdet_loss_workspace_bytes(int B, long long A, int num_classes) {
+  LossK k{};
+  return (long long)carve_loss(k, nullptr, B, A, num_classes);
+}
+
+extern "C" long long effdet_loss_opts_workspace_bytes(int B, long long A, int num_classes, int N) {
+  LossK k{}; OptsK o{};
+  return (long long)carve_loss_opts(k, o, nullptr, B, A, num_classes, N);
+}
+
+extern "C" int effdet_focal_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots,
+                                     float* losses, void* workspace, long long workspace_bytes, int B, long long A,
+                                     int num_classes, int N, effdet_stream_t stream) {
+  LossK k = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k.losses = losses;
+  return loss_forward_default(k, workspace, workspace_bytes, false, EFFDET_F32, stream);
+}
+
+extern "C" int effdet_focal_loss_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots,
+                                          float* losses, void* workspace, long long workspace_bytes, void* dcls_pix, int dld,
+                                          int dtype, int B, long long A, int num_classes, int N, effdet_stream_t stream) {
+  LossK k = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k.losses = losses; k.dcls = dcls_pix; k.dld = dld;
+  return loss_forward_default(k, workspace, workspace_bytes, true, dtype, stream);
+}
+
+extern "C" int effdet_focal_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* annots,
+                                     const float* gscale, const void* workspace, void* dcls_logit, void* dreg, int dtype,
+                                     int B, long long A, int num_classes, int N, effdet_stream_t stream) {
+  return loss_bwd(cls, reg, anchors, annots, gscale, workspace, dcls_logit, 0, dreg, dtype, B, A, num_classes, N, stream);
+}
+
+extern "C" int effdet_focal_loss_bwd_pix(const float* cls, const float* reg, const float* anchors, const float* annots,
+                                         const float* gscale, const void* workspace, void* dcls_pix, int dld, void* dreg,
+                                         int dtype, int B, long long A, int num_classes, int N, effdet_stream_t stream) {
+  if (dld <= 0) return EFFDET_EINVAL;
+  return loss_bwd(cls, reg, anchors, annots, gscale, workspace, dcls_pix, dld, dreg, dtype, B, A, num_classes, N, stream);
+}
+
+extern "C" int effdet_focal_loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
+                                         const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N,
+                                         effdet_stream_t stream) {
+  return loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, stream,
+                      [&](const LossK& k, hipStream_t st) { launch_bwd_reg(k, KneeDefault{}, 1.0f, dtype, st); });
+}
 
 extern "C" int effdet_box_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                    void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N, int kind,
@@ -652,444 +867,13 @@ extern "C" int effdet_box_loss_fwd_grad(const float* cls, const float* reg, cons
 extern "C" int effdet_box_loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
                                        const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N, int kind,
                                        float weight, effdet_stream_t stream) {
-  if (!reg || !anchors || !annots || !gscale || !workspace || !dreg) return EFFDET_EINVAL;
-  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
-  if (reg_ld && (reg_ld < 36 || reg_ld % 4 || A % 9)) return EFFDET_EINVAL;
-  if (dtype == EFFDET_F32_SPLIT && (!reg_ld || reg_ld % 32 || ((unsigned long long)dreg & 127ull))) return EFFDET_EINVAL;
   if (!box_loss_args_ok(kind, weight)) return EFFDET_EINVAL;
-  LossK k{}; k.reg = reg; k.anchors = anchors; k.annots = annots; k.gscale = gscale; k.dreg = dreg;
-  k.B = B; k.N = N; k.A = A; k.reg_ld = reg_ld;
-  carve_loss(k, const_cast<void*>(workspace), B, A);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(grid_for((long long)B * A));
-  if (dtype == EFFDET_F32) hipLaunchKernelGGL(box_loss_bwd_reg_kernel<float>, grid, dim3(256), 0, st, k, kind, weight);
-  else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(box_loss_bwd_reg_kernel<split_t>, grid, dim3(256), 0, st, k, kind, weight);
-  else hipLaunchKernelGGL(box_loss_bwd_reg_kernel<bf16_t>, grid, dim3(256), 0, st, k, kind, weight);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Loss options (include/effdet_loss_opts.h fixes the semantics): focal alpha / gamma, label smoothing, the smooth-L1 knee and weight,
-// the matcher's IoU bands and low-quality matches, as launch arguments.  The kernels above are not edited: these are their twins.
-//   opts_iou_kernel     one thread per (image, anchor): loss_assign_kernel's IoU loop -> best[b][a], barg[b][a]; with low_quality also
-//                       gtmax[b][n] = max over the anchors, as an INTEGER atomicMax on the bit pattern of the non-negative IoU (order-
-//                       independent, exact), first per workgroup in LDS, then one global atomic per (workgroup, row)
-//   opts_assign_kernel  the same grid: bands on best; with low_quality the IoU loop once more, promoting an anchor whose IoU with any row
-//                       equals that row's gtmax (> 0); assign[], the smooth-L1 partials with the knee beta, the integer num_pos
-//   opts_cls_* / opts_bwd_cls_*  the class passes with focal_elem_opts in the place of focal_elem
-//   opts_final_kernel   loss_final_kernel with reg_weight on losses[1];  opts_bwd_reg_kernel  loss_bwd_reg_kernel with beta, reg_weight
-// An IoU-family box term (box_kind 1..4) is box_loss_fwd / box_loss_final / box_loss_bwd_reg_kernel as they are, over this assignment.
-namespace {
-
-struct FocalP { float alpha, gamma, eps; };
-struct OptsK {
-  FocalP f; float beta, reg_weight, pos_iou, neg_iou; int low_quality;
-  int* gtmax; float* best; int* barg;         // [B][N] bit patterns, [B][A], [B][A]
-};
-
-// loss_assign_kernel's IoU of anchor `an` (area aarea) with the box at r[0..3], statement for statement: both passes of the matcher
-// evaluate THIS function, so the equality test of the second pass compares a value with a maximum over the same values (no
-// contraction: whether a multiply-add is fused must not depend on the kernel the function is inlined into; loss_assign_kernel's
-// gfx950 code has none in this expression either)
-__device__ __forceinline__ float assign_iou(const float4 an, const float aarea, const float* r) {
-#pragma clang fp contract(off)
-  const float bx1 = r[0], by1 = r[1], bx2 = r[2], by2 = r[3];
-  const float barea = (bx2 - bx1) * (by2 - by1);
-  float iw = fminf(an.z, bx2) - fmaxf(an.x, bx1); float ih = fminf(an.w, by2) - fmaxf(an.y, by1);
-  iw = fmaxf(iw, 0.f); ih = fmaxf(ih, 0.f);
-  const float ua = fmaxf(aarea + barea - iw * ih, 1e-8f);
-  const float iou = iw * ih / ua;
-  return iou;
-}
-
-// thread 0 compacts the valid rows of chunk [n0, n0 + 64) of image b into ann[] (loss_assign_kernel's order and format) -> their number
-__device__ __forceinline__ int compact_chunk(const LossK& p, int b, int n0, float* ann) {
-  int c = 0;
-  for (int n = n0; n < min(p.N, n0 + 64); ++n) {
-    const float* r = p.annots + ((long long)b * p.N + n) * 5;
-    if (r[4] != -1.0f) { for (int q = 0; q < 5; ++q) ann[c * 5 + q] = r[q]; ann[c * 5 + 4] = (float)n; ++c; }
-  }
-  return c;
-}
-
-__global__ __launch_bounds__(256) void opts_zero_kernel(float* __restrict__ stat, int n, int* __restrict__ gtmax, int m) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) stat[i] = 0.f;
-  else if (i - n < m) gtmax[i - n] = 0;
-}
-
-__global__ __launch_bounds__(256) void opts_iou_kernel(const LossK p, const OptsK o) {
-  const int b = blockIdx.y;
-  const long long a = blockIdx.x * 256LL + threadIdx.x;
-  __shared__ float ann[64 * 5];
-  __shared__ int gm[64];
-  __shared__ int nvalid_s;
-  float best = -1.0f; int barg = -1;
-  float4 an = make_float4(0, 0, 0, 0);
-  const bool ok = a < p.A;
-  if (ok) an = ((const float4*)p.anchors)[a];
-  const float aarea = (an.z - an.x) * (an.w - an.y);
-  int total_valid = 0;
-  for (int n0 = 0; n0 < p.N; n0 += 64) {
-    __syncthreads();
-    if (threadIdx.x == 0) nvalid_s = compact_chunk(p, b, n0, ann);
-    if (threadIdx.x < 64) gm[threadIdx.x] = 0;
-    __syncthreads();
-    const int c = nvalid_s;
-    total_valid += c;
-    if (ok) {
-      for (int j = 0; j < c; ++j) {
-        const float iou = assign_iou(an, aarea, ann + j * 5);
-        if (iou > best) { best = iou; barg = (int)ann[j * 5 + 4]; }     // strict > keeps the FIRST max
-        if (o.low_quality && iou > 0.f && __float_as_int(iou) > *(volatile int*)&gm[j]) atomicMax(&gm[j], __float_as_int(iou));
-      }
-    }
-    if (o.low_quality) {
-      __syncthreads();
-      if ((int)threadIdx.x < c && gm[threadIdx.x] > 0) atomicMax(o.gtmax + (long long)b * p.N + (int)ann[threadIdx.x * 5 + 4], gm[threadIdx.x]);
-    }
-  }
-  if (ok) { o.best[(long long)b * p.A + a] = best; o.barg[(long long)b * p.A + a] = barg; }
-  if (blockIdx.x == 0 && threadIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
-}
-
-__global__ __launch_bounds__(256) void opts_assign_kernel(const LossK p, const OptsK o) {
-  const int b = blockIdx.y;
-  const long long a = blockIdx.x * 256LL + threadIdx.x;
-  __shared__ float ann[64 * 5];
-  __shared__ float gmf[64];
-  __shared__ int nvalid_s;
-  __shared__ float red[2][4];
-  const bool ok = a < p.A;
-  float4 an = make_float4(0, 0, 0, 0);
-  float best = -1.0f; int barg = -1;
-  if (ok) { an = ((const float4*)p.anchors)[a]; best = o.best[(long long)b * p.A + a]; barg = o.barg[(long long)b * p.A + a]; }
-  const bool any_valid = p.stat[b * SS + 3] > 0.f;
-  bool promoted = false;
-  if (o.low_quality && any_valid) {
-    const float aarea = (an.z - an.x) * (an.w - an.y);
-    for (int n0 = 0; n0 < p.N; n0 += 64) {
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const int c = compact_chunk(p, b, n0, ann);
-        for (int j = 0; j < c; ++j) gmf[j] = __int_as_float(o.gtmax[(long long)b * p.N + (int)ann[j * 5 + 4]]);
-        nvalid_s = c;
-      }
-      __syncthreads();
-      const int c = nvalid_s;
-      if (ok) {
-        for (int j = 0; j < c; ++j) {
-          const float iou = assign_iou(an, aarea, ann + j * 5);
-          promoted = promoted || (iou == gmf[j] && gmf[j] > 0.f);
-        }
-      }
-    }
-  }
-  float regl = 0.f, pos = 0.f;
-  int code = -2;                       // -2 ignore, -1 negative, >= 0 positive (annotation row)
-  if (ok && any_valid) {
-    if (best < o.neg_iou) code = -1;
-    if ((best >= o.pos_iou || promoted) && barg >= 0) {
-      code = barg; pos = 1.f;
-      const float* g = p.annots + ((long long)b * p.N + barg) * 5;
-      const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
-      float gw = g[2] - g[0], gh = g[3] - g[1];
-      const float gcx = g[0] + 0.5f * gw, gcy = g[1] + 0.5f * gh;
-      gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
-      const float t[4] = {(gcx - acx) / aw / 0.1f, (gcy - acy) / ah / 0.1f, logf(gw / aw) / 0.2f, logf(gh / ah) / 0.2f};
-      const float4 r = ((const float4*)p.reg)[(long long)b * p.A + a];
-      const float rv[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { const float d = fabsf(t[q] - rv[q]); regl += (d <= o.beta) ? 0.5f * d * d / o.beta : d - 0.5f * o.beta; }
-    }
-  }
-  if (ok) p.assign[(long long)b * p.A + a] = code;
-  regl = wave_sum(regl); pos = wave_sum(pos);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { red[0][wave] = regl; red[1][wave] = pos; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    p.part_reg[(long long)b * p.na + blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    atomicAdd((int*)(p.stat + b * SS + 2), (int)(red[1][0] + red[1][1] + red[1][2] + red[1][3]));    // num_pos is kept as an INTEGER (npos())
-  }
-}
-
-// focal_elem with the options: per-element term and its derivative wrt the (unclamped) probability p
-// (no contraction: every kernel and layout computes the same bits)
-__device__ __forceinline__ float focal_elem_opts(const FocalP f, float praw, bool target_one, float& dldp) {
-#pragma clang fp contract(off)
-  const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);
-  const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);
-  const float h = target_one ? 1.f : 0.f;
-  const float t = h * (1.f - f.eps) + 0.5f * f.eps;
-  const float u = target_one ? 1.f - pc : pc, aw = target_one ? f.alpha : 1.f - f.alpha;
-  const float pw = exp2f(f.gamma * log2f(u));
-  const float ce = -(t * logf(pc) + (1.f - t) * logf(1.f - pc));
-  const float dce = (1.f - t) / (1.f - pc) - t / pc;
-  const float dpw = f.gamma * pw / u;                               // d pw / d u; du / dp = -1 for a target of one
-  dldp = pass ? aw * ((target_one ? -dpw : dpw) * ce + pw * dce) : 0.f;
-  return aw * pw * ce;
-}
-
-__device__ __forceinline__ int label_of(const LossK& p, int b, int code) {
-  return code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
-}
-
-// loss_cls_kernel with the options
-__global__ __launch_bounds__(256) void opts_cls_kernel(const LossK p, const FocalP f) {
-  const int b = blockIdx.y;
-  const int per = (int)(p.A * p.nc);
-  float s = 0.f;
-  if (p.stat[b * SS + 3] > 0.f) {
-    const float* c = p.cls + (long long)b * per;
-    const int* asg = p.assign + (long long)b * p.A;
-#pragma unroll
-    for (int it = 0; it < CLS_IT; ++it) {
-      const int e0 = ((blockIdx.x * CLS_IT + it) * 256 + threadIdx.x) * 4;
-      if (e0 >= per) break;
-      float v[4]; const int cnt = min(4, per - e0);
-      const bool vec = cnt == 4 && ((per & 3) == 0);
-      if (vec) { const f32x4 t = *(const f32x4*)(c + e0); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
-      else for (int q = 0; q < cnt; ++q) v[q] = c[e0 + q];
-      int a = e0 / p.nc, k = e0 - a * p.nc;
-      int code = asg[a];
-      int lab = label_of(p, b, code);
-      for (int q = 0; q < cnt; ++q) {
-        if (code != -2) { float d; s += focal_elem_opts(f, v[q], lab == k, d); }
-        if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
-      }
-    }
-  }
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) p.part_cls[(long long)b * p.ncb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// loss_final_kernel with reg_weight on losses[1]
-__global__ __launch_bounds__(1024) void opts_final_kernel(const LossK p, const float reg_weight) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  auto lane_sum = [&](const float* q, int n) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int i = lane;
-    for (; i + 192 < n; i += 256) { s0 += q[i]; s1 += q[i + 64]; s2 += q[i + 128]; s3 += q[i + 192]; }
-    for (; i < n; i += 64) s0 += q[i];
-    return wave_sum((s0 + s1) + (s2 + s3));
-  };
-  for (int b = wave; b < p.B; b += 16) {
-    const float c = lane_sum(p.part_cls + (long long)b * p.ncb, p.ncb), r = lane_sum(p.part_reg + (long long)b * p.na, p.na);
-    if (lane == 0) { p.stat[b * SS + 0] = c; p.stat[b * SS + 1] = r; }
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  float cl = 0.f, rl = 0.f;
-  for (int b = 0; b < p.B; ++b) {
-    const float* s = p.stat + b * SS;
-    if (s[3] > 0.f) {
-      cl += s[0] / fmaxf(npos(s), 1.0f);
-      if (npos(s) > 0.f) rl += s[1] / (npos(s) * 4.0f);
-    }
-  }
-  p.losses[0] = cl / (float)p.B; p.losses[1] = reg_weight * (rl / (float)p.B);
-}
-
-// loss_bwd_cls_kernel with the options
-template <typename T>
-__global__ __launch_bounds__(256) void opts_bwd_cls_kernel(const LossK p, const FocalP f) {
-  const int b = blockIdx.y;
-  const int per = (int)(p.A * p.nc);
-  const int e0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (e0 >= per) return;
-  const float* st = p.stat + b * SS;
-  const bool active = st[3] > 0.f;
-  const float gs = active ? p.gscale[0] / ((float)p.B * fmaxf(npos(st), 1.0f)) : 0.f;
-  const float* c = p.cls + (long long)b * per;
-  const int* asg = p.assign + (long long)b * p.A;
-  T* out = (T*)p.dcls + (long long)b * per;
-  const int cnt = min(4, per - e0);
-  const bool vec = cnt == 4 && ((per & 3) == 0);
-  float v[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
-  if (vec) { const f32x4 t = *(const f32x4*)(c + e0); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
-  else for (int q = 0; q < cnt; ++q) v[q] = c[e0 + q];
-  int a = e0 / p.nc, k = e0 - a * p.nc;
-  int code = asg[a];
-  int lab = label_of(p, b, code);
-  for (int q = 0; q < cnt; ++q) {
-    if (active && code != -2) {
-      float d; (void)focal_elem_opts(f, v[q], lab == k, d);
-      g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
-    } else {
-      g[q] = nan_zero(v[q]);
-    }
-    if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
-  }
-  if (vec) store4(out + e0, f32x4{g[0], g[1], g[2], g[3]});
-  else for (int q = 0; q < cnt; ++q) Elem<T>::st(out + e0 + q, g[q]);
-}
-
-// loss_bwd_cls_pix_kernel (GRAD_ONLY: the upstream gradient gscale[0] applied, no partial) and loss_cls_grad_pix_kernel (forward and
-// gradient for an upstream gradient of one in ONE pass over cls) with the options; IT 4-element groups per thread
-template <typename T, bool GRAD_ONLY, int IT>
-__global__ __launch_bounds__(256) void opts_cls_pix_kernel(const LossK p, const FocalP f) {
-  const int b = blockIdx.y;
-  const int apix = (int)(p.A / 9), perp = apix * p.dld, cmax = 9 * p.nc;
-  const float* st = p.stat + b * SS;
-  const bool active = st[3] > 0.f;
-  const float gs = (GRAD_ONLY ? p.gscale[0] : 1.0f) / ((float)p.B * fmaxf(npos(st), 1.0f));
-  float s = 0.f;
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int e0 = ((blockIdx.x * IT + it) * 256 + threadIdx.x) * 4;
-    if (e0 >= perp) break;
-    const int pix = e0 / p.dld, ch = e0 - pix * p.dld;
-    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (ch < cmax) {
-      const int an = ch / p.nc, k = ch - an * p.nc, a = pix * 9 + an;
-      const int code = active ? p.assign[(long long)b * p.A + a] : -2;
-      const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
-      if (code != -2) {
-        const int lab = label_of(p, b, code);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float d; s += focal_elem_opts(f, v[q], lab == k + q, d);
-          g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = nan_zero(v[q]);
-      }
-    }
-    store4((T*)p.dcls + (long long)b * perp + e0, g);
-  }
-  if (GRAD_ONLY) return;
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) p.part_cls[(long long)b * p.ncb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// loss_bwd_reg_kernel with the knee beta and reg_weight: the same grid, layouts and pad zeroing
-template <typename T>
-__global__ void opts_bwd_reg_kernel(const LossK p, const float beta, const float reg_weight) {
-  const long long total = (long long)p.B * p.A;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / p.A, a = i - b * p.A;
-    const int code = p.assign[i];
-    const float* st = p.stat + b * SS;
-    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (code >= 0 && st[3] > 0.f && npos(st) > 0.f) {
-      const float gs = p.gscale[1] * reg_weight / ((float)p.B * npos(st) * 4.0f);
-      const float4 an = ((const float4*)p.anchors)[a];
-      const float* gt = p.annots + (b * p.N + code) * 5;
-      const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
-      float gw = gt[2] - gt[0], gh = gt[3] - gt[1];
-      const float gcx = gt[0] + 0.5f * gw, gcy = gt[1] + 0.5f * gh;
-      gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
-      const float t[4] = {(gcx - acx) / aw / 0.1f, (gcy - acy) / ah / 0.1f, logf(gw / aw) / 0.2f, logf(gh / ah) / 0.2f};
-      const float4 r = ((const float4*)p.reg)[i];
-      const float rv[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float diff = rv[q] - t[q], d = fabsf(diff);
-        const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-        g[q] = gs * ((d <= beta) ? diff / beta : sgn + 0.f * d);      // (0 * d: see loss_bwd_reg_kernel)
-      }
-    }
-    if (p.reg_ld) {
-      const long long pix = a / 9; const int an = (int)(a - pix * 9);
-      T* row = (T*)p.dreg + (b * (p.A / 9) + pix) * p.reg_ld;
-      store4(row + an * 4, g);
-      if (an == 8) for (int c = 36; c < p.reg_ld; c += 4) store4(row + c, f32x4{0.f, 0.f, 0.f, 0.f});
-    } else {
-      store4((T*)p.dreg + i * 4, g);
-    }
-  }
-}
-
-// carve_loss's layout, then gtmax [B][N], best [B][A], barg [B][A] -> bytes
-size_t carve_loss_opts(LossK& k, OptsK& o, void* ws, int B, long long A, int num_classes, int N) {
-  const size_t head = carve_loss(k, ws, B, A, num_classes);
-  Carver c(ws ? (char*)ws + head : nullptr);
-  o.gtmax = c.take<int>((size_t)B * N);
-  o.best = c.take<float>((size_t)B * A);
-  o.barg = c.take<int>((size_t)B * A);
-  return head + c.off;
-}
-
-inline bool finite_ge0(float v) { return v >= 0.f && v <= 3.402823466e38f; }      // (false for a NaN)
-
-bool loss_opts_ok(const effdet_loss_opts_t* o) {
-  if (!o) return false;
-  if (!(o->alpha > 0.f && o->alpha < 1.f) || !(o->gamma >= 0.f && o->gamma <= 8.f)) return false;
-  if (!(o->label_smoothing >= 0.f && o->label_smoothing < 1.f)) return false;
-  if (!(o->beta > 0.f && o->beta <= 3.402823466e38f) || !finite_ge0(o->reg_weight) || !finite_ge0(o->box_weight)) return false;
-  if (!(o->neg_iou >= 0.f && o->neg_iou <= o->pos_iou && o->pos_iou <= 1.f)) return false;
-  if (o->low_quality != 0 && o->low_quality != 1) return false;
-  return o->box_kind >= 0 && o->box_kind <= EFFDET_BOX_LOSS_CIOU;
-}
-
-OptsK opts_args(const effdet_loss_opts_t* o) {
-  OptsK k{};
-  k.f = FocalP{o->alpha, o->gamma, o->label_smoothing};
-  k.beta = o->beta; k.reg_weight = o->reg_weight; k.pos_iou = o->pos_iou; k.neg_iou = o->neg_iou; k.low_quality = o->low_quality;
-  return k;
-}
-
-// both forward entry points: dcls_pix == nullptr is effdet_loss_opts_fwd
-int loss_opts_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
-                      long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
-                      int N, const effdet_loss_opts_t* opts, effdet_stream_t stream) {
-  if (!cls || !reg || !anchors || !annots || !losses || !workspace || (grad && !dcls_pix)) return EFFDET_EINVAL;
-  if (!loss_opts_ok(opts) || B < 1 || B > 65535 || N < 1 || A < 1 || num_classes < 1) return EFFDET_EINVAL;
-  if (workspace_bytes < effdet_loss_opts_workspace_bytes(B, A, num_classes, N)) return EFFDET_EINVAL;
-  if (grad) {
-    if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
-    if (dld <= 0 || A % 9 || num_classes % 4 || dld % 4 || dld < 9 * num_classes) return EFFDET_EINVAL;
-    if (dtype == EFFDET_F32_SPLIT && (dld % 32 || ((unsigned long long)dcls_pix & 127ull))) return EFFDET_EINVAL;
-    if ((A / 9) * dld >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
-  }
-  if (A * num_classes >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
-  LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.losses = losses;
-  k.dcls = dcls_pix; k.dld = dld; k.B = B; k.nc = num_classes; k.N = N; k.A = A;
-  OptsK o = opts_args(opts);
-  carve_loss_opts(k, o, workspace, B, A, num_classes, N);
-  hipStream_t st = (hipStream_t)stream;
-  const int nz = B * SS, mz = B * N;
-  hipLaunchKernelGGL(opts_zero_kernel, dim3((unsigned)((nz + mz + 255) / 256)), dim3(256), 0, st, k.stat, nz, o.gtmax, mz);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(opts_iou_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(opts_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o);
-  EFFDET_CHECK_LAUNCH();
-  if (grad) {
-    const long long groups = (A / 9) * dld / 4;
-    k.ncb = (int)((groups + 256 * FG_IT - 1) / (256 * FG_IT));
-    if (k.ncb > cls_blocks_max(A, num_classes)) return EFFDET_EINVAL;
-    dim3 g1((unsigned)k.ncb, B);
-    if (dtype == EFFDET_F32) hipLaunchKernelGGL((opts_cls_pix_kernel<float, false, FG_IT>), g1, dim3(256), 0, st, k, o.f);
-    else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL((opts_cls_pix_kernel<split_t, false, FG_IT>), g1, dim3(256), 0, st, k, o.f);
-    else hipLaunchKernelGGL((opts_cls_pix_kernel<bf16_t, false, FG_IT>), g1, dim3(256), 0, st, k, o.f);
-  } else {
-    const long long groups = (A * num_classes + 3) / 4;
-    k.ncb = (int)((groups + 256 * CLS_IT - 1) / (256 * CLS_IT));
-    if (k.ncb > cls_blocks_max(A, num_classes)) return EFFDET_EINVAL;
-    hipLaunchKernelGGL(opts_cls_kernel, dim3((unsigned)k.ncb, B), dim3(256), 0, st, k, o.f);
-  }
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(opts_final_kernel, dim3(1), dim3(1024), 0, st, k, o.reg_weight);
-  EFFDET_CHECK_LAUNCH();
-  if (opts->box_kind == 0) return EFFDET_OK;
-  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
-}
-
-}  // namespace
-
-extern "C" long long effdet_loss_opts_workspace_bytes(int B, long long A, int num_classes, int N) {
-  LossK k{}; OptsK o{};
-  return (long long)carve_loss_opts(k, o, nullptr, B, A, num_classes, N);
+  return loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, stream, [&](const LossK& k, hipStream_t st) {
+    by_dtype<true>(dtype, [&](auto t) {
+      hipLaunchKernelGGL(box_loss_bwd_reg_kernel<typename decltype(t)::type>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k, kind,
+                         weight);
+    });
+  });
 }
 
 extern "C" int effdet_loss_opts_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
@@ -1111,22 +895,11 @@ extern "C" int effdet_loss_opts_bwd_cls(const float* cls, const float* annots, c
                                         effdet_stream_t stream) {
   if (!cls || !annots || !gscale || !workspace || !dcls) return EFFDET_EINVAL;
   if (!loss_opts_ok(opts) || B < 1 || B > 65535 || N < 1 || A < 1 || num_classes < 1 || dld < 0) return EFFDET_EINVAL;
-  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16) return EFFDET_EINVAL;
-  if (dld && (A % 9 || num_classes % 4 || dld % 4 || dld < 9 * num_classes)) return EFFDET_EINVAL;
-  if (A * num_classes >= 0x7fffffffLL || (dld && (A / 9) * dld >= 0x7fffffffLL)) return EFFDET_EUNSUPPORTED;
-  LossK k{}; k.cls = cls; k.annots = annots; k.gscale = gscale; k.dcls = dcls; k.B = B; k.nc = num_classes; k.N = N; k.A = A; k.dld = dld;
+  if (const int rc = check_dcls(dcls, dld, dtype, false, A, num_classes)) return rc;
+  if (A * num_classes >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
+  LossK k = loss_args(cls, nullptr, nullptr, annots, B, A, num_classes, N); k.gscale = gscale; k.dcls = dcls; k.dld = dld;
   carve_loss(k, const_cast<void*>(workspace), B, A);
-  const FocalP f{opts->alpha, opts->gamma, opts->label_smoothing};
-  hipStream_t st = (hipStream_t)stream;
-  const long long groups = dld ? (A / 9) * dld / 4 : (A * num_classes + 3) / 4;
-  dim3 g1((unsigned)((groups + 255) / 256), B);
-  if (dtype == EFFDET_F32) {
-    if (dld) hipLaunchKernelGGL((opts_cls_pix_kernel<float, true, 1>), g1, dim3(256), 0, st, k, f);
-    else hipLaunchKernelGGL(opts_bwd_cls_kernel<float>, g1, dim3(256), 0, st, k, f);
-  } else {
-    if (dld) hipLaunchKernelGGL((opts_cls_pix_kernel<bf16_t, true, 1>), g1, dim3(256), 0, st, k, f);
-    else hipLaunchKernelGGL(opts_bwd_cls_kernel<bf16_t>, g1, dim3(256), 0, st, k, f);
-  }
+  launch_bwd_cls(k, FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, dtype, (hipStream_t)stream);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
@@ -1138,18 +911,8 @@ extern "C" int effdet_loss_opts_bwd_reg(const float* reg, const float* anchors, 
   if (opts->box_kind != 0)
     return effdet_box_loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, opts->box_kind,
                                    opts->box_weight, stream);
-  if (!reg || !anchors || !annots || !gscale || !workspace || !dreg || B < 1 || N < 1 || A < 1) return EFFDET_EINVAL;
-  if (dtype != EFFDET_F32 && dtype != EFFDET_BF16 && dtype != EFFDET_F32_SPLIT) return EFFDET_EINVAL;
-  if (reg_ld && (reg_ld < 36 || reg_ld % 4 || A % 9)) return EFFDET_EINVAL;
-  if (dtype == EFFDET_F32_SPLIT && (!reg_ld || reg_ld % 32 || ((unsigned long long)dreg & 127ull))) return EFFDET_EINVAL;
-  LossK k{}; k.reg = reg; k.anchors = anchors; k.annots = annots; k.gscale = gscale; k.dreg = dreg;
-  k.B = B; k.N = N; k.A = A; k.reg_ld = reg_ld;
-  carve_loss(k, const_cast<void*>(workspace), B, A);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(grid_for((long long)B * A));
-  if (dtype == EFFDET_F32) hipLaunchKernelGGL(opts_bwd_reg_kernel<float>, grid, dim3(256), 0, st, k, opts->beta, opts->reg_weight);
-  else if (dtype == EFFDET_F32_SPLIT) hipLaunchKernelGGL(opts_bwd_reg_kernel<split_t>, grid, dim3(256), 0, st, k, opts->beta, opts->reg_weight);
-  else hipLaunchKernelGGL(opts_bwd_reg_kernel<bf16_t>, grid, dim3(256), 0, st, k, opts->beta, opts->reg_weight);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
+  if (B < 1 || N < 1 || A < 1) return EFFDET_EINVAL;
+  return loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, stream, [&](const LossK& k, hipStream_t st) {
+    launch_bwd_reg(k, KneeBeta{opts->beta}, opts->reg_weight, dtype, st);
+  });
 }

@@ -316,11 +316,10 @@ LOSS_FWD_GRAD = os.environ.get('EFFDET_LOSS_FWD_GRAD', '1') == '1'    # A/B swit
 
 class _HeadLossFn(torch.autograd.Function):
     """RetinaHead + focal / smooth-L1 loss as ONE node: the loss kernel hands the head's data-gradient convs
-    d(logit) and d(reg) directly in the activation dtype (no fp32 gradient tensor round trip).  box: None = smooth-L1 (the
-    ops.focal_loss_* calls), an ops.BoxLossOptions of an IoU kind = the ops.box_loss_* calls, which keep the output contract of
-    d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them).  loss: None =
-    the reference's constants (the calls above), a non-default ops.LossOptions = the ops.loss_opts_* calls with box inside them; they
-    keep the same contracts for d(logit) and d(reg)."""
+    d(logit) and d(reg) directly in the activation dtype (no fp32 gradient tensor round trip).  box: None = smooth-L1, an
+    ops.BoxLossOptions of an IoU kind = that term in its place; loss: None = the reference's constants, a non-default ops.LossOptions =
+    the options.  The ops.loss_opts_* calls choose the entry points for either; every choice keeps the output contract of d(logit)
+    and d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them)."""
 
     @staticmethod
     def forward(ctx, dtype, num_classes, anchors, annots, train, box, loss, *args):
@@ -333,18 +332,10 @@ class _HeadLossFn(torch.autograd.Function):
             # ONE pass over the 15.7 MB/image of probabilities: losses + d(logits) for an upstream gradient of one, already in
             # the pixel-major, 64-channel-padded rows the head's gradient convs read; cls itself is not kept for backward
             dld = (9 * nc + 63) // 64 * 64
-            if loss is not None:
-                losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], loss=loss, box=box)
-            elif box is None:
-                losses, ws, dpix = ops.focal_loss_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5])    # (split-layout head: see functional.head_uses_split)
-            else:
-                losses, ws, dpix = ops.box_loss_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], options=box)
+            losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], loss=loss, box=box)    # (split-layout head: see functional.head_uses_split)
             ctx.saved = (saved, None, reg, anchors, annots, ws, dtype, dpix, dld)
         else:
-            if loss is not None:
-                losses, ws = ops.loss_opts_fwd(cls, reg, anchors, annots, loss, box)
-            else:
-                losses, ws = ops.focal_loss_fwd(cls, reg, anchors, annots) if box is None else ops.box_loss_fwd(cls, reg, anchors, annots, box)
+            losses, ws = ops.loss_opts_fwd(cls, reg, anchors, annots, loss, box)
             ctx.saved = (saved, cls, reg, anchors, annots, ws, dtype, None, 0) if train else None
         return losses[0:1].clone(), losses[1:2].clone()
 
@@ -360,12 +351,7 @@ class _HeadLossFn(torch.autograd.Function):
         if dpix is not None:
             split = saved[5]
             rld = 64 if split else 0                # split layout: d(reg) pixel-major, 36 -> 64 channels (two [hi|lo] groups)
-            if ctx.loss is not None:
-                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, loss=ctx.loss, box=ctx.box)
-            elif ctx.box is None:
-                dreg = ops.focal_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split)
-            else:
-                dreg = ops.box_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, options=ctx.box)
+            dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, loss=ctx.loss, box=ctx.box)
             with ops.unpack_batch():                               # the head's 10 weight-gradient unpacks: one launch
                 dp, g = Fn.head_bwd(saved, dpix, dreg, dtype, dcls_ld=dld, cls_gscale=gscale[0:1], dreg_ld=rld, in_split=split)
         else:
@@ -373,13 +359,12 @@ class _HeadLossFn(torch.autograd.Function):
             dld = (9 * nc + 63) // 64 * 64 if nc % 4 == 0 else 0      # d(logits) straight into the pixel-major, 64-channel-padded rows the head's gradient convs read
             if ctx.loss is not None:
                 dcls = ops.loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, ctx.loss, dld=dld)
-                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, loss=ctx.loss, box=ctx.box)
-            elif dld:
+            elif dld:                                 # the reference's constants: the combined calls (smooth-L1 d(reg) in the same launch pair)
                 dcls, dreg = ops.focal_loss_bwd_pix(cls, reg, anchors, annots, gscale, ws, dtype, dld)
             else:
                 dcls, dreg = ops.focal_loss_bwd(cls, reg, anchors, annots, gscale, ws, dtype)
-            if ctx.loss is None and ctx.box is not None:      # (the class gradient above is the focal term's either way; its smooth-L1 d(reg) is replaced)
-                dreg = ops.box_loss_bwd_reg(reg, anchors, annots, gscale, ws, dtype, options=ctx.box)
+            if ctx.loss is not None or ctx.box is not None:      # (the class gradient above is the focal term's either way; a smooth-L1 d(reg) is replaced)
+                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, loss=ctx.loss, box=ctx.box)
             with ops.unpack_batch():
                 dp, g = Fn.head_bwd(saved, dcls, dreg, dtype, dcls_ld=dld)
         ctx.saved = None

@@ -1285,62 +1285,9 @@ def model_nms(model, boxes, score, label):
 
 
 # ----------------------------------------------------------------------------- loss
-def focal_loss_fwd(cls, reg, anc, annots):
-    B, A, nc = cls.shape
-    N = annots.shape[1]
-    nbytes = int(L.lib().effdet_loss_workspace_bytes(B, A, nc))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
-    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
-    L.check(L.lib().effdet_focal_loss_fwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws),
-                                          nbytes, B, A, nc, N, L.stream_ptr()), 'effdet_focal_loss_fwd')
-    return losses, ws
-
-
-def focal_loss_bwd(cls, reg, anc, annots, gscale, ws, dtype):
-    B, A, nc = cls.shape
-    dcls = torch.empty((B, A, nc), dtype=dtype, device=cls.device)
-    dreg = torch.empty((B, A, 4), dtype=dtype, device=cls.device)
-    L.check(L.lib().effdet_focal_loss_bwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls),
-                                          L.ptr(dreg), L.dtype_code(dtype), B, A, nc, annots.shape[1], L.stream_ptr()),
-            'effdet_focal_loss_bwd')
-    return dcls, dreg
-
-
-def focal_loss_bwd_pix(cls, reg, anc, annots, gscale, ws, dtype, dld):
-    """focal_loss_bwd with d(cls logits) pixel-major and channel-padded: -> (dcls_pix [B, A/9, dld], dreg [B, A, 4])."""
-    B, A, nc = cls.shape
-    dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
-    dreg = torch.empty((B, A, 4), dtype=dtype, device=cls.device)
-    L.check(L.lib().effdet_focal_loss_bwd_pix(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls),
-                                              dld, L.ptr(dreg), L.dtype_code(dtype), B, A, nc, annots.shape[1],
-                                              L.stream_ptr()), 'effdet_focal_loss_bwd_pix')
-    return dcls, dreg
-
-
-def focal_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False):
-    """Training fast path: -> (losses [2], ws, dcls_pix [B, A/9, dld]) in one pass over cls; dcls_pix is the gradient wrt the
-    logits for an upstream gradient of ONE (the caller scales downstream, see effdet_hip.h)."""
-    B, A, nc = cls.shape
-    nbytes = int(L.lib().effdet_loss_workspace_bytes(B, A, nc))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
-    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
-    dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
-    L.check(L.lib().effdet_focal_loss_fwd_grad(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws),
-                                               nbytes, L.ptr(dcls), dld, L.F32_SPLIT if split else L.dtype_code(dtype), B, A, nc,
-                                               annots.shape[1], L.stream_ptr()), 'effdet_focal_loss_fwd_grad')
-    return losses, ws, dcls
-
-
-def focal_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False):
-    """-> dreg [B, A, 4], or with reg_ld pixel-major and channel-padded [B, A/9, reg_ld] (split=True: in the split layout)."""
-    B, A, _ = reg.shape
-    dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
-    L.check(L.lib().effdet_focal_loss_bwd_reg(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld,
-                                              L.F32_SPLIT if split else L.dtype_code(dtype), B, A, annots.shape[1],
-                                              L.stream_ptr()), 'effdet_focal_loss_bwd_reg')
-    return dreg
-
-
+# Three sets of entry points, one per kind of call: effdet_focal_loss_* (the reference's constants), effdet_box_loss_* (an IoU-family
+# box term: kind, weight) and effdet_loss_opts_* (non-default LossOptions: the struct, with the box term inside it).  They take the same
+# arguments, the extra ones just before the stream.  Each public function below names the call it wants; _loss_entry chooses the set.
 BOX_LOSS_KINDS = {'smooth_l1': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}     # EFFDET_BOX_LOSS_* (0: the effdet_focal_loss_* calls)
 
 
@@ -1383,52 +1330,6 @@ def _box_loss_args(options):
     if not isinstance(options, BoxLossOptions):
         raise TypeError('box loss options must be a BoxLossOptions or None, not %r' % (options,))
     return None if options.is_default() else (BOX_LOSS_KINDS[options.kind], options.weight)
-
-
-def box_loss_fwd(cls, reg, anc, annots, options=None):
-    """focal_loss_fwd with the box term of options (None / 'smooth_l1': focal_loss_fwd itself) -> (losses [2], ws)."""
-    kw = _box_loss_args(options)
-    if kw is None:
-        return focal_loss_fwd(cls, reg, anc, annots)
-    lib = L.require('effdet_box_loss_fwd')
-    B, A, nc = cls.shape
-    nbytes = int(lib.effdet_loss_workspace_bytes(B, A, nc))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
-    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
-    L.check(lib.effdet_box_loss_fwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes, B, A, nc,
-                                    annots.shape[1], kw[0], kw[1], L.stream_ptr()), 'effdet_box_loss_fwd')
-    return losses, ws
-
-
-def box_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, options=None):
-    """focal_loss_fwd_grad with the box term of options -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
-    kw = _box_loss_args(options)
-    if kw is None:
-        return focal_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=split)
-    lib = L.require('effdet_box_loss_fwd_grad')
-    B, A, nc = cls.shape
-    nbytes = int(lib.effdet_loss_workspace_bytes(B, A, nc))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
-    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
-    dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
-    L.check(lib.effdet_box_loss_fwd_grad(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes,
-                                         L.ptr(dcls), dld, L.F32_SPLIT if split else L.dtype_code(dtype), B, A, nc, annots.shape[1],
-                                         kw[0], kw[1], L.stream_ptr()), 'effdet_box_loss_fwd_grad')
-    return losses, ws, dcls
-
-
-def box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, options=None):
-    """focal_loss_bwd_reg with the box term of options: d(reg) in the same three layouts, from the workspace of any forward call."""
-    kw = _box_loss_args(options)
-    if kw is None:
-        return focal_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=reg_ld, split=split)
-    lib = L.require('effdet_box_loss_bwd_reg')
-    B, A, _ = reg.shape
-    dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
-    L.check(lib.effdet_box_loss_bwd_reg(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld,
-                                        L.F32_SPLIT if split else L.dtype_code(dtype), B, A, annots.shape[1], kw[0], kw[1],
-                                        L.stream_ptr()), 'effdet_box_loss_bwd_reg')
-    return dreg
 
 
 def _f32(v):
@@ -1501,66 +1402,132 @@ def _loss_opts_struct(loss, box=None):
                       1 if loss.low_quality else 0, kind, weight)
 
 
-def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None):
-    """box_loss_fwd with the options of loss (None / the defaults: box_loss_fwd itself) -> (losses [2], ws)."""
+def _loss_entry(stem, loss=None, box=None):
+    """-> (the entry point of the call `stem` for (loss, box), its name, its extra arguments, whether it is of the options set)."""
     o = _loss_opts_struct(loss, box)
-    if o is None:
-        return box_loss_fwd(cls, reg, anc, annots, box)
-    lib = L.require('effdet_loss_opts_fwd', 'effdet_loss_opts_workspace_bytes')
+    if o is not None:
+        name, extra = 'effdet_loss_opts_' + stem, (C.byref(o),)
+    else:
+        kw = _box_loss_args(box)
+        name, extra = ('effdet_focal_loss_' if kw is None else 'effdet_box_loss_') + stem, kw or ()
+    return getattr(L.require(name), name), name, extra, o is not None
+
+
+def _dtype_code(dtype, split):
+    return L.F32_SPLIT if split else L.dtype_code(dtype)
+
+
+def _loss_forward(cls, reg, anc, annots, loss, box, grad=None):
+    """Forward of (loss, box) -> (losses [2], ws), and with grad = (dtype, dld, split) also dcls_pix [B, A/9, dld]."""
+    fn, name, extra, opts = _loss_entry('fwd_grad' if grad else 'fwd', loss, box)
     B, A, nc = cls.shape
     N = annots.shape[1]
-    nbytes = int(lib.effdet_loss_opts_workspace_bytes(B, A, nc, N))
+    if opts:
+        nbytes = int(L.require('effdet_loss_opts_workspace_bytes').effdet_loss_opts_workspace_bytes(B, A, nc, N))
+    else:
+        nbytes = int(L.lib().effdet_loss_workspace_bytes(B, A, nc))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
     losses = torch.empty(2, dtype=torch.float32, device=cls.device)
-    L.check(lib.effdet_loss_opts_fwd(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes, B, A, nc, N,
-                                     C.byref(o), L.stream_ptr()), 'effdet_loss_opts_fwd')
-    return losses, ws
+    out, args = (losses, ws), ()
+    if grad:
+        dtype, dld, split = grad
+        dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
+        out, args = (losses, ws, dcls), (L.ptr(dcls), dld, _dtype_code(dtype, split))
+    L.check(fn(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes, *args, B, A, nc, N, *extra,
+               L.stream_ptr()), name)
+    return out
+
+
+def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box):
+    """-> dreg [B, A, 4], or with reg_ld pixel-major and channel-padded [B, A/9, reg_ld] (split=True: in the split layout), from the
+    workspace of a forward call with the same (loss, box)."""
+    fn, name, extra, _ = _loss_entry('bwd_reg', loss, box)
+    B, A, _ = reg.shape
+    dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
+    L.check(fn(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld, _dtype_code(dtype, split), B, A,
+               annots.shape[1], *extra, L.stream_ptr()), name)
+    return dreg
+
+
+def _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld, loss=None):
+    """d(logits) [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld].  The reference's constants: the combined entry
+    points (dld None: the flat one), which also write the smooth-L1 dreg [B, A, 4] -> (dcls, dreg); options: the class gradient
+    alone -> dcls."""
+    B, A, nc = cls.shape
+    dcls = torch.empty((B, A // 9, dld) if dld else (B, A, nc), dtype=dtype, device=cls.device)
+    if loss is not None:
+        fn, name, extra, _ = _loss_entry('bwd_cls', loss)
+        L.check(fn(L.ptr(cls), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls), dld, L.dtype_code(dtype), B, A, nc,
+                   annots.shape[1], *extra, L.stream_ptr()), name)
+        return dcls
+    name = 'effdet_focal_loss_bwd' if dld is None else 'effdet_focal_loss_bwd_pix'
+    dreg = torch.empty((B, A, 4), dtype=dtype, device=cls.device)
+    L.check(getattr(L.lib(), name)(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls),
+                                   *(() if dld is None else (dld,)), L.ptr(dreg), L.dtype_code(dtype), B, A, nc, annots.shape[1],
+                                   L.stream_ptr()), name)
+    return dcls, dreg
+
+
+def focal_loss_fwd(cls, reg, anc, annots):
+    return _loss_forward(cls, reg, anc, annots, None, None)
+
+
+def focal_loss_bwd(cls, reg, anc, annots, gscale, ws, dtype):
+    return _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, None)
+
+
+def focal_loss_bwd_pix(cls, reg, anc, annots, gscale, ws, dtype, dld):
+    """focal_loss_bwd with d(cls logits) pixel-major and channel-padded: -> (dcls_pix [B, A/9, dld], dreg [B, A, 4])."""
+    return _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld)
+
+
+def focal_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False):
+    """Training fast path: -> (losses [2], ws, dcls_pix [B, A/9, dld]) in one pass over cls; dcls_pix is the gradient wrt the
+    logits for an upstream gradient of ONE (the caller scales downstream, see effdet_hip.h)."""
+    return _loss_forward(cls, reg, anc, annots, None, None, (dtype, dld, split))
+
+
+def focal_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False):
+    """-> dreg [B, A, 4], or with reg_ld pixel-major and channel-padded [B, A/9, reg_ld] (split=True: in the split layout)."""
+    return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, None, None)
+
+
+def box_loss_fwd(cls, reg, anc, annots, options=None):
+    """focal_loss_fwd with the box term of options (None / 'smooth_l1': focal_loss_fwd itself) -> (losses [2], ws)."""
+    return _loss_forward(cls, reg, anc, annots, None, options)
+
+
+def box_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, options=None):
+    """focal_loss_fwd_grad with the box term of options -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
+    return _loss_forward(cls, reg, anc, annots, None, options, (dtype, dld, split))
+
+
+def box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, options=None):
+    """focal_loss_bwd_reg with the box term of options: d(reg) in the same three layouts, from the workspace of any forward call."""
+    return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, None, options)
+
+
+def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None):
+    """box_loss_fwd with the options of loss (None / the defaults: box_loss_fwd itself) -> (losses [2], ws)."""
+    return _loss_forward(cls, reg, anc, annots, loss, box)
 
 
 def loss_opts_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, loss=None, box=None):
     """box_loss_fwd_grad with the options of loss -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
-    o = _loss_opts_struct(loss, box)
-    if o is None:
-        return box_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=split, options=box)
-    lib = L.require('effdet_loss_opts_fwd_grad', 'effdet_loss_opts_workspace_bytes')
-    B, A, nc = cls.shape
-    N = annots.shape[1]
-    nbytes = int(lib.effdet_loss_opts_workspace_bytes(B, A, nc, N))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
-    losses = torch.empty(2, dtype=torch.float32, device=cls.device)
-    dcls = torch.empty((B, A // 9, dld), dtype=dtype, device=cls.device)
-    L.check(lib.effdet_loss_opts_fwd_grad(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(losses), L.ptr(ws), nbytes,
-                                          L.ptr(dcls), dld, L.F32_SPLIT if split else L.dtype_code(dtype), B, A, nc, N, C.byref(o),
-                                          L.stream_ptr()), 'effdet_loss_opts_fwd_grad')
-    return losses, ws, dcls
+    return _loss_forward(cls, reg, anc, annots, loss, box, (dtype, dld, split))
 
 
 def loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, loss, dld=0):
     """d(logits) of the class term with the (non-default) options of loss, from the workspace of a forward call with them:
     [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld]."""
-    o = _loss_opts_struct(loss)
-    if o is None:
+    if _loss_opts_struct(loss) is None:
         raise ValueError('loss_opts_bwd_cls is the non-default path: the defaults are focal_loss_bwd / focal_loss_bwd_pix')
-    lib = L.require('effdet_loss_opts_bwd_cls')
-    B, A, nc = cls.shape
-    dcls = torch.empty((B, A // 9, dld) if dld else (B, A, nc), dtype=dtype, device=cls.device)
-    L.check(lib.effdet_loss_opts_bwd_cls(L.ptr(cls), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls), dld, L.dtype_code(dtype), B, A,
-                                         nc, annots.shape[1], C.byref(o), L.stream_ptr()), 'effdet_loss_opts_bwd_cls')
-    return dcls
+    return _loss_bwd_cls(cls, None, None, annots, gscale, ws, dtype, dld, loss)
 
 
 def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, loss=None, box=None):
     """box_loss_bwd_reg with the options of loss: d(reg) in the same three layouts."""
-    o = _loss_opts_struct(loss, box)
-    if o is None:
-        return box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=reg_ld, split=split, options=box)
-    lib = L.require('effdet_loss_opts_bwd_reg')
-    B, A, _ = reg.shape
-    dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
-    L.check(lib.effdet_loss_opts_bwd_reg(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld,
-                                         L.F32_SPLIT if split else L.dtype_code(dtype), B, A, annots.shape[1], C.byref(o),
-                                         L.stream_ptr()), 'effdet_loss_opts_bwd_reg')
-    return dreg
+    return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box)
 
 
 def pad_rows(src_map, cpad):

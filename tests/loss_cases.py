@@ -19,7 +19,7 @@ CODE_IGN, CODE_NEG = -2, -1                          # loss.hip's per-anchor cod
 
 # loss.hip constants the host test recomputes launch sizes from
 CHUNK = 64                                           # annotation rows compacted into LDS per pass of loss_assign_kernel
-CLS_IT, FG_IT = 8, 4                                 # 4-element groups per thread: loss_cls_kernel / loss_cls_grad_pix_kernel
+CLS_IT, FG_IT = 8, 4                                 # 4-element groups per thread: loss_cls_kernel / loss_cls_pix_kernel (forward + gradient)
 LANE_SUM_CHAINS = 192                                # loss_final_kernel's four-chain loop runs while i + 192 < n
 
 
@@ -34,7 +34,7 @@ def ncb_fwd(A, nc):
 
 
 def ncb_fwd_grad(A, nc):
-    """Workgroups per image of loss_cls_grad_pix_kernel at the padded pitch dld_for(nc)."""
+    """Workgroups per image of the forward + gradient loss_cls_pix_kernel at the padded pitch dld_for(nc)."""
     groups = (A // 9) * dld_for(nc) // 4
     return (groups + 256 * FG_IT - 1) // (256 * FG_IT)
 
