@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_conv_plan.h).
+include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -105,6 +105,13 @@ class EmaCtl(C.Structure):       # effdet_ema_ctl_t (include/effdet_ema.h)
 class LossOpts(C.Structure):     # effdet_loss_opts_t (include/effdet_loss_opts.h)
     _fields_ = [(n, C.c_float) for n in ('alpha', 'gamma', 'label_smoothing', 'beta', 'reg_weight', 'pos_iou', 'neg_iou')] + \
                [('low_quality', C.c_int), ('box_kind', C.c_int), ('box_weight', C.c_float)]
+
+
+ATSS_MAX_LEVELS, ATSS_MAX_TOPK = 8, 16               # EFFDET_ATSS_MAX_LEVELS, EFFDET_ATSS_MAX_TOPK
+
+
+class Atss(C.Structure):         # effdet_atss_t (include/effdet_atss.h)
+    _fields_ = [('topk', C.c_int), ('num_levels', C.c_int), ('level_start', C.c_longlong * (ATSS_MAX_LEVELS + 1))]
 
 
 class ConvPlanInfo(C.Structure):   # effdet_conv_plan_info_t (include/effdet_conv_plan.h)
@@ -263,6 +270,14 @@ LOSS_OPTS_SIGNATURES = {
     'effdet_loss_opts_bwd_cls': 'i:pppppiiiqiips',
     'effdet_loss_opts_bwd_reg': 'i:ppppppiiiqips',
 }
+# The ATSS matcher of the detection loss, declared in include/effdet_atss.h (same generation, same letters, same rule;
+# tests/test_atss_host.py compares this table and Atss with that header).  The forward twins of effdet_loss_opts_fwd / _fwd_grad with
+# an Atss struct (host memory, byref) between the options and the stream; the backward calls are the options' own.
+ATSS_SIGNATURES = {
+    'effdet_loss_atss_workspace_bytes': 'q:iqiip',
+    'effdet_loss_atss_fwd': 'i:ppppppqiqiipps',
+    'effdet_loss_atss_fwd_grad': 'i:ppppppqpiiiqiipps',
+}
 # The host-only query of the dense-conv launch plan, declared in include/effdet_conv_plan.h (same generation, same letters, same rule;
 # tests/test_conv_plan_cases_host.py compares this table and ConvPlanInfo with that header).
 CONV_PLAN_SIGNATURES = {
@@ -291,7 +306,7 @@ def lib():
         _lib = cand
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
-                list(LOSS_OPTS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()):
+                list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

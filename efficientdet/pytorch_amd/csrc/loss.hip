@@ -18,6 +18,12 @@
 //                       exact), first per workgroup in LDS, then one global atomic per (workgroup, row).  Then the same grid: bands
 //                       on best; with low_quality the IoU loop once more, promoting an anchor whose IoU with any row equals that
 //                       row's gtmax (> 0); then the same tail (assign_tail)
+//              atss_select_kernel, atss_assign_kernel   the ATSS matcher (include/effdet_atss.h): one workgroup per (valid row, image)
+//                       selects the row's topk nearest anchors of every level (64-bit keys (bits of d2) << 32 | index within the level:
+//                       per-thread sorted lists in registers, then topk rounds of a workgroup arg-min) -> kth[b][n][level], the
+//                       topk-th key, and thr[b][n] = mean + std of the candidates' IoUs; then loss_assign_kernel's grid: an anchor is
+//                       a candidate of row n iff its own key <= kth[b][n][its level] (the same device function forms both keys), positive
+//                       iff its IoU >= thr and its centre is inside the box; the same tail
 //   cls      loss_cls_kernel<F>: one thread per 4 class probabilities (16-byte loads): focal BCE with the reference's clamp to
 //            [1e-4, 1-1e-4], one partial per workgroup in part_cls[b][block].  loss_cls_pix_kernel<T, F, GRAD_ONLY, IT>: the same
 //            sum AND d/d(logit) in one pass, or the gradient alone, written pixel-major (see there)
@@ -32,6 +38,7 @@
 #include "common.h"
 #include "../../../include/effdet_box_loss.h"
 #include "../../../include/effdet_loss_opts.h"
+#include "../../../include/effdet_atss.h"
 
 namespace {
 
@@ -53,6 +60,13 @@ struct LossK {
 struct OptsK {
   float pos_iou, neg_iou; int low_quality;
   int* gtmax; float* best; int* barg;         // [B][N] bit patterns, [B][A], [B][A]
+};
+
+// the ATSS matcher: topk, the levels of the anchor table, and the buffers between its two passes
+struct AtssK {
+  int topk, num_levels;
+  long long ls[EFFDET_ATSS_MAX_LEVELS + 1];
+  unsigned long long* kth; float* thr;        // [B][N][EFFDET_ATSS_MAX_LEVELS] keys, [B][N]
 };
 
 // stat[b][2] holds the number of positive anchors as an int32 bit pattern (integer atomics: exact, order-independent)
@@ -152,6 +166,34 @@ __device__ __forceinline__ int compact_chunk(const LossK& p, int b, int n0, floa
   }
   return c;
 }
+
+// ---- ATSS (include/effdet_atss.h)
+// The selection key of anchor `an` (index i within its level) for the box at r[0..3]: (bits of d2) << 32 | i.  d2 >= 0, so its bit
+// pattern orders as the float does, and the index breaks a distance tie towards the lower anchor.  BOTH ATSS kernels form the key with
+// THIS function (no contraction, as assign_iou): the candidate test of the assign pass compares a key with a k-th smallest of the same keys
+__device__ __forceinline__ unsigned long long atss_key(const float4 an, const float* r, unsigned i) {
+#pragma clang fp contract(off)
+  const float acx = 0.5f * (an.x + an.z), acy = 0.5f * (an.y + an.w);
+  const float gcx = 0.5f * (r[0] + r[2]), gcy = 0.5f * (r[1] + r[3]);
+  const float dx = acx - gcx, dy = acy - gcy;
+  const float d2 = dx * dx + dy * dy;
+  return ((unsigned long long)__float_as_uint(d2) << 32) | i;
+}
+
+// mmdet's centre test: the anchor's centre lies more than 0.01 inside every side of the box
+__device__ __forceinline__ bool atss_inside(const float4 an, const float* r) {
+#pragma clang fp contract(off)
+  const float acx = 0.5f * (an.x + an.z), acy = 0.5f * (an.y + an.w);
+  return fminf(fminf(acx - r[0], acy - r[1]), fminf(r[2] - acx, r[3] - acy)) > 0.01f;
+}
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o) {
+  const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+constexpr unsigned long long ATSS_NO_KEY = ~0ull;     // above every key (d2's sign bit is clear)
+constexpr int ATSS_MAX_CAND = EFFDET_ATSS_MAX_LEVELS * EFFDET_ATSS_MAX_TOPK;
 
 // the regression target of anchor `an` for the annotation at g[0..3] (models/losses.py:119-137)
 __device__ __forceinline__ void encode_target(const float4 an, const float* g, float* t) {
@@ -319,6 +361,128 @@ __global__ __launch_bounds__(256) void opts_assign_kernel(const LossK p, const O
     }
   }
   assign_tail(p, b, a, ok, ok && any_valid, best < o.neg_iou, (best >= o.pos_iou || promoted) && barg >= 0, barg, an, knee);
+}
+
+// ---- the ATSS matcher
+// One workgroup per (row, image); a pad row exits at once.  Per level: every thread strides over the level's anchors and keeps its K
+// smallest keys as a sorted list in registers (K >= topk is a compile-time bound: the insertion and the pop are fully unrolled, so the
+// list never becomes a runtime-indexed array in scratch); then min(topk, level size) rounds, each the workgroup's arg-min over the
+// heads of the lists (keys are distinct, so the minimum names its owner), which the owner pops.  The winners, in level then rank
+// order, are the row's candidates; the last winner's key of a level is kth[b][n][level].  Then one IoU per candidate, and thread 0
+// forms thr sequentially in that order.
+template <int K>
+__global__ __launch_bounds__(256) void atss_select_kernel(const LossK p, const AtssK t) {
+  const int n = blockIdx.x, b = blockIdx.y;
+  const float* rp = p.annots + ((long long)b * p.N + n) * 5;
+  if (rp[4] == -1.0f) return;
+  const float r[4] = {rp[0], rp[1], rp[2], rp[3]};
+  __shared__ unsigned long long wmin[2][4];
+  __shared__ long long cand[ATSS_MAX_CAND];
+  __shared__ float ciou[ATSS_MAX_CAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float4* anc = (const float4*)p.anchors;
+  int cnt = 0, round = 0;
+  for (int l = 0; l < t.num_levels; ++l) {
+    const long long base = t.ls[l], size = t.ls[l + 1] - base;
+    unsigned long long keys[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) keys[j] = ATSS_NO_KEY;
+    for (long long i = threadIdx.x; i < size; i += 256) {
+      const unsigned long long key = atss_key(anc[base + i], r, (unsigned)i);
+      if (key < keys[K - 1]) {
+#pragma unroll
+        for (int j = K - 1; j > 0; --j) {                    // new[j] = min(old[j], max(old[j - 1], key)), from the top down
+          const unsigned long long m = keys[j - 1] > key ? keys[j - 1] : key;
+          keys[j] = keys[j] < m ? keys[j] : m;
+        }
+        keys[0] = keys[0] < key ? keys[0] : key;
+      }
+    }
+    const int k = (int)(size < (long long)t.topk ? size : (long long)t.topk);
+    for (int q = 0; q < k; ++q, ++round) {
+      unsigned long long m = keys[0];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { const unsigned long long v = shfl_xor_u64(m, o); m = v < m ? v : m; }
+      unsigned long long* w = wmin[round & 1];               // two slots: one barrier per round
+      if (lane == 0) w[wave] = m;
+      __syncthreads();
+      const unsigned long long m01 = w[0] < w[1] ? w[0] : w[1], m23 = w[2] < w[3] ? w[2] : w[3];
+      m = m01 < m23 ? m01 : m23;
+      if (keys[0] == m) {                                    // the owner pops its head
+#pragma unroll
+        for (int j = 0; j + 1 < K; ++j) keys[j] = keys[j + 1];
+        keys[K - 1] = ATSS_NO_KEY;
+      }
+      if (threadIdx.x == 0) {
+        cand[cnt] = base + (long long)(unsigned)m;
+        if (q == k - 1) t.kth[((long long)b * p.N + n) * EFFDET_ATSS_MAX_LEVELS + l] = m;
+      }
+      ++cnt;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < cnt) {
+    const float4 an = anc[cand[threadIdx.x]];
+    ciou[threadIdx.x] = assign_iou(an, (an.z - an.x) * (an.w - an.y), r);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    float sum = 0.f;
+    for (int j = 0; j < cnt; ++j) sum += ciou[j];
+    const float mean = sum / (float)cnt;
+    float sq = 0.f;
+    for (int j = 0; j < cnt; ++j) { const float d = ciou[j] - mean; sq += d * d; }
+    const float var = cnt < 2 ? 0.f : sq / (float)(cnt - 1);
+    t.thr[(long long)b * p.N + n] = mean + sqrtf(var);
+  }
+}
+
+// loss_assign_kernel's grid and loop with the ATSS rule: per valid row (thr and the kth keys of every level ride along in LDS) the
+// anchor's own key against the row's kth of the anchor's level, then the two tests of a positive; the best IoU among the rows it is
+// positive for with strict > (the first row wins a tie)
+__global__ __launch_bounds__(256) void atss_assign_kernel(const LossK p, const AtssK t, const KneeBeta knee) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  __shared__ float ann[64 * 5];
+  __shared__ float thr_s[64];
+  __shared__ unsigned long long kth_s[64 * EFFDET_ATSS_MAX_LEVELS];
+  __shared__ int nvalid_s;
+  float best = -1.0f; int barg = -1;
+  float4 an = make_float4(0, 0, 0, 0);
+  const bool ok = a < p.A;
+  int lev = 0; unsigned idx = 0;
+  if (ok) {
+    an = ((const float4*)p.anchors)[a];
+    while (lev + 1 < t.num_levels && a >= t.ls[lev + 1]) ++lev;
+    idx = (unsigned)(a - t.ls[lev]);
+  }
+  const float aarea = (an.z - an.x) * (an.w - an.y);
+  int total_valid = 0;
+  for (int n0 = 0; n0 < p.N; n0 += 64) {
+    __syncthreads();
+    if (threadIdx.x == 0) nvalid_s = compact_chunk(p, b, n0, ann);
+    __syncthreads();
+    const int c = nvalid_s;
+    total_valid += c;
+    for (int e = threadIdx.x; e < c * EFFDET_ATSS_MAX_LEVELS; e += 256) {
+      const int j = e / EFFDET_ATSS_MAX_LEVELS, l = e - j * EFFDET_ATSS_MAX_LEVELS;
+      const long long row = (long long)b * p.N + (int)ann[j * 5 + 4];
+      kth_s[e] = l < t.num_levels ? t.kth[row * EFFDET_ATSS_MAX_LEVELS + l] : 0ull;
+      if (l == 0) thr_s[j] = t.thr[row];
+    }
+    __syncthreads();
+    if (ok) {
+      for (int j = 0; j < c; ++j) {
+        const float* r = ann + j * 5;
+        if (atss_key(an, r, idx) > kth_s[j * EFFDET_ATSS_MAX_LEVELS + lev]) continue;
+        const float iou = assign_iou(an, aarea, r);
+        if (iou >= thr_s[j] && atss_inside(an, r) && iou > best) { best = iou; barg = (int)r[4]; }
+      }
+    }
+  }
+  assign_tail(p, b, a, ok, ok && total_valid > 0, barg < 0, barg >= 0, barg, an, knee);
+  if (blockIdx.x == 0 && threadIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
 }
 
 // 32-bit index arithmetic (A*nc < 2^31 is checked by the host): the 64-bit divisions per element of the first version made this HBM
@@ -623,6 +787,15 @@ size_t carve_loss_opts(LossK& k, OptsK& o, void* ws, int B, long long A, int num
   return head + c.off;
 }
 
+// carve_loss's layout, then kth [B][N][EFFDET_ATSS_MAX_LEVELS], thr [B][N] -> bytes
+size_t carve_loss_atss(LossK& k, AtssK& t, void* ws, int B, long long A, int num_classes, int N) {
+  const size_t head = carve_loss(k, ws, B, A, num_classes);
+  Carver c(ws ? (char*)ws + head : nullptr);
+  t.kth = c.take<unsigned long long>((size_t)B * N * EFFDET_ATSS_MAX_LEVELS);
+  t.thr = c.take<float>((size_t)B * N);
+  return head + c.off;
+}
+
 LossK loss_args(const float* cls, const float* reg, const float* anchors, const float* annots, int B, long long A, int nc, int N) {
   LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.B = B; k.nc = nc; k.N = N; k.A = A;
   return k;
@@ -644,6 +817,14 @@ bool loss_opts_ok(const effdet_loss_opts_t* o) {
   if (!(o->neg_iou >= 0.f && o->neg_iou <= o->pos_iou && o->pos_iou <= 1.f)) return false;
   if (o->low_quality != 0 && o->low_quality != 1) return false;
   return o->box_kind >= 0 && o->box_kind <= EFFDET_BOX_LOSS_CIOU;
+}
+
+bool atss_ok(const effdet_atss_t* t, long long A) {
+  if (!t || t->topk < 1 || t->topk > EFFDET_ATSS_MAX_TOPK || t->num_levels < 1 || t->num_levels > EFFDET_ATSS_MAX_LEVELS) return false;
+  if (t->level_start[0] != 0 || t->level_start[t->num_levels] != A) return false;
+  for (int l = 0; l < t->num_levels; ++l)
+    if (t->level_start[l + 1] <= t->level_start[l]) return false;
+  return true;
 }
 
 inline bool dtype_ok(int dtype, bool split) { return dtype == EFFDET_F32 || dtype == EFFDET_BF16 || (split && dtype == EFFDET_F32_SPLIT); }
@@ -746,6 +927,31 @@ int loss_opts_forward(const float* cls, const float* reg, const float* anchors, 
     hipLaunchKernelGGL(opts_iou_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o);
     EFFDET_CHECK_LAUNCH();
     hipLaunchKernelGGL(opts_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o, KneeBeta{opts->beta});
+    EFFDET_CHECK_LAUNCH();
+    return EFFDET_OK;
+  });
+  if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
+  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
+}
+
+// both forward entry points of the ATSS matcher: loss_opts_forward with the ATSS assign path
+int loss_atss_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
+                      long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
+                      int N, const effdet_loss_opts_t* opts, const effdet_atss_t* atss, effdet_stream_t stream) {
+  if (!loss_opts_ok(opts) || opts->low_quality != 0 || B < 1 || N < 1 || A < 1 || num_classes < 1 || !atss_ok(atss, A)) return EFFDET_EINVAL;
+  LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = loss_forward(k0, FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, opts->reg_weight, workspace, workspace_bytes,
+                              effdet_loss_atss_workspace_bytes(B, A, num_classes, N, atss), grad, dtype, st, [&](LossK& k) -> int {
+    AtssK t{}; t.topk = atss->topk; t.num_levels = atss->num_levels;      // (A < 2^31 has been checked: an index within a level fits the low half of a key)
+    for (int l = 0; l <= atss->num_levels; ++l) t.ls[l] = atss->level_start[l];
+    carve_loss_atss(k, t, workspace, B, A, num_classes, N);
+    hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((B * SS + 255) / 256)), dim3(256), 0, st, k.stat, B * SS);
+    EFFDET_CHECK_LAUNCH();
+    if (t.topk <= 9) hipLaunchKernelGGL(atss_select_kernel<9>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
+    else hipLaunchKernelGGL(atss_select_kernel<EFFDET_ATSS_MAX_TOPK>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
+    EFFDET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(atss_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, t, KneeBeta{opts->beta});
     EFFDET_CHECK_LAUNCH();
     return EFFDET_OK;
   });
@@ -915,4 +1121,25 @@ extern "C" int effdet_loss_opts_bwd_reg(const float* reg, const float* anchors, 
   return loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, stream, [&](const LossK& k, hipStream_t st) {
     launch_bwd_reg(k, KneeBeta{opts->beta}, opts->reg_weight, dtype, st);
   });
+}
+
+extern "C" long long effdet_loss_atss_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_atss_t* atss) {
+  if (!atss_ok(atss, A)) return EFFDET_EINVAL;
+  LossK k{}; AtssK t{};
+  return (long long)carve_loss_atss(k, t, nullptr, B, A, num_classes, N);
+}
+
+extern "C" int effdet_loss_atss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                    void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
+                                    const effdet_loss_opts_t* opts, const effdet_atss_t* atss, effdet_stream_t stream) {
+  return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
+                           num_classes, N, opts, atss, stream);
+}
+
+extern "C" int effdet_loss_atss_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                         void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
+                                         long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
+                                         const effdet_atss_t* atss, effdet_stream_t stream) {
+  return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
+                           num_classes, N, opts, atss, stream);
 }

@@ -117,18 +117,35 @@ class Anchors(nn.Module):
 class FocalLoss(nn.Module):
     """models/losses.py:29-152 as two HIP passes; forward only (training uses the fused head+loss node).  box_loss: an
     ops.BoxLossOptions puts an IoU-family loss in the place of smooth-L1 (None: the reference's term); loss: an ops.LossOptions sets
-    focal alpha / gamma, label smoothing, the smooth-L1 knee and weight and the matcher's rules (None: the reference's constants)."""
+    focal alpha / gamma, label smoothing, the smooth-L1 knee and weight and the matcher's rules (None: the reference's constants);
+    matcher: an ops.ATSSOptions assigns by ATSS in place of the IoU bands (None: the bands).  With a matcher, forward takes the
+    anchor count of every pyramid level as `levels`; without it the levels are read off the table (a level starts where the anchors
+    double in size), which costs one device -> host sync."""
 
-    def __init__(self, box_loss=None, loss=None):
+    def __init__(self, box_loss=None, loss=None, matcher=None):
         super().__init__()
         ops._box_loss_args(box_loss)                            # (TypeError on anything but BoxLossOptions / None)
         ops._loss_opts_struct(loss)                             # (TypeError on anything but LossOptions / None)
+        ops.check_matcher(matcher, loss)                        # (TypeError / ValueError: a matcher with bands or low_quality)
         self.box_loss = box_loss
         self.loss = loss
+        self.matcher = matcher
 
-    def forward(self, classifications, regressions, anchors, annotations):
-        losses, _ = ops.loss_opts_fwd(classifications.contiguous(), regressions.contiguous(), anchors.contiguous(),
-                                      annotations.contiguous().float(), getattr(self, 'loss', None), self.box_loss)
+    @staticmethod
+    def table_levels(anchors):
+        """Anchor count per level of an [1, A, 4] table of 9 anchors per pixel: a level starts where slot 0's width grows by half."""
+        w = (anchors[0, ::9, 2] - anchors[0, ::9, 0]).float()
+        cut = [0] + (torch.nonzero(w[1:] > 1.5 * w[:-1]).reshape(-1) + 1).tolist() + [w.numel()]
+        return [9 * (b - a) for a, b in zip(cut[:-1], cut[1:])]
+
+    def forward(self, classifications, regressions, anchors, annotations, levels=None):
+        matcher = getattr(self, 'matcher', None)                # (a criterion pickled before the option existed has no such attribute)
+        anchors = anchors.contiguous()
+        if matcher is not None and levels is None:
+            levels = self.table_levels(anchors)
+        losses, _ = ops.loss_opts_fwd(classifications.contiguous(), regressions.contiguous(), anchors,
+                                      annotations.contiguous().float(), getattr(self, 'loss', None), self.box_loss,
+                                      matcher=matcher, levels=levels)
         return losses[0:1], losses[1:2]
 
 
@@ -319,23 +336,28 @@ class _HeadLossFn(torch.autograd.Function):
     d(logit) and d(reg) directly in the activation dtype (no fp32 gradient tensor round trip).  box: None = smooth-L1, an
     ops.BoxLossOptions of an IoU kind = that term in its place; loss: None = the reference's constants, a non-default ops.LossOptions =
     the options.  The ops.loss_opts_* calls choose the entry points for either; every choice keeps the output contract of d(logit)
-    and d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them)."""
+    and d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them).
+    An ops.ATSSOptions may follow the head's parameters as one trailing argument: the matcher, over the five level maps."""
 
     @staticmethod
     def forward(ctx, dtype, num_classes, anchors, annots, train, box, loss, *args):
         ctx.prep, ctx.arith, ctx.box, ctx.loss = ops.get_prep(), ops.F32_ARITH_BWD, box, loss
+        ctx.matcher = matcher = args[5 + len(_HEAD_KEYS)] if len(args) > 5 + len(_HEAD_KEYS) else None
+        ctx.extra = len(args) - 5 - len(_HEAD_KEYS)
         p = [Map.of(t) for t in args[:5]]
         HP = dict(zip(_HEAD_KEYS, args[5:]))
+        levels = [m.H * m.W * 9 for m in p] if matcher is not None else None
         cls, reg, saved = Fn.head_fwd(p, HP, num_classes, dtype, train)
         nc = num_classes
         if train and nc % 4 == 0 and LOSS_FWD_GRAD:
             # ONE pass over the 15.7 MB/image of probabilities: losses + d(logits) for an upstream gradient of one, already in
             # the pixel-major, 64-channel-padded rows the head's gradient convs read; cls itself is not kept for backward
             dld = (9 * nc + 63) // 64 * 64
-            losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], loss=loss, box=box)    # (split-layout head: see functional.head_uses_split)
+            losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], loss=loss, box=box,    # (split-layout head: see functional.head_uses_split)
+                                                      matcher=matcher, levels=levels)
             ctx.saved = (saved, None, reg, anchors, annots, ws, dtype, dpix, dld)
         else:
-            losses, ws = ops.loss_opts_fwd(cls, reg, anchors, annots, loss, box)
+            losses, ws = ops.loss_opts_fwd(cls, reg, anchors, annots, loss, box, matcher=matcher, levels=levels)
             ctx.saved = (saved, cls, reg, anchors, annots, ws, dtype, None, 0) if train else None
         return losses[0:1].clone(), losses[1:2].clone()
 
@@ -351,24 +373,26 @@ class _HeadLossFn(torch.autograd.Function):
         if dpix is not None:
             split = saved[5]
             rld = 64 if split else 0                # split layout: d(reg) pixel-major, 36 -> 64 channels (two [hi|lo] groups)
-            dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, loss=ctx.loss, box=ctx.box)
+            dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, loss=ctx.loss, box=ctx.box,
+                                         matcher=ctx.matcher)
             with ops.unpack_batch():                               # the head's 10 weight-gradient unpacks: one launch
                 dp, g = Fn.head_bwd(saved, dpix, dreg, dtype, dcls_ld=dld, cls_gscale=gscale[0:1], dreg_ld=rld, in_split=split)
         else:
             nc = cls.shape[2]
             dld = (9 * nc + 63) // 64 * 64 if nc % 4 == 0 else 0      # d(logits) straight into the pixel-major, 64-channel-padded rows the head's gradient convs read
-            if ctx.loss is not None:
-                dcls = ops.loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, ctx.loss, dld=dld)
+            if ctx.loss is not None or ctx.matcher is not None:
+                dcls = ops.loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, ctx.loss, dld=dld, matcher=ctx.matcher)
             elif dld:                                 # the reference's constants: the combined calls (smooth-L1 d(reg) in the same launch pair)
                 dcls, dreg = ops.focal_loss_bwd_pix(cls, reg, anchors, annots, gscale, ws, dtype, dld)
             else:
                 dcls, dreg = ops.focal_loss_bwd(cls, reg, anchors, annots, gscale, ws, dtype)
-            if ctx.loss is not None or ctx.box is not None:      # (the class gradient above is the focal term's either way; a smooth-L1 d(reg) is replaced)
-                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, loss=ctx.loss, box=ctx.box)
+            if ctx.loss is not None or ctx.box is not None or ctx.matcher is not None:      # (the class gradient above is the focal term's either way; a smooth-L1 d(reg) is replaced)
+                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, loss=ctx.loss, box=ctx.box, matcher=ctx.matcher)
             with ops.unpack_batch():
                 dp, g = Fn.head_bwd(saved, dcls, dreg, dtype, dcls_ld=dld)
         ctx.saved = None
-        return (None, None, None, None, None, None, None) + tuple(Fn.level_tensor(m) for m in dp) + tuple(g[k] for k in _HEAD_KEYS)
+        return (None, None, None, None, None, None, None) + tuple(Fn.level_tensor(m) for m in dp) + tuple(g[k] for k in _HEAD_KEYS) + \
+            (None,) * ctx.extra
 
 
 # --------------------------------------------------------------------------- the model
@@ -386,6 +410,7 @@ class EfficientDet(nn.Module):
         self.nms_options = None                                 # set_nms(): None = the reference's class-agnostic greedy NMS
         self.box_loss = None                                    # set_box_loss(): None = the reference's smooth-L1 on encoded deltas
         self.loss_options = None                                # set_loss(): None = the reference's focal / smooth-L1 / matcher constants
+        self.matcher = None                                     # set_matcher(): None = the IoU bands of the loss options
         self.num_classes = num_classes
         self.compute_dtype = compute_dtype
         # MFMA arithmetic on fp32 storage: 'f32' = exact fp32 products (v_mfma_f32_16x16x4_f32), 'bf16x3' = operands split into
@@ -448,8 +473,23 @@ class EfficientDet(nn.Module):
         before a change keeps the old loss until it is captured again."""
         if options is not None and not isinstance(options, ops.LossOptions):
             raise TypeError('set_loss takes a LossOptions or None, not %r' % (options,))
+        ops.check_matcher(getattr(self, 'matcher', None), options)      # (ValueError: bands / low_quality while a matcher is set)
         self.loss_options = options
         self.criterion.loss = options
+        return self
+
+    def set_matcher(self, options):
+        """Anchor assignment of the training loss: None (the default) = the IoU bands of set_loss (0.4 / 0.5 unless set), through the
+        same calls as ever; an ops.ATSSOptions(topk) = Adaptive Training Sample Selection over the five pyramid levels
+        (include/effdet_atss.h), with everything downstream of the assignment as set_loss / set_box_loss say.  It replaces the
+        bands: combined with a LossOptions of non-default pos_iou / neg_iou or low_quality=True it raises ValueError.  topk and the
+        levels are launch arguments: a graph.GraphedTrainStep / GraphedTrainLoop captured before a change keeps the old matcher
+        until it is captured again."""
+        if options is not None and not isinstance(options, ops.ATSSOptions):
+            raise TypeError('set_matcher takes an ATSSOptions or None, not %r' % (options,))
+        ops.check_matcher(options, getattr(self, 'loss_options', None))
+        self.matcher = options
+        self.criterion.matcher = options
         return self
 
     def live_parameters(self):
@@ -601,8 +641,10 @@ class EfficientDet(nn.Module):
             box = None if (box is None or box.is_default()) else box
             loss = getattr(self, 'loss_options', None)           # (likewise)
             loss = None if (loss is None or loss.is_default()) else loss
+            matcher = getattr(self, 'matcher', None)             # (likewise)
             return _HeadLossFn.apply(self.compute_dtype, self.num_classes, anc, annotations.float().contiguous(),
-                                     torch.is_grad_enabled(), box, loss, *p, *self._head_params())
+                                     torch.is_grad_enabled(), box, loss, *p, *self._head_params(),
+                                     *(() if matcher is None else (matcher,)))
         dets = self.detect(inputs)
         s, l, b = dets[0]
         if s.numel() == 0:

@@ -1288,6 +1288,8 @@ def model_nms(model, boxes, score, label):
 # Three sets of entry points, one per kind of call: effdet_focal_loss_* (the reference's constants), effdet_box_loss_* (an IoU-family
 # box term: kind, weight) and effdet_loss_opts_* (non-default LossOptions: the struct, with the box term inside it).  They take the same
 # arguments, the extra ones just before the stream.  Each public function below names the call it wants; _loss_entry chooses the set.
+# A matcher (ATSSOptions) is a fourth set for the two forward calls, effdet_loss_atss_* (the options struct, then the matcher's); its
+# backward calls are the options set's, with the options struct even where its values are the defaults.
 BOX_LOSS_KINDS = {'smooth_l1': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}     # EFFDET_BOX_LOSS_* (0: the effdet_focal_loss_* calls)
 
 
@@ -1388,13 +1390,63 @@ class LossOptions:
 _LOSS_DEFAULT_KEY = LossOptions().key()
 
 
-def _loss_opts_struct(loss, box=None):
-    """-> None where the existing calls apply (loss None or equal to the defaults), else the effdet_loss_opts_t of (loss, box)."""
+class ATSSOptions:
+    """The ATSS matcher of EfficientDet.set_matcher / FocalLoss(matcher=) (include/effdet_atss.h), in place of the IoU bands: per
+    annotation the topk anchors nearest its centre on every pyramid level are candidates, positive where their IoU reaches the
+    candidates' mean + standard deviation and their centre lies inside the box."""
+
+    def __init__(self, topk=9):
+        if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= L.ATSS_MAX_TOPK:
+            raise ValueError('ATSSOptions: topk must be an int in [1, %d], not %r' % (L.ATSS_MAX_TOPK, topk))
+        self.topk = topk
+
+    def key(self):
+        return (self.topk,)
+
+    def __eq__(self, other):
+        return isinstance(other, ATSSOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'ATSSOptions(topk=%r)' % self.topk
+
+
+def check_matcher(matcher, loss):
+    """TypeError on anything but an ATSSOptions / None; ValueError where loss sets what a matcher replaces (bands, low_quality)."""
+    if matcher is None:
+        return
+    if not isinstance(matcher, ATSSOptions):
+        raise TypeError('matcher must be an ATSSOptions or None, not %r' % (matcher,))
+    if isinstance(loss, LossOptions) and (loss.low_quality or (loss.pos_iou, loss.neg_iou) != _LOSS_DEFAULT_KEY[5:7]):
+        raise ValueError('%r replaces the IoU bands: it cannot be combined with the pos_iou / neg_iou / low_quality of %r'
+                         % (matcher, loss))
+
+
+def _atss_struct(matcher, levels, A):
+    """-> the effdet_atss_t of matcher on a table of A anchors cut into levels (the anchor count of every level, in table order)."""
+    if levels is None:
+        raise ValueError('a matcher needs levels: the anchor count of every pyramid level')
+    levels = [int(v) for v in levels]
+    if not 1 <= len(levels) <= L.ATSS_MAX_LEVELS or min(levels) < 1 or sum(levels) != A:
+        raise ValueError('levels must be 1 .. %d positive anchor counts that add up to A = %d, not %r' % (L.ATSS_MAX_LEVELS, A, levels))
+    t = L.Atss(matcher.topk, len(levels))
+    for i, v in enumerate(levels):
+        t.level_start[i + 1] = t.level_start[i] + v
+    return t
+
+
+def _loss_opts_struct(loss, box=None, force=False):
+    """-> None where the existing calls apply (loss None or equal to the defaults), else the effdet_loss_opts_t of (loss, box).
+    force: the options path although default (a matcher's calls take the struct whatever its values)."""
+    if loss is None and force:
+        loss = LossOptions()
     if loss is None:
         return None
     if not isinstance(loss, LossOptions):
         raise TypeError('loss options must be a LossOptions or None, not %r' % (loss,))
-    if loss.is_default():
+    if loss.is_default() and not force:
         return None
     kw = _box_loss_args(box)
     kind, weight = (0, 1.0) if kw is None else kw
@@ -1402,10 +1454,14 @@ def _loss_opts_struct(loss, box=None):
                       1 if loss.low_quality else 0, kind, weight)
 
 
-def _loss_entry(stem, loss=None, box=None):
-    """-> (the entry point of the call `stem` for (loss, box), its name, its extra arguments, whether it is of the options set)."""
-    o = _loss_opts_struct(loss, box)
-    if o is not None:
+def _loss_entry(stem, loss=None, box=None, matcher=None, atss=None):
+    """-> (the entry point of the call `stem` for (loss, box, matcher), its name, its extra arguments, whether it is of the options
+    set).  atss: the matcher's effdet_atss_t, for the forward calls."""
+    check_matcher(matcher, loss)
+    o = _loss_opts_struct(loss, box, force=matcher is not None)
+    if atss is not None:
+        name, extra = 'effdet_loss_atss_' + stem, (C.byref(o), C.byref(atss))
+    elif o is not None:
         name, extra = 'effdet_loss_opts_' + stem, (C.byref(o),)
     else:
         kw = _box_loss_args(box)
@@ -1417,12 +1473,16 @@ def _dtype_code(dtype, split):
     return L.F32_SPLIT if split else L.dtype_code(dtype)
 
 
-def _loss_forward(cls, reg, anc, annots, loss, box, grad=None):
-    """Forward of (loss, box) -> (losses [2], ws), and with grad = (dtype, dld, split) also dcls_pix [B, A/9, dld]."""
-    fn, name, extra, opts = _loss_entry('fwd_grad' if grad else 'fwd', loss, box)
+def _loss_forward(cls, reg, anc, annots, loss, box, grad=None, matcher=None, levels=None):
+    """Forward of (loss, box, matcher) -> (losses [2], ws), and with grad = (dtype, dld, split) also dcls_pix [B, A/9, dld]."""
     B, A, nc = cls.shape
     N = annots.shape[1]
-    if opts:
+    check_matcher(matcher, loss)
+    atss = None if matcher is None else _atss_struct(matcher, levels, A)
+    fn, name, extra, opts = _loss_entry('fwd_grad' if grad else 'fwd', loss, box, matcher, atss)
+    if atss is not None:
+        nbytes = int(L.require('effdet_loss_atss_workspace_bytes').effdet_loss_atss_workspace_bytes(B, A, nc, N, C.byref(atss)))
+    elif opts:
         nbytes = int(L.require('effdet_loss_opts_workspace_bytes').effdet_loss_opts_workspace_bytes(B, A, nc, N))
     else:
         nbytes = int(L.lib().effdet_loss_workspace_bytes(B, A, nc))
@@ -1438,10 +1498,10 @@ def _loss_forward(cls, reg, anc, annots, loss, box, grad=None):
     return out
 
 
-def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box):
+def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher=None):
     """-> dreg [B, A, 4], or with reg_ld pixel-major and channel-padded [B, A/9, reg_ld] (split=True: in the split layout), from the
-    workspace of a forward call with the same (loss, box)."""
-    fn, name, extra, _ = _loss_entry('bwd_reg', loss, box)
+    workspace of a forward call with the same (loss, box, matcher)."""
+    fn, name, extra, _ = _loss_entry('bwd_reg', loss, box, matcher)
     B, A, _ = reg.shape
     dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
     L.check(fn(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld, _dtype_code(dtype, split), B, A,
@@ -1449,14 +1509,14 @@ def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box)
     return dreg
 
 
-def _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld, loss=None):
+def _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld, loss=None, matcher=None):
     """d(logits) [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld].  The reference's constants: the combined entry
     points (dld None: the flat one), which also write the smooth-L1 dreg [B, A, 4] -> (dcls, dreg); options: the class gradient
     alone -> dcls."""
     B, A, nc = cls.shape
     dcls = torch.empty((B, A // 9, dld) if dld else (B, A, nc), dtype=dtype, device=cls.device)
-    if loss is not None:
-        fn, name, extra, _ = _loss_entry('bwd_cls', loss)
+    if loss is not None or matcher is not None:
+        fn, name, extra, _ = _loss_entry('bwd_cls', loss, None, matcher)
         L.check(fn(L.ptr(cls), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls), dld, L.dtype_code(dtype), B, A, nc,
                    annots.shape[1], *extra, L.stream_ptr()), name)
         return dcls
@@ -1507,27 +1567,29 @@ def box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False,
     return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, None, options)
 
 
-def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None):
-    """box_loss_fwd with the options of loss (None / the defaults: box_loss_fwd itself) -> (losses [2], ws)."""
-    return _loss_forward(cls, reg, anc, annots, loss, box)
+def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None, matcher=None, levels=None):
+    """box_loss_fwd with the options of loss (None / the defaults: box_loss_fwd itself) -> (losses [2], ws).  matcher: an ATSSOptions
+    assigns by ATSS over the pyramid levels (levels: the anchor count of every level) through the effdet_loss_atss_* calls, with
+    the options struct of loss (None / the defaults: the default VALUES through the option kernels)."""
+    return _loss_forward(cls, reg, anc, annots, loss, box, None, matcher, levels)
 
 
-def loss_opts_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, loss=None, box=None):
-    """box_loss_fwd_grad with the options of loss -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
-    return _loss_forward(cls, reg, anc, annots, loss, box, (dtype, dld, split))
+def loss_opts_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, loss=None, box=None, matcher=None, levels=None):
+    """box_loss_fwd_grad with the options of loss (and the matcher) -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
+    return _loss_forward(cls, reg, anc, annots, loss, box, (dtype, dld, split), matcher, levels)
 
 
-def loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, loss, dld=0):
+def loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, loss, dld=0, matcher=None):
     """d(logits) of the class term with the (non-default) options of loss, from the workspace of a forward call with them:
-    [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld]."""
-    if _loss_opts_struct(loss) is None:
+    [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld].  With a matcher the options path is taken whatever loss."""
+    if matcher is None and _loss_opts_struct(loss) is None:
         raise ValueError('loss_opts_bwd_cls is the non-default path: the defaults are focal_loss_bwd / focal_loss_bwd_pix')
-    return _loss_bwd_cls(cls, None, None, annots, gscale, ws, dtype, dld, loss)
+    return _loss_bwd_cls(cls, None, None, annots, gscale, ws, dtype, dld, loss, matcher)
 
 
-def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, loss=None, box=None):
-    """box_loss_bwd_reg with the options of loss: d(reg) in the same three layouts."""
-    return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box)
+def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, loss=None, box=None, matcher=None):
+    """box_loss_bwd_reg with the options of loss: d(reg) in the same three layouts (matcher: the options path whatever loss)."""
+    return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher)
 
 
 def pad_rows(src_map, cpad):
