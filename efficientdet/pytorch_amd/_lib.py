@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h).
+include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -117,6 +117,17 @@ class Atss(C.Structure):         # effdet_atss_t (include/effdet_atss.h)
 class ConvPlanInfo(C.Structure):   # effdet_conv_plan_info_t (include/effdet_conv_plan.h)
     _fields_ = [(n, C.c_int) for n in ('id', 'form', 'persistent', 'tile_m', 'tile_n', 'stages', 'threads', 'mtiles', 'ntiles', 'grid',
                                        'ksteps', 'kord', 'lds_bytes', 'm32')] + [('reserved', C.c_int * 2)]
+
+
+WBF_MAX_VIEWS, WBF_MAX_IN = 8, 4096                  # EFFDET_WBF_MAX_VIEWS, EFFDET_WBF_MAX_IN
+
+
+class Wbf(C.Structure):          # effdet_wbf_t (include/effdet_wbf.h)
+    _fields_ = [(n, C.c_void_p * WBF_MAX_VIEWS) for n in ('score', 'label', 'boxes', 'count')] + \
+               [('A', C.c_longlong * WBF_MAX_VIEWS)] + [(n, C.c_float * WBF_MAX_VIEWS) for n in ('weight', 'width', 'mul')] + \
+               [('flip', C.c_int * WBF_MAX_VIEWS)] + [(n, C.c_int) for n in ('V', 'B', 'top_n', 'conf_type')] + \
+               [('iou_thr', C.c_float), ('skip_thr', C.c_float)] + \
+               [(n, C.c_void_p) for n in ('out_score', 'out_label', 'out_boxes', 'out_count')]
 
 
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
@@ -283,6 +294,13 @@ ATSS_SIGNATURES = {
 CONV_PLAN_SIGNATURES = {
     'effdet_conv2d_plan_info': 'i:pp',
 }
+# Weighted Boxes Fusion of several views' detection lists, declared in include/effdet_wbf.h (same generation, same letters, same rule;
+# tests/test_wbf_host.py compares this table and Wbf with that header).  The views, options and outputs travel as a Wbf struct in host
+# memory (byref).
+WBF_SIGNATURES = {
+    'effdet_wbf_workspace_bytes': 'q:iii',
+    'effdet_wbf': 'i:ppqs',
+}
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
 DW_PLAN_FWD, DW_PLAN_DGRAD, DW_PLAN_WGRAD, DW_PLAN_BWD, DW_PLAN_EXPAND_FWD = 0, 1, 2, 3, 4      # EFFDET_DW_PLAN_*
@@ -306,7 +324,8 @@ def lib():
         _lib = cand
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
-                list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()):
+                list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
+                list(WBF_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

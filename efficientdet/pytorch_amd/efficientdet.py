@@ -408,6 +408,7 @@ class EfficientDet(nn.Module):
         self.threshold = threshold
         self.iou_threshold = iou_threshold
         self.nms_options = None                                 # set_nms(): None = the reference's class-agnostic greedy NMS
+        self.tta_options = None                                 # set_tta(): None = one view, no fusion
         self.box_loss = None                                    # set_box_loss(): None = the reference's smooth-L1 on encoded deltas
         self.loss_options = None                                # set_loss(): None = the reference's focal / smooth-L1 / matcher constants
         self.matcher = None                                     # set_matcher(): None = the IoU bands of the loss options
@@ -451,6 +452,17 @@ class EfficientDet(nn.Module):
         if options is not None and not isinstance(options, ops.NMSOptions):
             raise TypeError('set_nms takes an NMSOptions or None, not %r' % (options,))
         self.nms_options = options
+        return self
+
+    def set_tta(self, options):
+        """Test-time augmentation of the detection paths (detect, evaluate.*, graph.GraphedDetect): None = one view (the default), an
+        ops.TTAOptions = the batch and, with hflip, its mirror image, each through its own forward + decode + NMS, the lists merged on
+        the device by weighted boxes fusion (include/effdet_wbf.h).  With hflip a PackedImages batch must hold a dense [B,H,W,C]
+        tensor (ops.flip_images raises TypeError otherwise).  Under two-view 'avg' fusion a detection only one view made keeps half
+        its score."""
+        if options is not None and not isinstance(options, ops.TTAOptions):
+            raise TypeError('set_tta takes a TTAOptions or None, not %r' % (options,))
+        self.tta_options = options
         return self
 
     def set_box_loss(self, options):
@@ -622,10 +634,7 @@ class EfficientDet(nn.Module):
         if f16x3:
             ops.clear_range_flag(img.device)                     # (report this call's overflow only, not one of an earlier training step)
         with torch.no_grad():
-            cls, reg, anc = self.forward_raw(img)
-        H, W = int(img.shape[2]), int(img.shape[3])
-        boxes, score, label = ops.decode_score(anc, reg, cls, H, W)
-        s, l, b, count = ops.model_nms(self, boxes, score, label)
+            s, l, b, count = ops.model_detections(self, img, int(img.shape[2]), int(img.shape[3]))
         counts = count.tolist()                                  # the one device->host sync (the reference syncs too)
         if f16x3 and not torch.cuda.is_current_stream_capturing():
             ops.check_range_flag(s.device)                       # (a sigmoid turns an inf logit into a plausible score: make overflow an error)

@@ -60,11 +60,60 @@ def finalize_device(s, l, b, count, scales, score_threshold=0.05, max_detections
 
 def detections_batched(model, images, scales, score_threshold=0.05, max_detections=None, xywh=False):
     """-> (dets [B, max_detections, 6] fp32 on the HOST: x1,y1,x2,y2 (or x,y,w,h), score, label; counts [B] ints).
-    images: NCHW fp32 batch or PackedImages; scales: [B] resize factors (tensor, array or list)."""
+    images: NCHW fp32 batch or PackedImages; scales: [B] resize factors (tensor, array or list); model: an EfficientDet (its set_nms /
+    set_tta apply) or an EnsembleDetector."""
     with torch.no_grad():
-        cls, reg, anc = model.forward_raw(images)
-        s, l, b, count = postprocess(model, cls, reg, anc, int(images.shape[2]), int(images.shape[3]))
+        s, l, b, count = ops.model_detections(model, images, int(images.shape[2]), int(images.shape[3]))
         return finalize(s, l, b, count, scales, score_threshold, max_detections, xywh, getattr(model, 'num_classes', None))
+
+
+class EnsembleDetector:
+    """Several detectors as one: every member runs its own detection pass on the batch (its own set_nms and set_tta included) and the
+    lists are merged on the device by weighted boxes fusion (ops.fuse_detections) under the members' weights.  Has ``detect(images)``
+    like EfficientDet and is taken as ``model`` by detections_batched, evaluate_voc and evaluate_coco.  Members may differ in family
+    (D0 with D1, raw with EMA weights) but share num_classes; they see the same image tensor, so no box is rescaled."""
+
+    def __init__(self, models, weights=None, fusion=None):
+        self.models = list(models)
+        self.fusion = ops.WBFOptions() if fusion is None else fusion
+        V = len(self.models)
+        if not 1 <= V <= ops.WBF_MAX_VIEWS:
+            raise ValueError('EnsembleDetector: 1..%d members, got %d' % (ops.WBF_MAX_VIEWS, V))
+        if len({int(m.num_classes) for m in self.models}) != 1:
+            raise ValueError('EnsembleDetector: members must share num_classes, got %s' % [int(m.num_classes) for m in self.models])
+        if V * self.fusion.top_n > ops.WBF_MAX_IN:
+            raise ValueError('EnsembleDetector: members * fusion.top_n must be <= %d' % ops.WBF_MAX_IN)
+        self.weights = ops._view_weights(weights, V, 'EnsembleDetector')
+        self.num_classes = int(self.models[0].num_classes)
+
+    def eval(self):
+        for m in self.models:
+            m.eval()
+        return self
+
+    def train(self, mode=True):
+        for m in self.models:
+            m.train(mode)
+        return self
+
+    def parameters(self):
+        return (p for m in self.models for p in m.parameters())
+
+    def detections(self, images, H, W):
+        """ops.model_detections' tuple for the ensemble (what that function asks a model with its own pass for)."""
+        return ops.fuse_detections([ops.model_detections(m, images, H, W) for m in self.models], self.weights, None, None, self.fusion)
+
+    def detect(self, images):
+        """-> list of (scores[K], labels[K] int64, boxes[K,4]) per image, score-descending, as EfficientDet.detect."""
+        f16x3 = any(ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3' for m in self.models)
+        if f16x3:
+            ops.clear_range_flag(images.device)
+        with torch.no_grad():
+            s, l, b, count = self.detections(images, int(images.shape[2]), int(images.shape[3]))
+        counts = count.tolist()
+        if f16x3 and not torch.cuda.is_current_stream_capturing():
+            ops.check_range_flag(s.device)
+        return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
 
 
 def all_detections_rows(dets, counts, num_classes):
@@ -254,11 +303,10 @@ def _model_device(model):
 
 
 def _detect_batch(model, batch, device):
-    """One batch of _image_batches (HWC images of one size) through forward_raw + postprocess
+    """One batch of _image_batches (HWC images of one size) through ops.model_detections
     -> (scores, labels, boxes, count, number of classes of the head)."""
     x = torch.stack([img.permute(2, 0, 1) for _, img, _ in batch]).to(device).float().contiguous()
-    cls, reg, anc = model.forward_raw(x)
-    return postprocess(model, cls, reg, anc, int(x.shape[2]), int(x.shape[3])) + (int(cls.shape[-1]),)
+    return ops.model_detections(model, x, int(x.shape[2]), int(x.shape[3]), num_classes=True)
 
 
 def evaluate_voc(generator, model, iou_threshold=0.5, score_threshold=0.05, max_detections=100, batch_size=1):

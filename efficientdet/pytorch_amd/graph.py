@@ -301,9 +301,7 @@ class GraphedDetect:
             if f16x3:
                 ops.clear_range_flag(self.images.device)       # (a kernel node of the graph: every replay reports its own overflow only)
             with torch.no_grad():
-                cls, reg, anc = model.forward_raw(self.images)
-                boxes, score, label = ops.decode_score(anc, reg, cls, H, W)
-                return ops.model_nms(model, boxes, score, label)
+                return ops.model_detections(model, self.images, H, W)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -315,6 +313,7 @@ class GraphedDetect:
         self.graph = torch.cuda.CUDAGraph()
         self.thresholds = (float(model.threshold), float(model.iou_threshold))       # baked into the captured launches
         self.nms_options = getattr(model, 'nms_options', None)                       # and so is which NMS runs, with what arguments
+        self.tta_options = getattr(model, 'tta_options', None)                       # and the views and their fusion
         # (inside a torch.distributed job the process group's watchdog thread polls events while this capture is open: 'thread_local'
         #  confines the unsafe-call check to this thread, as in GraphedTrainStep)
         dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -330,6 +329,9 @@ class GraphedDetect:
         if getattr(m, 'nms_options', None) != self.nms_options:
             raise RuntimeError('GraphedDetect: model.nms_options changed after capture (%r was captured; the NMS and its arguments are '
                                'part of the graph); build a new GraphedDetect' % (self.nms_options,))
+        if getattr(m, 'tta_options', None) != self.tta_options:
+            raise RuntimeError('GraphedDetect: model.tta_options changed after capture (%r was captured; the views and their fusion are '
+                               'part of the graph); build a new GraphedDetect' % (self.tta_options,))
         self.graph.replay()
         counts = self.count.tolist()                       # the one device->host sync (the reference syncs too)
         if ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3':

@@ -1284,6 +1284,181 @@ def model_nms(model, boxes, score, label):
     return new_score, l, b, count
 
 
+# ----------------------------------------------------------------------------- weighted boxes fusion / test-time augmentation
+WBF_CONF_TYPES = {'avg': 0, 'max': 1}                # EFFDET_WBF_AVG, EFFDET_WBF_MAX
+WBF_MAX_VIEWS, WBF_MAX_IN = L.WBF_MAX_VIEWS, L.WBF_MAX_IN
+
+
+class WBFOptions:
+    """Weighted Boxes Fusion of fuse_detections (effdet_wbf): a candidate joins the same-label cluster it overlaps most when that IoU is
+    > iou_thr; rows scoring below skip_box_thr take no part; the fused score is the members' mean confidence scaled by how many views
+    agreed ('avg') or the largest one ('max'); of every view the first top_n rows per image take part (views * top_n <= 4096)."""
+
+    def __init__(self, iou_thr=0.55, skip_box_thr=0.0, conf_type='avg', top_n=1000):
+        if not 0.0 <= float(iou_thr) <= 1.0:
+            raise ValueError('WBFOptions: iou_thr must be in [0, 1]')
+        if not 0.0 <= float(skip_box_thr) < float('inf'):
+            raise ValueError('WBFOptions: skip_box_thr must be finite and >= 0')
+        if conf_type not in WBF_CONF_TYPES:
+            raise ValueError('WBFOptions: conf_type must be one of %s, not %r' % (sorted(WBF_CONF_TYPES), conf_type))
+        if not 1 <= int(top_n) <= WBF_MAX_IN:
+            raise ValueError('WBFOptions: top_n must be in 1..%d' % WBF_MAX_IN)
+        self.iou_thr, self.skip_box_thr, self.conf_type, self.top_n = float(iou_thr), float(skip_box_thr), conf_type, int(top_n)
+
+    def key(self):
+        return (self.iou_thr, self.skip_box_thr, self.conf_type, self.top_n)
+
+    def __eq__(self, other):
+        return isinstance(other, WBFOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'WBFOptions(iou_thr=%r, skip_box_thr=%r, conf_type=%r, top_n=%d)' % self.key()
+
+
+def _view_weights(weights, V, what):
+    """weights (None: all 1) -> tuple of V positive finite floats."""
+    w = (1.0,) * V if weights is None else tuple(float(x) for x in weights)
+    if len(w) != V:
+        raise ValueError('%s: %d weights for %d views' % (what, len(w), V))
+    if not all(0.0 < x < float('inf') for x in w):
+        raise ValueError('%s: weights must be positive and finite' % what)
+    return w
+
+
+class TTAOptions:
+    """Test-time augmentation of EfficientDet.set_tta: the image and, with hflip, its mirror image, each through the whole detection
+    path (its own forward of batch B), the lists merged by fuse_detections.  weights: one per view (None: all 1)."""
+
+    def __init__(self, hflip=True, weights=None, fusion=None):
+        fusion = WBFOptions() if fusion is None else fusion
+        if not isinstance(fusion, WBFOptions):
+            raise TypeError('TTAOptions: fusion must be a WBFOptions, not %r' % (fusion,))
+        self.hflip, self.fusion = bool(hflip), fusion
+        self.weights = None if weights is None else _view_weights(weights, self.num_views, 'TTAOptions')
+        if self.num_views * fusion.top_n > WBF_MAX_IN:
+            raise ValueError('TTAOptions: views * fusion.top_n must be <= %d' % WBF_MAX_IN)
+
+    @property
+    def num_views(self):
+        return 2 if self.hflip else 1
+
+    def key(self):
+        return (self.hflip, self.weights, self.fusion.key())
+
+    def __eq__(self, other):
+        return isinstance(other, TTAOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'TTAOptions(hflip=%r, weights=%r, fusion=%r)' % (self.hflip, self.weights, self.fusion)
+
+
+_wbf_ws = {}           # (device, B, V, top_n) -> workspace of eager calls (a capture allocates its own, from the graph's pool)
+
+
+def fuse_detections(views, weights=None, flips=None, muls=None, options=None):
+    """Weighted Boxes Fusion (include/effdet_wbf.h: effdet_wbf) of V <= 8 views of one batch -> (scores [B,N], labels [B,N] int64, boxes
+    [B,N,4], count [B] int32) with N = V * options.top_n: fused detections score-descending, count[b] of them valid, zero rows after
+    them -- model_nms's layout.  views: (scores [B,A_v], labels [B,A_v] int64, boxes [B,A_v,4], count [B] int32) each, as model_nms
+    returns them; weights: one per view (None: all 1); flips: per view None or the width to mirror the boxes about; muls: per view a
+    factor applied to every coordinate after the flip (None: 1).  All on device, no sync."""
+    lib = L.require('effdet_wbf', 'effdet_wbf_workspace_bytes')
+    options = WBFOptions() if options is None else options
+    views = list(views)
+    V = len(views)
+    if not 1 <= V <= WBF_MAX_VIEWS:
+        raise ValueError('fuse_detections: 1..%d views, got %d' % (WBF_MAX_VIEWS, V))
+    if V * options.top_n > WBF_MAX_IN:
+        raise ValueError('fuse_detections: views * top_n must be <= %d, got %d * %d' % (WBF_MAX_IN, V, options.top_n))
+    w = _view_weights(weights, V, 'fuse_detections')
+    flips = [None] * V if flips is None else list(flips)
+    muls = [1.0] * V if muls is None else [float(x) for x in muls]
+    if len(flips) != V or len(muls) != V:
+        raise ValueError('fuse_detections: flips and muls take one entry per view')
+    if not all(0.0 < x < float('inf') for x in muls):
+        raise ValueError('fuse_detections: muls must be positive and finite')
+    d = L.Wbf()
+    B, dev = int(views[0][0].shape[0]), views[0][0].device
+    keep = []
+    for v, (s, l, b, c) in enumerate(views):
+        if s.dim() != 2 or s.shape[0] != B or tuple(l.shape) != tuple(s.shape) or tuple(b.shape) != tuple(s.shape) + (4,) or tuple(c.shape) != (B,):
+            raise ValueError('fuse_detections: view %d must be scores [B,A], labels [B,A], boxes [B,A,4], count [B]' % v)
+        if (s.dtype, l.dtype, b.dtype, c.dtype) != (torch.float32, torch.int64, torch.float32, torch.int32):
+            raise TypeError('fuse_detections: view %d must be (float32, int64, float32, int32) tensors' % v)
+        s, l, b, c = s.contiguous(), l.contiguous(), b.contiguous(), c.contiguous()
+        keep.append((s, l, b, c))
+        d.score[v], d.label[v], d.boxes[v], d.count[v], d.A[v] = L.ptr(s), L.ptr(l), L.ptr(b), L.ptr(c), int(s.shape[1])
+        d.weight[v], d.mul[v] = w[v], muls[v]
+        d.flip[v], d.width[v] = (0, 0.0) if flips[v] is None else (1, float(flips[v]))
+    N = V * options.top_n
+    d.V, d.B, d.top_n, d.conf_type = V, B, options.top_n, WBF_CONF_TYPES[options.conf_type]
+    d.iou_thr, d.skip_thr = options.iou_thr, options.skip_box_thr
+    os_ = torch.empty((B, N), dtype=torch.float32, device=dev)
+    ol = torch.empty((B, N), dtype=torch.int64, device=dev)
+    ob = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    d.out_score, d.out_label, d.out_boxes, d.out_count = L.ptr(os_), L.ptr(ol), L.ptr(ob), L.ptr(count)
+    nbytes = int(lib.effdet_wbf_workspace_bytes(B, V, options.top_n))
+    ws = None
+    if nbytes and torch.cuda.is_current_stream_capturing():
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif nbytes:
+        k = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), B, V, options.top_n)
+        ws = _wbf_ws.get(k)
+        if ws is None:
+            ws = _wbf_ws[k] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    # algorithmic bytes: every view's rows read once (score, label, box: 28 B), the fused rows written once; the clustering is LDS / latency
+    _timed('wbf (per-image sort + sequential clustering)', 28 * B * sum(min(int(s.shape[1]), options.top_n) for s, _, _, _ in keep) + 28 * B * N,
+           lambda: L.check(lib.effdet_wbf(C.byref(d), L.ptr(ws), nbytes, L.stream_ptr()), 'effdet_wbf'), 'BYTES B%d V%d N%d' % (B, V, N))
+    return os_, ol, ob, count
+
+
+def flip_images(images):
+    """The mirror image of a batch: NCHW tensor, or a PackedImages whose map is a dense [B,H,W,C] tensor (TypeError otherwise)."""
+    m = getattr(images, 'map', None)
+    if m is None:
+        return torch.flip(images, (3,))
+    if not (m.off == 0 and m.ld == m.C and m.bstride == m.H * m.W * m.C and m.t.numel() == m.B * m.H * m.W * m.C):
+        raise TypeError('TTA with hflip needs PackedImages over a dense [B,H,W,C] tensor (this map is strided or an arena slice): '
+                        'pass the NCHW batch instead')
+    return type(images)(Map.of(torch.flip(m.tensor(), (2,)).contiguous()))
+
+
+def _detections_pass(model, images, H, W):
+    cls, reg, anc = model.forward_raw(images)
+    boxes, score, label = decode_score(anc, reg, cls, H, W)
+    return model_nms(model, boxes, score, label) + (int(cls.shape[-1]),)
+
+
+def model_detections(model, images, H, W, num_classes=False):
+    """THE detection pass of every path (EfficientDet.detect, evaluate.detections_batched / evaluate_voc / evaluate_coco,
+    graph.GraphedDetect) -> (scores [B,N], labels [B,N] int64, boxes [B,N,4], count [B] int32), model_nms's layout.  No TTA
+    (model.tta_options None): forward_raw -> decode_score -> model_nms.  With TTAOptions: one such pass per view -- separate forwards of
+    batch B, so every launch plan and summation order is the plain pass's -- and fuse_detections over them, the mirror view's boxes
+    flipped back about W.  A model that brings its own pass (evaluate.EnsembleDetector) is asked for it.  num_classes=True appends the
+    head's class count to the tuple.  The caller holds no_grad and the f16x3 range watch."""
+    own = getattr(model, 'detections', None)
+    tta = getattr(model, 'tta_options', None)            # (a model pickled before the option existed has no such attribute)
+    if own is not None:
+        out = own(images, H, W) + (int(model.num_classes),)
+    elif tta is None:
+        out = _detections_pass(model, images, H, W)
+    else:
+        mirror = flip_images(images) if tta.hflip else None          # (first: a batch that cannot be mirrored is refused before any launch)
+        first = _detections_pass(model, images, H, W)
+        views, flips = [first[:4]], [None]
+        if tta.hflip:
+            views.append(_detections_pass(model, mirror, H, W)[:4])
+            flips.append(W)
+        out = fuse_detections(views, tta.weights, flips, None, tta.fusion) + first[4:]
+    return out if num_classes else out[:4]
+
+
 # ----------------------------------------------------------------------------- loss
 # Three sets of entry points, one per kind of call: effdet_focal_loss_* (the reference's constants), effdet_box_loss_* (an IoU-family
 # box term: kind, weight) and effdet_loss_opts_* (non-default LossOptions: the struct, with the box term inside it).  They take the same
