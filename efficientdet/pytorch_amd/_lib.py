@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h).
+include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -264,6 +264,14 @@ LIVE_SIGNATURES = {
     'effdet_conv2d_live': 'i:ppis',
     'effdet_conv2d_wgrad_live': 'i:ppqps',
 }
+# The positive-pixel map, the flags derived from it and the conv launch that skips the tiles nobody reads (the sparse regression-tower
+# FORWARD), declared in include/effdet_needed_tiles.h (same generation, same letters, same rule; tests/test_needed_tiles_host.py
+# compares this table with that header's prototypes).
+NEEDED_SIGNATURES = {
+    'effdet_positive_pixel_map': 'i:ppiqiippps',
+    'effdet_live_tiles_from_map': 'i:piippppps',
+    'effdet_conv2d_needed': 'i:ppis',
+}
 # The IoU-family box regression losses, declared in include/effdet_box_loss.h (same generation, same letters, same rule;
 # tests/test_box_loss_host.py compares this table with that header's prototypes).
 BOX_LOSS_SIGNATURES = {
@@ -325,7 +333,7 @@ def lib():
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
-                list(WBF_SIGNATURES.items()):
+                list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -25,6 +25,7 @@
 //     tiles (n fastest), so the activation tile is fetched into one private L2 only.
 #include "common.h"
 #include "../../../include/effdet_live_tiles.h"
+#include "../../../include/effdet_needed_tiles.h"
 #include "../../../include/effdet_conv_plan.h"
 #include <stdlib.h>
 
@@ -60,6 +61,8 @@ struct ConvK {
   long long w_img_bytes;       // != 0: image b reads its own packed weights at w + b * w_img_bytes (one segment, Ho*Wo % BM == 0)
   const unsigned char* live;   // SPLIT == 2 only, may be NULL: live[mt - live_tile0] == 0 = every input tap of pixel tile mt is zero (effdet_conv2d_live)
   int live_tile0;              // pixel tiles below it carry no flag and are live
+  const unsigned char* needed; // SPLIT == 3 only, may be NULL: needed[mt - needed_tile0] == 0 = nobody reads pixel tile mt's result (effdet_conv2d_needed)
+  int needed_tile0;            // pixel tiles below it carry no flag and are computed
   SegD seg[EFFDET_MAX_CONV_SEG];
 };
 
@@ -159,6 +162,16 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
       } else tile = b;
     }
   }
+  if constexpr (SPLIT == 3) {
+    // "needed" flags (effdet_conv2d_needed): the needed tiles cluster the same way, so the same round-robin deal.  Speed only.
+    if (p.needed) {
+      const int b = blockIdx.x, whole = (p.mtiles >> 3) << 3;
+      if (b < whole * p.ntiles) {
+        const int i = b >> 3, j = i / p.ntiles;
+        tile = (j * 8 + (b & 7)) * p.ntiles + (i - j * p.ntiles);
+      } else tile = b;
+    }
+  }
   const int mt = tile / p.ntiles, nt = tile - mt * p.ntiles;
   int si = 0;
 #pragma unroll
@@ -185,6 +198,32 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
           *(uint4*)((float*)p.y + sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + 4 * c) = make_uint4(0u, 0u, 0u, 0u);
         }
       } else {
+        for (int i = tid; i < rows * nch; i += NTHREADS) {
+          const int row = i / nch, c = i - row * nch;
+          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
+          ((float*)p.y)[sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + c] = 0.f;
+        }
+      }
+      return;
+    }
+  }
+
+  if constexpr (SPLIT == 3) {
+    // A tile nobody needs (workgroup-uniform, ahead of every barrier and DMA): not computed.  Its rows of every output stream are
+    // written as zero bytes -- H-split y and its split twin (the tile's channels are contiguous in a row: 32-channel groups of 128
+    // bytes), or retina_reg's fp32 rows -- so that what later multiplies them by an exact zero never meets recycled memory.
+    if (p.needed && mt >= p.needed_tile0 && p.needed[mt - p.needed_tile0] == 0) {
+      const int rows = min(BM, sg.M - m_base), nch = min(BN, p.Cout - n_base);
+      if (p.vec_ok) {
+        const int q4 = nch >> 2;
+        for (int i = tid; i < rows * q4; i += NTHREADS) {
+          const int row = i / q4, c = i - row * q4;
+          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
+          const long long o = sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + 4 * c;
+          *(uint4*)((float*)p.y + o) = make_uint4(0u, 0u, 0u, 0u);
+          if (p.ysplit) *(uint4*)((float*)p.ysplit + o) = make_uint4(0u, 0u, 0u, 0u);
+        }
+      } else {     // (fp32 rows off the 16-byte grid: out_f32 only, the split layouts are always aligned)
         for (int i = tid; i < rows * nch; i += NTHREADS) {
           const int row = i / nch, c = i - row * nch;
           const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
@@ -1398,6 +1437,7 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c) {
   k.nseg = p->nseg;
   k.w_img_bytes = p->w_image_stride;
   k.live = nullptr; k.live_tile0 = 0;
+  k.needed = nullptr; k.needed_tile0 = 0;
   if (p->w_image_stride) {
     // per-image weights: one level whose images are whole numbers of 128-pixel tiles, on the implicit-GEMM kernels only
     if (p->w_image_stride < 0 || (p->w_image_stride & 15) || p->nseg != 1 || splitfmt || (p->seg[0].Ho * p->seg[0].Wo) % BM) return EFFDET_EUNSUPPORTED;
@@ -1528,5 +1568,18 @@ extern "C" int effdet_conv2d_live(const effdet_conv_t* p, const unsigned char* l
   const bool res_ok = p->out_f32 ? (p->res_mode == EFFDET_RES_NONE || (p->res_mode == EFFDET_RES_ADD && p->res == p->y))
                                  : (p->res_mode == EFFDET_RES_NONE || p->res_mode == EFFDET_RES_RELU_MASK);
   if (live && (id == 8 || id == 9) && plain && no_shift && res_ok) { c.k.live = live; c.k.live_tile0 = live_tile0; }
+  return c.launch(c, (hipStream_t)stream);
+}
+
+// effdet_conv2d with "needed" flags (include/effdet_needed_tiles.h): per call, like the liveness flags above, but a statement about the
+// READERS of the output, not about the input -- so bias, activation and the second output stream do not matter, a tile that is not
+// needed is zero bytes in all of them.  They reach the f16x3 128-pixel-tile kernels (the forward RetinaHead) and are dropped elsewhere.
+extern "C" int effdet_conv2d_needed(const effdet_conv_t* p, const unsigned char* needed, int needed_tile0, effdet_stream_t stream) {
+  ConvPlan c;
+  const int id = plan_conv(p, c);
+  if (id < 0) return id;
+  if (needed_tile0 < 0) return EFFDET_EINVAL;
+  // (vec_ok off: only fp32 rows may leave the 16-byte grid; the split streams never do -- plan_conv has checked their offsets and pitch)
+  if (needed && (id == 30 || id == 31) && (c.k.vec_ok || (p->out_f32 && !p->y_split))) { c.k.needed = needed; c.k.needed_tile0 = needed_tile0; }
   return c.launch(c, (hipStream_t)stream);
 }

@@ -14,6 +14,7 @@
 // All are plain kernel launches: capturable, no memset, no host sync.
 #include "common.h"
 #include "../../../include/effdet_live_tiles.h"
+#include "../../../include/effdet_needed_tiles.h"
 
 namespace {
 
@@ -150,6 +151,23 @@ extern "C" int effdet_live_tiles(const void* dreg, int dtype, int reg_ld, int B,
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(live_nz_kernel, dim3((unsigned)g), dim3(256), 0, st, k);
   EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(live_hdist_kernel, dim3((unsigned)((k.P + 255) / 256)), dim3(256), 0, st, k);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(live_flags_kernel, dim3((unsigned)k.ntiles), dim3(128), 0, st, k);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// The same flags from a per-pixel map the caller brings (include/effdet_needed_tiles.h: the positive-pixel map of the forward pass):
+// the row-distance and flag kernels above read it where they read live_nz_kernel's.
+extern "C" int effdet_live_tiles_from_map(const unsigned char* map, int B, int nlev, const int* H, const int* W, unsigned char* scratch,
+                                          unsigned char* live32, unsigned char* live128, effdet_stream_t stream) {
+  if (!map || !scratch || !live32 || !live128) return EFFDET_EINVAL;
+  LiveK k;
+  const int rc = live_geometry(B, nlev, H, W, k);
+  if (rc != EFFDET_OK) return rc;
+  k.dreg = nullptr; k.nz = const_cast<unsigned char*>(map); k.hd = scratch + k.P; k.l32 = live32; k.l128 = live128; k.reg_ld = 0; k.mask = 0u;
+  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(live_hdist_kernel, dim3((unsigned)((k.P + 255) / 256)), dim3(256), 0, st, k);
   EFFDET_CHECK_LAUNCH();
   hipLaunchKernelGGL(live_flags_kernel, dim3((unsigned)k.ntiles), dim3(128), 0, st, k);

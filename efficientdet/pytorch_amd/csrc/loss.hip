@@ -24,6 +24,8 @@
 //                       topk-th key, and thr[b][n] = mean + std of the candidates' IoUs; then loss_assign_kernel's grid: an anchor is
 //                       a candidate of row n iff its own key <= kth[b][n][its level] (the same device function forms both keys), positive
 //                       iff its IoU >= thr and its centre is inside the box; the same tail
+//              loss_pos_map_kernel                   the default pass's decision alone, per pixel and ahead of the head: one byte per
+//                       pixel = one of its 9 anchors is positive (include/effdet_needed_tiles.h: the sparse regression-tower forward)
 //   cls      loss_cls_kernel<F>: one thread per 4 class probabilities (16-byte loads): focal BCE with the reference's clamp to
 //            [1e-4, 1-1e-4], one partial per workgroup in part_cls[b][block].  loss_cls_pix_kernel<T, F, GRAD_ONLY, IT>: the same
 //            sum AND d/d(logit) in one pass, or the gradient alone, written pixel-major (see there)
@@ -39,6 +41,7 @@
 #include "../../../include/effdet_box_loss.h"
 #include "../../../include/effdet_loss_opts.h"
 #include "../../../include/effdet_atss.h"
+#include "../../../include/effdet_needed_tiles.h"
 
 namespace {
 
@@ -292,6 +295,55 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const LossK p) {
   }
   assign_tail(p, b, a, ok, ok && total_valid > 0, best < 0.4f, best >= 0.5f, barg, an, KneeDefault{});
   if (blockIdx.x == 0 && threadIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
+}
+
+// The positive-pixel map (include/effdet_needed_tiles.h): loss_assign_kernel's IoU loop and its decision (an image with a valid
+// annotation, best >= 0.5f) ahead of the head, one thread per (image, pixel) over the pixel's 9 anchors -- the same device functions
+// on the same operands, so map == (assign[] >= 0 OR-ed over the nine anchors) bit for bit.  No reg, no statistics, every byte stored.
+struct PosMapK {
+  unsigned char* map; int nlev, apix;
+  int hw[EFFDET_MAX_SEG], poff[EFFDET_MAX_SEG], pix0[EFFDET_MAX_SEG];     // pixels per image, first pixel within an image, first byte of the level in the map
+};
+
+__global__ __launch_bounds__(256) void loss_pos_map_kernel(const LossK p, const PosMapK g) {
+  const int b = blockIdx.y;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  __shared__ float ann[64 * 5];
+  __shared__ int nvalid_s;
+  const bool ok = q < g.apix;
+  float4 an[9]; float aarea[9], best[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    an[k] = ok ? ((const float4*)p.anchors)[(long long)q * 9 + k] : make_float4(0, 0, 0, 0);
+    aarea[k] = (an[k].z - an[k].x) * (an[k].w - an[k].y);
+    best[k] = -1.0f;
+  }
+  int total_valid = 0;
+  for (int n0 = 0; n0 < p.N; n0 += 64) {
+    __syncthreads();
+    if (threadIdx.x == 0) nvalid_s = compact_chunk(p, b, n0, ann);
+    __syncthreads();
+    const int c = nvalid_s;
+    total_valid += c;
+    if (ok) {
+      for (int j = 0; j < c; ++j) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          const float iou = assign_iou(an[k], aarea[k], ann + j * 5);
+          if (iou > best[k]) best[k] = iou;
+        }
+      }
+    }
+  }
+  if (!ok) return;
+  bool pos = false;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pos = pos || (best[k] >= 0.5f);
+  int l = 0;
+#pragma unroll
+  for (int s = 1; s < EFFDET_MAX_SEG; ++s)
+    if (s < g.nlev && q >= g.poff[s]) l = s;
+  g.map[(long long)g.pix0[l] + (long long)b * g.hw[l] + (q - g.poff[l])] = (pos && total_valid > 0) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void opts_iou_kernel(const LossK p, const OptsK o) {
@@ -1010,6 +1062,30 @@ int loss_bwd_reg(const float* reg, const float* anchors, const float* annots, co
 extern "C" long long effdet_loss_workspace_bytes(int B, long long A, int num_classes) {
   LossK k{};
   return (long long)carve_loss(k, nullptr, B, A, num_classes);
+}
+
+extern "C" int effdet_positive_pixel_map(const float* anchors, const float* annots, int B, long long A, int N, int nlev, const int* H,
+                                         const int* W, unsigned char* map, effdet_stream_t stream) {
+  if (!anchors || !annots || !map || !H || !W) return EFFDET_EINVAL;
+  if (B < 1 || B > 65535 || N < 1 || nlev < 1 || nlev > EFFDET_MAX_SEG) return EFFDET_EINVAL;
+  PosMapK g{}; g.map = map; g.nlev = nlev;
+  long long apix = 0, P = 0;
+  for (int l = 0; l < nlev; ++l) {
+    if (H[l] < 1 || W[l] < 1) return EFFDET_EINVAL;
+    apix += (long long)H[l] * W[l];
+  }
+  if (A != 9 * apix) return EFFDET_EINVAL;
+  if (apix * B >= 0x40000000LL) return EFFDET_EUNSUPPORTED;
+  g.apix = (int)apix; apix = 0;
+  for (int l = 0; l < nlev; ++l) {
+    const long long hw = (long long)H[l] * W[l];
+    g.hw[l] = (int)hw; g.poff[l] = (int)apix; g.pix0[l] = (int)P;
+    apix += hw; P += hw * B;
+  }
+  const LossK k = loss_args(nullptr, nullptr, anchors, annots, B, A, 0, N);
+  hipLaunchKernelGGL(loss_pos_map_kernel, dim3((unsigned)((apix + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, k, g);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
 }
 
 extern "C" long long effdet_loss_opts_workspace_bytes(int B, long long A, int num_classes, int N) {

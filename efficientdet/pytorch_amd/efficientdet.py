@@ -347,7 +347,12 @@ class _HeadLossFn(torch.autograd.Function):
         p = [Map.of(t) for t in args[:5]]
         HP = dict(zip(_HEAD_KEYS, args[5:]))
         levels = [m.H * m.W * 9 for m in p] if matcher is not None else None
-        cls, reg, saved = Fn.head_fwd(p, HP, num_classes, dtype, train)
+        # the default matcher's positives are known before the head runs, and every box term reads `reg` at them alone: the regression
+        # tower computes the tiles that can reach one (two small launches per step, no host read: a captured step follows its annotations)
+        need = None
+        if matcher is None and loss is None and Fn.head_fwd_takes_needed(p, dtype, train):
+            need = ops.needed_tiles(anchors, annots, p[0].B, [(m.H, m.W) for m in p])
+        cls, reg, saved = Fn.head_fwd(p, HP, num_classes, dtype, train, reg_needed=need)
         nc = num_classes
         if train and nc % 4 == 0 and LOSS_FWD_GRAD:
             # ONE pass over the 15.7 MB/image of probabilities: losses + d(logits) for an upstream gradient of one, already in

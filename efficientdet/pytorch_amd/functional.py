@@ -480,6 +480,11 @@ HEAD_SPLIT = os.environ.get('EFFDET_HEAD_SPLIT', '1') == '1'     # A/B switch: s
 # layers the gradient is confined to Chebyshev distance k of those pixels: ops.live_tiles flags the units, the split-layout kernels skip
 # the rest.  Bit for bit the dense pass (DESIGN.md section 3 names the one exception: non-finite weights / activations under a zero gradient).
 HEAD_SPARSE_REG = os.environ.get('EFFDET_HEAD_SPARSE_REG', '1') == '1'
+# A/B switch: the forward counterpart.  In training the regression output is read at the positive anchors only, and those follow from
+# anchors and annotations alone: ops.needed_tiles flags, ahead of the head, the tiles of every regression-tower layer whose output can
+# reach a positive anchor (the same geometry, read forwards); the f16x3 kernels write zeros into the rest.  Losses and gradients are bit
+# for bit the dense ones (include/effdet_needed_tiles.h).
+HEAD_SPARSE_REG_FWD = os.environ.get('EFFDET_HEAD_SPARSE_REG_FWD', '1') == '1'
 _split_ok = {}
 
 
@@ -513,7 +518,24 @@ def head_uses_f16x3(Wc, dtype):
     return HEAD_SPLIT and dtype == torch.float32 and ops.F32_ARITH == 'f32' and ops.F32_ARITH_HEAD == 'f16x3' and Wc % 32 == 0
 
 
-def head_fwd(p, HP, num_classes, dtype, train):
+def _head_forms(B, sizes, Wc, dtype, train):
+    """The form head_fwd runs in -> (split, split_bwd, hs).  split: the all-bf16x3 head on split-layout activations.  split_bwd: an exact
+    or f16x3 forward whose backward runs the split-layout gradient kernels (their operands / masks ride along as `ysplit`).  hs: the
+    f16x3 forward (fp32-equivalent three-product fp16 form) -- every conv reads H-split operands and writes H-split outputs; training
+    geometries the split gradient kernels cannot take keep the exact-fp32 head."""
+    split = head_uses_split(B, sizes, Wc, dtype)
+    split_bwd = (not split) and train and ops.F32_ARITH_BWD == 'bf16x3' and head_uses_split(B, sizes, Wc, dtype, 'bf16x3')
+    hs = (not split) and head_uses_f16x3(Wc, dtype) and (split_bwd or not train)
+    return split, split_bwd, hs
+
+
+def head_fwd_takes_needed(p, dtype, train):
+    """Will head_fwd(p, ..., dtype, train) honour reg_needed?  The training f16x3 forward with the split-layout backward, switch on."""
+    _, split_bwd, hs = _head_forms(p[0].B, [(m.H, m.W) for m in p], p[0].C, dtype, train)
+    return bool(HEAD_SPARSE_REG_FWD and train and hs and split_bwd)
+
+
+def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
     """models/retinahead.py:109-132 for all 5 levels per launch (weights are shared across levels).
     p: 5 Maps; HP: dict of head parameter tensors.  -> classification [B,A,nc] fp32 (probabilities),
     regression [B,A,4] fp32.
@@ -521,17 +543,21 @@ def head_fwd(p, HP, num_classes, dtype, train):
     activations with exact-fp32 products, and every activation the BACKWARD will read -- the pyramid and the eight tower outputs,
     operands of the weight gradients and ReLU masks of the data gradients -- is stored a second time in the split layout by the
     conv that produces it (`ysplit`: the epilogue writes both forms; the plain copy dies with the next layer), so that head_bwd
-    runs the split-layout gradient kernels unchanged."""
+    runs the split-layout gradient kernels unchanged.
+    reg_needed (uint8 [radius][tiles], ops.needed_tiles; f16x3 forward only): the caller reads the regression output at the flagged
+    pixels alone, so layer t of the regression tower computes the tiles of row 4 - t and retina_reg those of row 0; the rest of `reg`
+    and of the tower's activations is zeros.  None: dense."""
     dev = p[0].t.device
     B, Wc = p[0].B, p[0].C
     sizes = [(m.H, m.W) for m in p]
     A = sum(h * w for (h, w) in sizes) * 9
-    split = head_uses_split(B, sizes, Wc, dtype)
-    split_bwd = (not split) and train and ops.F32_ARITH_BWD == 'bf16x3' and head_uses_split(B, sizes, Wc, dtype, 'bf16x3')
-    # f16x3 forward (fp32-equivalent three-product fp16 form): every conv below reads H-split operands and writes H-split outputs; the
-    # backward is the split-layout bf16x3 one (split_bwd: its operands / masks ride along as `ysplit`).  Training geometries the split
-    # gradient kernels cannot take keep the exact-fp32 head.
-    hs = (not split) and head_uses_f16x3(Wc, dtype) and (split_bwd or not train)
+    split, split_bwd, hs = _head_forms(B, sizes, Wc, dtype, train)
+    if not (hs and split_bwd):
+        reg_needed = None
+    ntile = sum((B * h * w + 127) // 128 for (h, w) in sizes)
+
+    def need(r):
+        return reg_needed[r] if reg_needed is not None else None
     pin, pin_h = p, None
     if split or split_bwd or hs:    # the pyramid once in the split layout(s): operand of both towers' first conv and of their weight gradients
         pin, pin_h = _pyramid_to_split(p, B, sizes, Wc, dtype, dev, bf=split or split_bwd, h=hs)
@@ -548,7 +574,7 @@ def head_fwd(p, HP, num_classes, dtype, train):
             _, nxt = pyramid_alloc(B, sizes, 256, dtype, dev)
             nxs = pyramid_alloc(B, sizes, 256, dtype, dev)[1] if split_bwd else None
             ops.conv2d(cur, ops.pack_weight(w, dtype, x3=split, h3=hs), nxt, Cin=w.shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1,
-                       shift=b, act=ACT_RELU, split=split, ysplit=nxs, hsplit=hs)
+                       shift=b, act=ACT_RELU, split=split, ysplit=nxs, hsplit=hs, needed=need(4 - t) if tower == 'reg' else None)
             acts[tower].append(nxs if split_bwd else nxt); cur = nxt       # (split_bwd: `cur` stays plain fp32 / H-split and is not kept for backward)
         if tower == 'cls':
             ops.conv2d(cur, ops.pack_weight(HP['retina_cls.weight'], dtype, x3=split, h3=hs), head_out_maps(cls, B, sizes, num_classes),
@@ -556,7 +582,8 @@ def head_fwd(p, HP, num_classes, dtype, train):
                        act=ACT_SIGMOID, out_f32=True, split=split, hsplit=hs)
         else:
             ops.conv2d(cur, ops.pack_weight(HP['retina_reg.weight'], dtype, x3=split, h3=hs), head_out_maps(reg, B, sizes, 4),
-                       Cin=256, Cout=36, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_reg.bias'], out_f32=True, split=split, hsplit=hs)
+                       Cin=256, Cout=36, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_reg.bias'], out_f32=True, split=split, hsplit=hs,
+                       needed=need(0))
     paired = hs and HEAD_PAIR_TOWERS
     if paired:
         # The two towers are independent chains of identical launches: layer t of BOTH as ONE launch (per-segment weights / bias,
@@ -574,14 +601,15 @@ def head_fwd(p, HP, num_classes, dtype, train):
             L5 = len(sizes)
             ops.conv2d(cur['cls'] + cur['reg'], wp2[0], ya + yb, Cin=w2[0].shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1, shift=b2[0],
                        act=ACT_RELU, hsplit=True, ysplit=(sa + sb) if split_bwd else None,
-                       seg_w=[wp2[0]] * L5 + [wp2[1]] * L5, seg_shift=[b2[0]] * L5 + [b2[1]] * L5)
+                       seg_w=[wp2[0]] * L5 + [wp2[1]] * L5, seg_shift=[b2[0]] * L5 + [b2[1]] * L5,
+                       needed=need(4 - t), needed_tile0=ntile if reg_needed is not None else 0)
             acts['cls'].append(sa if split_bwd else ya); acts['reg'].append(sb if split_bwd else yb)
             cur = {'cls': ya, 'reg': yb}
         ops.conv2d(cur['cls'], ops.pack_weight(HP['retina_cls.weight'], dtype, h3=True), head_out_maps(cls, B, sizes, num_classes),
                    Cin=256, Cout=9 * num_classes, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_cls.bias'],
                    act=ACT_SIGMOID, out_f32=True, hsplit=True)
         ops.conv2d(cur['reg'], ops.pack_weight(HP['retina_reg.weight'], dtype, h3=True), head_out_maps(reg, B, sizes, 4),
-                   Cin=256, Cout=36, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_reg.bias'], out_f32=True, hsplit=True)
+                   Cin=256, Cout=36, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_reg.bias'], out_f32=True, hsplit=True, needed=need(0))
     else:
         with _Fork(dev, HEAD_TWO_STREAMS and ops.PROFILE is None) as fk:
             with fk.side():

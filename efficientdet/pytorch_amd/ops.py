@@ -437,7 +437,7 @@ def scale_pack_weight(w_oihw, gate, dtype):
 
 def _conv_desc(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
                res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
-               w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0):
+               w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0, needed=None, needed_tile0=0):
     """The effdet_conv_t of a conv2d(...) call -> (descriptor, xs, ys as lists).  The one place it is built: conv2d launches from it and
     conv2d_plan_info asks the planner about it, so the query describes the launch conv2d makes."""
     if isinstance(xs, Map):
@@ -487,12 +487,16 @@ def _conv_desc(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, sca
         assert live.dtype == torch.uint8 and live.is_contiguous()
         ntile = sum((y.B * y.H * y.W + 127) // 128 for y in ys)
         assert 0 <= live_tile0 <= ntile and live.numel() == ntile - live_tile0, (live.numel(), ntile, live_tile0)
+    if needed is not None:
+        assert live is None and needed.dtype == torch.uint8 and needed.is_contiguous()
+        ntile = sum((y.B * y.H * y.W + 127) // 128 for y in ys)
+        assert 0 <= needed_tile0 <= ntile and needed.numel() == ntile - needed_tile0, (needed.numel(), ntile, needed_tile0)
     return d, xs, ys
 
 
 def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
            res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
-           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0):
+           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0, needed=None, needed_tile0=0):
     """Grouped implicit-GEMM conv: xs/ys (and optional zs/res) are lists of Map, one per pyramid level.
     split=True (EFFDET_F32_SPLIT): xs hold the split layout ([32 x bf16 hi | 32 x bf16 lo] per 32 channels, 4 B per element), wp
     is packed for bf16x3; ys are written split too unless out_f32 (then plain fp32; res, if any, is plain and ADDed).
@@ -503,11 +507,14 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     weights / bias rows -- the same layer of the head's two towers in one launch (<= 10 maps).  Same values as separate launches.
     live (uint8 tensor, one byte per 128-pixel tile from tile live_tile0 on: live_tiles()[1][r]): a 0 marks a tile whose every input
     tap is zero; the split-layout kernels without bias / affine / activation skip it (zeros out, or nothing under an in-place RES_ADD),
-    every other launch ignores the flags.  Same values as without, but 0 where the dense launch would give 0 * Inf = NaN."""
+    every other launch ignores the flags.  Same values as without, but 0 where the dense launch would give 0 * Inf = NaN.
+    needed (uint8 tensor, one byte per 128-pixel tile from tile needed_tile0 on: needed_tiles()[r]): a 0 marks a tile whose result
+    nobody reads; the f16x3 kernels (hsplit) do not compute it and write zeros into every output stream (ys, ysplit) instead, every
+    other launch ignores the flags.  The needed tiles hold what the dense launch gives them."""
     d, xs, ys = _conv_desc(xs, wp, ys, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad_t=pad_t, pad_l=pad_l, scale=scale, shift=shift,
                            act=act, res=res, res_mode=res_mode, rowscale=rowscale, zs=zs, out_f32=out_f32, split=split, bc_scale=bc_scale,
                            bc_shift=bc_shift, w_image_stride=w_image_stride, ysplit=ysplit, hsplit=hsplit, seg_w=seg_w, seg_shift=seg_shift,
-                           live=live, live_tile0=live_tile0)
+                           live=live, live_tile0=live_tile0, needed=needed, needed_tile0=needed_tile0)
     x0, y0 = xs[0], ys[0]
     isx, isy = x0.t.element_size(), y0.t.element_size()
     flops = 2.0 * KH * KW * Cin * Cout * sum(y.B * y.H * y.W for y in ys)
@@ -517,11 +524,18 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     if live is not None:
         run = lambda: L.check(L.require('effdet_conv2d_live').effdet_conv2d_live(C.byref(d), live.data_ptr(), int(live_tile0), L.stream_ptr()),
                               'effdet_conv2d_live')
+    elif needed is not None:
+        NEEDED_LAUNCHES[0] += 1
+        run = lambda: L.check(L.require('effdet_conv2d_needed').effdet_conv2d_needed(C.byref(d), needed.data_ptr(), int(needed_tile0),
+                                                                                     L.stream_ptr()), 'effdet_conv2d_needed')
     else:
         run = lambda: L.check(L.lib().effdet_conv2d(C.byref(d), L.stream_ptr()), 'effdet_conv2d')
     # (flops stay those of the dense launch: a flagged launch reports an EFFECTIVE rate)
     _timed(_igemm_symbol(x0.dtype, d) if PROFILE is not None else '', flops, run,
            'k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, sum(y.B * y.H * y.W for y in ys)), nbytes=float(nbytes))
+
+
+NEEDED_LAUNCHES = [0]        # conv2d(..., needed=...) calls made so far (tests: which path a step took)
 
 
 def conv2d_plan_info(xs, wp, ys, **kw):
@@ -773,6 +787,49 @@ def live_tiles(dreg, B, sizes, reg_ld, split):
     L.check(lib_.effdet_live_tiles(dreg.data_ptr(), L.F32_SPLIT if split else L.F32, reg_ld, B, n, Hs, Ws, scratch.data_ptr(),
                                    l32.data_ptr(), l128.data_ptr(), L.stream_ptr()), 'effdet_live_tiles')
     return l32, l128
+
+
+def _level_arrays(sizes):
+    n = len(sizes)
+    return n, (C.c_int * n)(*[h for h, _ in sizes]), (C.c_int * n)(*[w for _, w in sizes])
+
+
+def positive_pixel_map(anc, annots, sizes):
+    """The pixels with at least one positive anchor under the default matcher (include/effdet_needed_tiles.h), from the anchor table
+    [1, A, 4] and the annotations [B, N, 5] alone -> uint8 [sum B*H*W], level-major, each level in (b, h, w) order: the layout of
+    live_tiles' per-pixel map.  Equal to (assign >= 0) of the loss's assign pass OR-ed over each pixel's 9 anchors.  One launch."""
+    B, N = annots.shape[0], annots.shape[1]
+    A = anc.numel() // 4
+    n, Hs, Ws = _level_arrays(sizes)
+    assert anc.dtype == torch.float32 and anc.is_contiguous() and annots.dtype == torch.float32 and annots.is_contiguous()
+    out = torch.empty(B * sum(h * w for h, w in sizes), dtype=torch.uint8, device=annots.device)
+    L.check(L.require('effdet_positive_pixel_map').effdet_positive_pixel_map(L.ptr(anc), L.ptr(annots), B, A, N, n, Hs, Ws, out.data_ptr(),
+                                                                             L.stream_ptr()), 'effdet_positive_pixel_map')
+    return out
+
+
+def live_tiles_from_map(pixmap, B, sizes):
+    """live_tiles' flags from a per-pixel byte map (positive_pixel_map's layout; non-zero = non-zero pixel) -> (live32 [6][steps],
+    live128 [6][tiles]) uint8.  Two kernel launches, nothing else."""
+    lib_ = L.require('effdet_live_tiles_counts', 'effdet_live_tiles_from_map')
+    n, Hs, Ws = _level_arrays(sizes)
+    steps, tiles = C.c_longlong(), C.c_longlong()
+    pixels = int(lib_.effdet_live_tiles_counts(B, n, Hs, Ws, C.byref(steps), C.byref(tiles)))
+    if pixels < 0:
+        L.check(pixels, 'effdet_live_tiles_counts')
+    assert pixmap.dtype == torch.uint8 and pixmap.is_contiguous() and pixmap.numel() == pixels
+    S, T, R = steps.value, tiles.value, L.LIVE_RADII
+    buf = torch.empty(R * S + R * T + 2 * pixels, dtype=torch.uint8, device=pixmap.device)
+    l32, l128, scratch = buf[:R * S].view(R, S), buf[R * S:R * (S + T)].view(R, T), buf[R * (S + T):]
+    L.check(lib_.effdet_live_tiles_from_map(pixmap.data_ptr(), B, n, Hs, Ws, scratch.data_ptr(), l32.data_ptr(), l128.data_ptr(),
+                                            L.stream_ptr()), 'effdet_live_tiles_from_map')
+    return l32, l128
+
+
+def needed_tiles(anc, annots, B, sizes):
+    """-> uint8 [6][tiles]: row r flags the 128-pixel tiles holding a pixel within Chebyshev distance r of a pixel with a positive
+    anchor -- the tiles of the regression tower's forward pass whose output can reach the loss (conv2d(..., needed=row))."""
+    return live_tiles_from_map(positive_pixel_map(anc, annots, sizes), B, sizes)[1]
 
 
 def to_split(t):
