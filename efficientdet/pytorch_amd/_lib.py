@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h).
+include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -309,6 +309,12 @@ WBF_SIGNATURES = {
     'effdet_wbf_workspace_bytes': 'q:iii',
     'effdet_wbf': 'i:ppqs',
 }
+# Mosaic and MixUp in front of the 'train' augmentation chain, declared in include/effdet_mosaic.h (same generation, same letters, same
+# rule; tests/test_mosaic_host.py compares this table with that header's prototypes).
+MOSAIC_SIGNATURES = {
+    'effdet_mosaic_compose': 'i:ppppiiips',
+    'effdet_mosaic_boxes': 'i:ppiipiffpips',
+}
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
 DW_PLAN_FWD, DW_PLAN_DGRAD, DW_PLAN_WGRAD, DW_PLAN_BWD, DW_PLAN_EXPAND_FWD = 0, 1, 2, 3, 4      # EFFDET_DW_PLAN_*
@@ -333,7 +339,7 @@ def lib():
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
-                list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()):
+                list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

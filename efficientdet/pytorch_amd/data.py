@@ -284,6 +284,126 @@ def check_augment_table(table, B, S):
     return t
 
 
+# ------------------------------------------------------------------------------------------------ Mosaic / MixUp on the device
+# Columns of the per-image mosaic table (include/effdet_mosaic.h, EFFDET_MOSAIC_P), one row per OUTPUT image.
+MOSAIC_COLUMNS = ('on', 'cx', 'cy', 'src0', 'src1', 'src2', 'src3', 'side0', 'side1', 'side2', 'side3', 'mix', 'mix_src', 'lam')
+MOSAIC = {n: i for i, n in enumerate(MOSAIC_COLUMNS)}
+
+
+def _lms_dims(h, w, S):
+    """LongestMaxSize(S)'s output size of an h x w image (Python's round: half to even, as the kernels' rint)."""
+    scale = S / max(h, w)
+    return int(round(h * scale)), int(round(w * scale))
+
+
+class MosaicOptions:
+    """Mosaic (four images of the batch around a random centre) and MixUp (a partner image blended in) in front of the 'train' chain
+    of DeviceAugmentation; include/effdet_mosaic.h holds the semantics.
+
+    p: probability that an output image is a mosaic (else it is its own source, as without the option).  centre: range of the
+    centre, as fractions of the canvas side.  scale: range of each quadrant image's longest side, as fractions of the canvas side.
+    fill: the background byte.  mixup_p: probability that a mosaic is blended with a partner; the blend weight is Beta(mixup_alpha,
+    mixup_alpha).  Sources come from the batch itself, with replacement."""
+
+    def __init__(self, p=1.0, centre=(0.25, 0.75), scale=(0.5, 1.0), fill=114, mixup_p=0.0, mixup_alpha=8.0):
+        self.p, self.mixup_p, self.mixup_alpha = float(p), float(mixup_p), float(mixup_alpha)
+        self.centre, self.scale = tuple(float(v) for v in centre), tuple(float(v) for v in scale)
+        if not 0.0 <= self.p <= 1.0 or not 0.0 <= self.mixup_p <= 1.0:
+            raise ValueError('p and mixup_p are probabilities in [0, 1]')
+        if len(self.centre) != 2 or not 0.0 <= self.centre[0] <= self.centre[1] <= 1.0:
+            raise ValueError('centre is a range (lo, hi) with 0 <= lo <= hi <= 1')
+        if len(self.scale) != 2 or not 0.0 < self.scale[0] <= self.scale[1] <= 1.0:
+            raise ValueError('scale is a range (lo, hi) with 0 < lo <= hi <= 1')
+        if isinstance(fill, bool) or int(fill) != fill or not 0 <= int(fill) <= 255:
+            raise ValueError('fill is a byte, 0 .. 255')
+        self.fill = int(fill)
+        if not (self.mixup_alpha > 0.0 and math.isfinite(self.mixup_alpha)):
+            raise ValueError('mixup_alpha must be positive and finite')
+
+    def key(self):
+        return (self.p, self.centre, self.scale, self.fill, self.mixup_p, self.mixup_alpha)
+
+    def __eq__(self, other):
+        return isinstance(other, MosaicOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'MosaicOptions(p=%r, centre=%r, scale=%r, fill=%r, mixup_p=%r, mixup_alpha=%r)' % self.key()
+
+
+def sample_mosaic_table(rng, B, S, opts):
+    """Draw the mosaic parameters of B output images on an S x S canvas from rng (np.random.RandomState) -> [B, len(MOSAIC_COLUMNS)]
+    fp32.  Order per image: on (probability p); then, only when on: cx and cy (integers in round(centre * S)), src1..3 (uniform
+    over the batch, with replacement; src0 = b), side0..3 (max(1, round(U(scale) * S))), mix (probability mixup_p) and, only when
+    mix, mix_src (uniform over the batch) and lam ~ Beta(mixup_alpha, mixup_alpha)."""
+    t = np.zeros((B, len(MOSAIC_COLUMNS)), dtype=np.float32)
+    c_lo, c_hi = int(round(opts.centre[0] * S)), int(round(opts.centre[1] * S))
+    for b in range(B):
+        r = t[b]
+        r[MOSAIC['src0']] = b
+        if rng.rand() >= opts.p:
+            continue
+        r[MOSAIC['on']] = 1
+        r[MOSAIC['cx']], r[MOSAIC['cy']] = rng.randint(c_lo, c_hi + 1), rng.randint(c_lo, c_hi + 1)
+        r[MOSAIC['src1']:MOSAIC['src3'] + 1] = rng.randint(0, B, size=3)
+        for q in range(4):
+            r[MOSAIC['side0'] + q] = min(S, max(1, int(round(rng.uniform(opts.scale[0], opts.scale[1]) * S))))
+        if rng.rand() < opts.mixup_p:
+            r[MOSAIC['mix']], r[MOSAIC['mix_src']] = 1, rng.randint(0, B)
+            r[MOSAIC['lam']] = min(1.0, max(0.0, rng.beta(opts.mixup_alpha, opts.mixup_alpha)))
+    return t
+
+
+def check_mosaic_table(table, B, S, hw):
+    """Refuse a table the mosaic stage cannot mean (include/effdet_mosaic.h, Domain): wrong shape, non-integers, sources outside the
+    batch, centres or sides outside their ranges, mix without on, lam outside [0, 1], or a resized side that rounds to 0.  hw: the
+    sources' (h, w) [B, 2] on the host.  Raises ValueError naming the row -> the table as fp32."""
+    t = np.asarray(table, dtype=np.float32)
+    if t.shape != (B, len(MOSAIC_COLUMNS)):
+        raise ValueError('mosaic table must be [%d, %d], got %s' % (B, len(MOSAIC_COLUMNS), t.shape))
+    hw = np.asarray(hw).reshape(-1, 2)
+    if hw.shape != (B, 2):
+        raise ValueError('mosaic table check needs the %d source sizes [B, 2], got %s' % (B, hw.shape))
+
+    def bad(b, what):
+        raise ValueError('mosaic table row %d: %s' % (b, what))
+    for b in range(B):
+        r = t[b]
+        on, mix = r[MOSAIC['on']], r[MOSAIC['mix']]
+        if on not in (0.0, 1.0) or mix not in (0.0, 1.0):
+            bad(b, 'on and mix are 0 or 1')
+        if mix and not on:
+            bad(b, 'mix needs on')
+        if min(_lms_dims(int(hw[b, 0]), int(hw[b, 1]), S)) < 1:
+            bad(b, 'source %d (%d x %d) has a side that resizes to 0 at %d' % (b, hw[b, 0], hw[b, 1], S))
+        if not on:
+            continue                                               # the rest of a pass-through row is ignored
+        ints = r[:MOSAIC['lam']]
+        if not np.all(np.isfinite(ints)) or np.any(ints != np.round(ints)):
+            bad(b, 'every column but lam is an integer')
+        if not (0 <= r[MOSAIC['cx']] <= S and 0 <= r[MOSAIC['cy']] <= S):
+            bad(b, 'the centre lies in [0, %d]' % S)
+        for q in range(4):
+            src, side = r[MOSAIC['src0'] + q], r[MOSAIC['side0'] + q]
+            if not 0 <= src < B:
+                bad(b, 'src%d = %d is outside the batch of %d' % (q, src, B))
+            if not 1 <= side <= S:
+                bad(b, 'side%d = %d is outside [1, %d]' % (q, side, S))
+            if min(_lms_dims(int(hw[int(src), 0]), int(hw[int(src), 1]), int(side))) < 1:
+                bad(b, 'source %d (%d x %d) has a side that resizes to 0 at side%d = %d' % (src, hw[int(src), 0], hw[int(src), 1], q, side))
+        if mix:
+            src, lam = r[MOSAIC['mix_src']], r[MOSAIC['lam']]
+            if not 0 <= src < B:
+                bad(b, 'mix_src = %d is outside the batch of %d' % (src, B))
+            if not 0.0 <= lam <= 1.0:                              # (refuses NaN too)
+                bad(b, 'lam = %r is outside [0, 1]' % float(lam))
+            if min(_lms_dims(int(hw[int(src), 0]), int(hw[int(src), 1]), S)) < 1:
+                bad(b, 'partner %d (%d x %d) has a side that resizes to 0 at %d' % (src, hw[int(src), 0], hw[int(src), 1], S))
+    return t
+
+
 class DeviceAugmentation(DeviceCollater):
     """get_augumentation(phase, width, height, min_area, min_visibility) + detection_collate (datasets/augmentation.py:8-67) on the
     device: ``images, annotations, params = aug(samples)``.
@@ -297,12 +417,18 @@ class DeviceAugmentation(DeviceCollater):
     ``aug(samples, table=...)`` runs 'train' with an explicit table (numpy or tensor, columns AUG_COLUMNS).
 
     The host draws the table (sample_augment_table) and copies the uint8 bytes; every pixel and box operation runs in
-    csrc/augment.hip.  'train' needs width == height (the reference's transpose and crop assume a square output)."""
+    csrc/augment.hip.  'train' needs width == height (the reference's transpose and crop assume a square output).
+
+    mosaic: a MosaicOptions puts Mosaic / MixUp (csrc/mosaic.hip) in front of the 'train' chain: the batch's images are composed
+    into B canvases of width x width, and the chain runs on those as if they were the dataset's images.  Annotations then have up to
+    5 x the longest input list of rows before trimming.  It is a plain attribute: ``aug.mosaic = None`` switches the stage off (the
+    last epochs of a schedule), and nothing of it runs then.  ``aug(samples, mosaic_table=...)`` takes an explicit table (host
+    memory: numpy or CPU tensor, columns MOSAIC_COLUMNS); it always passes check_mosaic_table."""
 
     PHASES = ('train', 'valid', 'test')
 
     def __init__(self, phase='train', width=512, height=512, min_area=0., min_visibility=0., dtype=torch.bfloat16, device='cuda',
-                 seed=0, trim=True, decode_threads=8, decode_fallback=None):
+                 seed=0, trim=True, decode_threads=8, decode_fallback=None, mosaic=None):
         if phase not in self.PHASES:
             raise ValueError('phase must be one of %s' % (self.PHASES,))
         if phase == 'train' and (width != height or width < 8):
@@ -311,10 +437,23 @@ class DeviceAugmentation(DeviceCollater):
                          decode_fallback=decode_fallback)
         self.phase, self.W, self.H = phase, int(width), int(height)
         self.min_area, self.min_visibility, self.trim = float(min_area), float(min_visibility), bool(trim)
+        if mosaic is not None and not isinstance(mosaic, MosaicOptions):
+            raise TypeError('mosaic is a MosaicOptions or None')
+        if mosaic is not None and phase != 'train':
+            raise ValueError("mosaic only applies to the 'train' phase")
+        self.mosaic = mosaic
 
-    def __call__(self, samples, table=None, stages=None):
-        """stages: optional dict that receives the uint8 intermediates of ops.augment_train / ops.augment_resize (tests)."""
+    def __call__(self, samples, table=None, stages=None, mosaic_table=None):
+        """stages: optional dict that receives the uint8 intermediates of ops.augment_train / ops.augment_resize (tests), and with
+        mosaic 'mosaic' (uint8 [B,S,S,3]) and 'mosaic_table' (the device table)."""
         B = len(samples)
+        mosaic = getattr(self, 'mosaic', None)
+        if mosaic is not None and self.phase != 'train':
+            raise ValueError("mosaic only applies to the 'train' phase")
+        if mosaic_table is not None and mosaic is None:
+            raise ValueError('mosaic_table was given, but this augmentation has no mosaic options')
+        if mosaic_table is not None and torch.is_tensor(mosaic_table) and mosaic_table.device.type != 'cpu':
+            raise ValueError('a mosaic table comes from the host (numpy or CPU tensor): it is checked before anything is launched')
         staged = self._stage_batch(samples)
         if self.phase == 'train':
             if table is None:
@@ -326,6 +465,21 @@ class DeviceAugmentation(DeviceCollater):
         ann = self._padded_annots(samples) if self.phase != 'test' else None
         dev = self.device
         src, d_off, d_hw, hw = self._upload(samples, staged)
+        d_ann = None
+        if mosaic is not None:
+            if mosaic_table is None:
+                mosaic_table = sample_mosaic_table(self.rng, B, self.S, mosaic)
+            mt = check_mosaic_table(mosaic_table.numpy() if torch.is_tensor(mosaic_table) else mosaic_table, B, self.S, hw)
+            d_mt = torch.from_numpy(np.ascontiguousarray(mt)).to(dev, non_blocking=True)
+            canvas = ops.mosaic_compose(src, d_off, d_hw, d_mt, self.S, mosaic.fill)
+            d_ann, _ = ops.mosaic_boxes(d_hw, d_mt, self.S, torch.from_numpy(ann).to(dev, non_blocking=True), self.min_area,
+                                        self.min_visibility)
+            if stages is not None:
+                stages.update(mosaic=canvas, mosaic_table=d_mt)
+            # the chain takes the canvases as a batch of S x S dataset images
+            src = canvas.view(-1)
+            d_off = torch.arange(B, dtype=torch.int64, device=dev) * (self.S * self.S * 3)
+            d_hw = torch.full((B, 2), self.S, dtype=torch.int32, device=dev)
         if self.phase == 'train':
             params = (table if torch.is_tensor(table) else torch.from_numpy(table)).to(dev, torch.float32, non_blocking=True).contiguous()
             m = ops.augment_train(src, d_off, d_hw, params, self.S, self.dtype, chunk_elems(self.dtype), MEAN, STD, stages)
@@ -335,7 +489,8 @@ class DeviceAugmentation(DeviceCollater):
             m = ops.augment_resize(src, d_off, d_hw, self.H, self.W, self.dtype, chunk_elems(self.dtype), MEAN, STD, stages)
         if ann is None:
             return PackedImages(m), None, params
-        d_ann = torch.from_numpy(ann).to(dev, non_blocking=True)
+        if d_ann is None:
+            d_ann = torch.from_numpy(ann).to(dev, non_blocking=True)
         out, counts = ops.augment_boxes(d_hw, params if self.phase == 'train' else None, self.H, self.W, d_ann, self.min_area,
                                         self.min_visibility)
         if self.trim:

@@ -2043,6 +2043,36 @@ def augment_boxes(src_hw, table, H, W, annots, min_area=0.0, min_visibility=0.0)
     return out, counts
 
 
+# ----------------------------------------------------------------------------- Mosaic / MixUp (csrc/mosaic.hip)
+_MOSAIC = ('effdet_mosaic_compose', 'effdet_mosaic_boxes')
+MOSAIC_P = 14                      # EFFDET_MOSAIC_P: columns of the per-image mosaic table (include/effdet_mosaic.h)
+
+
+def mosaic_compose(src_u8, src_off, src_hw, table, S, fill=114):
+    """Mosaic / MixUp of a batch (include/effdet_mosaic.h): uint8 HWC images (concatenated, device) + table [B, MOSAIC_P] fp32
+    (device) -> uint8 [B,S,S,3], the input of augment_train with src_off = b * S*S*3 and src_hw = (S, S)."""
+    B = int(src_hw.shape[0])
+    assert table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (B, MOSAIC_P)
+    out = torch.empty((B, int(S), int(S), 3), dtype=torch.uint8, device=src_u8.device)
+    L.check(L.require(*_MOSAIC).effdet_mosaic_compose(L.ptr(src_u8), L.ptr(src_off), L.ptr(src_hw), L.ptr(table), B, int(S), int(fill),
+                                                      L.ptr(out), L.stream_ptr()), 'effdet_mosaic_compose')
+    return out
+
+
+def mosaic_boxes(src_hw, table, S, annots, min_area=0.0, min_visibility=0.0):
+    """Boxes [B,M,5] fp32 of the SOURCE images (label -1 = padding) through the mosaic geometry of `table`, clipped to their windows
+    and filtered -> (out [B,5M,5]: per image the kept rows of TL, TR, BL, BR and the partner, -1 rows after; counts [B] int32)."""
+    B, M = int(annots.shape[0]), int(annots.shape[1])
+    assert annots.dtype == torch.float32 and annots.is_contiguous() and annots.shape[2] == 5
+    assert table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (B, MOSAIC_P)
+    out = torch.empty((B, 5 * M, 5), dtype=torch.float32, device=annots.device)
+    counts = torch.empty(B, dtype=torch.int32, device=annots.device)
+    L.check(L.require(*_MOSAIC).effdet_mosaic_boxes(L.ptr(src_hw), L.ptr(table), B, int(S), L.ptr(annots), M, float(min_area),
+                                                    float(min_visibility), L.ptr(out), 5 * M, L.ptr(counts), L.stream_ptr()),
+            'effdet_mosaic_boxes')
+    return out, counts
+
+
 # ----------------------------------------------------------------------------- JPEG decode (csrc/jpeg.hip)
 _JPEG = ('effdet_jpeg_probe', 'effdet_jpeg_entropy_batch', 'effdet_jpeg_reconstruct')
 JPEG_GREY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3
