@@ -315,6 +315,11 @@ MOSAIC_SIGNATURES = {
     'effdet_mosaic_compose': 'i:ppppiiips',
     'effdet_mosaic_boxes': 'i:ppiipiffpips',
 }
+# Two weight gradients of one geometry as one launch, declared in include/effdet_wgrad_pair.h (same generation, same letters, same
+# rule; tests/test_wgrad_pair_host.py compares this table with that header's prototype).
+WGRAD_PAIR_SIGNATURES = {
+    'effdet_conv2d_wgrad_pair': 'i:pppqps',
+}
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
 DW_PLAN_FWD, DW_PLAN_DGRAD, DW_PLAN_WGRAD, DW_PLAN_BWD, DW_PLAN_EXPAND_FWD = 0, 1, 2, 3, 4      # EFFDET_DW_PLAN_*
@@ -339,7 +344,8 @@ def lib():
         for name, sig in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()) + list(EMA_SIGNATURES.items()) + \
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
-                list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()):
+                list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
+                list(WGRAD_PAIR_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

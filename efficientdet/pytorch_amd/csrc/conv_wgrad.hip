@@ -23,6 +23,7 @@
 //     consumer sums the rows in slab order -- no float atomics anywhere: two runs are bitwise equal.
 #include "common.h"
 #include "../../../include/effdet_live_tiles.h"
+#include "../../../include/effdet_wgrad_pair.h"
 #include <stdlib.h>
 
 #ifndef EFFDET_WGRAD_TR_WAVES
@@ -494,20 +495,16 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_tr_kernel(const WgradK p) 
 // p.live32 is set, in order, through the same two-stage pipeline -- a skipped step would have added +-0 to every accumulator and bias
 // sum.  The flags of up to 64 steps are fetched as one ballot (every wave reads the same bytes: the walk is workgroup-uniform) and
 // stage() gets a seek() that recomputes the scalar pixel cursor on a jump.  A range without a live step takes the zero-slab branch.
-template <int ALLR, int LIVE = 0>     // ALLR = 1: all 24 fragment reads of a K-step issued before its first MFMA (A/B knob EFFDET_WGRAD_SPLIT_ALLR)
-__global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
+// The body is one workgroup's work on tile (nt, jt) of split `split`: p carries the geometry, the arguments the problem's own pieces --
+// its level sg, operand bases, slab / bias-row bases and flags -- so that conv_wgrad_pair_kernel can run two problems in one grid.
+template <int ALLR, int LIVE>         // ALLR = 1: all 24 fragment reads of a K-step issued before its first MFMA (A/B knob EFFDET_WGRAD_SPLIT_ALLR)
+__device__ __forceinline__ void wgrad_split_block(const WgradK& p, const WSeg& sg, const void* const px, const void* const pdz, float* const pslab,
+                                                  float* const pdbp, const unsigned char* const plive, const int nt, const int jt, const int split) {
   constexpr unsigned OPB = 16384, BUFB = 2 * OPB, RG = 4096;     // operand / stage / row-group (8 pixels x 4 pieces) bytes
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave >> 2, wj = wave & 3;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int nt = logical % p.ntiles, jt = (logical / p.ntiles) % p.jtiles, split = logical / (p.ntiles * p.jtiles);
-  int si = 0;
-#pragma unroll
-  for (int s = 1; s < EFFDET_MAX_SEG; ++s)
-    if (s < p.nseg && split >= p.seg[s].split_start) si = s;
-  const WSeg sg = p.seg[si];
   const int m_begin = (split - sg.split_start) * p.mchunk;
   const int m_end = min(sg.M, m_begin + p.mchunk);
   const int nsteps = (m_end - m_begin + 31) / 32;
@@ -539,8 +536,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
                 ((dkw < 0 && dwo == 0) ? 8u : 0u) | ((dkw > 0 && dwo == Wr - 1) ? 16u : 0u);
     }
   }
-  const u32x4_t srd = stage_x ? make_srd_raw((const bf16_t*)p.x + sg.in_off, sg.x_bytes)
-                              : make_srd_raw((const bf16_t*)p.dz + sg.out_off, sg.dz_bytes);
+  const u32x4_t srd = stage_x ? make_srd_raw((const bf16_t*)px + sg.in_off, sg.x_bytes)
+                              : make_srd_raw((const bf16_t*)pdz + sg.out_off, sg.dz_bytes);
   const u32x4_t srd_u = u32x4_t{(unsigned)__builtin_amdgcn_readfirstlane((int)srd[0]), (unsigned)__builtin_amdgcn_readfirstlane((int)srd[1]),
                                 (unsigned)__builtin_amdgcn_readfirstlane((int)srd[2]), (unsigned)__builtin_amdgcn_readfirstlane((int)srd[3])};
   const unsigned s_bs = (unsigned)((stage_x ? sg.in_bs : sg.out_bs) * 2), s_ld = (unsigned)((stage_x ? p.ldx : p.lddz) * 2);
@@ -557,7 +554,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
     cho = crem / sg.Wo; cwo = crem - cho * sg.Wo;
   };
   // LIVE: first live step >= s of the range (nsteps: none).  The flags of the 64-step window around s are held as a lane mask.
-  const unsigned char* const lv = LIVE ? p.live32 + sg.step0 + m_begin / 32 : nullptr;
+  const unsigned char* const lv = LIVE ? plive + sg.step0 + m_begin / 32 : nullptr;
   int lwin = -1; unsigned long long lmask = 0ull;
   auto next_live = [&](int s) -> int {
     while (s < nsteps) {
@@ -612,10 +609,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
 #pragma unroll
       for (int b = 0; b < 2; ++b) acc[gi][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-  const bool want_bias = (p.dbp != nullptr) && (jt == 0) && (wj == 0);
+  const bool want_bias = (pdbp != nullptr) && (jt == 0) && (wj == 0);
   const uint4 ones = WMma<bf16_t>::ones();
   const int l15 = lane & 15, lq = lane >> 4;
-  float* slab = p.slab + (long long)split * p.Cout * p.K;
+  float* slab = pslab + (long long)split * p.Cout * p.K;
   const int n_alg0 = nt * 128 + wn * 64, j_alg0 = jt * 128 + wj * 32;
 
   int nxt = LIVE ? next_live(0) : 0;                                // (LIVE: the step staged next; else unused past this test)
@@ -688,15 +685,70 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
             const int j = j_alg0 + b * 16 + l15;
             if (j < p.K) slab[(long long)n * p.K + j] = acc[gi][a][b][rr];
           }
-          if (want_bias && l15 == 0) p.dbp[(long long)split * p.Cout + n] = bsum[gi][a][rr];
+          if (want_bias && l15 == 0) pdbp[(long long)split * p.Cout + n] = bsum[gi][a][rr];
         }
   } else {
     for (int i = tid; i < 128 * 128; i += 512) {
       const int n = nt * 128 + i / 128, j = jt * 128 + (i & 127);
       if (n < p.Cout && j < p.K) slab[(long long)n * p.K + j] = 0.f;
     }
-    if (p.dbp && jt == 0 && tid < 128 && nt * 128 + tid < p.Cout) p.dbp[(long long)split * p.Cout + nt * 128 + tid] = 0.f;
+    if (pdbp && jt == 0 && tid < 128 && nt * 128 + tid < p.Cout) pdbp[(long long)split * p.Cout + nt * 128 + tid] = 0.f;
   }
+}
+
+
+template <int ALLR, int LIVE = 0>
+__global__ __launch_bounds__(512) void conv_wgrad_split_kernel(const WgradK p) {
+  const int logical = xcd_remap(blockIdx.x, gridDim.x);
+  const int nt = logical % p.ntiles, jt = (logical / p.ntiles) % p.jtiles, split = logical / (p.ntiles * p.jtiles);
+  int si = 0;
+#pragma unroll
+  for (int s = 1; s < EFFDET_MAX_SEG; ++s)
+    if (s < p.nseg && split >= p.seg[s].split_start) si = s;
+  wgrad_split_block<ALLR, LIVE>(p, p.seg[si], p.x, p.dz, p.slab, p.dbp, p.live32, nt, jt, split);
+}
+
+// Two problems of one geometry (effdet_conv2d_wgrad_pair: the same layer of the RetinaHead's two towers) as ONE grid: a workgroup is a
+// (tile, split) of problem 0 or 1, planned exactly as the problem's own launch plans it, so slabs and bias rows are bit for bit those
+// of the separate launches.  Problem 1 may carry step flags (LIVEB); the dense problem runs the LIVE = 0 body (no flag walk): the choice
+// is workgroup-uniform and made once, ahead of the body.
+// Block order.  Workgroup bid runs on XCD bid & 7 as that XCD's (bid >> 3)-th, so xcd_remap's contiguous eighth of ONE index space over
+// both problems would put each problem on four of the eight XCDs.  Instead every XCD takes its eighth of problem `first`, then its
+// eighth of the other one (both partitions are xcd_remap's).  A dense problem numbers its blocks tile-fastest as the single launch does
+// (the blocks of an XCD share pixel ranges and their dz / x tiles stay in its L2).  The flagged problem numbers them SPLIT-fastest, splits
+// descending: the live steps cluster -- dilated flags leave the ranges of the coarse levels almost entirely live, most ranges of the
+// fine levels almost empty -- and tile-fastest eighths would hand all the long ranges to one XCD (which is what makes the single
+// flagged launch last as long as a dense range started late); dealt over the XCDs they start at once, the many short ranges cost next
+// to nothing and the dense blocks fill every slot behind them.
+struct WgradPairK {
+  WgradK k;                             // the shared geometry (problem 0's plan; the fields below replace its per-problem ones)
+  const void* x[2]; const void* dz[2];
+  float* slab[2]; float* dbp[2];
+  const unsigned char* live32;          // problem 1's flags (LIVEB = 1)
+  int nseg[2], splits[2];
+  int first;                            // the problem whose blocks come first
+  WSeg seg[2][EFFDET_MAX_SEG];
+};
+
+template <int ALLR, int LIVEB>
+__global__ __launch_bounds__(512) void conv_wgrad_pair_kernel(const WgradPairK q) {
+  const int tiles = q.k.ntiles * q.k.jtiles;
+  const int xcd = (int)blockIdx.x & 7, idx = (int)blockIdx.x >> 3;
+  auto eighth = [](int n, int x) { return x * (n >> 3) + min(x, n & 7); };      // first block of XCD x in xcd_remap's partition of n blocks
+  const int f0 = eighth(tiles * q.splits[q.first], xcd), nf = eighth(tiles * q.splits[q.first], xcd + 1) - f0;
+  const int prob = idx < nf ? q.first : q.first ^ 1;                  // (workgroup-uniform: scalar)
+  const int l = idx < nf ? f0 + idx : eighth((int)gridDim.x, xcd) - f0 + (idx - nf);
+  int split, tile;
+  if (LIVEB && prob == 1) { tile = l / q.splits[1]; split = q.splits[1] - 1 - (l - tile * q.splits[1]); }
+  else { split = l / tiles; tile = l - split * tiles; }
+  const int nt = tile % q.k.ntiles, jt = tile / q.k.ntiles;
+  int si = 0;
+#pragma unroll
+  for (int s = 1; s < EFFDET_MAX_SEG; ++s)
+    if (s < q.nseg[prob] && split >= q.seg[prob][s].split_start) si = s;
+  const WSeg sg = q.seg[prob][si];
+  if (LIVEB && prob == 1) wgrad_split_block<ALLR, 1>(q.k, sg, q.x[1], q.dz[1], q.slab[1], q.dbp[1], q.live32, nt, jt, split);
+  else wgrad_split_block<ALLR, 0>(q.k, sg, q.x[prob], q.dz[prob], q.slab[prob], q.dbp[prob], nullptr, nt, jt, split);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1518,4 +1570,60 @@ extern "C" int effdet_conv2d_wgrad_live(const effdet_wgrad_t* p, void* workspace
                                         const unsigned char* live32, effdet_stream_t stream) {
   if (!live32) return EFFDET_EINVAL;
   return wgrad_launch(p, workspace, workspace_bytes, live32, stream);
+}
+
+// Two split-layout problems of one geometry as one launch (include/effdet_wgrad_pair.h): each planned as plan_wgrad plans it alone,
+// a's slabs and bias rows at the head of the workspace in effdet_conv2d_wgrad's layout, b's behind them.
+extern "C" int effdet_conv2d_wgrad_pair(const effdet_wgrad_t* a, const effdet_wgrad_t* b, void* workspace, long long workspace_bytes,
+                                        const unsigned char* live32_b, effdet_stream_t stream) {
+  if (!a || !b || !a->x || !a->dz || !b->x || !b->dz || !workspace) return EFFDET_EINVAL;
+  WgradPlan wa, wb;
+  int rc = plan_wgrad(a, wa);
+  if (rc != EFFDET_OK) return rc;
+  rc = plan_wgrad(b, wb);
+  if (rc != EFFDET_OK) return rc;
+  if (wa.path != WG_SPLIT || wb.path != WG_SPLIT) return EFFDET_EUNSUPPORTED;
+  const WgradK &ka = wa.k, &kb = wb.k;
+  if (ka.Cin != kb.Cin || ka.Cout != kb.Cout || a->KH != b->KH || a->KW != b->KW || ka.stride != kb.stride || ka.pad_t != kb.pad_t ||
+      ka.pad_l != kb.pad_l || ka.ldx != kb.ldx || ka.lddz != kb.lddz || ka.B != kb.B || ka.mchunk != kb.mchunk || wa.allr != wb.allr ||
+      ka.ntiles != kb.ntiles || ka.jtiles != kb.jtiles || ka.K != kb.K || ka.Kc != kb.Kc || ka.cpt != kb.cpt || wa.lds != wb.lds)
+    return EFFDET_EUNSUPPORTED;
+  if (workspace_bytes < wa.workspace_bytes + wb.workspace_bytes) return EFFDET_EINVAL;
+  if (live32_b && ka.mchunk % 32) return EFFDET_EINVAL;       // a split must start on a step of the flag array
+  hipStream_t st = (hipStream_t)stream;
+  WgradPairK q;
+  q.k = ka;
+  const WgradPlan* w[2] = {&wa, &wb};
+  const effdet_wgrad_t* d[2] = {a, b};
+  float* base = (float*)workspace;
+  for (int i = 0; i < 2; ++i) {
+    q.x[i] = w[i]->k.x; q.dz[i] = w[i]->k.dz;
+    q.slab[i] = base;
+    q.dbp[i] = d[i]->dbias ? base + (long long)w[i]->splits * w[i]->slab_floats : nullptr;
+    q.nseg[i] = w[i]->k.nseg; q.splits[i] = w[i]->splits;
+    for (int s = 0; s < EFFDET_MAX_SEG; ++s) q.seg[i][s] = w[i]->k.seg[s];
+    base += w[i]->workspace_bytes / (long long)sizeof(float);
+  }
+  q.live32 = live32_b;
+  // block order (A/B knob, read per call so that tools/pair_wgrad_timing.py can time both): 1 = problem b first, 0 = problem a first;
+  // default: the flagged problem first (see the kernel), a first when both are dense
+  const char* ord = getenv("EFFDET_WGRAD_PAIR_ORDER");
+  q.first = ord ? (atoi(ord) ? 1 : 0) : (live32_b ? 1 : 0);
+  const unsigned grid = (unsigned)(ka.ntiles * ka.jtiles) * (unsigned)(wa.splits + wb.splits);
+  if (live32_b && wa.allr) {
+    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<1, 1>), wa.lds);
+    hipLaunchKernelGGL((conv_wgrad_pair_kernel<1, 1>), dim3(grid), dim3(512), wa.lds, st, q);
+  } else if (live32_b) {
+    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<0, 1>), wa.lds);
+    hipLaunchKernelGGL((conv_wgrad_pair_kernel<0, 1>), dim3(grid), dim3(512), wa.lds, st, q);
+  } else if (wa.allr) {
+    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<1, 0>), wa.lds);
+    hipLaunchKernelGGL((conv_wgrad_pair_kernel<1, 0>), dim3(grid), dim3(512), wa.lds, st, q);
+  } else {
+    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<0, 0>), wa.lds);
+    hipLaunchKernelGGL((conv_wgrad_pair_kernel<0, 0>), dim3(grid), dim3(512), wa.lds, st, q);
+  }
+  EFFDET_CHECK_LAUNCH();
+  rc = reduce_slabs(a, wa, q.slab[0], q.dbp[0], st);
+  return rc != EFFDET_OK ? rc : reduce_slabs(b, wb, q.slab[1], q.dbp[1], st);
 }

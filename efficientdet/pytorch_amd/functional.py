@@ -485,6 +485,11 @@ HEAD_SPARSE_REG = os.environ.get('EFFDET_HEAD_SPARSE_REG', '1') == '1'
 # reach a positive anchor (the same geometry, read forwards); the f16x3 kernels write zeros into the rest.  Losses and gradients are bit
 # for bit the dense ones (include/effdet_needed_tiles.h).
 HEAD_SPARSE_REG_FWD = os.environ.get('EFFDET_HEAD_SPARSE_REG_FWD', '1') == '1'
+# A/B switch: in the paired head backward, the weight gradients of layer t of BOTH towers as one launch (ops.conv2d_wgrad_pair).  The
+# regression tower's flagged launch lasts as long as its few almost entirely live ranges, which are dispatched last; in one grid with the
+# classification tower's dense launch they start first and the dense blocks fill the slots behind them.  Same plans, same slabs: bit for
+# bit the separate launches.  Off: one launch per (tower, layer).
+HEAD_PAIR_WGRAD = os.environ.get('EFFDET_HEAD_PAIR_WGRAD', '1') == '1'
 _split_ok = {}
 
 
@@ -695,6 +700,16 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
         dw = torch.empty_like(w); db = ops.unpack_wgrad(G, dw, dbias_part=dbp)
         g[f'{tower}_convs.{t}.weight'], g[f'{tower}_convs.{t}.bias'] = dw, db
 
+    def layer_wgrad_pair(t, dz_cls, dz_reg):
+        """layer t of both towers: the dense classification problem and the (flagged) regression problem in one launch"""
+        ws = [HP[f'{tw}_convs.{t}.weight'] for tw in ('cls', 'reg')]
+        xin = [acts[tw][t - 1] if t > 0 else p for tw in ('cls', 'reg')]
+        res = ops.conv2d_wgrad_pair(xin[0], dz_cls, xin[1], dz_reg, Cin=ws[0].shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1,
+                                    live32_b=lv('reg', 0, 4 - t))
+        for tw, w, (G, dbp) in reversed(list(zip(('cls', 'reg'), ws, res))):      # (unpack jobs in the order of the separate launches)
+            dw = torch.empty_like(w); db = ops.unpack_wgrad(G, dw, dbias_part=dbp)
+            g[f'{tw}_convs.{t}.weight'], g[f'{tw}_convs.{t}.bias'] = dw, db
+
     def tower_bwd(tower, dout, per, pix_ld):
         dz = tower_final(tower, dout, per, pix_ld)
         for t in range(3, -1, -1):
@@ -709,13 +724,16 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
                 last[tower] = (dz, wd)                  # 256 -> Wc back to the neck: after the join (the towers' sum)
 
     if paired:
-        # both towers in lockstep: the weight gradients stay one launch per (tower, layer), the 256 -> 256 data gradients of layer t run
-        # as ONE launch for both towers (head_fwd's pairing, same reason: 10.66 rounds of tiles instead of twice 5.33)
+        # both towers in lockstep: the weight gradients of layer t run as ONE launch for both towers (HEAD_PAIR_WGRAD; off: one per tower)
+        # and so do the 256 -> 256 data gradients (head_fwd's pairing, same reason: 10.66 rounds of tiles instead of twice 5.33)
         dzs = {'reg': tower_final('reg', dreg, 4, dreg_ld), 'cls': tower_final('cls', dcls_logit, nc, dcls_ld)}
         L5 = len(sizes)
         for t in range(3, -1, -1):
-            for tw in ('reg', 'cls'):
-                layer_wgrad(tw, t, dzs[tw])
+            if HEAD_PAIR_WGRAD:
+                layer_wgrad_pair(t, dzs['cls'], dzs['reg'])
+            else:
+                for tw in ('reg', 'cls'):
+                    layer_wgrad(tw, t, dzs[tw])
             wd2 = [ops.pack_weight(HP[f'{tw}_convs.{t}.weight'], dtype, mode=1, x3=split) for tw in ('cls', 'reg')]
             if t > 0:
                 _, na, nb = pyramid_alloc_pair(B, sizes, 256, dtype, dev)

@@ -626,6 +626,42 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     return slabs, parts
 
 
+def conv2d_wgrad_pair(xs_a, dzs_a, xs_b, dzs_b, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, live32_b=None):
+    """conv2d_wgrad(xs_a, dzs_a, split=True) and conv2d_wgrad(xs_b, dzs_b, split=True, live32=live32_b) as ONE launch
+    (effdet_conv2d_wgrad_pair: two split-layout problems of one geometry, e.g. the same layer of the RetinaHead's two towers)
+    -> ((slabs_a, parts_a), (slabs_b, parts_b)), views of one workspace, bit for bit what the two separate launches leave.
+    live32_b: problem b's step flags (see conv2d_wgrad) or None for two dense problems; problem a is always dense."""
+    if isinstance(xs_a, Map):
+        xs_a, dzs_a = [xs_a], [dzs_a]
+    if isinstance(xs_b, Map):
+        xs_b, dzs_b = [xs_b], [dzs_b]
+    lib_ = L.require('effdet_conv2d_wgrad_pair')
+    ds = [_wgrad_desc(xs, dzs, None, None, Cin, Cout, KH, KW, stride, pad_t, pad_l, want_bias, True, False)
+          for xs, dzs in ((xs_a, dzs_a), (xs_b, dzs_b))]
+    splits = [int(lib_.effdet_conv2d_wgrad_splits(C.byref(d))) for d in ds]
+    if min(splits) < 1:
+        raise RuntimeError('effdet_conv2d_wgrad_pair: unsupported geometry')
+    n = Cout * KH * KW * Cin
+    ws = torch.empty(sum(splits) * (n + Cout), dtype=torch.float32, device=xs_a[0].t.device)
+    nbytes = ws.numel() * 4
+    if live32_b is not None:
+        assert live32_b.dtype == torch.uint8 and live32_b.is_contiguous()
+        assert live32_b.numel() == sum((z.B * z.H * z.W + 31) // 32 for z in dzs_b)
+    run = lambda: L.check(lib_.effdet_conv2d_wgrad_pair(C.byref(ds[0]), C.byref(ds[1]), L.ptr(ws), nbytes, L.ptr(live32_b), L.stream_ptr()),
+                          'effdet_conv2d_wgrad_pair')
+    # (flops stay those of the two dense launches: a flagged half reports an EFFECTIVE rate)
+    pix = sum(z.B * z.H * z.W for z in dzs_a) + sum(z.B * z.H * z.W for z in dzs_b)
+    _timed('conv_wgrad_split_kernel', 2.0 * KH * KW * Cin * Cout * pix, run, 'pair k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, pix),
+           nbytes=float(xs_a[0].t.element_size() * Cin * (sum(x.B * x.H * x.W for x in xs_a) + sum(x.B * x.H * x.W for x in xs_b)) +
+                        dzs_a[0].t.element_size() * Cout * pix + 4.0 * sum(splits) * (n + Cout)))
+    out, o = [], 0
+    for sp in splits:
+        slabs = ws[o:o + sp * n].view(sp, Cout, KH * KW, Cin)
+        parts = ws[o + sp * n:o + sp * (n + Cout)].view(sp, Cout) if want_bias else None
+        out.append((slabs, parts)); o += sp * (n + Cout)
+    return tuple(out)
+
+
 class _TailBatch:
     """Deferred leaf work of one backward node (effdet_backward_tail): inside ``with unpack_batch():`` unpack_wgrad /
     unpack_wgrad_bn / dw_unpack_wgrad_bn / the parameter-gradient half of se_gate_bwd only record a job (outputs are allocated
