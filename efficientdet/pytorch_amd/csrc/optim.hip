@@ -24,8 +24,16 @@
 // opt_norm_final_kernel (one workgroup) from the counter `updates` of effdet_ema_ctl_t, stored next to the norm (scratch[1]) and read
 // from there by the update kernel's workgroups; the same thread then advances `updates`: it is the word's only reader and only writer,
 // so no launch is added.  ema_swap_kernel exchanges p and e in place over the same block table (evaluation with the averaged weights).
+//
+// Parameter groups and a second update rule (include/effdet_opt_groups.h; the GROUPED instantiations of the update kernel): the step
+// already works per tensor, so a group is tensor_group[ti], an index into a DEVICE table of 8-float rows, read once per workgroup in
+// place of the one hyper buffer.  The norm pass reads no per-group value (one global norm, one EMA counter; max_norm and ema_decay are
+// optimizer-wide and sit at the legacy offsets 0 and 6 of row 0), so opt_norm_kernel / opt_norm_final_kernel serve both forms as they
+// are and only the update kernel has a grouped form.  RULE_SGD is torch.optim.SGD's update (sgd1) over the same tables with ONE moment
+// arena; like ema1 it is separately rounded fp32 with contraction off, so a NumPy restatement is bit-exact.
 #include "common.h"
 #include "../../../include/effdet_ema.h"
+#include "../../../include/effdet_opt_groups.h"
 
 namespace {
 
@@ -46,6 +54,13 @@ struct OptK {
   // null; hyper[6] otherwise) and the warm-up switch.  om lives in norm[1].
   const unsigned long long* e; effdet_ema_ctl_t* ectl; float ema_decay; int ema_warmup;
 };
+
+// GROUPED instantiations only (a struct of its own: OptK, the kernel argument of the one-group instantiations, stays as it is)
+struct OptG : OptK {
+  const int* tensor_group;   // int32[ntensors]: row of `table` for tensor ti
+  const float* table;        // ngroups rows of EFFDET_OPT_ROW floats (effdet_opt_groups.h); k.hyper aliases it (row 0) for the norm pass
+};
+constexpr int RULE_ADAMW = EFFDET_OPT_RULE_ADAMW, RULE_SGD = EFFDET_OPT_RULE_SGD;
 
 static_assert(sizeof(effdet_train_ctl_t) == 32, "effdet_train_ctl_t is read back as 32 bytes by the binding");
 static_assert(sizeof(effdet_ema_ctl_t) == 16, "effdet_ema_ctl_t is read back as 16 bytes by the binding");
@@ -149,6 +164,25 @@ __device__ __forceinline__ void adamw1(float& p, float& m, float& v, float g, co
   p -= step_size * m / (sqrtf(v) / bc2_sqrt + k.eps);
 }
 
+// torch.optim.SGD, one element (effdet_opt_groups.h): every operation a separately rounded fp32 one, never an FMA (see ema1).  The row
+// is read through Hyper's names: beta1 = momentum, beta2 = 1 - dampening, eps = the nesterov flag.  `first`: this is the tensor's first
+// step, the buffer starts as a copy of d.  The branches are uniform over the workgroup.
+__device__ __forceinline__ void sgd1(float& p, float& buf, float& g, float coef, const Hyper& k, bool first) {
+#pragma clang fp contract(off)
+  g = g * coef;                                              // (in here: the product may not fuse into d's sum either)
+  float d = g;
+  if (k.wd != 0.f) { const float w = k.wd * p; d = g + w; }
+  float u = d;
+  if (k.beta1 != 0.f) {
+    if (first) buf = d;
+    else { const float a = k.beta1 * buf; const float b = k.beta2 * d; buf = a + b; }
+    if (k.eps != 0.f) { const float a = k.beta1 * buf; u = d + a; }
+    else u = buf;
+  }
+  const float s = k.lr * u;
+  p = p - s;
+}
+
 // a tensor without a gradient in this step: AdamW leaves it alone, its average still follows the unchanged p
 __device__ __forceinline__ void ema_only_chunk(const OptK& kk, int ti, float om) {
   const float* p = (const float*)kk.p[ti]; float* e = (float*)kk.e[ti];
@@ -172,20 +206,97 @@ __device__ __forceinline__ void ema_only_chunk(const OptK& kk, int ti, float om)
   }
 }
 
-template <bool GATED, bool EMA> __global__ __launch_bounds__(256) void opt_adamw_kernel(const OptK kk) {
+template <bool GROUPED> struct OptArg { using type = OptK; };
+template <> struct OptArg<true> { using type = OptG; };
+
+// the one set of hypers, read where the one-group kernel has always read it, or (GROUPED) the row of the workgroup's tensor
+__device__ __forceinline__ Hyper hyper_one(const OptK& k) { return hyper_of(k); }
+__device__ __forceinline__ Hyper hyper_one(const OptG&) { return Hyper{}; }
+__device__ __forceinline__ Hyper hyper_row(const OptK&, int, const Hyper& one) { return one; }
+__device__ __forceinline__ Hyper hyper_row(const OptG& k, int ti, const Hyper&) {
+  const float* r = k.table + (long long)k.tensor_group[ti] * EFFDET_OPT_ROW;
+  return Hyper{r[0], r[1], r[2], r[3], r[4], r[5]};
+}
+
+// clip_grad_norm_: min(1, max_norm / (norm + 1e-6)) with torch.clamp's NaN rule -- a NaN norm turns every gradient into NaN
+__device__ __forceinline__ float clip_coef(const Hyper& k, float norm) {
+  return k.max_norm > 0.f ? nan_min(1.0f, k.max_norm / (norm + 1e-6f)) : 1.0f;
+}
+
+// RULE_SGD over one chunk: g twice with clipping (norm pass + here), p and the momentum buffer read and written once; a group with
+// momentum 0 never touches the buffer
+template <bool EMA>
+__device__ __forceinline__ void sgd_chunk(const OptK& kk, const Hyper& k, int ti, float* g, float coef, float om) {
+  float* p = (float*)kk.p[ti]; float* b = (float*)kk.m[ti];
+  float* ea = EMA ? (float*)kk.e[ti] : nullptr;
+  const bool mom = k.beta1 != 0.f, first = kk.steps[ti] == 1;              // (already advanced by opt_norm_final_kernel)
+  const long long n = kk.n[ti], off = (long long)(blockIdx.x - kk.block_first[ti]) * OPT_CHUNK;
+  const long long end = off + OPT_CHUNK < n ? off + OPT_CHUNK : n;
+  const bool alg = (((unsigned long long)(g + off)) & 15ull) == 0;
+  const bool alp = ((((unsigned long long)(p + off)) | ((unsigned long long)(b + off))) & 15ull) == 0;
+  const bool ale = EMA && (((unsigned long long)(ea + off)) & 15ull) == 0;
+  for (long long i = off + threadIdx.x * 4; i < end; i += 1024) {
+    if (i + 3 < end) {
+      f32x4 gv = load4_any(g + i, alg), pv = load4_any(p + i, alp), bv{}, ev{};
+      if (mom && !first) bv = load4_any(b + i, alp);
+      if (EMA) ev = load4_any(ea + i, ale);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pv[e], be = bv[e];
+        float ge = gv[e];
+        sgd1(pe, be, ge, coef, k, first);
+        pv[e] = pe; bv[e] = be; gv[e] = ge;
+        if (EMA) ev[e] = ema1(ev[e], pe, om);
+      }
+      if (alp) { *(f32x4*)(p + i) = pv; if (mom) *(f32x4*)(b + i) = bv; }
+      else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { p[i + e] = pv[e]; if (mom) b[i + e] = bv[e]; }
+      }
+      if (EMA) {
+        if (ale) *(f32x4*)(ea + i) = ev;
+        else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ea[i + e] = ev[e];
+        }
+      }
+      if (kk.write_grad) {
+        if (alg) *(f32x4*)(g + i) = gv;
+        else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) g[i + e] = gv[e];
+        }
+      }
+    } else {
+      for (long long j = i; j < end; ++j) {
+        float pe = p[j], be = mom && !first ? b[j] : 0.f;
+        float gj = g[j];
+        sgd1(pe, be, gj, coef, k, first);
+        p[j] = pe;
+        if (mom) b[j] = be;
+        if (EMA) ea[j] = ema1(ea[j], pe, om);
+        if (kk.write_grad) g[j] = gj;
+      }
+    }
+  }
+}
+
+template <bool GATED, bool EMA, bool GROUPED = false, int RULE = RULE_ADAMW>
+__global__ __launch_bounds__(256) void opt_adamw_kernel(const typename OptArg<GROUPED>::type kk) {
   if (GATED && !gate_open(kk.ctl)) return;
-  const Hyper k = hyper_of(kk);
+  const Hyper one = hyper_one(kk);
   const int ti = kk.block_tensor[blockIdx.x];
+  const Hyper k = hyper_row(kk, ti, one);
   float* g = (float*)(GATED && !kk.has[ti] ? 0ull : kk.g[ti]);
   const float om = EMA ? kk.norm[1] : 0.f;                   // written by opt_norm_final_kernel of this step
   if (!g) {
     if (EMA) ema_only_chunk(kk, ti, om);
     return;
   }
+  if (RULE == RULE_SGD) { sgd_chunk<EMA>(kk, k, ti, g, clip_coef(k, kk.norm[0]), om); return; }     // (before kk.v is read: SGD has no second arena)
   float* p = (float*)kk.p[ti]; float* m = (float*)kk.m[ti]; float* v = (float*)kk.v[ti];
   float* ea = EMA ? (float*)kk.e[ti] : nullptr;
-  // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)) with torch.clamp's NaN rule -- a NaN norm turns every gradient into NaN
-  const float coef = k.max_norm > 0.f ? nan_min(1.0f, k.max_norm / (kk.norm[0] + 1e-6f)) : 1.0f;
+  const float coef = clip_coef(k, kk.norm[0]);
   const float t = (float)kk.steps[ti];                       // already advanced by opt_norm_final_kernel
   const float step_size = k.lr / (1.0f - powf(k.beta1, t)), bc2_sqrt = sqrtf(1.0f - powf(k.beta2, t));
   const long long n = kk.n[ti], off = (long long)(blockIdx.x - kk.block_first[ti]) * OPT_CHUNK;
@@ -431,6 +542,67 @@ extern "C" int effdet_ema_swap(const unsigned long long* params, const unsigned 
   hipLaunchKernelGGL(ema_swap_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, params, ema, numel, block_tensor, block_first);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
+}
+
+// ---- include/effdet_opt_groups.h: parameter groups (a hyper table indexed per tensor) and the SGD rule, all four forms ----
+namespace {
+
+// the norm pass is the one-group form's (it reads the OptK part only: max_norm / ema_decay of row 0 through k.hyper); the update is the
+// GROUPED instantiation of the rule
+template <bool GATED, bool EMA, int RULE> int launch_step_groups(const OptG& k, float max_norm, hipStream_t st) {
+  const OptK& k1 = k;
+  if (max_norm > 0.f) {
+    hipLaunchKernelGGL(opt_norm_kernel<GATED>, dim3(k.nblocks), dim3(256), 0, st, k1);
+    EFFDET_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((opt_norm_final_kernel<GATED, EMA>), dim3(1), dim3(1024), 0, st, (const float*)k.partial, max_norm > 0.f ? k.nblocks : 0,
+                     k.norm, GATED ? k.has : k.g, k.steps, k.ntensors, k.ctl, EmaStep{k.ectl, k.hyper, k.ema_decay, k.ema_warmup});
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL((opt_adamw_kernel<GATED, EMA, true, RULE>), dim3(k.nblocks), dim3(256), 0, st, k);
+  EFFDET_CHECK_LAUNCH();
+  if (GATED) {
+    hipLaunchKernelGGL(train_release_kernel, dim3(1), dim3(1), 0, st, const_cast<effdet_train_ctl_t*>(k.ctl));
+    EFFDET_CHECK_LAUNCH();
+  }
+  return EFFDET_OK;
+}
+
+template <int RULE> int launch_step_groups_form(const OptG& k, int flags, float max_norm, hipStream_t st) {
+  switch (flags) {
+    case 0: return launch_step_groups<false, false, RULE>(k, max_norm, st);
+    case EFFDET_OPT_EMA: return launch_step_groups<false, true, RULE>(k, max_norm, st);
+    case EFFDET_OPT_GATED: return launch_step_groups<true, false, RULE>(k, max_norm, st);
+    default: return launch_step_groups<true, true, RULE>(k, max_norm, st);
+  }
+}
+
+}  // namespace
+
+extern "C" int effdet_opt_step_groups(int rule, int flags, const unsigned long long* params, const unsigned long long* grads,
+                                      const unsigned long long* acc, const unsigned long long* moment1, const unsigned long long* moment2,
+                                      const unsigned long long* ema, const long long* numel, const int* block_tensor,
+                                      const int* block_first, const int* tensor_group, int ntensors, int nblocks, int ngroups,
+                                      float* scratch, int* steps, const float* hyper_table, float max_norm, int write_grad,
+                                      int ema_warmup, effdet_train_ctl_t* ctl, effdet_ema_ctl_t* ema_ctl, effdet_stream_t stream) {
+  if (rule != EFFDET_OPT_RULE_ADAMW && rule != EFFDET_OPT_RULE_SGD) return EFFDET_EINVAL;
+  if (flags & ~(EFFDET_OPT_GATED | EFFDET_OPT_EMA)) return EFFDET_EINVAL;
+  const bool gated = flags & EFFDET_OPT_GATED, avg = flags & EFFDET_OPT_EMA;
+  if (!params || !grads || !moment1 || !numel || !block_tensor || !block_first || !tensor_group || !scratch || !steps || !hyper_table ||
+      nblocks < 1 || ntensors < 1 || ngroups < 1)
+    return EFFDET_EINVAL;
+  if ((rule == EFFDET_OPT_RULE_ADAMW) != (moment2 != nullptr)) return EFFDET_EINVAL;      // two arenas for AdamW, one for SGD
+  if (gated != (acc != nullptr) || gated != (ctl != nullptr) || avg != (ema != nullptr) || avg != (ema_ctl != nullptr)) return EFFDET_EINVAL;
+  if (gated && write_grad) return EFFDET_EINVAL;
+  OptG k{};
+  k.p = params; k.m = moment1; k.v = moment2; k.n = numel; k.block_tensor = block_tensor; k.block_first = block_first;
+  if (gated) { k.g = acc; k.has = grads; k.ctl = ctl; } else k.g = grads;
+  k.norm = scratch; k.partial = scratch + 64;                       // scratch: 64 + nblocks floats
+  k.steps = steps; k.nblocks = nblocks; k.ntensors = ntensors; k.write_grad = write_grad;
+  k.hyper = hyper_table; k.table = hyper_table; k.tensor_group = tensor_group;
+  k.e = ema; k.ectl = ema_ctl; k.ema_warmup = ema_warmup;
+  hipStream_t st = (hipStream_t)stream;
+  if (rule == EFFDET_OPT_RULE_SGD) return launch_step_groups_form<RULE_SGD>(k, flags, max_norm, st);
+  return launch_step_groups_form<RULE_ADAMW>(k, flags, max_norm, st);
 }
 
 extern "C" int effdet_opt_chunk(void) { return OPT_CHUNK; }

@@ -148,8 +148,8 @@ class GraphedTrainLoop:
             raise NotImplementedError('GraphedTrainLoop: %s is not supported -- a rank whose loss is 0 would skip collectives the other '
                                       'ranks wait for (the reference has the same hazard); use GraphedTrainStep' % type(model).__name__)
         if not getattr(optimizer, 'accumulate', False):
-            raise RuntimeError('GraphedTrainLoop needs optim.ClipAdamW(accumulate=True): the skip gate, the accumulation arena and the '
-                               'loss meter live in the optimizer')
+            raise RuntimeError('GraphedTrainLoop needs optim.ClipAdamW(accumulate=True) or optim.ClipSGD(accumulate=True): the skip gate, '
+                               'the accumulation arena and the loss meter live in the optimizer')
         if int(accumulation_steps) < 1:
             raise ValueError('accumulation_steps must be >= 1')
         if not images.is_cuda:
@@ -208,8 +208,9 @@ class GraphedTrainLoop:
 
 
 def replay_vs_eager(graphed, eager_step=None):
-    """Is a replay of `graphed` (a GraphedTrainStep over optim.ClipAdamW) the eager step?  From ONE saved state -- parameters, Adam
-    moments + per-tensor step counters, the drop_connect counter, all restored IN PLACE so the graph's pointers stay valid -- run the eager
+    """Is a replay of `graphed` (a GraphedTrainStep over optim.ClipAdamW or optim.ClipSGD) the eager step?  From ONE saved state --
+    parameters, the optimizer's moment arenas (whichever it has: two for AdamW, one for SGD) + per-tensor step counters, the drop_connect
+    counter, all restored IN PLACE so the graph's pointers stay valid -- run the eager
     step (default: graphed._step on the capture stream) and the replay, each twice, on the graph's static batch, and compare the
     parameters they produce.  The path has no float atomics, so eager == eager and replay == replay bit for bit (which also proves the
     restore complete), and replay vs eager differs at most by what a collective's summation order may change under DDP.
@@ -224,8 +225,9 @@ def replay_vs_eager(graphed, eager_step=None):
     model = graphed.model
     while isinstance(model, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)):
         model = model.module
-    if not hasattr(opt, 'exp_avg') or getattr(opt, '_table', None) is None:
-        raise RuntimeError('replay_vs_eager needs optim.ClipAdamW (its state lives in arenas that can be restored in place)')
+    if not hasattr(opt, 'moment_arenas') or getattr(opt, '_table', None) is None:
+        raise RuntimeError('replay_vs_eager needs optim.ClipAdamW or optim.ClipSGD after a step (their state lives in arenas that can be '
+                           'restored in place)')
     ps = [p for p in opt._table['params']]
     t = opt._table
     dc = [v for k, v in getattr(model, '_dc', {}).items() if isinstance(k, tuple) and k[0] == 'step_dev']
@@ -233,7 +235,7 @@ def replay_vs_eager(graphed, eager_step=None):
     def flat():
         return torch.cat([p.detach().reshape(-1).float() for p in ps]).clone()
     torch.cuda.synchronize()
-    p0, m0, v0, s0 = flat(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), t['steps'].clone()
+    p0, a0, s0 = flat(), [a.clone() for a in opt.moment_arenas()], t['steps'].clone()
     dc0 = [d.clone() for d in dc]
     ema = bool(getattr(opt, 'ema', False))
     if ema:
@@ -245,7 +247,9 @@ def replay_vs_eager(graphed, eager_step=None):
             o = 0
             for p in ps:
                 n = p.numel(); p.copy_(p0[o:o + n].view_as(p)); o += n
-            opt.exp_avg.copy_(m0); opt.exp_avg_sq.copy_(v0); t['steps'].copy_(s0)
+            for a, saved in zip(opt.moment_arenas(), a0):
+                a.copy_(saved)
+            t['steps'].copy_(s0)
             if ema:
                 opt.ema_avg.copy_(e0); t['ectl'].copy_(u0)
             for d, d0 in zip(dc, dc0):
