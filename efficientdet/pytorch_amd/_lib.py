@@ -1,6 +1,6 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h,
-include/effdet_opt_groups.h).
+include/effdet_opt_groups.h, include/effdet_gate_operand.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -326,6 +326,15 @@ WGRAD_PAIR_SIGNATURES = {
 OPT_GROUPS_SIGNATURES = {
     'effdet_opt_step_groups': 'i:iippppppppppiiipppfiipps',
 }
+# The squeeze-excite gate applied in the project conv's operand registers (forward and per-image weight gradient), declared in
+# include/effdet_gate_operand.h (same generation, same letters, same rule; tests/test_gate_operand_host.py compares this table with that
+# header's prototypes).
+GATE_OPERAND_SIGNATURES = {
+    'effdet_conv2d_gated': 'i:ppis',
+    'effdet_conv2d_gated_plan_info': 'i:ppip',
+    'effdet_conv2d_wgrad_gated': 'i:ppipqs',
+    'effdet_conv2d_wgrad_gated_kernel': 'i:ppi',
+}
 OPT_ROW, OPT_RULE_ADAMW, OPT_RULE_SGD, OPT_GATED, OPT_EMA = 8, 0, 1, 1, 2      # EFFDET_OPT_* of that header
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
@@ -352,7 +361,7 @@ def lib():
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
                 list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
-                list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()):
+                list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -27,6 +27,7 @@
 #include "../../../include/effdet_live_tiles.h"
 #include "../../../include/effdet_needed_tiles.h"
 #include "../../../include/effdet_conv_plan.h"
+#include "../../../include/effdet_gate_operand.h"
 #include <stdlib.h>
 
 #ifndef EFFDET_IGEMM_BIG_DEFAULT
@@ -63,6 +64,7 @@ struct ConvK {
   int live_tile0;              // pixel tiles below it carry no flag and are live
   const unsigned char* needed; // SPLIT == 3 only, may be NULL: needed[mt - needed_tile0] == 0 = nobody reads pixel tile mt's result (effdet_conv2d_needed)
   int needed_tile0;            // pixel tiles below it carry no flag and are computed
+  const float* a_gate;         // GATE != 0 only (effdet_conv2d_gated): [B][Cin] fp32, the activation operand is act(x) * a_gate[image][channel]
   SegD seg[EFFDET_MAX_CONV_SEG];
 };
 
@@ -121,7 +123,11 @@ template <> struct Mma<float> {
 // algorithmic) -- the ceiling a bare loop of that instruction showed (1195-1335, tools/probe/mfma_peak.hip) -- so the faster-issuing
 // shape was the obvious try: it measured 342-360 against 370-390 (same LDS fragment bytes per MAC, longer dependent chains per
 // accumulator): the loop is bound by LDS port + latency hiding at this tile size, not by MFMA issue.
-template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0>
+// GATE (exact fp32, SPLIT == 0, 1x1 stride 1, whole tiles per image; effdet_conv2d_gated): the activation operand is formed in registers,
+// between the fragment's ds_read and its MFMAs, as x * a_gate[image][channel] (GATE = 1) or swish(x) * a_gate[image][channel] (GATE = 2) --
+// the two statements of se.hip's channel_scale_kernel, so every MFMA receives bit for bit the operand it would read from that kernel's
+// output, in the same order.  The image's gate row sits in LDS behind the operand tiles (zeros past Cin: the K padding stays +0).
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0, int GATE = 0>
 // (second launch bound = waves per SIMD asked of the register allocator: the 4-wave split-layout forms fit three workgroups per CU by LDS, but
 //  left to itself hipcc spends 110 VGPRs + 72 AGPRs on the f16x3 one -- two waves per SIMD)
 __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) void conv_igemm_kernel(const ConvK p) {
@@ -129,6 +135,7 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   static_assert(!M32 || SPLIT == 2, "the 32x32x16 form is built for the split layout");
   static_assert(SPLIT != 3 || NS == 2, "f16x3: two stages");
   static_assert(NS == 2 || !M32, "deep staging is not built for the 32x32 tile loop");
+  static_assert(!GATE || (SPLIT == 0 && sizeof(T) == 4), "the operand gate is built for the exact-fp32 form");
   constexpr int CE = Elem<T>::CE;
   constexpr int NTHREADS = NWAVES * 64;
   constexpr int WAVES_M = NWAVES / WAVES_N;
@@ -336,6 +343,12 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   //              gave +23 %, removing the DMA alone +36 %).
   const int nk = (p.Kc + 7) >> 3;
   const int l15 = lane & 15, lq = lane >> 4, lsw = l15 >> 1;  // swizzle term (row>>1)&7 for row%16 = l15
+  float* const gl = (float*)(smem + NS * (XLD + WLD));        // GATE: the image's gate row, [nk * 32] floats (visible after the first barrier below)
+  if constexpr (GATE) {
+    // (a tile never straddles images: Ho*Wo % BM == 0, checked by the host; 1x1: the K index is the channel; never read past Cin)
+    const float* grow = p.a_gate + (long long)(m_base / HoWo) * p.Cin;
+    for (int i = tid; i < nk * 32; i += NTHREADS) gl[i] = i < p.Cin ? grow[i] : 0.f;
+  }
   auto load = [&](int buf, int s, uint4 (&wf)[NT], uint4 (&xf)[MT]) {
     const int ch = ((s * 4 + lq) ^ lsw);
 #pragma unroll
@@ -501,25 +514,50 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
     }
   } else {
     uint4 wfA[NT], xfA[MT], wfB[NT], xfB[MT];
+    // GATE: the four floats of an X fragment are channels 4 * (8 kt + 4 s + lq) .. + 3 (the UNswizzled chunk index); their gate values
+    // are read with the fragment, applied after the MFMAs of the fragment before have been issued (VALU under the matrix pipe)
+    f32x4 gA = f32x4{0.f, 0.f, 0.f, 0.f}, gB = gA;
+    auto loadg = [&](int kt, int s) -> f32x4 { return *(const f32x4*)(gl + ((kt * 8 + s * 4 + lq) << 2)); };
+    auto gatex = [&](uint4 (&xf)[MT], const f32x4& g) {
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int b = 0; b < MT; ++b) {
+        float v[4] = {__uint_as_float(xf[b].x), __uint_as_float(xf[b].y), __uint_as_float(xf[b].z), __uint_as_float(xf[b].w)};
+        if constexpr (GATE == 2) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = swishf_(v[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] *= g[e];
+        xf[b] = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+      }
+    };
     int issued = 0;
     for (; issued < NS && issued < nk; ++issued) stage(issued);
     wait_tile(issued - 1);
     __syncthreads();
     load(0, 0, wfA, xfA);
+    if constexpr (GATE) { gA = loadg(0, 0); gatex(xfA, gA); }
     for (int kt = 0; kt + 1 < nk; ++kt) {  // (last K-step peeled: a conditional barrier block would make hipcc merge the
       const int cur = kt % NS, nxt = (kt + 1) % NS;    //  LDS counters of both paths and wait for the A fragments before the B MFMAs)
       load(cur, 1, wfB, xfB);
+      if constexpr (GATE) gB = loadg(kt, 1);
       __builtin_amdgcn_sched_barrier(0);   // keep the LDS reads AHEAD of the MFMAs they hide under (hipcc sinks them otherwise)
       mma(wfA, xfA);
+      if constexpr (GATE) gatex(xfB, gB);
       wait_tile(issued - (kt + 2));        // this wave's pieces of tile kt+1 have landed ...
       __syncthreads();                     // ... and everyone's; every wave holds its last fragments of tile kt in registers
       if (issued < nk) { stage(cur); ++issued; }   // tile kt+NS refills the buffer just drained (asm DMA: no compiler-inserted drain)
       load(nxt, 0, wfA, xfA);
+      if constexpr (GATE) gA = loadg(kt + 1, 0);
       __builtin_amdgcn_sched_barrier(0);
       mma(wfB, xfB);
+      if constexpr (GATE) gatex(xfA, gA);
     }
     load((nk - 1) % NS, 1, wfB, xfB);
+    if constexpr (GATE) gB = loadg(nk - 1, 1);
     mma(wfA, xfA);
+    if constexpr (GATE) gatex(xfB, gB);
     mma(wfB, xfB);
   }
 
@@ -1257,21 +1295,24 @@ struct ConvPlan {
   int form, pers;              // EFFDET_CONV_FORM_*; 1 = conv_igemm_pers_kernel
   int tile_m, tile_n, stages, threads, m32;      // workgroup tile (pixels x channels), LDS stages of the K loop, threads per workgroup, 32x32x16 tiles
   int ksteps;                  // trips of the K loop
+  int gate;                    // the kernel's GATE parameter: 0, or the operand-gate form (1 multiply, 2 Swish + multiply)
 };
 
-template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT, int NS, int M32>
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT, int NS, int M32, int GATE>
 int launch_igemm(const ConvPlan& c, hipStream_t st) {
-  if (c.lds > 48 * 1024) EFFDET_SET_MAX_LDS((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>), c.lds);
-  hipLaunchKernelGGL((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>), dim3(c.grid), dim3(NWAVES * 64), c.lds, st, c.k);
+  if (c.lds > 48 * 1024) EFFDET_SET_MAX_LDS((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>), c.lds);
+  hipLaunchKernelGGL((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>), dim3(c.grid), dim3(NWAVES * 64), c.lds, st, c.k);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
-template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0>
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0, int GATE = 0>
 int use_igemm(ConvPlan& c, int id) {
   c.k.ntiles = (c.k.Cout + BN - 1) / BN;
   c.grid = (unsigned)(c.k.mtiles * c.k.ntiles);
   c.lds = (size_t)NS * (BM + BN) * 8 * sizeof(uint4);                    // NS-stage operand tiles
-  c.launch = launch_igemm<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32>;
+  if (GATE) c.lds += (size_t)((c.k.Kc + 7) >> 3) * 32 * sizeof(float);   // + the image's gate row, one float per K slot
+  c.gate = GATE;
+  c.launch = launch_igemm<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>;
   static_assert(EFFDET_CONV_FORM_PLAIN == 0 && EFFDET_CONV_FORM_BF16X3 == 1 && EFFDET_CONV_FORM_SPLIT == 2 && EFFDET_CONV_FORM_HSPLIT == 3,
                 "the kernel's SPLIT parameter is the public form code");
   c.form = SPLIT; c.pers = 0; c.tile_m = BM; c.tile_n = BN; c.stages = NS; c.threads = NWAVES * 64; c.m32 = M32;
@@ -1346,7 +1387,7 @@ static int big_variant() {
 }
 
 // Block tile (bt = 0..3: 128 / 64 / 32 / 16 channels) and staging depth of the 128-pixel-tile kernel: ids 0..3, 4..7 with SPLIT = 1
-template <typename T, int SPLIT>
+template <typename T, int SPLIT, int GATE = 0>
 int use_tile(ConvPlan& c, int bt) {
   const ConvK& k = c.k;
   const int id = bt + (SPLIT ? 4 : 0), bn = 128 >> bt;
@@ -1363,15 +1404,15 @@ int use_tile(ConvPlan& c, int bt) {
     // 1.78 to 1.05 ms per forward (49.8 -> 84.9 TFLOP/s, 12 launches); configs[4] forward 4.758 -> 4.627 ms/img, D0 train / inference +-0
     static const int narrow = getenv("EFFDET_IGEMM_NARROW") ? atoi(getenv("EFFDET_IGEMM_NARROW")) : 128;
     static const int narrow_k = getenv("EFFDET_IGEMM_NARROW_K") ? atoi(getenv("EFFDET_IGEMM_NARROW_K")) : 16;
-    if (narrow && bt <= 1 && tiles <= narrow && k.Kc >= narrow_k * 8) return use_igemm<T, 32, 1, 4, SPLIT, 4>(c, id);
-    if (bt == 0) return use_igemm<T, 128, 2, 8, SPLIT, 4>(c, id);
-    if (bt == 1) return use_igemm<T, 64, 1, 4, SPLIT, 4>(c, id);
+    if (narrow && bt <= 1 && tiles <= narrow && k.Kc >= narrow_k * 8) return use_igemm<T, 32, 1, 4, SPLIT, 4, 0, GATE>(c, id);
+    if (bt == 0) return use_igemm<T, 128, 2, 8, SPLIT, 4, 0, GATE>(c, id);
+    if (bt == 1) return use_igemm<T, 64, 1, 4, SPLIT, 4, 0, GATE>(c, id);
   }
   switch (bt) {
-    case 0: return use_igemm<T, 128, 2, 8, SPLIT>(c, id);
-    case 1: return use_igemm<T, 64, 1, 4, SPLIT>(c, id);
-    case 2: return use_igemm<T, 32, 1, 4, SPLIT>(c, id);
-    default: return use_igemm<T, 16, 1, 4, SPLIT>(c, id);
+    case 0: return use_igemm<T, 128, 2, 8, SPLIT, 2, 0, GATE>(c, id);
+    case 1: return use_igemm<T, 64, 1, 4, SPLIT, 2, 0, GATE>(c, id);
+    case 2: return use_igemm<T, 32, 1, 4, SPLIT, 2, 0, GATE>(c, id);
+    default: return use_igemm<T, 16, 1, 4, SPLIT, 2, 0, GATE>(c, id);
   }
 }
 
@@ -1386,8 +1427,10 @@ extern "C" int effdet_tuning_set(int key, int value) {
 }
 
 // Validates the descriptor and fills the plan: -> EFFDET_E* (< 0), or the kernel id (the list at effdet_conv2d_kernel in the header).
-static int plan_conv(const effdet_conv_t* p, ConvPlan& c) {
+// a_gate != NULL: the operand-gate form (effdet_conv2d_gated) or EFFDET_EUNSUPPORTED -- never a plain launch on ungated data.
+static int plan_conv(const effdet_conv_t* p, ConvPlan& c, const float* a_gate = nullptr, int a_act = EFFDET_ACT_NONE) {
   ConvK& k = c.k;
+  c.gate = 0;
   if (!p || !p->x || !p->w || !p->y) return EFFDET_EINVAL;
   if (p->nseg < 1 || p->nseg > EFFDET_MAX_CONV_SEG) return EFFDET_EINVAL;
   if (p->dtype != EFFDET_F32 && p->dtype != EFFDET_BF16 && p->dtype != EFFDET_F32_BF16X3 && p->dtype != EFFDET_F32_SPLIT && p->dtype != EFFDET_F32_HSPLIT) return EFFDET_EINVAL;
@@ -1438,6 +1481,14 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c) {
   k.w_img_bytes = p->w_image_stride;
   k.live = nullptr; k.live_tile0 = 0;
   k.needed = nullptr; k.needed_tile0 = 0;
+  k.a_gate = a_gate;
+  if (a_gate) {
+    // operand gate: exact fp32, pointwise (the K index is the channel), one level whose images are whole numbers of 128-pixel tiles
+    // (the image, hence the gate row, is workgroup-uniform), shared weights, the 128-pixel-tile kernels only
+    if (a_act != EFFDET_ACT_NONE && a_act != EFFDET_ACT_SWISH) return EFFDET_EINVAL;
+    if (p->dtype != EFFDET_F32 || p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad_t || p->pad_l || p->nseg != 1 || p->w_image_stride ||
+        p->seg[0].H != p->seg[0].Ho || p->seg[0].W != p->seg[0].Wo || (p->seg[0].Ho * p->seg[0].Wo) % BM || ((size_t)a_gate & 3)) return EFFDET_EUNSUPPORTED;
+  }
   if (p->w_image_stride) {
     // per-image weights: one level whose images are whole numbers of 128-pixel tiles, on the implicit-GEMM kernels only
     if (p->w_image_stride < 0 || (p->w_image_stride & 15) || p->nseg != 1 || splitfmt || (p->seg[0].Ho * p->seg[0].Wo) % BM) return EFFDET_EUNSUPPORTED;
@@ -1499,6 +1550,12 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c) {
       return use_big(c, 10 + ((p->Cout > 128 || v == 423) ? v : (v == 243 ? 4230 : 4220)));
     }
   }
+  if (a_gate) {
+    if (per_seg) return EFFDET_EUNSUPPORTED;
+    k.kord = 0;
+    const int gbt = k.Cout > 64 ? 0 : k.Cout > 32 ? 1 : k.Cout > 16 ? 2 : 3;
+    return a_act == EFFDET_ACT_SWISH ? use_tile<float, 0, 2>(c, gbt) : use_tile<float, 0, 1>(c, gbt);
+  }
   if (!per_seg && !p->w_image_stride && !p->y_split && pw_eligible(p)) return use_pw(c);
   const int bt = k.Cout > 64 ? 0 : k.Cout > 32 ? 1 : k.Cout > 16 ? 2 : 3;
   if (p->dtype == EFFDET_F32_BF16X3) {
@@ -1535,17 +1592,32 @@ extern "C" int effdet_conv2d_kernel(const effdet_conv_t* p) {
 }
 
 // The decision effdet_conv2d launches from, copied out of the same ConvPlan (include/effdet_conv_plan.h): no device work, no HIP runtime call
-extern "C" int effdet_conv2d_plan_info(const effdet_conv_t* p, effdet_conv_plan_info_t* info) {
+static int plan_info(const effdet_conv_t* p, const float* a_gate, int a_act, effdet_conv_plan_info_t* info) {
   ConvPlan c;
-  const int id = plan_conv(p, c);
+  const int id = plan_conv(p, c, a_gate, a_act);
   if (id < 0) return id;
   if (!info) return EFFDET_EINVAL;
   info->id = c.id; info->form = c.form; info->persistent = c.pers;
   info->tile_m = c.tile_m; info->tile_n = c.tile_n; info->stages = c.stages; info->threads = c.threads;
   info->mtiles = c.k.mtiles; info->ntiles = c.k.ntiles; info->grid = (int)c.grid;
   info->ksteps = c.ksteps; info->kord = c.k.kord; info->lds_bytes = (int)c.lds; info->m32 = c.m32;
-  info->reserved[0] = info->reserved[1] = 0;
+  info->reserved[0] = c.gate; info->reserved[1] = 0;       // (reserved[0]: the operand-gate form of the launch, effdet_gate_operand.h)
   return id;
+}
+extern "C" int effdet_conv2d_plan_info(const effdet_conv_t* p, effdet_conv_plan_info_t* info) { return plan_info(p, nullptr, EFFDET_ACT_NONE, info); }
+
+// effdet_conv2d on act(x) * a_gate[image][channel], the product formed in the kernel's operand registers (include/effdet_gate_operand.h)
+extern "C" int effdet_conv2d_gated_plan_info(const effdet_conv_t* p, const float* a_gate, int a_act, effdet_conv_plan_info_t* info) {
+  if (!a_gate) return EFFDET_EINVAL;
+  return plan_info(p, a_gate, a_act, info);
+}
+extern "C" int effdet_conv2d_gated(const effdet_conv_t* p, const float* a_gate, int a_act, effdet_stream_t stream) {
+  if (!a_gate) return EFFDET_EINVAL;
+  ConvPlan c;
+  const int id = plan_conv(p, c, a_gate, a_act);
+  if (id < 0) return id;
+  if (!c.gate) return EFFDET_EUNSUPPORTED;
+  return c.launch(c, (hipStream_t)stream);
 }
 
 extern "C" int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream) {

@@ -22,6 +22,7 @@
 //     operand (blocks of j-tile 0 only); every split stores its partial row [Cout] next to its slab, and the
 //     consumer sums the rows in slab order -- no float atomics anywhere: two runs are bitwise equal.
 #include "common.h"
+#include "../../../include/effdet_gate_operand.h"
 #include "../../../include/effdet_live_tiles.h"
 #include "../../../include/effdet_wgrad_pair.h"
 #include <stdlib.h>
@@ -49,6 +50,8 @@ struct WgradK {
   int mchunk;       // pixels per split (multiple of the K-step)
   int nseg, ntiles, jtiles, vec_a;
   const unsigned char* live32;  // conv_wgrad_split_kernel<., 1> only: live32[step] == 0 = the 32 dz pixels of the step are all zero
+  const float* a_gate;          // GATE != 0 kernels only (effdet_conv2d_wgrad_gated): [B][Cin] fp32, the x operand is act(x) * a_gate[image][channel]
+  int gate_hw;                  // ... pixels per image (image_splits: a split lies in one image, m_begin / gate_hw)
   WSeg seg[EFFDET_MAX_SEG];
 };
 
@@ -773,8 +776,13 @@ __global__ __launch_bounds__(512) void conv_wgrad_pair_kernel(const WgradPairK q
 // v_mfma_f32_16x16x32_bf16: lane (c, k) gathers its 8 stage pixels 4e + k (e = 0..7, the eight reads the fp32 form issues
 // k-step by k-step; the k-slot <-> pixel map is shared by both operands), splits each value into bf16 hi + lo in registers
 // and the tile costs 3 MFMAs per stage (hi*hi + hi*lo + lo*hi) instead of 8 v_mfma_f32_16x16x4_f32.
-template <int NW, int X3 = 0>
-__global__ __launch_bounds__(NW * 64) void conv_wgrad_f32dma_kernel(const WgradK p) {
+// GATE (pointwise, image_splits; effdet_conv2d_wgrad_gated): the x operand is formed in registers at the raw fragment read, as
+// x * a_gate[image][j] (GATE = 1) or swish(x) * a_gate[image][j] (GATE = 2) -- the two statements of se.hip's channel_scale_kernel, so
+// every MFMA (and, X3, every split) receives bit for bit the value it would read from that kernel's output.  A split lies in one image
+// and is whole 32-pixel stages: the lane's JB gate values are loaded once, 0 for the zero-filled j >= K lanes (they keep their +0).
+// (the gated bf16x3 form: 260 VGPRs left to itself, i.e. one workgroup per CU; asked to stay at the plain form's two waves per SIMD)
+template <int NW, int X3 = 0, int GATE = 0>
+__global__ __launch_bounds__(NW * 64, (GATE && X3) ? 2 : 1) void conv_wgrad_f32dma_kernel(const WgradK p) {
   constexpr int WJ = NW / 2;                    // waves along j (2 along n)
   constexpr int WTJ = 128 / WJ, JB = WTJ / 16;  // j per wave (64 | 32), B tiles per wave = floats per lane of the B read (4 | 2)
   constexpr int BKM = 32;                       // pixels per stage
@@ -858,6 +866,20 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_f32dma_kernel(const WgradK
   }
   const bool want_bias = (p.dbp != nullptr) && (jt == 0) && (wj0 == 0);
   float* slab = p.slab + (long long)split * p.Cout * p.K;
+  float gb[JB];
+  if constexpr (GATE) {
+    const float* grow = p.a_gate + (long long)(m_begin / p.gate_hw) * p.K;
+#pragma unroll
+    for (int b = 0; b < JB; ++b) { const int j = jt * 128 + wj0 + JB * c15 + b; gb[b] = j < p.K ? grow[j] : 0.f; }
+  }
+  auto gate1 = [&](float v, int b) -> float {
+    if constexpr (GATE == 2) v = swishf_(v);
+    v *= gb[b];
+    // the ROUNDED product is the operand: without this, hipcc contracts it with the subtraction of split8 (lo = fma(act, gate, -hi))
+    // and the X3 form's lo halves differ from those of the stored value
+    asm volatile("" : "+v"(v));
+    return v;
+  };
 
   if (nsteps > 0) {
     stage(0);
@@ -911,6 +933,12 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_f32dma_kernel(const WgradK
         }
         __builtin_amdgcn_sched_barrier(0);
         if (have) mma_stage();
+        if constexpr (GATE) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int b = 0; b < JB; ++b) rb[e][b] = gate1(rb[e][b], b);
+        }
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
           const float v[8] = {ra[0][a], ra[1][a], ra[2][a], ra[3][a], ra[4][a], ra[5][a], ra[6][a], ra[7][a]};
@@ -942,6 +970,10 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_f32dma_kernel(const WgradK
           }
         };
         f32x4 av = lda(0), bv = ldb(0);
+        if constexpr (GATE) {
+  #pragma unroll
+          for (int b = 0; b < JB; ++b) bv[b] = gate1(bv[b], b);
+        }
   #pragma unroll
         for (int ks = 0; ks < BKM / 4; ++ks) {
           f32x4 an = av, bn = bv;
@@ -954,6 +986,12 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_f32dma_kernel(const WgradK
           if (want_bias) {
   #pragma unroll
             for (int a = 0; a < 4; ++a) bsum[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], 1.0f, bsum[a], 0, 0, 0);
+          }
+          if constexpr (GATE) {          // (the next k-step's x values, behind the MFMAs just issued)
+            if (ks + 1 < BKM / 4) {
+  #pragma unroll
+              for (int b = 0; b < JB; ++b) bn[b] = gate1(bn[b], b);
+            }
           }
           av = an; bv = bn;
         }
@@ -1004,8 +1042,11 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_f32dma_kernel(const WgradK
 // 16 bytes gathered by the DMA lanes (lane = (pixel, tap): computed source address, halo taps out of range = zeros), i.e. an im2col row
 // of 36 floats = the packed [tap][channel] gradient row; everything behind the staging is the pointwise kernel with Cin = 36.
 // (On the 128 x 128-tile kernel this launch was 250 us for 402 MB: 97 % of its tile is padding.)
-template <int NTA, int NTB, bool STEM = false>
+// GATE (pointwise form, image_splits; effdet_conv2d_wgrad_gated): as in conv_wgrad_f32dma_kernel, on the x fragments fb[u][b].  The lanes
+// of the zero dump piece get gate 0 (swish(+0) * 0 = +0) and the zero-filled pixels past the split's end are left as they are.
+template <int NTA, int NTB, bool STEM = false, int GATE = 0>
 __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(const WgradK p, int P, int pps, int NS) {
+  static_assert(!GATE || !STEM, "the operand gate covers the pointwise form");
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1081,6 +1122,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(const WgradK p, in
   }
   const bool want_ds = p.dbp != nullptr;
   const char* lds = (const char*)smem;
+  float gb[NTB];
+  if constexpr (GATE) {
+    const float* grow = p.a_gate + (long long)(m_begin / p.gate_hw) * Cin;
+#pragma unroll
+    for (int b = 0; b < NTB; ++b) gb[b] = okb[b] ? grow[16 * b + li] : 0.f;
+  }
   // NS slots, NS - 1 stages in flight: the loaded HBM round trip is 4-5 us here, i.e. ~100 KB per CU must be under way to stream at
   // 20 GB/s per CU (three slots of a 112-channel stage, 57 KB in flight, gave 2.6 TB/s; two workgroups x two 24-KB stages 5.2)
   for (int i = 0; i < NS - 1 && i < nst; ++i) stage(i);
@@ -1101,6 +1148,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(const WgradK p, in
         for (int a = 0; a < NTA; ++a) fa[u][a] = *(const float*)(sl + (oka[a] ? zr + offa[a] : dump));
 #pragma unroll
         for (int b = 0; b < NTB; ++b) fb[u][b] = *(const float*)(sl + (okb[b] ? xr + offb[b] : dump));
+      }
+      if constexpr (GATE) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const bool pv = m_begin + it * P + 4 * (g + 4 * u) + lk < m_end;
+#pragma unroll
+          for (int b = 0; b < NTB; ++b) {
+            float v = fb[u][b];
+            if constexpr (GATE == 2) v = swishf_(v);
+            v *= gb[b];
+            fb[u][b] = pv ? v : fb[u][b];
+          }
+        }
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -1334,23 +1394,25 @@ struct WgradPlan {
   int first[EFFDET_MAX_SEG], count[EFFDET_MAX_SEG];                  // slab range of every level (effdet_conv2d_wgrad_seg_slabs)
   int P, NS, pps;              // thin kernel: pixels per stage, ring slots, DMA instructions per wave and stage
   ThinLaunch thin;             // thin kernel: the instance for the (Cout / 16, Cin / 16) tile shape
+  int gate;                    // the kernels' GATE parameter: 0, or the operand-gate form (1 multiply, 2 Swish + multiply)
   size_t lds;                  // dynamic LDS bytes of the main launch
   int allr;                    // split kernel: all fragment reads of a K-step issued ahead of its MFMAs
   long long slab_floats;       // floats per slab (cout x algorithmic K)
   long long workspace_bytes;   // slabs + the [splits][cout] bias partial rows
 };
 
-template <int NTA, int NTB, bool STEM = false>
+template <int NTA, int NTB, bool STEM = false, int GATE = 0>
 void launch_thin(const WgradPlan& w, const WgradK& k, hipStream_t st) {
-  EFFDET_SET_MAX_LDS((conv_wgrad_thin_kernel<NTA, NTB, STEM>), w.lds);
-  hipLaunchKernelGGL((conv_wgrad_thin_kernel<NTA, NTB, STEM>), dim3((unsigned)w.splits), dim3(256), w.lds, st, k, w.P, w.pps, w.NS);
+  EFFDET_SET_MAX_LDS((conv_wgrad_thin_kernel<NTA, NTB, STEM, GATE>), w.lds);
+  hipLaunchKernelGGL((conv_wgrad_thin_kernel<NTA, NTB, STEM, GATE>), dim3((unsigned)w.splits), dim3(256), w.lds, st, k, w.P, w.pps, w.NS);
 }
 // (Cout / 16, Cin / 16) tile shapes conv_wgrad_thin_kernel is built for: EfficientNet-B0..B2's high-resolution 1x1 convs
-const struct { int nta, ntb; ThinLaunch launch; } thin_shapes[] = {
-  {1, 2, launch_thin<1, 2>}, {6, 1, launch_thin<6, 1>}, {2, 6, launch_thin<2, 6>}, {9, 2, launch_thin<9, 2>}, {2, 9, launch_thin<2, 9>},
-  {3, 9, launch_thin<3, 9>}, {1, 1, launch_thin<1, 1>}, {2, 1, launch_thin<2, 1>}, {1, 3, launch_thin<1, 3>}, {2, 2, launch_thin<2, 2>}};
-ThinLaunch thin_launch(int nta, int ntb) {
-  for (const auto& t : thin_shapes) if (t.nta == nta && t.ntb == ntb) return t.launch;
+#define THIN_(a, b) {a, b, {launch_thin<a, b>, launch_thin<a, b, false, 1>, launch_thin<a, b, false, 2>}}
+const struct { int nta, ntb; ThinLaunch launch[3]; } thin_shapes[] = {      // launch[GATE]
+  THIN_(1, 2), THIN_(6, 1), THIN_(2, 6), THIN_(9, 2), THIN_(2, 9), THIN_(3, 9), THIN_(1, 1), THIN_(2, 1), THIN_(1, 3), THIN_(2, 2)};
+#undef THIN_
+ThinLaunch thin_launch(int nta, int ntb, int gate = 0) {
+  for (const auto& t : thin_shapes) if (t.nta == nta && t.ntb == ntb) return t.launch[gate];
   return nullptr;
 }
 // Does the (normalised) descriptor go to conv_wgrad_thin_kernel?  1 = one contiguous pointwise level, few channels, many pixels;
@@ -1375,8 +1437,11 @@ int thin_eligible(const effdet_wgrad_t* p, bool splitfmt) {
 }
 
 // Validates the descriptor and fills the plan: -> EFFDET_OK or EFFDET_E* (< 0).
-int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w) {
+// a_gate != NULL: the operand-gate form (effdet_conv2d_wgrad_gated) or EFFDET_EUNSUPPORTED -- never a plain launch on ungated data.
+int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w, const float* a_gate = nullptr, int a_act = EFFDET_ACT_NONE) {
   if (!p) return EFFDET_EINVAL;
+  if (a_gate && a_act != EFFDET_ACT_NONE && a_act != EFFDET_ACT_SWISH) return EFFDET_EINVAL;
+  w.gate = a_gate ? (a_act == EFFDET_ACT_SWISH ? 2 : 1) : 0;
   effdet_wgrad_t& q = w.d;
   q = *p; w.cout = q.Cout; w.x3 = w.split = false;
   if (q.dtype == EFFDET_F32_BF16X3) { q.dtype = EFFDET_F32; w.x3 = true; }
@@ -1390,6 +1455,16 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w) {
   WgradK& k = w.k;
   const int rc = plan(&q, k, w.splits, w.split || thin ? 256 : 128);      // (tile 256 of the bf16 VIEW for the split-layout kernel)
   if (rc != EFFDET_OK) return rc;
+  k.a_gate = a_gate; k.gate_hw = 1;
+  if (a_gate) {
+    // operand gate: one pointwise level of contiguous fp32 maps, per-image splits of whole 32-pixel stages, a 4-byte aligned gate
+    if (q.nseg != 1) return EFFDET_EUNSUPPORTED;
+    const effdet_seg_t& g = q.seg[0];
+    if (w.split || q.dtype != EFFDET_F32 || !q.image_splits || thin == 2 || q.KH != 1 || q.KW != 1 || q.stride != 1 || q.pad_t || q.pad_l ||
+        g.H != g.Ho || g.W != g.Wo || g.in_bstride != (long long)g.H * g.W * q.ldx || g.out_bstride != (long long)g.Ho * g.Wo * q.lddz ||
+        (k.mchunk & 31) || ((long long)g.Ho * g.Wo) % k.mchunk || ((size_t)a_gate & 3)) return EFFDET_EUNSUPPORTED;
+    k.gate_hw = g.Ho * g.Wo;
+  }
   // slab ranges, in the order of the launches: the levels the DMA-staged kernels take first, then the register-transpose kernel's
   // (each launch numbers its own splits from 0 and owns a contiguous range; the split-layout kernel takes every level in order)
   static const int f32dma = getenv("EFFDET_WGRAD_F32DMA") ? atoi(getenv("EFFDET_WGRAD_F32DMA")) : 1;      // A/B switch
@@ -1441,7 +1516,7 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w) {
     while (w.NS > 2 && (w.NS - 2) * w.pps > 48) --w.NS;                                       // (the vmcnt immediates the kernel has)
     w.lds = (size_t)w.NS * ((size_t)w.P * ch * 4 + 1024);
     if (w.lds < 32 * 1024) w.lds = 32 * 1024;                                                 // the final cross-wave reduction (8 tiles x 4 waves)
-    w.thin = thin_launch((q.Cout + 15) / 16, (q.Cin + 15) / 16);
+    w.thin = thin_launch((q.Cout + 15) / 16, (q.Cin + 15) / 16, w.gate);
   } else {
     // the levels split between the DMA-staged kernel (fast) and the register-transpose kernel
     w.path = WG_TILED;
@@ -1456,6 +1531,7 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w) {
     for (int s = ns; s < EFFDET_MAX_SEG; ++s) { w.ks.seg[s] = w.ks.seg[0]; w.ks.seg[s].split_start = 0x7fffffff; }
     k.nseg = nf; w.ks.nseg = ns;
     w.lds = (size_t)4 * 128 * 8 * sizeof(uint4);
+    if (a_gate && ns) return EFFDET_EUNSUPPORTED;      // only the DMA-staged fp32 kernel has the hook, not the register-transpose one
   }
   w.slab_floats = (long long)w.cout * k.K;
   w.workspace_bytes = (long long)w.splits * (w.slab_floats + w.cout) * (long long)sizeof(float);
@@ -1504,11 +1580,12 @@ extern "C" int effdet_conv2d_wgrad_seg_slabs(const effdet_wgrad_t* p, int* first
 
 // live32 (effdet_conv2d_wgrad_live, include/effdet_live_tiles.h; NULL: the dense launch): per-call flags of the split-layout kernel
 static int wgrad_launch(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes, const unsigned char* live32,
-                        effdet_stream_t stream) {
+                        effdet_stream_t stream, const float* a_gate = nullptr, int a_act = EFFDET_ACT_NONE) {
   if (!p || !p->x || !p->dz || !workspace) return EFFDET_EINVAL;
   WgradPlan w;
-  const int rc = plan_wgrad(p, w);
+  const int rc = plan_wgrad(p, w, a_gate, a_act);
   if (rc != EFFDET_OK) return rc;
+  if (a_gate && live32) return EFFDET_EUNSUPPORTED;
   if (workspace_bytes < w.workspace_bytes) return EFFDET_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   WgradK k = w.k;
@@ -1538,7 +1615,14 @@ static int wgrad_launch(const effdet_wgrad_t* p, void* workspace, long long work
     WgradK ks = w.ks;
     ks.slab = k.slab + (long long)w.nfast * w.slab_floats;
     ks.dbp = k.dbp ? k.dbp + (long long)w.nfast * w.cout : nullptr;
-    if (w.nfast > 0 && w.d.dtype == EFFDET_F32 && w.x3) {
+    if (w.gate) {
+      // (plan_wgrad accepted the gate: one level, all of it on the DMA-staged fp32 kernel)
+#define GATED_(NW, X3, G) do { EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<NW, X3, G>), w.lds); \
+        hipLaunchKernelGGL((conv_wgrad_f32dma_kernel<NW, X3, G>), dim3(tiles * w.nfast), dim3(NW * 64), w.lds, st, k); } while (0)
+      if (w.x3) { if (w.gate == 2) GATED_(X3_NW, 1, 2); else GATED_(X3_NW, 1, 1); }
+      else { if (w.gate == 2) GATED_(F32_NW, 0, 2); else GATED_(F32_NW, 0, 1); }
+#undef GATED_
+    } else if (w.nfast > 0 && w.d.dtype == EFFDET_F32 && w.x3) {
       EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<X3_NW, 1>), w.lds);
       hipLaunchKernelGGL((conv_wgrad_f32dma_kernel<X3_NW, 1>), dim3(tiles * w.nfast), dim3(X3_NW * 64), w.lds, st, k);
     } else if (w.nfast > 0 && w.d.dtype == EFFDET_F32) {
@@ -1564,6 +1648,19 @@ static int wgrad_launch(const effdet_wgrad_t* p, void* workspace, long long work
 extern "C" int effdet_conv2d_wgrad(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes,
                                    effdet_stream_t stream) {
   return wgrad_launch(p, workspace, workspace_bytes, nullptr, stream);
+}
+
+// effdet_conv2d_wgrad on act(x) * a_gate[image][channel], the product formed in the kernels' operand registers (include/effdet_gate_operand.h)
+extern "C" int effdet_conv2d_wgrad_gated(const effdet_wgrad_t* p, const float* a_gate, int a_act, void* workspace, long long workspace_bytes,
+                                         effdet_stream_t stream) {
+  if (!a_gate) return EFFDET_EINVAL;
+  return wgrad_launch(p, workspace, workspace_bytes, nullptr, stream, a_gate, a_act);
+}
+extern "C" int effdet_conv2d_wgrad_gated_kernel(const effdet_wgrad_t* p, const float* a_gate, int a_act) {
+  if (!a_gate) return EFFDET_EINVAL;
+  WgradPlan w;
+  const int rc = plan_wgrad(p, w, a_gate, a_act);
+  return rc != EFFDET_OK ? rc : w.path;
 }
 
 extern "C" int effdet_conv2d_wgrad_live(const effdet_wgrad_t* p, void* workspace, long long workspace_bytes,

@@ -37,6 +37,21 @@ GATE_IN_WEIGHTS = os.environ.get('EFFDET_GATE_IN_WEIGHTS', '1') == '1'  # the SE
 # rounding of the project conv's products, and with it the D1 and D6 train goldens leave their `1e-3 + s_k` gates (the single ReLU /
 # max-pool ties of those fixtures fall the other way): 0.4 % of the step is not worth a parity gate
 GATE_IN_WEIGHTS_TRAIN = os.environ.get('EFFDET_GATE_IN_WEIGHTS_TRAIN', '0') == '1'
+# The gate in the project conv's OPERAND (training, fp32 storage, exact-fp32 forward, z-only depthwise storage): the conv and its per-image
+# weight gradient read the depthwise pre-activation and form swish(z_d) * gate[b][c] in their operand registers (ops.conv2d /
+# conv2d_wgrad a_gate=), the very statements channel_scale runs -- every MFMA gets the operand it got, losses and gradients are
+# torch.equal to the channel_scale path's (tests/test_gpu_gate_operand.py), and xs is neither written, read twice nor kept for the
+# backward.  Unlike GATE_IN_WEIGHTS_TRAIN above, which changes the products.
+GATE_IN_OPERAND = os.environ.get('EFFDET_GATE_IN_OPERAND', '1') == '1'
+# ... for maps of at least this many pixels per image (Ho * Wo).  Per block, D0 B = 32 @512, channel_scale + project forward + per-image
+# weight gradient against the two gated launches (tools/gate_operand_timing.py, profiles/gate_operand_launch_timing.json; us):
+#   block   0 (256^2)  1 (128^2)  2 (128^2)  3 (64^2)  4 (64^2)  5 (32^2)  6 (32^2)  7 (32^2) |  8 (16^2)  9 (16^2)  10 (16^2)
+#   old       273.3      192.4      287.2      95.6     147.0      56.8      87.5      87.6   |    65.0      50.9       50.5
+#   gated     193.3      130.6      202.2      76.3     109.1      52.6      82.2      82.1   |    68.5      52.4       52.7
+# The consumers pay 5-30 % for the Swish they now run (forward +0 .. +8 us, weight gradient +3 .. +23 us per launch): that stays below
+# channel_scale's pass down to the 32 x 32 maps and exceeds it on the 16 x 16 ones, whose 8.6 us pass was mostly launch latency.
+# Blocks 11 .. 15 (8 x 8, 4 x 4) are no whole 128-pixel tiles per image: the planners refuse them.  Hence 1024.
+GATE_OPERAND_MIN_HW = int(os.environ.get('EFFDET_GATE_OPERAND_MIN_HW', '1024'))
 
 
 def chunk_elems(dtype):
@@ -172,10 +187,20 @@ def mbconv_fwd(x, blk, P, dtype, train, rowscale=None, xpre=None, in_act=ACT_NON
                    rowscale=rowscale if blk.skip else None,
                    res=x if blk.skip else None, res_mode=RES_ADD if blk.skip else RES_NONE, w_image_stride=wstride)
     else:
-        xs = ops.channel_scale(zd, gate, ACT_SWISH) if z_only else ops.channel_scale(xd, gate)
-        ops.conv2d(xs, ops.pack_weight(P['project.weight'], dtype), y, Cin=blk.cexp, Cout=blk.cout, KH=1, KW=1,
-                   scale=s2, shift=t2, act=ACT_NONE, rowscale=rowscale if blk.skip else None,
+        wpp = ops.pack_weight(P['project.weight'], dtype)
+        pkw = dict(Cin=blk.cexp, Cout=blk.cout, KH=1, KW=1, scale=s2, shift=t2, act=ACT_NONE, rowscale=rowscale if blk.skip else None,
                    res=x if blk.skip else None, res_mode=RES_ADD if blk.skip else RES_NONE)
+        # gate in the operand: both readers of xs must take the form (the planners say: exact-fp32 launch, whole 128-pixel tiles per image,
+        # per-image splits on the thin / DMA-staged weight-gradient kernels), else xs is materialised as before
+        gio = (GATE_IN_OPERAND and z_only and dtype == torch.float32 and SE_FUSED and Ho * Wo >= GATE_OPERAND_MIN_HW
+               and ops.conv2d_gated_ok(zd, wpp, y, gate, ACT_SWISH, **pkw)
+               and ops.conv2d_wgrad_gated_ok(zd, y, gate, ACT_SWISH, Cin=blk.cexp, Cout=blk.cout))
+        if gio:
+            xs = None
+            ops.conv2d(zd, wpp, y, a_gate=gate, a_act=ACT_SWISH, **pkw)
+        else:
+            xs = ops.channel_scale(zd, gate, ACT_SWISH) if z_only else ops.channel_scale(xd, gate)
+            ops.conv2d(xs, wpp, y, **pkw)
     if train:
         sv.update(xe=xe, s1=s1, i1=i1, wk=wk, xd=xd, zd=zd, pool=pool, gate=gate, mid=mid, xs=xs, s2=s2, i2=i2,
                   inv_hw=inv_hw, dw_in_act=dw_in_act, giw=giw)
@@ -197,6 +222,12 @@ def mbconv_bwd(sv, dy):
     giw = sv.get('giw', False)
     if giw and not (SE_FUSED and hw % 32 == 0):       # (the switch was flipped between forward and backward: tests do that)
         sv['xs'] = ops.channel_scale(sv['xd'], sv['gate']); giw = False
+    # gate in the operand (the forward kept no xs): the fused branch below takes z_d + the gate; with the switch flipped since the forward,
+    # or on the un-fused branch, xs is materialised first -- the same values either way
+    gio = (not giw and sv['xs'] is None and GATE_IN_OPERAND and SE_FUSED and hw % 32 == 0 and dtype == torch.float32
+           and ops.conv2d_wgrad_gated_ok(sv['zd'], dy, sv['gate'], ACT_SWISH, Cin=Ce, Cout=Co))
+    if not giw and sv['xs'] is None and not gio:
+        sv['xs'] = ops.channel_scale(sv['zd'], sv['gate'], ACT_SWISH)
     if SE_FUSED and hw % (64 if dtype == torch.bfloat16 else 32) == 0:
         # Fused form (no pass over the activations for the gate gradient, dxs never materialised):
         #   per-image partial weight gradients M_b = dy_b^T xs_b (split-K on image boundaries)
@@ -205,7 +236,10 @@ def mbconv_bwd(sv, dy):
         # -- se_dgate (2 tensor reads), se_bwd_apply (2 reads + 1 write) and the drop_connect act_bwd become one extra read of z_d.
         # (giw: the forward ran on W diag(gate_b) and x_d; the slabs are then M'_b = dy_b^T x_d,b -- the gate re-enters as a per-(image,
         #  channel) factor of the unpack, and sum_n W'[n][c] M'_b[n][c] is d(loss)/d(gate) itself, not yet times the gate)
-        G2, dsum2 = ops.conv2d_wgrad(sv['xd'] if giw else sv['xs'], dy, Cin=Ce, Cout=Co, KH=1, KW=1, image_splits=True)
+        if gio:
+            G2, dsum2 = ops.conv2d_wgrad(sv['zd'], dy, Cin=Ce, Cout=Co, KH=1, KW=1, image_splits=True, a_gate=sv['gate'], a_act=ACT_SWISH)
+        else:
+            G2, dsum2 = ops.conv2d_wgrad(sv['xd'] if giw else sv['xs'], dy, Cin=Ce, Cout=Co, KH=1, KW=1, image_splits=True)
         g['project.weight'], g['bn2.weight'], g['bn2.bias'] = ops.unpack_wgrad_bn(G2, wp, sv['s2'], dsum2, P['bn2.running_mean'], sv['i2'],
                                                                                  slab_scale=rs, slab_cscale=sv['gate'] if giw else None)
         dgg = ops.se_dgate_from_wgrad(G2, wp, sv['s2'], rs, B)

@@ -496,8 +496,12 @@ def _conv_desc(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, sca
 
 def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
            res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
-           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0, needed=None, needed_tile0=0):
+           w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0, needed=None, needed_tile0=0,
+           a_gate=None, a_act=ACT_NONE):
     """Grouped implicit-GEMM conv: xs/ys (and optional zs/res) are lists of Map, one per pyramid level.
+    a_gate ([B][Cin] fp32, with a_act = ACT_NONE or ACT_SWISH): the conv runs on act(xs) * a_gate[image][channel], formed in the kernel's
+    operand registers (effdet_conv2d_gated) -- bit for bit conv2d(channel_scale(xs, a_gate, a_act), ...) without that pass.  Exact-fp32
+    1x1 convs on one map whose images are whole 128-pixel tiles (conv2d_gated_ok); anything else raises.
     split=True (EFFDET_F32_SPLIT): xs hold the split layout ([32 x bf16 hi | 32 x bf16 lo] per 32 channels, 4 B per element), wp
     is packed for bf16x3; ys are written split too unless out_f32 (then plain fp32; res, if any, is plain and ADDed).
     ysplit (exact-fp32 and f16x3 convs only): Maps addressed like ys that receive the output a second time in the split layout.
@@ -521,7 +525,14 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     # algorithmic bytes: the input map, the packed weights, every output stream (y, the pre-activation copy, the split copy), the residual
     nbytes = isx * Cin * sum(x.B * x.H * x.W for x in xs) + wp.numel() * wp.element_size() + \
         (4 if out_f32 else isy) * Cout * sum(y.B * y.H * y.W for y in ys) * (1 + (zs is not None) + (ysplit is not None) + (res is not None))
-    if live is not None:
+    if a_gate is not None:
+        assert live is None and needed is None and a_gate.dtype == torch.float32 and a_gate.is_contiguous() and a_gate.shape == (x0.B, Cin)
+
+        def run():
+            L.check(L.require('effdet_conv2d_gated').effdet_conv2d_gated(C.byref(d), a_gate.data_ptr(), int(a_act), L.stream_ptr()),
+                    'effdet_conv2d_gated')
+            GATE_OPERAND_LAUNCHES[0] += 1
+    elif live is not None:
         run = lambda: L.check(L.require('effdet_conv2d_live').effdet_conv2d_live(C.byref(d), live.data_ptr(), int(live_tile0), L.stream_ptr()),
                               'effdet_conv2d_live')
     elif needed is not None:
@@ -536,6 +547,42 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
 
 
 NEEDED_LAUNCHES = [0]        # conv2d(..., needed=...) calls made so far (tests: which path a step took)
+GATE_OPERAND_LAUNCHES = [0, 0]     # conv2d(..., a_gate=...) / conv2d_wgrad(..., a_gate=...) calls made so far (tests: which path a step took)
+
+
+def conv2d_gated_plan_info(xs, wp, ys, a_gate, a_act=ACT_NONE, **kw):
+    """conv2d_plan_info for conv2d(xs, wp, ys, a_gate=a_gate, a_act=a_act, **kw) (effdet_conv2d_gated_plan_info: no device work) -> its
+    dict plus 'gate' (the form the launch takes: 1 = x * gate, 2 = swish(x) * gate), or None where the planner answers
+    EFFDET_EUNSUPPORTED; other refusals raise."""
+    d, _, _ = _conv_desc(xs, wp, ys, **kw)
+    info = L.ConvPlanInfo()
+    rc = int(L.require('effdet_conv2d_gated_plan_info').effdet_conv2d_gated_plan_info(C.byref(d), a_gate.data_ptr(), int(a_act), C.byref(info)))
+    if rc == -3:
+        return None
+    if rc < 0:
+        L.check(rc, 'effdet_conv2d_gated_plan_info')
+    out = {n: int(getattr(info, n)) for n, _ in L.ConvPlanInfo._fields_ if n != 'reserved'}
+    out['form'] = L.CONV_FORMS[out['form']]
+    out['persistent'], out['m32'], out['gate'] = bool(out['persistent']), bool(out['m32']), int(info.reserved[0])
+    return out
+
+
+def conv2d_gated_ok(xs, wp, ys, a_gate, a_act=ACT_NONE, **kw):
+    """Does the planner accept conv2d(xs, wp, ys, a_gate=a_gate, a_act=a_act, **kw)?  False: the caller materialises channel_scale's
+    output instead."""
+    info = conv2d_gated_plan_info(xs, wp, ys, a_gate, a_act, **kw)
+    return info is not None and info['gate'] == (2 if a_act == ACT_SWISH else 1)
+
+
+def conv2d_wgrad_gated_ok(x, dz, a_gate, a_act=ACT_NONE, *, Cin, Cout, KH=1, KW=1, image_splits=True):
+    """Does the planner accept conv2d_wgrad(x, dz, ..., a_gate=a_gate, a_act=a_act)?  (effdet_conv2d_wgrad_gated_kernel: no device work.)"""
+    d = _wgrad_desc([x], [dz], None, None, Cin, Cout, KH, KW, 1, 0, 0, True, False, image_splits)
+    rc = int(L.require('effdet_conv2d_wgrad_gated_kernel').effdet_conv2d_wgrad_gated_kernel(C.byref(d), a_gate.data_ptr(), int(a_act)))
+    if rc == -3:
+        return False
+    if rc < 0:
+        L.check(rc, 'effdet_conv2d_wgrad_gated_kernel')
+    return True
 
 
 def conv2d_plan_info(xs, wp, ys, **kw):
@@ -572,21 +619,28 @@ def _wgrad_desc(xs, dzs, dw, dbias, Cin, Cout, KH, KW, stride, pad_t, pad_l, wan
     return d
 
 
-def conv2d_wgrad_kernel_id(x, dz, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, split=False):
-    """Which kernel conv2d_wgrad would launch for one map pair (effdet_conv2d_wgrad_kernel): 0 tiled, 1 thin pointwise, 2 split."""
-    d = _wgrad_desc([x], [dz], None, None, Cin, Cout, KH, KW, stride, pad_t, pad_l, True, split, False)
+def conv2d_wgrad_kernel_id(x, dz, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, split=False, image_splits=False, a_gate=None,
+                           a_act=ACT_NONE):
+    """Which kernel conv2d_wgrad would launch for one map pair (effdet_conv2d_wgrad_kernel): 0 tiled, 1 thin pointwise, 2 split;
+    with a_gate: the operand-gate launch's (effdet_conv2d_wgrad_gated_kernel), negative where it is refused."""
+    d = _wgrad_desc([x], [dz], None, None, Cin, Cout, KH, KW, stride, pad_t, pad_l, True, split, image_splits)
+    if a_gate is not None:
+        return int(L.require('effdet_conv2d_wgrad_gated_kernel').effdet_conv2d_wgrad_gated_kernel(C.byref(d), a_gate.data_ptr(), int(a_act)))
     return int(L.lib().effdet_conv2d_wgrad_kernel(C.byref(d)))
 
 
 def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, split=False,
-                 image_splits=False, group=False, live32=None):
+                 image_splits=False, group=False, live32=None, a_gate=None, a_act=ACT_NONE):
     """Weight gradient -> (slabs [splits][Cout][taps][Cin] fp32, bias partial rows [splits][Cout] fp32 or None): the UNREDUCED
     split-K partials for unpack_wgrad / unpack_wgrad_bn to sum, in slab order, while unpacking (no float atomics anywhere: two
     runs are bitwise equal).  With dw given (packed [Cout][taps][Cin] fp32) the library reduces itself: dw += ..., dbias += ...
     group=True (dw None, <= 5 maps): the maps are INDEPENDENT problems of the same conv geometry (different tensors, different
     weights) sharing one launch -> a list of (slabs_i, parts_i), one per map (effdet_conv2d_wgrad_seg_slabs).
     live32 (split only; uint8 tensor, one byte per 32-pixel step of dzs: live_tiles()[0][r]): a 0 marks a step whose dz pixels are all
-    zero; every split-K block walks only its live steps.  Same slabs and bias rows as without."""
+    zero; every split-K block walks only its live steps.  Same slabs and bias rows as without.
+    a_gate ([B][Cin] fp32, with a_act = ACT_NONE or ACT_SWISH; image_splits, one 1x1 map pair): the gradient against
+    act(xs) * a_gate[image][channel], formed in the kernels' operand registers (effdet_conv2d_wgrad_gated) -- bit for bit
+    conv2d_wgrad(channel_scale(xs, a_gate, a_act), ...) without that pass; raises where the planner refuses (conv2d_wgrad_gated_ok)."""
     if isinstance(xs, Map):
         xs, dzs = [xs], [dzs]
     x0 = xs[0]
@@ -598,7 +652,14 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     n = Cout * KH * KW * Cin
     ws = torch.empty(splits * (n + Cout), dtype=torch.float32, device=x0.t.device)
     nbytes = ws.numel() * 4
-    if live32 is not None:
+    if a_gate is not None:
+        assert live32 is None and not group and a_gate.dtype == torch.float32 and a_gate.is_contiguous() and a_gate.shape == (x0.B, Cin)
+
+        def run():
+            L.check(L.require('effdet_conv2d_wgrad_gated').effdet_conv2d_wgrad_gated(
+                C.byref(d), a_gate.data_ptr(), int(a_act), L.ptr(ws), nbytes, L.stream_ptr()), 'effdet_conv2d_wgrad_gated')
+            GATE_OPERAND_LAUNCHES[1] += 1
+    elif live32 is not None:
         assert split and live32.dtype == torch.uint8 and live32.is_contiguous()
         assert live32.numel() == sum((z.B * z.H * z.W + 31) // 32 for z in dzs)
         run = lambda: L.check(L.require('effdet_conv2d_wgrad_live').effdet_conv2d_wgrad_live(C.byref(d), L.ptr(ws), nbytes, live32.data_ptr(),
