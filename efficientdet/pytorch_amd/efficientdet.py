@@ -358,7 +358,7 @@ class _HeadLossFn(torch.autograd.Function):
             # ONE pass over the 15.7 MB/image of probabilities: losses + d(logits) for an upstream gradient of one, already in
             # the pixel-major, 64-channel-padded rows the head's gradient convs read; cls itself is not kept for backward
             dld = (9 * nc + 63) // 64 * 64
-            losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved[5], loss=loss, box=box,    # (split-layout head: see functional.head_uses_split)
+            losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved.split, loss=loss, box=box,    # (split-layout head: see functional.head_uses_split)
                                                       matcher=matcher, levels=levels)
             ctx.saved = (saved, None, reg, anchors, annots, ws, dtype, dpix, dld)
         else:
@@ -376,7 +376,7 @@ class _HeadLossFn(torch.autograd.Function):
         saved, cls, reg, anchors, annots, ws, dtype, dpix, dld = ctx.saved
         gscale = torch.cat([gcls.reshape(1), greg.reshape(1)]).float().contiguous()
         if dpix is not None:
-            split = saved[5]
+            split = saved.split
             rld = 64 if split else 0                # split layout: d(reg) pixel-major, 36 -> 64 channels (two [hi|lo] groups)
             dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, loss=ctx.loss, box=ctx.box,
                                          matcher=ctx.matcher)

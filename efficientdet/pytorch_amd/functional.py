@@ -9,6 +9,8 @@ Frozen-BN backward without re-reading the conv output: for y = act(s
 s = gamma*invstd:   dz = dy*act'(z);  dx = dgrad(dz, W*s);  G = x^T dz;  dW = s*G;
 dgamma = invstd*(sum_k W*G - mean*sum dz);  dbeta = sum dz.
 """
+import collections
+import contextlib
 import os
 
 import torch
@@ -426,30 +428,30 @@ def bifpn_module_bwd(saved, douts, dtype, own=False):
 
 
 # ------------------------------------------------------------------------------------------ RetinaHead
+def _pyramid_alloc_n(n, B, sizes, C, dtype, device):
+    """n pyramids of one geometry (one activation of n towers of the head) in ONE flat buffer, tower-major then level-major, so that
+    grouped launches can address every pyramid tensor of the same channel count with identical relative offsets: outputs, split copies
+    and ReLU-mask residuals of all n towers from one base each.  -> (flat, [maps of tower 0, ...])"""
+    flat = torch.empty(n * sum(B * h * w * C for (h, w) in sizes), dtype=dtype, device=device)
+    out, off = [], 0
+    for _ in range(n):
+        maps = []
+        for (h, w) in sizes:
+            maps.append(Map(flat, B, h, w, C, off=off)); off += B * h * w * C
+        out.append(maps)
+    return flat, out
+
+
 def pyramid_alloc(B, sizes, C, dtype, device):
-    """All levels of one activation in ONE flat buffer (level-major) so that grouped launches can
-    address every pyramid tensor of the same channel count with identical relative offsets."""
-    tot = sum(B * h * w * C for (h, w) in sizes)
-    flat = torch.empty(tot, dtype=dtype, device=device)
-    maps, off = [], 0
-    for (h, w) in sizes:
-        maps.append(Map(flat, B, h, w, C, off=off)); off += B * h * w * C
+    """All levels of one activation in ONE flat buffer (level-major).  -> (flat, maps)"""
+    flat, (maps,) = _pyramid_alloc_n(1, B, sizes, C, dtype, device)
     return flat, maps
 
 
 def pyramid_alloc_pair(B, sizes, C, dtype, device):
-    """Two pyramids of one geometry (the same layer of the head's two towers) in ONE flat buffer, tower-major then level-major: every
-    buffer allocated this way has the same relative offsets, which is what lets one grouped launch address outputs, split copies and
-    ReLU-mask residuals of both towers from one base each.  -> (flat, maps of tower A, maps of tower B)"""
-    tot = sum(B * h * w * C for (h, w) in sizes)
-    flat = torch.empty(2 * tot, dtype=dtype, device=device)
-    out = []
-    for half in (0, 1):
-        maps, off = [], half * tot
-        for (h, w) in sizes:
-            maps.append(Map(flat, B, h, w, C, off=off)); off += B * h * w * C
-        out.append(maps)
-    return flat, out[0], out[1]
+    """The same layer of the head's two towers in ONE flat buffer.  -> (flat, maps of tower A, maps of tower B)"""
+    flat, (a, b) = _pyramid_alloc_n(2, B, sizes, C, dtype, device)
+    return flat, a, b
 
 
 def level_tensor(m):
@@ -494,7 +496,6 @@ class _Fork:
         return self
 
     def side(self):
-        import contextlib
         return torch.cuda.stream(self.s) if self.on else contextlib.nullcontext()
 
     def join(self):
@@ -574,6 +575,41 @@ def head_fwd_takes_needed(p, dtype, train):
     return bool(HEAD_SPARSE_REG_FWD and train and hs and split_bwd)
 
 
+_K3 = dict(KH=3, KW=3, pad_t=1, pad_l=1)       # every conv of the head, forward and backward: 3x3, stride 1, same-padded
+# what head_fwd hands head_bwd: the pyramid as the weight gradients read it, {tower: its four layer outputs in that form}, the level
+# sizes, the parameter dict, the class count, whether all of it is in the split layout, and whether the forward ran the towers as a pair
+HeadSaved = collections.namedtuple('HeadSaved', 'pyramid acts sizes HP num_classes split paired')
+
+
+def _tower_layer(group, xs, wp, geo, Cin, shift=None, ysplit=False, res=None, **kw):
+    """The 3x3 conv to 256 channels of every tower of `group` (a tuple of tower names, in segment order) as ONE launch: a forward layer
+    or its data gradient.  xs / wp / shift / res: {tower: input maps / packed weight / bias / residual maps}; geo: (B, sizes, dtype,
+    device, 128-pixel tiles of one pyramid); kw: ops.conv2d's other arguments, needed= / live= being the REGRESSION tower's flags.
+    -> ({tower: output maps}, {tower: maps of the split copy} or None), each set in one flat tower-major buffer.
+    The towers are independent chains of identical launches: two run concatenated, with per-segment weights / bias (effdet_conv_t.seg_w
+    / seg_shift) and the flags starting at the regression tower's first tile -- 2 x 2728 tiles on the 512 workgroup slots = 10.66 rounds
+    instead of twice 5.33: the draining third of a round is paid once per layer, not twice.  Same tiles, same K walk: bit for bit the
+    separate launches.  A single tower passes no per-segment operands (the planner takes those for another kind of launch)."""
+    B, sizes, dtype, dev, ntile = geo
+    first = group[0]
+    ys = dict(zip(group, _pyramid_alloc_n(len(group), B, sizes, 256, dtype, dev)[1]))
+    ss = dict(zip(group, _pyramid_alloc_n(len(group), B, sizes, 256, dtype, dev)[1])) if ysplit else None
+    if len(group) > 1:
+        L = len(sizes)
+        kw['seg_w'] = [wp[tw] for tw in group for _ in range(L)]
+        if shift is not None:
+            kw['seg_shift'] = [shift[tw] for tw in group for _ in range(L)]
+    for flags in ('needed', 'live'):
+        if kw.get(flags) is not None:
+            kw[flags + '_tile0'] = ntile * group.index('reg')
+
+    def cat(d):
+        return [m for tw in group for m in d[tw]] if d is not None else None
+    ops.conv2d(cat(xs), wp[first], cat(ys), Cin=Cin, Cout=256, **_K3, shift=shift[first] if shift is not None else None, ysplit=cat(ss),
+               res=cat(res), **kw)
+    return ys, ss
+
+
 def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
     """models/retinahead.py:109-132 for all 5 levels per launch (weights are shared across levels).
     p: 5 Maps; HP: dict of head parameter tensors.  -> classification [B,A,nc] fp32 (probabilities),
@@ -593,10 +629,13 @@ def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
     split, split_bwd, hs = _head_forms(B, sizes, Wc, dtype, train)
     if not (hs and split_bwd):
         reg_needed = None
-    ntile = sum((B * h * w + 127) // 128 for (h, w) in sizes)
+    geo = (B, sizes, dtype, dev, sum((B * h * w + 127) // 128 for (h, w) in sizes))
 
-    def need(r):
-        return reg_needed[r] if reg_needed is not None else None
+    def need(towers, r):
+        return reg_needed[r] if (reg_needed is not None and 'reg' in towers) else None
+
+    def pack(w):
+        return ops.pack_weight(w, dtype, x3=split, h3=hs)
     pin, pin_h = p, None
     if split or split_bwd or hs:    # the pyramid once in the split layout(s): operand of both towers' first conv and of their weight gradients
         pin, pin_h = _pyramid_to_split(p, B, sizes, Wc, dtype, dev, bf=split or split_bwd, h=hs)
@@ -605,56 +644,31 @@ def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
     acts = {'cls': [], 'reg': []}
     cls = torch.empty((B, A, num_classes), dtype=torch.float32, device=dev)
     reg = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
+    out = {'cls': (cls, num_classes, ACT_SIGMOID), 'reg': (reg, 4, ACT_NONE)}
 
-    def tower_fwd(tower):
-        cur = pin_h if hs else (p if split_bwd else pin)
+    def towers_fwd(group):
+        """the four layers of the group's towers, one launch per layer, then the output conv of each tower"""
+        cur = dict.fromkeys(group, pin_h if hs else (p if split_bwd else pin))
         for t in range(4):
-            w, b = HP[f'{tower}_convs.{t}.weight'], HP[f'{tower}_convs.{t}.bias']
-            _, nxt = pyramid_alloc(B, sizes, 256, dtype, dev)
-            nxs = pyramid_alloc(B, sizes, 256, dtype, dev)[1] if split_bwd else None
-            ops.conv2d(cur, ops.pack_weight(w, dtype, x3=split, h3=hs), nxt, Cin=w.shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1,
-                       shift=b, act=ACT_RELU, split=split, ysplit=nxs, hsplit=hs, needed=need(4 - t) if tower == 'reg' else None)
-            acts[tower].append(nxs if split_bwd else nxt); cur = nxt       # (split_bwd: `cur` stays plain fp32 / H-split and is not kept for backward)
-        if tower == 'cls':
-            ops.conv2d(cur, ops.pack_weight(HP['retina_cls.weight'], dtype, x3=split, h3=hs), head_out_maps(cls, B, sizes, num_classes),
-                       Cin=256, Cout=9 * num_classes, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_cls.bias'],
-                       act=ACT_SIGMOID, out_f32=True, split=split, hsplit=hs)
-        else:
-            ops.conv2d(cur, ops.pack_weight(HP['retina_reg.weight'], dtype, x3=split, h3=hs), head_out_maps(reg, B, sizes, 4),
-                       Cin=256, Cout=36, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_reg.bias'], out_f32=True, split=split, hsplit=hs,
-                       needed=need(0))
-    paired = hs and HEAD_PAIR_TOWERS
+            w = {tw: HP[f'{tw}_convs.{t}.weight'] for tw in group}
+            cur, ysp = _tower_layer(group, cur, {tw: pack(w[tw]) for tw in group}, geo, w[group[0]].shape[1],
+                                    shift={tw: HP[f'{tw}_convs.{t}.bias'] for tw in group}, ysplit=split_bwd, act=ACT_RELU, split=split,
+                                    hsplit=hs, needed=need(group, 4 - t))
+            for tw in group:          # (split_bwd: `cur` stays plain fp32 / H-split and is not kept for backward)
+                acts[tw].append(ysp[tw] if split_bwd else cur[tw])
+        for tw in group:
+            buf, per, act = out[tw]
+            ops.conv2d(cur[tw], pack(HP[f'retina_{tw}.weight']), head_out_maps(buf, B, sizes, per), Cin=256, Cout=9 * per, **_K3,
+                       shift=HP[f'retina_{tw}.bias'], act=act, out_f32=True, split=split, hsplit=hs, needed=need((tw,), 0))
+    paired = hs and HEAD_PAIR_TOWERS         # layer t of both towers as one launch
     if paired:
-        # The two towers are independent chains of identical launches: layer t of BOTH as ONE launch (per-segment weights / bias,
-        # effdet_conv_t.seg_w / seg_shift): 2 x 2728 tiles on the 512 workgroup slots = 10.66 rounds instead of twice 5.33 -- the
-        # draining third of a round is paid once per layer, not twice.  Same tiles, same K walk: bit for bit the separate launches.
-        cur = {'cls': pin_h, 'reg': pin_h}
-        for t in range(4):
-            w2 = [HP[f'{tw}_convs.{t}.weight'] for tw in ('cls', 'reg')]
-            b2 = [HP[f'{tw}_convs.{t}.bias'] for tw in ('cls', 'reg')]
-            wp2 = [ops.pack_weight(w, dtype, h3=True) for w in w2]
-            _, ya, yb = pyramid_alloc_pair(B, sizes, 256, dtype, dev)
-            sa = sb = None
-            if split_bwd:
-                _, sa, sb = pyramid_alloc_pair(B, sizes, 256, dtype, dev)
-            L5 = len(sizes)
-            ops.conv2d(cur['cls'] + cur['reg'], wp2[0], ya + yb, Cin=w2[0].shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1, shift=b2[0],
-                       act=ACT_RELU, hsplit=True, ysplit=(sa + sb) if split_bwd else None,
-                       seg_w=[wp2[0]] * L5 + [wp2[1]] * L5, seg_shift=[b2[0]] * L5 + [b2[1]] * L5,
-                       needed=need(4 - t), needed_tile0=ntile if reg_needed is not None else 0)
-            acts['cls'].append(sa if split_bwd else ya); acts['reg'].append(sb if split_bwd else yb)
-            cur = {'cls': ya, 'reg': yb}
-        ops.conv2d(cur['cls'], ops.pack_weight(HP['retina_cls.weight'], dtype, h3=True), head_out_maps(cls, B, sizes, num_classes),
-                   Cin=256, Cout=9 * num_classes, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_cls.bias'],
-                   act=ACT_SIGMOID, out_f32=True, hsplit=True)
-        ops.conv2d(cur['reg'], ops.pack_weight(HP['retina_reg.weight'], dtype, h3=True), head_out_maps(reg, B, sizes, 4),
-                   Cin=256, Cout=36, KH=3, KW=3, pad_t=1, pad_l=1, shift=HP['retina_reg.bias'], out_f32=True, hsplit=True, needed=need(0))
+        towers_fwd(('cls', 'reg'))
     else:
         with _Fork(dev, HEAD_TWO_STREAMS and ops.PROFILE is None) as fk:
             with fk.side():
-                tower_fwd('reg')
-            tower_fwd('cls')
-    saved = (pin, acts, sizes, HP, num_classes, split or split_bwd, paired and split_bwd) if train else None
+                towers_fwd(('reg',))
+            towers_fwd(('cls',))
+    saved = HeadSaved(pin, acts, sizes, HP, num_classes, split or split_bwd, paired and split_bwd) if train else None
     return cls, reg, saved
 
 
@@ -671,13 +685,12 @@ def _split_rows(maps, Cfp, dtype):
 def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld=0, in_split=False):
     """dcls_logit [B,A,nc] (or, with dcls_ld, pixel-major and channel-padded [B,A/9,dcls_ld]: ops.focal_loss_bwd_pix),
     dreg [B,A,4] (or, with dreg_ld, pixel-major [B,A/9,dreg_ld]): gradients wrt the cls LOGITS and box deltas, in `dtype` -- when
-    the head was run in the split layout (saved[5]) they are needed in the split layout too: in_split says the pixel-major forms
+    the head was run in the split layout (saved.split) they are needed in the split layout too: in_split says the pixel-major forms
     already are (the loss kernels write it directly), anything else is converted here.  -> (dp: 5 Maps, grads dict keyed like HP).
     cls_gscale (fp32 tensor [1]): dcls_logit was computed for an upstream gradient of one (ops.focal_loss_fwd_grad); the
     real scalar enters here where the chain is linear: as the per-image output scale of retina_cls's data-gradient conv
     and as a factor on retina_cls's own parameter gradients."""
-    p, acts, sizes, HP, nc, split = saved[:6]
-    paired = len(saved) > 6 and saved[6] and split          # the forward laid both towers' activations out pairwise (pyramid_alloc_pair)
+    p, acts, sizes, HP, nc, split, paired = saved
     dev = p[0].t.device
     B, Wc = p[0].B, p[0].C
     g = {}
@@ -688,10 +701,11 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
     live = None
     if HEAD_SPARSE_REG and split and dreg_ld and (in_split or dreg.dtype == torch.float32):
         live = ops.live_tiles(dreg, B, sizes, dreg_ld, in_split)
-    ntile = sum((B * h * w + 127) // 128 for (h, w) in sizes)
+    geo = (B, sizes, dtype, dev, sum((B * h * w + 127) // 128 for (h, w) in sizes))
+    douts = {'cls': (dcls_logit, nc, dcls_ld), 'reg': (dreg, 4, dreg_ld)}      # tower -> (gradient, values per anchor, its pixel-major ld)
 
-    def lv(tower, kind, r):
-        return live[kind][r] if (live is not None and tower == 'reg') else None
+    def lv(towers, kind, r):
+        return live[kind][r] if (live is not None and 'reg' in towers) else None
 
     def tower_final(tower, dout, per, pix_ld):
         """retina_cls / retina_reg: weight gradient + data gradient back into the tower (ReLU mask of its last layer fused) -> dz maps"""
@@ -714,7 +728,7 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
                 dzmaps = _split_rows(dzmaps, Cfp, dtype)
             elif Cfp != Cf:          # 9*num_classes (or 36) channels are not whole 16-byte chunks: zero-pad the rows
                 dzmaps = [ops.pad_rows(m, Cfp) for m in dzmaps]
-        G, dbp = ops.conv2d_wgrad(acts[tower][3], dzmaps, Cin=256, Cout=Cf, KH=3, KW=3, pad_t=1, pad_l=1, split=split, live32=lv(tower, 0, 0))
+        G, dbp = ops.conv2d_wgrad(acts[tower][3], dzmaps, Cin=256, Cout=Cf, **_K3, split=split, live32=lv((tower,), 0, 0))
         # (cls_gscale: the class-loss gradient was written for an upstream gradient of one -- the upstream scalar multiplies the
         #  slabs and bias partial rows inside the unpack, and the rows of the data gradient)
         gs = cls_gscale if tower == 'cls' else None
@@ -723,60 +737,41 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
         g[fin + '.weight'], g[fin + '.bias'] = dw, db
         # data gradient with the ReLU mask of the producing tower layer fused into the epilogue
         _, dz = pyramid_alloc(B, sizes, 256, dtype, dev)
-        ops.conv2d(dzmaps, ops.pack_weight(wf, dtype, mode=1, cin_pad=Cfp, x3=split), dz, Cin=Cfp, Cout=256, KH=3, KW=3, pad_t=1,
-                   pad_l=1, res=acts[tower][3], res_mode=RES_RELU_MASK, rowscale=rows, split=split, live=lv(tower, 1, 1))
+        ops.conv2d(dzmaps, ops.pack_weight(wf, dtype, mode=1, cin_pad=Cfp, x3=split), dz, Cin=Cfp, Cout=256, **_K3, res=acts[tower][3],
+                   res_mode=RES_RELU_MASK, rowscale=rows, split=split, live=lv((tower,), 1, 1))
         return dz
 
-    def layer_wgrad(tower, t, dz):
-        w = HP[f'{tower}_convs.{t}.weight']
-        xin = acts[tower][t - 1] if t > 0 else p
-        G, dbp = ops.conv2d_wgrad(xin, dz, Cin=w.shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1, split=split, live32=lv(tower, 0, 4 - t))
-        dw = torch.empty_like(w); db = ops.unpack_wgrad(G, dw, dbias_part=dbp)
-        g[f'{tower}_convs.{t}.weight'], g[f'{tower}_convs.{t}.bias'] = dw, db
-
-    def layer_wgrad_pair(t, dz_cls, dz_reg):
-        """layer t of both towers: the dense classification problem and the (flagged) regression problem in one launch"""
-        ws = [HP[f'{tw}_convs.{t}.weight'] for tw in ('cls', 'reg')]
-        xin = [acts[tw][t - 1] if t > 0 else p for tw in ('cls', 'reg')]
-        res = ops.conv2d_wgrad_pair(xin[0], dz_cls, xin[1], dz_reg, Cin=ws[0].shape[1], Cout=256, KH=3, KW=3, pad_t=1, pad_l=1,
-                                    live32_b=lv('reg', 0, 4 - t))
-        for tw, w, (G, dbp) in reversed(list(zip(('cls', 'reg'), ws, res))):      # (unpack jobs in the order of the separate launches)
-            dw = torch.empty_like(w); db = ops.unpack_wgrad(G, dw, dbias_part=dbp)
+    def layer_wgrads(group, t, dz):
+        """weight gradients of layer t of the group's towers, `reg` first; both towers with HEAD_PAIR_WGRAD: the dense classification
+        problem and the (flagged) regression problem in one launch, unpacked in the order of the separate launches"""
+        w = {tw: HP[f'{tw}_convs.{t}.weight'] for tw in group}
+        xin = {tw: acts[tw][t - 1] if t > 0 else p for tw in group}
+        both = None
+        if len(group) == 2 and HEAD_PAIR_WGRAD:
+            a, b = group
+            both = dict(zip(group, ops.conv2d_wgrad_pair(xin[a], dz[a], xin[b], dz[b], Cin=w[a].shape[1], Cout=256, **_K3,
+                                                         live32_b=lv((b,), 0, 4 - t))))
+        for tw in reversed(group):
+            G, dbp = both[tw] if both else ops.conv2d_wgrad(xin[tw], dz[tw], Cin=w[tw].shape[1], Cout=256, **_K3, split=split,
+                                                            live32=lv((tw,), 0, 4 - t))
+            dw = torch.empty_like(w[tw]); db = ops.unpack_wgrad(G, dw, dbias_part=dbp)
             g[f'{tw}_convs.{t}.weight'], g[f'{tw}_convs.{t}.bias'] = dw, db
 
-    def tower_bwd(tower, dout, per, pix_ld):
-        dz = tower_final(tower, dout, per, pix_ld)
+    def towers_bwd(group):
+        """the output convs of the group's towers, `reg` first, then per layer the weight gradient(s) and ONE data-gradient launch"""
+        dz = {tw: tower_final(tw, *douts[tw]) for tw in reversed(group)}
         for t in range(3, -1, -1):
-            layer_wgrad(tower, t, dz)
-            wd = ops.pack_weight(HP[f'{tower}_convs.{t}.weight'], dtype, mode=1, x3=split)
+            layer_wgrads(group, t, dz)
+            wd = {tw: ops.pack_weight(HP[f'{tw}_convs.{t}.weight'], dtype, mode=1, x3=split) for tw in group}
             if t > 0:
-                _, nz = pyramid_alloc(B, sizes, 256, dtype, dev)
-                ops.conv2d(dz, wd, nz, Cin=256, Cout=256, KH=3, KW=3, pad_t=1, pad_l=1, res=acts[tower][t - 1],
-                           res_mode=RES_RELU_MASK, split=split, live=lv(tower, 1, 5 - t))
-                dz = nz
+                dz, _ = _tower_layer(group, dz, wd, geo, 256, res={tw: acts[tw][t - 1] for tw in group}, res_mode=RES_RELU_MASK,
+                                     split=split, live=lv(group, 1, 5 - t))
             else:
-                last[tower] = (dz, wd)                  # 256 -> Wc back to the neck: after the join (the towers' sum)
+                for tw in group:
+                    last[tw] = (dz[tw], wd[tw])     # 256 -> Wc back to the neck: after the join (the towers' sum)
 
-    if paired:
-        # both towers in lockstep: the weight gradients of layer t run as ONE launch for both towers (HEAD_PAIR_WGRAD; off: one per tower)
-        # and so do the 256 -> 256 data gradients (head_fwd's pairing, same reason: 10.66 rounds of tiles instead of twice 5.33)
-        dzs = {'reg': tower_final('reg', dreg, 4, dreg_ld), 'cls': tower_final('cls', dcls_logit, nc, dcls_ld)}
-        L5 = len(sizes)
-        for t in range(3, -1, -1):
-            if HEAD_PAIR_WGRAD:
-                layer_wgrad_pair(t, dzs['cls'], dzs['reg'])
-            else:
-                for tw in ('reg', 'cls'):
-                    layer_wgrad(tw, t, dzs[tw])
-            wd2 = [ops.pack_weight(HP[f'{tw}_convs.{t}.weight'], dtype, mode=1, x3=split) for tw in ('cls', 'reg')]
-            if t > 0:
-                _, na, nb = pyramid_alloc_pair(B, sizes, 256, dtype, dev)
-                ops.conv2d(dzs['cls'] + dzs['reg'], wd2[0], na + nb, Cin=256, Cout=256, KH=3, KW=3, pad_t=1, pad_l=1,
-                           res=acts['cls'][t - 1] + acts['reg'][t - 1], res_mode=RES_RELU_MASK, split=split,
-                           seg_w=[wd2[0]] * L5 + [wd2[1]] * L5, live=lv('reg', 1, 5 - t), live_tile0=ntile if live is not None else 0)
-                dzs = {'cls': na, 'reg': nb}
-            else:
-                last['cls'], last['reg'] = (dzs['cls'], wd2[0]), (dzs['reg'], wd2[1])
+    if paired and split:          # the forward laid both towers' activations out pairwise: both towers in lockstep
+        towers_bwd(('cls', 'reg'))
     else:
         # (the two towers on two streams, see HEAD_TWO_STREAMS: the deferred unpack jobs of both leave in the node's ONE tail launch, on
         #  the main stream, after the join -- hence no early flush in between)
@@ -785,15 +780,14 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
         try:
             with _Fork(dev, two) as fk:
                 with fk.side():
-                    tower_bwd('reg', dreg, 4, dreg_ld)
-                tower_bwd('cls', dcls_logit, nc, dcls_ld)
+                    towers_bwd(('reg',))
+                towers_bwd(('cls',))
         finally:
             ops.hold_tail_flush(False)
     # back to plain fp32 for the neck (out_f32 in the split form): the first tower writes, the second accumulates onto it
     _, dp_maps = pyramid_alloc(B, sizes, Wc, dtype, dev)
     dz, wd = last['cls']
-    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, KH=3, KW=3, pad_t=1, pad_l=1, split=split, out_f32=split)
+    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, **_K3, split=split, out_f32=split)
     dz, wd = last['reg']
-    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, KH=3, KW=3, pad_t=1, pad_l=1, res=dp_maps, res_mode=RES_ADD, split=split, out_f32=split,
-               live=lv('reg', 1, 5))
+    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, **_K3, res=dp_maps, res_mode=RES_ADD, split=split, out_f32=split, live=lv(('reg',), 1, 5))
     return dp_maps, g
