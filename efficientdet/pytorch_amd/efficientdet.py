@@ -242,7 +242,7 @@ class _MBConvFn(torch.autograd.Function):
     def _bwd(ctx, dy):
         with ops.unpack_batch():                                   # the node's weight-gradient unpacks leave as one launch
             dx, g = Fn.mbconv_bwd(ctx.saved, Map.of(dy.contiguous()))
-        if ctx.saved['blk'].expand == 1 and ctx.saved['blk'].skip:
+        if ctx.saved.blk.expand == 1 and ctx.saved.blk.skip:
             ops.add_inplace(dx, Map.of(dy.contiguous()))
         keys = ctx.keys
         if ctx.link is not None:

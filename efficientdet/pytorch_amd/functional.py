@@ -122,115 +122,180 @@ def stem_bwd(saved, dy, dy_is_dz=False):
 
 
 # ------------------------------------------------------------------------------------------ MBConv
-def mbconv_fwd(x, blk, P, dtype, train, rowscale=None, xpre=None, in_act=ACT_NONE):
-    """models/efficientnet.py:75-105.  P: dict of parameter / buffer tensors of the block.
-    rowscale: optional [B] fp32 = drop_connect keep-mask / keep_prob (models/utils.py:79-90).
-    in_act=ACT_SWISH (expand == 1 blocks only, with xpre = x): x is the producer's PRE-activation (stem_fwd z_only) -- stated by the
-    caller, never inferred."""
-    assert in_act == ACT_NONE or (blk.expand == 1 and xpre is x)
-    dev = x.t.device
-    B, H, W = x.B, x.H, x.W
-    sv = {'x': x, 'blk': blk, 'P': P, 'rowscale': rowscale, 'xpre': xpre}      # xpre: see mbconv_bwd (expand == 1 blocks)
-    dw_in_act = ACT_NONE
-    Ho, Wo = conv_out(H, blk.k, blk.stride, blk.pad), conv_out(W, blk.k, blk.stride, blk.pad)
-    # (measured per block, D0 B = 32 @512, expand + depthwise -> fused: k3/s2 Cin 16 492 -> 335 us, k3/s1 Cin 24 267 -> 216; but
-    #  k5/s2 Cin 24 224 -> 333, k5/s1 Cin 40 157 -> 168, k3/s2 Cin 40 107 -> 143: the k = 5 tiles leave one workgroup per CU and at
-    #  Cin = 40 the expand's MFMA work outweighs the bytes saved -- so only the k = 3, Cin <= 32 blocks take it)
-    fuse = (not train and FUSE_EXPAND_DW and blk.expand != 1 and dtype == torch.float32 and blk.k == 3 and blk.cin in FUSE_CIN
-            and x.ld == x.C and x.off == 0)
-    if fuse:
-        s0, t0, i0 = ops.bn_fold(P['bn0.weight'], P['bn0.bias'], P['bn0.running_mean'], P['bn0.running_var'], BN_EPS)
-        xe = None            # (the 6x-expanded map exists only tile by tile, in LDS: see ops.expand_dw_fwd)
-    elif blk.expand != 1:
-        s0, t0, i0 = ops.bn_fold(P['bn0.weight'], P['bn0.bias'], P['bn0.running_mean'], P['bn0.running_var'], BN_EPS)
-        if train and EXPAND_Z_ONLY and Ho * Wo > 64:      # (<= 8x8 maps: the direct weight-gradient kernel would Swish every tap load)
-            # training stores ONE tensor for the expand conv, its pre-activation: the depthwise forward / weight-gradient kernels
-            # Swish their staged tiles (the two streams y_e, z_e were 35 % of the backbone's forward writes)
-            ze = Map.new(B, H, W, blk.cexp, dtype, dev)
-            ops.conv2d(x, ops.pack_weight(P['expand.weight'], dtype), ze, Cin=blk.cin, Cout=blk.cexp, KH=1, KW=1,
-                       scale=s0, shift=t0, act=ACT_NONE)
-            xe, dw_in_act = ze, ACT_SWISH
-        else:
-            xe = Map.new(B, H, W, blk.cexp, dtype, dev)
-            ze = Map.new(B, H, W, blk.cexp, dtype, dev) if train else None
-            ops.conv2d(x, ops.pack_weight(P['expand.weight'], dtype), xe, Cin=blk.cin, Cout=blk.cexp, KH=1, KW=1,
-                       scale=s0, shift=t0, act=ACT_SWISH, zs=ze)
-        sv.update(s0=s0, i0=i0, ze=ze)
+# A block's path is chosen once, by mbconv_path (forward) and mbconv_bwd_path (backward): nothing else reads the switches above, and the
+# stages below branch on the records alone.  DESIGN.md section 3 has the table of gate forms and the backward's reaction to each.
+# MBConvPath.expand -- how the expand conv runs
+EXPAND_NONE = 'none'      # expand == 1: the depthwise conv reads the block input
+EXPAND_IN_DW = 'in_dw'    # inference: inside the depthwise kernel (ops.expand_dw_fwd)
+EXPAND_Z = 'z'            # training: it stores its pre-activation only, the depthwise kernels Swish their staged tiles
+EXPAND_YZ = 'yz'          # it stores its output and, in training, its pre-activation
+# MBConvPath.gate -- what the depthwise forward stores and how the squeeze-excite gate reaches the project conv
+GATE_WEIGHTS = 'weights'          # x_d (+ z_d in training) stored; the gate rides in per-image project weights
+GATE_OPERAND = 'operand'          # z_d stored; the project conv and its weight gradient form swish(z_d) * gate in their operand registers
+GATE_XS_FROM_ZD = 'xs_from_zd'    # z_d stored; xs = channel_scale(z_d, gate, swish) is materialised
+GATE_XS_FROM_XD = 'xs_from_xd'    # x_d (+ z_d in training) stored; xs = channel_scale(x_d, gate) is materialised
+# the forward path of one block.  dw_in_act: ACT_SWISH = the depthwise conv's input is a pre-activation that it Swishes itself
+MBConvPath = collections.namedtuple('MBConvPath', 'expand dw_in_act gate')
+# the backward's choices.  se_fused: the fused squeeze-excite backward, else the se_dgate / se_bwd_apply chain; gate: the form the project
+# conv's weight gradient takes (GATE_OPERAND: if its planner accepts); xs_from: None = the forward kept xs, 'xd' / 'zd' = a switch changed
+# since the forward (or the chain runs) and xs is materialised first, from that tensor; ask_*: whether to ask the fused kernel at all
+MBConvBwdPath = collections.namedtuple('MBConvBwdPath', 'se_fused gate xs_from ask_pw_dgrad_se ask_dw_bwd ask_pw_bwd')
+# what mbconv_fwd hands mbconv_bwd.  A field that a path does not produce is None (s0 / i0 / ze with expand == 1, xd with z-only storage,
+# xs where it was never materialised, xpre without a producer's pre-activation)
+MBConvSaved = collections.namedtuple('MBConvSaved', 'path blk P x rowscale xpre s0 i0 ze xe s1 i1 wk xd zd pool gate mid xs s2 i2 inv_hw')
+
+
+def mbconv_path(blk, x, dtype, train, in_act):
+    """The forward path of one block -- the only reader of the forward switches.  GATE_OPERAND is subject to the two planners, which
+    need the operands: mbconv_gate_settled, in the project stage."""
+    hw = conv_out(x.H, blk.k, blk.stride, blk.pad) * conv_out(x.W, blk.k, blk.stride, blk.pad)
+    f32 = dtype == torch.float32
+    if blk.expand == 1:
+        expand, dw_in_act = EXPAND_NONE, in_act      # ACT_SWISH: the producer (the stem) handed its pre-activation ONLY (stem_fwd z_only)
+    elif not train and FUSE_EXPAND_DW and f32 and blk.k == 3 and blk.cin in FUSE_CIN and x.ld == x.C and x.off == 0:
+        # (measured per block, D0 B = 32 @512, expand + depthwise -> fused: k3/s2 Cin 16 492 -> 335 us, k3/s1 Cin 24 267 -> 216; but
+        #  k5/s2 Cin 24 224 -> 333, k5/s1 Cin 40 157 -> 168, k3/s2 Cin 40 107 -> 143: the k = 5 tiles leave one workgroup per CU and at
+        #  Cin = 40 the expand's MFMA work outweighs the bytes saved -- so only the k = 3, Cin <= 32 blocks take it)
+        expand, dw_in_act = EXPAND_IN_DW, ACT_NONE
+    elif train and EXPAND_Z_ONLY and hw > 64:          # (<= 8x8 maps: the direct weight-gradient kernel would Swish every tap load)
+        # training stores ONE tensor for the expand conv, its pre-activation: the depthwise forward / weight-gradient kernels
+        # Swish their staged tiles (the two streams y_e, z_e were 35 % of the backbone's forward writes)
+        expand, dw_in_act = EXPAND_Z, ACT_SWISH
     else:
-        xe = x
-        dw_in_act = in_act          # ACT_SWISH: the producer (the stem) handed its pre-activation ONLY (stem_fwd z_only)
-    s1, t1, i1 = ops.bn_fold(P['bn1.weight'], P['bn1.bias'], P['bn1.running_mean'], P['bn1.running_var'], BN_EPS)
-    wk = ops.dw_pack_weight(P['dw.weight'])
+        expand, dw_in_act = EXPAND_YZ, ACT_NONE
     # training stores the depthwise pre-activation ONLY (the step is bound by HBM write bandwidth, ~2.5 TB/s measured):
     # the gate multiply and the backward of the gate recompute Swish from it
     # gate in per-image project weights (round 4): inference always; training when the fused SE backward applies (it takes the
     # project conv's weight gradient per image, which is where the gate re-enters) -- the depthwise conv then stores BOTH its
     # pre-activation (backward) and its Swish output (the project conv's operand) and channel_scale's read + write pass is gone
-    giw = GATE_IN_WEIGHTS and (Ho * Wo) % 128 == 0 and (not train or (
-        GATE_IN_WEIGHTS_TRAIN and SE_FUSED and dtype == torch.float32 and (Ho * Wo) % 32 == 0))
-    z_only = train and not DW_SAVE_Y and not giw
-    if fuse:
+    if GATE_IN_WEIGHTS and hw % 128 == 0 and (not train or (GATE_IN_WEIGHTS_TRAIN and SE_FUSED and f32 and hw % 32 == 0)):
+        gate = GATE_WEIGHTS
+    elif not train or DW_SAVE_Y:
+        gate = GATE_XS_FROM_XD
+    elif GATE_IN_OPERAND and f32 and SE_FUSED and hw >= GATE_OPERAND_MIN_HW:
+        gate = GATE_OPERAND
+    else:
+        gate = GATE_XS_FROM_ZD
+    return MBConvPath(expand, dw_in_act, gate)
+
+
+def mbconv_gate_settled(path, zd, wpp, y, gate, pkw):
+    """`path` with the planners' answer in it: the gate stays in the operand only if both readers of xs take the form (exact-fp32 launch,
+    whole 128-pixel tiles per image, per-image splits on the thin / DMA-staged weight-gradient kernels), else xs is materialised as
+    before.  pkw: the project conv's keyword arguments."""
+    if path.gate != GATE_OPERAND or (ops.conv2d_gated_ok(zd, wpp, y, gate, ACT_SWISH, **pkw)
+                                     and ops.conv2d_wgrad_gated_ok(zd, y, gate, ACT_SWISH, Cin=pkw['Cin'], Cout=pkw['Cout'])):
+        return path
+    return path._replace(gate=GATE_XS_FROM_ZD)
+
+
+def mbconv_bwd_path(path, dtype, hw):
+    """The backward's choices for a block whose forward took `path`, on maps of `hw` pixels per image -- the only reader of the backward
+    switches, read when the backward runs (a switch may have changed since the forward: tests do that)."""
+    f32 = dtype == torch.float32
+    se_fused = SE_FUSED and hw % (64 if dtype == torch.bfloat16 else 32) == 0
+    if path.gate == GATE_WEIGHTS:         # the forward ran on W diag(gate_b) and x_d; only the fused form takes the gate back in its unpack
+        gate, xs_from = (GATE_WEIGHTS, None) if se_fused else (GATE_XS_FROM_XD, 'xd')
+    elif path.gate == GATE_OPERAND:       # the forward kept no xs: the fused form takes z_d + the gate, anything else the same values as xs
+        gate, xs_from = (GATE_OPERAND if GATE_IN_OPERAND and se_fused else GATE_XS_FROM_ZD), 'zd'
+    else:
+        gate, xs_from = path.gate, None
+    return MBConvBwdPath(se_fused, gate, xs_from, ask_pw_dgrad_se=se_fused and PW_DGRAD_SE and f32,
+                         ask_dw_bwd=DW_BWD_FUSED and path.dw_in_act == ACT_SWISH and f32,
+                         ask_pw_bwd=path.expand != EXPAND_NONE and PW_BWD_FUSED and f32)
+
+
+def _mbconv_expand_fwd(path, x, blk, P, dtype, train):
+    """-> (xe, ze, s0, t0, i0): the depthwise conv's input, the expand conv's stored pre-activation, its folded BN"""
+    if path.expand == EXPAND_NONE:
+        return x, None, None, None, None
+    s0, t0, i0 = ops.bn_fold(P['bn0.weight'], P['bn0.bias'], P['bn0.running_mean'], P['bn0.running_var'], BN_EPS)
+    if path.expand == EXPAND_IN_DW:
+        return None, None, s0, t0, i0       # (the 6x-expanded map exists only tile by tile, in LDS: see ops.expand_dw_fwd)
+    dev = x.t.device
+    if path.expand == EXPAND_Z:
+        ze = Map.new(x.B, x.H, x.W, blk.cexp, dtype, dev)
+        ops.conv2d(x, ops.pack_weight(P['expand.weight'], dtype), ze, Cin=blk.cin, Cout=blk.cexp, KH=1, KW=1,
+                   scale=s0, shift=t0, act=ACT_NONE)
+        return ze, ze, s0, t0, i0
+    xe = Map.new(x.B, x.H, x.W, blk.cexp, dtype, dev)
+    ze = Map.new(x.B, x.H, x.W, blk.cexp, dtype, dev) if train else None
+    ops.conv2d(x, ops.pack_weight(P['expand.weight'], dtype), xe, Cin=blk.cin, Cout=blk.cexp, KH=1, KW=1,
+               scale=s0, shift=t0, act=ACT_SWISH, zs=ze)
+    return xe, ze, s0, t0, i0
+
+
+def _mbconv_dw_se_fwd(path, x, xe, s0, t0, blk, P, train):
+    """Depthwise conv (with the expand conv inside it on EXPAND_IN_DW) + squeeze-excite gate
+    -> (xd, zd, wk, s1, i1, gate, mid, pool, inv_hw)"""
+    Ho, Wo = conv_out(x.H, blk.k, blk.stride, blk.pad), conv_out(x.W, blk.k, blk.stride, blk.pad)
+    s1, t1, i1 = ops.bn_fold(P['bn1.weight'], P['bn1.bias'], P['bn1.running_mean'], P['bn1.running_var'], BN_EPS)
+    wk = ops.dw_pack_weight(P['dw.weight'])
+    if path.expand == EXPAND_IN_DW:
         xd, pool_part = ops.expand_dw_fwd(x, P['expand.weight'], s0, t0, wk, s1, t1, blk.k, blk.stride, blk.pad[0], blk.pad[0], Ho, Wo)
         zd = None
     else:
         xd, zd, pool_part = ops.dwconv_fwd(xe, wk, s1, t1, blk.k, blk.stride, blk.pad[0], blk.pad[0], Ho, Wo, save_z=train, pool=True,
-                                           save_y=not z_only, in_act=dw_in_act)
+                                           save_y=path.gate in (GATE_WEIGHTS, GATE_XS_FROM_XD), in_act=path.dw_in_act)
     inv_hw = 1.0 / (Ho * Wo)
     w1 = P['se_reduce.weight'].view(blk.cse, blk.cexp); w2 = P['se_expand.weight'].view(blk.cexp, blk.cse)
     gate, mid, pool = ops.se_gate_fwd(pool_part, w1, P['se_reduce.bias'], w2, P['se_expand.bias'], inv_hw, save_mid=train)
+    return xd, zd, wk, s1, i1, gate, mid, pool, inv_hw
+
+
+def _mbconv_project_fwd(path, x, xd, zd, gate, blk, P, dtype, rowscale):
+    """Project conv with the gate in the form `path` names (+ drop_connect scale and identity skip in its epilogue)
+    -> (y, xs, s2, i2, path with the planners' answer)"""
+    Ho, Wo = conv_out(x.H, blk.k, blk.stride, blk.pad), conv_out(x.W, blk.k, blk.stride, blk.pad)
     s2, t2, i2 = ops.bn_fold(P['bn2.weight'], P['bn2.bias'], P['bn2.running_mean'], P['bn2.running_var'], BN_EPS)
-    y = Map.new(B, Ho, Wo, blk.cout, dtype, dev)
-    if giw:
+    y = Map.new(x.B, Ho, Wo, blk.cout, dtype, x.t.device)
+    pkw = dict(Cin=blk.cexp, Cout=blk.cout, KH=1, KW=1, scale=s2, shift=t2, act=ACT_NONE, rowscale=rowscale if blk.skip else None,
+               res=x if blk.skip else None, res_mode=RES_ADD if blk.skip else RES_NONE)
+    if path.gate == GATE_WEIGHTS:
         # y = (W diag(gate_b)) x_d -- the gate rides in per-image project weights (a few MB for the whole batch) instead of
         # a read + write pass over the expanded map (16 channel_scale launches moved 3.2 GB per D0 B = 32 forward: 5 % of it)
-        xs = None
         wpb, wstride = ops.scale_pack_weight(P['project.weight'], gate, dtype)
-        ops.conv2d(xd, wpb, y, Cin=blk.cexp, Cout=blk.cout, KH=1, KW=1, scale=s2, shift=t2, act=ACT_NONE,
-                   rowscale=rowscale if blk.skip else None,
-                   res=x if blk.skip else None, res_mode=RES_ADD if blk.skip else RES_NONE, w_image_stride=wstride)
+        ops.conv2d(xd, wpb, y, w_image_stride=wstride, **pkw)
+        return y, None, s2, i2, path
+    wpp = ops.pack_weight(P['project.weight'], dtype)
+    path = mbconv_gate_settled(path, zd, wpp, y, gate, pkw)
+    if path.gate == GATE_OPERAND:
+        xs = None
+        ops.conv2d(zd, wpp, y, a_gate=gate, a_act=ACT_SWISH, **pkw)
     else:
-        wpp = ops.pack_weight(P['project.weight'], dtype)
-        pkw = dict(Cin=blk.cexp, Cout=blk.cout, KH=1, KW=1, scale=s2, shift=t2, act=ACT_NONE, rowscale=rowscale if blk.skip else None,
-                   res=x if blk.skip else None, res_mode=RES_ADD if blk.skip else RES_NONE)
-        # gate in the operand: both readers of xs must take the form (the planners say: exact-fp32 launch, whole 128-pixel tiles per image,
-        # per-image splits on the thin / DMA-staged weight-gradient kernels), else xs is materialised as before
-        gio = (GATE_IN_OPERAND and z_only and dtype == torch.float32 and SE_FUSED and Ho * Wo >= GATE_OPERAND_MIN_HW
-               and ops.conv2d_gated_ok(zd, wpp, y, gate, ACT_SWISH, **pkw)
-               and ops.conv2d_wgrad_gated_ok(zd, y, gate, ACT_SWISH, Cin=blk.cexp, Cout=blk.cout))
-        if gio:
-            xs = None
-            ops.conv2d(zd, wpp, y, a_gate=gate, a_act=ACT_SWISH, **pkw)
-        else:
-            xs = ops.channel_scale(zd, gate, ACT_SWISH) if z_only else ops.channel_scale(xd, gate)
-            ops.conv2d(xs, wpp, y, **pkw)
-    if train:
-        sv.update(xe=xe, s1=s1, i1=i1, wk=wk, xd=xd, zd=zd, pool=pool, gate=gate, mid=mid, xs=xs, s2=s2, i2=i2,
-                  inv_hw=inv_hw, dw_in_act=dw_in_act, giw=giw)
-    return y, sv
+        xs = ops.channel_scale(zd, gate, ACT_SWISH) if path.gate == GATE_XS_FROM_ZD else ops.channel_scale(xd, gate)
+        ops.conv2d(xs, wpp, y, **pkw)
+    return y, xs, s2, i2, path
 
 
-def mbconv_bwd(sv, dy):
-    """-> (dx Map, grads dict keyed like P)."""
-    blk, P, x = sv['blk'], sv['P'], sv['x']
-    dtype, dev = x.dtype, x.t.device
-    B, H, W = x.B, x.H, x.W
+def mbconv_fwd(x, blk, P, dtype, train, rowscale=None, xpre=None, in_act=ACT_NONE):
+    """models/efficientnet.py:75-105.  P: dict of parameter / buffer tensors of the block.
+    rowscale: optional [B] fp32 = drop_connect keep-mask / keep_prob (models/utils.py:79-90).
+    in_act=ACT_SWISH (expand == 1 blocks only, with xpre = x): x is the producer's PRE-activation (stem_fwd z_only) -- stated by the
+    caller, never inferred.  -> (y Map, MBConvSaved)"""
+    assert in_act == ACT_NONE or (blk.expand == 1 and xpre is x)
+    path = mbconv_path(blk, x, dtype, train, in_act)
+    xe, ze, s0, t0, i0 = _mbconv_expand_fwd(path, x, blk, P, dtype, train)
+    xd, zd, wk, s1, i1, gate, mid, pool, inv_hw = _mbconv_dw_se_fwd(path, x, xe, s0, t0, blk, P, train)
+    y, xs, s2, i2, path = _mbconv_project_fwd(path, x, xd, zd, gate, blk, P, dtype, rowscale)
+    return y, MBConvSaved(path, blk, P, x, rowscale, xpre, s0, i0, ze, xe, s1, i1, wk, xd, zd, pool, gate, mid, xs, s2, i2, inv_hw)
+
+
+def _mbconv_project_se_bwd(bp, sv, dy):
+    """Project conv (+ drop_connect scale on the branch) + squeeze-excite backward -> (dz_d Map, their gradients keyed like P)"""
+    blk, P = sv.blk, sv.P
+    dtype, dev = sv.x.dtype, sv.x.t.device
+    B, Ce, Co, Cs = sv.x.B, blk.cexp, blk.cout, blk.cse
     g = {}
-    Ce, Co, Ci, Cs, kk = blk.cexp, blk.cout, blk.cin, blk.cse, blk.k * blk.k
-    # ---- project conv (+ drop_connect scale on the branch) + squeeze-excite backward ----
-    rs = sv['rowscale'] if blk.skip else None
+    rs = sv.rowscale if blk.skip else None
     wp = P['project.weight']
     w1 = P['se_reduce.weight'].view(Cs, Ce); w2 = P['se_expand.weight'].view(Ce, Cs)
-    hw = dy.H * dy.W
-    giw = sv.get('giw', False)
-    if giw and not (SE_FUSED and hw % 32 == 0):       # (the switch was flipped between forward and backward: tests do that)
-        sv['xs'] = ops.channel_scale(sv['xd'], sv['gate']); giw = False
-    # gate in the operand (the forward kept no xs): the fused branch below takes z_d + the gate; with the switch flipped since the forward,
-    # or on the un-fused branch, xs is materialised first -- the same values either way
-    gio = (not giw and sv['xs'] is None and GATE_IN_OPERAND and SE_FUSED and hw % 32 == 0 and dtype == torch.float32
-           and ops.conv2d_wgrad_gated_ok(sv['zd'], dy, sv['gate'], ACT_SWISH, Cin=Ce, Cout=Co))
-    if not giw and sv['xs'] is None and not gio:
-        sv['xs'] = ops.channel_scale(sv['zd'], sv['gate'], ACT_SWISH)
-    if SE_FUSED and hw % (64 if dtype == torch.bfloat16 else 32) == 0:
+    form, xs = bp.gate, sv.xs
+    if form == GATE_OPERAND and not ops.conv2d_wgrad_gated_ok(sv.zd, dy, sv.gate, ACT_SWISH, Cin=Ce, Cout=Co):
+        form = GATE_XS_FROM_ZD
+    if bp.xs_from is not None and form != GATE_OPERAND:       # the same values as the forward's xs either way
+        xs = ops.channel_scale(sv.xd, sv.gate) if bp.xs_from == 'xd' else ops.channel_scale(sv.zd, sv.gate, ACT_SWISH)
+    if bp.se_fused:
         # Fused form (no pass over the activations for the gate gradient, dxs never materialised):
         #   per-image partial weight gradients M_b = dy_b^T xs_b (split-K on image boundaries)
         #   dW = sum_b rs_b M_b (slab scale in the unpack);  (dgate*gate)[b][c] = rs_b sum_n W'[n][c] M_b[n][c]
@@ -238,64 +303,88 @@ def mbconv_bwd(sv, dy):
         # -- se_dgate (2 tensor reads), se_bwd_apply (2 reads + 1 write) and the drop_connect act_bwd become one extra read of z_d.
         # (giw: the forward ran on W diag(gate_b) and x_d; the slabs are then M'_b = dy_b^T x_d,b -- the gate re-enters as a per-(image,
         #  channel) factor of the unpack, and sum_n W'[n][c] M'_b[n][c] is d(loss)/d(gate) itself, not yet times the gate)
-        if gio:
-            G2, dsum2 = ops.conv2d_wgrad(sv['zd'], dy, Cin=Ce, Cout=Co, KH=1, KW=1, image_splits=True, a_gate=sv['gate'], a_act=ACT_SWISH)
+        giw = form == GATE_WEIGHTS
+        if form == GATE_OPERAND:
+            G2, dsum2 = ops.conv2d_wgrad(sv.zd, dy, Cin=Ce, Cout=Co, KH=1, KW=1, image_splits=True, a_gate=sv.gate, a_act=ACT_SWISH)
         else:
-            G2, dsum2 = ops.conv2d_wgrad(sv['xd'] if giw else sv['xs'], dy, Cin=Ce, Cout=Co, KH=1, KW=1, image_splits=True)
-        g['project.weight'], g['bn2.weight'], g['bn2.bias'] = ops.unpack_wgrad_bn(G2, wp, sv['s2'], dsum2, P['bn2.running_mean'], sv['i2'],
-                                                                                 slab_scale=rs, slab_cscale=sv['gate'] if giw else None)
-        dgg = ops.se_dgate_from_wgrad(G2, wp, sv['s2'], rs, B)
-        dpool, dw1, db1, dw2, db2 = ops.se_gate_bwd(dgg, sv['gate'], sv['mid'], sv['pool'], w1, P['se_reduce.bias'], w2,
-                                                    sv['inv_hw'], times_gate=not giw)
+            G2, dsum2 = ops.conv2d_wgrad(sv.xd if giw else xs, dy, Cin=Ce, Cout=Co, KH=1, KW=1, image_splits=True)
+        g['project.weight'], g['bn2.weight'], g['bn2.bias'] = ops.unpack_wgrad_bn(G2, wp, sv.s2, dsum2, P['bn2.running_mean'], sv.i2,
+                                                                                 slab_scale=rs, slab_cscale=sv.gate if giw else None)
+        dgg = ops.se_dgate_from_wgrad(G2, wp, sv.s2, rs, B)
+        dpool, dw1, db1, dw2, db2 = ops.se_gate_bwd(dgg, sv.gate, sv.mid, sv.pool, w1, P['se_reduce.bias'], w2, sv.inv_hw,
+                                                    times_gate=not giw)
         # the high-resolution blocks (Co 16 / 24 / 40 over >= 64 k pixels): a streaming kernel of its own (round 6)
-        dzd = ops.pw_dgrad_se(dy, wp, sv['s2'], rs, sv['gate'], dpool, sv['zd']) if PW_DGRAD_SE and dtype == torch.float32 else None
+        dzd = ops.pw_dgrad_se(dy, wp, sv.s2, rs, sv.gate, dpool, sv.zd) if bp.ask_pw_dgrad_se else None
         if dzd is None:
             dzd = Map.new(B, dy.H, dy.W, Ce, dtype, dev)
-            ops.conv2d(dy, ops.pack_weight(wp, dtype, mode=1, scale=sv['s2']), dzd, Cin=Co, Cout=Ce, KH=1, KW=1, rowscale=rs,
-                       bc_scale=sv['gate'], bc_shift=dpool, res=sv['zd'], res_mode=ops.RES_SWISH_GRAD)
+            ops.conv2d(dy, ops.pack_weight(wp, dtype, mode=1, scale=sv.s2), dzd, Cin=Co, Cout=Ce, KH=1, KW=1, rowscale=rs,
+                       bc_scale=sv.gate, bc_shift=dpool, res=sv.zd, res_mode=ops.RES_SWISH_GRAD)
     else:
         dz2 = ops.act_bwd(dy, None, ACT_NONE, rowscale=rs) if rs is not None else dy
-        G2, dsum2 = ops.conv2d_wgrad(sv['xs'], dz2, Cin=Ce, Cout=Co, KH=1, KW=1)
-        g['project.weight'], g['bn2.weight'], g['bn2.bias'] = ops.unpack_wgrad_bn(G2, wp, sv['s2'], dsum2, P['bn2.running_mean'], sv['i2'])
+        G2, dsum2 = ops.conv2d_wgrad(xs, dz2, Cin=Ce, Cout=Co, KH=1, KW=1)
+        g['project.weight'], g['bn2.weight'], g['bn2.bias'] = ops.unpack_wgrad_bn(G2, wp, sv.s2, dsum2, P['bn2.running_mean'], sv.i2)
         dxs = Map.new(B, dy.H, dy.W, Ce, dtype, dev)
-        ops.conv2d(dz2, ops.pack_weight(wp, dtype, mode=1, scale=sv['s2']), dxs, Cin=Co, Cout=Ce, KH=1, KW=1)
-        dgate = ops.se_dgate(dxs, sv['xd']) if sv['xd'] is not None else ops.se_dgate(dxs, sv['zd'], ACT_SWISH)
-        dpool, dw1, db1, dw2, db2 = ops.se_gate_bwd(dgate, sv['gate'], sv['mid'], sv['pool'], w1, P['se_reduce.bias'], w2,
-                                                    sv['inv_hw'])
-        dzd = ops.se_bwd_apply(dxs, sv['gate'], dpool, sv['zd'])
+        ops.conv2d(dz2, ops.pack_weight(wp, dtype, mode=1, scale=sv.s2), dxs, Cin=Co, Cout=Ce, KH=1, KW=1)
+        dgate = ops.se_dgate(dxs, sv.xd) if form == GATE_XS_FROM_XD else ops.se_dgate(dxs, sv.zd, ACT_SWISH)
+        dpool, dw1, db1, dw2, db2 = ops.se_gate_bwd(dgate, sv.gate, sv.mid, sv.pool, w1, P['se_reduce.bias'], w2, sv.inv_hw)
+        dzd = ops.se_bwd_apply(dxs, sv.gate, dpool, sv.zd)
     g['se_reduce.weight'], g['se_reduce.bias'] = dw1.view(Cs, Ce, 1, 1), db1
     g['se_expand.weight'], g['se_expand.bias'] = dw2.view(Ce, Cs, 1, 1), db2
-    # ---- depthwise ----
+    return dzd, g
+
+
+def _mbconv_dw_bwd(bp, sv, dzd):
+    """Depthwise conv backward -> (dz_e Map: the gradient of the depthwise conv's input, through the Swish of `zprev` where there is one,
+    its gradients keyed like P)"""
+    blk, P = sv.blk, sv.P
     # (expand == 1, i.e. block 0: the depthwise conv reads the block input itself; given the pre-activation `xpre` of the producer --
     #  the stem's z -- its Swish' is applied here, in the data gradient's epilogue, instead of a separate pass in the stem's backward)
-    zprev = sv.get('ze') if blk.expand != 1 else sv.get('xpre')
+    zprev = sv.ze if blk.expand != 1 else sv.xpre
     fused = None
-    if DW_BWD_FUSED and sv['dw_in_act'] == ACT_SWISH and zprev is sv['xe'] and dtype == torch.float32:
+    if bp.ask_dw_bwd:
         # z-only storage: the depthwise input IS swish(zprev) -- one kernel reads dz_d and zprev once for both gradients (round 6)
-        fused = ops.dwconv_bwd(dzd, sv['wk'], sv['s1'], zprev, blk.k, blk.stride, blk.pad[0], blk.pad[0])
+        assert zprev is sv.xe
+        fused = ops.dwconv_bwd(dzd, sv.wk, sv.s1, zprev, blk.k, blk.stride, blk.pad[0], blk.pad[0])
     if fused is not None:
         dze, gk, dsum1 = fused
     else:
-        gk, dsum1 = ops.dwconv_wgrad(sv['xe'], dzd, blk.k, blk.stride, blk.pad[0], blk.pad[0], in_act=sv['dw_in_act'])
-        dze = ops.dwconv_dgrad(dzd, sv['wk'], sv['s1'], zprev, H, W, blk.k, blk.stride, blk.pad[0], blk.pad[0])
-    g['dw.weight'], g['bn1.weight'], g['bn1.bias'] = ops.dw_unpack_wgrad_bn(gk, sv['s1'], P['dw.weight'], dsum1,
-                                                                             P['bn1.running_mean'], sv['i1'])
-    if blk.expand == 1:
-        return dze, g           # block 0: depthwise acts on the block input directly, no skip
-    # ---- expand conv; the identity-skip gradient is added in the data-gradient epilogue ----
+        gk, dsum1 = ops.dwconv_wgrad(sv.xe, dzd, blk.k, blk.stride, blk.pad[0], blk.pad[0], in_act=sv.path.dw_in_act)
+        dze = ops.dwconv_dgrad(dzd, sv.wk, sv.s1, zprev, sv.x.H, sv.x.W, blk.k, blk.stride, blk.pad[0], blk.pad[0])
+    g = {}
+    g['dw.weight'], g['bn1.weight'], g['bn1.bias'] = ops.dw_unpack_wgrad_bn(gk, sv.s1, P['dw.weight'], dsum1, P['bn1.running_mean'], sv.i1)
+    return dze, g
+
+
+def _mbconv_expand_bwd(bp, sv, dze, dy):
+    """Expand conv backward; the identity-skip gradient is added in the data-gradient epilogue -> (dx Map, its gradients keyed like P).
+    expand == 1 (block 0, no skip): the depthwise conv acted on the block input directly, dz_e is dx."""
+    if sv.path.expand == EXPAND_NONE:
+        return dze, {}
+    blk, P, x = sv.blk, sv.P, sv.x
+    Ce, Ci = blk.cexp, blk.cin
+    g = {}
     we = P['expand.weight']
-    fusedp = ops.pw_bwd(dze, x, we, sv['s0'], dy if blk.skip else None) if PW_BWD_FUSED and dtype == torch.float32 else None
+    fusedp = ops.pw_bwd(dze, x, we, sv.s0, dy if blk.skip else None) if bp.ask_pw_bwd else None
     if fusedp is not None:
         # the high-resolution blocks (Cin 16 / 24 / 32): both gradients of the expand conv from ONE read of the 6x-expanded gradient (round 6)
         dx, G0, dsum0 = fusedp
     else:
         G0, dsum0 = ops.conv2d_wgrad(x, dze, Cin=Ci, Cout=Ce, KH=1, KW=1)
-    g['expand.weight'], g['bn0.weight'], g['bn0.bias'] = ops.unpack_wgrad_bn(G0, we, sv['s0'], dsum0, P['bn0.running_mean'], sv['i0'])
+    g['expand.weight'], g['bn0.weight'], g['bn0.bias'] = ops.unpack_wgrad_bn(G0, we, sv.s0, dsum0, P['bn0.running_mean'], sv.i0)
     if fusedp is None:
-        dx = Map.new(B, H, W, Ci, dtype, dev)
-        ops.conv2d(dze, ops.pack_weight(we, dtype, mode=1, scale=sv['s0']), dx, Cin=Ce, Cout=Ci, KH=1, KW=1,
+        dx = Map.new(x.B, x.H, x.W, Ci, x.dtype, x.t.device)
+        ops.conv2d(dze, ops.pack_weight(we, x.dtype, mode=1, scale=sv.s0), dx, Cin=Ce, Cout=Ci, KH=1, KW=1,
                    res=dy if blk.skip else None, res_mode=RES_ADD if blk.skip else RES_NONE)
     return dx, g
+
+
+def mbconv_bwd(sv, dy):
+    """sv: the MBConvSaved of mbconv_fwd -> (dx Map, grads dict keyed like P)."""
+    bp = mbconv_bwd_path(sv.path, sv.x.dtype, dy.H * dy.W)
+    dzd, g2 = _mbconv_project_se_bwd(bp, sv, dy)
+    dze, g1 = _mbconv_dw_bwd(bp, sv, dzd)
+    dx, g0 = _mbconv_expand_bwd(bp, sv, dze, dy)
+    return dx, {**g2, **g1, **g0}
 
 
 # ------------------------------------------------------------------------------------------ BiFPN

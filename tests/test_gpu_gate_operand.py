@@ -117,7 +117,7 @@ def _mbconv_step(blk, P, x, dy, rs, on_fwd, on_bwd):
         with torch.no_grad():
             Fn.GATE_IN_OPERAND = on_fwd
             y, sv = Fn.mbconv_fwd(Map.of(x), blk, P, torch.float32, True, rs)
-            kept = sv['xs'] is not None
+            kept = sv.xs is not None
             Fn.GATE_IN_OPERAND = on_bwd
             dx, gr = Fn.mbconv_bwd(sv, Map.of(dy))
         torch.cuda.synchronize()
@@ -168,6 +168,44 @@ def test_one_block_forward_and_backward(on_bwd):
     assert _bits_equal(on[0], off[0]) and _bits_equal(on[1], off[1])
     assert on[2].keys() == off[2].keys()
     bad = [k for k in on[2] if not _bits_equal(on[2][k], off[2][k])]
+    assert not bad, bad
+
+
+def test_gate_in_weights_forward_then_chain_backward():
+    """The gate in per-image weights in the forward (GATE_IN_WEIGHTS_TRAIN), the fused squeeze-excite backward switched off before the
+    backward: mbconv_bwd materialises xs = channel_scale(xd, gate) and runs the chain.  Against DW_SAVE_Y on and SE_FUSED off throughout:
+    both backwards run the chain on the same xd, zd, gate, mid, pool, the same xs and the same dy, so dx and every parameter gradient are
+    torch.equal (the outputs y differ in rounding -- W diag(gate) against gate x -- and are not compared)."""
+    from efficientdet.pytorch_amd import functional as Fn
+    from efficientdet.pytorch_amd.ops import Map
+    g = torch.Generator().manual_seed(11)
+    blk = _block()
+    P = _block_params(blk, g)
+    x = torch.randn(2, 16, 16, blk.cin, generator=g).to(DEV); dy = torch.randn(2, 16, 16, blk.cout, generator=g).to(DEV)
+    rs = torch.tensor([1.25, 0.0], device=DEV)
+    names = ('GATE_IN_WEIGHTS_TRAIN', 'SE_FUSED', 'DW_SAVE_Y')
+    old = {k: getattr(Fn, k) for k in names}
+
+    def step(fwd, bwd):
+        try:
+            with torch.no_grad():
+                for k in names:
+                    setattr(Fn, k, fwd.get(k, old[k]))
+                y, sv = Fn.mbconv_fwd(Map.of(x), blk, P, torch.float32, True, rs)
+                for k in names:
+                    setattr(Fn, k, bwd.get(k, old[k]))
+                dx, gr = Fn.mbconv_bwd(sv, Map.of(dy))
+            torch.cuda.synchronize()
+        finally:
+            for k in names:
+                setattr(Fn, k, old[k])
+        return dx.t, gr, sv.path.gate
+    a_dx, a, a_form = step({'GATE_IN_WEIGHTS_TRAIN': True, 'SE_FUSED': True}, {'GATE_IN_WEIGHTS_TRAIN': True, 'SE_FUSED': False})
+    b_dx, b, b_form = step({'DW_SAVE_Y': True, 'SE_FUSED': False}, {'DW_SAVE_Y': True, 'SE_FUSED': False})
+    assert a_form == Fn.GATE_WEIGHTS and b_form == Fn.GATE_XS_FROM_XD
+    assert _bits_equal(a_dx, b_dx)
+    assert a.keys() == b.keys() and len(a) == 13
+    bad = [k for k in a if not _bits_equal(a[k], b[k])]
     assert not bad, bad
 
 
