@@ -1,6 +1,6 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h,
-include/effdet_opt_groups.h, include/effdet_gate_operand.h).
+include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -118,6 +118,11 @@ class Atss(C.Structure):         # effdet_atss_t (include/effdet_atss.h)
 class ConvPlanInfo(C.Structure):   # effdet_conv_plan_info_t (include/effdet_conv_plan.h)
     _fields_ = [(n, C.c_int) for n in ('id', 'form', 'persistent', 'tile_m', 'tile_n', 'stages', 'threads', 'mtiles', 'ntiles', 'grid',
                                        'ksteps', 'kord', 'lds_bytes', 'm32')] + [('reserved', C.c_int * 2)]
+
+
+class WgradPlanInfo(C.Structure):   # effdet_wgrad_plan_info_t (include/effdet_wgrad_plan.h)
+    _fields_ = [(n, C.c_int) for n in ('path', 'splits', 'nfast', 'mchunk', 'ntiles', 'jtiles', 'stage_pixels', 'allr', 'thin_ns', 'gate',
+                                       'nseg')] + [('first', C.c_int * MAX_SEG), ('count', C.c_int * MAX_SEG), ('reserved', C.c_int * 3)]
 
 
 WBF_MAX_VIEWS, WBF_MAX_IN = 8, 4096                  # EFFDET_WBF_MAX_VIEWS, EFFDET_WBF_MAX_IN
@@ -335,6 +340,12 @@ GATE_OPERAND_SIGNATURES = {
     'effdet_conv2d_wgrad_gated': 'i:ppipqs',
     'effdet_conv2d_wgrad_gated_kernel': 'i:ppi',
 }
+# The host-only query of the weight-gradient launch plan, declared in include/effdet_wgrad_plan.h (same generation, same letters, same
+# rule; tests/test_wgrad_plan_cases_host.py compares this table and WgradPlanInfo with that header).
+WGRAD_PLAN_SIGNATURES = {
+    'effdet_conv2d_wgrad_plan_info': 'i:pp',
+}
+WGRAD_PATHS = ('tiled', 'thin', 'split', 'stem')                                                  # EFFDET_WGRAD_PATH_* in order
 OPT_ROW, OPT_RULE_ADAMW, OPT_RULE_SGD, OPT_GATED, OPT_EMA = 8, 0, 1, 1, 2      # EFFDET_OPT_* of that header
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
@@ -361,7 +372,8 @@ def lib():
                 list(PLAN_SIGNATURES.items()) + list(LIVE_SIGNATURES.items()) + list(BOX_LOSS_SIGNATURES.items()) + \
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
                 list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
-                list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()):
+                list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
+                list(WGRAD_PLAN_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -25,6 +25,7 @@
 #include "../../../include/effdet_gate_operand.h"
 #include "../../../include/effdet_live_tiles.h"
 #include "../../../include/effdet_wgrad_pair.h"
+#include "../../../include/effdet_wgrad_plan.h"
 #include <stdlib.h>
 
 #ifndef EFFDET_WGRAD_TR_WAVES
@@ -1488,7 +1489,8 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w, const float* a_gate = null
     k.Cout = w.cout; k.K /= 2;
     for (int s = 0; s < q.nseg; ++s) flatten(k.seg[s]);
     // all fragment reads of a K-step ahead of its MFMAs (122 VGPRs instead of 106, still 4 waves / SIMD): +2.5 .. 3.5 % on the
-    // 256-channel head shapes (342 -> 355, 353 -> 362 TFLOP/s standalone), -2.5 % on 64 -> 256 -- so by input width (A/B: env 0 / 1)
+    // 256-channel head shapes (342 -> 355, 353 -> 362 TFLOP/s standalone), -2.5 % on 64 -> 256 -- so by input width (A/B: env 0 / 1).
+    // (q.Cin is the bf16 VIEW's doubled count: the rule as it stands is 1 from 64 input channels up, 0 only below)
     static const int allr_env = getenv("EFFDET_WGRAD_SPLIT_ALLR") ? atoi(getenv("EFFDET_WGRAD_SPLIT_ALLR")) : -1;
     w.allr = allr_env >= 0 ? allr_env : (q.Cin >= 128 ? 1 : 0);
     w.lds = (size_t)4 * 128 * 8 * sizeof(uint4);                       // 2 stages x (dz 16 KiB + x 16 KiB)
@@ -1576,6 +1578,23 @@ extern "C" int effdet_conv2d_wgrad_seg_slabs(const effdet_wgrad_t* p, int* first
   if (rc != EFFDET_OK) return rc;
   for (int s = 0; s < p->nseg; ++s) { first[s] = w.first[s]; count[s] = w.count[s]; }
   return w.splits;
+}
+
+// The plan wgrad_launch reads, copied out (include/effdet_wgrad_plan.h): host only, no HIP runtime call
+extern "C" int effdet_conv2d_wgrad_plan_info(const effdet_wgrad_t* p, effdet_wgrad_plan_info_t* info) {
+  if (!p || !info) return EFFDET_EINVAL;
+  WgradPlan w;
+  const int rc = plan_wgrad(p, w);
+  if (rc != EFFDET_OK) return rc;
+  const bool thin = w.path == WG_THIN || w.path == WG_STEM;
+  effdet_wgrad_plan_info_t o = {};
+  o.path = w.path; o.splits = w.splits; o.nfast = w.path == WG_TILED ? w.nfast : w.splits; o.mchunk = w.k.mchunk;
+  o.ntiles = thin ? 1 : w.k.ntiles; o.jtiles = thin ? 1 : w.k.jtiles;
+  o.stage_pixels = thin ? w.P : (w.path == WG_SPLIT || w.d.dtype == EFFDET_F32) ? 32 : 64;
+  o.allr = w.path == WG_SPLIT ? w.allr : 0; o.thin_ns = thin ? w.NS : 0; o.gate = w.gate; o.nseg = p->nseg;
+  for (int s = 0; s < p->nseg; ++s) { o.first[s] = w.first[s]; o.count[s] = w.count[s]; }
+  *info = o;
+  return w.path;
 }
 
 // live32 (effdet_conv2d_wgrad_live, include/effdet_live_tiles.h; NULL: the dense launch): per-call flags of the split-layout kernel

@@ -629,8 +629,35 @@ def conv2d_wgrad_kernel_id(x, dz, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l
     return int(L.lib().effdet_conv2d_wgrad_kernel(C.byref(d)))
 
 
+def conv2d_wgrad_plan_info(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, split=False,
+                           image_splits=False, **_launch_only):
+    """What conv2d_wgrad(xs, dzs, ...) would launch, asked of the library's own planner without device work
+    (effdet_conv2d_wgrad_plan_info) on the descriptor conv2d_wgrad builds (_wgrad_desc; the tensors only lend their addresses and may live
+    on the host; group / live32 do not change the plan) -> dict of path ('tiled', 'thin', 'split', 'stem'), splits, nfast, mchunk, ntiles,
+    jtiles, stage_pixels, allr, thin_ns, gate, first and count (lists, one entry per map).  Raises where conv2d_wgrad would."""
+    if isinstance(xs, Map):
+        xs, dzs = [xs], [dzs]
+    d = _wgrad_desc(xs, dzs, dw, dbias, Cin, Cout, KH, KW, stride, pad_t, pad_l, want_bias, split, image_splits)
+    info = L.WgradPlanInfo()
+    rc = int(L.require('effdet_conv2d_wgrad_plan_info').effdet_conv2d_wgrad_plan_info(C.byref(d), C.byref(info)))
+    if rc < 0:
+        L.check(rc, 'effdet_conv2d_wgrad_plan_info')
+    out = {n: int(getattr(info, n)) for n, _ in L.WgradPlanInfo._fields_ if n not in ('first', 'count', 'reserved', 'nseg')}
+    out['path'], out['allr'] = L.WGRAD_PATHS[out['path']], bool(out['allr'])
+    out['first'], out['count'] = list(info.first[:info.nseg]), list(info.count[:info.nseg])
+    return out
+
+
+def _wgrad_workspace(ws, floats, device):
+    """The caller's workspace (a contiguous fp32 tensor of at least `floats` elements, e.g. pre-filled by a test) or a fresh one."""
+    if ws is None:
+        return torch.empty(floats, dtype=torch.float32, device=device)
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.dim() == 1 and ws.numel() >= floats and ws.device == torch.device(device)
+    return ws[:floats]
+
+
 def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, split=False,
-                 image_splits=False, group=False, live32=None, a_gate=None, a_act=ACT_NONE):
+                 image_splits=False, group=False, live32=None, a_gate=None, a_act=ACT_NONE, ws=None):
     """Weight gradient -> (slabs [splits][Cout][taps][Cin] fp32, bias partial rows [splits][Cout] fp32 or None): the UNREDUCED
     split-K partials for unpack_wgrad / unpack_wgrad_bn to sum, in slab order, while unpacking (no float atomics anywhere: two
     runs are bitwise equal).  With dw given (packed [Cout][taps][Cin] fp32) the library reduces itself: dw += ..., dbias += ...
@@ -640,7 +667,9 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     zero; every split-K block walks only its live steps.  Same slabs and bias rows as without.
     a_gate ([B][Cin] fp32, with a_act = ACT_NONE or ACT_SWISH; image_splits, one 1x1 map pair): the gradient against
     act(xs) * a_gate[image][channel], formed in the kernels' operand registers (effdet_conv2d_wgrad_gated) -- bit for bit
-    conv2d_wgrad(channel_scale(xs, a_gate, a_act), ...) without that pass; raises where the planner refuses (conv2d_wgrad_gated_ok)."""
+    conv2d_wgrad(channel_scale(xs, a_gate, a_act), ...) without that pass; raises where the planner refuses (conv2d_wgrad_gated_ok).
+    ws (default: a fresh torch.empty): the caller's own fp32 workspace of at least splits * (Cout * taps * Cin + Cout) floats; the
+    results are views of its head (tests pre-fill it, so that a slab no workgroup wrote shows)."""
     if isinstance(xs, Map):
         xs, dzs = [xs], [dzs]
     x0 = xs[0]
@@ -650,7 +679,7 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     if splits < 1:
         raise RuntimeError('effdet_conv2d_wgrad: unsupported geometry')
     n = Cout * KH * KW * Cin
-    ws = torch.empty(splits * (n + Cout), dtype=torch.float32, device=x0.t.device)
+    ws = _wgrad_workspace(ws, splits * (n + Cout), x0.t.device)
     nbytes = ws.numel() * 4
     if a_gate is not None:
         assert live32 is None and not group and a_gate.dtype == torch.float32 and a_gate.is_contiguous() and a_gate.shape == (x0.B, Cin)
@@ -687,11 +716,12 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     return slabs, parts
 
 
-def conv2d_wgrad_pair(xs_a, dzs_a, xs_b, dzs_b, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, live32_b=None):
+def conv2d_wgrad_pair(xs_a, dzs_a, xs_b, dzs_b, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, live32_b=None, ws=None):
     """conv2d_wgrad(xs_a, dzs_a, split=True) and conv2d_wgrad(xs_b, dzs_b, split=True, live32=live32_b) as ONE launch
     (effdet_conv2d_wgrad_pair: two split-layout problems of one geometry, e.g. the same layer of the RetinaHead's two towers)
     -> ((slabs_a, parts_a), (slabs_b, parts_b)), views of one workspace, bit for bit what the two separate launches leave.
-    live32_b: problem b's step flags (see conv2d_wgrad) or None for two dense problems; problem a is always dense."""
+    live32_b: problem b's step flags (see conv2d_wgrad) or None for two dense problems; problem a is always dense.
+    ws: the caller's own workspace for both problems (see conv2d_wgrad)."""
     if isinstance(xs_a, Map):
         xs_a, dzs_a = [xs_a], [dzs_a]
     if isinstance(xs_b, Map):
@@ -703,7 +733,7 @@ def conv2d_wgrad_pair(xs_a, dzs_a, xs_b, dzs_b, *, Cin, Cout, KH, KW, stride=1, 
     if min(splits) < 1:
         raise RuntimeError('effdet_conv2d_wgrad_pair: unsupported geometry')
     n = Cout * KH * KW * Cin
-    ws = torch.empty(sum(splits) * (n + Cout), dtype=torch.float32, device=xs_a[0].t.device)
+    ws = _wgrad_workspace(ws, sum(splits) * (n + Cout), xs_a[0].t.device)
     nbytes = ws.numel() * 4
     if live32_b is not None:
         assert live32_b.dtype == torch.uint8 and live32_b.is_contiguous()
