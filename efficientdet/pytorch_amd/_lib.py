@@ -1,5 +1,5 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
-include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h,
+include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h, include/effdet_affine.h,
 include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
@@ -321,6 +321,12 @@ MOSAIC_SIGNATURES = {
     'effdet_mosaic_compose': 'i:ppppiiips',
     'effdet_mosaic_boxes': 'i:ppiipiffpips',
 }
+# The random affine / perspective warp between the mosaic stage and the 'train' chain, declared in include/effdet_affine.h (same
+# generation, same letters, same rule; tests/test_affine_host.py compares this table with that header's prototypes).
+AFFINE_SIGNATURES = {
+    'effdet_affine_warp': 'i:ppppiiips',
+    'effdet_affine_boxes': 'i:ppiipidddpps',
+}
 # Two weight gradients of one geometry as one launch, declared in include/effdet_wgrad_pair.h (same generation, same letters, same
 # rule; tests/test_wgrad_pair_host.py compares this table with that header's prototype).
 WGRAD_PAIR_SIGNATURES = {
@@ -373,7 +379,7 @@ def lib():
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
                 list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
                 list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
-                list(WGRAD_PLAN_SIGNATURES.items()):
+                list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

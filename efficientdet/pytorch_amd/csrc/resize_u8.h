@@ -1,6 +1,7 @@
 // The uint8 resize rule shared by the augmentation chain (augment.hip) and the mosaic stage (mosaic.hip): cv2.resize INTER_LINEAR as
 // tests/augment_restated.py restates it (half-pixel centres, edge clamp, fp32 blend, round half up) and LongestMaxSize's dimensions.
-// Both files are built with -ffp-contract=off, so every float step rounds as the restatement's.
+// Both files are built with -ffp-contract=off, so every float step rounds as the restatement's.  The warp (affine.hip) has its own
+// geometry and takes the pass-through resize and the blend of four taps (blend_u8) from here.
 #pragma once
 #include "common.h"
 
@@ -44,6 +45,15 @@ __device__ __forceinline__ void bilinear_u8(const unsigned char* base, int bpp, 
     const float bot = (float)p10[c] + fx * ((float)p11[c] - (float)p10[c]);
     out[c] = round_u8(top + fy * (bot - top));
   }
+}
+
+// bilinear_u8's blend of one channel for a caller that has its four taps as values (the warp of affine.hip, whose taps outside the
+// source are the border byte): top, bot and the result in fp32, then round_u8.  bilinear_u8 keeps the same three lines written out:
+// routed through this function its loads come out in another order, and augment.hip and mosaic.hip are to compile as they did.
+__device__ __forceinline__ unsigned char blend_u8(float p00, float p01, float p10, float p11, float fx, float fy) {
+  const float top = p00 + fx * (p01 - p00);
+  const float bot = p10 + fx * (p11 - p10);
+  return round_u8(top + fy * (bot - top));
 }
 
 // LongestMaxSize(S): scale = S / max(h, w), new dims rounded half to even (Python's round)

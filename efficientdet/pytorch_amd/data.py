@@ -404,6 +404,128 @@ def check_mosaic_table(table, B, S, hw):
     return t
 
 
+# ------------------------------------------------------------------------------------------------ affine / perspective warp on the device
+# Columns of the per-image warp table (include/effdet_affine.h, EFFDET_AFFINE_P), one row per OUTPUT image: the forward matrix F
+# (source pixel -> output pixel, row-major), its inverse G and the isotropic scale in F.  The table is fp64.
+AFFINE_COLUMNS = ('on',) + tuple('f%d' % i for i in range(9)) + tuple('g%d' % i for i in range(9)) + ('scale',)
+AFFINE = {n: i for i, n in enumerate(AFFINE_COLUMNS)}
+
+
+class AffineOptions:
+    """The random affine / perspective warp (YOLOv5's random_perspective) between the mosaic stage and the 'train' chain of
+    DeviceAugmentation; include/effdet_affine.h holds the semantics.
+
+    p: probability that an image is warped (else it goes through LongestMaxSize + pad, as without the option).  degrees: rotation
+    range, +-.  translate: range of the centre's offset, +- fractions of the output side.  scale: range (lo, hi) of the scale
+    relative to LongestMaxSize's.  shear: range of the two shear angles, +- degrees.  perspective: range of the two perspective
+    terms, +-.  fill: the border byte.  wh_thr, ar_thr, area_thr: box_candidates' thresholds (a warped box is kept if both sides
+    exceed wh_thr px, its aspect ratio stays below ar_thr and its area exceeds area_thr of the scaled source box's).  canvas: 1, or 2
+    with a mosaic in front: the mosaic is then composed on a canvas of twice the output side and the warp brings it down (the
+    published recipe)."""
+
+    def __init__(self, p=1.0, degrees=0.0, translate=0.1, scale=(0.5, 1.5), shear=0.0, perspective=0.0, fill=114, wh_thr=2.0,
+                 ar_thr=100.0, area_thr=0.1, canvas=1):
+        self.p, self.degrees, self.translate = float(p), float(degrees), float(translate)
+        self.scale = tuple(float(v) for v in scale)
+        self.shear, self.perspective = float(shear), float(perspective)
+        self.wh_thr, self.ar_thr, self.area_thr = float(wh_thr), float(ar_thr), float(area_thr)
+        if not 0.0 <= self.p <= 1.0:
+            raise ValueError('p is a probability in [0, 1]')
+        if not 0.0 <= self.degrees <= 180.0:
+            raise ValueError('degrees is a range +- in [0, 180]')
+        if not 0.0 <= self.translate <= 0.5:
+            raise ValueError('translate is a range +- in [0, 0.5] of the output side')
+        if len(self.scale) != 2 or not 0.0 < self.scale[0] <= self.scale[1] or not math.isfinite(self.scale[1]):
+            raise ValueError('scale is a range (lo, hi) with 0 < lo <= hi, finite')
+        if not 0.0 <= self.shear < 90.0:
+            raise ValueError('shear is a range +- in [0, 90) degrees')
+        if not (0.0 <= self.perspective and math.isfinite(self.perspective)):
+            raise ValueError('perspective is a range +-, non-negative and finite')
+        if isinstance(fill, bool) or int(fill) != fill or not 0 <= int(fill) <= 255:
+            raise ValueError('fill is a byte, 0 .. 255')
+        self.fill = int(fill)
+        if not (self.wh_thr >= 0.0 and self.area_thr >= 0.0 and self.ar_thr > 0.0) or not all(
+                math.isfinite(v) for v in (self.wh_thr, self.ar_thr, self.area_thr)):
+            raise ValueError('wh_thr and area_thr are non-negative, ar_thr is positive, all finite')
+        if isinstance(canvas, bool) or canvas not in (1, 2):
+            raise ValueError('canvas is 1 or 2')
+        self.canvas = int(canvas)
+
+    def key(self):
+        return (self.p, self.degrees, self.translate, self.scale, self.shear, self.perspective, self.fill, self.wh_thr, self.ar_thr,
+                self.area_thr, self.canvas)
+
+    def __eq__(self, other):
+        return isinstance(other, AffineOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return ('AffineOptions(p=%r, degrees=%r, translate=%r, scale=%r, shear=%r, perspective=%r, fill=%r, wh_thr=%r, ar_thr=%r, '
+                'area_thr=%r, canvas=%r)' % self.key())
+
+
+def sample_affine_table(rng, B, S, hw, opts):
+    """Draw the warp parameters of B output images of S x S from rng (np.random.RandomState) -> [B, len(AFFINE_COLUMNS)] fp64.  hw:
+    the sources' (h, w) [B, 2].  Order per image: on (probability p); then, only when on: the two perspective terms (uniform in
+    +-perspective), the angle (+-degrees), s (uniform in scale), the two shears (+-shear degrees) and the two translations
+    (uniform in (0.5 +- translate) * S).  F = T . Sh . R . P . C in fp64: C moves the source centre (w / 2, h / 2) to the origin,
+    P holds the perspective terms, R is the rotation with scale s * S / max(h, w) (LongestMaxSize folded in), Sh the shears, T
+    moves the origin to the drawn point; G = inv(F), and the scale column is s * S / max(h, w)."""
+    hw = np.asarray(hw).reshape(-1, 2)
+    if hw.shape != (B, 2):
+        raise ValueError('the warp table needs the %d source sizes [B, 2], got %s' % (B, hw.shape))
+    t = np.zeros((B, len(AFFINE_COLUMNS)), dtype=np.float64)
+    for b in range(B):
+        if rng.rand() >= opts.p:
+            continue
+        h, w = float(hw[b, 0]), float(hw[b, 1])
+        C_, P_, R_, Sh, T_ = (np.eye(3) for _ in range(5))
+        C_[0, 2], C_[1, 2] = -w / 2, -h / 2
+        P_[2, 0], P_[2, 1] = rng.uniform(-opts.perspective, opts.perspective), rng.uniform(-opts.perspective, opts.perspective)
+        a = math.radians(rng.uniform(-opts.degrees, opts.degrees))
+        k = rng.uniform(opts.scale[0], opts.scale[1]) * S / max(h, w)
+        R_[0, 0], R_[0, 1], R_[1, 0], R_[1, 1] = k * math.cos(a), k * math.sin(a), -k * math.sin(a), k * math.cos(a)
+        Sh[0, 1] = math.tan(math.radians(rng.uniform(-opts.shear, opts.shear)))
+        Sh[1, 0] = math.tan(math.radians(rng.uniform(-opts.shear, opts.shear)))
+        T_[0, 2] = rng.uniform(0.5 - opts.translate, 0.5 + opts.translate) * S
+        T_[1, 2] = rng.uniform(0.5 - opts.translate, 0.5 + opts.translate) * S
+        F = T_ @ Sh @ R_ @ P_ @ C_
+        t[b, AFFINE['on']] = 1
+        t[b, AFFINE['f0']:AFFINE['f8'] + 1] = F.reshape(-1)
+        t[b, AFFINE['g0']:AFFINE['g8'] + 1] = np.linalg.inv(F).reshape(-1)
+        t[b, AFFINE['scale']] = k
+    return t
+
+
+def check_affine_table(table, B, S):
+    """Refuse a table the warp cannot mean (include/effdet_affine.h): wrong shape, `on` outside {0, 1}, and for a row that is on:
+    non-finite entries, scale <= 0, or a G that is not the inverse of F (the largest absolute row sum of F.G - I above 1e-9).  The
+    rest of a row that is off is ignored.  Raises ValueError naming the row -> the table as fp64."""
+    t = np.asarray(table, dtype=np.float64)
+    if t.shape != (B, len(AFFINE_COLUMNS)):
+        raise ValueError('warp table must be [%d, %d], got %s' % (B, len(AFFINE_COLUMNS), t.shape))
+
+    def bad(b, what):
+        raise ValueError('warp table row %d: %s' % (b, what))
+    for b in range(B):
+        r = t[b]
+        if r[AFFINE['on']] not in (0.0, 1.0):
+            bad(b, 'on is 0 or 1')
+        if not r[AFFINE['on']]:
+            continue
+        if not np.all(np.isfinite(r)):
+            bad(b, 'every entry is finite')
+        if not r[AFFINE['scale']] > 0.0:
+            bad(b, 'scale = %r is not positive' % float(r[AFFINE['scale']]))
+        F, G = r[AFFINE['f0']:AFFINE['f8'] + 1].reshape(3, 3), r[AFFINE['g0']:AFFINE['g8'] + 1].reshape(3, 3)
+        err = float(np.abs(F @ G - np.eye(3)).sum(1).max())
+        if not err <= 1e-9:
+            bad(b, 'G is not the inverse of F (|F.G - I| = %.3g > 1e-9)' % err)
+    return t
+
+
 class DeviceAugmentation(DeviceCollater):
     """get_augumentation(phase, width, height, min_area, min_visibility) + detection_collate (datasets/augmentation.py:8-67) on the
     device: ``images, annotations, params = aug(samples)``.
@@ -423,12 +545,20 @@ class DeviceAugmentation(DeviceCollater):
     into B canvases of width x width, and the chain runs on those as if they were the dataset's images.  Annotations then have up to
     5 x the longest input list of rows before trimming.  It is a plain attribute: ``aug.mosaic = None`` switches the stage off (the
     last epochs of a schedule), and nothing of it runs then.  ``aug(samples, mosaic_table=...)`` takes an explicit table (host
-    memory: numpy or CPU tensor, columns MOSAIC_COLUMNS); it always passes check_mosaic_table."""
+    memory: numpy or CPU tensor, columns MOSAIC_COLUMNS); it always passes check_mosaic_table.
+
+    affine: an AffineOptions puts the random affine / perspective warp (csrc/affine.hip) between the mosaic stage and the chain: each
+    source (a dataset image, or a mosaic canvas) becomes one width x width image through a homography, its boxes go along and are
+    filtered by box_candidates' rule, and the chain runs on the result.  With ``canvas=2`` (which needs `mosaic`) the mosaic is
+    composed at twice the width, its table sampled and checked at that side, and the warp brings it down.  Like `mosaic` it is a
+    plain attribute, ``aug.affine = None`` switches it off and nothing of it runs then, not even a random draw; its table is drawn
+    after the mosaic's.  ``aug(samples, affine_table=...)`` takes an explicit host table (fp64, columns AFFINE_COLUMNS); it always
+    passes check_affine_table."""
 
     PHASES = ('train', 'valid', 'test')
 
     def __init__(self, phase='train', width=512, height=512, min_area=0., min_visibility=0., dtype=torch.bfloat16, device='cuda',
-                 seed=0, trim=True, decode_threads=8, decode_fallback=None, mosaic=None):
+                 seed=0, trim=True, decode_threads=8, decode_fallback=None, mosaic=None, affine=None):
         if phase not in self.PHASES:
             raise ValueError('phase must be one of %s' % (self.PHASES,))
         if phase == 'train' and (width != height or width < 8):
@@ -442,18 +572,37 @@ class DeviceAugmentation(DeviceCollater):
         if mosaic is not None and phase != 'train':
             raise ValueError("mosaic only applies to the 'train' phase")
         self.mosaic = mosaic
+        if affine is not None and not isinstance(affine, AffineOptions):
+            raise TypeError('affine is an AffineOptions or None')
+        self._check_affine(affine, mosaic)
+        self.affine = affine
 
-    def __call__(self, samples, table=None, stages=None, mosaic_table=None):
-        """stages: optional dict that receives the uint8 intermediates of ops.augment_train / ops.augment_resize (tests), and with
-        mosaic 'mosaic' (uint8 [B,S,S,3]) and 'mosaic_table' (the device table)."""
+    def _check_affine(self, affine, mosaic):
+        if affine is not None and self.phase != 'train':
+            raise ValueError("affine only applies to the 'train' phase")
+        if affine is not None and affine.canvas == 2 and mosaic is None:
+            raise ValueError('affine canvas=2 warps a mosaic canvas of twice the side down: it needs mosaic options')
+
+    def __call__(self, samples, table=None, stages=None, mosaic_table=None, affine_table=None):
+        """stages: optional dict that receives the uint8 intermediates of ops.augment_train / ops.augment_resize (tests), with mosaic
+        'mosaic' (uint8 [B,side,side,3], side = canvas * S) and 'mosaic_table' (the device table), and with affine 'affine' (uint8
+        [B,S,S,3]) and 'affine_table' (the device table, fp64)."""
         B = len(samples)
         mosaic = getattr(self, 'mosaic', None)
+        affine = getattr(self, 'affine', None)
         if mosaic is not None and self.phase != 'train':
             raise ValueError("mosaic only applies to the 'train' phase")
         if mosaic_table is not None and mosaic is None:
             raise ValueError('mosaic_table was given, but this augmentation has no mosaic options')
         if mosaic_table is not None and torch.is_tensor(mosaic_table) and mosaic_table.device.type != 'cpu':
             raise ValueError('a mosaic table comes from the host (numpy or CPU tensor): it is checked before anything is launched')
+        self._check_affine(affine, mosaic)
+        if affine_table is not None and affine is None:
+            raise ValueError('affine_table was given, but this augmentation has no affine options')
+        if affine_table is not None and torch.is_tensor(affine_table) and affine_table.device.type != 'cpu':
+            raise ValueError('an affine table comes from the host (numpy or CPU tensor): it is checked before anything is launched')
+        if affine_table is not None:
+            affine_table = check_affine_table(affine_table.numpy() if torch.is_tensor(affine_table) else affine_table, B, self.S)
         staged = self._stage_batch(samples)
         if self.phase == 'train':
             if table is None:
@@ -467,17 +616,32 @@ class DeviceAugmentation(DeviceCollater):
         src, d_off, d_hw, hw = self._upload(samples, staged)
         d_ann = None
         if mosaic is not None:
+            side = self.S * (affine.canvas if affine is not None else 1)   # canvas=2: composed at 2S, the warp brings it down to S
             if mosaic_table is None:
-                mosaic_table = sample_mosaic_table(self.rng, B, self.S, mosaic)
-            mt = check_mosaic_table(mosaic_table.numpy() if torch.is_tensor(mosaic_table) else mosaic_table, B, self.S, hw)
+                mosaic_table = sample_mosaic_table(self.rng, B, side, mosaic)
+            mt = check_mosaic_table(mosaic_table.numpy() if torch.is_tensor(mosaic_table) else mosaic_table, B, side, hw)
             d_mt = torch.from_numpy(np.ascontiguousarray(mt)).to(dev, non_blocking=True)
-            canvas = ops.mosaic_compose(src, d_off, d_hw, d_mt, self.S, mosaic.fill)
-            d_ann, _ = ops.mosaic_boxes(d_hw, d_mt, self.S, torch.from_numpy(ann).to(dev, non_blocking=True), self.min_area,
+            canvas = ops.mosaic_compose(src, d_off, d_hw, d_mt, side, mosaic.fill)
+            d_ann, _ = ops.mosaic_boxes(d_hw, d_mt, side, torch.from_numpy(ann).to(dev, non_blocking=True), self.min_area,
                                         self.min_visibility)
             if stages is not None:
                 stages.update(mosaic=canvas, mosaic_table=d_mt)
-            # the chain takes the canvases as a batch of S x S dataset images
+            # the next stage takes the canvases as a batch of side x side dataset images
             src = canvas.view(-1)
+            d_off = torch.arange(B, dtype=torch.int64, device=dev) * (side * side * 3)
+            d_hw = torch.full((B, 2), side, dtype=torch.int32, device=dev)
+            hw = np.full((B, 2), side, dtype=np.int32)
+        if affine is not None:
+            wt = affine_table if affine_table is not None else check_affine_table(sample_affine_table(self.rng, B, self.S, hw, affine), B, self.S)
+            d_wt = torch.from_numpy(np.ascontiguousarray(wt)).to(dev, non_blocking=True)
+            warped = ops.affine_warp(src, d_off, d_hw, d_wt, self.S, affine.fill)
+            if d_ann is None:
+                d_ann = torch.from_numpy(ann).to(dev, non_blocking=True)
+            d_ann, _ = ops.affine_boxes(d_hw, d_wt, self.S, d_ann, affine.wh_thr, affine.ar_thr, affine.area_thr)
+            if stages is not None:
+                stages.update(affine=warped, affine_table=d_wt)
+            # the chain takes the warped images as a batch of S x S dataset images
+            src = warped.view(-1)
             d_off = torch.arange(B, dtype=torch.int64, device=dev) * (self.S * self.S * 3)
             d_hw = torch.full((B, 2), self.S, dtype=torch.int32, device=dev)
         if self.phase == 'train':

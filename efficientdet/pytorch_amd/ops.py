@@ -2200,6 +2200,36 @@ def mosaic_boxes(src_hw, table, S, annots, min_area=0.0, min_visibility=0.0):
     return out, counts
 
 
+# ----------------------------------------------------------------------------- affine / perspective warp (csrc/affine.hip)
+_AFFINE = ('effdet_affine_warp', 'effdet_affine_boxes')
+AFFINE_P = 20                      # EFFDET_AFFINE_P: columns of the per-image warp table (include/effdet_affine.h)
+
+
+def affine_warp(src_u8, src_off, src_hw, table, S, fill=114):
+    """The warp of a batch (include/effdet_affine.h): uint8 HWC images (concatenated, device) + table [B, AFFINE_P] fp64 (device) ->
+    uint8 [B,S,S,3], the input of augment_train with src_off = b * S*S*3 and src_hw = (S, S)."""
+    B = int(src_hw.shape[0])
+    assert table.dtype == torch.float64 and table.is_contiguous() and tuple(table.shape) == (B, AFFINE_P)
+    out = torch.empty((B, int(S), int(S), 3), dtype=torch.uint8, device=src_u8.device)
+    L.check(L.require(*_AFFINE).effdet_affine_warp(L.ptr(src_u8), L.ptr(src_off), L.ptr(src_hw), L.ptr(table), B, int(S), int(fill),
+                                                   L.ptr(out), L.stream_ptr()), 'effdet_affine_warp')
+    return out
+
+
+def affine_boxes(src_hw, table, S, annots, wh_thr=2.0, ar_thr=100.0, area_thr=0.1):
+    """Boxes [B,M,5] fp32 of the source images (label -1 = padding) through the forward matrices of `table`, clipped to the output
+    and filtered by box_candidates' rule -> (out [B,M,5] with the kept rows first in input order and -1 after, counts [B] int32)."""
+    B, M = int(annots.shape[0]), int(annots.shape[1])
+    assert annots.dtype == torch.float32 and annots.is_contiguous() and annots.shape[2] == 5
+    assert table.dtype == torch.float64 and table.is_contiguous() and tuple(table.shape) == (B, AFFINE_P)
+    out = torch.empty_like(annots)
+    counts = torch.empty(B, dtype=torch.int32, device=annots.device)
+    L.check(L.require(*_AFFINE).effdet_affine_boxes(L.ptr(src_hw), L.ptr(table), B, int(S), L.ptr(annots), M, float(wh_thr),
+                                                    float(ar_thr), float(area_thr), L.ptr(out), L.ptr(counts), L.stream_ptr()),
+            'effdet_affine_boxes')
+    return out, counts
+
+
 # ----------------------------------------------------------------------------- JPEG decode (csrc/jpeg.hip)
 _JPEG = ('effdet_jpeg_probe', 'effdet_jpeg_entropy_batch', 'effdet_jpeg_reconstruct')
 JPEG_GREY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3
