@@ -24,6 +24,7 @@ F32_HSPLIT = 4                                     # the f16x3 forward arithmeti
 ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = 0, 1, 2, 3
 RES_NONE, RES_ADD, RES_RELU_MASK, RES_SWISH_GRAD = 0, 1, 2, 3
 TUNE_IGEMM_BIG, TUNE_IGEMM_BIG_MIN_M, TUNE_SPLIT_PERS, TUNE_IGEMM_KORD, TUNE_SPLIT_KORD = 0, 1, 2, 3, 4
+TUNE_ROWSLAB = 5                   # row-slab activation staging of the split-layout 3x3 convs: 1 (default) on, 0 per-tap staging
 
 _ERR = {-1: 'EFFDET_EINVAL', -2: 'EFFDET_ELAUNCH', -3: 'EFFDET_EUNSUPPORTED'}
 

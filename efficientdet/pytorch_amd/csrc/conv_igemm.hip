@@ -21,6 +21,13 @@
 //   * im2col-free: per-thread (tap, channel-chunk) cursors advance incrementally, halo / tail
 //     lanes load zeros.  Several pyramid levels that share weights run as ONE grouped launch
 //     (segments), which keeps the tiny 8x8 / 4x4 levels from being launch-bound.
+//   * the split-layout 3x3 convs of the head (SPLIT >= 2: stride 1, pad 1, channel-group-major walk) do not stage a tile per TAP:
+//     on segments 8 .. 64 pixels wide a 128-pixel tile is whole image rows, and per 32-channel group and kernel row ONE slab -- those
+//     rows at h + kh - 1 with a zero halo column on each side, 132 .. 160 entries of 128 B -- serves the three taps kw, which read it
+//     one entry apart (activation DMA per group 3 x 17 .. 20 KiB instead of 9 x 16, DMA instructions per thread 27 instead of 36;
+//     LDS 2 x 16 KiB of weights + 2 slabs = 66 .. 72 KiB, still two workgroups per CU).  Same operands into every MFMA in the same
+//     order: bit for bit the per-tap form, which stays for W = 4, widths that do not divide 128, the tap-major walk and behind the
+//     tuning knob EFFDET_TUNE_ROWSLAB.  Measured (profiles/rowslab_*): 3.5 - 5 % on the head's launches, 22.8 -> 22.1 ms per step.
 //   * 1-D grid with a bijective XCD remap: the 8 blocks that land on one XCD walk neighbouring
 //     tiles (n fastest), so the activation tile is fetched into one private L2 only.
 #include "common.h"
@@ -65,10 +72,21 @@ struct ConvK {
   const unsigned char* needed; // SPLIT == 3 only, may be NULL: needed[mt - needed_tile0] == 0 = nobody reads pixel tile mt's result (effdet_conv2d_needed)
   int needed_tile0;            // pixel tiles below it carry no flag and are computed
   const float* a_gate;         // GATE != 0 only (effdet_conv2d_gated): [B][Cin] fp32, the activation operand is act(x) * a_gate[image][channel]
+  int slab;                    // SPLIT >= 2 only: segments that pass slab_seg_ok stage one activation row slab per kernel row (see the kernel)
+  int xld;                     // SPLIT >= 2 only: uint4 per activation LDS buffer (128 * 8, or the largest slab of the launch's segments)
   SegD seg[EFFDET_MAX_CONV_SEG];
 };
 
 constexpr int BM = 128;
+
+// Row-slab staging (3x3, stride 1, pad 1, channel-group-major walk): a 128-pixel tile of a segment whose width is a power of two
+// in 8 .. 64 is 128 / W whole image rows, and the three taps of one kernel row read the same rows.  slab_entries: 128-byte entries
+// of its slab (132 / 136 / 144 / 160 for W = 64 / 32 / 16 / 8).  The 64-channel tile keeps W = 8 on the per-tap form: with slabs of at
+// most 144 entries its workgroup stays at 52 KiB of LDS, three to a CU as before (160 entries: 56 KiB, two).
+__host__ __device__ inline int slab_entries(int W) { return (BM / W) * (W + 2); }
+__host__ __device__ inline bool slab_seg_ok(const SegD& s, int bn) {
+  return (s.W & (s.W - 1)) == 0 && s.W >= (bn > 64 ? 8 : 16) && s.W <= 64 && s.Ho == s.H && s.Wo == s.W;
+}
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <typename T> struct Mma;
@@ -147,9 +165,17 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   constexpr int XROWS = BM / RSTEP;         // X pieces per thread per K-step (4 or 2)
   constexpr int WROWS = (BN + RSTEP - 1) / RSTEP;     // weight pieces per thread per K-step
 
+  // SLABCAP: the instances that can stage row slabs (the two-stage split-layout loop on 16x16x32 tiles).  Their activation buffers are
+  // p.xld uint4 long (a slab of 132 .. 160 entries is longer than the 128 rows of a tap tile) and sit BEHIND the weight buffers.
+  constexpr bool SLABCAP = SPLIT >= 2 && NS == 2 && !M32;
+  constexpr int SP = SLABCAP ? (160 + RSTEP - 1) / RSTEP : 1;      // DMA passes of the workgroup over a slab of up to 160 entries (3 or 5)
+  static_assert(!SLABCAP || ((SP - 1) * RSTEP == 128 && WROWS * RSTEP == BN), "slab passes: 128 entries for every wave, the rest in the last pass");
+  static_assert(!SLABCAP || MT <= 2, "slab fragments: fragment 1 is one uniform entry step from fragment 0");
+
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
-  uint4* xs = smem;                // [NS][BM*8]
-  uint4* ws = smem + NS * XLD;     // [NS][BN*8]
+  const int xld = SLABCAP ? p.xld : XLD;
+  uint4* xs = SLABCAP ? smem + NS * WLD : smem;                // [NS][xld]
+  uint4* ws = SLABCAP ? smem : smem + NS * XLD;                // [NS][BN*8]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -254,11 +280,13 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   const unsigned xs_a = lds_addr(xs), ws_a = lds_addr(ws);
   const int kc = (tid & 7) ^ ((tid >> 4) & 7), r0 = tid >> 3;
   const int wrow0 = __builtin_amdgcn_readfirstlane(wave) * 8;     // first tile row of this wave's 1-KiB DMA piece
+  // (workgroup-uniform: this tile's segment stages row slabs; the host sized the buffers with the same test)
+  const bool slab = SLABCAP && p.slab && slab_seg_ok(sg, BN);
   unsigned xoff[XROWS]; int hi0[XROWS], wi0[XROWS];
 #pragma unroll
   for (int j = 0; j < XROWS; ++j) {
     const int m = m_base + r0 + RSTEP * j;
-    if (m < sg.M) {
+    if (m < sg.M && !slab) {       // (the slab path keeps its own per-entry cursors, below)
       const int b = m / HoWo, rem = m - b * HoWo;
       const int ho = rem / sg.Wo, wo = rem - ho * sg.Wo;
       hi0[j] = ho * p.stride - p.pad_t; wi0[j] = wo * p.stride - p.pad_l;
@@ -294,7 +322,7 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
     const bool kok = kq < p.Kc;
 #pragma unroll
     for (int j = 0; j < XROWS; ++j)
-      dma16_async(rx, xs_a + (unsigned)(buf * XLD + (wrow0 + RSTEP * j) * 8) * 16u, kok ? xcur[j] : EFFDET_OOB);
+      dma16_async(rx, xs_a + (unsigned)(buf * xld + (wrow0 + RSTEP * j) * 8) * 16u, kok ? xcur[j] : EFFDET_OOB);
 #pragma unroll
     for (int j = 0; j < WROWS; ++j) {
       if (wrow0 + RSTEP * j < BN)     // wave-uniform: the whole 8-row piece is inside the weight tile
@@ -340,7 +368,10 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   //              first slice of tile t+1 is fetched under the second slice of tile t.  With the barrier at the
   //              loop end the 8 waves of a workgroup marched in lockstep (DMA issue -> LDS latency -> MFMA burst)
   //              and the matrix pipe idled through every LDS round trip (experiment: removing the LDS reads alone
-  //              gave +23 %, removing the DMA alone +36 %).
+  //              gave +23 %, removing the DMA alone +36 %).  (Those figures are from an older form of the kernel.  On today's split-layout
+  //              loop, dropping the activation DMA of the kw != 0 K-steps -- two thirds of it, results wrong -- took the paired
+  //              256 -> 256 tower launch from 1151-1181 to 1106-1122 us forward and from 1082-1096 to 1033-1049 us in the data
+  //              gradient: the vector-memory -> LDS path is still a co-limiter, which the row-slab staging below acts on.)
   const int nk = (p.Kc + 7) >> 3;
   const int l15 = lane & 15, lq = lane >> 4, lsw = l15 >> 1;  // swizzle term (row>>1)&7 for row%16 = l15
   float* const gl = (float*)(smem + NS * (XLD + WLD));        // GATE: the image's gate row, [nk * 32] floats (visible after the first barrier below)
@@ -453,9 +484,9 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
 #pragma unroll
         for (int a = 0; a < NT; ++a) f.wh[a] = ws[buf * WLD + (wn0 + a * 16 + l15) * 8 + (lq ^ lsw)];
 #pragma unroll
-        for (int b = 0; b < MT; ++b) f.xh[b] = xs[buf * XLD + (wm0 + b * 16 + l15) * 8 + (lq ^ lsw)];
+        for (int b = 0; b < MT; ++b) f.xh[b] = xs[buf * xld + (wm0 + b * 16 + l15) * 8 + (lq ^ lsw)];
 #pragma unroll
-        for (int b = 0; b < MT; ++b) f.xl[b] = xs[buf * XLD + (wm0 + b * 16 + l15) * 8 + ((4 + lq) ^ lsw)];
+        for (int b = 0; b < MT; ++b) f.xl[b] = xs[buf * xld + (wm0 + b * 16 + l15) * 8 + ((4 + lq) ^ lsw)];
 #pragma unroll
         for (int a = 0; a < NT; ++a) f.wl[a] = ws[buf * WLD + (wn0 + a * 16 + l15) * 8 + ((4 + lq) ^ lsw)];
       } else {
@@ -490,6 +521,112 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
     // workgroup's waves cover the LDS round trip + split better than software pipelining inside one wave does.  The same
     // loop on v_mfma_f32_32x32x16_bf16 tiles (higher instruction ceiling) measured 267-327: the matrix pipe is not the limiter.
     Frags f;
+    bool walked = false;
+    if constexpr (SLABCAP) {
+      if (slab) {
+        // ---- row-slab staging (p.slab; 3x3, stride 1, pad 1, channel-group-major walk; the segment passes slab_seg_ok) ----
+        // The tile is R = 128 / W whole image rows.  Per 32-channel group and kernel row kh ONE slab is staged: entry
+        // rt * (W + 2) + (w + 1) holds pixel (b, h + kh - 1, w) of tile row rt = image row (b, h), w = -1 .. W; rows outside the image,
+        // the two halo columns, rows past M and the entries that round the slab up to whole 8-entry DMA pieces pass EFFDET_OOB (zeros).
+        // Tap (kh, kw) of pixel (rt, w) is entry rt * (W + 2) + w + kw: the three taps of a kernel row read ONE staged slab where the
+        // per-tap form stages three shifted copies of the tile (activation DMA per group: 3 x 132 .. 160 entries for 9 x 128).  The
+        // swizzle is keyed on the entry, slot = chunk ^ ((e >> 1) & 7), applied at the DMA source like the tap tile's (piece q of a
+        // pass starts at entry 8 q: the term is the same per-thread constant kc); 16 consecutive entries read conflict-free at any
+        // parity of the first.  Weights stay per tap.  Every MFMA receives the operands of the per-tap form in its order: same bits.
+        // Pipeline: weight tile kt + 2 is issued after the barrier that ends K-step kt, as there; slab s + 1 right behind the weights
+        // issued after K-step 3 s - 1 (the barrier that frees its buffer).  DMA loads retire in order, so the wait that ends K-step 3 s
+        // -- for the weights issued AHEAD of the slab -- leaves the slab's pieces in flight (a counted vmcnt) and the one that ends
+        // K-step 3 s + 1 drains them: two K-steps to land, one before its first read.
+        const int W = sg.W, W2 = W + 2, lw = 31 - __builtin_clz((unsigned)W), R = BM >> lw;
+        const int npieces = (R * W2 + 7) >> 3;
+        const bool slast = (wrow0 >> 3) + (SP - 1) * NWAVES < npieces;       // wave-uniform: this wave owns a piece of the last pass
+        const int grow0 = m_base >> lw, nrows = sg.M >> lw;                   // first image row (b * H + h) of the tile; rows of the segment
+        const int rowb = W * p.ldx * (int)ES;                                 // bytes from one image row to the next
+        // per thread: the byte offset of each pass's entry in the CENTRE row (this thread's chunk kc of group 0 included) and ONE mask,
+        // bit 3 j + kh = the entry of pass j is a pixel of the image in kernel row kh; everything that moves with the walk is uniform
+        unsigned sbase[SP], vmask = 0u;
+#pragma unroll
+        for (int j = 0; j < SP; ++j) {
+          const int e = r0 + RSTEP * j, rt = e / W2, w = e - rt * W2 - 1, g = grow0 + rt;
+          const bool ok = rt < R && w >= 0 && w < W && g < nrows;
+          const int b = g / sg.H, h = g - b * sg.H;
+          sbase[j] = (unsigned)((long long)b * sg.in_bs * ES) + (unsigned)((h * W + w) * p.ldx) * ES + (unsigned)kc * 16u;
+          if (ok) vmask |= ((h > 0 ? 1u : 0u) | 2u | (h + 1 < sg.H ? 4u : 0u)) << (3 * j);
+        }
+        // entry of this lane's pixel of fragment 0 at kw = 0; fragment b is 16 b pixels on: the same row (W >= 32) or 16 b / W rows down
+        const int pt0 = wm0 + l15, ebase = (pt0 >> lw) * W2 + (pt0 & (W - 1)), estep = (16 >> lw) * W2 + (16 & (W - 1));
+        int s_kh = 0, s_g = 0;                 // slab cursor: kernel row, channel group
+        auto stage_slab = [&](int buf) {
+          const unsigned walk = (unsigned)((s_kh - 1) * rowb + s_g * 128);
+#pragma unroll
+          for (int j = 0; j < SP; ++j) {
+            if (j < SP - 1 || slast)
+              dma16_async(rx, xs_a + (unsigned)(buf * xld + (wrow0 + RSTEP * j) * 8) * 16u, ((vmask >> (3 * j + s_kh)) & 1u) ? sbase[j] + walk : EFFDET_OOB);
+          }
+          if (++s_kh == 3) { s_kh = 0; ++s_g; }
+        };
+#pragma unroll
+        for (int j = 0; j < WROWS; ++j) woff[j] += (unsigned)kc * 16u;       // (this thread's chunk of group 0; wok lanes only are used)
+        int w_g = 0;                           // weight cursor (tapi, w_g): K chunk tapi * cpt + 8 w_g + kc, uniform but for kc
+        auto stage_w = [&](int buf) {          // the weight half of stage()
+          const bool kok = w_g * 8 < p.cpt;
+          const unsigned walk = (unsigned)(tapi * p.cpt + w_g * 8) * 16u;
+#pragma unroll
+          for (int j = 0; j < WROWS; ++j)
+            dma16_async(rw, ws_a + (unsigned)(buf * WLD + (wrow0 + RSTEP * j) * 8) * 16u, (kok && wok[j]) ? woff[j] + walk : EFFDET_OOB);
+          if (++tapi == 9) { tapi = 0; ++w_g; }
+        };
+        auto wait_keep = [&](bool w1) {        // everything but the newest slab (and, w1, the weight tile ahead of it) has landed
+          if (w1) {
+            if (slast) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(SP + WROWS) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(SP - 1 + WROWS) : "memory");
+          } else {
+            if (slast) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(SP) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(SP - 1) : "memory");
+          }
+        };
+        auto loadslab = [&](int wbuf, int sbuf, int kw3, Frags& fr) {      // loadsp with the activation rows found in the slab
+          int xi[MT];
+#pragma unroll
+          for (int b = 0; b < MT; ++b) {
+            const int e = ebase + b * estep + kw3;
+            xi[b] = sbuf * xld + e * 8 + (lq ^ ((e >> 1) & 7));
+          }
+#pragma unroll
+          for (int a = 0; a < NT; ++a) fr.wh[a] = ws[wbuf * WLD + (wn0 + a * 16 + l15) * 8 + (lq ^ lsw)];
+#pragma unroll
+          for (int b = 0; b < MT; ++b) fr.xh[b] = xs[xi[b]];
+#pragma unroll
+          for (int b = 0; b < MT; ++b) fr.xl[b] = xs[xi[b] ^ 4];             // chunk (4 + lq) ^ swizzle
+#pragma unroll
+          for (int a = 0; a < NT; ++a) fr.wl[a] = ws[wbuf * WLD + (wn0 + a * 16 + l15) * 8 + ((4 + lq) ^ lsw)];
+        };
+        const int nslab = nk / 3;              // (nk = 9 x groups)
+        int issued = 2, sissued = 1, kw3 = 0, sbuf = 0;
+        bool inflight = false;                 // the newest slab may still be landing
+        stage_slab(0); stage_w(0); stage_w(1);
+        if (nslab > 1) { stage_slab(1); sissued = 2; inflight = true; wait_keep(true); }
+        else dma_wait_all();
+        __syncthreads();
+        for (int kt = 0; kt < nk; ++kt) {
+          const int c = kt & 1;
+          loadslab(c, sbuf, kw3, f);
+          mmasp(f);
+          if (kt + 1 < nk) {
+            if (kw3 == 0 && inflight) wait_keep(false);      // weight tile kt+1 has landed; the slab issued behind it need not
+            else { dma_wait_all(); inflight = false; }
+            __syncthreads();                                 // ... for everyone, and every wave has read K-step kt's buffers
+            if (issued < nk) { stage_w(c); ++issued; }
+            if (kw3 == 2) {
+              if (sissued < nslab) { stage_slab(sbuf); ++sissued; inflight = true; }     // slab kt/3 was read for the last time
+              sbuf ^= 1; kw3 = 0;
+            } else ++kw3;
+          }
+        }
+        walked = true;
+      }
+    }
+    if (!walked) {
     int issued = 0;
     for (; issued < NS && issued < nk; ++issued) stage(issued);
     wait_tile(issued - 1);
@@ -505,6 +642,7 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
         __syncthreads();                   // ... for everyone, and every wave has read tile kt out of buffer c
         if (issued < nk) { stage(c); ++issued; }
       }
+    }
     }
     if constexpr (SPLIT == 3) {
 #pragma unroll
@@ -1298,6 +1436,14 @@ struct ConvPlan {
   int gate;                    // the kernel's GATE parameter: 0, or the operand-gate form (1 multiply, 2 Swish + multiply)
 };
 
+// Tuning knobs (effdet_tuning_set; A/B experiments and tests).  Speed only: every setting computes the same values.
+static int g_tuning[EFFDET_TUNE_COUNT] = {-1, 16384, -1, 1, -1, -1};
+// EFFDET_TUNE_ROWSLAB / env EFFDET_ROWSLAB: row-slab activation staging of the split-layout 3x3 convs (1, the default) or per-tap staging (0)
+static bool rowslab_on() {
+  if (g_tuning[EFFDET_TUNE_ROWSLAB] < 0) g_tuning[EFFDET_TUNE_ROWSLAB] = getenv("EFFDET_ROWSLAB") ? atoi(getenv("EFFDET_ROWSLAB")) : 1;
+  return g_tuning[EFFDET_TUNE_ROWSLAB] != 0;
+}
+
 template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT, int NS, int M32, int GATE>
 int launch_igemm(const ConvPlan& c, hipStream_t st) {
   if (c.lds > 48 * 1024) EFFDET_SET_MAX_LDS((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>), c.lds);
@@ -1309,7 +1455,19 @@ template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2
 int use_igemm(ConvPlan& c, int id) {
   c.k.ntiles = (c.k.Cout + BN - 1) / BN;
   c.grid = (unsigned)(c.k.mtiles * c.k.ntiles);
-  c.lds = (size_t)NS * (BM + BN) * 8 * sizeof(uint4);                    // NS-stage operand tiles
+  c.k.slab = 0; c.k.xld = BM * 8;
+  if constexpr (SPLIT >= 2 && NS == 2 && !M32) {
+    // row-slab staging (see the kernel): 3x3, stride 1, pad 1 on the channel-group-major walk, decided per segment by slab_seg_ok; the
+    // activation buffers of the launch take the largest slab among its segments, rounded up to whole 8-entry DMA pieces
+    const ConvK& k = c.k;
+    if (rowslab_on() && k.kord == 1 && k.KW == 3 && k.Kc == 9 * k.cpt && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1) {
+      int ent = 0;
+      for (int s = 0; s < k.nseg; ++s)
+        if (slab_seg_ok(k.seg[s], BN) && ((slab_entries(k.seg[s].W) + 7) & ~7) > ent) ent = (slab_entries(k.seg[s].W) + 7) & ~7;
+      if (ent) { c.k.slab = 1; c.k.xld = (ent > BM ? ent : BM) * 8; }
+    }
+  }
+  c.lds = (size_t)NS * (c.k.xld + BN * 8) * sizeof(uint4);               // NS-stage operand tiles
   if (GATE) c.lds += (size_t)((c.k.Kc + 7) >> 3) * 32 * sizeof(float);   // + the image's gate row, one float per K slot
   c.gate = GATE;
   c.launch = launch_igemm<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>;
@@ -1376,10 +1534,8 @@ static int use_pw(ConvPlan& c) {
   return c.id = 20;
 }
 
-// Tuning knobs (effdet_tuning_set; A/B experiments and tests): which persistent big-tile shape serves an eligible conv
-// (0 = off | 1 = 442 | 242 | 243 | 423; env EFFDET_IGEMM_BIG overrides the built-in default), from how many output pixels
-// per launch, and its K walk.  Speed only: every setting computes the same values.
-static int g_tuning[EFFDET_TUNE_COUNT] = {-1, 16384, -1, 1, -1};
+// Which persistent big-tile shape serves an eligible conv (0 = off | 1 = 442 | 242 | 243 | 423; env EFFDET_IGEMM_BIG overrides the
+// built-in default), from how many output pixels per launch, and its K walk: g_tuning, above.
 static int big_variant() {
   if (g_tuning[EFFDET_TUNE_IGEMM_BIG] < 0)
     g_tuning[EFFDET_TUNE_IGEMM_BIG] = getenv("EFFDET_IGEMM_BIG") ? atoi(getenv("EFFDET_IGEMM_BIG")) : EFFDET_IGEMM_BIG_DEFAULT;
@@ -1482,6 +1638,7 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c, const float* a_gate = 
   k.live = nullptr; k.live_tile0 = 0;
   k.needed = nullptr; k.needed_tile0 = 0;
   k.a_gate = a_gate;
+  k.slab = 0; k.xld = BM * 8;
   if (a_gate) {
     // operand gate: exact fp32, pointwise (the K index is the channel), one level whose images are whole numbers of 128-pixel tiles
     // (the image, hence the gate row, is workgroup-uniform), shared weights, the 128-pixel-tile kernels only
