@@ -1,6 +1,6 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h, include/effdet_affine.h,
-include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h).
+include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h, include/effdet_resample.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -135,6 +135,15 @@ class Wbf(C.Structure):          # effdet_wbf_t (include/effdet_wbf.h)
                [('flip', C.c_int * WBF_MAX_VIEWS)] + [(n, C.c_int) for n in ('V', 'B', 'top_n', 'conf_type')] + \
                [('iou_thr', C.c_float), ('skip_thr', C.c_float)] + \
                [(n, C.c_void_p) for n in ('out_score', 'out_label', 'out_boxes', 'out_count')]
+
+
+RESAMPLE_NCHW, RESAMPLE_NHWC = 0, 1                  # EFFDET_RESAMPLE_NCHW, EFFDET_RESAMPLE_NHWC
+
+
+class Resample(C.Structure):     # effdet_resample_t (include/effdet_resample.h)
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p)] + \
+               [(n, C.c_int) for n in ('src_layout', 'dtype', 'B', 'H', 'W', 'Ho', 'Wo', 'C', 'flip')] + \
+               [('src_ld', C.c_longlong), ('src_bstride', C.c_longlong)]
 
 
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
@@ -352,6 +361,12 @@ GATE_OPERAND_SIGNATURES = {
 WGRAD_PLAN_SIGNATURES = {
     'effdet_conv2d_wgrad_plan_info': 'i:pp',
 }
+# The model-input resampler (scaled TTA views, mixed-size ensembles), declared in include/effdet_resample.h (same generation, same
+# letters, same rule; tests/test_resample_host.py compares this table and Resample with that header).  The geometry travels as a
+# Resample struct in host memory (byref).
+RESAMPLE_SIGNATURES = {
+    'effdet_resample_images': 'i:ps',
+}
 WGRAD_PATHS = ('tiled', 'thin', 'split', 'stem')                                                  # EFFDET_WGRAD_PATH_* in order
 OPT_ROW, OPT_RULE_ADAMW, OPT_RULE_SGD, OPT_GATED, OPT_EMA = 8, 0, 1, 1, 2      # EFFDET_OPT_* of that header
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
@@ -380,7 +395,7 @@ def lib():
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
                 list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
                 list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
-                list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()):
+                list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -464,7 +464,9 @@ class EfficientDet(nn.Module):
         ops.TTAOptions = the batch and, with hflip, its mirror image, each through its own forward + decode + NMS, the lists merged on
         the device by weighted boxes fusion (include/effdet_wbf.h).  With hflip a PackedImages batch must hold a dense [B,H,W,C]
         tensor (ops.flip_images raises TypeError otherwise).  Under two-view 'avg' fusion a detection only one view made keeps half
-        its score."""
+        its score.  TTAOptions(scales=(0.5, 1.5)) adds the batch resampled on the device to those sizes (ops.resample_images; with
+        hflip each with its mirror image), every view a full forward at its own size; H * s and W * s must be multiples of 128.  A
+        scaled view is a PackedImages of the batch's dtype (fp32 for an NCHW batch), which the model must compute in."""
         if options is not None and not isinstance(options, ops.TTAOptions):
             raise TypeError('set_tta takes a TTAOptions or None, not %r' % (options,))
         self.tta_options = options

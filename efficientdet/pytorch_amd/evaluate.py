@@ -71,9 +71,13 @@ class EnsembleDetector:
     """Several detectors as one: every member runs its own detection pass on the batch (its own set_nms and set_tta included) and the
     lists are merged on the device by weighted boxes fusion (ops.fuse_detections) under the members' weights.  Has ``detect(images)``
     like EfficientDet and is taken as ``model`` by detections_batched, evaluate_voc and evaluate_coco.  Members may differ in family
-    (D0 with D1, raw with EMA weights) but share num_classes; they see the same image tensor, so no box is rescaled."""
+    (D0 with D1, raw with EMA weights) but share num_classes.  scales: None, or one entry per member: None or 1.0 gives the member the
+    image tensor as it is, and none of its boxes is rescaled; any other s gives it the batch resampled to (H * s, W * s)
+    (ops.resample_images; both sides whole multiples of 128, checked at the call before anything is launched) -- D0 at 512 next to D1 at
+    640 is scales=(None, 1.25) -- and its boxes are multiplied by H / (H * s) in the fusion.  A member's own set_tta applies to the
+    input that member sees."""
 
-    def __init__(self, models, weights=None, fusion=None):
+    def __init__(self, models, weights=None, fusion=None, scales=None):
         self.models = list(models)
         self.fusion = ops.WBFOptions() if fusion is None else fusion
         V = len(self.models)
@@ -84,6 +88,15 @@ class EnsembleDetector:
         if V * self.fusion.top_n > ops.WBF_MAX_IN:
             raise ValueError('EnsembleDetector: members * fusion.top_n must be <= %d' % ops.WBF_MAX_IN)
         self.weights = ops._view_weights(weights, V, 'EnsembleDetector')
+        if scales is not None:
+            scales = tuple(None if s is None or float(s) == 1.0 else float(s) for s in scales)
+            if len(scales) != V:
+                raise ValueError('EnsembleDetector: %d scales for %d members' % (len(scales), V))
+            if not all(s is None or 0.0 < s < float('inf') for s in scales):
+                raise ValueError('EnsembleDetector: scales must be positive and finite (or None), got %r' % (scales,))
+            if all(s is None for s in scales):
+                scales = None
+        self.scales = scales
         self.num_classes = int(self.models[0].num_classes)
 
     def eval(self):
@@ -101,7 +114,14 @@ class EnsembleDetector:
 
     def detections(self, images, H, W):
         """ops.model_detections' tuple for the ensemble (what that function asks a model with its own pass for)."""
-        return ops.fuse_detections([ops.model_detections(m, images, H, W) for m in self.models], self.weights, None, None, self.fusion)
+        scales = getattr(self, 'scales', None)                 # (an ensemble pickled before the option existed has no such attribute)
+        if scales is None:
+            return ops.fuse_detections([ops.model_detections(m, images, H, W) for m in self.models], self.weights, None, None, self.fusion)
+        sizes = [(H, W) if s is None else ops.scaled_size(H, W, s, 'EnsembleDetector') for s in scales]   # (every refusal before a launch)
+        views = [ops.model_detections(m, images if s is None else ops.resample_images(images, hw), hw[0], hw[1])
+                 for m, s, hw in zip(self.models, scales, sizes)]
+        muls = [float(np.float32(float(H) / float(hw[0]))) for hw in sizes]
+        return ops.fuse_detections(views, self.weights, None, muls, self.fusion)
 
     def detect(self, images):
         """-> list of (scores[K], labels[K] int64, boxes[K,4]) per image, score-descending, as EfficientDet.detect."""

@@ -1512,25 +1512,44 @@ def _view_weights(weights, V, what):
     return w
 
 
-class TTAOptions:
-    """Test-time augmentation of EfficientDet.set_tta: the image and, with hflip, its mirror image, each through the whole detection
-    path (its own forward of batch B), the lists merged by fuse_detections.  weights: one per view (None: all 1)."""
+def _tta_scales(scales):
+    """scales -> tuple of distinct positive finite floats, none equal to 1 (the unscaled view is always there)."""
+    sc = tuple(float(x) for x in scales)
+    if not all(0.0 < x < float('inf') for x in sc):
+        raise ValueError('TTAOptions: scales must be positive and finite, got %r' % (sc,))
+    if 1.0 in sc:
+        raise ValueError('TTAOptions: a scale of 1 is the base view, which is always present; got %r' % (sc,))
+    if len(set(sc)) != len(sc):
+        raise ValueError('TTAOptions: scales must be distinct, got %r' % (sc,))
+    return sc
 
-    def __init__(self, hflip=True, weights=None, fusion=None):
+
+class TTAOptions:
+    """Test-time augmentation of EfficientDet.set_tta: views of the batch, each through the whole detection path (its own forward of batch
+    B at the view's size), the lists merged by fuse_detections.  The views, in this order: the batch as given; with hflip its mirror
+    image; then for each s of scales, in the order given, the batch resampled to (H * s, W * s) (resample_images: bilinear, no
+    antialiasing) and, with hflip, that view mirrored.  num_views = (1 + len(scales)) * (2 if hflip else 1) <= 8.  weights: one per view
+    in that order (None: all 1).  H * s and W * s must be multiples of 128 (tta_view_plan checks it at the call)."""
+
+    def __init__(self, hflip=True, weights=None, fusion=None, scales=()):
         fusion = WBFOptions() if fusion is None else fusion
         if not isinstance(fusion, WBFOptions):
             raise TypeError('TTAOptions: fusion must be a WBFOptions, not %r' % (fusion,))
-        self.hflip, self.fusion = bool(hflip), fusion
+        self.hflip, self.fusion, self.scales = bool(hflip), fusion, _tta_scales(scales)
+        if self.num_views > WBF_MAX_VIEWS:
+            raise ValueError('TTAOptions: %d views (%d sizes%s) exceed the limit of %d'
+                             % (self.num_views, 1 + len(self.scales), ', each with its mirror image' if self.hflip else '', WBF_MAX_VIEWS))
         self.weights = None if weights is None else _view_weights(weights, self.num_views, 'TTAOptions')
         if self.num_views * fusion.top_n > WBF_MAX_IN:
-            raise ValueError('TTAOptions: views * fusion.top_n must be <= %d' % WBF_MAX_IN)
+            raise ValueError('TTAOptions: views * fusion.top_n must be <= %d, got %d * %d' % (WBF_MAX_IN, self.num_views, fusion.top_n))
 
     @property
     def num_views(self):
-        return 2 if self.hflip else 1
+        return (1 + len(getattr(self, 'scales', ()))) * (2 if self.hflip else 1)     # (options pickled before scales existed have none)
 
     def key(self):
-        return (self.hflip, self.weights, self.fusion.key())
+        sc = getattr(self, 'scales', ())
+        return (self.hflip, self.weights, self.fusion.key()) + ((sc,) if sc else ())
 
     def __eq__(self, other):
         return isinstance(other, TTAOptions) and self.key() == other.key()
@@ -1539,7 +1558,37 @@ class TTAOptions:
         return hash(self.key())
 
     def __repr__(self):
-        return 'TTAOptions(hflip=%r, weights=%r, fusion=%r)' % (self.hflip, self.weights, self.fusion)
+        sc = getattr(self, 'scales', ())
+        return 'TTAOptions(hflip=%r, weights=%r, fusion=%r%s)' % (self.hflip, self.weights, self.fusion, ', scales=%r' % (sc,) if sc else '')
+
+
+def scaled_size(H, W, s, what='tta_view_plan'):
+    """The size (H * s, W * s) of a scaled view: both whole numbers (within 1e-6) and multiples of 128 -- the pyramid halves five times
+    and the BiFPN upsamples by exactly 2 -- else ValueError.  Host only."""
+    hv, wv = float(H) * float(s), float(W) * float(s)
+    Hv, Wv = int(round(hv)), int(round(wv))
+    if not (0.0 < float(s) < float('inf')) or abs(hv - Hv) > 1e-6 or abs(wv - Wv) > 1e-6 or Hv < 128 or Wv < 128 or Hv % 128 or Wv % 128:
+        raise ValueError('%s: H = %d, W = %d at scale s = %r gives %r x %r; both sides of a scaled view must be whole multiples of 128'
+                         % (what, H, W, s, hv, wv))
+    return Hv, Wv
+
+
+def tta_view_plan(H, W, options):
+    """The views of TTAOptions `options` on a batch of H x W, in the documented order -> [(H_v, W_v, flip, mul, weight)]: the view's size,
+    whether it is mirrored, the factor that takes its boxes back to the batch's frame (H / H_v in fp64, rounded to fp32; both axes scale
+    by the same s, so one factor serves x and y) and its fusion weight.  ValueError for a scale whose size is not whole multiples of
+    128.  Host only: nothing is launched."""
+    if not isinstance(options, TTAOptions):
+        raise TypeError('tta_view_plan takes a TTAOptions, not %r' % (options,))
+    H, W = int(H), int(W)
+    w = options.weights if options.weights is not None else (1.0,) * options.num_views
+    plan = []
+    for s in (1.0,) + tuple(getattr(options, 'scales', ())):
+        Hv, Wv = (H, W) if s == 1.0 else scaled_size(H, W, s)
+        mul = float(np.float32(float(H) / float(Hv)))
+        for flip in ((False, True) if options.hflip else (False,)):
+            plan.append((Hv, Wv, flip, mul, w[len(plan)]))
+    return plan
 
 
 _wbf_ws = {}           # (device, B, V, top_n) -> workspace of eager calls (a capture allocates its own, from the graph's pool)
@@ -1613,6 +1662,49 @@ def flip_images(images):
     return type(images)(Map.of(torch.flip(m.tensor(), (2,)).contiguous()))
 
 
+def resample_images(images, size, flip=False, out=None):
+    """A batch at another resolution (include/effdet_resample.h: effdet_resample_images): bilinear with half-pixel centres and edge clamp,
+    no antialiasing, then mirrored left-right with flip -> a dense PackedImages of size = (H_out, W_out) in the stem conv's layout (NHWC,
+    channels zero-padded to one 16-byte chunk).  images: a contiguous NCHW fp32 [B,3,H,W] tensor (the result is fp32) or a PackedImages
+    in fp32 / bf16 (the result keeps its dtype) over any map: strided and arena slices included.  size == (H, W) without flip is
+    refused: an unscaled view is the batch itself.  out: a dense Map [B, H_out, W_out, one chunk] of the result's dtype to write into
+    (an arena slice at a 16-byte aligned address, say); None allocates one."""
+    from .efficientdet import PackedImages
+    lib = L.require('effdet_resample_images')
+    Ho, Wo = (int(v) for v in size)
+    d = L.Resample()
+    m = getattr(images, 'map', None)
+    if m is None:
+        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3:
+            raise TypeError('resample_images takes an NCHW [B,3,H,W] tensor or a PackedImages')
+        if images.dtype != torch.float32:
+            raise TypeError('resample_images: an NCHW batch must be float32, not %s (pack other dtypes as PackedImages)' % images.dtype)
+        if not images.is_contiguous():
+            raise ValueError('resample_images: the NCHW batch must be contiguous')
+        B, _, H, W = (int(v) for v in images.shape)
+        dtype, src_bytes = torch.float32, 12
+        d.src, d.src_layout, d.C, d.src_ld, d.src_bstride = L.ptr(images), L.RESAMPLE_NCHW, 3, 0, 0
+    else:
+        if m.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError('resample_images: PackedImages must be float32 or bfloat16, not %s' % m.dtype)
+        B, H, W, dtype, src_bytes = m.B, m.H, m.W, m.dtype, 3 * m.t.element_size()
+        d.src, d.src_layout, d.C, d.src_ld, d.src_bstride = m.addr(), L.RESAMPLE_NHWC, m.C, m.ld, m.bstride
+    if (Ho, Wo) == (H, W) and not flip:
+        raise ValueError('resample_images: size %r is the size of the batch: use the batch itself for an unscaled view' % ((Ho, Wo),))
+    ce = 4 if dtype == torch.float32 else 8                          # one 16-byte chunk of channels
+    if out is None:
+        out = Map.new(B, Ho, Wo, ce, dtype, images.device)
+    elif (out.B, out.H, out.W, out.C, out.ld, out.bstride, out.dtype) != (B, Ho, Wo, ce, ce, Ho * Wo * ce, dtype) or out.addr() % 16:
+        raise ValueError('resample_images: out must be a dense, 16-byte aligned [%d,%d,%d,%d] %s map' % (B, Ho, Wo, ce, dtype))
+    d.dst, d.dtype, d.flip = out.addr(), L.dtype_code(dtype), 1 if flip else 0
+    d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, Ho, Wo
+    # algorithmic bytes: four taps of three channels read and one 16-byte chunk written per output pixel
+    _timed('resample (bilinear, one output pixel per thread)', B * Ho * Wo * (4 * src_bytes + 16),
+           lambda: L.check(lib.effdet_resample_images(C.byref(d), L.stream_ptr()), 'effdet_resample_images'),
+           'BYTES B%d %dx%d->%dx%d' % (B, H, W, Ho, Wo))
+    return PackedImages(out)
+
+
 def _detections_pass(model, images, H, W):
     cls, reg, anc = model.forward_raw(images)
     boxes, score, label = decode_score(anc, reg, cls, H, W)
@@ -1622,9 +1714,11 @@ def _detections_pass(model, images, H, W):
 def model_detections(model, images, H, W, num_classes=False):
     """THE detection pass of every path (EfficientDet.detect, evaluate.detections_batched / evaluate_voc / evaluate_coco,
     graph.GraphedDetect) -> (scores [B,N], labels [B,N] int64, boxes [B,N,4], count [B] int32), model_nms's layout.  No TTA
-    (model.tta_options None): forward_raw -> decode_score -> model_nms.  With TTAOptions: one such pass per view -- separate forwards of
-    batch B, so every launch plan and summation order is the plain pass's -- and fuse_detections over them, the mirror view's boxes
-    flipped back about W.  A model that brings its own pass (evaluate.EnsembleDetector) is asked for it.  num_classes=True appends the
+    (model.tta_options None): forward_raw -> decode_score -> model_nms.  With TTAOptions: one such pass per view of tta_view_plan --
+    separate forwards of batch B, so every launch plan and summation order is the plain pass's at that size -- and fuse_detections over
+    them: a mirrored view's boxes flipped back about the view's own width, a scaled view's then multiplied by H / H_v.  The base view and
+    its mirror image are the batch and flip_images(batch); a scaled view is resample_images(batch, (H_v, W_v), flip) and decodes
+    against its own size.  A model that brings its own pass (evaluate.EnsembleDetector) is asked for it.  num_classes=True appends the
     head's class count to the tuple.  The caller holds no_grad and the f16x3 range watch."""
     own = getattr(model, 'detections', None)
     tta = getattr(model, 'tta_options', None)            # (a model pickled before the option existed has no such attribute)
@@ -1633,13 +1727,18 @@ def model_detections(model, images, H, W, num_classes=False):
     elif tta is None:
         out = _detections_pass(model, images, H, W)
     else:
-        mirror = flip_images(images) if tta.hflip else None          # (first: a batch that cannot be mirrored is refused before any launch)
+        plan = tta_view_plan(H, W, tta)                               # (first: a scale this size cannot take is refused before any launch,
+        mirror = flip_images(images) if tta.hflip else None          #  and so is a batch that cannot be mirrored)
         first = _detections_pass(model, images, H, W)
         views, flips = [first[:4]], [None]
         if tta.hflip:
             views.append(_detections_pass(model, mirror, H, W)[:4])
             flips.append(W)
-        out = fuse_detections(views, tta.weights, flips, None, tta.fusion) + first[4:]
+        for Hv, Wv, flip, _, _ in plan[len(views):]:
+            views.append(_detections_pass(model, resample_images(images, (Hv, Wv), flip), Hv, Wv)[:4])
+            flips.append(Wv if flip else None)
+        muls = [p[3] for p in plan] if getattr(tta, 'scales', ()) else None      # (no scales: no multiplier at all, as before)
+        out = fuse_detections(views, tta.weights, flips, muls, tta.fusion) + first[4:]
     return out if num_classes else out[:4]
 
 
