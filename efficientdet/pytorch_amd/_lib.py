@@ -288,6 +288,14 @@ NEEDED_SIGNATURES = {
     'effdet_live_tiles_from_map': 'i:piippppps',
     'effdet_conv2d_needed': 'i:ppis',
 }
+# The compacted 32-pixel unit lists and the flagged conv launches in the gathered form, declared in include/effdet_unit_lists.h (same
+# generation, same letters, same rule; tests/test_unit_lists_host.py compares this table with that header's prototypes).
+UNIT_LISTS_SIGNATURES = {
+    'effdet_unit_lists': 'i:ppqqpps',
+    'effdet_conv2d_needed_units': 'i:pppppis',
+    'effdet_conv2d_live_units': 'i:pppppis',
+}
+UNIT_COUNTS = 4                    # EFFDET_UNIT_COUNTS
 # The IoU-family box regression losses, declared in include/effdet_box_loss.h (same generation, same letters, same rule;
 # tests/test_box_loss_host.py compares this table with that header's prototypes).
 BOX_LOSS_SIGNATURES = {
@@ -395,7 +403,8 @@ def lib():
                 list(LOSS_OPTS_SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(CONV_PLAN_SIGNATURES.items()) + \
                 list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
                 list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
-                list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()):
+                list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
+                list(UNIT_LISTS_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -33,6 +33,7 @@
 #include "common.h"
 #include "../../../include/effdet_live_tiles.h"
 #include "../../../include/effdet_needed_tiles.h"
+#include "../../../include/effdet_unit_lists.h"
 #include "../../../include/effdet_conv_plan.h"
 #include "../../../include/effdet_gate_operand.h"
 #include <stdlib.h>
@@ -71,6 +72,10 @@ struct ConvK {
   int live_tile0;              // pixel tiles below it carry no flag and are live
   const unsigned char* needed; // SPLIT == 3 only, may be NULL: needed[mt - needed_tile0] == 0 = nobody reads pixel tile mt's result (effdet_conv2d_needed)
   int needed_tile0;            // pixel tiles below it carry no flag and are computed
+  // gathered form of a flagged launch (include/effdet_unit_lists.h; SPLIT >= 2, with live / needed set): the flagged segments' 32-pixel
+  // step flags, the list of the set ones and { n, set tile flags, gather, 0 }, all of the launch's radius; NULL = tile flags only
+  const unsigned char* uflags32; const int* units; const int* ucounts;
+  long long g_in_off; unsigned g_x_bytes;      // ONE window over the flagged segments' inputs: a gathered tile's rows come from several
   const float* a_gate;         // GATE != 0 only (effdet_conv2d_gated): [B][Cin] fp32, the activation operand is act(x) * a_gate[image][channel]
   int slab;                    // SPLIT >= 2 only: segments that pass slab_seg_ok stage one activation row slab per kernel row (see the kernel)
   int xld;                     // SPLIT >= 2 only: uint4 per activation LDS buffer (128 * 8, or the largest slab of the launch's segments)
@@ -215,54 +220,91 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   const int n_base = nt * BN;
   const int HoWo = sg.Ho * sg.Wo;
 
+  // rows lo .. hi - 1 of pixel tile mt, this workgroup's channels, as zero bytes in every output stream: split / H-split y and its split
+  // twin (the tile's channels are contiguous in a row: 32-channel groups of 128 bytes) or fp32 rows -- the same zero bytes in either
+  auto zero_rows = [&](int lo, int hi) {
+    const int rows = hi - lo, nch = min(BN, p.Cout - n_base);
+    if (p.vec_ok) {
+      const int q4 = nch >> 2;
+      for (int i = tid; i < rows * q4; i += NTHREADS) {
+        const int row = i / q4, c = i - row * q4;
+        const int m = m_base + lo + row, bi = m / HoWo, pix = m - bi * HoWo;
+        const long long o = sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + 4 * c;
+        *(uint4*)((float*)p.y + o) = make_uint4(0u, 0u, 0u, 0u);
+        if (SPLIT == 3 && p.ysplit) *(uint4*)((float*)p.ysplit + o) = make_uint4(0u, 0u, 0u, 0u);
+      }
+    } else {     // (fp32 rows off the 16-byte grid: out_f32 only, the split layouts are always aligned)
+      for (int i = tid; i < rows * nch; i += NTHREADS) {
+        const int row = i / nch, c = i - row * nch;
+        const int m = m_base + lo + row, bi = m / HoWo, pix = m - bi * HoWo;
+        ((float*)p.y)[sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + c] = 0.f;
+      }
+    }
+  };
+
+  // Gathered form of a flagged launch (include/effdet_unit_lists.h; workgroup-uniform, ahead of every barrier and DMA).  The flagged
+  // segments' set 32-pixel units are listed in p.units; workgroup row mt (a) writes the zero rows of ITS OWN tile's clear units -- the
+  // stores of the dead-tile branches below, unit by unit -- and (b) if it is one of the first ceil(n / 4) flagged rows, computes the
+  // tile whose four 32-row groups are units 4 j .. 4 j + 3 of the list, j = mt - (first flagged tile); a short tail has fewer.  Rows of
+  // set units are written by (b) of some row, rows of clear ones by (a) of their own: every row once.  A gathered tile stages its activations PER TAP on every level (a unit plus its halo is one contiguous run on
+  // the 64 and 32 pixel wide levels only; per-unit slabs are not built): a wave's 8-row DMA piece lies in one unit, so what the tile
+  // path takes from its segment -- image size, batch pitch, base -- is wave-uniform per piece, and border validity comes from the
+  // unit's own (image, h, w).  Same operands into every MFMA in the same K order as the dense tile that holds the pixel.
+  constexpr bool GCAP = SLABCAP && WTM == 32;          // (WTM == 32: a wave's output rows are one unit)
+  bool gath = false;
+  // group q of the gathered tile -> its segment (-1: none, the short tail) and first pixel there.  (Asked again by the epilogue: nothing
+  // of it stays in registers through the K loop, which runs at the register budget of the dense tiles.)
+  auto unit_of = [&](int q, int& m0) -> int {
+    const int ft0 = SPLIT == 2 ? p.live_tile0 : p.needed_tile0;
+    const int i = (mt - ft0) * 4 + q;
+    int sq = -1;
+    m0 = 0;
+    if (i < p.ucounts[0]) {
+      const int u = p.units[i];
+      int a = 0;
+#pragma unroll 1
+      for (int s = 0; s < p.nseg; ++s)
+        if (p.seg[s].tile_start >= ft0) {
+          const int ns = (p.seg[s].M + 31) >> 5;
+          if (u >= a && u < a + ns) { sq = s; m0 = (u - a) * 32; }
+          a += ns;
+        }
+    }
+    return sq;
+  };
+  if constexpr (GCAP) {
+    const unsigned char* const fl = SPLIT == 2 ? p.live : p.needed;
+    const int ft0 = SPLIT == 2 ? p.live_tile0 : p.needed_tile0;
+    if (fl && p.units && mt >= ft0 && p.ucounts[2] != 0) {
+      gath = true;
+      int s0 = (mt - sg.tile_start) * 4;               // this tile's first step among the flagged segments' steps
+#pragma unroll 1
+      for (int s = 0; s < si; ++s)
+        if (p.seg[s].tile_start >= ft0) s0 += (p.seg[s].M + 31) >> 5;
+      if (!(SPLIT == 2 && p.res_mode == EFFDET_RES_ADD)) {
+#pragma unroll 1
+        for (int q = 0; q < 4; ++q)
+          if (m_base + 32 * q < sg.M && p.uflags32[s0 + q] == 0) zero_rows(32 * q, min(32 * q + 32, sg.M - m_base));
+      }
+      if ((mt - ft0) * 4 >= p.ucounts[0]) return;
+    }
+  }
+
   if constexpr (SPLIT == 2) {
     // Dead tile (workgroup-uniform, ahead of every barrier and DMA): all its input taps are exact zeros and the launch has no bias /
     // affine / activation (the host passes flags only then), so the dense loop would produce +0 everywhere -- zeros after a ReLU mask
-    // too, and the unchanged value under an in-place RES_ADD.  Write the tile's rows (split layout or fp32: the same zero bytes, the
-    // tile's channels are contiguous in either) and leave.
-    if (p.live && mt >= p.live_tile0 && p.live[mt - p.live_tile0] == 0) {
-      if (p.res_mode == EFFDET_RES_ADD) return;
-      const int rows = min(BM, sg.M - m_base), nch = min(BN, p.Cout - n_base);
-      if (p.vec_ok) {
-        const int q4 = nch >> 2;
-        for (int i = tid; i < rows * q4; i += NTHREADS) {
-          const int row = i / q4, c = i - row * q4;
-          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
-          *(uint4*)((float*)p.y + sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + 4 * c) = make_uint4(0u, 0u, 0u, 0u);
-        }
-      } else {
-        for (int i = tid; i < rows * nch; i += NTHREADS) {
-          const int row = i / nch, c = i - row * nch;
-          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
-          ((float*)p.y)[sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + c] = 0.f;
-        }
-      }
+    // too, and the unchanged value under an in-place RES_ADD.  Write the tile's rows as zero bytes and leave.
+    if (p.live && !gath && mt >= p.live_tile0 && p.live[mt - p.live_tile0] == 0) {
+      if (p.res_mode != EFFDET_RES_ADD) zero_rows(0, min(BM, sg.M - m_base));
       return;
     }
   }
 
   if constexpr (SPLIT == 3) {
     // A tile nobody needs (workgroup-uniform, ahead of every barrier and DMA): not computed.  Its rows of every output stream are
-    // written as zero bytes -- H-split y and its split twin (the tile's channels are contiguous in a row: 32-channel groups of 128
-    // bytes), or retina_reg's fp32 rows -- so that what later multiplies them by an exact zero never meets recycled memory.
-    if (p.needed && mt >= p.needed_tile0 && p.needed[mt - p.needed_tile0] == 0) {
-      const int rows = min(BM, sg.M - m_base), nch = min(BN, p.Cout - n_base);
-      if (p.vec_ok) {
-        const int q4 = nch >> 2;
-        for (int i = tid; i < rows * q4; i += NTHREADS) {
-          const int row = i / q4, c = i - row * q4;
-          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
-          const long long o = sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + 4 * c;
-          *(uint4*)((float*)p.y + o) = make_uint4(0u, 0u, 0u, 0u);
-          if (p.ysplit) *(uint4*)((float*)p.ysplit + o) = make_uint4(0u, 0u, 0u, 0u);
-        }
-      } else {     // (fp32 rows off the 16-byte grid: out_f32 only, the split layouts are always aligned)
-        for (int i = tid; i < rows * nch; i += NTHREADS) {
-          const int row = i / nch, c = i - row * nch;
-          const int m = m_base + row, bi = m / HoWo, pix = m - bi * HoWo;
-          ((float*)p.y)[sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy + n_base + c] = 0.f;
-        }
-      }
+    // written as zero bytes so that what later multiplies them by an exact zero never meets recycled memory.
+    if (p.needed && !gath && mt >= p.needed_tile0 && p.needed[mt - p.needed_tile0] == 0) {
+      zero_rows(0, min(BM, sg.M - m_base));
       return;
     }
   }
@@ -276,17 +318,35 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   constexpr unsigned ES = sizeof(T);
   // (per-image weights: a tile never straddles images -- Ho*Wo % BM == 0, checked by the host -- so the image is workgroup-uniform)
   const long long w_img = p.w_img_bytes ? (long long)(m_base / HoWo) * p.w_img_bytes : 0ll;
-  const u32x4_t rx = make_srd_raw((const T*)p.x + sg.in_off, sg.x_bytes), rw = make_srd_raw((const char*)p.w + w_img + sg.w_off, p.w_bytes);
+  // (a gathered tile reads through one window over all flagged segments; they share weights and bias, so sg's are the units' too)
+  const u32x4_t rx = make_srd_raw((const T*)p.x + (gath ? p.g_in_off : sg.in_off), gath ? p.g_x_bytes : sg.x_bytes);
+  const u32x4_t rw = make_srd_raw((const char*)p.w + w_img + sg.w_off, p.w_bytes);
   const unsigned xs_a = lds_addr(xs), ws_a = lds_addr(ws);
   const int kc = (tid & 7) ^ ((tid >> 4) & 7), r0 = tid >> 3;
   const int wrow0 = __builtin_amdgcn_readfirstlane(wave) * 8;     // first tile row of this wave's 1-KiB DMA piece
   // (workgroup-uniform: this tile's segment stages row slabs; the host sized the buffers with the same test)
-  const bool slab = SLABCAP && p.slab && slab_seg_ok(sg, BN);
+  const bool slab = SLABCAP && p.slab && slab_seg_ok(sg, BN) && !gath;
   unsigned xoff[XROWS]; int hi0[XROWS], wi0[XROWS];
 #pragma unroll
   for (int j = 0; j < XROWS; ++j) {
     const int m = m_base + r0 + RSTEP * j;
-    if (m < sg.M && !slab) {       // (the slab path keeps its own per-entry cursors, below)
+    if (GCAP && gath) {
+      // gathered tile (3x3, stride 1, pad 1): the piece's unit is wave-uniform.  hi0 = the 9 taps' validity bits (bit 3 kh + kw) from the
+      // unit's own (image, h, w), wi0 = the width of its image, xoff = the byte offset of the row's CENTRE pixel in the gathered window
+      int m0;
+      const int sq = unit_of((wrow0 + RSTEP * j) >> 5, m0);
+      const int mm = m0 + ((r0 + RSTEP * j) & 31);
+      hi0[j] = 0; wi0[j] = 0; xoff[j] = 0;
+      if (sq >= 0 && mm < p.seg[sq].M) {
+        const SegD& us = p.seg[sq];
+        const int hw = us.H * us.W, b = mm / hw, rem = mm - b * hw;
+        const int h = rem / us.W, w = rem - h * us.W;
+        const int rowm = (w > 0 ? 1 : 0) | 2 | (w + 1 < us.W ? 4 : 0);
+        hi0[j] = (h > 0 ? rowm : 0) | (rowm << 3) | (h + 1 < us.H ? rowm << 6 : 0);
+        wi0[j] = us.W;
+        xoff[j] = (unsigned)((us.in_off - p.g_in_off + (long long)b * us.in_bs + (long long)rem * p.ldx) * ES);
+      }
+    } else if (m < sg.M && !slab) {       // (the slab path keeps its own per-entry cursors, below)
       const int b = m / HoWo, rem = m - b * HoWo;
       const int ho = rem / sg.Wo, wo = rem - ho * sg.Wo;
       hi0[j] = ho * p.stride - p.pad_t; wi0[j] = wo * p.stride - p.pad_l;
@@ -309,6 +369,12 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   int tapi = tap;                // (tap index of the channel-group-major walk: kord == 1)
   unsigned xcur[XROWS];          // current byte offset per row, or EFFDET_OOB when the tap falls outside the image
   auto retap = [&]() {
+    if (GCAP && gath) {
+#pragma unroll
+      for (int j = 0; j < XROWS; ++j)
+        xcur[j] = ((hi0[j] >> (3 * kh + kw)) & 1) ? xoff[j] + (unsigned)(((kh - 1) * wi0[j] + kw - 1) * p.ldx + cc * CE) * ES : EFFDET_OOB;
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < XROWS; ++j) {
       const int hi = hi0[j] + kh, wi = wi0[j] + kw;
@@ -836,12 +902,21 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   f32x4 scv[NT], shv[NT];
 #pragma unroll
   for (int a = 0; a < NT; ++a) scale_shift(n_base + wn0 + a * 16 + lq * 4, scv[a], shv[a]);
+  // the wave's output rows: of the tile's own segment or, gathered, of its unit's (first pixel, pixels, image size, offsets)
+  int em0 = m_base + wm0, eM = sg.M, eHW = HoWo;
+  long long eoff = sg.out_off, ebs = sg.out_bs;
+  if (GCAP && gath) {
+    const int sq = unit_of((wrow0 >> 3) / WAVES_N, em0);       // (wave-uniform, like wrow0: the group of wm0)
+    if (sq < 0) return;
+    const SegD& us = p.seg[sq];
+    eM = us.M; eHW = us.H * us.W; eoff = us.out_off; ebs = us.out_bs;
+  }
 #pragma unroll
   for (int b = 0; b < MT; ++b) {
-    const int m = m_base + wm0 + b * 16 + l15;
-    if (m >= sg.M) continue;
-    const int bi = m / HoWo, pix = m - bi * HoWo;
-    const long long orow = sg.out_off + (long long)bi * sg.out_bs + (long long)pix * p.ldy;
+    const int m = em0 + b * 16 + l15;
+    if (m >= eM) continue;
+    const int bi = m / eHW, pix = m - bi * eHW;
+    const long long orow = eoff + (long long)bi * ebs + (long long)pix * p.ldy;
     const float rs = p.rowscale ? p.rowscale[bi] : 1.0f;
 #pragma unroll
     for (int a = 0; a < NT; ++a) {
@@ -1637,6 +1712,7 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c, const float* a_gate = 
   k.w_img_bytes = p->w_image_stride;
   k.live = nullptr; k.live_tile0 = 0;
   k.needed = nullptr; k.needed_tile0 = 0;
+  k.uflags32 = nullptr; k.units = nullptr; k.ucounts = nullptr; k.g_in_off = 0; k.g_x_bytes = 0;
   k.a_gate = a_gate;
   k.slab = 0; k.xld = BM * 8;
   if (a_gate) {
@@ -1786,29 +1862,84 @@ extern "C" int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream) {
 // effdet_conv2d with per-tile liveness flags (include/effdet_live_tiles.h).  The flags are per call, like x and y, and only a hint: they
 // reach the kernel where a dead tile's dense result is known to be zero bytes (or, adding in place, no change) -- the split-layout
 // 128-pixel-tile kernels without bias, affine, row scale, activation, second output or per-image weights -- and are dropped elsewhere.
-extern "C" int effdet_conv2d_live(const effdet_conv_t* p, const unsigned char* live, int live_tile0, effdet_stream_t stream) {
-  ConvPlan c;
-  const int id = plan_conv(p, c);
-  if (id < 0) return id;
-  if (live_tile0 < 0) return EFFDET_EINVAL;
+static bool live_flags_ok(const effdet_conv_t* p, int id) {
   const bool plain = !p->scale && !p->shift && !p->rowscale && !p->bc_scale && !p->z && !p->y_split && p->act == EFFDET_ACT_NONE && !p->w_image_stride;
   bool no_shift = true;
   for (int s = 0; s < p->nseg; ++s) if (p->seg_shift[s]) no_shift = false;
   const bool res_ok = p->out_f32 ? (p->res_mode == EFFDET_RES_NONE || (p->res_mode == EFFDET_RES_ADD && p->res == p->y))
                                  : (p->res_mode == EFFDET_RES_NONE || p->res_mode == EFFDET_RES_RELU_MASK);
-  if (live && (id == 8 || id == 9) && plain && no_shift && res_ok) { c.k.live = live; c.k.live_tile0 = live_tile0; }
+  return (id == 8 || id == 9) && plain && no_shift && res_ok;
+}
+extern "C" int effdet_conv2d_live(const effdet_conv_t* p, const unsigned char* live, int live_tile0, effdet_stream_t stream) {
+  ConvPlan c;
+  const int id = plan_conv(p, c);
+  if (id < 0) return id;
+  if (live_tile0 < 0) return EFFDET_EINVAL;
+  if (live && live_flags_ok(p, id)) { c.k.live = live; c.k.live_tile0 = live_tile0; }
   return c.launch(c, (hipStream_t)stream);
 }
 
 // effdet_conv2d with "needed" flags (include/effdet_needed_tiles.h): per call, like the liveness flags above, but a statement about the
 // READERS of the output, not about the input -- so bias, activation and the second output stream do not matter, a tile that is not
 // needed is zero bytes in all of them.  They reach the f16x3 128-pixel-tile kernels (the forward RetinaHead) and are dropped elsewhere.
+static bool needed_flags_ok(const effdet_conv_t* p, const ConvPlan& c, int id) {
+  return (id == 30 || id == 31) && (c.k.vec_ok || (p->out_f32 && !p->y_split));
+}
 extern "C" int effdet_conv2d_needed(const effdet_conv_t* p, const unsigned char* needed, int needed_tile0, effdet_stream_t stream) {
   ConvPlan c;
   const int id = plan_conv(p, c);
   if (id < 0) return id;
   if (needed_tile0 < 0) return EFFDET_EINVAL;
   // (vec_ok off: only fp32 rows may leave the 16-byte grid; the split streams never do -- plan_conv has checked their offsets and pitch)
-  if (needed && (id == 30 || id == 31) && (c.k.vec_ok || (p->out_f32 && !p->y_split))) { c.k.needed = needed; c.k.needed_tile0 = needed_tile0; }
+  if (needed && needed_flags_ok(p, c, id)) { c.k.needed = needed; c.k.needed_tile0 = needed_tile0; }
+  return c.launch(c, (hipStream_t)stream);
+}
+
+// The gathered form of a flagged launch (include/effdet_unit_lists.h), on a plan whose tile flags (k.live / k.needed) are already set:
+// taken where the kernel's gathered path holds -- a 3x3, stride 1, pad 1 conv, tile0 the first tile of a segment, the flagged segments
+// sharing weights and bias, their inputs inside one 32-bit window -- and left at the tile flags everywhere else.
+static void take_units(const effdet_conv_t* p, ConvPlan& c, int tile0, const unsigned char* flags32, const int* units, const int* counts) {
+  ConvK& k = c.k;
+  if (!flags32 || !units || !counts || (!k.live && !k.needed)) return;
+  if (p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad_t != 1 || p->pad_l != 1 || p->w_image_stride) return;
+  int first = -1;
+  long long lo = 0, hi = 0;
+  for (int s = 0; s < k.nseg; ++s) {
+    const SegD& d = k.seg[s];
+    if (d.tile_start < tile0) continue;
+    if (d.Ho != d.H || d.Wo != d.W) return;
+    const long long b = d.in_off * 4, e = b + d.x_bytes;
+    if (first < 0) { if (d.tile_start != tile0) return; first = s; lo = b; hi = e; }
+    else {
+      if (d.w_off != k.seg[first].w_off || d.sh_off != k.seg[first].sh_off) return;
+      if (b < lo) lo = b;
+      if (e > hi) hi = e;
+    }
+  }
+  if (first < 0 || hi - lo >= 0xFFFF0000LL) return;
+  k.uflags32 = flags32; k.units = units; k.ucounts = counts; k.g_in_off = lo / 4; k.g_x_bytes = (unsigned)(hi - lo);
+}
+
+extern "C" int effdet_conv2d_live_units(const effdet_conv_t* p, const unsigned char* flags128, const unsigned char* flags32, const int* units,
+                                        const int* counts, int tile0, effdet_stream_t stream) {
+  ConvPlan c;
+  const int id = plan_conv(p, c);
+  if (id < 0) return id;
+  if (tile0 < 0 || !flags128 || !flags32 || !units || !counts) return EFFDET_EINVAL;
+  if (!live_flags_ok(p, id)) return EFFDET_EUNSUPPORTED;       // (a dense launch on flagged data is the caller's to ask for)
+  c.k.live = flags128; c.k.live_tile0 = tile0;
+  take_units(p, c, tile0, flags32, units, counts);
+  return c.launch(c, (hipStream_t)stream);
+}
+
+extern "C" int effdet_conv2d_needed_units(const effdet_conv_t* p, const unsigned char* flags128, const unsigned char* flags32, const int* units,
+                                          const int* counts, int tile0, effdet_stream_t stream) {
+  ConvPlan c;
+  const int id = plan_conv(p, c);
+  if (id < 0) return id;
+  if (tile0 < 0 || !flags128 || !flags32 || !units || !counts) return EFFDET_EINVAL;
+  if (!needed_flags_ok(p, c, id)) return EFFDET_EUNSUPPORTED;
+  c.k.needed = flags128; c.k.needed_tile0 = tile0;
+  take_units(p, c, tile0, flags32, units, counts);
   return c.launch(c, (hipStream_t)stream);
 }

@@ -11,10 +11,14 @@
 //                      shuffles) and over the tile (LDS), then for r = 0..5 the flags live32[r][step] = (min d <= r),
 //                      live128[r][tile] likewise -- each flag one plain store of one workgroup, no atomics, nothing assumed about
 //                      the buffers' previous content.
+//   unit_lists_kernel  (include/effdet_unit_lists.h; one workgroup per radius) live32[r] -> the ascending list of its set flags and the
+//                      counts the gathered conv launches read on the device.
 // All are plain kernel launches: capturable, no memset, no host sync.
 #include "common.h"
 #include "../../../include/effdet_live_tiles.h"
 #include "../../../include/effdet_needed_tiles.h"
+#include "../../../include/effdet_unit_lists.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -107,6 +111,45 @@ __global__ __launch_bounds__(128) void live_flags_kernel(const LiveK p) {
   }
 }
 
+// Compacted unit lists (include/effdet_unit_lists.h): workgroup r walks live32[r] in runs of 256 x 8 flags -- thread t counts its 8
+// consecutive flags, a block scan in thread order places them behind the runs before -- and writes the set flags' indices in ascending
+// order; then the set flags of live128[r] are counted the same way.  Plain stores, one writer per word.
+__global__ __launch_bounds__(256) void unit_lists_kernel(const unsigned char* l32, const unsigned char* l128, long long S32, long long S128,
+                                                         int* units, int* counts) {
+  __shared__ int wtot[4];
+  const int r = blockIdx.x, t = threadIdx.x;
+  const unsigned char* f = l32 + (long long)r * S32;
+  int* out = units + (long long)r * S32;
+  int base = 0;
+  for (long long run = 0; run < S32; run += 2048) {
+    const long long i0 = run + 8 * t;
+    int c = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) c += (i0 + e < S32 && f[i0 + e]) ? 1 : 0;
+    int total;
+    int o = base + block_scan_sum(c, wtot, &total) - c;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (i0 + e < S32 && f[i0 + e]) out[o++] = (int)(i0 + e);
+    base += total;
+  }
+  const unsigned char* g = l128 + (long long)r * S128;
+  int n128 = 0;
+  for (long long run = 0; run < S128; run += 2048) {
+    const long long i0 = run + 8 * t;
+    int c = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) c += (i0 + e < S128 && g[i0 + e]) ? 1 : 0;
+    int total;
+    (void)block_scan_sum(c, wtot, &total);
+    n128 += total;
+  }
+  if (t < EFFDET_UNIT_COUNTS) {
+    const int gt = (base + 3) >> 2;
+    counts[r * EFFDET_UNIT_COUNTS + t] = t == 0 ? base : t == 1 ? n128 : t == 2 ? (16 * gt <= 15 * n128 ? 1 : 0) : 0;
+  }
+}
+
 // geometry of the flag arrays; -> EFFDET_OK or an error
 int live_geometry(int B, int nlev, const int* H, const int* W, LiveK& k) {
   if (B < 1 || nlev < 1 || nlev > EFFDET_MAX_SEG || !H || !W) return EFFDET_EINVAL;
@@ -171,6 +214,17 @@ extern "C" int effdet_live_tiles_from_map(const unsigned char* map, int B, int n
   hipLaunchKernelGGL(live_hdist_kernel, dim3((unsigned)((k.P + 255) / 256)), dim3(256), 0, st, k);
   EFFDET_CHECK_LAUNCH();
   hipLaunchKernelGGL(live_flags_kernel, dim3((unsigned)k.ntiles), dim3(128), 0, st, k);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// The compacted lists of the set live32 flags, per radius (include/effdet_unit_lists.h)
+extern "C" int effdet_unit_lists(const unsigned char* live32, const unsigned char* live128, long long steps, long long tiles, int* units,
+                                 int* counts, effdet_stream_t stream) {
+  if (!live32 || !live128 || !units || !counts) return EFFDET_EINVAL;
+  if (steps < 1 || tiles < 1 || tiles > steps) return EFFDET_EINVAL;
+  if (steps >= 0x40000000LL) return EFFDET_EUNSUPPORTED;
+  hipLaunchKernelGGL(unit_lists_kernel, dim3(EFFDET_LIVE_RADII), dim3(256), 0, (hipStream_t)stream, live32, live128, steps, tiles, units, counts);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }

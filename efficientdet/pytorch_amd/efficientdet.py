@@ -349,10 +349,13 @@ class _HeadLossFn(torch.autograd.Function):
         levels = [m.H * m.W * 9 for m in p] if matcher is not None else None
         # the default matcher's positives are known before the head runs, and every box term reads `reg` at them alone: the regression
         # tower computes the tiles that can reach one (two small launches per step, no host read: a captured step follows its annotations)
-        need = None
+        need = need_units = None
         if matcher is None and loss is None and Fn.head_fwd_takes_needed(p, dtype, train):
-            need = ops.needed_tiles(anchors, annots, p[0].B, [(m.H, m.W) for m in p])
-        cls, reg, saved = Fn.head_fwd(p, HP, num_classes, dtype, train, reg_needed=need)
+            sizes_ = [(m.H, m.W) for m in p]
+            n32, need = ops.live_tiles_from_map(ops.positive_pixel_map(anchors, annots, sizes_), p[0].B, sizes_)
+            if Fn.HEAD_SPARSE_UNITS:      # ... and their 32-pixel units, four to a tile (one more small launch)
+                need_units = ops.UnitLists(n32, need)
+        cls, reg, saved = Fn.head_fwd(p, HP, num_classes, dtype, train, reg_needed=need, reg_units=need_units)
         nc = num_classes
         if train and nc % 4 == 0 and LOSS_FWD_GRAD:
             # ONE pass over the 15.7 MB/image of probabilities: losses + d(logits) for an upstream gradient of one, already in

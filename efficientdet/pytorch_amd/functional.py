@@ -609,6 +609,11 @@ HEAD_SPARSE_REG = os.environ.get('EFFDET_HEAD_SPARSE_REG', '1') == '1'
 # reach a positive anchor (the same geometry, read forwards); the f16x3 kernels write zeros into the rest.  Losses and gradients are bit
 # for bit the dense ones (include/effdet_needed_tiles.h).
 HEAD_SPARSE_REG_FWD = os.environ.get('EFFDET_HEAD_SPARSE_REG_FWD', '1') == '1'
+# A/B switch: the flagged forward and data-gradient launches of the regression tower in the gathered form (include/effdet_unit_lists.h):
+# the flagged 32-pixel units, four to a 128-pixel tile, instead of every tile that holds a flagged pixel -- 0.53 - 0.80 of the computed
+# tiles on the benchmark's batch (profiles/unit_count_b32_512.json).  One more small launch per pass builds the lists; the weight
+# gradients (which walk the 32-pixel flags already) do not change.  Bit for bit the tile flags' results where anything reads them.
+HEAD_SPARSE_UNITS = os.environ.get('EFFDET_HEAD_SPARSE_UNITS', '1') == '1'
 # A/B switch: in the paired head backward, the weight gradients of layer t of BOTH towers as one launch (ops.conv2d_wgrad_pair).  The
 # regression tower's flagged launch lasts as long as its few almost entirely live ranges, which are dispatched last; in one grid with the
 # classification tower's dense launch they start first and the dense blocks fill the slots behind them.  Same plans, same slabs: bit for
@@ -699,7 +704,7 @@ def _tower_layer(group, xs, wp, geo, Cin, shift=None, ysplit=False, res=None, **
     return ys, ss
 
 
-def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
+def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None, reg_units=None):
     """models/retinahead.py:109-132 for all 5 levels per launch (weights are shared across levels).
     p: 5 Maps; HP: dict of head parameter tensors.  -> classification [B,A,nc] fp32 (probabilities),
     regression [B,A,4] fp32.
@@ -710,7 +715,8 @@ def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
     runs the split-layout gradient kernels unchanged.
     reg_needed (uint8 [radius][tiles], ops.needed_tiles; f16x3 forward only): the caller reads the regression output at the flagged
     pixels alone, so layer t of the regression tower computes the tiles of row 4 - t and retina_reg those of row 0; the rest of `reg`
-    and of the tower's activations is zeros.  None: dense."""
+    and of the tower's activations is zeros.  None: dense.
+    reg_units (ops.UnitLists of the same flags, or None): those launches in the gathered form."""
     dev = p[0].t.device
     B, Wc = p[0].B, p[0].C
     sizes = [(m.H, m.W) for m in p]
@@ -718,10 +724,15 @@ def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
     split, split_bwd, hs = _head_forms(B, sizes, Wc, dtype, train)
     if not (hs and split_bwd):
         reg_needed = None
+    if reg_needed is None or not HEAD_SPARSE_UNITS:
+        reg_units = None
     geo = (B, sizes, dtype, dev, sum((B * h * w + 127) // 128 for (h, w) in sizes))
 
     def need(towers, r):
         return reg_needed[r] if (reg_needed is not None and 'reg' in towers) else None
+
+    def need_units(towers, r):
+        return reg_units.row(r) if (reg_units is not None and 'reg' in towers) else None
 
     def pack(w):
         return ops.pack_weight(w, dtype, x3=split, h3=hs)
@@ -742,13 +753,14 @@ def head_fwd(p, HP, num_classes, dtype, train, reg_needed=None):
             w = {tw: HP[f'{tw}_convs.{t}.weight'] for tw in group}
             cur, ysp = _tower_layer(group, cur, {tw: pack(w[tw]) for tw in group}, geo, w[group[0]].shape[1],
                                     shift={tw: HP[f'{tw}_convs.{t}.bias'] for tw in group}, ysplit=split_bwd, act=ACT_RELU, split=split,
-                                    hsplit=hs, needed=need(group, 4 - t))
+                                    hsplit=hs, needed=need(group, 4 - t), units=need_units(group, 4 - t))
             for tw in group:          # (split_bwd: `cur` stays plain fp32 / H-split and is not kept for backward)
                 acts[tw].append(ysp[tw] if split_bwd else cur[tw])
         for tw in group:
             buf, per, act = out[tw]
             ops.conv2d(cur[tw], pack(HP[f'retina_{tw}.weight']), head_out_maps(buf, B, sizes, per), Cin=256, Cout=9 * per, **_K3,
-                       shift=HP[f'retina_{tw}.bias'], act=act, out_f32=True, split=split, hsplit=hs, needed=need((tw,), 0))
+                       shift=HP[f'retina_{tw}.bias'], act=act, out_f32=True, split=split, hsplit=hs, needed=need((tw,), 0),
+                       units=need_units((tw,), 0))
     paired = hs and HEAD_PAIR_TOWERS         # layer t of both towers as one launch
     if paired:
         towers_fwd(('cls', 'reg'))
@@ -790,11 +802,15 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
     live = None
     if HEAD_SPARSE_REG and split and dreg_ld and (in_split or dreg.dtype == torch.float32):
         live = ops.live_tiles(dreg, B, sizes, dreg_ld, in_split)
+    ulists = ops.UnitLists(*live) if (live is not None and HEAD_SPARSE_UNITS) else None      # the data-gradient launches gather their units
     geo = (B, sizes, dtype, dev, sum((B * h * w + 127) // 128 for (h, w) in sizes))
     douts = {'cls': (dcls_logit, nc, dcls_ld), 'reg': (dreg, 4, dreg_ld)}      # tower -> (gradient, values per anchor, its pixel-major ld)
 
     def lv(towers, kind, r):
         return live[kind][r] if (live is not None and 'reg' in towers) else None
+
+    def lu(towers, r):
+        return ulists.row(r) if (ulists is not None and 'reg' in towers) else None
 
     def tower_final(tower, dout, per, pix_ld):
         """retina_cls / retina_reg: weight gradient + data gradient back into the tower (ReLU mask of its last layer fused) -> dz maps"""
@@ -827,7 +843,7 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
         # data gradient with the ReLU mask of the producing tower layer fused into the epilogue
         _, dz = pyramid_alloc(B, sizes, 256, dtype, dev)
         ops.conv2d(dzmaps, ops.pack_weight(wf, dtype, mode=1, cin_pad=Cfp, x3=split), dz, Cin=Cfp, Cout=256, **_K3, res=acts[tower][3],
-                   res_mode=RES_RELU_MASK, rowscale=rows, split=split, live=lv((tower,), 1, 1))
+                   res_mode=RES_RELU_MASK, rowscale=rows, split=split, live=lv((tower,), 1, 1), units=lu((tower,), 1))
         return dz
 
     def layer_wgrads(group, t, dz):
@@ -854,7 +870,7 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
             wd = {tw: ops.pack_weight(HP[f'{tw}_convs.{t}.weight'], dtype, mode=1, x3=split) for tw in group}
             if t > 0:
                 dz, _ = _tower_layer(group, dz, wd, geo, 256, res={tw: acts[tw][t - 1] for tw in group}, res_mode=RES_RELU_MASK,
-                                     split=split, live=lv(group, 1, 5 - t))
+                                     split=split, live=lv(group, 1, 5 - t), units=lu(group, 5 - t))
             else:
                 for tw in group:
                     last[tw] = (dz[tw], wd[tw])     # 256 -> Wc back to the neck: after the join (the towers' sum)
@@ -878,5 +894,6 @@ def head_bwd(saved, dcls_logit, dreg, dtype, dcls_ld=0, cls_gscale=None, dreg_ld
     dz, wd = last['cls']
     ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, **_K3, split=split, out_f32=split)
     dz, wd = last['reg']
-    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, **_K3, res=dp_maps, res_mode=RES_ADD, split=split, out_f32=split, live=lv(('reg',), 1, 5))
+    ops.conv2d(dz, wd, dp_maps, Cin=256, Cout=Wc, **_K3, res=dp_maps, res_mode=RES_ADD, split=split, out_f32=split, live=lv(('reg',), 1, 5),
+               units=lu(('reg',), 5))
     return dp_maps, g

@@ -497,7 +497,7 @@ def _conv_desc(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, sca
 def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=None, shift=None, act=ACT_NONE,
            res=None, res_mode=RES_NONE, rowscale=None, zs=None, out_f32=False, split=False, bc_scale=None, bc_shift=None,
            w_image_stride=0, ysplit=None, hsplit=False, seg_w=None, seg_shift=None, live=None, live_tile0=0, needed=None, needed_tile0=0,
-           a_gate=None, a_act=ACT_NONE):
+           a_gate=None, a_act=ACT_NONE, units=None):
     """Grouped implicit-GEMM conv: xs/ys (and optional zs/res) are lists of Map, one per pyramid level.
     a_gate ([B][Cin] fp32, with a_act = ACT_NONE or ACT_SWISH): the conv runs on act(xs) * a_gate[image][channel], formed in the kernel's
     operand registers (effdet_conv2d_gated) -- bit for bit conv2d(channel_scale(xs, a_gate, a_act), ...) without that pass.  Exact-fp32
@@ -514,7 +514,10 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     every other launch ignores the flags.  Same values as without, but 0 where the dense launch would give 0 * Inf = NaN.
     needed (uint8 tensor, one byte per 128-pixel tile from tile needed_tile0 on: needed_tiles()[r]): a 0 marks a tile whose result
     nobody reads; the f16x3 kernels (hsplit) do not compute it and write zeros into every output stream (ys, ysplit) instead, every
-    other launch ignores the flags.  The needed tiles hold what the dense launch gives them."""
+    other launch ignores the flags.  The needed tiles hold what the dense launch gives them.
+    units (with live or needed; UnitLists.row(r) of the same radius): the gathered form of the flagged launch (include/effdet_unit_lists.h)
+    -- the flagged 32-pixel units, four to a tile, are computed and every other row is zero bytes.  Where the planner or the device-side
+    count declines it the launch is the one with the tile flags; a launch that takes no flags at all raises."""
     d, xs, ys = _conv_desc(xs, wp, ys, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad_t=pad_t, pad_l=pad_l, scale=scale, shift=shift,
                            act=act, res=res, res_mode=res_mode, rowscale=rowscale, zs=zs, out_f32=out_f32, split=split, bc_scale=bc_scale,
                            bc_shift=bc_shift, w_image_stride=w_image_stride, ysplit=ysplit, hsplit=hsplit, seg_w=seg_w, seg_shift=seg_shift,
@@ -532,6 +535,24 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
             L.check(L.require('effdet_conv2d_gated').effdet_conv2d_gated(C.byref(d), a_gate.data_ptr(), int(a_act), L.stream_ptr()),
                     'effdet_conv2d_gated')
             GATE_OPERAND_LAUNCHES[0] += 1
+    elif units is not None:
+        assert (live is None) != (needed is None)
+        name = 'effdet_conv2d_live_units' if live is not None else 'effdet_conv2d_needed_units'
+        f128, tile0 = (live, live_tile0) if live is not None else (needed, needed_tile0)
+        f32, ulist, ucount = units
+        assert f32.dtype == torch.uint8 and f32.is_contiguous() and ulist.dtype == torch.int32 and ulist.is_contiguous()
+        assert ucount.dtype == torch.int32 and ucount.is_contiguous() and ucount.numel() == L.UNIT_COUNTS
+        nstep, t_ = 0, 0                       # steps of the flagged segments: those from tile tile0 on
+        for y in ys:
+            if t_ >= tile0:
+                nstep += (y.B * y.H * y.W + 31) // 32
+            t_ += (y.B * y.H * y.W + 127) // 128
+        assert f32.numel() == nstep and ulist.numel() == nstep, (f32.numel(), ulist.numel(), nstep)
+        if needed is not None:
+            NEEDED_LAUNCHES[0] += 1
+        UNIT_LAUNCHES[0] += 1
+        run = lambda: L.check(getattr(L.require(name), name)(C.byref(d), f128.data_ptr(), f32.data_ptr(), ulist.data_ptr(), ucount.data_ptr(),
+                                                            int(tile0), L.stream_ptr()), name)
     elif live is not None:
         run = lambda: L.check(L.require('effdet_conv2d_live').effdet_conv2d_live(C.byref(d), live.data_ptr(), int(live_tile0), L.stream_ptr()),
                               'effdet_conv2d_live')
@@ -547,6 +568,7 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
 
 
 NEEDED_LAUNCHES = [0]        # conv2d(..., needed=...) calls made so far (tests: which path a step took)
+UNIT_LAUNCHES = [0]          # conv2d(..., units=...) calls made so far
 GATE_OPERAND_LAUNCHES = [0, 0]     # conv2d(..., a_gate=...) / conv2d_wgrad(..., a_gate=...) calls made so far (tests: which path a step took)
 
 
@@ -951,6 +973,25 @@ def live_tiles_from_map(pixmap, B, sizes):
     L.check(lib_.effdet_live_tiles_from_map(pixmap.data_ptr(), B, n, Hs, Ws, scratch.data_ptr(), l32.data_ptr(), l128.data_ptr(),
                                             L.stream_ptr()), 'effdet_live_tiles_from_map')
     return l32, l128
+
+
+class UnitLists:
+    """The flags of one pyramid with their compacted 32-pixel unit lists (include/effdet_unit_lists.h): live32 [6][steps], live128
+    [6][tiles] uint8 as live_tiles returns them, units [6][steps] int32 (row r: the indices of live32[r]'s set flags, ascending, in its
+    first counts[r][0] entries) and counts [6][4] int32 = {set steps, set tiles, gather, 0} per radius.  One more launch."""
+
+    def __init__(self, live32, live128):
+        R, S = live32.shape
+        assert live32.dtype == torch.uint8 and live128.dtype == torch.uint8 and live32.is_contiguous() and live128.is_contiguous() and R == L.LIVE_RADII
+        self.live32, self.live128 = live32, live128
+        buf = torch.empty(R * S + R * L.UNIT_COUNTS, dtype=torch.int32, device=live32.device)
+        self.units, self.counts = buf[:R * S].view(R, S), buf[R * S:].view(R, L.UNIT_COUNTS)
+        L.check(L.require('effdet_unit_lists').effdet_unit_lists(live32.data_ptr(), live128.data_ptr(), S, live128.shape[1], self.units.data_ptr(),
+                                                                 self.counts.data_ptr(), L.stream_ptr()), 'effdet_unit_lists')
+
+    def row(self, r):
+        """conv2d's units= for radius r"""
+        return self.live32[r], self.units[r], self.counts[r]
 
 
 def needed_tiles(anc, annots, B, sizes):
