@@ -7,5 +7,7 @@ reference's nn.Module surface).  See DESIGN.md / INTEGRATION.md.
 from .checkpoint import get_state_dict  # noqa: F401
 from .config import EFFICIENTDET, MODEL_MAP  # noqa: F401
 from .efficientdet import EfficientDet, PackedImages  # noqa: F401
-from .ops import ATSSOptions, BoxLossOptions, LossOptions, NMSOptions, TTAOptions, WBFOptions  # noqa: F401
+from .evaluate import SlicedDetector  # noqa: F401
+from .ops import (ATSSOptions, BoxLossOptions, LossOptions, NMSOptions, SliceMergeOptions, SliceOptions, TTAOptions,  # noqa: F401
+                  WBFOptions)
 from .synthetic import synthetic_batch  # noqa: F401

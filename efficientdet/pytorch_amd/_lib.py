@@ -1,6 +1,6 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h, include/effdet_affine.h,
-include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h, include/effdet_resample.h).
+include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h, include/effdet_resample.h, include/effdet_slices.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -144,6 +144,27 @@ class Resample(C.Structure):     # effdet_resample_t (include/effdet_resample.h)
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p)] + \
                [(n, C.c_int) for n in ('src_layout', 'dtype', 'B', 'H', 'W', 'Ho', 'Wo', 'C', 'flip')] + \
                [('src_ld', C.c_longlong), ('src_bstride', C.c_longlong)]
+
+
+SLICE_MAX_TILES, SLICE_MAX_IN = 1024, 8192           # EFFDET_SLICE_MAX_TILES, EFFDET_SLICE_MAX_IN
+SLICE_NMS, SLICE_NMM, SLICE_IOU, SLICE_IOS = 0, 1, 0, 1     # EFFDET_SLICE_* method and metric
+
+
+class SliceTile(C.Structure):    # effdet_slice_tile_t (include/effdet_slices.h)
+    _fields_ = [('x0', C.c_int), ('y0', C.c_int), ('mx', C.c_float), ('my', C.c_float)]
+
+
+class SliceImages(C.Structure):  # effdet_slice_images_t (include/effdet_slices.h)
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('tiles', C.c_void_p)] + \
+               [(n, C.c_int) for n in ('src_layout', 'dtype', 'B', 'H', 'W', 'C', 'T', 't0', 't1', 'h', 'w')] + \
+               [('src_ld', C.c_longlong), ('src_bstride', C.c_longlong)]
+
+
+class SliceMerge(C.Structure):   # effdet_slice_merge_t (include/effdet_slices.h)
+    _fields_ = [(n, C.c_void_p) for n in ('score', 'label', 'boxes', 'count', 'tiles')] + \
+               [(n, C.c_int) for n in ('B', 'TPI', 'R', 'method', 'metric', 'class_aware', 'max_det')] + \
+               [(n, C.c_float) for n in ('W', 'H', 'thr', 'skip_thr')] + \
+               [(n, C.c_void_p) for n in ('out_score', 'out_label', 'out_boxes', 'out_count')]
 
 
 TAIL_UNPACK, TAIL_SE_PARAMS, TAIL_DW_UNPACK = 0, 1, 2
@@ -375,7 +396,15 @@ WGRAD_PLAN_SIGNATURES = {
 RESAMPLE_SIGNATURES = {
     'effdet_resample_images': 'i:ps',
 }
-WGRAD_PATHS = ('tiled', 'thin', 'split', 'stem')                                                  # EFFDET_WGRAD_PATH_* in order
+# Sliced inference (tile extractor, cross-tile merge), declared in include/effdet_slices.h (same generation, same letters, same rule;
+# tests/test_slices_host.py compares this table and SliceTile / SliceImages / SliceMerge with that header).  Geometry and options travel
+# as structs in host memory (byref).
+SLICES_SIGNATURES = {
+    'effdet_slice_images': 'i:ps',
+    'effdet_slice_merge_workspace_bytes': 'q:iii',
+    'effdet_slice_merge': 'i:ppqs',
+}
+WGRAD_PATHS = ('tiled', 'thin', 'split', 'stem')                                                 # EFFDET_WGRAD_PATH_* in order
 OPT_ROW, OPT_RULE_ADAMW, OPT_RULE_SGD, OPT_GATED, OPT_EMA = 8, 0, 1, 1, 2      # EFFDET_OPT_* of that header
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
 LIVE_RADII = 6                     # EFFDET_LIVE_RADII: flags for dilation radius 0 .. 5
@@ -404,7 +433,7 @@ def lib():
                 list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
                 list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
                 list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
-                list(UNIT_LISTS_SIGNATURES.items()):
+                list(UNIT_LISTS_SIGNATURES.items()) + list(SLICES_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -136,6 +136,77 @@ class EnsembleDetector:
         return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
 
 
+class SlicedDetector:
+    """A detector for images larger than its network input (sliced inference, SAHI): the batch is cut into overlapping tiles of
+    options.slice on the device (ops.slice_images), the tiles go through ``model``'s own detection pass tile_batch at a time (its
+    set_nms and set_tta apply per tile), with options.full_view the whole image resampled to the tile size (ops.resample_images) goes
+    through one more pass of batch B, and the lists are moved into the image's frame and merged on the device (ops.merge_slices).
+    ``model``: an EfficientDet or an EnsembleDetector.  Has ``detect(images)`` like EfficientDet and is taken as ``model`` by
+    detections_batched, evaluate_voc and evaluate_coco.  images: an NCHW fp32 batch or a PackedImages of any H x W >= the slice, one
+    size per batch; the tiles are PackedImages of the batch's dtype (fp32 for an NCHW batch), which the model must compute in.  A batch
+    of exactly the slice's size is one tile: it goes through ``model``'s own pass as it is and nothing is merged."""
+
+    def __init__(self, model, options=None):
+        options = ops.SliceOptions() if options is None else options
+        if not isinstance(options, ops.SliceOptions):
+            raise TypeError('SlicedDetector: options must be a SliceOptions, not %r' % (options,))
+        if not hasattr(model, 'num_classes') or not (hasattr(model, 'forward_raw') or hasattr(model, 'detections')):
+            raise TypeError('SlicedDetector: model must be an EfficientDet or an EnsembleDetector, not %r' % (model,))
+        self.model, self.options = model, options
+        self.num_classes = int(model.num_classes)
+
+    def eval(self):
+        self.model.eval()
+        return self
+
+    def train(self, mode=True):
+        self.model.train(mode)
+        return self
+
+    def parameters(self):
+        return self.model.parameters()
+
+    def detections(self, images, H, W):
+        """ops.model_detections' tuple for the sliced pass (what that function asks a model with its own pass for)."""
+        o = self.options
+        h, w = o.slice
+        plan = ops.slice_plan(H, W, o)                                # (first: every refusal comes before any launch)
+        if len(plan) == 1:                                            # the image is one tile: the model's own pass, nothing to merge
+            return ops.model_detections(self.model, images, H, W)
+        full = o.full_view and (int(H), int(W)) != (h, w)             # (slice_plan's rule: its last record is then the whole image)
+        B, TPI = int(images.shape[0]), len(plan)
+        T = TPI - (1 if full else 0)
+        table = ops.slice_table(plan, images.device)
+        cut = ops.slice_table(plan[:T], images.device)                # (the flat tile index counts the T tiles: the full view is not one)
+        parts = []
+        for t0 in range(0, B * T, o.tile_batch):
+            tiles = ops.slice_images(images, cut, (h, w), t0, min(t0 + o.tile_batch, B * T))
+            parts.append(ops.model_detections(self.model, tiles, h, w))
+        whole = ops.model_detections(self.model, ops.resample_images(images, (h, w)), h, w) if full else None
+        R = min(o.merge.top_n, int(parts[0][0].shape[1]))
+
+        def gather(i, tail):
+            t = torch.cat([p[i][:, :R] for p in parts]).reshape((B, T, R) + tail)
+            return t if whole is None else torch.cat([t, whole[i][:, None, :R]], dim=1)
+        count = torch.cat([p[3] for p in parts]).reshape(B, T)
+        if whole is not None:
+            count = torch.cat([count, whole[3][:, None]], dim=1)
+        return ops.merge_slices((gather(0, ()), gather(1, ()), gather(2, (4,)), count), table, H, W, o.merge)
+
+    def detect(self, images):
+        """-> list of (scores[K], labels[K] int64, boxes[K,4]) per image, score-descending, as EfficientDet.detect."""
+        members = getattr(self.model, 'models', [self.model])
+        f16x3 = any(ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3' for m in members)
+        if f16x3:
+            ops.clear_range_flag(images.device)
+        with torch.no_grad():
+            s, l, b, count = self.detections(images, int(images.shape[2]), int(images.shape[3]))
+        counts = count.tolist()
+        if f16x3 and not torch.cuda.is_current_stream_capturing():
+            ops.check_range_flag(s.device)
+        return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
+
+
 def all_detections_rows(dets, counts, num_classes):
     """eval.py:118-123: per image, per label -> [n,5] arrays (boxes + score)."""
     rows = []

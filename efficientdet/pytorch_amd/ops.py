@@ -1783,6 +1783,248 @@ def model_detections(model, images, H, W, num_classes=False):
     return out if num_classes else out[:4]
 
 
+# ----------------------------------------------------------------------------- sliced inference
+SLICE_METHODS = {'nms': L.SLICE_NMS, 'nmm': L.SLICE_NMM}          # EFFDET_SLICE_NMS, EFFDET_SLICE_NMM
+SLICE_METRICS = {'iou': L.SLICE_IOU, 'ios': L.SLICE_IOS}          # EFFDET_SLICE_IOU, EFFDET_SLICE_IOS
+SLICE_MAX_TILES, SLICE_MAX_IN = L.SLICE_MAX_TILES, L.SLICE_MAX_IN
+
+
+class SliceMergeOptions:
+    """The cross-tile merge of merge_slices (effdet_slice_merge): candidates in score order; a keeper takes every later candidate whose
+    metric with the keeper's own box is > thr ('iou', or 'ios': intersection over the smaller box, which is what lets a full box absorb
+    one truncated at a tile edge) and, with class_aware, whose label is the keeper's.  'nms' drops what a keeper takes, 'nmm' also
+    grows the keeper's box to the hull of what it took.  Rows scoring below skip_thr take no part; of every tile the first top_n rows
+    take part (lists * top_n <= 8192); at most max_det detections per image come out."""
+
+    def __init__(self, method='nmm', metric='ios', thr=0.5, class_aware=True, skip_thr=0.0, top_n=256, max_det=300):
+        if method not in SLICE_METHODS:
+            raise ValueError('SliceMergeOptions: method must be one of %s, not %r' % (sorted(SLICE_METHODS), method))
+        if metric not in SLICE_METRICS:
+            raise ValueError('SliceMergeOptions: metric must be one of %s, not %r' % (sorted(SLICE_METRICS), metric))
+        if not 0.0 <= float(thr) <= 1.0:
+            raise ValueError('SliceMergeOptions: thr must be in [0, 1]')
+        if not 0.0 <= float(skip_thr) < float('inf'):
+            raise ValueError('SliceMergeOptions: skip_thr must be finite and >= 0')
+        if not 1 <= int(top_n) <= SLICE_MAX_IN:
+            raise ValueError('SliceMergeOptions: top_n must be in 1..%d' % SLICE_MAX_IN)
+        if not 1 <= int(max_det) <= SLICE_MAX_IN:
+            raise ValueError('SliceMergeOptions: max_det must be in 1..%d' % SLICE_MAX_IN)
+        self.method, self.metric, self.thr, self.class_aware = method, metric, float(thr), bool(class_aware)
+        self.skip_thr, self.top_n, self.max_det = float(skip_thr), int(top_n), int(max_det)
+
+    def key(self):
+        return (self.method, self.metric, self.thr, self.class_aware, self.skip_thr, self.top_n, self.max_det)
+
+    def __eq__(self, other):
+        return isinstance(other, SliceMergeOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'SliceMergeOptions(method=%r, metric=%r, thr=%r, class_aware=%r, skip_thr=%r, top_n=%d, max_det=%d)' % self.key()
+
+
+class SliceOptions:
+    """Sliced inference of evaluate.SlicedDetector: the image is cut into tiles of slice = (h, w) (whole multiples of 128: a tile is a
+    network input) that overlap by overlap = (ratio_y, ratio_x) of the tile, each in [0, 0.9]; with full_view the whole image resampled
+    to (h, w) is one more view; the tiles go through the detector tile_batch at a time; merge: the SliceMergeOptions (None: defaults)."""
+
+    def __init__(self, slice=(512, 512), overlap=(0.2, 0.2), full_view=True, tile_batch=32, merge=None):
+        merge = SliceMergeOptions() if merge is None else merge
+        if not isinstance(merge, SliceMergeOptions):
+            raise TypeError('SliceOptions: merge must be a SliceMergeOptions, not %r' % (merge,))
+        try:
+            sl, ov = tuple(int(v) for v in slice), tuple(float(v) for v in overlap)
+            whole = all(float(v) == int(v) for v in slice)
+        except TypeError:
+            raise ValueError('SliceOptions: slice and overlap take one entry per axis: (h, w) and (ratio_y, ratio_x)') from None
+        if len(sl) != 2 or not whole or not all(v >= 128 and v % 128 == 0 for v in sl):
+            raise ValueError('SliceOptions: both sides of slice must be whole multiples of 128, got %r' % (slice,))
+        if len(ov) != 2 or not all(0.0 <= v <= 0.9 for v in ov):
+            raise ValueError('SliceOptions: overlap ratios must be in [0, 0.9], got %r' % (overlap,))
+        if not int(tile_batch) >= 1:
+            raise ValueError('SliceOptions: tile_batch must be >= 1')
+        self.slice, self.overlap, self.full_view, self.tile_batch, self.merge = sl, ov, bool(full_view), int(tile_batch), merge
+
+    def key(self):
+        return (self.slice, self.overlap, self.full_view, self.tile_batch, self.merge.key())
+
+    def __eq__(self, other):
+        return isinstance(other, SliceOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'SliceOptions(slice=%r, overlap=%r, full_view=%r, tile_batch=%d, merge=%r)' % (self.slice, self.overlap, self.full_view,
+                                                                                             self.tile_batch, self.merge)
+
+
+def _slice_positions(L_, s, ratio, side):
+    """Tile origins along an axis of length L_: k * step while the tile ends before L_, then L_ - s (the last tile is shifted back
+    into the image, not shrunk)."""
+    if L_ < s:
+        raise ValueError('slice_plan: the image %s %d is smaller than the slice %s %d: an image smaller than the slice needs no slicing'
+                         % (side, L_, side, s))
+    step = s - int(np.floor(ratio * s))
+    pos, k = [], 0
+    while k * step + s < L_:
+        pos.append(k * step)
+        k += 1
+    return pos + [L_ - s]
+
+
+def slice_plan(H, W, options):
+    """The views of SliceOptions `options` on a batch of H x W -> [(y0, x0, h, w, my, mx)], tiles row-major (y outer): origin, size
+    and the multipliers that take a view's boxes back to the image's frame (1 for a tile).  With full_view one more record goes last:
+    the whole image at (0, 0) as an h x w view, my = fp32(H / h), mx = fp32(W / w) (anisotropic when the image's shape is not the
+    tile's); (H, W) == (h, w) is one tile and no full view.  ValueError for an image smaller than the slice and for more candidates
+    than the merge holds.  Host only: nothing is launched."""
+    if not isinstance(options, SliceOptions):
+        raise TypeError('slice_plan takes a SliceOptions, not %r' % (options,))
+    H, W = int(H), int(W)
+    h, w = options.slice
+    ys = _slice_positions(H, h, options.overlap[0], 'height')
+    xs = _slice_positions(W, w, options.overlap[1], 'width')
+    plan = [(y, x, h, w, 1.0, 1.0) for y in ys for x in xs]
+    if options.full_view and (H, W) != (h, w):
+        plan.append((0, 0, h, w, float(np.float32(float(H) / float(h))), float(np.float32(float(W) / float(w)))))
+    what = '%d x %d at slice %r, overlap %r gives %d x %d tiles%s' % (H, W, options.slice, options.overlap, len(ys), len(xs),
+                                                                      ' and the full view' if len(plan) > len(ys) * len(xs) else '')
+    if len(plan) > SLICE_MAX_TILES:
+        raise ValueError('slice_plan: %s: %d views exceed the limit of %d' % (what, len(plan), SLICE_MAX_TILES))
+    if len(plan) * options.merge.top_n > SLICE_MAX_IN:
+        raise ValueError('slice_plan: %s; views * merge.top_n = %d * %d exceeds %d: raise the slice, lower the overlap or lower merge.top_n'
+                         % (what, len(plan), options.merge.top_n, SLICE_MAX_IN))
+    return plan
+
+
+_slice_tables = {}     # (device, plan) -> the plan's device table: built once, so that a call copies nothing from the host
+_slice_ws = {}         # (device, B, TPI, R) -> workspace of eager calls (a capture allocates its own, from the graph's pool)
+
+
+def slice_table(plan, device):
+    """The device tile table (effdet_slice_tile_t records as an int32 [T, 4] tensor: x0, y0 and the bits of mx, my) of a slice_plan
+    list, or of any list of (y0, x0, h, w, my, mx); cached per device and plan."""
+    device = torch.device(device)
+    k = (device.type, device.index if device.index is not None else torch.cuda.current_device(), tuple(tuple(r) for r in plan))
+    t = _slice_tables.get(k)
+    if t is None:
+        rec = np.zeros((len(plan), 4), dtype=np.int32)
+        for i, (y0, x0, _, _, my, mx) in enumerate(plan):
+            rec[i, 0], rec[i, 1] = int(x0), int(y0)
+            rec[i, 2:] = np.asarray([mx, my], dtype=np.float32).view(np.int32)
+        t = _slice_tables[k] = torch.from_numpy(rec).to(device)
+    return t
+
+
+def _as_slice_table(plan_or_table, device):
+    if torch.is_tensor(plan_or_table):
+        t = plan_or_table
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous() or t.shape[0] < 1 or t.data_ptr() % 16:
+            raise ValueError('a tile table is a contiguous, 16-byte aligned int32 [T, 4] tensor (slice_table makes one)')
+        return t
+    if not len(plan_or_table):
+        raise ValueError('a tile plan needs at least one tile')
+    return slice_table(plan_or_table, device)
+
+
+def slice_images(images, plan_or_table, size, t0, t1, out=None):
+    """Tiles of a batch (include/effdet_slices.h: effdet_slice_images) -> a dense PackedImages [t1 - t0, h, w] with size = (h, w) in the
+    stem conv's layout (NHWC, channels zero-padded to one 16-byte chunk): the flat tiles t0 <= t < t1 of the image-major order
+    t = b * T + j, pixels copied bit for bit, origins outside the image edge-clamped.  images: a contiguous NCHW fp32 [B,3,H,W] tensor
+    (the result is fp32) or a PackedImages in fp32 / bf16 (the result keeps its dtype) over any map.  plan_or_table: a slice_plan list
+    or a slice_table tensor.  out: a dense Map [t1 - t0, h, w, one chunk] of the result's dtype to write into; None allocates one."""
+    from .efficientdet import PackedImages
+    lib = L.require('effdet_slice_images')
+    h, w = (int(v) for v in size)
+    t0, t1 = int(t0), int(t1)
+    d = L.SliceImages()
+    m = getattr(images, 'map', None)
+    if m is None:
+        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3:
+            raise TypeError('slice_images takes an NCHW [B,3,H,W] tensor or a PackedImages')
+        if images.dtype != torch.float32:
+            raise TypeError('slice_images: an NCHW batch must be float32, not %s (pack other dtypes as PackedImages)' % images.dtype)
+        if not images.is_contiguous():
+            raise ValueError('slice_images: the NCHW batch must be contiguous')
+        B, _, H, W = (int(v) for v in images.shape)
+        dtype, src_bytes = torch.float32, 12
+        d.src, d.src_layout, d.C, d.src_ld, d.src_bstride = L.ptr(images), L.RESAMPLE_NCHW, 3, 0, 0
+    else:
+        if m.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError('slice_images: PackedImages must be float32 or bfloat16, not %s' % m.dtype)
+        B, H, W, dtype, src_bytes = m.B, m.H, m.W, m.dtype, 3 * m.t.element_size()
+        d.src, d.src_layout, d.C, d.src_ld, d.src_bstride = m.addr(), L.RESAMPLE_NHWC, m.C, m.ld, m.bstride
+    table = _as_slice_table(plan_or_table, images.device)
+    T = int(table.shape[0])
+    if not 0 <= t0 < t1 <= B * T:
+        raise ValueError('slice_images: the tile range [%d, %d) is not inside [0, %d) (%d images of %d tiles)' % (t0, t1, B * T, B, T))
+    n = t1 - t0
+    ce = 4 if dtype == torch.float32 else 8                          # one 16-byte chunk of channels
+    if out is None:
+        out = Map.new(n, h, w, ce, dtype, images.device)
+    elif (out.B, out.H, out.W, out.C, out.ld, out.bstride, out.dtype) != (n, h, w, ce, ce, h * w * ce, dtype) or out.addr() % 16:
+        raise ValueError('slice_images: out must be a dense, 16-byte aligned [%d,%d,%d,%d] %s map' % (n, h, w, ce, dtype))
+    d.dst, d.tiles, d.dtype = out.addr(), L.ptr(table), L.dtype_code(dtype)
+    d.B, d.H, d.W, d.T, d.t0, d.t1, d.h, d.w = B, H, W, T, t0, t1, h, w
+    # algorithmic bytes: three channels read and one 16-byte chunk written per output pixel
+    _timed('slice_images (copy, one output pixel per thread)', n * h * w * (src_bytes + 16),
+           lambda: L.check(lib.effdet_slice_images(C.byref(d), L.stream_ptr()), 'effdet_slice_images'),
+           'BYTES B%d %dx%d tiles %d..%d of %dx%d' % (B, H, W, t0, t1, h, w))
+    return PackedImages(out)
+
+
+def merge_slices(lists, table, H, W, options=None):
+    """The cross-tile merge (include/effdet_slices.h: effdet_slice_merge) of the detection lists of every view of a batch -> (scores
+    [B,K], labels [B,K] int64, boxes [B,K,4], count [B] int32) with K = min(options.max_det, TPI * R): detections of the H x W image
+    score-descending, count[b] of them valid, zero rows after them -- model_nms's layout.  lists: (scores [B,TPI,R], labels [B,TPI,R]
+    int64, boxes [B,TPI,R,4], count [B,TPI] int32), each list (b, j) in tile j's frame as model_nms returns it, narrowed to R columns;
+    table: the slice_plan list or slice_table tensor of the TPI views.  options.top_n is not applied here: R is.  All on device, no sync."""
+    lib = L.require('effdet_slice_merge', 'effdet_slice_merge_workspace_bytes')
+    options = SliceMergeOptions() if options is None else options
+    s, l, b, c = lists
+    if s.dim() != 3 or tuple(l.shape) != tuple(s.shape) or tuple(b.shape) != tuple(s.shape) + (4,) or tuple(c.shape) != tuple(s.shape[:2]):
+        raise ValueError('merge_slices: lists must be scores [B,TPI,R], labels [B,TPI,R], boxes [B,TPI,R,4], count [B,TPI]')
+    if (s.dtype, l.dtype, b.dtype, c.dtype) != (torch.float32, torch.int64, torch.float32, torch.int32):
+        raise TypeError('merge_slices: lists must be (float32, int64, float32, int32) tensors')
+    B, TPI, R = (int(v) for v in s.shape)
+    dev = s.device
+    table = _as_slice_table(table, dev)
+    if int(table.shape[0]) != TPI:
+        raise ValueError('merge_slices: %d lists per image but %d tiles in the table' % (TPI, int(table.shape[0])))
+    if B < 1 or R < 1 or TPI > SLICE_MAX_TILES or TPI * R > SLICE_MAX_IN:
+        raise ValueError('merge_slices: B >= 1, R >= 1, TPI <= %d and TPI * R <= %d, got B = %d, TPI * R = %d * %d'
+                         % (SLICE_MAX_TILES, SLICE_MAX_IN, B, TPI, R))
+    if not (0.0 < float(H) < float('inf') and 0.0 < float(W) < float('inf')):
+        raise ValueError('merge_slices: H and W must be positive and finite')
+    s, l, b, c = s.contiguous(), l.contiguous(), b.contiguous(), c.contiguous()
+    K = min(options.max_det, TPI * R)
+    d = L.SliceMerge()
+    d.score, d.label, d.boxes, d.count, d.tiles = L.ptr(s), L.ptr(l), L.ptr(b), L.ptr(c), L.ptr(table)
+    d.B, d.TPI, d.R, d.method, d.metric = B, TPI, R, SLICE_METHODS[options.method], SLICE_METRICS[options.metric]
+    d.class_aware, d.max_det, d.W, d.H, d.thr, d.skip_thr = int(options.class_aware), K, float(W), float(H), options.thr, options.skip_thr
+    os_ = torch.empty((B, K), dtype=torch.float32, device=dev)
+    ol = torch.empty((B, K), dtype=torch.int64, device=dev)
+    ob = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    d.out_score, d.out_label, d.out_boxes, d.out_count = L.ptr(os_), L.ptr(ol), L.ptr(ob), L.ptr(count)
+    nbytes = int(lib.effdet_slice_merge_workspace_bytes(B, TPI, R))
+    if torch.cuda.is_current_stream_capturing():
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    else:
+        k = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), B, TPI, R)
+        ws = _slice_ws.get(k)
+        if ws is None:
+            ws = _slice_ws[k] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    # algorithmic bytes: every list's rows read once (score, label, box: 28 B), the merged rows written once; the greedy pass is LDS / latency
+    _timed('slice_merge (keys + radix sort + per-image greedy pass)', 28 * B * TPI * R + 28 * B * K,
+           lambda: L.check(lib.effdet_slice_merge(C.byref(d), L.ptr(ws), nbytes, L.stream_ptr()), 'effdet_slice_merge'),
+           'BYTES B%d TPI%d R%d' % (B, TPI, R))
+    return os_, ol, ob, count
+
+
 # ----------------------------------------------------------------------------- loss
 # Three sets of entry points, one per kind of call: effdet_focal_loss_* (the reference's constants), effdet_box_loss_* (an IoU-family
 # box term: kind, weight) and effdet_loss_opts_* (non-default LossOptions: the struct, with the box term inside it).  They take the same
