@@ -8,6 +8,6 @@ from .checkpoint import get_state_dict  # noqa: F401
 from .config import EFFICIENTDET, MODEL_MAP  # noqa: F401
 from .efficientdet import EfficientDet, PackedImages  # noqa: F401
 from .evaluate import SlicedDetector  # noqa: F401
-from .ops import (ATSSOptions, BoxLossOptions, LossOptions, NMSOptions, SliceMergeOptions, SliceOptions, TTAOptions,  # noqa: F401
-                  WBFOptions)
+from .ops import (ATSSOptions, BoxLossOptions, LossOptions, NMSOptions, QualityLossOptions, SliceMergeOptions, SliceOptions,  # noqa: F401
+                  TTAOptions, WBFOptions)
 from .synthetic import synthetic_batch  # noqa: F401

@@ -4,6 +4,8 @@
 //
 //   focal policy  FocalDefault: alpha 0.25, gamma 2 as q * q, __logf, contraction left to the compiler (the reference's constants)
 //                 FocalP:       alpha / gamma / label smoothing as launch arguments, exp2f(gamma log2f(u)), no contraction
+//                 FocalQfl / FocalVfl: the quality focal / varifocal loss on a SOFT target (include/effdet_quality_loss.h): the
+//                               per-anchor quality q[b][a] that loss_quality_kernel leaves after the assign pass, read where code >= 0
 //   knee policy   KneeDefault:  the smooth-L1 knee 1/9 with the literals 0.5f * 9.0f, 0.5f / 9.0f, 9.0f spelled out
 //                 KneeBeta:     the knee beta as a launch argument (0.5 d^2 / beta, d - 0.5 beta, diff / beta)
 //   The default path is NOT the option kernels with default values: its arithmetic (and its single assign pass) stays as it was.
@@ -26,6 +28,8 @@
 //                       iff its IoU >= thr and its centre is inside the box; the same tail
 //              loss_pos_map_kernel                   the default pass's decision alone, per pixel and ahead of the head: one byte per
 //                       pixel = one of its 9 anchors is positive (include/effdet_needed_tiles.h: the sparse regression-tower forward)
+//   quality  loss_quality_kernel: with a quality loss, after whichever assign pass ran: one thread per (image, anchor), q = the IoU
+//            between the decoded prediction and the assigned annotation (box_overlap, the box terms' expression) at a positive, else 0
 //   cls      loss_cls_kernel<F>: one thread per 4 class probabilities (16-byte loads): focal BCE with the reference's clamp to
 //            [1e-4, 1-1e-4], one partial per workgroup in part_cls[b][block].  loss_cls_pix_kernel<T, F, GRAD_ONLY, IT>: the same
 //            sum AND d/d(logit) in one pass, or the gradient alone, written pixel-major (see there)
@@ -41,6 +45,7 @@
 #include "../../../include/effdet_box_loss.h"
 #include "../../../include/effdet_loss_opts.h"
 #include "../../../include/effdet_atss.h"
+#include "../../../include/effdet_quality_loss.h"
 #include "../../../include/effdet_needed_tiles.h"
 
 namespace {
@@ -83,9 +88,12 @@ __device__ __forceinline__ int label_of(const LossK& p, int b, int code) {
   return code >= 0 ? (int)p.annots[((long long)b * p.N + code) * 5 + 4] : -1;
 }
 
-// ---- focal policies: f(praw, target_one, dldp) -> the per-element focal term; dldp its derivative wrt the (unclamped) probability
+// ---- focal policies: f(praw, target_one, tq, dldp) -> the per-element class term; dldp its derivative wrt the (unclamped)
+// probability.  tq = f.quality(b * A + a) is the soft target of a POSITIVE anchor (include/effdet_quality_loss.h), which the kernels
+// ask for where code >= 0 only; the hard-target policies have none (no load, the argument is dead)
 struct FocalDefault {
-  __device__ __forceinline__ float operator()(float praw, bool target_one, float& dldp) const {
+  __device__ __forceinline__ float quality(long long) const { return 0.f; }
+  __device__ __forceinline__ float operator()(float praw, bool target_one, float, float& dldp) const {
     constexpr float ALPHA = 0.25f;
     const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);         // (torch.clamp keeps a NaN: so does the loss)
     const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);   // clamp passes the gradient inside the range
@@ -107,7 +115,8 @@ struct FocalDefault {
 // (no contraction: every kernel and layout computes the same bits)
 struct FocalP {
   float alpha, gamma, eps;
-  __device__ __forceinline__ float operator()(float praw, bool target_one, float& dldp) const {
+  __device__ __forceinline__ float quality(long long) const { return 0.f; }
+  __device__ __forceinline__ float operator()(float praw, bool target_one, float, float& dldp) const {
 #pragma clang fp contract(off)
     const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);
     const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);
@@ -120,6 +129,58 @@ struct FocalP {
     const float dpw = gamma * pw / u;                                 // d pw / d u; du / dp = -1 for a target of one
     dldp = pass ? aw * ((target_one ? -dpw : dpw) * ce + pw * dce) : 0.f;
     return aw * pw * ce;
+  }
+};
+
+// The soft-target policies (include/effdet_quality_loss.h): t = q[b][a] on the assigned label of a positive anchor, 0 elsewhere; q is a
+// constant of the gradient.  No contraction, as FocalP.
+__device__ __forceinline__ float soft_bce(float pc, float t, float& dce) {
+#pragma clang fp contract(off)
+  dce = (1.f - t) / (1.f - pc) - t / pc;
+  return -(t * logf(pc) + (1.f - t) * logf(1.f - pc));
+}
+
+// GFL's quality focal loss: |t - p|^beta BCE(p, t)
+struct FocalQfl {
+  float beta; const float* q;
+  __device__ __forceinline__ float quality(long long i) const { return q[i]; }
+  __device__ __forceinline__ float operator()(float praw, bool target_one, float tq, float& dldp) const {
+#pragma clang fp contract(off)
+    const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);
+    const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);
+    const float t = target_one ? tq : 0.f;
+    const float u = fabsf(t - pc);
+    float dce;
+    const float ce = soft_bce(pc, t, dce);
+    // u == 0 (p == t exactly): the power and its derivative are 0, not exp2(beta * -inf) and 0 / 0.  (A NaN t leaves pw * ce = NaN.)
+    const float pw = u == 0.f ? 0.f : exp2f(beta * log2f(u));
+    const float dpw = u == 0.f ? 0.f : beta * pw / u;                 // d pw / d u; du / dp = sign(p - t)
+    dldp = pass ? (pc > t ? dpw : -dpw) * ce + pw * dce : 0.f;
+    return pw * ce;
+  }
+};
+
+// VarifocalNet's varifocal loss: t BCE(p, t) where t > 0, alpha p^gamma BCE(p, 0) elsewhere
+struct FocalVfl {
+  float alpha, gamma; const float* q;
+  __device__ __forceinline__ float quality(long long i) const { return q[i]; }
+  __device__ __forceinline__ float operator()(float praw, bool target_one, float tq, float& dldp) const {
+#pragma clang fp contract(off)
+    const float pc = nan_min(nan_max(praw, 1e-4f), 1.0f - 1e-4f);
+    const bool pass = (praw >= 1e-4f) && (praw <= 1.0f - 1e-4f);
+    const float t = target_one ? tq : 0.f;
+    float l, d;
+    if (!(t <= 0.f)) {                                                // t > 0, or a NaN t (which the loss must keep)
+      float dce;
+      const float ce = soft_bce(pc, t, dce);
+      l = t * ce; d = t * dce;
+    } else {
+      const float pw = exp2f(gamma * log2f(pc)), ce = -logf(1.f - pc);
+      l = alpha * pw * ce;
+      d = alpha * (gamma * pw / pc * ce + pw / (1.f - pc));
+    }
+    dldp = pass ? d : 0.f;
+    return l;
   }
 };
 
@@ -558,9 +619,13 @@ __global__ __launch_bounds__(256) void loss_cls_kernel(const LossK p, const F f)
       int a = e0 / p.nc, k = e0 - a * p.nc;
       int code = asg[a];
       int lab = label_of(p, b, code);
+      float tq = code >= 0 ? f.quality((long long)b * p.A + a) : 0.f;
       for (int q = 0; q < cnt; ++q) {
-        if (code != -2) { float d; s += f(v[q], lab == k, d); }
-        if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
+        if (code != -2) { float d; s += f(v[q], lab == k, tq, d); }
+        if (++k == p.nc && q + 1 < cnt) {
+          k = 0; ++a; code = asg[a]; lab = label_of(p, b, code);
+          tq = code >= 0 ? f.quality((long long)b * p.A + a) : 0.f;
+        }
       }
     }
   }
@@ -587,14 +652,18 @@ __global__ __launch_bounds__(256) void loss_bwd_cls_kernel(const LossK p, const 
   int a = e0 / p.nc, k = e0 - a * p.nc;
   int code = asg[a];
   int lab = label_of(p, b, code);
+  float tq = code >= 0 ? f.quality((long long)b * p.A + a) : 0.f;
   for (int q = 0; q < cnt; ++q) {
     if (active && code != -2) {
-      float d; (void)f(v[q], lab == k, d);
+      float d; (void)f(v[q], lab == k, tq, d);
       g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
     } else {
       g[q] = nan_zero(v[q]);
     }
-    if (++k == p.nc && q + 1 < cnt) { k = 0; ++a; code = asg[a]; lab = label_of(p, b, code); }
+    if (++k == p.nc && q + 1 < cnt) {
+      k = 0; ++a; code = asg[a]; lab = label_of(p, b, code);
+      tq = code >= 0 ? f.quality((long long)b * p.A + a) : 0.f;
+    }
   }
   if (vec) store4(out + e0, f32x4{g[0], g[1], g[2], g[3]});
   else for (int q = 0; q < cnt; ++q) Elem<T>::st(out + e0 + q, g[q]);
@@ -629,9 +698,10 @@ __global__ __launch_bounds__(256) void loss_cls_pix_kernel(const LossK p, const 
       const f32x4 v = *(const f32x4*)(p.cls + (long long)b * p.A * p.nc + (long long)pix * cmax + ch);
       if (code != -2) {
         const int lab = label_of(p, b, code);
+        const float tq = code >= 0 ? f.quality((long long)b * p.A + a) : 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          float d; s += f(v[q], lab == k + q, d);
+          float d; s += f(v[q], lab == k + q, tq, d);
           g[q] = gs * d * v[q] * (1.f - v[q]);                 // through the sigmoid
         }
       } else {
@@ -709,18 +779,35 @@ constexpr float BOX_4_PI2 = 0.40528473456935109f;    // 4 / pi^2
 // d min(a, b) / d a (= d max(b, a) / d b) the way autograd splits it: 1 where a is selected, 0.5 on a tie
 __device__ __forceinline__ float sel_lt(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
 
+// `decode` and `overlap` of include/effdet_box_loss.h for anchor an, annotation row g and regression row r: ONE expression for every
+// IoU-family box term and for the quality target of include/effdet_quality_loss.h.  Contraction is left to the compiler, as it was
+// when these lines stood in box_loss_elem: the box terms keep their bits.  (The quality target is computed by one kernel and read
+// from memory by every class pass, so no two kernels have to agree on its bits.)
+struct BoxOverlap {
+  float aw, ah, pcx, pcy, dwr, dhr, pw, ph, px1, px2, py1, py2, gx1, gy1, gx2, gy2, gw, gh, iwr, ihr, iw, ih, I, U, D, iou;
+};
+__device__ __forceinline__ BoxOverlap box_overlap(float4 an, const float* __restrict__ g, float4 r) {
+  BoxOverlap o;
+  o.aw = an.z - an.x; o.ah = an.w - an.y;
+  const float acx = an.x + 0.5f * o.aw, acy = an.y + 0.5f * o.ah;
+  o.pcx = acx + 0.1f * r.x * o.aw; o.pcy = acy + 0.1f * r.y * o.ah;
+  o.dwr = 0.2f * r.z; o.dhr = 0.2f * r.w;
+  o.pw = expf(fminf(o.dwr, EFFDET_BOX_LOSS_DW_MAX)) * o.aw; o.ph = expf(fminf(o.dhr, EFFDET_BOX_LOSS_DW_MAX)) * o.ah;
+  o.px1 = o.pcx - 0.5f * o.pw; o.px2 = o.pcx + 0.5f * o.pw; o.py1 = o.pcy - 0.5f * o.ph; o.py2 = o.pcy + 0.5f * o.ph;
+  o.gx1 = g[0]; o.gy1 = g[1]; o.gx2 = g[2]; o.gy2 = g[3]; o.gw = o.gx2 - o.gx1; o.gh = o.gy2 - o.gy1;
+  o.iwr = fminf(o.px2, o.gx2) - fmaxf(o.px1, o.gx1); o.ihr = fminf(o.py2, o.gy2) - fmaxf(o.py1, o.gy1);
+  o.iw = fmaxf(o.iwr, 0.f); o.ih = fmaxf(o.ihr, 0.f);
+  o.I = o.iw * o.ih; o.U = o.pw * o.ph + o.gw * o.gh - o.I; o.D = o.U + BOX_EPS; o.iou = o.I / o.D;
+  return o;
+}
+
 // loss of one positive anchor; with GRAD its gradient wrt the regression row r (not yet scaled) in gr[4]
 template <bool GRAD>
 __device__ __forceinline__ float box_loss_elem(int kind, float4 an, const float* __restrict__ g, float4 r, float* gr) {
-  const float aw = an.z - an.x, ah = an.w - an.y, acx = an.x + 0.5f * aw, acy = an.y + 0.5f * ah;
-  const float pcx = acx + 0.1f * r.x * aw, pcy = acy + 0.1f * r.y * ah;
-  const float dwr = 0.2f * r.z, dhr = 0.2f * r.w;
-  const float pw = expf(fminf(dwr, EFFDET_BOX_LOSS_DW_MAX)) * aw, ph = expf(fminf(dhr, EFFDET_BOX_LOSS_DW_MAX)) * ah;
-  const float px1 = pcx - 0.5f * pw, px2 = pcx + 0.5f * pw, py1 = pcy - 0.5f * ph, py2 = pcy + 0.5f * ph;
-  const float gx1 = g[0], gy1 = g[1], gx2 = g[2], gy2 = g[3], gw = gx2 - gx1, gh = gy2 - gy1;
-  const float iwr = fminf(px2, gx2) - fmaxf(px1, gx1), ihr = fminf(py2, gy2) - fmaxf(py1, gy1);
-  const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
-  const float I = iw * ih, U = pw * ph + gw * gh - I, D = U + BOX_EPS, iou = I / D;
+  const BoxOverlap o = box_overlap(an, g, r);
+  const float aw = o.aw, ah = o.ah, pcx = o.pcx, pcy = o.pcy, dwr = o.dwr, dhr = o.dhr, pw = o.pw, ph = o.ph;
+  const float px1 = o.px1, px2 = o.px2, py1 = o.py1, py2 = o.py2, gx1 = o.gx1, gy1 = o.gy1, gx2 = o.gx2, gy2 = o.gy2, gw = o.gw, gh = o.gh;
+  const float iwr = o.iwr, ihr = o.ihr, iw = o.iw, ih = o.ih, I = o.I, U = o.U, D = o.D, iou = o.iou;
   const float cw = fmaxf(px2, gx2) - fminf(px1, gx1), ch = fmaxf(py2, gy2) - fminf(py1, gy1);
   float L = 1.f - iou;
   // gradients of L wrt the intermediate quantities, accumulated term by term
@@ -811,6 +898,24 @@ __global__ void box_loss_bwd_reg_kernel(const LossK p, const int kind, const flo
   }
 }
 
+// The quality target of include/effdet_quality_loss.h, after whichever assign pass ran and ahead of the class pass: the assign
+// pass's grid, one thread per (image, anchor); q = the IoU of box_overlap clamped to [0, 1] at a positive anchor (NaN for a
+// non-finite r: r - r is 0 or NaN), 0 elsewhere.  Every element is stored, so the buffer needs no zeroing.
+__global__ __launch_bounds__(256) void loss_quality_kernel(const LossK p, float* __restrict__ q) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  if (a >= p.A) return;
+  const long long i = (long long)b * p.A + a;
+  const int code = p.assign[i];
+  float v = 0.f;
+  if (code >= 0) {
+    const float4 r = ((const float4*)p.reg)[i];
+    const BoxOverlap o = box_overlap(((const float4*)p.anchors)[a], p.annots + ((long long)b * p.N + code) * 5, r);
+    v = nan_min(nan_max(o.iou, 0.f), 1.f) + (((r.x - r.x) + (r.y - r.y)) + ((r.z - r.z) + (r.w - r.w)));
+  }
+  q[i] = v;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 
@@ -848,6 +953,17 @@ size_t carve_loss_atss(LossK& k, AtssK& t, void* ws, int B, long long A, int num
   return head + c.off;
 }
 
+// the quality target q [B][A] of a workspace of effdet_loss_quality_workspace_bytes: past the longer of the two matchers' layouts
+// (the same place whichever matcher ran, so the class backward finds it without knowing the matcher) -> bytes
+size_t carve_loss_quality(float*& q, void* ws, int B, long long A, int num_classes, int N) {
+  LossK k{}; OptsK o{}; AtssK t{};
+  const size_t a = carve_loss_opts(k, o, nullptr, B, A, num_classes, N), b = carve_loss_atss(k, t, nullptr, B, A, num_classes, N);
+  const size_t head = a > b ? a : b;
+  Carver c(ws ? (char*)ws + head : nullptr);
+  q = c.take<float>((size_t)B * A);
+  return head + c.off;
+}
+
 LossK loss_args(const float* cls, const float* reg, const float* anchors, const float* annots, int B, long long A, int nc, int N) {
   LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.B = B; k.nc = nc; k.N = N; k.A = A;
   return k;
@@ -869,6 +985,11 @@ bool loss_opts_ok(const effdet_loss_opts_t* o) {
   if (!(o->neg_iou >= 0.f && o->neg_iou <= o->pos_iou && o->pos_iou <= 1.f)) return false;
   if (o->low_quality != 0 && o->low_quality != 1) return false;
   return o->box_kind >= 0 && o->box_kind <= EFFDET_BOX_LOSS_CIOU;
+}
+
+bool quality_ok(const effdet_quality_loss_t* q) {
+  if (!q || (q->kind != EFFDET_QUALITY_QFL && q->kind != EFFDET_QUALITY_VFL)) return false;
+  return q->beta >= 1.f && q->beta <= 8.f && q->alpha > 0.f && q->alpha <= 1.f && q->gamma >= 0.f && q->gamma <= 8.f;    // (false for a NaN)
 }
 
 bool atss_ok(const effdet_atss_t* t, long long A) {
@@ -962,15 +1083,37 @@ int box_loss_finish(const float* reg, const float* anchors, const float* annots,
   return EFFDET_OK;
 }
 
-// both forward entry points of the options: dcls_pix == nullptr is effdet_loss_opts_fwd
+// The class policy of a forward call: FocalP of the options, or with a quality loss (checked by the caller) its soft-target policy
+// reading q, which then lies in a workspace of effdet_loss_quality_workspace_bytes.  -> fn(policy, q, bytes needed); q == nullptr:
+// no quality pass
+template <typename Fn>
+int with_class_policy(const effdet_loss_opts_t* opts, const effdet_quality_loss_t* ql, void* workspace, int B, long long A,
+                      int num_classes, int N, long long plain_bytes, Fn&& fn) {
+  if (!ql) return fn(FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, (float*)nullptr, plain_bytes);
+  float* q = nullptr;
+  const long long need = (long long)carve_loss_quality(q, workspace, B, A, num_classes, N);
+  if (ql->kind == EFFDET_QUALITY_QFL) return fn(FocalQfl{ql->beta, q}, q, need);
+  return fn(FocalVfl{ql->alpha, ql->gamma, q}, q, need);
+}
+
+// after the assign pass of a forward call with a quality loss: q for the class pass
+int launch_quality(const LossK& k, float* q, hipStream_t st) {
+  hipLaunchKernelGGL(loss_quality_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k, q);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// both forward entry points of the options: dcls_pix == nullptr is effdet_loss_opts_fwd.  ql: null, or the quality loss in the place
+// of the focal term (include/effdet_quality_loss.h)
 int loss_opts_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
                       long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
-                      int N, const effdet_loss_opts_t* opts, effdet_stream_t stream) {
+                      int N, const effdet_loss_opts_t* opts, effdet_stream_t stream, const effdet_quality_loss_t* ql = nullptr) {
   if (!loss_opts_ok(opts) || B < 1 || N < 1 || A < 1 || num_classes < 1) return EFFDET_EINVAL;
   LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
   hipStream_t st = (hipStream_t)stream;
-  const int rc = loss_forward(k0, FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, opts->reg_weight, workspace, workspace_bytes,
-                              effdet_loss_opts_workspace_bytes(B, A, num_classes, N), grad, dtype, st, [&](LossK& k) -> int {
+  const int rc = with_class_policy(opts, ql, workspace, B, A, num_classes, N, effdet_loss_opts_workspace_bytes(B, A, num_classes, N),
+                                   [&](auto f, float* q, long long need) -> int {
+   return loss_forward(k0, f, opts->reg_weight, workspace, workspace_bytes, need, grad, dtype, st, [&](LossK& k) -> int {
     OptsK o{opts->pos_iou, opts->neg_iou, opts->low_quality};
     carve_loss_opts(k, o, workspace, B, A, num_classes, N);
     const int nz = B * SS, mz = B * N;
@@ -980,7 +1123,8 @@ int loss_opts_forward(const float* cls, const float* reg, const float* anchors, 
     EFFDET_CHECK_LAUNCH();
     hipLaunchKernelGGL(opts_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o, KneeBeta{opts->beta});
     EFFDET_CHECK_LAUNCH();
-    return EFFDET_OK;
+    return q ? launch_quality(k, q, st) : EFFDET_OK;
+   });
   });
   if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
   return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
@@ -989,12 +1133,14 @@ int loss_opts_forward(const float* cls, const float* reg, const float* anchors, 
 // both forward entry points of the ATSS matcher: loss_opts_forward with the ATSS assign path
 int loss_atss_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
                       long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
-                      int N, const effdet_loss_opts_t* opts, const effdet_atss_t* atss, effdet_stream_t stream) {
+                      int N, const effdet_loss_opts_t* opts, const effdet_atss_t* atss, effdet_stream_t stream,
+                      const effdet_quality_loss_t* ql = nullptr) {
   if (!loss_opts_ok(opts) || opts->low_quality != 0 || B < 1 || N < 1 || A < 1 || num_classes < 1 || !atss_ok(atss, A)) return EFFDET_EINVAL;
   LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
   hipStream_t st = (hipStream_t)stream;
-  const int rc = loss_forward(k0, FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, opts->reg_weight, workspace, workspace_bytes,
-                              effdet_loss_atss_workspace_bytes(B, A, num_classes, N, atss), grad, dtype, st, [&](LossK& k) -> int {
+  const int rc = with_class_policy(opts, ql, workspace, B, A, num_classes, N, effdet_loss_atss_workspace_bytes(B, A, num_classes, N, atss),
+                                   [&](auto f, float* q, long long need) -> int {
+   return loss_forward(k0, f, opts->reg_weight, workspace, workspace_bytes, need, grad, dtype, st, [&](LossK& k) -> int {
     AtssK t{}; t.topk = atss->topk; t.num_levels = atss->num_levels;      // (A < 2^31 has been checked: an index within a level fits the low half of a key)
     for (int l = 0; l <= atss->num_levels; ++l) t.ls[l] = atss->level_start[l];
     carve_loss_atss(k, t, workspace, B, A, num_classes, N);
@@ -1005,7 +1151,8 @@ int loss_atss_forward(const float* cls, const float* reg, const float* anchors, 
     EFFDET_CHECK_LAUNCH();
     hipLaunchKernelGGL(atss_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, t, KneeBeta{opts->beta});
     EFFDET_CHECK_LAUNCH();
-    return EFFDET_OK;
+    return q ? launch_quality(k, q, st) : EFFDET_OK;
+   });
   });
   if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
   return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
@@ -1172,18 +1319,29 @@ extern "C" int effdet_loss_opts_fwd_grad(const float* cls, const float* reg, con
                            num_classes, N, opts, stream);
 }
 
-extern "C" int effdet_loss_opts_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls,
-                                        int dld, int dtype, int B, long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
-                                        effdet_stream_t stream) {
+// the class backward of the options, and with ql of a quality loss
+int loss_opts_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls, int dld, int dtype,
+                      int B, long long A, int num_classes, int N, const effdet_loss_opts_t* opts, const effdet_quality_loss_t* ql,
+                      effdet_stream_t stream) {
   if (!cls || !annots || !gscale || !workspace || !dcls) return EFFDET_EINVAL;
   if (!loss_opts_ok(opts) || B < 1 || B > 65535 || N < 1 || A < 1 || num_classes < 1 || dld < 0) return EFFDET_EINVAL;
   if (const int rc = check_dcls(dcls, dld, dtype, false, A, num_classes)) return rc;
   if (A * num_classes >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
   LossK k = loss_args(cls, nullptr, nullptr, annots, B, A, num_classes, N); k.gscale = gscale; k.dcls = dcls; k.dld = dld;
   carve_loss(k, const_cast<void*>(workspace), B, A);
-  launch_bwd_cls(k, FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, dtype, (hipStream_t)stream);
+  const int rc = with_class_policy(opts, ql, const_cast<void*>(workspace), B, A, num_classes, N, 0, [&](auto f, float*, long long) -> int {
+    launch_bwd_cls(k, f, dtype, (hipStream_t)stream);
+    return EFFDET_OK;
+  });
+  if (rc != EFFDET_OK) return rc;
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
+}
+
+extern "C" int effdet_loss_opts_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls,
+                                        int dld, int dtype, int B, long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
+                                        effdet_stream_t stream) {
+  return loss_opts_bwd_cls(cls, annots, gscale, workspace, dcls, dld, dtype, B, A, num_classes, N, opts, nullptr, stream);
 }
 
 extern "C" int effdet_loss_opts_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
@@ -1218,4 +1376,41 @@ extern "C" int effdet_loss_atss_fwd_grad(const float* cls, const float* reg, con
                                          const effdet_atss_t* atss, effdet_stream_t stream) {
   return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
                            num_classes, N, opts, atss, stream);
+}
+
+extern "C" long long effdet_loss_quality_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_atss_t* atss) {
+  if (atss && !atss_ok(atss, A)) return EFFDET_EINVAL;
+  float* q = nullptr;
+  return (long long)carve_loss_quality(q, nullptr, B, A, num_classes, N);
+}
+
+extern "C" int effdet_loss_quality_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                       void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
+                                       const effdet_loss_opts_t* opts, const effdet_atss_t* atss, const effdet_quality_loss_t* quality,
+                                       effdet_stream_t stream) {
+  if (!quality_ok(quality)) return EFFDET_EINVAL;
+  if (atss)
+    return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
+                             num_classes, N, opts, atss, stream, quality);
+  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
+                           num_classes, N, opts, stream, quality);
+}
+
+extern "C" int effdet_loss_quality_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                            void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
+                                            long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
+                                            const effdet_atss_t* atss, const effdet_quality_loss_t* quality, effdet_stream_t stream) {
+  if (!quality_ok(quality)) return EFFDET_EINVAL;
+  if (atss)
+    return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
+                             num_classes, N, opts, atss, stream, quality);
+  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
+                           num_classes, N, opts, stream, quality);
+}
+
+extern "C" int effdet_loss_quality_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls,
+                                           int dld, int dtype, int B, long long A, int num_classes, int N,
+                                           const effdet_loss_opts_t* opts, const effdet_quality_loss_t* quality, effdet_stream_t stream) {
+  if (!quality_ok(quality)) return EFFDET_EINVAL;
+  return loss_opts_bwd_cls(cls, annots, gscale, workspace, dcls, dld, dtype, B, A, num_classes, N, opts, quality, stream);
 }

@@ -120,16 +120,21 @@ class FocalLoss(nn.Module):
     focal alpha / gamma, label smoothing, the smooth-L1 knee and weight and the matcher's rules (None: the reference's constants);
     matcher: an ops.ATSSOptions assigns by ATSS in place of the IoU bands (None: the bands).  With a matcher, forward takes the
     anchor count of every pyramid level as `levels`; without it the levels are read off the table (a level starts where the anchors
-    double in size), which costs one device -> host sync."""
+    double in size), which costs one device -> host sync.  quality: an ops.QualityLossOptions puts the quality focal / varifocal
+    loss in the place of the focal class term (None: the focal term); the workspace of the last forward call with one is kept as
+    `last_workspace` for ops.loss_quality_targets."""
 
-    def __init__(self, box_loss=None, loss=None, matcher=None):
+    def __init__(self, box_loss=None, loss=None, matcher=None, quality=None):
         super().__init__()
         ops._box_loss_args(box_loss)                            # (TypeError on anything but BoxLossOptions / None)
         ops._loss_opts_struct(loss)                             # (TypeError on anything but LossOptions / None)
         ops.check_matcher(matcher, loss)                        # (TypeError / ValueError: a matcher with bands or low_quality)
+        ops.check_quality(quality, loss)                        # (TypeError / ValueError: a quality loss with focal alpha / gamma / smoothing)
         self.box_loss = box_loss
         self.loss = loss
         self.matcher = matcher
+        self.quality = quality
+        self.last_workspace = None
 
     @staticmethod
     def table_levels(anchors):
@@ -143,9 +148,12 @@ class FocalLoss(nn.Module):
         anchors = anchors.contiguous()
         if matcher is not None and levels is None:
             levels = self.table_levels(anchors)
-        losses, _ = ops.loss_opts_fwd(classifications.contiguous(), regressions.contiguous(), anchors,
-                                      annotations.contiguous().float(), getattr(self, 'loss', None), self.box_loss,
-                                      matcher=matcher, levels=levels)
+        quality = getattr(self, 'quality', None)                # (likewise)
+        losses, ws = ops.loss_opts_fwd(classifications.contiguous(), regressions.contiguous(), anchors,
+                                       annotations.contiguous().float(), getattr(self, 'loss', None), self.box_loss,
+                                       matcher=matcher, levels=levels, quality=quality)
+        if quality is not None:
+            self.last_workspace = ws
         return losses[0:1], losses[1:2]
 
 
@@ -337,18 +345,24 @@ class _HeadLossFn(torch.autograd.Function):
     ops.BoxLossOptions of an IoU kind = that term in its place; loss: None = the reference's constants, a non-default ops.LossOptions =
     the options.  The ops.loss_opts_* calls choose the entry points for either; every choice keeps the output contract of d(logit)
     and d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them).
-    An ops.ATSSOptions may follow the head's parameters as one trailing argument: the matcher, over the five level maps."""
+    An ops.ATSSOptions and / or an ops.QualityLossOptions may follow the head's parameters as trailing arguments: the matcher, over
+    the five level maps, and the quality loss in the place of the focal term (forward + gradient and the class backward then go through
+    the effdet_loss_quality_* calls)."""
 
     @staticmethod
     def forward(ctx, dtype, num_classes, anchors, annots, train, box, loss, *args):
         ctx.prep, ctx.arith, ctx.box, ctx.loss = ops.get_prep(), ops.F32_ARITH_BWD, box, loss
-        ctx.matcher = matcher = args[5 + len(_HEAD_KEYS)] if len(args) > 5 + len(_HEAD_KEYS) else None
-        ctx.extra = len(args) - 5 - len(_HEAD_KEYS)
+        tail = args[5 + len(_HEAD_KEYS):]
+        ctx.matcher = matcher = next((t for t in tail if isinstance(t, ops.ATSSOptions)), None)
+        ctx.quality = quality = next((t for t in tail if isinstance(t, ops.QualityLossOptions)), None)
+        ctx.extra = len(tail)
         p = [Map.of(t) for t in args[:5]]
         HP = dict(zip(_HEAD_KEYS, args[5:]))
         levels = [m.H * m.W * 9 for m in p] if matcher is not None else None
         # the default matcher's positives are known before the head runs, and every box term reads `reg` at them alone: the regression
         # tower computes the tiles that can reach one (two small launches per step, no host read: a captured step follows its annotations)
+        # A quality loss keeps this forward: its target q reads `reg` at positive anchors only, which the needed tiles cover by
+        # construction (without a LossOptions its assign pass applies the default bands to the same IoU expression as the map).
         need = need_units = None
         if matcher is None and loss is None and Fn.head_fwd_takes_needed(p, dtype, train):
             sizes_ = [(m.H, m.W) for m in p]
@@ -362,10 +376,10 @@ class _HeadLossFn(torch.autograd.Function):
             # the pixel-major, 64-channel-padded rows the head's gradient convs read; cls itself is not kept for backward
             dld = (9 * nc + 63) // 64 * 64
             losses, ws, dpix = ops.loss_opts_fwd_grad(cls, reg, anchors, annots, dtype, dld, split=saved.split, loss=loss, box=box,    # (split-layout head: see functional.head_uses_split)
-                                                      matcher=matcher, levels=levels)
+                                                      matcher=matcher, levels=levels, quality=quality)
             ctx.saved = (saved, None, reg, anchors, annots, ws, dtype, dpix, dld)
         else:
-            losses, ws = ops.loss_opts_fwd(cls, reg, anchors, annots, loss, box, matcher=matcher, levels=levels)
+            losses, ws = ops.loss_opts_fwd(cls, reg, anchors, annots, loss, box, matcher=matcher, levels=levels, quality=quality)
             ctx.saved = (saved, cls, reg, anchors, annots, ws, dtype, None, 0) if train else None
         return losses[0:1].clone(), losses[1:2].clone()
 
@@ -382,20 +396,21 @@ class _HeadLossFn(torch.autograd.Function):
             split = saved.split
             rld = 64 if split else 0                # split layout: d(reg) pixel-major, 36 -> 64 channels (two [hi|lo] groups)
             dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, reg_ld=rld, split=split, loss=ctx.loss, box=ctx.box,
-                                         matcher=ctx.matcher)
+                                         matcher=ctx.matcher, quality=ctx.quality)
             with ops.unpack_batch():                               # the head's 10 weight-gradient unpacks: one launch
                 dp, g = Fn.head_bwd(saved, dpix, dreg, dtype, dcls_ld=dld, cls_gscale=gscale[0:1], dreg_ld=rld, in_split=split)
         else:
             nc = cls.shape[2]
             dld = (9 * nc + 63) // 64 * 64 if nc % 4 == 0 else 0      # d(logits) straight into the pixel-major, 64-channel-padded rows the head's gradient convs read
-            if ctx.loss is not None or ctx.matcher is not None:
-                dcls = ops.loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, ctx.loss, dld=dld, matcher=ctx.matcher)
+            if ctx.loss is not None or ctx.matcher is not None or ctx.quality is not None:
+                dcls = ops.loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, ctx.loss, dld=dld, matcher=ctx.matcher, quality=ctx.quality)
             elif dld:                                 # the reference's constants: the combined calls (smooth-L1 d(reg) in the same launch pair)
                 dcls, dreg = ops.focal_loss_bwd_pix(cls, reg, anchors, annots, gscale, ws, dtype, dld)
             else:
                 dcls, dreg = ops.focal_loss_bwd(cls, reg, anchors, annots, gscale, ws, dtype)
-            if ctx.loss is not None or ctx.box is not None or ctx.matcher is not None:      # (the class gradient above is the focal term's either way; a smooth-L1 d(reg) is replaced)
-                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, loss=ctx.loss, box=ctx.box, matcher=ctx.matcher)
+            if ctx.loss is not None or ctx.box is not None or ctx.matcher is not None or ctx.quality is not None:      # (the class gradient above is the focal term's either way; a smooth-L1 d(reg) is replaced)
+                dreg = ops.loss_opts_bwd_reg(reg, anchors, annots, gscale, ws, dtype, loss=ctx.loss, box=ctx.box, matcher=ctx.matcher,
+                                             quality=ctx.quality)
             with ops.unpack_batch():
                 dp, g = Fn.head_bwd(saved, dcls, dreg, dtype, dcls_ld=dld)
         ctx.saved = None
@@ -420,6 +435,7 @@ class EfficientDet(nn.Module):
         self.box_loss = None                                    # set_box_loss(): None = the reference's smooth-L1 on encoded deltas
         self.loss_options = None                                # set_loss(): None = the reference's focal / smooth-L1 / matcher constants
         self.matcher = None                                     # set_matcher(): None = the IoU bands of the loss options
+        self.quality_loss = None                                # set_quality_loss(): None = the hard-target focal class term
         self.num_classes = num_classes
         self.compute_dtype = compute_dtype
         # MFMA arithmetic on fp32 storage: 'f32' = exact fp32 products (v_mfma_f32_16x16x4_f32), 'bf16x3' = operands split into
@@ -496,6 +512,7 @@ class EfficientDet(nn.Module):
         if options is not None and not isinstance(options, ops.LossOptions):
             raise TypeError('set_loss takes a LossOptions or None, not %r' % (options,))
         ops.check_matcher(getattr(self, 'matcher', None), options)      # (ValueError: bands / low_quality while a matcher is set)
+        ops.check_quality(getattr(self, 'quality_loss', None), options)  # (ValueError: alpha / gamma / smoothing while a quality loss is set)
         self.loss_options = options
         self.criterion.loss = options
         return self
@@ -512,6 +529,23 @@ class EfficientDet(nn.Module):
         ops.check_matcher(options, getattr(self, 'loss_options', None))
         self.matcher = options
         self.criterion.matcher = options
+        return self
+
+    def set_quality_loss(self, options):
+        """Class term of the training loss: None (the default) = the hard-target focal loss, through the same calls as ever; an
+        ops.QualityLossOptions('qfl' | 'vfl') = the quality focal loss of GFL resp. the varifocal loss of VarifocalNet
+        (include/effdet_quality_loss.h): the target of a positive anchor's label is the IoU between its decoded prediction and its
+        annotation, so the score that NMS ranks by carries the localisation quality.  It composes with set_matcher, set_box_loss and
+        the beta / reg_weight / bands / low_quality of set_loss; it replaces the focal term: combined with a LossOptions of non-default
+        alpha / gamma / label_smoothing it raises ValueError.  The sums are normalised per image by its positives (mmdet: batch-wide),
+        there is no distribution focal loss and no distribution head, and no mAP has been measured with it.  The kind and the values
+        are launch arguments: a graph.GraphedTrainStep / GraphedTrainLoop captured before a change keeps the old term until it is
+        captured again."""
+        if options is not None and not isinstance(options, ops.QualityLossOptions):
+            raise TypeError('set_quality_loss takes a QualityLossOptions or None, not %r' % (options,))
+        ops.check_quality(options, getattr(self, 'loss_options', None))
+        self.quality_loss = options
+        self.criterion.quality = options
         return self
 
     def live_parameters(self):
@@ -661,9 +695,10 @@ class EfficientDet(nn.Module):
             loss = getattr(self, 'loss_options', None)           # (likewise)
             loss = None if (loss is None or loss.is_default()) else loss
             matcher = getattr(self, 'matcher', None)             # (likewise)
+            quality = getattr(self, 'quality_loss', None)        # (likewise)
             return _HeadLossFn.apply(self.compute_dtype, self.num_classes, anc, annotations.float().contiguous(),
                                      torch.is_grad_enabled(), box, loss, *p, *self._head_params(),
-                                     *(() if matcher is None else (matcher,)))
+                                     *(() if matcher is None else (matcher,)), *(() if quality is None else (quality,)))
         dets = self.detect(inputs)
         s, l, b = dets[0]
         if s.numel() == 0:

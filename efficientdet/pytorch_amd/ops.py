@@ -2030,7 +2030,9 @@ def merge_slices(lists, table, H, W, options=None):
 # box term: kind, weight) and effdet_loss_opts_* (non-default LossOptions: the struct, with the box term inside it).  They take the same
 # arguments, the extra ones just before the stream.  Each public function below names the call it wants; _loss_entry chooses the set.
 # A matcher (ATSSOptions) is a fourth set for the two forward calls, effdet_loss_atss_* (the options struct, then the matcher's); its
-# backward calls are the options set's, with the options struct even where its values are the defaults.
+# backward calls are the options set's, with the options struct even where its values are the defaults.  A quality loss
+# (QualityLossOptions) is a fifth set for the forward calls and the class backward, effdet_loss_quality_* (the options struct, the
+# matcher's or NULL, its own); its d(reg) call is the options set's.
 BOX_LOSS_KINDS = {'smooth_l1': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}     # EFFDET_BOX_LOSS_* (0: the effdet_focal_loss_* calls)
 
 
@@ -2154,6 +2156,58 @@ class ATSSOptions:
         return 'ATSSOptions(topk=%r)' % self.topk
 
 
+QUALITY_KINDS = {'qfl': L.QUALITY_QFL, 'vfl': L.QUALITY_VFL}     # EFFDET_QUALITY_*
+
+
+class QualityLossOptions:
+    """The IoU-aware class term of EfficientDet.set_quality_loss / FocalLoss(quality=) (include/effdet_quality_loss.h), in place of the
+    hard-target focal loss: the target of a positive anchor's assigned label is q, the IoU between its DECODED prediction and its
+    annotation (a constant of the gradient).  kind 'qfl': GFL's quality focal loss |q - p|^beta BCE(p, q); kind 'vfl': the varifocal
+    loss, q BCE(p, q) on those elements and alpha p^gamma BCE(p, 0) on every other.  Values are kept as the fp32 the kernels receive
+    (each must be in range whatever the kind).  The sums are normalised per image by its number of positives, as every class term
+    here (mmdet: one batch-wide normaliser); there is no distribution focal loss and no distribution head."""
+
+    def __init__(self, kind='qfl', beta=2.0, alpha=0.75, gamma=2.0):
+        if kind not in QUALITY_KINDS:
+            raise ValueError('QualityLossOptions: kind must be one of %s, not %r' % (sorted(QUALITY_KINDS), kind))
+        b, a, g = _f32(beta), _f32(alpha), _f32(gamma)
+        if not 1.0 <= b <= 8.0:
+            raise ValueError('QualityLossOptions: beta must lie in [1, 8], not %r' % (beta,))
+        if not 0.0 < a <= 1.0:
+            raise ValueError('QualityLossOptions: alpha must lie in (0, 1], not %r' % (alpha,))
+        if not 0.0 <= g <= 8.0:
+            raise ValueError('QualityLossOptions: gamma must lie in [0, 8], not %r' % (gamma,))
+        self.kind, self.beta, self.alpha, self.gamma = kind, b, a, g
+
+    def key(self):
+        return (self.kind, self.beta, self.alpha, self.gamma)
+
+    def __eq__(self, other):
+        return isinstance(other, QualityLossOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'QualityLossOptions(kind=%r, beta=%r, alpha=%r, gamma=%r)' % self.key()
+
+
+def check_quality(quality, loss):
+    """TypeError on anything but a QualityLossOptions / None; ValueError where loss sets what a quality loss replaces (focal alpha /
+    gamma, label smoothing)."""
+    if quality is None:
+        return
+    if not isinstance(quality, QualityLossOptions):
+        raise TypeError('quality loss options must be a QualityLossOptions or None, not %r' % (quality,))
+    if isinstance(loss, LossOptions) and loss.key()[:3] != _LOSS_DEFAULT_KEY[:3]:
+        raise ValueError('%r replaces the focal class term: it cannot be combined with the alpha / gamma / label_smoothing of %r'
+                         % (quality, loss))
+
+
+def _quality_struct(quality):
+    return L.QualityLoss(QUALITY_KINDS[quality.kind], quality.beta, quality.alpha, quality.gamma)
+
+
 def check_matcher(matcher, loss):
     """TypeError on anything but an ATSSOptions / None; ValueError where loss sets what a matcher replaces (bands, low_quality)."""
     if matcher is None:
@@ -2195,12 +2249,19 @@ def _loss_opts_struct(loss, box=None, force=False):
                       1 if loss.low_quality else 0, kind, weight)
 
 
-def _loss_entry(stem, loss=None, box=None, matcher=None, atss=None):
-    """-> (the entry point of the call `stem` for (loss, box, matcher), its name, its extra arguments, whether it is of the options
-    set).  atss: the matcher's effdet_atss_t, for the forward calls."""
+def _loss_entry(stem, loss=None, box=None, matcher=None, atss=None, quality=None):
+    """-> (the entry point of the call `stem` for (loss, box, matcher, quality), its name, its extra arguments, whether it is of the
+    options set).  atss: the matcher's effdet_atss_t, for the forward calls.  A quality loss has calls of its own for the forward
+    and the class backward (the options struct, the matcher's or NULL on the forward calls, its own); its d(reg) call is the
+    options set's, with the options struct even where its values are the defaults."""
     check_matcher(matcher, loss)
-    o = _loss_opts_struct(loss, box, force=matcher is not None)
-    if atss is not None:
+    check_quality(quality, loss)
+    o = _loss_opts_struct(loss, box, force=matcher is not None or quality is not None)
+    if quality is not None and stem != 'bwd_reg':
+        name = 'effdet_loss_quality_' + stem
+        mid = () if stem == 'bwd_cls' else (None if atss is None else C.byref(atss),)
+        extra = (C.byref(o),) + mid + (C.byref(_quality_struct(quality)),)
+    elif atss is not None:
         name, extra = 'effdet_loss_atss_' + stem, (C.byref(o), C.byref(atss))
     elif o is not None:
         name, extra = 'effdet_loss_opts_' + stem, (C.byref(o),)
@@ -2214,14 +2275,17 @@ def _dtype_code(dtype, split):
     return L.F32_SPLIT if split else L.dtype_code(dtype)
 
 
-def _loss_forward(cls, reg, anc, annots, loss, box, grad=None, matcher=None, levels=None):
-    """Forward of (loss, box, matcher) -> (losses [2], ws), and with grad = (dtype, dld, split) also dcls_pix [B, A/9, dld]."""
+def _loss_forward(cls, reg, anc, annots, loss, box, grad=None, matcher=None, levels=None, quality=None):
+    """Forward of (loss, box, matcher, quality) -> (losses [2], ws), and with grad = (dtype, dld, split) also dcls_pix [B, A/9, dld]."""
     B, A, nc = cls.shape
     N = annots.shape[1]
     check_matcher(matcher, loss)
     atss = None if matcher is None else _atss_struct(matcher, levels, A)
-    fn, name, extra, opts = _loss_entry('fwd_grad' if grad else 'fwd', loss, box, matcher, atss)
-    if atss is not None:
+    fn, name, extra, opts = _loss_entry('fwd_grad' if grad else 'fwd', loss, box, matcher, atss, quality)
+    if quality is not None:
+        nbytes = int(L.require('effdet_loss_quality_workspace_bytes').effdet_loss_quality_workspace_bytes(
+            B, A, nc, N, None if atss is None else C.byref(atss)))
+    elif atss is not None:
         nbytes = int(L.require('effdet_loss_atss_workspace_bytes').effdet_loss_atss_workspace_bytes(B, A, nc, N, C.byref(atss)))
     elif opts:
         nbytes = int(L.require('effdet_loss_opts_workspace_bytes').effdet_loss_opts_workspace_bytes(B, A, nc, N))
@@ -2239,10 +2303,10 @@ def _loss_forward(cls, reg, anc, annots, loss, box, grad=None, matcher=None, lev
     return out
 
 
-def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher=None):
+def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher=None, quality=None):
     """-> dreg [B, A, 4], or with reg_ld pixel-major and channel-padded [B, A/9, reg_ld] (split=True: in the split layout), from the
-    workspace of a forward call with the same (loss, box, matcher)."""
-    fn, name, extra, _ = _loss_entry('bwd_reg', loss, box, matcher)
+    workspace of a forward call with the same (loss, box, matcher, quality)."""
+    fn, name, extra, _ = _loss_entry('bwd_reg', loss, box, matcher, quality=quality)
     B, A, _ = reg.shape
     dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
     L.check(fn(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld, _dtype_code(dtype, split), B, A,
@@ -2250,14 +2314,14 @@ def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box,
     return dreg
 
 
-def _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld, loss=None, matcher=None):
+def _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld, loss=None, matcher=None, quality=None):
     """d(logits) [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld].  The reference's constants: the combined entry
     points (dld None: the flat one), which also write the smooth-L1 dreg [B, A, 4] -> (dcls, dreg); options: the class gradient
     alone -> dcls."""
     B, A, nc = cls.shape
     dcls = torch.empty((B, A // 9, dld) if dld else (B, A, nc), dtype=dtype, device=cls.device)
-    if loss is not None or matcher is not None:
-        fn, name, extra, _ = _loss_entry('bwd_cls', loss, None, matcher)
+    if loss is not None or matcher is not None or quality is not None:
+        fn, name, extra, _ = _loss_entry('bwd_cls', loss, None, matcher, quality=quality)
         L.check(fn(L.ptr(cls), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls), dld, L.dtype_code(dtype), B, A, nc,
                    annots.shape[1], *extra, L.stream_ptr()), name)
         return dcls
@@ -2308,29 +2372,46 @@ def box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False,
     return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, None, options)
 
 
-def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None, matcher=None, levels=None):
+def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None, matcher=None, levels=None, quality=None):
     """box_loss_fwd with the options of loss (None / the defaults: box_loss_fwd itself) -> (losses [2], ws).  matcher: an ATSSOptions
     assigns by ATSS over the pyramid levels (levels: the anchor count of every level) through the effdet_loss_atss_* calls, with
-    the options struct of loss (None / the defaults: the default VALUES through the option kernels)."""
-    return _loss_forward(cls, reg, anc, annots, loss, box, None, matcher, levels)
+    the options struct of loss (None / the defaults: the default VALUES through the option kernels).  quality: a QualityLossOptions
+    puts its IoU-aware class term in the place of the focal one through the effdet_loss_quality_* calls (the options struct likewise;
+    one more launch, which leaves the targets in the workspace: loss_quality_targets)."""
+    return _loss_forward(cls, reg, anc, annots, loss, box, None, matcher, levels, quality)
 
 
-def loss_opts_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, loss=None, box=None, matcher=None, levels=None):
-    """box_loss_fwd_grad with the options of loss (and the matcher) -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
-    return _loss_forward(cls, reg, anc, annots, loss, box, (dtype, dld, split), matcher, levels)
+def loss_opts_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False, loss=None, box=None, matcher=None, levels=None, quality=None):
+    """box_loss_fwd_grad with the options of loss (and the matcher, and the quality loss) -> (losses [2], ws, dcls_pix [B, A/9, dld])."""
+    return _loss_forward(cls, reg, anc, annots, loss, box, (dtype, dld, split), matcher, levels, quality)
 
 
-def loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, loss, dld=0, matcher=None):
+def loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, loss, dld=0, matcher=None, quality=None):
     """d(logits) of the class term with the (non-default) options of loss, from the workspace of a forward call with them:
-    [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld].  With a matcher the options path is taken whatever loss."""
-    if matcher is None and _loss_opts_struct(loss) is None:
+    [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld].  With a matcher or a quality loss the options path is taken
+    whatever loss."""
+    if matcher is None and quality is None and _loss_opts_struct(loss) is None:
         raise ValueError('loss_opts_bwd_cls is the non-default path: the defaults are focal_loss_bwd / focal_loss_bwd_pix')
-    return _loss_bwd_cls(cls, None, None, annots, gscale, ws, dtype, dld, loss, matcher)
+    return _loss_bwd_cls(cls, None, None, annots, gscale, ws, dtype, dld, loss, matcher, quality)
 
 
-def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, loss=None, box=None, matcher=None):
-    """box_loss_bwd_reg with the options of loss: d(reg) in the same three layouts (matcher: the options path whatever loss)."""
-    return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher)
+def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, loss=None, box=None, matcher=None, quality=None):
+    """box_loss_bwd_reg with the options of loss: d(reg) in the same three layouts (matcher / quality: the options path whatever loss)."""
+    return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher, quality)
+
+
+def loss_quality_targets(ws, B, A, N, matcher=None):
+    """-> q [B, A] fp32, a VIEW of the workspace ws that a forward call with a quality loss left (include/effdet_quality_loss.h): the
+    IoU between a positive anchor's decoded prediction and its annotation, clamped to [0, 1]; 0 at every other anchor (so
+    q.sum() / (codes >= 0).sum() is the mean IoU of the positives).  It is the last buffer of the workspace and lies at the same offset
+    for either matcher; N and matcher name the call that left ws and are only checked."""
+    if matcher is not None and not isinstance(matcher, ATSSOptions):
+        raise TypeError('matcher must be an ATSSOptions or None, not %r' % (matcher,))
+    nq = (4 * B * A + 255) // 256 * 256
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or N < 1 or ws.numel() < nq + 4 * B * A:
+        raise ValueError('ws is not the workspace of a forward call with a quality loss on [%d, %d] anchors' % (B, A))
+    off = ws.numel() - nq
+    return ws[off:off + 4 * B * A].view(torch.float32).reshape(B, A)
 
 
 def pad_rows(src_map, cpad):
