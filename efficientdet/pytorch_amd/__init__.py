@@ -9,5 +9,5 @@ from .config import EFFICIENTDET, MODEL_MAP  # noqa: F401
 from .efficientdet import EfficientDet, PackedImages  # noqa: F401
 from .evaluate import SlicedDetector  # noqa: F401
 from .ops import (ATSSOptions, BoxLossOptions, LossOptions, NMSOptions, QualityLossOptions, SliceMergeOptions, SliceOptions,  # noqa: F401
-                  TTAOptions, WBFOptions)
+                  TTAOptions, TaskAlignedOptions, WBFOptions)
 from .synthetic import synthetic_batch  # noqa: F401

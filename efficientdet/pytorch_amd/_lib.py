@@ -1,7 +1,7 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h, include/effdet_affine.h,
 include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h, include/effdet_resample.h, include/effdet_slices.h,
-include/effdet_quality_loss.h).
+include/effdet_quality_loss.h, include/effdet_tal.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -122,6 +122,13 @@ QUALITY_QFL, QUALITY_VFL = 1, 2                     # EFFDET_QUALITY_*
 
 class QualityLoss(C.Structure):  # effdet_quality_loss_t (include/effdet_quality_loss.h)
     _fields_ = [('kind', C.c_int), ('beta', C.c_float), ('alpha', C.c_float), ('gamma', C.c_float)]
+
+
+TAL_MAX_TOPK = 16                                   # EFFDET_TAL_MAX_TOPK
+
+
+class Tal(C.Structure):          # effdet_tal_t (include/effdet_tal.h)
+    _fields_ = [('topk', C.c_int), ('alpha', C.c_float), ('beta', C.c_float), ('aligned_target', C.c_int)]
 
 
 class ConvPlanInfo(C.Structure):   # effdet_conv_plan_info_t (include/effdet_conv_plan.h)
@@ -359,6 +366,16 @@ QUALITY_LOSS_SIGNATURES = {
     'effdet_loss_quality_fwd_grad': 'i:ppppppqpiiiqiippps',
     'effdet_loss_quality_bwd_cls': 'i:pppppiiiqiipps',
 }
+# The task-aligned matcher of the detection loss, declared in include/effdet_tal.h (same generation, same letters, same rule;
+# tests/test_tal_host.py compares this table and Tal with that header).  The forward twins of effdet_loss_quality_fwd / _fwd_grad with a
+# Tal struct (host memory, byref) in the place of the Atss one and a QualityLoss struct or NULL; the backward calls are the options' and
+# the quality loss's own.  effdet_loss_tal_metrics: the inspection call.
+TAL_SIGNATURES = {
+    'effdet_loss_tal_workspace_bytes': 'q:iqiip',
+    'effdet_loss_tal_fwd': 'i:ppppppqiqiippps',
+    'effdet_loss_tal_fwd_grad': 'i:ppppppqpiiiqiippps',
+    'effdet_loss_tal_metrics': 'i:pppppiqiips',
+}
 # The host-only query of the dense-conv launch plan, declared in include/effdet_conv_plan.h (same generation, same letters, same rule;
 # tests/test_conv_plan_cases_host.py compares this table and ConvPlanInfo with that header).
 CONV_PLAN_SIGNATURES = {
@@ -450,7 +467,8 @@ def lib():
                 list(WBF_SIGNATURES.items()) + list(NEEDED_SIGNATURES.items()) + list(MOSAIC_SIGNATURES.items()) + \
                 list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
                 list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
-                list(UNIT_LISTS_SIGNATURES.items()) + list(SLICES_SIGNATURES.items()) + list(QUALITY_LOSS_SIGNATURES.items()):
+                list(UNIT_LISTS_SIGNATURES.items()) + list(SLICES_SIGNATURES.items()) + list(QUALITY_LOSS_SIGNATURES.items()) + \
+                list(TAL_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

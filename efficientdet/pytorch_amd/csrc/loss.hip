@@ -28,6 +28,13 @@
 //                       iff its IoU >= thr and its centre is inside the box; the same tail
 //              loss_pos_map_kernel                   the default pass's decision alone, per pixel and ahead of the head: one byte per
 //                       pixel = one of its 9 anchors is positive (include/effdet_needed_tiles.h: the sparse regression-tower forward)
+//              tal_select_kernel, tal_assign_kernel     the task-aligned matcher (include/effdet_tal.h): one workgroup per (valid row,
+//                       image) scans ALL anchors, centre test first, and keeps the topk largest metrics m = s^alpha u^beta of the
+//                       PREDICTIONS (64-bit keys ~bits(m) << 32 | anchor, the same register lists and arg-min rounds) -> keys[b][n][16];
+//                       every winner then claims its anchor with a 64-bit integer atomicMax of bits(u) << 32 | ~n into slot[b][a]
+//                       (zeroed by tal_zero_kernel; max is order-independent, so two runs agree bit for bit); then
+//                       loss_assign_kernel's grid reads the slot -> the row with the largest u, the first on a tie; the same tail.
+//                       tal_target_kernel (after the quality pass): per row the normalised metric over its final anchors -> q
 //   quality  loss_quality_kernel: with a quality loss, after whichever assign pass ran: one thread per (image, anchor), q = the IoU
 //            between the decoded prediction and the assigned annotation (box_overlap, the box terms' expression) at a positive, else 0
 //   cls      loss_cls_kernel<F>: one thread per 4 class probabilities (16-byte loads): focal BCE with the reference's clamp to
@@ -46,6 +53,7 @@
 #include "../../../include/effdet_loss_opts.h"
 #include "../../../include/effdet_atss.h"
 #include "../../../include/effdet_quality_loss.h"
+#include "../../../include/effdet_tal.h"
 #include "../../../include/effdet_needed_tiles.h"
 
 namespace {
@@ -786,20 +794,28 @@ __device__ __forceinline__ float sel_lt(float a, float b) { return a < b ? 1.f :
 struct BoxOverlap {
   float aw, ah, pcx, pcy, dwr, dhr, pw, ph, px1, px2, py1, py2, gx1, gy1, gx2, gy2, gw, gh, iwr, ihr, iw, ih, I, U, D, iou;
 };
-__device__ __forceinline__ BoxOverlap box_overlap(float4 an, const float* __restrict__ g, float4 r) {
-  BoxOverlap o;
-  o.aw = an.z - an.x; o.ah = an.w - an.y;
-  const float acx = an.x + 0.5f * o.aw, acy = an.y + 0.5f * o.ah;
-  o.pcx = acx + 0.1f * r.x * o.aw; o.pcy = acy + 0.1f * r.y * o.ah;
-  o.dwr = 0.2f * r.z; o.dhr = 0.2f * r.w;
-  o.pw = expf(fminf(o.dwr, EFFDET_BOX_LOSS_DW_MAX)) * o.aw; o.ph = expf(fminf(o.dhr, EFFDET_BOX_LOSS_DW_MAX)) * o.ah;
-  o.px1 = o.pcx - 0.5f * o.pw; o.px2 = o.pcx + 0.5f * o.pw; o.py1 = o.pcy - 0.5f * o.ph; o.py2 = o.pcy + 0.5f * o.ph;
-  o.gx1 = g[0]; o.gy1 = g[1]; o.gx2 = g[2]; o.gy2 = g[3]; o.gw = o.gx2 - o.gx1; o.gh = o.gy2 - o.gy1;
-  o.iwr = fminf(o.px2, o.gx2) - fmaxf(o.px1, o.gx1); o.ihr = fminf(o.py2, o.gy2) - fmaxf(o.py1, o.gy1);
-  o.iw = fmaxf(o.iwr, 0.f); o.ih = fmaxf(o.ihr, 0.f);
-  o.I = o.iw * o.ih; o.U = o.pw * o.ph + o.gw * o.gh - o.I; o.D = o.U + BOX_EPS; o.iou = o.I / o.D;
+#define EFFDET_BOX_OVERLAP_BODY \
+  BoxOverlap o; \
+  o.aw = an.z - an.x; o.ah = an.w - an.y; \
+  const float acx = an.x + 0.5f * o.aw, acy = an.y + 0.5f * o.ah; \
+  o.pcx = acx + 0.1f * r.x * o.aw; o.pcy = acy + 0.1f * r.y * o.ah; \
+  o.dwr = 0.2f * r.z; o.dhr = 0.2f * r.w; \
+  o.pw = expf(fminf(o.dwr, EFFDET_BOX_LOSS_DW_MAX)) * o.aw; o.ph = expf(fminf(o.dhr, EFFDET_BOX_LOSS_DW_MAX)) * o.ah; \
+  o.px1 = o.pcx - 0.5f * o.pw; o.px2 = o.pcx + 0.5f * o.pw; o.py1 = o.pcy - 0.5f * o.ph; o.py2 = o.pcy + 0.5f * o.ph; \
+  o.gx1 = g[0]; o.gy1 = g[1]; o.gx2 = g[2]; o.gy2 = g[3]; o.gw = o.gx2 - o.gx1; o.gh = o.gy2 - o.gy1; \
+  o.iwr = fminf(o.px2, o.gx2) - fmaxf(o.px1, o.gx1); o.ihr = fminf(o.py2, o.gy2) - fmaxf(o.py1, o.gy1); \
+  o.iw = fmaxf(o.iwr, 0.f); o.ih = fmaxf(o.ihr, 0.f); \
+  o.I = o.iw * o.ih; o.U = o.pw * o.ph + o.gw * o.gh - o.I; o.D = o.U + BOX_EPS; o.iou = o.I / o.D; \
   return o;
+__device__ __forceinline__ BoxOverlap box_overlap(float4 an, const float* __restrict__ g, float4 r) { EFFDET_BOX_OVERLAP_BODY }
+// ... and the same lines with no multiply-add contracted, for the task-aligned matcher (include/effdet_tal.h): ITS kernels evaluate the
+// IoU at several places (the select pass, its claim, the inspection call) and compare the bits, so whether a multiply-add is fused
+// must not depend on the kernel the function is inlined into (as assign_iou)
+__device__ __forceinline__ BoxOverlap box_overlap_strict(float4 an, const float* __restrict__ g, float4 r) {
+#pragma clang fp contract(off)
+  EFFDET_BOX_OVERLAP_BODY
 }
+#undef EFFDET_BOX_OVERLAP_BODY
 
 // loss of one positive anchor; with GRAD its gradient wrt the regression row r (not yet scaled) in gr[4]
 template <bool GRAD>
@@ -916,6 +932,194 @@ __global__ __launch_bounds__(256) void loss_quality_kernel(const LossK p, float*
   q[i] = v;
 }
 
+// ---- the task-aligned matcher (include/effdet_tal.h)
+// topk and the exponents, and the buffers between its passes
+struct TalK {
+  int topk; float alpha, beta;
+  unsigned long long* keys; float* mm; unsigned long long* slot;      // [B][N][EFFDET_TAL_MAX_TOPK] keys, [B][N][2] (mmax, umax), [B][A] claims
+};
+
+constexpr unsigned long long TAL_NO_KEY = ~0ull;      // above every key: a candidate has m > 0, so the high half of its key is not all ones
+
+// exp2(e log2(x)), 0 at x == 0 (a negative or NaN x gives NaN)
+__device__ __forceinline__ float tal_pow(float x, float e) {
+#pragma clang fp contract(off)
+  return x == 0.f ? 0.f : exp2f(e * log2f(x));
+}
+
+// The pair quantities of anchor a (box an) of image b and the annotation row at g[0..3] with label lab: u = loss_quality_kernel's
+// expression on box_overlap_strict, m = s^alpha u^beta.  EVERY kernel of the matcher evaluates THIS function (no contraction): the
+// claim recomputes a winner's pair, and the inspection call's planes are compared with the keys bit for bit.
+struct TalPair { float m, u; };
+__device__ __forceinline__ TalPair tal_pair(const LossK& p, const TalK& t, int b, long long a, const float4 an, const float* g, int lab) {
+#pragma clang fp contract(off)
+  const long long i = (long long)b * p.A + a;
+  const float4 r = ((const float4*)p.reg)[i];
+  const BoxOverlap o = box_overlap_strict(an, g, r);
+  TalPair v;
+  v.u = nan_min(nan_max(o.iou, 0.f), 1.f) + (((r.x - r.x) + (r.y - r.y)) + ((r.z - r.z) + (r.w - r.w)));
+  const float s = p.cls[i * p.nc + lab];
+  v.m = tal_pow(s, t.alpha) * tal_pow(v.u, t.beta);
+  return v;
+}
+
+// the label of the row at rp as a class index, or -1 for a pad row or a label outside [0, nc) (a NaN included): no candidates
+__device__ __forceinline__ int tal_label(const float* rp, int nc) {
+  return (rp[4] != -1.0f && rp[4] >= 0.f && rp[4] < (float)nc) ? (int)rp[4] : -1;
+}
+
+// every pass starts from stat = 0 (num_pos is an integer atomic count), no claim, no key and (mmax, umax) = 0: a kernel, as
+// loss_zero_stat_kernel
+__global__ __launch_bounds__(256) void tal_zero_kernel(float* __restrict__ stat, long long ns, const TalK t, long long nk, long long na) {
+  const long long total = ns + nk + 2 * (nk / EFFDET_TAL_MAX_TOPK) + na;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += gridDim.x * 256LL) {
+    long long j = i;
+    if (j < ns) { stat[j] = 0.f; continue; }
+    j -= ns;
+    if (j < nk) { t.keys[j] = TAL_NO_KEY; continue; }
+    j -= nk;
+    if (j < 2 * (nk / EFFDET_TAL_MAX_TOPK)) { t.mm[j] = 0.f; continue; }
+    j -= 2 * (nk / EFFDET_TAL_MAX_TOPK);
+    t.slot[j] = 0ull;
+  }
+}
+
+// One workgroup per (row, image); a pad row (or a row whose label names no class) exits at once.  atss_select_kernel's shape over the
+// WHOLE table: every thread strides over the anchors, the centre test first (one 16-byte read for most anchors), then the pair
+// through tal_pair, and keeps its K smallest keys ~bits(m) << 32 | a as a sorted list in registers (K >= topk at compile time: the
+// insertion and the pop are fully unrolled, no runtime-indexed array); then up to topk rounds of the workgroup's arg-min over the list
+// heads, which the owner pops.  A round that finds no key left ends the rounds (every thread reads the same minimum: the exit is
+// uniform), so the sentinel is never a winner.  The winners go to keys[b][n][] in rank order; then thread j claims winner j's anchor
+// for this row: atomicMax of bits(u) << 32 | (0xFFFFFFFF - n) -- u > 0 at a winner (m > 0), so a claim is never 0 -- the largest u,
+// then the lowest row.
+template <int K>
+__global__ __launch_bounds__(256) void tal_select_kernel(const LossK p, const TalK t) {
+  const int n = blockIdx.x, b = blockIdx.y;
+  const float* rp = p.annots + ((long long)b * p.N + n) * 5;
+  const int lab = tal_label(rp, p.nc);
+  if (lab < 0) return;
+  const float r[4] = {rp[0], rp[1], rp[2], rp[3]};
+  __shared__ unsigned long long wmin[2][4];
+  __shared__ unsigned long long win[EFFDET_TAL_MAX_TOPK];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float4* anc = (const float4*)p.anchors;
+  unsigned long long keys[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) keys[j] = TAL_NO_KEY;
+  for (long long a = threadIdx.x; a < p.A; a += 256) {
+    const float4 an = anc[a];
+    if (!atss_inside(an, r)) continue;
+    const TalPair v = tal_pair(p, t, b, a, an, r, lab);
+    if (!(v.m > 0.f)) continue;                              // (a NaN metric is no candidate)
+    const unsigned long long key = ((unsigned long long)(~__float_as_uint(v.m)) << 32) | (unsigned)a;
+    if (key < keys[K - 1]) {
+#pragma unroll
+      for (int j = K - 1; j > 0; --j) {                      // new[j] = min(old[j], max(old[j - 1], key)), from the top down
+        const unsigned long long m = keys[j - 1] > key ? keys[j - 1] : key;
+        keys[j] = keys[j] < m ? keys[j] : m;
+      }
+      keys[0] = keys[0] < key ? keys[0] : key;
+    }
+  }
+  int cnt = 0;
+  for (int q = 0; q < t.topk; ++q) {
+    unsigned long long m = keys[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long v = shfl_xor_u64(m, o); m = v < m ? v : m; }
+    unsigned long long* w = wmin[q & 1];                     // two slots: one barrier per round
+    if (lane == 0) w[wave] = m;
+    __syncthreads();
+    const unsigned long long m01 = w[0] < w[1] ? w[0] : w[1], m23 = w[2] < w[3] ? w[2] : w[3];
+    m = m01 < m23 ? m01 : m23;
+    if (m == TAL_NO_KEY) break;                              // fewer candidates than topk
+    if (keys[0] == m) {                                      // the owner pops its head (keys are distinct: the anchor index)
+#pragma unroll
+      for (int j = 0; j + 1 < K; ++j) keys[j] = keys[j + 1];
+      keys[K - 1] = TAL_NO_KEY;
+    }
+    if (threadIdx.x == 0) {
+      win[q] = m;
+      t.keys[((long long)b * p.N + n) * EFFDET_TAL_MAX_TOPK + q] = m;
+    }
+    ++cnt;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < cnt) {
+    const long long a = (long long)(unsigned)win[threadIdx.x];
+    const TalPair v = tal_pair(p, t, b, a, anc[a], r, lab);
+    atomicMax(t.slot + (long long)b * p.A + a, ((unsigned long long)__float_as_uint(v.u) << 32) | (0xFFFFFFFFu - (unsigned)n));
+  }
+}
+
+// loss_assign_kernel's grid: the anchor's claim names its row (none: negative), then the shared tail.  The valid rows are only
+// counted here (the matcher has no per-anchor loop over them), 256 at a time.
+__global__ __launch_bounds__(256) void tal_assign_kernel(const LossK p, const TalK t, const KneeBeta knee) {
+  const int b = blockIdx.y;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  int total_valid = 0;
+  for (int n0 = 0; n0 < p.N; n0 += 256) {
+    const int n = n0 + (int)threadIdx.x;
+    total_valid += __syncthreads_count(n < p.N && p.annots[((long long)b * p.N + n) * 5 + 4] != -1.0f);
+  }
+  const bool ok = a < p.A;
+  float4 an = make_float4(0, 0, 0, 0);
+  int barg = -1;
+  if (ok) {
+    an = ((const float4*)p.anchors)[a];
+    const unsigned long long s = t.slot[(long long)b * p.A + a];
+    if (s != 0ull) barg = (int)(0xFFFFFFFFu - (unsigned)s);
+  }
+  assign_tail(p, b, a, ok, ok && total_valid > 0, barg < 0, barg >= 0, barg, an, knee);
+  if (blockIdx.x == 0 && threadIdx.x == 0) p.stat[b * SS + 3] = (float)total_valid;
+}
+
+// The aligned target, after loss_quality_kernel has stored q everywhere: one wave per (row, image), lane j < 16 holds winner j.  A
+// winner whose anchor's claim names this row is finally assigned to it: its m is in its key, its u in the claim (no recomputation);
+// mmax / umax over those lanes (shuffles: the 16 values never leave the wave), then q at their anchors.  A row without winners (a pad
+// row has none) writes nothing: (mmax, umax) stay tal_zero_kernel's zeros.
+__global__ __launch_bounds__(64) void tal_target_kernel(const LossK p, const TalK t, float* __restrict__ q) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x, b = blockIdx.y, j = threadIdx.x;
+  const long long row = (long long)b * p.N + n;
+  float m = 0.f, u = 0.f;
+  bool mine = false;
+  long long i = 0;
+  if (j < EFFDET_TAL_MAX_TOPK) {
+    const unsigned long long key = t.keys[row * EFFDET_TAL_MAX_TOPK + j];
+    if (key != TAL_NO_KEY) {
+      i = (long long)b * p.A + (long long)(unsigned)key;
+      const unsigned long long s = t.slot[i];
+      if (0xFFFFFFFFu - (unsigned)s == (unsigned)n) {
+        mine = true;
+        m = __uint_as_float(~(unsigned)(key >> 32));
+        u = __uint_as_float((unsigned)(s >> 32));
+      }
+    }
+  }
+  const float mmax = wave_max(m), umax = wave_max(u);      // (m, u >= 0 at a winner; the other lanes hold 0)
+  if (mine) q[i] = (m * umax) / (mmax + 1e-9f);
+  if (j == 0 && mmax > 0.f) { t.mm[row * 2] = mmax; t.mm[row * 2 + 1] = umax; }
+}
+
+// inspection: one thread per (anchor, row, image) -> out[0][b][n][a] = m, out[1][b][n][a] = u through tal_pair; 0 where the anchor's
+// centre is not inside the row's box and for a row without candidates
+__global__ __launch_bounds__(256) void tal_metrics_kernel(const LossK p, const TalK t, float* __restrict__ out) {
+  const int n = blockIdx.y, b = blockIdx.z;
+  const long long a = blockIdx.x * 256LL + threadIdx.x;
+  if (a >= p.A) return;
+  const float* rp = p.annots + ((long long)b * p.N + n) * 5;
+  const int lab = tal_label(rp, p.nc);
+  TalPair v{0.f, 0.f};
+  if (lab >= 0) {
+    const float r[4] = {rp[0], rp[1], rp[2], rp[3]};
+    const float4 an = ((const float4*)p.anchors)[a];
+    if (atss_inside(an, r)) v = tal_pair(p, t, b, a, an, r, lab);
+  }
+  const long long o = ((long long)b * p.N + n) * p.A + a;
+  out[o] = v.m;
+  out[(long long)p.B * p.N * p.A + o] = v.u;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 
@@ -964,6 +1168,19 @@ size_t carve_loss_quality(float*& q, void* ws, int B, long long A, int num_class
   return head + c.off;
 }
 
+// carve_loss_quality's layout (q where the class backward looks for it, whichever matcher ran), then the task-aligned matcher's
+// keys [B][N][EFFDET_TAL_MAX_TOPK], (mmax, umax) [B][N][2] and claims [B][A] -> bytes.  One layout with or without a quality loss.
+size_t carve_loss_tal(LossK& k, TalK& t, void* ws, int B, long long A, int num_classes, int N) {
+  carve_loss(k, ws, B, A, num_classes);
+  float* q = nullptr;
+  const size_t head = carve_loss_quality(q, ws, B, A, num_classes, N);
+  Carver c(ws ? (char*)ws + head : nullptr);
+  t.keys = c.take<unsigned long long>((size_t)B * N * EFFDET_TAL_MAX_TOPK);
+  t.mm = c.take<float>((size_t)B * N * 2);
+  t.slot = c.take<unsigned long long>((size_t)B * A);
+  return head + c.off;
+}
+
 LossK loss_args(const float* cls, const float* reg, const float* anchors, const float* annots, int B, long long A, int nc, int N) {
   LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.B = B; k.nc = nc; k.N = N; k.A = A;
   return k;
@@ -998,6 +1215,12 @@ bool atss_ok(const effdet_atss_t* t, long long A) {
   for (int l = 0; l < t->num_levels; ++l)
     if (t->level_start[l + 1] <= t->level_start[l]) return false;
   return true;
+}
+
+bool tal_ok(const effdet_tal_t* t) {
+  if (!t || t->topk < 1 || t->topk > EFFDET_TAL_MAX_TOPK) return false;
+  if (!(t->alpha >= 0.f && t->alpha <= 4.f) || !(t->beta >= 0.f && t->beta <= 16.f)) return false;      // (false for a NaN)
+  return t->aligned_target == 0 || t->aligned_target == 1;
 }
 
 inline bool dtype_ok(int dtype, bool split) { return dtype == EFFDET_F32 || dtype == EFFDET_BF16 || (split && dtype == EFFDET_F32_SPLIT); }
@@ -1152,6 +1375,47 @@ int loss_atss_forward(const float* cls, const float* reg, const float* anchors, 
     hipLaunchKernelGGL(atss_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, t, KneeBeta{opts->beta});
     EFFDET_CHECK_LAUNCH();
     return q ? launch_quality(k, q, st) : EFFDET_OK;
+   });
+  });
+  if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
+  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
+}
+
+TalK tal_args(const effdet_tal_t* tal) {
+  TalK t{}; t.topk = tal->topk; t.alpha = tal->alpha; t.beta = tal->beta;
+  return t;
+}
+
+// both forward entry points of the task-aligned matcher: loss_atss_forward with its assign path, and with a quality loss and
+// aligned_target the target pass behind the quality pass
+int loss_tal_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
+                     long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
+                     int N, const effdet_loss_opts_t* opts, const effdet_tal_t* tal, const effdet_quality_loss_t* ql,
+                     effdet_stream_t stream) {
+  if (!loss_opts_ok(opts) || opts->low_quality != 0 || B < 1 || N < 1 || A < 1 || num_classes < 1 || !tal_ok(tal)) return EFFDET_EINVAL;
+  if (ql && !quality_ok(ql)) return EFFDET_EINVAL;
+  LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
+  hipStream_t st = (hipStream_t)stream;
+  const long long need = effdet_loss_tal_workspace_bytes(B, A, num_classes, N, tal);
+  const int rc = with_class_policy(opts, ql, workspace, B, A, num_classes, N, need, [&](auto f, float* q, long long) -> int {
+   return loss_forward(k0, f, opts->reg_weight, workspace, workspace_bytes, need, grad, dtype, st, [&](LossK& k) -> int {
+    TalK t = tal_args(tal);                                  // (A < 2^31 has been checked: an anchor index fits the low half of a key)
+    carve_loss_tal(k, t, workspace, B, A, num_classes, N);
+    const long long ns = (long long)B * SS, nk = (long long)B * N * EFFDET_TAL_MAX_TOPK, na = (long long)B * A;
+    hipLaunchKernelGGL(tal_zero_kernel, dim3(grid_for(ns + nk + nk / EFFDET_TAL_MAX_TOPK * 2 + na)), dim3(256), 0, st, k.stat, ns, t, nk, na);
+    EFFDET_CHECK_LAUNCH();
+    if (t.topk <= 13) hipLaunchKernelGGL(tal_select_kernel<13>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
+    else hipLaunchKernelGGL(tal_select_kernel<EFFDET_TAL_MAX_TOPK>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
+    EFFDET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(tal_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, t, KneeBeta{opts->beta});
+    EFFDET_CHECK_LAUNCH();
+    if (!q) return EFFDET_OK;
+    if (const int rq = launch_quality(k, q, st)) return rq;
+    if (tal->aligned_target) {
+      hipLaunchKernelGGL(tal_target_kernel, dim3((unsigned)N, B), dim3(64), 0, st, k, t, q);
+      EFFDET_CHECK_LAUNCH();
+    }
+    return EFFDET_OK;
    });
   });
   if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
@@ -1413,4 +1677,37 @@ extern "C" int effdet_loss_quality_bwd_cls(const float* cls, const float* annots
                                            const effdet_loss_opts_t* opts, const effdet_quality_loss_t* quality, effdet_stream_t stream) {
   if (!quality_ok(quality)) return EFFDET_EINVAL;
   return loss_opts_bwd_cls(cls, annots, gscale, workspace, dcls, dld, dtype, B, A, num_classes, N, opts, quality, stream);
+}
+
+extern "C" long long effdet_loss_tal_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_tal_t* tal) {
+  if (!tal_ok(tal)) return EFFDET_EINVAL;
+  LossK k{}; TalK t{};
+  return (long long)carve_loss_tal(k, t, nullptr, B, A, num_classes, N);
+}
+
+extern "C" int effdet_loss_tal_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                   void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
+                                   const effdet_loss_opts_t* opts, const effdet_tal_t* tal, const effdet_quality_loss_t* quality,
+                                   effdet_stream_t stream) {
+  return loss_tal_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
+                          num_classes, N, opts, tal, quality, stream);
+}
+
+extern "C" int effdet_loss_tal_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
+                                        void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
+                                        long long A, int num_classes, int N, const effdet_loss_opts_t* opts, const effdet_tal_t* tal,
+                                        const effdet_quality_loss_t* quality, effdet_stream_t stream) {
+  return loss_tal_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
+                          num_classes, N, opts, tal, quality, stream);
+}
+
+extern "C" int effdet_loss_tal_metrics(const float* cls, const float* reg, const float* anchors, const float* annots, float* out, int B,
+                                       long long A, int num_classes, int N, const effdet_tal_t* tal, effdet_stream_t stream) {
+  if (!cls || !reg || !anchors || !annots || !out || !tal_ok(tal)) return EFFDET_EINVAL;
+  if (B < 1 || B > 65535 || N < 1 || N > 65535 || A < 1 || num_classes < 1) return EFFDET_EINVAL;
+  if (A * num_classes >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
+  const LossK k = loss_args(cls, reg, anchors, annots, B, A, num_classes, N);
+  hipLaunchKernelGGL(tal_metrics_kernel, dim3((unsigned)assign_blocks(A), N, B), dim3(256), 0, (hipStream_t)stream, k, tal_args(tal), out);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
 }

@@ -118,9 +118,10 @@ class FocalLoss(nn.Module):
     """models/losses.py:29-152 as two HIP passes; forward only (training uses the fused head+loss node).  box_loss: an
     ops.BoxLossOptions puts an IoU-family loss in the place of smooth-L1 (None: the reference's term); loss: an ops.LossOptions sets
     focal alpha / gamma, label smoothing, the smooth-L1 knee and weight and the matcher's rules (None: the reference's constants);
-    matcher: an ops.ATSSOptions assigns by ATSS in place of the IoU bands (None: the bands).  With a matcher, forward takes the
-    anchor count of every pyramid level as `levels`; without it the levels are read off the table (a level starts where the anchors
-    double in size), which costs one device -> host sync.  quality: an ops.QualityLossOptions puts the quality focal / varifocal
+    matcher: an ops.ATSSOptions assigns by ATSS in place of the IoU bands, an ops.TaskAlignedOptions by the task-aligned rule on the
+    predictions (None: the bands).  With an ATSSOptions, forward takes the anchor count of every pyramid level as `levels`; without it
+    the levels are read off the table (a level starts where the anchors double in size), which costs one device -> host sync; a
+    TaskAlignedOptions needs no levels.  quality: an ops.QualityLossOptions puts the quality focal / varifocal
     loss in the place of the focal class term (None: the focal term); the workspace of the last forward call with one is kept as
     `last_workspace` for ops.loss_quality_targets."""
 
@@ -146,7 +147,7 @@ class FocalLoss(nn.Module):
     def forward(self, classifications, regressions, anchors, annotations, levels=None):
         matcher = getattr(self, 'matcher', None)                # (a criterion pickled before the option existed has no such attribute)
         anchors = anchors.contiguous()
-        if matcher is not None and levels is None:
+        if isinstance(matcher, ops.ATSSOptions) and levels is None:
             levels = self.table_levels(anchors)
         quality = getattr(self, 'quality', None)                # (likewise)
         losses, ws = ops.loss_opts_fwd(classifications.contiguous(), regressions.contiguous(), anchors,
@@ -345,20 +346,20 @@ class _HeadLossFn(torch.autograd.Function):
     ops.BoxLossOptions of an IoU kind = that term in its place; loss: None = the reference's constants, a non-default ops.LossOptions =
     the options.  The ops.loss_opts_* calls choose the entry points for either; every choice keeps the output contract of d(logit)
     and d(reg): the three layouts, exact zeros away from the positives (the sparse regression-tower backward rests on them).
-    An ops.ATSSOptions and / or an ops.QualityLossOptions may follow the head's parameters as trailing arguments: the matcher, over
-    the five level maps, and the quality loss in the place of the focal term (forward + gradient and the class backward then go through
+    A matcher (ops.ATSSOptions or ops.TaskAlignedOptions) and / or an ops.QualityLossOptions may follow the head's parameters as
+    trailing arguments: the matcher (ATSS over the five level maps), and the quality loss in the place of the focal term (forward + gradient and the class backward then go through
     the effdet_loss_quality_* calls)."""
 
     @staticmethod
     def forward(ctx, dtype, num_classes, anchors, annots, train, box, loss, *args):
         ctx.prep, ctx.arith, ctx.box, ctx.loss = ops.get_prep(), ops.F32_ARITH_BWD, box, loss
         tail = args[5 + len(_HEAD_KEYS):]
-        ctx.matcher = matcher = next((t for t in tail if isinstance(t, ops.ATSSOptions)), None)
+        ctx.matcher = matcher = next((t for t in tail if isinstance(t, ops.MATCHERS)), None)
         ctx.quality = quality = next((t for t in tail if isinstance(t, ops.QualityLossOptions)), None)
         ctx.extra = len(tail)
         p = [Map.of(t) for t in args[:5]]
         HP = dict(zip(_HEAD_KEYS, args[5:]))
-        levels = [m.H * m.W * 9 for m in p] if matcher is not None else None
+        levels = [m.H * m.W * 9 for m in p] if isinstance(matcher, ops.ATSSOptions) else None
         # the default matcher's positives are known before the head runs, and every box term reads `reg` at them alone: the regression
         # tower computes the tiles that can reach one (two small launches per step, no host read: a captured step follows its annotations)
         # A quality loss keeps this forward: its target q reads `reg` at positive anchors only, which the needed tiles cover by
@@ -520,12 +521,17 @@ class EfficientDet(nn.Module):
     def set_matcher(self, options):
         """Anchor assignment of the training loss: None (the default) = the IoU bands of set_loss (0.4 / 0.5 unless set), through the
         same calls as ever; an ops.ATSSOptions(topk) = Adaptive Training Sample Selection over the five pyramid levels
-        (include/effdet_atss.h), with everything downstream of the assignment as set_loss / set_box_loss say.  It replaces the
-        bands: combined with a LossOptions of non-default pos_iou / neg_iou or low_quality=True it raises ValueError.  topk and the
-        levels are launch arguments: a graph.GraphedTrainStep / GraphedTrainLoop captured before a change keeps the old matcher
-        until it is captured again."""
-        if options is not None and not isinstance(options, ops.ATSSOptions):
-            raise TypeError('set_matcher takes an ATSSOptions or None, not %r' % (options,))
+        (include/effdet_atss.h); an ops.TaskAlignedOptions(topk, alpha, beta, aligned_target) = the task-aligned assigner of TOOD /
+        PP-YOLOE / YOLOv8 (include/effdet_tal.h), which picks positives by how well the PREDICTED class score and box agree with an
+        annotation and, with set_quality_loss, trains the score towards that agreement.  Everything downstream of the assignment
+        is as set_loss / set_box_loss / set_quality_loss say.  A matcher replaces the bands: combined with a LossOptions of
+        non-default pos_iou / neg_iou or low_quality=True it raises ValueError.  With a matcher the regression tower's forward is
+        dense (the positives are not known before the head runs); its sparse backward stays.  The matcher's values (and ATSS's
+        levels) are launch arguments: a graph.GraphedTrainStep / GraphedTrainLoop captured before a change keeps the old matcher
+        until it is captured again -- the usual recipe, ATSS for the first epochs and then the task-aligned matcher, is one
+        set_matcher call plus a new capture.  No mAP has been measured with either."""
+        if options is not None and not isinstance(options, ops.MATCHERS):
+            raise TypeError('set_matcher takes an ATSSOptions, a TaskAlignedOptions or None, not %r' % (options,))
         ops.check_matcher(options, getattr(self, 'loss_options', None))
         self.matcher = options
         self.criterion.matcher = options

@@ -2032,7 +2032,9 @@ def merge_slices(lists, table, H, W, options=None):
 # A matcher (ATSSOptions) is a fourth set for the two forward calls, effdet_loss_atss_* (the options struct, then the matcher's); its
 # backward calls are the options set's, with the options struct even where its values are the defaults.  A quality loss
 # (QualityLossOptions) is a fifth set for the forward calls and the class backward, effdet_loss_quality_* (the options struct, the
-# matcher's or NULL, its own); its d(reg) call is the options set's.
+# matcher's or NULL, its own); its d(reg) call is the options set's.  The task-aligned matcher (TaskAlignedOptions) has forward calls of
+# its own, effdet_loss_tal_* (the options struct, the matcher's, the quality loss's or NULL); its backward calls are the options set's
+# resp. the quality loss's.
 BOX_LOSS_KINDS = {'smooth_l1': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}     # EFFDET_BOX_LOSS_* (0: the effdet_focal_loss_* calls)
 
 
@@ -2156,6 +2158,43 @@ class ATSSOptions:
         return 'ATSSOptions(topk=%r)' % self.topk
 
 
+class TaskAlignedOptions:
+    """The task-aligned matcher of EfficientDet.set_matcher / FocalLoss(matcher=) (include/effdet_tal.h; TOOD, PP-YOLOE, YOLOv8), in
+    place of the IoU bands: per annotation, among the anchors whose centre lies inside its box, the topk with the largest alignment
+    metric m = s^alpha u^beta are selected -- s the PREDICTED probability of the annotation's class, u the IoU between the DECODED
+    prediction and the annotation -- and an anchor selected by several annotations takes the one with the largest u.  With a quality
+    loss and aligned_target the soft target of a positive is m normalised per annotation to its largest IoU (TOOD's target) instead of
+    the IoU itself.  Values are kept as the fp32 the kernels receive.  The assignment reads the predictions, so it is usually switched
+    on after a few epochs of ATSS (set_matcher plus a new capture of a graphed step); it needs no pyramid levels."""
+
+    def __init__(self, topk=13, alpha=1.0, beta=6.0, aligned_target=True):
+        if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= L.TAL_MAX_TOPK:
+            raise ValueError('TaskAlignedOptions: topk must be an int in [1, %d], not %r' % (L.TAL_MAX_TOPK, topk))
+        a, b = _f32(alpha), _f32(beta)
+        if not 0.0 <= a <= 4.0:
+            raise ValueError('TaskAlignedOptions: alpha must lie in [0, 4], not %r' % (alpha,))
+        if not 0.0 <= b <= 16.0:
+            raise ValueError('TaskAlignedOptions: beta must lie in [0, 16], not %r' % (beta,))
+        if aligned_target not in (False, True, 0, 1):
+            raise ValueError('TaskAlignedOptions: aligned_target must be a bool, not %r' % (aligned_target,))
+        self.topk, self.alpha, self.beta, self.aligned_target = topk, a, b, bool(aligned_target)
+
+    def key(self):
+        return (self.topk, self.alpha, self.beta, self.aligned_target)
+
+    def __eq__(self, other):
+        return isinstance(other, TaskAlignedOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'TaskAlignedOptions(topk=%r, alpha=%r, beta=%r, aligned_target=%r)' % self.key()
+
+
+MATCHERS = (ATSSOptions, TaskAlignedOptions)
+
+
 QUALITY_KINDS = {'qfl': L.QUALITY_QFL, 'vfl': L.QUALITY_VFL}     # EFFDET_QUALITY_*
 
 
@@ -2209,11 +2248,12 @@ def _quality_struct(quality):
 
 
 def check_matcher(matcher, loss):
-    """TypeError on anything but an ATSSOptions / None; ValueError where loss sets what a matcher replaces (bands, low_quality)."""
+    """TypeError on anything but an ATSSOptions / TaskAlignedOptions / None; ValueError where loss sets what a matcher replaces (bands,
+    low_quality)."""
     if matcher is None:
         return
-    if not isinstance(matcher, ATSSOptions):
-        raise TypeError('matcher must be an ATSSOptions or None, not %r' % (matcher,))
+    if not isinstance(matcher, MATCHERS):
+        raise TypeError('matcher must be an ATSSOptions, a TaskAlignedOptions or None, not %r' % (matcher,))
     if isinstance(loss, LossOptions) and (loss.low_quality or (loss.pos_iou, loss.neg_iou) != _LOSS_DEFAULT_KEY[5:7]):
         raise ValueError('%r replaces the IoU bands: it cannot be combined with the pos_iou / neg_iou / low_quality of %r'
                          % (matcher, loss))
@@ -2230,6 +2270,17 @@ def _atss_struct(matcher, levels, A):
     for i, v in enumerate(levels):
         t.level_start[i + 1] = t.level_start[i] + v
     return t
+
+
+def _tal_struct(matcher):
+    return L.Tal(matcher.topk, matcher.alpha, matcher.beta, 1 if matcher.aligned_target else 0)
+
+
+def _matcher_struct(matcher, levels, A):
+    """-> the host struct of matcher for the forward calls: an effdet_atss_t (it needs levels), an effdet_tal_t, or None."""
+    if matcher is None:
+        return None
+    return _tal_struct(matcher) if isinstance(matcher, TaskAlignedOptions) else _atss_struct(matcher, levels, A)
 
 
 def _loss_opts_struct(loss, box=None, force=False):
@@ -2251,13 +2302,17 @@ def _loss_opts_struct(loss, box=None, force=False):
 
 def _loss_entry(stem, loss=None, box=None, matcher=None, atss=None, quality=None):
     """-> (the entry point of the call `stem` for (loss, box, matcher, quality), its name, its extra arguments, whether it is of the
-    options set).  atss: the matcher's effdet_atss_t, for the forward calls.  A quality loss has calls of its own for the forward
-    and the class backward (the options struct, the matcher's or NULL on the forward calls, its own); its d(reg) call is the
-    options set's, with the options struct even where its values are the defaults."""
+    options set).  atss: the matcher's effdet_atss_t resp. effdet_tal_t, for the forward calls.  A quality loss has calls of its own
+    for the forward and the class backward (the options struct, the matcher's or NULL on the forward calls, its own); its d(reg) call
+    is the options set's, with the options struct even where its values are the defaults.  A TaskAlignedOptions has forward calls of
+    its own (the options struct, its own, the quality loss's or NULL)."""
     check_matcher(matcher, loss)
     check_quality(quality, loss)
     o = _loss_opts_struct(loss, box, force=matcher is not None or quality is not None)
-    if quality is not None and stem != 'bwd_reg':
+    if isinstance(atss, L.Tal) and stem in ('fwd', 'fwd_grad'):
+        name = 'effdet_loss_tal_' + stem
+        extra = (C.byref(o), C.byref(atss), None if quality is None else C.byref(_quality_struct(quality)))
+    elif quality is not None and stem != 'bwd_reg':
         name = 'effdet_loss_quality_' + stem
         mid = () if stem == 'bwd_cls' else (None if atss is None else C.byref(atss),)
         extra = (C.byref(o),) + mid + (C.byref(_quality_struct(quality)),)
@@ -2280,9 +2335,11 @@ def _loss_forward(cls, reg, anc, annots, loss, box, grad=None, matcher=None, lev
     B, A, nc = cls.shape
     N = annots.shape[1]
     check_matcher(matcher, loss)
-    atss = None if matcher is None else _atss_struct(matcher, levels, A)
+    atss = _matcher_struct(matcher, levels, A)
     fn, name, extra, opts = _loss_entry('fwd_grad' if grad else 'fwd', loss, box, matcher, atss, quality)
-    if quality is not None:
+    if isinstance(atss, L.Tal):
+        nbytes = int(L.require('effdet_loss_tal_workspace_bytes').effdet_loss_tal_workspace_bytes(B, A, nc, N, C.byref(atss)))
+    elif quality is not None:
         nbytes = int(L.require('effdet_loss_quality_workspace_bytes').effdet_loss_quality_workspace_bytes(
             B, A, nc, N, None if atss is None else C.byref(atss)))
     elif atss is not None:
@@ -2374,7 +2431,8 @@ def box_loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False,
 
 def loss_opts_fwd(cls, reg, anc, annots, loss=None, box=None, matcher=None, levels=None, quality=None):
     """box_loss_fwd with the options of loss (None / the defaults: box_loss_fwd itself) -> (losses [2], ws).  matcher: an ATSSOptions
-    assigns by ATSS over the pyramid levels (levels: the anchor count of every level) through the effdet_loss_atss_* calls, with
+    assigns by ATSS over the pyramid levels (levels: the anchor count of every level) through the effdet_loss_atss_* calls, a
+    TaskAlignedOptions by the task-aligned rule on the predictions through the effdet_loss_tal_* calls (no levels), either with
     the options struct of loss (None / the defaults: the default VALUES through the option kernels).  quality: a QualityLossOptions
     puts its IoU-aware class term in the place of the focal one through the effdet_loss_quality_* calls (the options struct likewise;
     one more launch, which leaves the targets in the workspace: loss_quality_targets)."""
@@ -2400,18 +2458,59 @@ def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False
     return _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher, quality)
 
 
+def _al256(n):
+    return (n + 255) // 256 * 256
+
+
+def _tal_tail_bytes(B, A, N):
+    """The task-aligned matcher's own buffers behind q (include/effdet_tal.h): keys, (mmax, umax), claims."""
+    return _al256(8 * L.TAL_MAX_TOPK * B * N) + _al256(8 * B * N) + _al256(8 * B * A)
+
+
 def loss_quality_targets(ws, B, A, N, matcher=None):
     """-> q [B, A] fp32, a VIEW of the workspace ws that a forward call with a quality loss left (include/effdet_quality_loss.h): the
     IoU between a positive anchor's decoded prediction and its annotation, clamped to [0, 1]; 0 at every other anchor (so
     q.sum() / (codes >= 0).sum() is the mean IoU of the positives).  It is the last buffer of the workspace and lies at the same offset
-    for either matcher; N and matcher name the call that left ws and are only checked."""
-    if matcher is not None and not isinstance(matcher, ATSSOptions):
-        raise TypeError('matcher must be an ATSSOptions or None, not %r' % (matcher,))
-    nq = (4 * B * A + 255) // 256 * 256
-    if ws.dtype != torch.uint8 or ws.dim() != 1 or N < 1 or ws.numel() < nq + 4 * B * A:
+    for the bands and ATSS; behind a TaskAlignedOptions call (matcher must then name it) the matcher's own buffers follow it, and with
+    aligned_target q is the normalised alignment metric (include/effdet_tal.h).  N and matcher name the call that left ws."""
+    if matcher is not None and not isinstance(matcher, MATCHERS):
+        raise TypeError('matcher must be an ATSSOptions, a TaskAlignedOptions or None, not %r' % (matcher,))
+    nq = _al256(4 * B * A)
+    tail = _tal_tail_bytes(B, A, N) if isinstance(matcher, TaskAlignedOptions) else 0
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or N < 1 or ws.numel() < tail + nq + 4 * B * A:
         raise ValueError('ws is not the workspace of a forward call with a quality loss on [%d, %d] anchors' % (B, A))
-    off = ws.numel() - nq
+    off = ws.numel() - tail - nq
     return ws[off:off + 4 * B * A].view(torch.float32).reshape(B, A)
+
+
+def loss_tal_candidates(ws, B, A, N):
+    """-> (keys [B, N, 16] int64, mm [B, N, 2] fp32), VIEWS of the workspace ws that a forward call with a TaskAlignedOptions left
+    (include/effdet_tal.h).  keys: every annotation's selected anchors in rank order, (~bits(m) << 32) | anchor as the 64-bit pattern,
+    padded with -1 (all ones); mm: (mmax, umax) of the rows an aligned target was formed for, else 0."""
+    tail = _tal_tail_bytes(B, A, N)
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or N < 1 or ws.numel() < tail:
+        raise ValueError('ws is not the workspace of a forward call with a TaskAlignedOptions on [%d, %d] anchors, %d rows' % (B, A, N))
+    off = ws.numel() - tail
+    nk = 8 * L.TAL_MAX_TOPK * B * N
+    keys = ws[off:off + nk].view(torch.int64).reshape(B, N, L.TAL_MAX_TOPK)
+    off += _al256(nk)
+    return keys, ws[off:off + 8 * B * N].view(torch.float32).reshape(B, N, 2)
+
+
+def loss_tal_metrics(cls, reg, anc, annots, options):
+    """-> (m, u), each [B, N, A] fp32: the alignment metric and the IoU of every (annotation, anchor) pair as the task-aligned matcher
+    of options evaluates them (the same device function); 0 where the anchor's centre is not inside the annotation, for a pad row and
+    for a label outside the classes.  For inspection and tests: B N A values are written."""
+    if not isinstance(options, TaskAlignedOptions):
+        raise TypeError('options must be a TaskAlignedOptions, not %r' % (options,))
+    B, A, nc = cls.shape
+    N = annots.shape[1]
+    out = torch.empty((2, B, N, A), dtype=torch.float32, device=cls.device)
+    t = _tal_struct(options)
+    lib = L.require('effdet_loss_tal_metrics')
+    L.check(lib.effdet_loss_tal_metrics(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(out), B, A, nc, N, C.byref(t),
+                                        L.stream_ptr()), 'effdet_loss_tal_metrics')
+    return out[0], out[1]
 
 
 def pad_rows(src_map, cpad):
