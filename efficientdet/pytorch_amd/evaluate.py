@@ -8,7 +8,9 @@ MS-COCO result dicts {'image_id', 'category_id', 'score', 'bbox': [x, y, w, h]}.
 The VOC metric itself (eval.py:165-257 `evaluate` after `_get_detections`) runs on the device too: ``VOCMeanAP`` keeps one record per
 detection slot on the GPU across the dataset (csrc/voc_map.hip) and the host receives the per-class APs once, in ``compute``;
 ``evaluate_voc`` is the drop-in for ``evaluate(generator, model)``.  The COCO box metric (pycocotools' ``COCOeval`` as eval.py:260-338
-`evaluate_coco` runs it) is on the device the same way: ``COCOMeanAP`` (csrc/coco_map.hip) and the drop-in ``evaluate_coco``."""
+`evaluate_coco` runs it) is on the device the same way: ``COCOMeanAP`` (csrc/coco_map.hip) and the drop-in ``evaluate_coco``.
+``OperatingPoint`` / ``evaluate_operating_point`` (csrc/op_point.hip; the reference has no counterpart) answer where to cut the
+detections: precision / recall / F1 against a grid of confidence thresholds and a confusion matrix, over the VOC meter's records."""
 import numpy as np
 import torch
 
@@ -418,6 +420,116 @@ def evaluate_voc(generator, model, iou_threshold=0.5, score_threshold=0.05, max_
         print('{}: {}'.format(generator.label_to_name(label), average_precisions[label][0]))
     print('avg mAP: {}'.format(mean))
     return mean, average_precisions
+
+
+# ------------------------------------------------------------------------------------------------ operating point
+class OperatingPoint(VOCMeanAP):
+    """Where to cut the detections: precision / recall / F1 of every class against a grid of confidence thresholds, the threshold
+    with the best F1, and a confusion matrix, accumulated on the device over VOCMeanAP's records (include/effdet_op_point.h,
+    csrc/op_point.hip).
+
+    ``add(dets, counts, gt)`` takes what VOCMeanAP.add takes (finalize_device's rows, score-descending per image -- the curves rely on
+    that order); besides the VOC records it adds the batch to the confusion matrix: the predictions are the rows with
+    score > conf_threshold, matched to the objects at IoU > confusion_iou whatever their labels (Ultralytics' process_batch with its
+    ties decided: a prediction keeps its best object, the first of equals; an object keeps its best prediction, the lowest row of
+    equals).  No device->host transfer.  ``compute()`` returns a dict:
+
+      thresholds            the grid, fp32 [M] (default i / 1000, i = 0..1000)
+      tp, npred             int32 [C, M]: TPs (at iou_threshold, VOC matching) and detections of the class with score > threshold
+      precision, recall, f1 fp64 [C, M]: tp / npred (1 without detections), tp / annotations (0 without), 2PR / (P + R) (0 for 0 / 0)
+      mean                  fp64 [3, M]: their means over the classes with annotations
+      num_annotations       int64 [C]
+      per_class             {label: (threshold, P, R, F1)} at the class's own best F1 (the lowest such threshold); classes without
+                            annotations are absent
+      overall               (threshold, P, R, F1) at the best mean F1; (None, 0.0, 0.0, 0.0) when no class has annotations
+      ap, mean_ap           VOC AP per class (fp64 [C]) at iou_threshold and their mean, as VOCMeanAP.compute gives them
+      confusion             int64 [C + 1, C + 1]: row = predicted class, column = true class, index C = background
+
+    Only these tables are copied to the host.  Unlike Ultralytics the F1 curve is not smoothed and the thresholds are a fixed grid, not
+    interpolated over all confidences."""
+
+    def __init__(self, num_classes, iou_threshold=0.5, conf_threshold=0.25, confusion_iou=0.45, thresholds=None, device=None):
+        self.thresholds = ops.op_thresholds(thresholds)
+        self.conf_threshold, self.confusion_iou = float(conf_threshold), float(confusion_iou)
+        if self.conf_threshold != self.conf_threshold or self.confusion_iou != self.confusion_iou:
+            raise ValueError('conf_threshold and confusion_iou must not be NaN')
+        super().__init__(num_classes, iou_threshold, device)
+
+    def reset(self):
+        super().reset()
+        self._confusion = torch.zeros((self.num_classes + 1, self.num_classes + 1), dtype=torch.int64, device=self.device)
+
+    def add(self, dets, counts, gt):
+        """dets [B, max_det, 6] fp32 and counts [B] of finalize_device (device tensors); gt: see VOCMeanAP."""
+        dets, counts = _check_dets(dets, counts, self.device)
+        B, M = int(dets.shape[0]), int(dets.shape[1])
+        if B == 0 or M == 0:
+            return
+        boxes, labels = self._ground_truth(gt, B)
+        self._reserve(self.num_records + B * M)
+        n = self.num_records
+        ops.voc_match(dets, counts, boxes, labels, self.num_classes, self.iou_threshold, self._rec[0][n:], self._rec[1][n:],
+                      self._gt_count)
+        ops.confusion_match(dets, counts, boxes, labels, self.num_classes, self.conf_threshold, self.confusion_iou, self._confusion)
+        self.num_records = n + B * M
+
+    def compute(self):
+        """-> the dict of the class docstring."""
+        C = self.num_classes
+        cur = ops.op_curves(*self._rec, self.num_records, self._gt_count, C, self.thresholds)
+        mean_ap, aps = super().compute()
+        out = {k: cur[k].cpu().numpy() for k in ('tp', 'npred', 'precision', 'recall', 'f1', 'mean')}
+        best = cur['best'].cpu().numpy()
+        th = self.thresholds.copy()
+        out['thresholds'] = th
+        out['num_annotations'] = self._gt_count.cpu().numpy().astype(np.int64)
+        out['per_class'] = {c: (float(th[int(best[c, 0])]), best[c, 1], best[c, 2], best[c, 3]) for c in range(C) if best[c, 0] >= 0}
+        j = int(best[C, 0])
+        out['overall'] = (float(th[j]), best[C, 1], best[C, 2], best[C, 3]) if j >= 0 else (None, 0.0, 0.0, 0.0)
+        out['ap'] = np.array([aps[c][0] for c in range(C)], dtype=np.float64)
+        out['mean_ap'] = mean_ap
+        out['confusion'] = self._confusion.cpu().numpy()
+        return out
+
+
+def operating_point_lines(result, names):
+    """The summary evaluate_operating_point prints for an OperatingPoint.compute() dict: one line per class (P, R and F1 at the overall
+    threshold, the class's own best threshold, AP), then the overall line."""
+    t = result['overall'][0]
+    j = -1 if t is None else int(np.flatnonzero(result['thresholds'] == np.float32(t))[0])      # (the grid is strictly ascending)
+    lines = []
+    for c, name in enumerate(names):
+        p, r, f = (result['precision'][c, j], result['recall'][c, j], result['f1'][c, j]) if j >= 0 else (0.0, 0.0, 0.0)
+        own = result['per_class'][c][0] if c in result['per_class'] else None
+        lines.append('{}: annotations {} P {:.4f} R {:.4f} F1 {:.4f} best threshold {} AP {}'.format(
+            name, int(result['num_annotations'][c]), p, r, f, own, result['ap'][c]))
+    t, p, r, f = result['overall']
+    lines.append('overall: threshold {} P {:.4f} R {:.4f} F1 {:.4f} mAP {}'.format(t, p, r, f, result['mean_ap']))
+    return lines
+
+
+def evaluate_operating_point(generator, model, iou_threshold=0.5, score_threshold=0.05, max_detections=100, batch_size=1,
+                             conf_threshold=0.25, confusion_iou=0.45, thresholds=None):
+    """The operating point of ``model`` on ``generator``: evaluate_voc's generator protocol, batching and models (an EfficientDet, an
+    EnsembleDetector or a SlicedDetector), an OperatingPoint meter instead of the VOC one.  Prints one line per class (annotations; P, R
+    and F1 at the overall threshold; the class's own best threshold; AP) and the overall line, and returns OperatingPoint.compute()'s
+    dict.  ``overall[0]`` is the score threshold with the best mean F1: assigning it to ``model.threshold`` is the intended use; this
+    function does not do it.  The detections are cut at score_threshold and max_detections before the meter sees them, so every
+    threshold of the grid below score_threshold sees the same detections as score_threshold itself, and the confusion matrix is that of
+    max(conf_threshold, score_threshold)."""
+    model.eval()
+    device = _model_device(model)
+    meter = OperatingPoint(generator.num_classes(), iou_threshold, conf_threshold, confusion_iou, thresholds, device)
+    with torch.no_grad():
+        for batch in _image_batches(generator, max(1, int(batch_size))):
+            s, l, b, count, _ = _detect_batch(model, batch, device)
+            dets, counts = finalize_device(s, l, b, count, [sc for _, _, sc in batch], score_threshold, max_detections)
+            meter.add(dets, counts, [generator.load_annotations(i) for i, _, _ in batch])
+    result = meter.compute()
+    print('\noperating point:')
+    for line in operating_point_lines(result, [generator.label_to_name(c) for c in range(generator.num_classes())]):
+        print(line)
+    return result
 
 
 # ------------------------------------------------------------------------------------------------ COCO box metric

@@ -2599,6 +2599,71 @@ def voc_ap(rec_key, rec_tp, num_records, gt_count, num_classes):
     return out, recall[:N], precision[:N], seg
 
 
+OP_MAX_THRESHOLDS = L.OP_MAX_THRESHOLDS                # thresholds per effdet_op_curves call
+_OP_POINT = ('effdet_op_curves_workspace_bytes', 'effdet_op_curves', 'effdet_confusion_match')
+
+
+def op_thresholds(thresholds=None):
+    """The confidence grid of op_curves as a checked fp32 array: None gives i / 1000 for i = 0..1000; anything else must be 1 to
+    OP_MAX_THRESHOLDS finite, strictly ascending values; -0.0 becomes +0.0 (the one threshold whose key differs from `score > t`)."""
+    if thresholds is None:
+        return (np.arange(1001) / 1000).astype(np.float32)
+    t = np.array(thresholds, dtype=np.float32).reshape(-1)
+    if not 1 <= t.size <= OP_MAX_THRESHOLDS:
+        raise ValueError('thresholds: 1 to %d values, got %d' % (OP_MAX_THRESHOLDS, t.size))
+    if not np.all(np.isfinite(t)):
+        raise ValueError('thresholds must be finite')
+    if not np.all(t[1:] > t[:-1]):
+        raise ValueError('thresholds must be strictly ascending')
+    t[t == 0] = 0.0
+    return t
+
+
+def op_curves(rec_key, rec_tp, num_records, gt_count, num_classes, thresholds=None, out=None):
+    """Precision / recall / F1 against a confidence grid over the first num_records records of voc_match (include/effdet_op_point.h)
+    -> dict of device tensors: thresholds [M] fp32, tp / npred [C, M] int32, precision / recall / f1 [C, M] fp64, mean [3, M] fp64,
+    best [C + 1, 4] fp64 (j*, P, R, F1; row C: the mean curves').  out: such a dict of the caller's (every element is overwritten)."""
+    Lb = L.require(*_OP_POINT)
+    dev = gt_count.device
+    N, Cn = int(num_records), int(num_classes)
+    th = op_thresholds(thresholds)
+    M = int(th.size)
+    assert gt_count.dtype == torch.int32 and gt_count.is_contiguous() and gt_count.numel() == Cn
+    assert N == 0 or (rec_key.dtype == torch.int64 and rec_tp.dtype == torch.uint8 and rec_key.numel() >= N and rec_tp.numel() >= N)
+    td = torch.from_numpy(th).to(dev)
+    ws = torch.empty(max(int(Lb.effdet_op_curves_workspace_bytes(N)), 1), dtype=torch.uint8, device=dev)
+    shapes = {'tp': ((Cn, M), torch.int32), 'npred': ((Cn, M), torch.int32), 'precision': ((Cn, M), torch.float64),
+              'recall': ((Cn, M), torch.float64), 'f1': ((Cn, M), torch.float64), 'mean': ((3, M), torch.float64),
+              'best': ((Cn + 1, 4), torch.float64)}
+    if out is None:
+        out = {k: torch.empty(s, dtype=dt, device=dev) for k, (s, dt) in shapes.items()}
+    else:
+        out = dict(out)
+        for k, (s, dt) in shapes.items():
+            assert tuple(out[k].shape) == s and out[k].dtype == dt and out[k].is_contiguous() and out[k].device == dev, k
+    out['thresholds'] = td
+    L.check(Lb.effdet_op_curves(L.ptr(rec_key) if N else None, L.ptr(rec_tp) if N else None, N, L.ptr(gt_count), Cn, L.ptr(td), M,
+                                L.ptr(ws), ws.numel(), L.ptr(out['tp']), L.ptr(out['npred']), L.ptr(out['precision']),
+                                L.ptr(out['recall']), L.ptr(out['f1']), L.ptr(out['mean']), L.ptr(out['best']), L.stream_ptr()),
+            'effdet_op_curves')
+    return out
+
+
+def confusion_match(dets, counts, gt_boxes, gt_labels, num_classes, conf_threshold, iou_threshold, matrix):
+    """Confusion counts of one batch (include/effdet_op_point.h): voc_match's dets / counts / gt_boxes / gt_labels; ADDS to matrix
+    [num_classes + 1, num_classes + 1] int64 (row = predicted class, column = true class, index num_classes = background)."""
+    B, max_det = int(dets.shape[0]), int(dets.shape[1])
+    G = int(gt_boxes.shape[1])
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.shape[2] == 6
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == B
+    assert gt_boxes.dtype == torch.float64 and gt_boxes.is_contiguous() and tuple(gt_boxes.shape) == (B, G, 4)
+    assert gt_labels.dtype == torch.int32 and gt_labels.is_contiguous() and tuple(gt_labels.shape) == (B, G)
+    assert matrix.dtype == torch.int64 and matrix.is_contiguous() and tuple(matrix.shape) == (num_classes + 1, num_classes + 1)
+    L.check(L.require(*_OP_POINT).effdet_confusion_match(L.ptr(dets), L.ptr(counts), L.ptr(gt_boxes), L.ptr(gt_labels), B, max_det, G,
+                                                         int(num_classes), float(conf_threshold), float(iou_threshold), L.ptr(matrix),
+                                                         L.stream_ptr()), 'effdet_confusion_match')
+
+
 COCO_MAX_GT = 2048                 # GT rows per image effdet_coco_match stages in LDS
 COCO_MAX_CATEGORIES = 1024
 _COCO = ('effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes')
