@@ -1,7 +1,7 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h, include/effdet_affine.h,
 include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h, include/effdet_resample.h, include/effdet_slices.h,
-include/effdet_quality_loss.h, include/effdet_tal.h, include/effdet_op_point.h).
+include/effdet_quality_loss.h, include/effdet_tal.h, include/effdet_op_point.h, include/effdet_track.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -446,6 +446,15 @@ OP_POINT_SIGNATURES = {
     'effdet_confusion_match': 'i:ppppiiiifdps',
 }
 OP_MAX_THRESHOLDS = 4096                                                                         # EFFDET_OP_MAX_THRESHOLDS
+# Multi-object tracking (ByteTrack over finalize_dets' rows), declared in include/effdet_track.h (same generation, same letters, same
+# rule; tests/test_track_host.py compares this table with that header's prototypes).
+TRACK_SIGNATURES = {
+    'effdet_track_state_bytes': 'q:ii',
+    'effdet_track_reset': 'i:piips',
+    'effdet_track_step': 'i:ppiipiffffffiiippps',
+    'effdet_track_overflow': 'i:piips',
+}
+TRACK_MAX_TRACKS, TRACK_MAX_DET, TRACK_ROW_WORDS = 256, 128, 28                                  # EFFDET_TRACK_*
 WGRAD_PATHS = ('tiled', 'thin', 'split', 'stem')                                                # EFFDET_WGRAD_PATH_* in order
 OPT_ROW, OPT_RULE_ADAMW, OPT_RULE_SGD, OPT_GATED, OPT_EMA = 8, 0, 1, 1, 2      # EFFDET_OPT_* of that header
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
@@ -476,7 +485,7 @@ def lib():
                 list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
                 list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
                 list(UNIT_LISTS_SIGNATURES.items()) + list(SLICES_SIGNATURES.items()) + list(QUALITY_LOSS_SIGNATURES.items()) + \
-                list(TAL_SIGNATURES.items()) + list(OP_POINT_SIGNATURES.items()):
+                list(TAL_SIGNATURES.items()) + list(OP_POINT_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

@@ -10,7 +10,9 @@ detection slot on the GPU across the dataset (csrc/voc_map.hip) and the host rec
 ``evaluate_voc`` is the drop-in for ``evaluate(generator, model)``.  The COCO box metric (pycocotools' ``COCOeval`` as eval.py:260-338
 `evaluate_coco` runs it) is on the device the same way: ``COCOMeanAP`` (csrc/coco_map.hip) and the drop-in ``evaluate_coco``.
 ``OperatingPoint`` / ``evaluate_operating_point`` (csrc/op_point.hip; the reference has no counterpart) answer where to cut the
-detections: precision / recall / F1 against a grid of confidence thresholds and a confusion matrix, over the VOC meter's records."""
+detections: precision / recall / F1 against a grid of confidence thresholds and a confusion matrix, over the VOC meter's records.
+``TrackedDetector`` (csrc/track.hip; the reference's camera mode has no counterpart) gives the boxes of a video identities: ByteTrack over
+finalize_device's rows, one tracker per image of the batch, state and outputs on the device."""
 import numpy as np
 import torch
 
@@ -207,6 +209,108 @@ class SlicedDetector:
         if f16x3 and not torch.cuda.is_current_stream_capturing():
             ops.check_range_flag(s.device)
         return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
+
+
+class TrackedDetector:
+    """A detector for video: every image of the batch is one camera stream, and each call is the streams' next frame.  ``update`` runs
+    ``model``'s own detection pass (an EfficientDet, an EnsembleDetector or a SlicedDetector: its NMS and TTA settings apply), the eval
+    consumer on the device (finalize_device; score_threshold None: options.low_thr, because ByteTrack needs the low detections) and ONE
+    ops.track_step (csrc/track.hip, include/effdet_track.h): ByteTrack with a greedy assignment, state on the device, no host read.  The
+    state is allocated at the first update for that batch size; another batch size later raises (reset() and a new wrapper are the ways
+    to start over).  options is read at every update; its max_tracks is fixed once the state exists (ops.track_step refuses another).
+
+    Capture.  update reads nothing back, so the caller can capture it in a torch.cuda.graph over a static image buffer -- with the
+    recipe of any captured forward here: two warm-up updates on a side stream (the first allocates the state and records the model's
+    parameter-preparation jobs, the second builds their device tables; neither may happen under capture), then reset() (the warm-up
+    frames advanced frame_id and next_id), then the capture; scales must be None or a device tensor (a host list would be uploaded
+    under capture).  The three tensors the captured call returned are rewritten by every replay.  For an f16x3 model the range flag
+    is cleared inside update (a node of the graph) and checked by tracks(), the form that reads back; after a replay
+    ops.check_range_flag(device) is the caller's:
+
+        side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            tracker.update(static); tracker.update(static)
+        torch.cuda.current_stream().wait_stream(side); tracker.reset()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            rows, ids, count = tracker.update(static)
+        static.copy_(frame); graph.replay()                   # per frame"""
+
+    def __init__(self, model, options=None, score_threshold=None, max_detections=100):
+        options = ops.TrackOptions() if options is None else options
+        if not isinstance(options, ops.TrackOptions):
+            raise TypeError('TrackedDetector: options must be a TrackOptions, not %r' % (options,))
+        if not hasattr(model, 'num_classes') or not (hasattr(model, 'forward_raw') or hasattr(model, 'detections')):
+            raise TypeError('TrackedDetector: model must be an EfficientDet, an EnsembleDetector or a SlicedDetector, not %r' % (model,))
+        if not 1 <= int(max_detections) <= ops.TRACK_MAX_DET:
+            raise ValueError('TrackedDetector: max_detections must be in 1..%d' % ops.TRACK_MAX_DET)
+        score_threshold = options.low_thr if score_threshold is None else float(score_threshold)
+        if not abs(score_threshold) < float('inf'):
+            raise ValueError('TrackedDetector: score_threshold must be finite')
+        self.model, self.options, self.score_threshold, self.max_detections = model, options, score_threshold, int(max_detections)
+        self.num_classes = int(model.num_classes)
+        self.state = None
+
+    def eval(self):
+        self.model.eval()
+        return self
+
+    def train(self, mode=True):
+        self.model.train(mode)
+        return self
+
+    def parameters(self):
+        return self.model.parameters()
+
+    def _f16x3(self):
+        def members(m):
+            inner = getattr(m, 'models', None) or ([m.model] if hasattr(m, 'model') and not hasattr(m, 'forward_raw') else None)
+            return [m] if inner is None else [x for i in inner for x in members(i)]
+        return any(ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3' for m in members(self.model))
+
+    def detections_device(self, images, scales=None):
+        """The detection half of update -> finalize_device's (dets [B, max_detections, 6], counts [B]) on the device."""
+        B = int(images.shape[0])
+        if self._f16x3():
+            ops.clear_range_flag(images.device)
+        if scales is None:
+            scales = torch.ones(B, dtype=torch.float32, device=images.device)
+        with torch.no_grad():
+            s, l, b, count = ops.model_detections(self.model, images, int(images.shape[2]), int(images.shape[3]))
+            return finalize_device(s, l, b, count, scales, self.score_threshold, self.max_detections)
+
+    def update(self, images, scales=None):
+        """The streams' next frame -> ops.track_step's (rows [B, max_tracks, 8], ids [B, max_tracks] int32, count [B] int32), all on the
+        device.  scales: finalize's resize factors (None: 1, boxes in the input's pixels)."""
+        B = int(images.shape[0])
+        if self.state is not None and self.state.B != B:
+            raise ValueError('TrackedDetector: the tracker holds %d streams, this batch has %d' % (self.state.B, B))
+        if self.state is None:
+            self.state = ops.track_state(B, self.options.max_tracks, images.device)
+        dets, counts = self.detections_device(images, scales)
+        return ops.track_step(dets, counts, self.state, self.options)
+
+    def tracks(self, images, scales=None):
+        """update, read back -> per image (ids[K] int64, scores[K], labels[K] int64, boxes[K, 4])."""
+        rows, ids, count = self.update(images, scales)
+        counts = count.tolist()
+        if self._f16x3() and not torch.cuda.is_current_stream_capturing():
+            ops.check_range_flag(rows.device)
+        return [(ids[i, :n].to(torch.int64), rows[i, :n, 4], rows[i, :n, 5].to(torch.int64), rows[i, :n, :4]) for i, n in enumerate(counts)]
+
+    def reset(self, streams=None):
+        """Forget the tracks of every stream (None) or of the listed stream indices; ids start at 1 again there."""
+        if self.state is None:
+            return
+        if streams is None:
+            ops.track_reset(self.state)
+            return
+        mask = [0] * self.state.B
+        for b in streams:
+            if not 0 <= int(b) < self.state.B:
+                raise ValueError('TrackedDetector.reset: stream %r of %d' % (b, self.state.B))
+            mask[int(b)] = 1
+        ops.track_reset(self.state, mask)
 
 
 def all_detections_rows(dets, counts, num_classes):

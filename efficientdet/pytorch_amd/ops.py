@@ -2664,6 +2664,123 @@ def confusion_match(dets, counts, gt_boxes, gt_labels, num_classes, conf_thresho
                                                          L.stream_ptr()), 'effdet_confusion_match')
 
 
+TRACK_MAX_TRACKS, TRACK_MAX_DET, TRACK_ROW_WORDS = L.TRACK_MAX_TRACKS, L.TRACK_MAX_DET, L.TRACK_ROW_WORDS
+_TRACK = ('effdet_track_state_bytes', 'effdet_track_reset', 'effdet_track_step', 'effdet_track_overflow')
+
+
+class TrackOptions:
+    """ByteTrack's settings for track_step (include/effdet_track.h): detections scoring >= track_thr are high, those in (low_thr,
+    track_thr) low; the three associations allow a pair whose similarity is > match_sim (tracked + lost x high), > second_sim (the
+    tracked left x low, plain IoU) and > unconfirmed_sim (unconfirmed x the high left); a high detection left over starts a track when
+    its score is >= new_thr (None: track_thr + 0.1); a lost track is dropped after track_buffer frames without a match; fuse_score
+    multiplies the IoU by the detection's score; class_aware also wants equal labels; max_tracks slots per stream."""
+
+    def __init__(self, track_thr=0.5, low_thr=0.1, new_thr=None, match_sim=0.2, second_sim=0.5, unconfirmed_sim=0.3, track_buffer=30,
+                 fuse_score=True, class_aware=False, max_tracks=128):
+        new_thr = float(np.float32(np.float32(track_thr) + np.float32(0.1))) if new_thr is None else new_thr
+        for name, v in (('track_thr', track_thr), ('low_thr', low_thr), ('new_thr', new_thr)):
+            if not abs(float(v)) < float('inf'):
+                raise ValueError('TrackOptions: %s must be finite, got %r' % (name, v))
+        if float(low_thr) > float(track_thr):
+            raise ValueError('TrackOptions: low_thr must not exceed track_thr')
+        for name, v in (('match_sim', match_sim), ('second_sim', second_sim), ('unconfirmed_sim', unconfirmed_sim)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError('TrackOptions: %s must be in [0, 1], got %r' % (name, v))
+        if not 0 <= float(track_buffer) < 2 ** 31 or int(track_buffer) != track_buffer:       # (the range first: int() of inf or NaN raises)
+            raise ValueError('TrackOptions: track_buffer must be a whole number of frames >= 0')
+        if not 1 <= float(max_tracks) <= TRACK_MAX_TRACKS or int(max_tracks) != max_tracks:
+            raise ValueError('TrackOptions: max_tracks must be in 1..%d' % TRACK_MAX_TRACKS)
+        self.track_thr, self.low_thr, self.new_thr = float(track_thr), float(low_thr), float(new_thr)
+        self.match_sim, self.second_sim, self.unconfirmed_sim = float(match_sim), float(second_sim), float(unconfirmed_sim)
+        self.track_buffer, self.fuse_score, self.class_aware, self.max_tracks = int(track_buffer), bool(fuse_score), bool(class_aware), int(max_tracks)
+
+    def key(self):
+        return (self.track_thr, self.low_thr, self.new_thr, self.match_sim, self.second_sim, self.unconfirmed_sim, self.track_buffer,
+                self.fuse_score, self.class_aware, self.max_tracks)
+
+    def __eq__(self, other):
+        return isinstance(other, TrackOptions) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return ('TrackOptions(track_thr=%r, low_thr=%r, new_thr=%r, match_sim=%r, second_sim=%r, unconfirmed_sim=%r, track_buffer=%d, '
+                'fuse_score=%r, class_aware=%r, max_tracks=%d)' % self.key())
+
+
+class TrackState:
+    """The device state of B trackers of max_tracks slots (opaque bytes; include/effdet_track.h gives the layout)."""
+
+    def __init__(self, buf, B, max_tracks):
+        self.buf, self.B, self.max_tracks = buf, int(B), int(max_tracks)
+
+
+def track_state(B, max_tracks, device, buf=None):
+    """-> a TrackState of B streams, already reset.  buf: the caller's uint8 tensor of exactly the state's size (tests put guards
+    around it)."""
+    B, T = int(B), int(max_tracks)
+    if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS:
+        raise ValueError('track_state: B >= 1 and max_tracks in 1..%d, got %d, %d' % (TRACK_MAX_TRACKS, B, T))
+    n = int(L.require(*_TRACK).effdet_track_state_bytes(B, T))
+    if buf is None:
+        buf = torch.empty(n, dtype=torch.uint8, device=device)
+    assert buf.dtype == torch.uint8 and buf.is_contiguous() and buf.numel() == n and buf.data_ptr() % 4 == 0
+    state = TrackState(buf, B, T)
+    track_reset(state)
+    return state
+
+
+def track_reset(state, mask=None):
+    """Resets the streams whose entry of mask (a sequence or tensor of B flags) is set; every stream for None."""
+    if mask is not None:
+        mask = torch.as_tensor(mask, device=state.buf.device).reshape(-1).ne(0).to(torch.int32).contiguous()
+        if mask.numel() != state.B:
+            raise ValueError('track_reset: %d flags for %d streams' % (mask.numel(), state.B))
+    L.check(L.require(*_TRACK).effdet_track_reset(L.ptr(state.buf), state.B, state.max_tracks, L.ptr(mask), L.stream_ptr()), 'effdet_track_reset')
+
+
+def track_overflow(state):
+    """-> [B] int32 on the device: the new tracks each stream has dropped for lack of a free slot since its last reset."""
+    out = torch.empty(state.B, dtype=torch.int32, device=state.buf.device)
+    L.check(L.require(*_TRACK).effdet_track_overflow(L.ptr(state.buf), state.B, state.max_tracks, L.ptr(out), L.stream_ptr()), 'effdet_track_overflow')
+    return out
+
+
+def track_step(dets, counts, state, options=None, out=None):
+    """One frame of every stream (include/effdet_track.h): dets [B, max_det, 6] fp32 + counts [B] int32 as finalize_dets writes them ->
+    (rows [B, max_tracks, 8] fp32: x1, y1, x2, y2, score, label, tracklet_len, frames_since_start; ids [B, max_tracks] int32; count [B]
+    int32), the activated tracks of each stream in ascending id, rows past the count zero with id -1.  Everything stays on the device and
+    nothing is read back, so the call can be captured in a graph.  out: such a triple of the caller's (every element is overwritten)."""
+    o = TrackOptions() if options is None else options
+    if not isinstance(o, TrackOptions):
+        raise TypeError('track_step: options must be a TrackOptions, not %r' % (o,))
+    if not isinstance(state, TrackState):
+        raise TypeError('track_step: state must come from track_state, not %r' % (state,))
+    B, T = state.B, state.max_tracks
+    if o.max_tracks != T:
+        raise ValueError('track_step: the state has %d slots per stream, options.max_tracks is %d' % (T, o.max_tracks))
+    if dets.dim() != 3 or dets.shape[0] != B or dets.shape[2] != 6:
+        raise ValueError('track_step: dets must be [%d, max_det, 6], got %s' % (B, tuple(dets.shape)))
+    max_det = int(dets.shape[1])
+    if not 1 <= max_det <= TRACK_MAX_DET:
+        raise ValueError('track_step: 1..%d detection rows per stream, got %d' % (TRACK_MAX_DET, max_det))
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.device == state.buf.device
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == B and counts.device == dets.device
+    if out is None:
+        out = (torch.empty((B, T, 8), dtype=torch.float32, device=dets.device), torch.empty((B, T), dtype=torch.int32, device=dets.device),
+               torch.empty(B, dtype=torch.int32, device=dets.device))
+    rows, ids, count = out
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and tuple(rows.shape) == (B, T, 8)
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape) == (B, T)
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == B
+    L.check(L.require(*_TRACK).effdet_track_step(L.ptr(dets), L.ptr(counts), B, max_det, L.ptr(state.buf), T, o.track_thr, o.low_thr, o.new_thr,
+                                                 o.match_sim, o.second_sim, o.unconfirmed_sim, o.track_buffer, int(o.fuse_score),
+                                                 int(o.class_aware), L.ptr(rows), L.ptr(ids), L.ptr(count), L.stream_ptr()),
+            'effdet_track_step')
+    return rows, ids, count
+
+
 COCO_MAX_GT = 2048                 # GT rows per image effdet_coco_match stages in LDS
 COCO_MAX_CATEGORIES = 1024
 _COCO = ('effdet_coco_slots', 'effdet_coco_match', 'effdet_coco_accumulate', 'effdet_coco_accumulate_workspace_bytes')
