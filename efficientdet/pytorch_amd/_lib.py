@@ -26,6 +26,7 @@ ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = 0, 1, 2, 3
 RES_NONE, RES_ADD, RES_RELU_MASK, RES_SWISH_GRAD = 0, 1, 2, 3
 TUNE_IGEMM_BIG, TUNE_IGEMM_BIG_MIN_M, TUNE_SPLIT_PERS, TUNE_IGEMM_KORD, TUNE_SPLIT_KORD = 0, 1, 2, 3, 4
 TUNE_ROWSLAB = 5                   # row-slab activation staging of the split-layout 3x3 convs: 1 (default) on, 0 per-tap staging
+TUNE_SHORT_TILE = 7                # 32-pixel workgroup tiles for the small-map exact-fp32 / bf16x3 convs: 1 (default) on, 0 the 128-pixel plans (index 6 is no key: EFFDET_EINVAL)
 
 _ERR = {-1: 'EFFDET_EINVAL', -2: 'EFFDET_ELAUNCH', -3: 'EFFDET_EUNSUPPORTED'}
 

@@ -82,17 +82,27 @@ struct ConvK {
   SegD seg[EFFDET_MAX_CONV_SEG];
 };
 
-constexpr int BM = 128;
+constexpr int BM128 = 128;      // the full pixel tile: every form but the short-tile instances (the kernel's BM parameter)
 
 // Row-slab staging (3x3, stride 1, pad 1, channel-group-major walk): a 128-pixel tile of a segment whose width is a power of two
 // in 8 .. 64 is 128 / W whole image rows, and the three taps of one kernel row read the same rows.  slab_entries: 128-byte entries
 // of its slab (132 / 136 / 144 / 160 for W = 64 / 32 / 16 / 8).  The 64-channel tile keeps W = 8 on the per-tap form: with slabs of at
 // most 144 entries its workgroup stays at 52 KiB of LDS, three to a CU as before (160 entries: 56 KiB, two).
-__host__ __device__ inline int slab_entries(int W) { return (BM / W) * (W + 2); }
+__host__ __device__ inline int slab_entries(int W) { return (BM128 / W) * (W + 2); }
 __host__ __device__ inline bool slab_seg_ok(const SegD& s, int bn) {
   return (s.W & (s.W - 1)) == 0 && s.W >= (bn > 64 ? 8 : 16) && s.W <= 64 && s.Ho == s.H && s.Wo == s.W;
 }
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// s_waitcnt vmcnt(min(ahead, A) * PPS): the counter is an immediate, so one compare per depth (ahead is wave-uniform)
+template <int PPS, int A>
+__device__ __forceinline__ void wait_ahead(int ahead) {
+  if constexpr (A == 0) { (void)ahead; dma_wait_all(); }
+  else {
+    if (ahead >= A) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A * PPS) : "memory");
+    else wait_ahead<PPS, A - 1>(ahead);
+  }
+}
 
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
@@ -150,7 +160,20 @@ template <> struct Mma<float> {
 // between the fragment's ds_read and its MFMAs, as x * a_gate[image][channel] (GATE = 1) or swish(x) * a_gate[image][channel] (GATE = 2) --
 // the two statements of se.hip's channel_scale_kernel, so every MFMA receives bit for bit the operand it would read from that kernel's
 // output, in the same order.  The image's gate row sits in LDS behind the operand tiles (zeros past Cin: the K padding stays +0).
-template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0, int GATE = 0>
+// BM: block tile height in pixels.  128 everywhere but in the SHORT-TILE instances (exact fp32 and register-split bf16x3, BN = 32, a 2 x 2
+// wave layout of 16 x 16 wave tiles: BM = 32, one accumulator per wave, NS = 8).  The launches of the deep window whose narrow plan
+// still leaves most CUs without a workgroup -- a BiFPN 3x3 conv on the 8x8 level is 32 workgroups of 128 x 32 -- are bound by the MFMA
+// chain of the few CUs they occupy (four accumulators per wave: 32 v_mfma_f32_16x16x4_f32 per wave and K-step, ~0.43 us) times the
+// K-steps.  A 32-pixel tile is four times the workgroups at a quarter of the chain, and 8 KiB of LDS per stage instead of 20: eight
+// stages (seven K-steps in flight) are 64 KiB, two workgroups per CU.  The price is operand traffic out of L2 (a 32 x 32 tile stages
+// 8 KiB per 32 x 32 x 32 MACs: 1.6x the bytes per MAC of the 128 x 32 tile) -- the 36-K-step project convs move ~110 MB per launch and
+// run at L2 rate, which is why the window stops where the narrow plan fills the CUs.  Measured alternatives (same shapes, temporary
+// builds, profiles/short_tile_variants_probe.txt): the whole K loop resident (NS = 18, 144 KiB, one workgroup per CU) 12.2 us where
+// NS = 8 gives 11.2; NS = 10 the same as 8; 64-pixel tiles (NS = 6 / 12) 14.5-15.5 us on the BiFPN convs and 22-23 us where BM = 32
+// gives 21.  The tile shape does not enter the arithmetic: every output element is one accumulator walked over k by the same
+// Mma<>::run sequence in the same K order through the same epilogue -- bit for bit the 128-pixel tile's values (use_tile picks;
+// tuning knob EFFDET_TUNE_SHORT_TILE).
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0, int GATE = 0, int BM = BM128>
 // (second launch bound = waves per SIMD asked of the register allocator: the 4-wave split-layout forms fit three workgroups per CU by LDS, but
 //  left to itself hipcc spends 110 VGPRs + 72 AGPRs on the f16x3 one -- two waves per SIMD)
 __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) void conv_igemm_kernel(const ConvK p) {
@@ -159,6 +182,8 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   static_assert(SPLIT != 3 || NS == 2, "f16x3: two stages");
   static_assert(NS == 2 || !M32, "deep staging is not built for the 32x32 tile loop");
   static_assert(!GATE || (SPLIT == 0 && sizeof(T) == 4), "the operand gate is built for the exact-fp32 form");
+  static_assert(BM == BM128 || (sizeof(T) == 4 && SPLIT <= 1 && !M32 && !GATE && NS > 2), "short pixel tiles: exact fp32 / register-split bf16x3, deep staging");
+  static_assert(BM % (NWAVES * 8) == 0 && BM % (16 * (NWAVES / WAVES_N)) == 0, "whole DMA passes and whole 16-row MFMA tiles per wave");
   constexpr int CE = Elem<T>::CE;
   constexpr int NTHREADS = NWAVES * 64;
   constexpr int WAVES_M = NWAVES / WAVES_N;
@@ -460,13 +485,10 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
       for (int b = 0; b < MT; ++b) Mma<T>::run(wf[a], xf[b], acc[a][b]);
   };
   constexpr int PPS = XROWS + WROWS;       // DMA instructions per wave and stage (uniform: NS > 2 is only built for BN >= RSTEP)
+  static_assert(NS == 2 || (BN >= RSTEP && (NS - 2) * PPS <= 63), "deep staging: the same pieces in every wave, a count s_waitcnt vmcnt can hold");
   auto wait_tile = [&](int ahead) {        // `ahead` tiles were issued after the one needed: only their pieces may be in flight
     if constexpr (NS == 2) { (void)ahead; dma_wait_all(); }
-    else {
-      if (NS >= 4 && ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PPS) : "memory");
-      else if (ahead >= 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PPS) : "memory");
-      else dma_wait_all();
-    }
+    else wait_ahead<PPS, NS - 2>(ahead);   // (at most NS - 2 tiles are ever issued behind tile kt + 1: vmcnt = ahead * PPS, wave-uniform)
   };
   constexpr int NT32 = M32 ? WTN / 32 : 1, MT32 = M32 ? WTM / 32 : 1;
   f32x16 acc32[NT32][MT32];
@@ -1512,22 +1534,26 @@ struct ConvPlan {
 };
 
 // Tuning knobs (effdet_tuning_set; A/B experiments and tests).  Speed only: every setting computes the same values.
-static int g_tuning[EFFDET_TUNE_COUNT] = {-1, 16384, -1, 1, -1, -1};
+static int g_tuning[EFFDET_TUNE_COUNT] = {-1, 16384, -1, 1, -1, -1, 0 /* index 6: not a key */, 1};
 // EFFDET_TUNE_ROWSLAB / env EFFDET_ROWSLAB: row-slab activation staging of the split-layout 3x3 convs (1, the default) or per-tap staging (0)
 static bool rowslab_on() {
   if (g_tuning[EFFDET_TUNE_ROWSLAB] < 0) g_tuning[EFFDET_TUNE_ROWSLAB] = getenv("EFFDET_ROWSLAB") ? atoi(getenv("EFFDET_ROWSLAB")) : 1;
   return g_tuning[EFFDET_TUNE_ROWSLAB] != 0;
 }
 
-template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT, int NS, int M32, int GATE>
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT, int NS, int M32, int GATE, int BM>
 int launch_igemm(const ConvPlan& c, hipStream_t st) {
-  if (c.lds > 48 * 1024) EFFDET_SET_MAX_LDS((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>), c.lds);
-  hipLaunchKernelGGL((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>), dim3(c.grid), dim3(NWAVES * 64), c.lds, st, c.k);
+  if (c.lds > 48 * 1024) EFFDET_SET_MAX_LDS((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE, BM>), c.lds);
+  hipLaunchKernelGGL((conv_igemm_kernel<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE, BM>), dim3(c.grid), dim3(NWAVES * 64), c.lds, st, c.k);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
-template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0, int GATE = 0>
+template <typename T, int BN, int WAVES_N, int NWAVES, int SPLIT = 0, int NS = 2, int M32 = 0, int GATE = 0, int BM = BM128>
 int use_igemm(ConvPlan& c, int id) {
+  if constexpr (BM != BM128) {      // plan_conv counted 128-pixel tiles: every segment's tile_start in units of BM-row tiles
+    c.k.mtiles = 0;
+    for (int s = 0; s < c.k.nseg; ++s) { c.k.seg[s].tile_start = c.k.mtiles; c.k.mtiles += (c.k.seg[s].M + BM - 1) / BM; }
+  }
   c.k.ntiles = (c.k.Cout + BN - 1) / BN;
   c.grid = (unsigned)(c.k.mtiles * c.k.ntiles);
   c.k.slab = 0; c.k.xld = BM * 8;
@@ -1539,13 +1565,13 @@ int use_igemm(ConvPlan& c, int id) {
       int ent = 0;
       for (int s = 0; s < k.nseg; ++s)
         if (slab_seg_ok(k.seg[s], BN) && ((slab_entries(k.seg[s].W) + 7) & ~7) > ent) ent = (slab_entries(k.seg[s].W) + 7) & ~7;
-      if (ent) { c.k.slab = 1; c.k.xld = (ent > BM ? ent : BM) * 8; }
+      if (ent) { c.k.slab = 1; c.k.xld = (ent > BM128 ? ent : BM128) * 8; }
     }
   }
   c.lds = (size_t)NS * (c.k.xld + BN * 8) * sizeof(uint4);               // NS-stage operand tiles
   if (GATE) c.lds += (size_t)((c.k.Kc + 7) >> 3) * 32 * sizeof(float);   // + the image's gate row, one float per K slot
   c.gate = GATE;
-  c.launch = launch_igemm<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE>;
+  c.launch = launch_igemm<T, BN, WAVES_N, NWAVES, SPLIT, NS, M32, GATE, BM>;
   static_assert(EFFDET_CONV_FORM_PLAIN == 0 && EFFDET_CONV_FORM_BF16X3 == 1 && EFFDET_CONV_FORM_SPLIT == 2 && EFFDET_CONV_FORM_HSPLIT == 3,
                 "the kernel's SPLIT parameter is the public form code");
   c.form = SPLIT; c.pers = 0; c.tile_m = BM; c.tile_n = BN; c.stages = NS; c.threads = NWAVES * 64; c.m32 = M32;
@@ -1617,7 +1643,7 @@ static int big_variant() {
   return g_tuning[EFFDET_TUNE_IGEMM_BIG];
 }
 
-// Block tile (bt = 0..3: 128 / 64 / 32 / 16 channels) and staging depth of the 128-pixel-tile kernel: ids 0..3, 4..7 with SPLIT = 1
+// Block tile (bt = 0..3: 128 / 64 / 32 / 16 channels), staging depth and pixel tile (128, or the short 32) of the tile kernel: ids 0..3, 4..7 with SPLIT = 1
 template <typename T, int SPLIT, int GATE = 0>
 int use_tile(ConvPlan& c, int bt) {
   const ConvK& k = c.k;
@@ -1635,7 +1661,20 @@ int use_tile(ConvPlan& c, int bt) {
     // 1.78 to 1.05 ms per forward (49.8 -> 84.9 TFLOP/s, 12 launches); configs[4] forward 4.758 -> 4.627 ms/img, D0 train / inference +-0
     static const int narrow = getenv("EFFDET_IGEMM_NARROW") ? atoi(getenv("EFFDET_IGEMM_NARROW")) : 128;
     static const int narrow_k = getenv("EFFDET_IGEMM_NARROW_K") ? atoi(getenv("EFFDET_IGEMM_NARROW_K")) : 16;
-    if (narrow && bt <= 1 && tiles <= narrow && k.Kc >= narrow_k * 8) return use_igemm<T, 32, 1, 4, SPLIT, 4, 0, GATE>(c, id);
+    if (narrow && bt <= 1 && tiles <= narrow && k.Kc >= narrow_k * 8) {
+      // short pixel tile (see the kernel's BM note; tuning knob EFFDET_TUNE_SHORT_TILE, read per call): where even the narrow plan
+      // gives at most SHORT_MAX_WG of the 256 CUs a workgroup -- or up to 128 of them when the launch is at most two channel tiles wide
+      // (Cout <= 64: the BiFPN convs on the 16x16 level) -- 32-pixel tiles on eight stages: four times the workgroups, a quarter of the
+      // MFMA chain per K-step, 64 KiB of LDS (two workgroups per CU).  Measured class by class (profiles/short_tile_launch_timing.json):
+      // 21 -> 11-14 us on the BiFPN convs, 32 -> 16-21 us on the 36-K-step project convs; every class inside the window wins
+      if constexpr (sizeof(T) == 4 && SPLIT <= 1 && !GATE) {
+        constexpr int SHORT_MAX_WG = 96, SHORT_MAX_WG_2N = 128;
+        const int nwg = k.mtiles * ((k.Cout + 31) / 32);
+        if (g_tuning[EFFDET_TUNE_SHORT_TILE] != 0 && !k.w_img_bytes && (nwg <= SHORT_MAX_WG || (k.Cout <= 64 && nwg <= SHORT_MAX_WG_2N)))
+          return use_igemm<T, 32, 2, 4, SPLIT, 8, 0, 0, 32>(c, id);
+      }
+      return use_igemm<T, 32, 1, 4, SPLIT, 4, 0, GATE>(c, id);
+    }
     if (bt == 0) return use_igemm<T, 128, 2, 8, SPLIT, 4, 0, GATE>(c, id);
     if (bt == 1) return use_igemm<T, 64, 1, 4, SPLIT, 4, 0, GATE>(c, id);
   }
@@ -1650,7 +1689,7 @@ int use_tile(ConvPlan& c, int bt) {
 }  // namespace
 
 extern "C" int effdet_tuning_set(int key, int value) {
-  if (key < 0 || key >= EFFDET_TUNE_COUNT) return EFFDET_EINVAL;
+  if (key < 0 || key >= EFFDET_TUNE_COUNT || key == EFFDET_TUNE_ROWSLAB + 1) return EFFDET_EINVAL;      // (the index after the row-slab knob is unassigned)
   (void)big_variant();
   const int old = g_tuning[key];
   g_tuning[key] = value;
@@ -1714,17 +1753,17 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c, const float* a_gate = 
   k.needed = nullptr; k.needed_tile0 = 0;
   k.uflags32 = nullptr; k.units = nullptr; k.ucounts = nullptr; k.g_in_off = 0; k.g_x_bytes = 0;
   k.a_gate = a_gate;
-  k.slab = 0; k.xld = BM * 8;
+  k.slab = 0; k.xld = BM128 * 8;
   if (a_gate) {
     // operand gate: exact fp32, pointwise (the K index is the channel), one level whose images are whole numbers of 128-pixel tiles
     // (the image, hence the gate row, is workgroup-uniform), shared weights, the 128-pixel-tile kernels only
     if (a_act != EFFDET_ACT_NONE && a_act != EFFDET_ACT_SWISH) return EFFDET_EINVAL;
     if (p->dtype != EFFDET_F32 || p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad_t || p->pad_l || p->nseg != 1 || p->w_image_stride ||
-        p->seg[0].H != p->seg[0].Ho || p->seg[0].W != p->seg[0].Wo || (p->seg[0].Ho * p->seg[0].Wo) % BM || ((size_t)a_gate & 3)) return EFFDET_EUNSUPPORTED;
+        p->seg[0].H != p->seg[0].Ho || p->seg[0].W != p->seg[0].Wo || (p->seg[0].Ho * p->seg[0].Wo) % BM128 || ((size_t)a_gate & 3)) return EFFDET_EUNSUPPORTED;
   }
   if (p->w_image_stride) {
     // per-image weights: one level whose images are whole numbers of 128-pixel tiles, on the implicit-GEMM kernels only
-    if (p->w_image_stride < 0 || (p->w_image_stride & 15) || p->nseg != 1 || splitfmt || (p->seg[0].Ho * p->seg[0].Wo) % BM) return EFFDET_EUNSUPPORTED;
+    if (p->w_image_stride < 0 || (p->w_image_stride & 15) || p->nseg != 1 || splitfmt || (p->seg[0].Ho * p->seg[0].Wo) % BM128) return EFFDET_EUNSUPPORTED;
   }
   int tiles = 0;
   bool per_seg = false;        // some segment brings its own weights / bias (effdet_conv_t.seg_w / seg_shift)
@@ -1743,7 +1782,7 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c, const float* a_gate = 
     if (d.M <= 0) return EFFDET_EINVAL;
     if (g.in_off % ce || g.in_bstride % ce) return EFFDET_EUNSUPPORTED;
     if (g.out_off % 4 || g.out_bstride % 4) vec = false;
-    tiles += (d.M + BM - 1) / BM;
+    tiles += (d.M + BM128 - 1) / BM128;
   }
   for (int s = p->nseg; s < EFFDET_MAX_CONV_SEG; ++s) { k.seg[s] = k.seg[0]; k.seg[s].tile_start = 0x7fffffff; }
   k.mtiles = tiles; k.vec_ok = vec ? 1 : 0;

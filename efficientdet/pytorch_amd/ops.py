@@ -176,6 +176,11 @@ def _igemm_symbol(dtype, desc):
         return 'conv_igemm_pers_kernel<%s,%s,%s>' % (v[0], v[1], v[2])
     if kid in (8, 9):
         return 'conv_igemm_kernel<split,%d,bf16x3>' % (128, 64)[kid - 8]
+    if 0 <= kid < 8 and dtype == torch.float32:
+        # ids 0..7 name a channel-tile class; the short-tile instances (TUNE_SHORT_TILE) are told apart by the plan's pixel tile
+        info = L.ConvPlanInfo()
+        if int(L.require('effdet_conv2d_plan_info').effdet_conv2d_plan_info(C.byref(desc), C.byref(info))) == kid and info.tile_m < 128:
+            return 'conv_igemm_kernel<f32,%d%s,short%d>' % (info.tile_n, ',bf16x3' if kid >= 4 else '', info.tile_m)
     if 4 <= kid < 8:
         return 'conv_igemm_kernel<f32,%d,bf16x3>' % (128, 64, 32, 16)[kid - 4]
     return 'conv_igemm_kernel<%s,%d>' % ('bf16' if dtype == torch.bfloat16 else 'f32', (128, 64, 32, 16)[max(kid, 0)])

@@ -143,7 +143,9 @@ enum { EFFDET_TUNE_IGEMM_BIG = 0, EFFDET_TUNE_IGEMM_BIG_MIN_M = 1,
        EFFDET_TUNE_IGEMM_KORD = 3 /* K walk of the persistent variants: 0 tap-major, 1 channel-group-major */,
        EFFDET_TUNE_SPLIT_KORD = 4 /* K walk of the EFFDET_F32_SPLIT convs: 0 tap-major, 1 channel-group-major */,
        EFFDET_TUNE_ROWSLAB = 5 /* EFFDET_F32_SPLIT / EFFDET_F32_HSPLIT 3x3 convs on the channel-group-major walk: 1 (default) one activation row slab per kernel row, 0 one tile per tap */,
-       EFFDET_TUNE_COUNT = 6 };
+       /* index 6 is not a key: effdet_tuning_set answers EFFDET_EINVAL for it, as it always has for the index after EFFDET_TUNE_ROWSLAB */
+       EFFDET_TUNE_SHORT_TILE = 7 /* exact-fp32 / EFFDET_F32_BF16X3 convs of the four-stage window whose narrow plan leaves most compute units idle: 1 (default) 32-pixel workgroup tiles, 0 the 128-pixel plans */,
+       EFFDET_TUNE_COUNT = 8 };
 int effdet_tuning_set(int key, int value);
 
 /* Weight gradient of the same convolution:  dw[n][tap][c] += sum_m dz[m][n] * x[pix(m)+tap][c]
