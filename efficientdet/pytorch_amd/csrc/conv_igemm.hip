@@ -68,11 +68,11 @@ struct ConvK {
   unsigned w_bytes;            // extent of the packed weights for the bounds-checked buffer loads
   int kord;                    // K walk of the persistent kernel: 0 tap-major, 1 channel-group-major
   long long w_img_bytes;       // != 0: image b reads its own packed weights at w + b * w_img_bytes (one segment, Ho*Wo % BM == 0)
-  const unsigned char* live;   // SPLIT == 2 only, may be NULL: live[mt - live_tile0] == 0 = every input tap of pixel tile mt is zero (effdet_conv2d_live)
-  int live_tile0;              // pixel tiles below it carry no flag and are live
-  const unsigned char* needed; // SPLIT == 3 only, may be NULL: needed[mt - needed_tile0] == 0 = nobody reads pixel tile mt's result (effdet_conv2d_needed)
-  int needed_tile0;            // pixel tiles below it carry no flag and are computed
-  // gathered form of a flagged launch (include/effdet_unit_lists.h; SPLIT >= 2, with live / needed set): the flagged segments' 32-pixel
+  // SPLIT >= 2 only, may be NULL: tflags[mt - tflag0] == 0 = pixel tile mt is skipped.  What a flag states follows from the instance:
+  // SPLIT == 2 input liveness (0 = every input tap of the tile is zero, effdet_conv2d_live), SPLIT == 3 output need (0 = nobody reads
+  // the tile's result, effdet_conv2d_needed).  Pixel tiles below tflag0 carry no flag and are computed.
+  const unsigned char* tflags; int tflag0;
+  // gathered form of a flagged launch (include/effdet_unit_lists.h; SPLIT >= 2, with tflags set): the flagged segments' 32-pixel
   // step flags, the list of the set ones and { n, set tile flags, gather, 0 }, all of the launch's radius; NULL = tile flags only
   const unsigned char* uflags32; const int* units; const int* ucounts;
   long long g_in_off; unsigned g_x_bytes;      // ONE window over the flagged segments' inputs: a gathered tile's rows come from several
@@ -212,22 +212,13 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   const int wm0 = (wave / WAVES_N) * WTM, wn0 = (wave % WAVES_N) * WTN;
 
   int tile = xcd_remap(blockIdx.x, gridDim.x);
-  if constexpr (SPLIT == 2) {
+  if constexpr (SPLIT >= 2) {
     // Flagged launch: the live tiles cluster (the coarse levels at the end of the tile range are mostly live, whole images of the fine
     // ones dead), and the remap above hands each XCD one contiguous eighth of the range -- one XCD would get most of the work.  Deal
     // the pixel tiles out round-robin instead (pixel tile 8 j + x to XCD x, its channel tiles back to back on it, so the activation
-    // tile is still fetched into one L2); the blocks past the last whole group of eight keep their own index.  Speed only.
-    if (p.live) {
-      const int b = blockIdx.x, whole = (p.mtiles >> 3) << 3;
-      if (b < whole * p.ntiles) {
-        const int i = b >> 3, j = i / p.ntiles;
-        tile = (j * 8 + (b & 7)) * p.ntiles + (i - j * p.ntiles);
-      } else tile = b;
-    }
-  }
-  if constexpr (SPLIT == 3) {
-    // "needed" flags (effdet_conv2d_needed): the needed tiles cluster the same way, so the same round-robin deal.  Speed only.
-    if (p.needed) {
+    // tile is still fetched into one L2); the blocks past the last whole group of eight keep their own index.  The needed tiles
+    // (effdet_conv2d_needed) cluster the same way, so both kinds of flag take the same deal.  Speed only.
+    if (p.tflags) {
       const int b = blockIdx.x, whole = (p.mtiles >> 3) << 3;
       if (b < whole * p.ntiles) {
         const int i = b >> 3, j = i / p.ntiles;
@@ -269,7 +260,7 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
 
   // Gathered form of a flagged launch (include/effdet_unit_lists.h; workgroup-uniform, ahead of every barrier and DMA).  The flagged
   // segments' set 32-pixel units are listed in p.units; workgroup row mt (a) writes the zero rows of ITS OWN tile's clear units -- the
-  // stores of the dead-tile branches below, unit by unit -- and (b) if it is one of the first ceil(n / 4) flagged rows, computes the
+  // stores of the flagged-off-tile branch below, unit by unit -- and (b) if it is one of the first ceil(n / 4) flagged rows, computes the
   // tile whose four 32-row groups are units 4 j .. 4 j + 3 of the list, j = mt - (first flagged tile); a short tail has fewer.  Rows of
   // set units are written by (b) of some row, rows of clear ones by (a) of their own: every row once.  A gathered tile stages its activations PER TAP on every level (a unit plus its halo is one contiguous run on
   // the 64 and 32 pixel wide levels only; per-unit slabs are not built): a wave's 8-row DMA piece lies in one unit, so what the tile
@@ -280,7 +271,7 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
   // group q of the gathered tile -> its segment (-1: none, the short tail) and first pixel there.  (Asked again by the epilogue: nothing
   // of it stays in registers through the K loop, which runs at the register budget of the dense tiles.)
   auto unit_of = [&](int q, int& m0) -> int {
-    const int ft0 = SPLIT == 2 ? p.live_tile0 : p.needed_tile0;
+    const int ft0 = p.tflag0;
     const int i = (mt - ft0) * 4 + q;
     int sq = -1;
     m0 = 0;
@@ -298,15 +289,14 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
     return sq;
   };
   if constexpr (GCAP) {
-    const unsigned char* const fl = SPLIT == 2 ? p.live : p.needed;
-    const int ft0 = SPLIT == 2 ? p.live_tile0 : p.needed_tile0;
-    if (fl && p.units && mt >= ft0 && p.ucounts[2] != 0) {
+    const int ft0 = p.tflag0;
+    if (p.tflags && p.units && mt >= ft0 && p.ucounts[2] != 0) {
       gath = true;
       int s0 = (mt - sg.tile_start) * 4;               // this tile's first step among the flagged segments' steps
 #pragma unroll 1
       for (int s = 0; s < si; ++s)
         if (p.seg[s].tile_start >= ft0) s0 += (p.seg[s].M + 31) >> 5;
-      if (!(SPLIT == 2 && p.res_mode == EFFDET_RES_ADD)) {
+      if (p.res_mode != EFFDET_RES_ADD) {
 #pragma unroll 1
         for (int q = 0; q < 4; ++q)
           if (m_base + 32 * q < sg.M && p.uflags32[s0 + q] == 0) zero_rows(32 * q, min(32 * q + 32, sg.M - m_base));
@@ -315,21 +305,15 @@ __global__ __launch_bounds__(NWAVES * 64, (SPLIT == 3 && NWAVES == 4) ? 3 : 1) v
     }
   }
 
-  if constexpr (SPLIT == 2) {
-    // Dead tile (workgroup-uniform, ahead of every barrier and DMA): all its input taps are exact zeros and the launch has no bias /
-    // affine / activation (the host passes flags only then), so the dense loop would produce +0 everywhere -- zeros after a ReLU mask
-    // too, and the unchanged value under an in-place RES_ADD.  Write the tile's rows as zero bytes and leave.
-    if (p.live && !gath && mt >= p.live_tile0 && p.live[mt - p.live_tile0] == 0) {
+  if constexpr (SPLIT >= 2) {
+    // Flagged-off tile (workgroup-uniform, ahead of every barrier and DMA): write its rows as zero bytes and leave.
+    // SPLIT == 2, a dead tile: all its input taps are exact zeros and the launch has no bias / affine / activation (the host passes flags
+    // only then), so the dense loop would produce +0 everywhere -- zeros after a ReLU mask too, and the unchanged value under an in-place
+    // RES_ADD, which therefore writes nothing.
+    // SPLIT == 3, a tile nobody needs: not computed.  Its rows of every output stream are written as zero bytes so that what later
+    // multiplies them by an exact zero never meets recycled memory (plan_conv refuses every residual mode for this form: always written).
+    if (p.tflags && !gath && mt >= p.tflag0 && p.tflags[mt - p.tflag0] == 0) {
       if (p.res_mode != EFFDET_RES_ADD) zero_rows(0, min(BM, sg.M - m_base));
-      return;
-    }
-  }
-
-  if constexpr (SPLIT == 3) {
-    // A tile nobody needs (workgroup-uniform, ahead of every barrier and DMA): not computed.  Its rows of every output stream are
-    // written as zero bytes so that what later multiplies them by an exact zero never meets recycled memory.
-    if (p.needed && !gath && mt >= p.needed_tile0 && p.needed[mt - p.needed_tile0] == 0) {
-      zero_rows(0, min(BM, sg.M - m_base));
       return;
     }
   }
@@ -1749,8 +1733,7 @@ static int plan_conv(const effdet_conv_t* p, ConvPlan& c, const float* a_gate = 
   }
   k.nseg = p->nseg;
   k.w_img_bytes = p->w_image_stride;
-  k.live = nullptr; k.live_tile0 = 0;
-  k.needed = nullptr; k.needed_tile0 = 0;
+  k.tflags = nullptr; k.tflag0 = 0;
   k.uflags32 = nullptr; k.units = nullptr; k.ucounts = nullptr; k.g_in_off = 0; k.g_x_bytes = 0;
   k.a_gate = a_gate;
   k.slab = 0; k.xld = BM128 * 8;
@@ -1883,20 +1866,6 @@ extern "C" int effdet_conv2d_gated_plan_info(const effdet_conv_t* p, const float
   if (!a_gate) return EFFDET_EINVAL;
   return plan_info(p, a_gate, a_act, info);
 }
-extern "C" int effdet_conv2d_gated(const effdet_conv_t* p, const float* a_gate, int a_act, effdet_stream_t stream) {
-  if (!a_gate) return EFFDET_EINVAL;
-  ConvPlan c;
-  const int id = plan_conv(p, c, a_gate, a_act);
-  if (id < 0) return id;
-  if (!c.gate) return EFFDET_EUNSUPPORTED;
-  return c.launch(c, (hipStream_t)stream);
-}
-
-extern "C" int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream) {
-  ConvPlan c;
-  const int id = plan_conv(p, c);
-  return id < 0 ? id : c.launch(c, (hipStream_t)stream);
-}
 
 // effdet_conv2d with per-tile liveness flags (include/effdet_live_tiles.h).  The flags are per call, like x and y, and only a hint: they
 // reach the kernel where a dead tile's dense result is known to be zero bytes (or, adding in place, no change) -- the split-layout
@@ -1909,37 +1878,21 @@ static bool live_flags_ok(const effdet_conv_t* p, int id) {
                                  : (p->res_mode == EFFDET_RES_NONE || p->res_mode == EFFDET_RES_RELU_MASK);
   return (id == 8 || id == 9) && plain && no_shift && res_ok;
 }
-extern "C" int effdet_conv2d_live(const effdet_conv_t* p, const unsigned char* live, int live_tile0, effdet_stream_t stream) {
-  ConvPlan c;
-  const int id = plan_conv(p, c);
-  if (id < 0) return id;
-  if (live_tile0 < 0) return EFFDET_EINVAL;
-  if (live && live_flags_ok(p, id)) { c.k.live = live; c.k.live_tile0 = live_tile0; }
-  return c.launch(c, (hipStream_t)stream);
-}
 
 // effdet_conv2d with "needed" flags (include/effdet_needed_tiles.h): per call, like the liveness flags above, but a statement about the
 // READERS of the output, not about the input -- so bias, activation and the second output stream do not matter, a tile that is not
 // needed is zero bytes in all of them.  They reach the f16x3 128-pixel-tile kernels (the forward RetinaHead) and are dropped elsewhere.
 static bool needed_flags_ok(const effdet_conv_t* p, const ConvPlan& c, int id) {
+  // (vec_ok off: only fp32 rows may leave the 16-byte grid; the split streams never do -- plan_conv has checked their offsets and pitch)
   return (id == 30 || id == 31) && (c.k.vec_ok || (p->out_f32 && !p->y_split));
 }
-extern "C" int effdet_conv2d_needed(const effdet_conv_t* p, const unsigned char* needed, int needed_tile0, effdet_stream_t stream) {
-  ConvPlan c;
-  const int id = plan_conv(p, c);
-  if (id < 0) return id;
-  if (needed_tile0 < 0) return EFFDET_EINVAL;
-  // (vec_ok off: only fp32 rows may leave the 16-byte grid; the split streams never do -- plan_conv has checked their offsets and pitch)
-  if (needed && needed_flags_ok(p, c, id)) { c.k.needed = needed; c.k.needed_tile0 = needed_tile0; }
-  return c.launch(c, (hipStream_t)stream);
-}
 
-// The gathered form of a flagged launch (include/effdet_unit_lists.h), on a plan whose tile flags (k.live / k.needed) are already set:
+// The gathered form of a flagged launch (include/effdet_unit_lists.h), on a plan whose tile flags (k.tflags) are already set:
 // taken where the kernel's gathered path holds -- a 3x3, stride 1, pad 1 conv, tile0 the first tile of a segment, the flagged segments
 // sharing weights and bias, their inputs inside one 32-bit window -- and left at the tile flags everywhere else.
 static void take_units(const effdet_conv_t* p, ConvPlan& c, int tile0, const unsigned char* flags32, const int* units, const int* counts) {
   ConvK& k = c.k;
-  if (!flags32 || !units || !counts || (!k.live && !k.needed)) return;
+  if (!flags32 || !units || !counts || !k.tflags) return;
   if (p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad_t != 1 || p->pad_l != 1 || p->w_image_stride) return;
   int first = -1;
   long long lo = 0, hi = 0;
@@ -1959,26 +1912,48 @@ static void take_units(const effdet_conv_t* p, ConvPlan& c, int tile0, const uns
   k.uflags32 = flags32; k.units = units; k.ucounts = counts; k.g_in_off = lo / 4; k.g_x_bytes = (unsigned)(hi - lo);
 }
 
-extern "C" int effdet_conv2d_live_units(const effdet_conv_t* p, const unsigned char* flags128, const unsigned char* flags32, const int* units,
-                                        const int* counts, int tile0, effdet_stream_t stream) {
+// What varies between the forward entry points below; conv_launch is the one path from a descriptor to a launch.
+enum { FLAGS_NONE = 0, FLAGS_LIVE, FLAGS_NEEDED };
+struct ConvCall {
+  const float* a_gate = nullptr; int a_act = EFFDET_ACT_NONE;      // operand gate (effdet_conv2d_gated)
+  int kind = FLAGS_NONE;                                           // what tflags state: picks live_flags_ok / needed_flags_ok
+  const unsigned char* tflags = nullptr; int tflag0 = 0;           // per 128-pixel tile, from tile tflag0 on
+  bool gathered = false;                                           // the unit-list form: every pointer required, no dense launch instead
+  const unsigned char* flags32 = nullptr; const int* units = nullptr; const int* counts = nullptr;
+};
+static int conv_launch(const effdet_conv_t* p, const ConvCall& a, hipStream_t st) {
   ConvPlan c;
-  const int id = plan_conv(p, c);
+  const int id = plan_conv(p, c, a.a_gate, a.a_act);
   if (id < 0) return id;
-  if (tile0 < 0 || !flags128 || !flags32 || !units || !counts) return EFFDET_EINVAL;
-  if (!live_flags_ok(p, id)) return EFFDET_EUNSUPPORTED;       // (a dense launch on flagged data is the caller's to ask for)
-  c.k.live = flags128; c.k.live_tile0 = tile0;
-  take_units(p, c, tile0, flags32, units, counts);
-  return c.launch(c, (hipStream_t)stream);
+  if (a.a_gate && !c.gate) return EFFDET_EUNSUPPORTED;
+  if (a.kind != FLAGS_NONE) {
+    if (a.tflag0 < 0 || (a.gathered && (!a.tflags || !a.flags32 || !a.units || !a.counts))) return EFFDET_EINVAL;
+    // flags the kernel cannot honour are only a hint and dropped; the gathered form refuses (a dense launch on flagged data is the caller's to ask for)
+    const bool ok = a.kind == FLAGS_LIVE ? live_flags_ok(p, id) : needed_flags_ok(p, c, id);
+    if (a.gathered && !ok) return EFFDET_EUNSUPPORTED;
+    if (a.tflags && ok) {
+      c.k.tflags = a.tflags; c.k.tflag0 = a.tflag0;
+      if (a.gathered) take_units(p, c, a.tflag0, a.flags32, a.units, a.counts);
+    }
+  }
+  return c.launch(c, st);
 }
 
+extern "C" int effdet_conv2d(const effdet_conv_t* p, effdet_stream_t stream) { return conv_launch(p, {}, (hipStream_t)stream); }
+extern "C" int effdet_conv2d_gated(const effdet_conv_t* p, const float* a_gate, int a_act, effdet_stream_t stream) {
+  return a_gate ? conv_launch(p, {a_gate, a_act}, (hipStream_t)stream) : EFFDET_EINVAL;
+}
+extern "C" int effdet_conv2d_live(const effdet_conv_t* p, const unsigned char* live, int live_tile0, effdet_stream_t stream) {
+  return conv_launch(p, {nullptr, EFFDET_ACT_NONE, FLAGS_LIVE, live, live_tile0}, (hipStream_t)stream);
+}
+extern "C" int effdet_conv2d_needed(const effdet_conv_t* p, const unsigned char* needed, int needed_tile0, effdet_stream_t stream) {
+  return conv_launch(p, {nullptr, EFFDET_ACT_NONE, FLAGS_NEEDED, needed, needed_tile0}, (hipStream_t)stream);
+}
+extern "C" int effdet_conv2d_live_units(const effdet_conv_t* p, const unsigned char* flags128, const unsigned char* flags32, const int* units,
+                                        const int* counts, int tile0, effdet_stream_t stream) {
+  return conv_launch(p, {nullptr, EFFDET_ACT_NONE, FLAGS_LIVE, flags128, tile0, true, flags32, units, counts}, (hipStream_t)stream);
+}
 extern "C" int effdet_conv2d_needed_units(const effdet_conv_t* p, const unsigned char* flags128, const unsigned char* flags32, const int* units,
                                           const int* counts, int tile0, effdet_stream_t stream) {
-  ConvPlan c;
-  const int id = plan_conv(p, c);
-  if (id < 0) return id;
-  if (tile0 < 0 || !flags128 || !flags32 || !units || !counts) return EFFDET_EINVAL;
-  if (!needed_flags_ok(p, c, id)) return EFFDET_EUNSUPPORTED;
-  c.k.needed = flags128; c.k.needed_tile0 = tile0;
-  take_units(p, c, tile0, flags32, units, counts);
-  return c.launch(c, (hipStream_t)stream);
+  return conv_launch(p, {nullptr, EFFDET_ACT_NONE, FLAGS_NEEDED, flags128, tile0, true, flags32, units, counts}, (hipStream_t)stream);
 }

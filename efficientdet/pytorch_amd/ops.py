@@ -488,14 +488,14 @@ def _conv_desc(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, sca
     d.act, d.res_mode = act, res_mode
     d.w_image_stride = int(w_image_stride)       # bytes; image b reads its own packed weights (scale_pack_weight)
     _segs(d, xs, ys, base_x, base_y, isx, isy)
-    if live is not None:
-        assert live.dtype == torch.uint8 and live.is_contiguous()
+    # live / needed are one (kind, tile flags, first tile) triple from here on: checked once, and what conv2d launches from
+    assert live is None or needed is None
+    kind, flags, tile0 = ('live', live, live_tile0) if live is not None else ('needed', needed, needed_tile0) if needed is not None else (None, None, 0)
+    if kind is not None:
+        assert flags.dtype == torch.uint8 and flags.is_contiguous()
         ntile = sum((y.B * y.H * y.W + 127) // 128 for y in ys)
-        assert 0 <= live_tile0 <= ntile and live.numel() == ntile - live_tile0, (live.numel(), ntile, live_tile0)
-    if needed is not None:
-        assert live is None and needed.dtype == torch.uint8 and needed.is_contiguous()
-        ntile = sum((y.B * y.H * y.W + 127) // 128 for y in ys)
-        assert 0 <= needed_tile0 <= ntile and needed.numel() == ntile - needed_tile0, (needed.numel(), ntile, needed_tile0)
+        assert 0 <= tile0 <= ntile and flags.numel() == ntile - tile0, (flags.numel(), ntile, tile0)
+    d.tile_flags = (kind, flags, tile0)          # (a Python attribute of the descriptor object: not part of effdet_conv_t)
     return d, xs, ys
 
 
@@ -533,17 +533,14 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
     # algorithmic bytes: the input map, the packed weights, every output stream (y, the pre-activation copy, the split copy), the residual
     nbytes = isx * Cin * sum(x.B * x.H * x.W for x in xs) + wp.numel() * wp.element_size() + \
         (4 if out_f32 else isy) * Cout * sum(y.B * y.H * y.W for y in ys) * (1 + (zs is not None) + (ysplit is not None) + (res is not None))
+    kind, flags, tile0 = d.tile_flags
+    key = (a_gate is not None, kind, units is not None)
+    assert key in _CONV_CALLS, key
+    name, args = _CONV_CALLS[key], []        # the entry point's own arguments, between descriptor and stream
     if a_gate is not None:
-        assert live is None and needed is None and a_gate.dtype == torch.float32 and a_gate.is_contiguous() and a_gate.shape == (x0.B, Cin)
-
-        def run():
-            L.check(L.require('effdet_conv2d_gated').effdet_conv2d_gated(C.byref(d), a_gate.data_ptr(), int(a_act), L.stream_ptr()),
-                    'effdet_conv2d_gated')
-            GATE_OPERAND_LAUNCHES[0] += 1
-    elif units is not None:
-        assert (live is None) != (needed is None)
-        name = 'effdet_conv2d_live_units' if live is not None else 'effdet_conv2d_needed_units'
-        f128, tile0 = (live, live_tile0) if live is not None else (needed, needed_tile0)
+        assert a_gate.dtype == torch.float32 and a_gate.is_contiguous() and a_gate.shape == (x0.B, Cin)
+        args = [a_gate.data_ptr(), int(a_act)]
+    if units is not None:
         f32, ulist, ucount = units
         assert f32.dtype == torch.uint8 and f32.is_contiguous() and ulist.dtype == torch.int32 and ulist.is_contiguous()
         assert ucount.dtype == torch.int32 and ucount.is_contiguous() and ucount.numel() == L.UNIT_COUNTS
@@ -553,20 +550,15 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
                 nstep += (y.B * y.H * y.W + 31) // 32
             t_ += (y.B * y.H * y.W + 127) // 128
         assert f32.numel() == nstep and ulist.numel() == nstep, (f32.numel(), ulist.numel(), nstep)
-        if needed is not None:
-            NEEDED_LAUNCHES[0] += 1
+        args = [f32.data_ptr(), ulist.data_ptr(), ucount.data_ptr()]
         UNIT_LAUNCHES[0] += 1
-        run = lambda: L.check(getattr(L.require(name), name)(C.byref(d), f128.data_ptr(), f32.data_ptr(), ulist.data_ptr(), ucount.data_ptr(),
-                                                            int(tile0), L.stream_ptr()), name)
-    elif live is not None:
-        run = lambda: L.check(L.require('effdet_conv2d_live').effdet_conv2d_live(C.byref(d), live.data_ptr(), int(live_tile0), L.stream_ptr()),
-                              'effdet_conv2d_live')
-    elif needed is not None:
-        NEEDED_LAUNCHES[0] += 1
-        run = lambda: L.check(L.require('effdet_conv2d_needed').effdet_conv2d_needed(C.byref(d), needed.data_ptr(), int(needed_tile0),
-                                                                                     L.stream_ptr()), 'effdet_conv2d_needed')
-    else:
-        run = lambda: L.check(L.lib().effdet_conv2d(C.byref(d), L.stream_ptr()), 'effdet_conv2d')
+    if kind is not None:
+        args = [flags.data_ptr()] + args + [int(tile0)]          # (tile flags, [unit lists,] first tile)
+        NEEDED_LAUNCHES[0] += kind == 'needed'
+
+    def run():
+        L.check(getattr(L.require(name), name)(C.byref(d), *args, L.stream_ptr()), name)
+        GATE_OPERAND_LAUNCHES[0] += a_gate is not None
     # (flops stay those of the dense launch: a flagged launch reports an EFFECTIVE rate)
     _timed(_igemm_symbol(x0.dtype, d) if PROFILE is not None else '', flops, run,
            'k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, sum(y.B * y.H * y.W for y in ys)), nbytes=float(nbytes))
@@ -575,6 +567,10 @@ def conv2d(xs, wp, ys, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, scale=N
 NEEDED_LAUNCHES = [0]        # conv2d(..., needed=...) calls made so far (tests: which path a step took)
 UNIT_LAUNCHES = [0]          # conv2d(..., units=...) calls made so far
 GATE_OPERAND_LAUNCHES = [0, 0]     # conv2d(..., a_gate=...) / conv2d_wgrad(..., a_gate=...) calls made so far (tests: which path a step took)
+# conv2d's library call by (a_gate given, kind of tile flags, units given); every other combination is refused
+_CONV_CALLS = {(False, None, False): 'effdet_conv2d', (True, None, False): 'effdet_conv2d_gated',
+               (False, 'live', False): 'effdet_conv2d_live', (False, 'needed', False): 'effdet_conv2d_needed',
+               (False, 'live', True): 'effdet_conv2d_live_units', (False, 'needed', True): 'effdet_conv2d_needed_units'}
 
 
 def conv2d_gated_plan_info(xs, wp, ys, a_gate, a_act=ACT_NONE, **kw):
@@ -588,10 +584,7 @@ def conv2d_gated_plan_info(xs, wp, ys, a_gate, a_act=ACT_NONE, **kw):
         return None
     if rc < 0:
         L.check(rc, 'effdet_conv2d_gated_plan_info')
-    out = {n: int(getattr(info, n)) for n, _ in L.ConvPlanInfo._fields_ if n != 'reserved'}
-    out['form'] = L.CONV_FORMS[out['form']]
-    out['persistent'], out['m32'], out['gate'] = bool(out['persistent']), bool(out['m32']), int(info.reserved[0])
-    return out
+    return dict(_plan_info_dict(info), gate=int(info.reserved[0]))
 
 
 def conv2d_gated_ok(xs, wp, ys, a_gate, a_act=ACT_NONE, **kw):
@@ -622,6 +615,11 @@ def conv2d_plan_info(xs, wp, ys, **kw):
     rc = int(L.require('effdet_conv2d_plan_info').effdet_conv2d_plan_info(C.byref(d), C.byref(info)))
     if rc < 0:
         L.check(rc, 'effdet_conv2d_plan_info')
+    return _plan_info_dict(info)
+
+
+def _plan_info_dict(info):
+    """effdet_conv_plan_info_t -> the dict of conv2d_plan_info / conv2d_gated_plan_info"""
     out = {n: int(getattr(info, n)) for n, _ in L.ConvPlanInfo._fields_ if n != 'reserved'}
     out['form'] = L.CONV_FORMS[out['form']]
     out['persistent'], out['m32'] = bool(out['persistent']), bool(out['m32'])
