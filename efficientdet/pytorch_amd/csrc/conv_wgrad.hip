@@ -1381,7 +1381,7 @@ constexpr int X3_NW = EFFDET_WGRAD_X3_WAVES;
 // What effdet_conv2d_wgrad launches for one descriptor, decided by plan_wgrad without a HIP runtime call
 enum { WG_TILED = 0, WG_THIN = 1, WG_SPLIT = 2, WG_STEM = 3 };      // (effdet_conv2d_wgrad_kernel reports the stem's form as 1)
 struct WgradPlan;
-typedef void (*ThinLaunch)(const WgradPlan&, const WgradK&, hipStream_t);
+typedef void (*WgradLaunch)(const WgradPlan&, const WgradK&, unsigned blocks, hipStream_t);
 struct WgradPlan {
   // the normalised descriptor: EFFDET_F32_BF16X3 as EFFDET_F32 (x3 set); EFFDET_F32_SPLIT (split set) as the bf16 tensor of twice the
   // channel count it is byte for byte (the VIEW: channel counts, pitches, offsets x 2; the dz width is its whole padded pitch)
@@ -1391,28 +1391,49 @@ struct WgradPlan {
   int path;                    // WG_*
   WgradK k;                    // kernel arguments but the workspace pointers; WG_TILED: the fast (DMA-staged) launch's ...
   WgradK ks;                   // ... and the register-transpose launch's
-  int splits, nfast;           // slabs in all / of the fast launch
+  int splits, nfast;           // slabs in all / of the main launch (WG_TILED: the fast one; every other path: all of them)
   int first[EFFDET_MAX_SEG], count[EFFDET_MAX_SEG];                  // slab range of every level (effdet_conv2d_wgrad_seg_slabs)
   int P, NS, pps;              // thin kernel: pixels per stage, ring slots, DMA instructions per wave and stage
-  ThinLaunch thin;             // thin kernel: the instance for the (Cout / 16, Cin / 16) tile shape
+  // the kernel instances, set where plan_wgrad decides the path (to add one: a launcher<...> in the table of its path, picked there)
+  WgradLaunch launch;          // the main launch on k, tiles x nfast blocks (null: WG_TILED with no fast level)
+  WgradLaunch launch_live;     // WG_SPLIT: the same with per-call step flags (LIVE = 1); null on every other path
+  WgradLaunch launch_rest;     // WG_TILED: the register-transpose launch on ks, tiles x (splits - nfast) blocks; null when splits == nfast
   int gate;                    // the kernels' GATE parameter: 0, or the operand-gate form (1 multiply, 2 Swish + multiply)
-  size_t lds;                  // dynamic LDS bytes of the main launch
+  size_t lds;                  // dynamic LDS bytes of every launch of the plan
   int allr;                    // split kernel: all fragment reads of a K-step issued ahead of its MFMAs
   long long slab_floats;       // floats per slab (cout x algorithmic K)
   long long workspace_bytes;   // slabs + the [splits][cout] bias partial rows
 };
 
-template <int NTA, int NTB, bool STEM = false, int GATE = 0>
-void launch_thin(const WgradPlan& w, const WgradK& k, hipStream_t st) {
-  EFFDET_SET_MAX_LDS((conv_wgrad_thin_kernel<NTA, NTB, STEM, GATE>), w.lds);
-  hipLaunchKernelGGL((conv_wgrad_thin_kernel<NTA, NTB, STEM, GATE>), dim3((unsigned)w.splits), dim3(256), w.lds, st, k, w.P, w.pps, w.NS);
+// One kernel instance as a launcher (the attribute of EFFDET_SET_MAX_LDS is per kernel: its static is this instantiation's own).
+// THIN: conv_wgrad_thin_kernel's extra arguments.  K: WgradPairK for the paired kernel.
+template <auto Kernel, int THREADS, bool THIN = false, typename K = WgradK>
+void launcher(const WgradPlan& w, const K& k, unsigned blocks, hipStream_t st) {
+  EFFDET_SET_MAX_LDS(Kernel, w.lds);
+  if constexpr (THIN) hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(THREADS), w.lds, st, k, w.P, w.pps, w.NS);
+  else hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(THREADS), w.lds, st, k);
 }
+const WgradLaunch split_launch[2][2] = {      // [ALLR][LIVE]
+  {launcher<conv_wgrad_split_kernel<0, 0>, 512>, launcher<conv_wgrad_split_kernel<0, 1>, 512>},
+  {launcher<conv_wgrad_split_kernel<1, 0>, 512>, launcher<conv_wgrad_split_kernel<1, 1>, 512>}};
+void (*const pair_launch[2][2])(const WgradPlan&, const WgradPairK&, unsigned, hipStream_t) = {      // [ALLR][LIVEB] (effdet_conv2d_wgrad_pair)
+  {launcher<conv_wgrad_pair_kernel<0, 0>, 512, false, WgradPairK>, launcher<conv_wgrad_pair_kernel<0, 1>, 512, false, WgradPairK>},
+  {launcher<conv_wgrad_pair_kernel<1, 0>, 512, false, WgradPairK>, launcher<conv_wgrad_pair_kernel<1, 1>, 512, false, WgradPairK>}};
+const WgradLaunch f32dma_launch[2][3] = {     // [X3][GATE]
+  {launcher<conv_wgrad_f32dma_kernel<F32_NW, 0, 0>, F32_NW * 64>, launcher<conv_wgrad_f32dma_kernel<F32_NW, 0, 1>, F32_NW * 64>,
+   launcher<conv_wgrad_f32dma_kernel<F32_NW, 0, 2>, F32_NW * 64>},
+  {launcher<conv_wgrad_f32dma_kernel<X3_NW, 1, 0>, X3_NW * 64>, launcher<conv_wgrad_f32dma_kernel<X3_NW, 1, 1>, X3_NW * 64>,
+   launcher<conv_wgrad_f32dma_kernel<X3_NW, 1, 2>, X3_NW * 64>}};
+const WgradLaunch tr_launch = launcher<conv_wgrad_tr_kernel<TR_NW>, TR_NW * 64>;
+const WgradLaunch rest_launch[2] = {launcher<conv_wgrad_kernel<float>, 256>, launcher<conv_wgrad_kernel<bf16_t>, 256>};      // [bf16 storage]
+template <int NTA, int NTB, bool STEM = false, int GATE = 0>
+constexpr WgradLaunch launch_thin = launcher<conv_wgrad_thin_kernel<NTA, NTB, STEM, GATE>, 256, true>;
 // (Cout / 16, Cin / 16) tile shapes conv_wgrad_thin_kernel is built for: EfficientNet-B0..B2's high-resolution 1x1 convs
 #define THIN_(a, b) {a, b, {launch_thin<a, b>, launch_thin<a, b, false, 1>, launch_thin<a, b, false, 2>}}
-const struct { int nta, ntb; ThinLaunch launch[3]; } thin_shapes[] = {      // launch[GATE]
+const struct { int nta, ntb; WgradLaunch launch[3]; } thin_shapes[] = {      // launch[GATE]
   THIN_(1, 2), THIN_(6, 1), THIN_(2, 6), THIN_(9, 2), THIN_(2, 9), THIN_(3, 9), THIN_(1, 1), THIN_(2, 1), THIN_(1, 3), THIN_(2, 2)};
 #undef THIN_
-ThinLaunch thin_launch(int nta, int ntb, int gate = 0) {
+WgradLaunch thin_launch(int nta, int ntb, int gate = 0) {
   for (const auto& t : thin_shapes) if (t.nta == nta && t.ntb == ntb) return t.launch[gate];
   return nullptr;
 }
@@ -1443,6 +1464,7 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w, const float* a_gate = null
   if (!p) return EFFDET_EINVAL;
   if (a_gate && a_act != EFFDET_ACT_NONE && a_act != EFFDET_ACT_SWISH) return EFFDET_EINVAL;
   w.gate = a_gate ? (a_act == EFFDET_ACT_SWISH ? 2 : 1) : 0;
+  w.launch = w.launch_live = w.launch_rest = nullptr;
   effdet_wgrad_t& q = w.d;
   q = *p; w.cout = q.Cout; w.x3 = w.split = false;
   if (q.dtype == EFFDET_F32_BF16X3) { q.dtype = EFFDET_F32; w.x3 = true; }
@@ -1493,13 +1515,14 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w, const float* a_gate = null
     // (q.Cin is the bf16 VIEW's doubled count: the rule as it stands is 1 from 64 input channels up, 0 only below)
     static const int allr_env = getenv("EFFDET_WGRAD_SPLIT_ALLR") ? atoi(getenv("EFFDET_WGRAD_SPLIT_ALLR")) : -1;
     w.allr = allr_env >= 0 ? allr_env : (q.Cin >= 128 ? 1 : 0);
+    w.launch = split_launch[w.allr ? 1 : 0][0]; w.launch_live = split_launch[w.allr ? 1 : 0][1];
     w.lds = (size_t)4 * 128 * 8 * sizeof(uint4);                       // 2 stages x (dz 16 KiB + x 16 KiB)
   } else if (thin == 2) {
     // the stem: 64 output pixels per stage = 9 KiB of gathered taps + 8 KiB of dz rows, 3 slots (two workgroups per CU)
     w.path = WG_STEM; w.P = 64; w.NS = 3; w.pps = (w.P * (36 + q.Cout) * 4 / 1024 + 3) / 4;
     w.lds = (size_t)w.NS * ((size_t)w.P * (36 + q.Cout) * 4 + 1024);
     if ((w.P * q.Cout * 4) & 1023) return EFFDET_EUNSUPPORTED;
-    w.thin = launch_thin<2, 3, true>;
+    w.launch = launch_thin<2, 3, true>; w.nfast = w.splits;           // (one block per slab: a thin plan has one channel tile)
   } else if (thin == 1) {
     // Stage size P (pixels) and ring depth NS, measured per channel budget (tools/wgrad_thin_bench.py, B = 32): the kernel is bound by
     // its LDS-read + fp32-MFMA loop (knock-outs: DMA alone streams at 5.2-6.1 TB/s, the loop alone at 3.6-4.8), so what pays is TWO
@@ -1518,7 +1541,7 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w, const float* a_gate = null
     while (w.NS > 2 && (w.NS - 2) * w.pps > 48) --w.NS;                                       // (the vmcnt immediates the kernel has)
     w.lds = (size_t)w.NS * ((size_t)w.P * ch * 4 + 1024);
     if (w.lds < 32 * 1024) w.lds = 32 * 1024;                                                 // the final cross-wave reduction (8 tiles x 4 waves)
-    w.thin = thin_launch((q.Cout + 15) / 16, (q.Cin + 15) / 16, w.gate);
+    w.launch = thin_launch((q.Cout + 15) / 16, (q.Cin + 15) / 16, w.gate); w.nfast = w.splits;
   } else {
     // the levels split between the DMA-staged kernel (fast) and the register-transpose kernel
     w.path = WG_TILED;
@@ -1534,6 +1557,9 @@ int plan_wgrad(const effdet_wgrad_t* p, WgradPlan& w, const float* a_gate = null
     k.nseg = nf; w.ks.nseg = ns;
     w.lds = (size_t)4 * 128 * 8 * sizeof(uint4);
     if (a_gate && ns) return EFFDET_EUNSUPPORTED;      // only the DMA-staged fp32 kernel has the hook, not the register-transpose one
+    // fp32 storage: the DMA + direct-operand kernel (an accepted gate: one level, all of it here); bf16: the DMA + transpose-read kernel
+    if (nf) w.launch = q.dtype == EFFDET_F32 ? f32dma_launch[w.x3][w.gate] : tr_launch;
+    if (ns) w.launch_rest = rest_launch[q.dtype == EFFDET_BF16];
   }
   w.slab_floats = (long long)w.cout * k.K;
   w.workspace_bytes = (long long)w.splits * (w.slab_floats + w.cout) * (long long)sizeof(float);
@@ -1588,7 +1614,7 @@ extern "C" int effdet_conv2d_wgrad_plan_info(const effdet_wgrad_t* p, effdet_wgr
   if (rc != EFFDET_OK) return rc;
   const bool thin = w.path == WG_THIN || w.path == WG_STEM;
   effdet_wgrad_plan_info_t o = {};
-  o.path = w.path; o.splits = w.splits; o.nfast = w.path == WG_TILED ? w.nfast : w.splits; o.mchunk = w.k.mchunk;
+  o.path = w.path; o.splits = w.splits; o.nfast = w.nfast; o.mchunk = w.k.mchunk;
   o.ntiles = thin ? 1 : w.k.ntiles; o.jtiles = thin ? 1 : w.k.jtiles;
   o.stage_pixels = thin ? w.P : (w.path == WG_SPLIT || w.d.dtype == EFFDET_F32) ? 32 : 64;
   o.allr = w.path == WG_SPLIT ? w.allr : 0; o.thin_ns = thin ? w.NS : 0; o.gate = w.gate; o.nseg = p->nseg;
@@ -1606,61 +1632,25 @@ static int wgrad_launch(const effdet_wgrad_t* p, void* workspace, long long work
   if (rc != EFFDET_OK) return rc;
   if (a_gate && live32) return EFFDET_EUNSUPPORTED;
   if (workspace_bytes < w.workspace_bytes) return EFFDET_EINVAL;
+  if (live32 && w.path != WG_SPLIT) return EFFDET_EUNSUPPORTED;
+  if (live32 && w.k.mchunk % 32) return EFFDET_EINVAL;      // a split must start on a step of the flag array
   hipStream_t st = (hipStream_t)stream;
   WgradK k = w.k;
   k.slab = (float*)workspace;
   k.dbp = p->dbias ? k.slab + (long long)w.splits * w.slab_floats : nullptr;
+  k.live32 = live32;
   const unsigned tiles = (unsigned)(k.ntiles * k.jtiles);
-  if (live32) {
-    if (w.path != WG_SPLIT) return EFFDET_EUNSUPPORTED;
-    if (k.mchunk % 32) return EFFDET_EINVAL;              // a split must start on a step of the flag array
-    k.live32 = live32;
-    if (w.allr) {
-      EFFDET_SET_MAX_LDS((conv_wgrad_split_kernel<1, 1>), w.lds);
-      hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1>), dim3(tiles * w.splits), dim3(512), w.lds, st, k);
-    } else {
-      EFFDET_SET_MAX_LDS((conv_wgrad_split_kernel<0, 1>), w.lds);
-      hipLaunchKernelGGL((conv_wgrad_split_kernel<0, 1>), dim3(tiles * w.splits), dim3(512), w.lds, st, k);
-    }
-  } else if (w.path == WG_SPLIT && w.allr) {
-    EFFDET_SET_MAX_LDS(conv_wgrad_split_kernel<1>, w.lds);
-    hipLaunchKernelGGL(conv_wgrad_split_kernel<1>, dim3(tiles * w.splits), dim3(512), w.lds, st, k);
-  } else if (w.path == WG_SPLIT) {
-    EFFDET_SET_MAX_LDS(conv_wgrad_split_kernel<0>, w.lds);
-    hipLaunchKernelGGL(conv_wgrad_split_kernel<0>, dim3(tiles * w.splits), dim3(512), w.lds, st, k);
-  } else if (w.path != WG_TILED) {
-    w.thin(w, k, st);
-  } else {
+  if (w.launch) {
+    (live32 ? w.launch_live : w.launch)(w, k, tiles * w.nfast, st);
+    EFFDET_CHECK_LAUNCH();
+  }
+  if (w.launch_rest) {
     WgradK ks = w.ks;
     ks.slab = k.slab + (long long)w.nfast * w.slab_floats;
     ks.dbp = k.dbp ? k.dbp + (long long)w.nfast * w.cout : nullptr;
-    if (w.gate) {
-      // (plan_wgrad accepted the gate: one level, all of it on the DMA-staged fp32 kernel)
-#define GATED_(NW, X3, G) do { EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<NW, X3, G>), w.lds); \
-        hipLaunchKernelGGL((conv_wgrad_f32dma_kernel<NW, X3, G>), dim3(tiles * w.nfast), dim3(NW * 64), w.lds, st, k); } while (0)
-      if (w.x3) { if (w.gate == 2) GATED_(X3_NW, 1, 2); else GATED_(X3_NW, 1, 1); }
-      else { if (w.gate == 2) GATED_(F32_NW, 0, 2); else GATED_(F32_NW, 0, 1); }
-#undef GATED_
-    } else if (w.nfast > 0 && w.d.dtype == EFFDET_F32 && w.x3) {
-      EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<X3_NW, 1>), w.lds);
-      hipLaunchKernelGGL((conv_wgrad_f32dma_kernel<X3_NW, 1>), dim3(tiles * w.nfast), dim3(X3_NW * 64), w.lds, st, k);
-    } else if (w.nfast > 0 && w.d.dtype == EFFDET_F32) {
-      EFFDET_SET_MAX_LDS((conv_wgrad_f32dma_kernel<F32_NW>), w.lds);
-      hipLaunchKernelGGL(conv_wgrad_f32dma_kernel<F32_NW>, dim3(tiles * w.nfast), dim3(F32_NW * 64), w.lds, st, k);
-    } else if (w.nfast > 0) {
-      EFFDET_SET_MAX_LDS((conv_wgrad_tr_kernel<TR_NW>), w.lds);
-      hipLaunchKernelGGL(conv_wgrad_tr_kernel<TR_NW>, dim3(tiles * w.nfast), dim3(TR_NW * 64), w.lds, st, k);
-    }
+    w.launch_rest(w, ks, tiles * (w.splits - w.nfast), st);
     EFFDET_CHECK_LAUNCH();
-    if (w.splits > w.nfast && w.d.dtype == EFFDET_F32) {
-      EFFDET_SET_MAX_LDS((conv_wgrad_kernel<float>), w.lds);
-      hipLaunchKernelGGL(conv_wgrad_kernel<float>, dim3(tiles * (w.splits - w.nfast)), dim3(256), w.lds, st, ks);
-    } else if (w.splits > w.nfast) {
-      EFFDET_SET_MAX_LDS((conv_wgrad_kernel<bf16_t>), w.lds);
-      hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, dim3(tiles * (w.splits - w.nfast)), dim3(256), w.lds, st, ks);
-    }
   }
-  EFFDET_CHECK_LAUNCH();
   return reduce_slabs(p, w, k.slab, k.dbp, st);
 }
 
@@ -1726,19 +1716,7 @@ extern "C" int effdet_conv2d_wgrad_pair(const effdet_wgrad_t* a, const effdet_wg
   const char* ord = getenv("EFFDET_WGRAD_PAIR_ORDER");
   q.first = ord ? (atoi(ord) ? 1 : 0) : (live32_b ? 1 : 0);
   const unsigned grid = (unsigned)(ka.ntiles * ka.jtiles) * (unsigned)(wa.splits + wb.splits);
-  if (live32_b && wa.allr) {
-    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<1, 1>), wa.lds);
-    hipLaunchKernelGGL((conv_wgrad_pair_kernel<1, 1>), dim3(grid), dim3(512), wa.lds, st, q);
-  } else if (live32_b) {
-    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<0, 1>), wa.lds);
-    hipLaunchKernelGGL((conv_wgrad_pair_kernel<0, 1>), dim3(grid), dim3(512), wa.lds, st, q);
-  } else if (wa.allr) {
-    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<1, 0>), wa.lds);
-    hipLaunchKernelGGL((conv_wgrad_pair_kernel<1, 0>), dim3(grid), dim3(512), wa.lds, st, q);
-  } else {
-    EFFDET_SET_MAX_LDS((conv_wgrad_pair_kernel<0, 0>), wa.lds);
-    hipLaunchKernelGGL((conv_wgrad_pair_kernel<0, 0>), dim3(grid), dim3(512), wa.lds, st, q);
-  }
+  pair_launch[wa.allr ? 1 : 0][live32_b ? 1 : 0](wa, q, grid, st);
   EFFDET_CHECK_LAUNCH();
   rc = reduce_slabs(a, wa, q.slab[0], q.dbp[0], st);
   return rc != EFFDET_OK ? rc : reduce_slabs(b, wb, q.slab[1], q.dbp[1], st);

@@ -596,13 +596,15 @@ def conv2d_gated_ok(xs, wp, ys, a_gate, a_act=ACT_NONE, **kw):
 
 def conv2d_wgrad_gated_ok(x, dz, a_gate, a_act=ACT_NONE, *, Cin, Cout, KH=1, KW=1, image_splits=True):
     """Does the planner accept conv2d_wgrad(x, dz, ..., a_gate=a_gate, a_act=a_act)?  (effdet_conv2d_wgrad_gated_kernel: no device work.)"""
-    d = _wgrad_desc([x], [dz], None, None, Cin, Cout, KH, KW, 1, 0, 0, True, False, image_splits)
-    rc = int(L.require('effdet_conv2d_wgrad_gated_kernel').effdet_conv2d_wgrad_gated_kernel(C.byref(d), a_gate.data_ptr(), int(a_act)))
-    if rc == -3:
-        return False
-    if rc < 0:
+    rc = _wgrad_gated_kernel(_wgrad_desc([x], [dz], None, None, Cin, Cout, KH, KW, 1, 0, 0, True, False, image_splits), a_gate, a_act)
+    if rc < 0 and rc != -3:
         L.check(rc, 'effdet_conv2d_wgrad_gated_kernel')
-    return True
+    return rc >= 0
+
+
+def _wgrad_gated_kernel(d, a_gate, a_act):
+    """effdet_conv2d_wgrad_gated_kernel on a descriptor: the path of the operand-gate launch, or the (negative) code it is refused with"""
+    return int(L.require('effdet_conv2d_wgrad_gated_kernel').effdet_conv2d_wgrad_gated_kernel(C.byref(d), a_gate.data_ptr(), int(a_act)))
 
 
 def conv2d_plan_info(xs, wp, ys, **kw):
@@ -649,9 +651,7 @@ def conv2d_wgrad_kernel_id(x, dz, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l
     """Which kernel conv2d_wgrad would launch for one map pair (effdet_conv2d_wgrad_kernel): 0 tiled, 1 thin pointwise, 2 split;
     with a_gate: the operand-gate launch's (effdet_conv2d_wgrad_gated_kernel), negative where it is refused."""
     d = _wgrad_desc([x], [dz], None, None, Cin, Cout, KH, KW, stride, pad_t, pad_l, True, split, image_splits)
-    if a_gate is not None:
-        return int(L.require('effdet_conv2d_wgrad_gated_kernel').effdet_conv2d_wgrad_gated_kernel(C.byref(d), a_gate.data_ptr(), int(a_act)))
-    return int(L.lib().effdet_conv2d_wgrad_kernel(C.byref(d)))
+    return _wgrad_gated_kernel(d, a_gate, a_act) if a_gate is not None else int(L.lib().effdet_conv2d_wgrad_kernel(C.byref(d)))
 
 
 def conv2d_wgrad_plan_info(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, split=False,
@@ -662,15 +662,29 @@ def conv2d_wgrad_plan_info(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, s
     jtiles, stage_pixels, allr, thin_ns, gate, first and count (lists, one entry per map).  Raises where conv2d_wgrad would."""
     if isinstance(xs, Map):
         xs, dzs = [xs], [dzs]
-    d = _wgrad_desc(xs, dzs, dw, dbias, Cin, Cout, KH, KW, stride, pad_t, pad_l, want_bias, split, image_splits)
+    return _wgrad_plan(_wgrad_desc(xs, dzs, dw, dbias, Cin, Cout, KH, KW, stride, pad_t, pad_l, want_bias, split, image_splits))
+
+
+def _wgrad_plan(d, refused=None):
+    """The library's plan for a descriptor, asked once (effdet_conv2d_wgrad_plan_info) -> the dict of conv2d_wgrad_plan_info.  A refused
+    plan raises RuntimeError(refused), or (refused None) the library's code as L.check words it."""
     info = L.WgradPlanInfo()
     rc = int(L.require('effdet_conv2d_wgrad_plan_info').effdet_conv2d_wgrad_plan_info(C.byref(d), C.byref(info)))
     if rc < 0:
+        if refused is not None:
+            raise RuntimeError(refused)
         L.check(rc, 'effdet_conv2d_wgrad_plan_info')
     out = {n: int(getattr(info, n)) for n, _ in L.WgradPlanInfo._fields_ if n not in ('first', 'count', 'reserved', 'nseg')}
     out['path'], out['allr'] = L.WGRAD_PATHS[out['path']], bool(out['allr'])
     out['first'], out['count'] = list(info.first[:info.nseg]), list(info.count[:info.nseg])
     return out
+
+
+def _wgrad_views(ws, splits, Cout, taps, Cin, bias, first=0, count=None):
+    """The head of a workspace in effdet_conv2d_wgrad's layout -> (slabs [splits][Cout][taps][Cin], bias partial rows [splits][Cout] or
+    None); first, count: that slab range only (one problem of a grouped launch)."""
+    n, r = Cout * taps * Cin, slice(first, splits if count is None else first + count)
+    return ws[:splits * n].view(splits, Cout, taps, Cin)[r], (ws[splits * n:splits * (n + Cout)].view(splits, Cout)[r] if bias else None)
 
 
 def _wgrad_workspace(ws, floats, device):
@@ -687,7 +701,7 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     split-K partials for unpack_wgrad / unpack_wgrad_bn to sum, in slab order, while unpacking (no float atomics anywhere: two
     runs are bitwise equal).  With dw given (packed [Cout][taps][Cin] fp32) the library reduces itself: dw += ..., dbias += ...
     group=True (dw None, <= 5 maps): the maps are INDEPENDENT problems of the same conv geometry (different tensors, different
-    weights) sharing one launch -> a list of (slabs_i, parts_i), one per map (effdet_conv2d_wgrad_seg_slabs).
+    weights) sharing one launch -> a list of (slabs_i, parts_i), one per map (the plan's first / count).
     live32 (split only; uint8 tensor, one byte per 32-pixel step of dzs: live_tiles()[0][r]): a 0 marks a step whose dz pixels are all
     zero; every split-K block walks only its live steps.  Same slabs and bias rows as without.
     a_gate ([B][Cin] fp32, with a_act = ACT_NONE or ACT_SWISH; image_splits, one 1x1 map pair): the gradient against
@@ -700,45 +714,34 @@ def conv2d_wgrad(xs, dzs, dw=None, dbias=None, *, Cin, Cout, KH, KW, stride=1, p
     x0 = xs[0]
     d = _wgrad_desc(xs, dzs, dw, dbias, Cin, Cout, KH, KW, stride, pad_t, pad_l, want_bias, split, image_splits)
     flops = 2.0 * KH * KW * Cin * Cout * sum(z.B * z.H * z.W for z in dzs)
-    splits = int(L.lib().effdet_conv2d_wgrad_splits(C.byref(d)))
-    if splits < 1:
-        raise RuntimeError('effdet_conv2d_wgrad: unsupported geometry')
-    n = Cout * KH * KW * Cin
+    plan = _wgrad_plan(d, 'effdet_conv2d_wgrad: unsupported geometry')
+    splits, n = plan['splits'], Cout * KH * KW * Cin
     ws = _wgrad_workspace(ws, splits * (n + Cout), x0.t.device)
-    nbytes = ws.numel() * 4
+    name, args = 'effdet_conv2d_wgrad', (L.ptr(ws), ws.numel() * 4)
     if a_gate is not None:
         assert live32 is None and not group and a_gate.dtype == torch.float32 and a_gate.is_contiguous() and a_gate.shape == (x0.B, Cin)
-
-        def run():
-            L.check(L.require('effdet_conv2d_wgrad_gated').effdet_conv2d_wgrad_gated(
-                C.byref(d), a_gate.data_ptr(), int(a_act), L.ptr(ws), nbytes, L.stream_ptr()), 'effdet_conv2d_wgrad_gated')
-            GATE_OPERAND_LAUNCHES[1] += 1
+        name, args = 'effdet_conv2d_wgrad_gated', (a_gate.data_ptr(), int(a_act)) + args
     elif live32 is not None:
         assert split and live32.dtype == torch.uint8 and live32.is_contiguous()
         assert live32.numel() == sum((z.B * z.H * z.W + 31) // 32 for z in dzs)
-        run = lambda: L.check(L.require('effdet_conv2d_wgrad_live').effdet_conv2d_wgrad_live(C.byref(d), L.ptr(ws), nbytes, live32.data_ptr(),
-                                                                                             L.stream_ptr()), 'effdet_conv2d_wgrad_live')
-    else:
-        run = lambda: L.check(L.lib().effdet_conv2d_wgrad(C.byref(d), L.ptr(ws), nbytes, L.stream_ptr()), 'effdet_conv2d_wgrad')
+        name, args = 'effdet_conv2d_wgrad_live', args + (live32.data_ptr(),)
+
+    def run():
+        L.check(getattr(L.require(name), name)(C.byref(d), *args, L.stream_ptr()), name)
+        GATE_OPERAND_LAUNCHES[1] += a_gate is not None
     # (bf16: DMA + LDS-transpose-read kernel, fp32: DMA + direct-operand kernel; levels neither can take use the register-transpose kernel)
     _timed('conv_wgrad_tr_kernel<8>' if x0.dtype == torch.bfloat16 else
-           ('conv_wgrad_split_kernel' if split else
-            ('conv_wgrad_thin_kernel' if int(L.lib().effdet_conv2d_wgrad_kernel(C.byref(d))) == 1 else
-             ('conv_wgrad_f32dma_kernel<4,bf16x3>' if d.dtype == L.F32_BF16X3 else 'conv_wgrad_f32dma_kernel<8>'))), flops,
+           'conv_wgrad_split_kernel' if split else
+           'conv_wgrad_thin_kernel' if plan['path'] in ('thin', 'stem') else
+           'conv_wgrad_f32dma_kernel<4,bf16x3>' if d.dtype == L.F32_BF16X3 else 'conv_wgrad_f32dma_kernel<8>', flops,
            run,
            'k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, sum(z.B * z.H * z.W for z in dzs)),
            nbytes=float(x0.t.element_size() * Cin * sum(x.B * x.H * x.W for x in xs) +
                         dzs[0].t.element_size() * Cout * sum(z.B * z.H * z.W for z in dzs) + 4.0 * splits * (n + Cout)))
-    slabs = ws[:splits * n].view(splits, Cout, KH * KW, Cin)
-    parts = ws[splits * n:].view(splits, Cout) if d.dbias else None
     if group:
         assert dw is None and not image_splits
-        first, count = (C.c_int * len(xs))(), (C.c_int * len(xs))()
-        tot = int(L.lib().effdet_conv2d_wgrad_seg_slabs(C.byref(d), first, count))
-        assert tot == splits
-        return [(slabs[first[i]:first[i] + count[i]], parts[first[i]:first[i] + count[i]] if parts is not None else None)
-                for i in range(len(xs))]
-    return slabs, parts
+        return [_wgrad_views(ws, splits, Cout, KH * KW, Cin, d.dbias, f, c) for f, c in zip(plan['first'], plan['count'])]
+    return _wgrad_views(ws, splits, Cout, KH * KW, Cin, d.dbias)
 
 
 def conv2d_wgrad_pair(xs_a, dzs_a, xs_b, dzs_b, *, Cin, Cout, KH, KW, stride=1, pad_t=0, pad_l=0, want_bias=True, live32_b=None, ws=None):
@@ -754,9 +757,7 @@ def conv2d_wgrad_pair(xs_a, dzs_a, xs_b, dzs_b, *, Cin, Cout, KH, KW, stride=1, 
     lib_ = L.require('effdet_conv2d_wgrad_pair')
     ds = [_wgrad_desc(xs, dzs, None, None, Cin, Cout, KH, KW, stride, pad_t, pad_l, want_bias, True, False)
           for xs, dzs in ((xs_a, dzs_a), (xs_b, dzs_b))]
-    splits = [int(lib_.effdet_conv2d_wgrad_splits(C.byref(d))) for d in ds]
-    if min(splits) < 1:
-        raise RuntimeError('effdet_conv2d_wgrad_pair: unsupported geometry')
+    splits = [_wgrad_plan(d, 'effdet_conv2d_wgrad_pair: unsupported geometry')['splits'] for d in ds]
     n = Cout * KH * KW * Cin
     ws = _wgrad_workspace(ws, sum(splits) * (n + Cout), xs_a[0].t.device)
     nbytes = ws.numel() * 4
@@ -770,12 +771,8 @@ def conv2d_wgrad_pair(xs_a, dzs_a, xs_b, dzs_b, *, Cin, Cout, KH, KW, stride=1, 
     _timed('conv_wgrad_split_kernel', 2.0 * KH * KW * Cin * Cout * pix, run, 'pair k%d s%d Cin%d Cout%d M%d' % (KH, stride, Cin, Cout, pix),
            nbytes=float(xs_a[0].t.element_size() * Cin * (sum(x.B * x.H * x.W for x in xs_a) + sum(x.B * x.H * x.W for x in xs_b)) +
                         dzs_a[0].t.element_size() * Cout * pix + 4.0 * sum(splits) * (n + Cout)))
-    out, o = [], 0
-    for sp in splits:
-        slabs = ws[o:o + sp * n].view(sp, Cout, KH * KW, Cin)
-        parts = ws[o + sp * n:o + sp * (n + Cout)].view(sp, Cout) if want_bias else None
-        out.append((slabs, parts)); o += sp * (n + Cout)
-    return tuple(out)
+    return (_wgrad_views(ws, splits[0], Cout, KH * KW, Cin, want_bias),
+            _wgrad_views(ws[splits[0] * (n + Cout):], splits[1], Cout, KH * KW, Cin, want_bias))
 
 
 class _TailBatch:
@@ -917,7 +914,7 @@ def wgrad_split_supported(B, sizes, Cin, Cout, lddz, KH=3, KW=3, pad=1):
         s.H, s.W, s.Ho, s.Wo = h, w, h, w
         s.in_off, s.in_bstride, s.out_off, s.out_bstride = ox, h * w * Cin, oz, h * w * lddz
         ox += B * h * w * Cin; oz += B * h * w * lddz
-    return int(L.lib().effdet_conv2d_wgrad_splits(C.byref(d))) >= 1
+    return int(L.require('effdet_conv2d_wgrad_plan_info').effdet_conv2d_wgrad_plan_info(C.byref(d), C.byref(L.WgradPlanInfo()))) >= 0
 
 
 def live_tiles(dreg, B, sizes, reg_ld, split):

@@ -210,7 +210,8 @@ def test_gate_in_weights_forward_then_chain_backward():
 
 
 # (Cout, Cin) at B = 2, 128 x 128 = 32768 pixels, the thin kernel's threshold: its <1,2>, <2,6>, <2,9> and <3,9> tile shapes
-THIN = [(16, 32), (24, 96), (24, 144), (40, 144)]
+THIN = [(16, 32), (24, 96), (24, 144), (40, 144),
+        (96, 16), (144, 24), (16, 16), (32, 16), (16, 48), (32, 32)]      # the table's other shapes: <6,1>, <9,2>, <1,1>, <2,1>, <1,3>, <2,2>
 # at B = 2, 16 x 16: the DMA-staged fp32 kernel, exact and bf16x3
 TILED = [(40, 240), (80, 240)]
 
