@@ -1121,69 +1121,97 @@ __global__ __launch_bounds__(256) void tal_metrics_kernel(const LossK p, const T
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// host side
+// host side.  Every extern "C" loss function fills one LossCall and hands it to a driver (loss_forward, loss_bwd, loss_bwd_cls,
+// loss_bwd_reg), which makes the entry point's checks, carves the workspace by the one rule loss_workspace and launches from the
+// record: the matcher picks one of four assign paths, opts / ql the class policy, the box term smooth-L1 or the IoU-family kernels.
 
 // workgroups per image of the assign pass / upper bound of the class pass (either kernel: dld <= 9*nc + 63)
 inline long long assign_blocks(long long A) { return (A + 255) / 256; }
 inline long long cls_blocks_max(long long A, int nc) { return ((A * nc + 3) / 4 + (A / 9 + 1) * 16 + 1023) / 1024 + 1; }
 
-// assign [B][A], stat [B][SS], part_reg [B][na], part_cls [B][cls_blocks_max] -> bytes (num_classes only sizes the last buffer)
-size_t carve_loss(LossK& k, void* ws, int B, long long A, int num_classes = 0) {
-  Carver c(ws);
-  k.assign = c.take<int>((size_t)B * A);
-  k.stat = c.take<float>((size_t)B * SS);
-  k.part_reg = c.take<float>((size_t)B * assign_blocks(A));
-  k.part_cls = c.take<float>((size_t)B * cls_blocks_max(A, num_classes));
-  k.na = (int)assign_blocks(A);
-  return c.off;
-}
-
-// carve_loss's layout, then gtmax [B][N], best [B][A], barg [B][A] -> bytes
-size_t carve_loss_opts(LossK& k, OptsK& o, void* ws, int B, long long A, int num_classes, int N) {
-  const size_t head = carve_loss(k, ws, B, A, num_classes);
-  Carver c(ws ? (char*)ws + head : nullptr);
-  o.gtmax = c.take<int>((size_t)B * N);
-  o.best = c.take<float>((size_t)B * A);
-  o.barg = c.take<int>((size_t)B * A);
-  return head + c.off;
-}
-
-// carve_loss's layout, then kth [B][N][EFFDET_ATSS_MAX_LEVELS], thr [B][N] -> bytes
-size_t carve_loss_atss(LossK& k, AtssK& t, void* ws, int B, long long A, int num_classes, int N) {
-  const size_t head = carve_loss(k, ws, B, A, num_classes);
-  Carver c(ws ? (char*)ws + head : nullptr);
-  t.kth = c.take<unsigned long long>((size_t)B * N * EFFDET_ATSS_MAX_LEVELS);
-  t.thr = c.take<float>((size_t)B * N);
-  return head + c.off;
-}
-
-// the quality target q [B][A] of a workspace of effdet_loss_quality_workspace_bytes: past the longer of the two matchers' layouts
-// (the same place whichever matcher ran, so the class backward finds it without knowing the matcher) -> bytes
-size_t carve_loss_quality(float*& q, void* ws, int B, long long A, int num_classes, int N) {
-  LossK k{}; OptsK o{}; AtssK t{};
-  const size_t a = carve_loss_opts(k, o, nullptr, B, A, num_classes, N), b = carve_loss_atss(k, t, nullptr, B, A, num_classes, N);
-  const size_t head = a > b ? a : b;
-  Carver c(ws ? (char*)ws + head : nullptr);
-  q = c.take<float>((size_t)B * A);
-  return head + c.off;
-}
-
-// carve_loss_quality's layout (q where the class backward looks for it, whichever matcher ran), then the task-aligned matcher's
-// keys [B][N][EFFDET_TAL_MAX_TOPK], (mmax, umax) [B][N][2] and claims [B][A] -> bytes.  One layout with or without a quality loss.
-size_t carve_loss_tal(LossK& k, TalK& t, void* ws, int B, long long A, int num_classes, int N) {
-  carve_loss(k, ws, B, A, num_classes);
-  float* q = nullptr;
-  const size_t head = carve_loss_quality(q, ws, B, A, num_classes, N);
-  Carver c(ws ? (char*)ws + head : nullptr);
-  t.keys = c.take<unsigned long long>((size_t)B * N * EFFDET_TAL_MAX_TOPK);
-  t.mm = c.take<float>((size_t)B * N * 2);
-  t.slot = c.take<unsigned long long>((size_t)B * A);
-  return head + c.off;
-}
-
 LossK loss_args(const float* cls, const float* reg, const float* anchors, const float* annots, int B, long long A, int nc, int N) {
   LossK k{}; k.cls = cls; k.reg = reg; k.anchors = anchors; k.annots = annots; k.B = B; k.nc = nc; k.N = N; k.A = A;
   return k;
+}
+
+TalK tal_args(const effdet_tal_t* tal) {
+  TalK t{}; t.topk = tal->topk; t.alpha = tal->alpha; t.beta = tal->beta;
+  return t;
+}
+
+// the assign path of a call: the reference's single pass, the bands of the options, ATSS, the task-aligned matcher
+enum { MATCH_DEFAULT = 0, MATCH_BANDS, MATCH_ATSS, MATCH_TAL };
+
+// What every loss entry point receives.  k holds what the CALLER fills of the kernels' arguments: the tensors, losses, dcls / dld,
+// dreg / reg_ld, gscale, B, A, nc, N (a backward call leaves what it does not take null / 0); the drivers carve the rest.
+struct LossCall {
+  LossK k;
+  const void* ws; long long ws_bytes;  // (the backward calls take no byte count)
+  hipStream_t st;
+  bool grad; int dtype;                // forward: also d(cls) into k.dcls, pixel-major; the dtype of k.dcls / k.dreg
+  int matcher;                         // MATCH_*: which of opts / atss / tal the entry point REQUIRES (a null one is refused)
+  const effdet_loss_opts_t* opts;      // null (MATCH_DEFAULT only): the reference's constants -- FocalDefault, KneeDefault, loss_assign_kernel
+  const effdet_atss_t* atss; const effdet_tal_t* tal;
+  const effdet_quality_loss_t* ql;     // the quality loss in the place of the focal term (include/effdet_quality_loss.h), or null
+  bool need_ql;                        // the effdet_loss_quality_* calls: a null ql is refused
+  bool box; int box_kind; float box_weight;      // the stand-alone box term of the effdet_box_loss_* calls
+};
+
+// the box term of a call: the stand-alone one, else the options' -> kind (0: smooth-L1) and its weight
+inline int box_term(const LossCall& c, float& weight) {
+  weight = c.box ? c.box_weight : c.opts ? c.opts->box_weight : 1.0f;
+  return c.box ? c.box_kind : c.opts ? c.opts->box_kind : 0;
+}
+
+// the buffers of a workspace beyond LossK's: between the passes of the three matchers, and the quality target
+struct LossBufs { OptsK o; AtssK t; TalK tal; float* q; };
+
+// THE workspace rule: (matcher, quality loss or not; k.B, k.A, k.nc, k.N) -> the bytes a forward call needs, and with ws the carved
+// pointers.  The five *_workspace_bytes exports and every driver come here.
+//   every call     assign [B][A], stat [B][SS], part_reg [B][na], part_cls [B][cls_blocks_max] (num_classes only sizes this last
+//                  buffer: a backward call or the box term, which know no class count, find the first three where the forward left them)
+//   bands          then gtmax [B][N], best [B][A], barg [B][A]
+//   ATSS           in their place kth [B][N][EFFDET_ATSS_MAX_LEVELS], thr [B][N]
+//   quality loss   the target q [B][A] past the LONGER of the two matchers' layouts: the same place whichever matcher ran, so the
+//                  class backward finds it without knowing the matcher
+//   task-aligned   the quality layout (q where the class backward looks for it; one layout with or without a quality loss), then keys
+//                  [B][N][EFFDET_TAL_MAX_TOPK], (mmax, umax) [B][N][2] and claims [B][A]
+size_t loss_workspace(LossK& k, LossBufs& w, const void* ws, int matcher, bool quality) {
+  const int B = k.B, N = k.N; const long long A = k.A;
+  Carver c(const_cast<void*>(ws));
+  k.assign = c.take<int>((size_t)B * A);
+  k.stat = c.take<float>((size_t)B * SS);
+  k.part_reg = c.take<float>((size_t)B * assign_blocks(A));
+  k.part_cls = c.take<float>((size_t)B * cls_blocks_max(A, k.nc));
+  k.na = (int)assign_blocks(A);
+  if (matcher == MATCH_DEFAULT) return c.off;
+  const size_t head = c.off;
+  w.o.gtmax = c.take<int>((size_t)B * N);
+  w.o.best = c.take<float>((size_t)B * A);
+  w.o.barg = c.take<int>((size_t)B * A);
+  const size_t bands = c.off;
+  if (matcher == MATCH_BANDS && !quality) return bands;
+  c.off = head;
+  w.t.kth = c.take<unsigned long long>((size_t)B * N * EFFDET_ATSS_MAX_LEVELS);
+  w.t.thr = c.take<float>((size_t)B * N);
+  if (matcher == MATCH_ATSS && !quality) return c.off;
+  if (c.off < bands) c.off = bands;
+  float* q = c.take<float>((size_t)B * A);
+  w.q = quality ? q : nullptr;
+  if (matcher != MATCH_TAL) return c.off;
+  w.tal.keys = c.take<unsigned long long>((size_t)B * N * EFFDET_TAL_MAX_TOPK);
+  w.tal.mm = c.take<float>((size_t)B * N * 2);
+  w.tal.slot = c.take<unsigned long long>((size_t)B * A);
+  return c.off;
+}
+
+// ... the part every call has, alone: what a backward call and the box term need
+void loss_workspace(LossK& k, const void* ws) { LossBufs w{}; loss_workspace(k, w, ws, MATCH_DEFAULT, false); }
+
+// a *_workspace_bytes export
+long long loss_workspace_bytes(int matcher, bool quality, int B, long long A, int num_classes, int N) {
+  LossK k = loss_args(nullptr, nullptr, nullptr, nullptr, B, A, num_classes, N); LossBufs w{};
+  return (long long)loss_workspace(k, w, nullptr, matcher, quality);
 }
 
 // ---- argument checks, each written once.  Every entry point makes all its EFFDET_EINVAL checks before the first
@@ -1253,227 +1281,204 @@ inline void by_dtype(int dtype, Fn&& fn) {
 }
 
 // ---- drivers
-// Every forward entry point.  assign(k): carves the workspace into k and enqueues the zero and assign kernels of its path.  Then the
-// class pass (grad: forward + gradient into k.dcls, pixel-major) and the final reduction.
-template <typename F, typename Assign>
-int loss_forward(LossK k, const F f, float reg_weight, const void* workspace, long long workspace_bytes, long long need, bool grad,
-                 int dtype, hipStream_t st, Assign&& assign) {
-  if (!k.cls || !k.reg || !k.anchors || !k.annots || !k.losses || !workspace || (grad && !k.dcls)) return EFFDET_EINVAL;
-  if (workspace_bytes < need || k.B > 65535 || k.N < 1) return EFFDET_EINVAL;
-  if (grad) {
+// Where a call's values become the class policy's type: FocalDefault without options (the reference's constants), FocalP of the
+// options, or with a quality loss (checked by the caller) its soft-target policy reading q, which loss_workspace has placed -> fn(policy)
+template <typename Fn>
+void with_class_policy(const LossCall& c, const float* q, Fn&& fn) {
+  if (!c.opts) return fn(FocalDefault{});
+  if (!c.ql) return fn(FocalP{c.opts->alpha, c.opts->gamma, c.opts->label_smoothing});
+  if (c.ql->kind == EFFDET_QUALITY_QFL) return fn(FocalQfl{c.ql->beta, q});
+  return fn(FocalVfl{c.ql->alpha, c.ql->gamma, q});
+}
+
+// The four assign paths: each zeroes what its passes accumulate into and enqueues its select / assign kernels; k and w are carved.
+int assign_default(const LossK& k, hipStream_t st) {
+  hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((k.B * SS + 255) / 256)), dim3(256), 0, st, k.stat, k.B * SS);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(loss_assign_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+int assign_bands(const LossK& k, OptsK o, const effdet_loss_opts_t* opts, hipStream_t st) {
+  o.pos_iou = opts->pos_iou; o.neg_iou = opts->neg_iou; o.low_quality = opts->low_quality;
+  const int nz = k.B * SS, mz = k.B * k.N;
+  hipLaunchKernelGGL(opts_zero_kernel, dim3((unsigned)((nz + mz + 255) / 256)), dim3(256), 0, st, k.stat, nz, o.gtmax, mz);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(opts_iou_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k, o);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(opts_assign_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k, o, KneeBeta{opts->beta});
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+int assign_atss(const LossK& k, AtssK t, const effdet_atss_t* atss, KneeBeta knee, hipStream_t st) {
+  t.topk = atss->topk; t.num_levels = atss->num_levels;      // (A < 2^31 has been checked: an index within a level fits the low half of a key)
+  for (int l = 0; l <= atss->num_levels; ++l) t.ls[l] = atss->level_start[l];
+  hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((k.B * SS + 255) / 256)), dim3(256), 0, st, k.stat, k.B * SS);
+  EFFDET_CHECK_LAUNCH();
+  if (t.topk <= 9) hipLaunchKernelGGL(atss_select_kernel<9>, dim3((unsigned)k.N, k.B), dim3(256), 0, st, k, t);
+  else hipLaunchKernelGGL(atss_select_kernel<EFFDET_ATSS_MAX_TOPK>, dim3((unsigned)k.N, k.B), dim3(256), 0, st, k, t);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(atss_assign_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k, t, knee);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+int assign_tal(const LossK& k, const TalK& t, KneeBeta knee, hipStream_t st) {      // (A < 2^31 has been checked: an anchor index fits the low half of a key)
+  const long long ns = (long long)k.B * SS, nk = (long long)k.B * k.N * EFFDET_TAL_MAX_TOPK, na = (long long)k.B * k.A;
+  hipLaunchKernelGGL(tal_zero_kernel, dim3(grid_for(ns + nk + nk / EFFDET_TAL_MAX_TOPK * 2 + na)), dim3(256), 0, st, k.stat, ns, t, nk, na);
+  EFFDET_CHECK_LAUNCH();
+  if (t.topk <= 13) hipLaunchKernelGGL(tal_select_kernel<13>, dim3((unsigned)k.N, k.B), dim3(256), 0, st, k, t);
+  else hipLaunchKernelGGL(tal_select_kernel<EFFDET_TAL_MAX_TOPK>, dim3((unsigned)k.N, k.B), dim3(256), 0, st, k, t);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(tal_assign_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k, t, knee);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// after the forward kernels have been enqueued with an IoU-family box term: the per-workgroup partials over their assignment, then
+// losses[1]
+int box_loss_finish(const LossCall& c, int kind, float weight) {
+  LossK k = loss_args(nullptr, c.k.reg, c.k.anchors, c.k.annots, c.k.B, c.k.A, 0, c.k.N); k.losses = c.k.losses;
+  loss_workspace(k, c.ws);
+  hipLaunchKernelGGL(box_loss_fwd_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, c.st, k, kind);
+  EFFDET_CHECK_LAUNCH();
+  hipLaunchKernelGGL(box_loss_final_kernel, dim3(1), dim3(1024), 0, c.st, k, weight);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// Every forward entry point (c.grad: the _fwd_grad ones).  The entry point's own EINVAL checks, the shared ones, the EUNSUPPORTED
+// one; then the matcher's assign path, with a quality loss q for the class pass (and the task-aligned target behind it), the class
+// pass (grad: forward + gradient into k.dcls, pixel-major), the final reduction, and with a box kind its term over the same assignment.
+int loss_forward(const LossCall& c) {
+  LossK k = c.k;
+  const effdet_loss_opts_t* o = c.opts;
+  hipStream_t st = c.st;
+  if (c.box && !box_loss_args_ok(c.box_kind, c.box_weight)) return EFFDET_EINVAL;
+  if ((c.need_ql || c.ql) && !quality_ok(c.ql)) return EFFDET_EINVAL;
+  if (c.matcher != MATCH_DEFAULT) {               // (the default calls check neither B < 1 nor A, num_classes)
+    if (!loss_opts_ok(o) || k.B < 1 || k.N < 1 || k.A < 1 || k.nc < 1) return EFFDET_EINVAL;
+    if (c.matcher != MATCH_BANDS && o->low_quality != 0) return EFFDET_EINVAL;      // a matcher replaces the bands and their promotion
+    if (c.matcher == MATCH_ATSS && !atss_ok(c.atss, k.A)) return EFFDET_EINVAL;
+    if (c.matcher == MATCH_TAL && !tal_ok(c.tal)) return EFFDET_EINVAL;
+  }
+  LossBufs w{};
+  if (c.matcher == MATCH_TAL) w.tal = tal_args(c.tal);
+  const long long need = (long long)loss_workspace(k, w, c.ws, c.matcher, c.ql != nullptr);
+  if (!k.cls || !k.reg || !k.anchors || !k.annots || !k.losses || !c.ws || (c.grad && !k.dcls)) return EFFDET_EINVAL;
+  if (c.ws_bytes < need || k.B > 65535 || k.N < 1) return EFFDET_EINVAL;
+  if (c.grad) {
     if (k.dld <= 0) return EFFDET_EINVAL;
-    if (const int rc = check_dcls(k.dcls, k.dld, dtype, true, k.A, k.nc)) return rc;
+    if (const int rc = check_dcls(k.dcls, k.dld, c.dtype, true, k.A, k.nc)) return rc;
   }
   if (k.A * k.nc >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
-  if (const int rc = assign(k)) return rc;
-  const long long groups = grad ? (k.A / 9) * k.dld / 4 : (k.A * k.nc + 3) / 4;
-  const int it = grad ? FG_IT : CLS_IT;
+
+  int rc = EFFDET_OK;
+  if (c.matcher == MATCH_DEFAULT) rc = assign_default(k, st);
+  else if (c.matcher == MATCH_BANDS) rc = assign_bands(k, w.o, o, st);
+  else if (c.matcher == MATCH_ATSS) rc = assign_atss(k, w.t, c.atss, KneeBeta{o->beta}, st);
+  else rc = assign_tal(k, w.tal, KneeBeta{o->beta}, st);
+  if (rc != EFFDET_OK) return rc;
+  if (w.q) {                                      // after whichever assign pass ran: q for the class pass
+    hipLaunchKernelGGL(loss_quality_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k, w.q);
+    EFFDET_CHECK_LAUNCH();
+    if (c.matcher == MATCH_TAL && c.tal->aligned_target) {
+      hipLaunchKernelGGL(tal_target_kernel, dim3((unsigned)k.N, k.B), dim3(64), 0, st, k, w.tal, w.q);
+      EFFDET_CHECK_LAUNCH();
+    }
+  }
+  const long long groups = c.grad ? (k.A / 9) * k.dld / 4 : (k.A * k.nc + 3) / 4;
+  const int it = c.grad ? FG_IT : CLS_IT;
   k.ncb = (int)((groups + 256 * it - 1) / (256 * it));
   if (k.ncb > cls_blocks_max(k.A, k.nc)) return EFFDET_EINVAL;
   const dim3 g1((unsigned)k.ncb, k.B);
-  if (grad) by_dtype<true>(dtype, [&](auto t) {
-    hipLaunchKernelGGL((loss_cls_pix_kernel<typename decltype(t)::type, F, false, FG_IT>), g1, dim3(256), 0, st, k, f);
+  with_class_policy(c, w.q, [&](auto f) {
+    using F = decltype(f);
+    if (c.grad) by_dtype<true>(c.dtype, [&](auto t) {
+      hipLaunchKernelGGL((loss_cls_pix_kernel<typename decltype(t)::type, F, false, FG_IT>), g1, dim3(256), 0, st, k, f);
+    });
+    else hipLaunchKernelGGL(loss_cls_kernel<F>, g1, dim3(256), 0, st, k, f);
   });
-  else hipLaunchKernelGGL(loss_cls_kernel<F>, g1, dim3(256), 0, st, k, f);
   EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, st, k, reg_weight);
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, st, k, o ? o->reg_weight : 1.0f);
   EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
+  float weight;
+  const int kind = box_term(c, weight);
+  return kind ? box_loss_finish(c, kind, weight) : EFFDET_OK;
 }
 
-int loss_forward_default(const LossK& k0, void* workspace, long long workspace_bytes, bool grad, int dtype, effdet_stream_t stream) {
-  hipStream_t st = (hipStream_t)stream;
-  return loss_forward(k0, FocalDefault{}, 1.0f, workspace, workspace_bytes, effdet_loss_workspace_bytes(k0.B, k0.A, k0.nc), grad, dtype,
-                      st, [&](LossK& k) -> int {
-    carve_loss(k, workspace, k.B, k.A);
-    hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((k.B * SS + 255) / 256)), dim3(256), 0, st, k.stat, k.B * SS);
-    EFFDET_CHECK_LAUNCH();
-    hipLaunchKernelGGL(loss_assign_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k);
-    EFFDET_CHECK_LAUNCH();
-    return EFFDET_OK;
-  });
-}
-
-// after a forward driver has been enqueued with an IoU-family box term: the per-workgroup partials over its assignment, then losses[1]
-int box_loss_finish(const float* reg, const float* anchors, const float* annots, float* losses, void* workspace, int B, long long A,
-                    int N, int kind, float weight, hipStream_t st) {
-  LossK k = loss_args(nullptr, reg, anchors, annots, B, A, 0, N); k.losses = losses;
-  carve_loss(k, workspace, B, A);
-  hipLaunchKernelGGL(box_loss_fwd_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, kind);
-  EFFDET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(box_loss_final_kernel, dim3(1), dim3(1024), 0, st, k, weight);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-// The class policy of a forward call: FocalP of the options, or with a quality loss (checked by the caller) its soft-target policy
-// reading q, which then lies in a workspace of effdet_loss_quality_workspace_bytes.  -> fn(policy, q, bytes needed); q == nullptr:
-// no quality pass
-template <typename Fn>
-int with_class_policy(const effdet_loss_opts_t* opts, const effdet_quality_loss_t* ql, void* workspace, int B, long long A,
-                      int num_classes, int N, long long plain_bytes, Fn&& fn) {
-  if (!ql) return fn(FocalP{opts->alpha, opts->gamma, opts->label_smoothing}, (float*)nullptr, plain_bytes);
-  float* q = nullptr;
-  const long long need = (long long)carve_loss_quality(q, workspace, B, A, num_classes, N);
-  if (ql->kind == EFFDET_QUALITY_QFL) return fn(FocalQfl{ql->beta, q}, q, need);
-  return fn(FocalVfl{ql->alpha, ql->gamma, q}, q, need);
-}
-
-// after the assign pass of a forward call with a quality loss: q for the class pass
-int launch_quality(const LossK& k, float* q, hipStream_t st) {
-  hipLaunchKernelGGL(loss_quality_kernel, dim3((unsigned)k.na, k.B), dim3(256), 0, st, k, q);
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
-}
-
-// both forward entry points of the options: dcls_pix == nullptr is effdet_loss_opts_fwd.  ql: null, or the quality loss in the place
-// of the focal term (include/effdet_quality_loss.h)
-int loss_opts_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
-                      long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
-                      int N, const effdet_loss_opts_t* opts, effdet_stream_t stream, const effdet_quality_loss_t* ql = nullptr) {
-  if (!loss_opts_ok(opts) || B < 1 || N < 1 || A < 1 || num_classes < 1) return EFFDET_EINVAL;
-  LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = with_class_policy(opts, ql, workspace, B, A, num_classes, N, effdet_loss_opts_workspace_bytes(B, A, num_classes, N),
-                                   [&](auto f, float* q, long long need) -> int {
-   return loss_forward(k0, f, opts->reg_weight, workspace, workspace_bytes, need, grad, dtype, st, [&](LossK& k) -> int {
-    OptsK o{opts->pos_iou, opts->neg_iou, opts->low_quality};
-    carve_loss_opts(k, o, workspace, B, A, num_classes, N);
-    const int nz = B * SS, mz = B * N;
-    hipLaunchKernelGGL(opts_zero_kernel, dim3((unsigned)((nz + mz + 255) / 256)), dim3(256), 0, st, k.stat, nz, o.gtmax, mz);
-    EFFDET_CHECK_LAUNCH();
-    hipLaunchKernelGGL(opts_iou_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o);
-    EFFDET_CHECK_LAUNCH();
-    hipLaunchKernelGGL(opts_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, o, KneeBeta{opts->beta});
-    EFFDET_CHECK_LAUNCH();
-    return q ? launch_quality(k, q, st) : EFFDET_OK;
-   });
-  });
-  if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
-  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
-}
-
-// both forward entry points of the ATSS matcher: loss_opts_forward with the ATSS assign path
-int loss_atss_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
-                      long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
-                      int N, const effdet_loss_opts_t* opts, const effdet_atss_t* atss, effdet_stream_t stream,
-                      const effdet_quality_loss_t* ql = nullptr) {
-  if (!loss_opts_ok(opts) || opts->low_quality != 0 || B < 1 || N < 1 || A < 1 || num_classes < 1 || !atss_ok(atss, A)) return EFFDET_EINVAL;
-  LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = with_class_policy(opts, ql, workspace, B, A, num_classes, N, effdet_loss_atss_workspace_bytes(B, A, num_classes, N, atss),
-                                   [&](auto f, float* q, long long need) -> int {
-   return loss_forward(k0, f, opts->reg_weight, workspace, workspace_bytes, need, grad, dtype, st, [&](LossK& k) -> int {
-    AtssK t{}; t.topk = atss->topk; t.num_levels = atss->num_levels;      // (A < 2^31 has been checked: an index within a level fits the low half of a key)
-    for (int l = 0; l <= atss->num_levels; ++l) t.ls[l] = atss->level_start[l];
-    carve_loss_atss(k, t, workspace, B, A, num_classes, N);
-    hipLaunchKernelGGL(loss_zero_stat_kernel, dim3((unsigned)((B * SS + 255) / 256)), dim3(256), 0, st, k.stat, B * SS);
-    EFFDET_CHECK_LAUNCH();
-    if (t.topk <= 9) hipLaunchKernelGGL(atss_select_kernel<9>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
-    else hipLaunchKernelGGL(atss_select_kernel<EFFDET_ATSS_MAX_TOPK>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
-    EFFDET_CHECK_LAUNCH();
-    hipLaunchKernelGGL(atss_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, t, KneeBeta{opts->beta});
-    EFFDET_CHECK_LAUNCH();
-    return q ? launch_quality(k, q, st) : EFFDET_OK;
-   });
-  });
-  if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
-  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
-}
-
-TalK tal_args(const effdet_tal_t* tal) {
-  TalK t{}; t.topk = tal->topk; t.alpha = tal->alpha; t.beta = tal->beta;
-  return t;
-}
-
-// both forward entry points of the task-aligned matcher: loss_atss_forward with its assign path, and with a quality loss and
-// aligned_target the target pass behind the quality pass
-int loss_tal_forward(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses, void* workspace,
-                     long long workspace_bytes, void* dcls_pix, int dld, int dtype, bool grad, int B, long long A, int num_classes,
-                     int N, const effdet_loss_opts_t* opts, const effdet_tal_t* tal, const effdet_quality_loss_t* ql,
-                     effdet_stream_t stream) {
-  if (!loss_opts_ok(opts) || opts->low_quality != 0 || B < 1 || N < 1 || A < 1 || num_classes < 1 || !tal_ok(tal)) return EFFDET_EINVAL;
-  if (ql && !quality_ok(ql)) return EFFDET_EINVAL;
-  LossK k0 = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k0.losses = losses; k0.dcls = dcls_pix; k0.dld = dld;
-  hipStream_t st = (hipStream_t)stream;
-  const long long need = effdet_loss_tal_workspace_bytes(B, A, num_classes, N, tal);
-  const int rc = with_class_policy(opts, ql, workspace, B, A, num_classes, N, need, [&](auto f, float* q, long long) -> int {
-   return loss_forward(k0, f, opts->reg_weight, workspace, workspace_bytes, need, grad, dtype, st, [&](LossK& k) -> int {
-    TalK t = tal_args(tal);                                  // (A < 2^31 has been checked: an anchor index fits the low half of a key)
-    carve_loss_tal(k, t, workspace, B, A, num_classes, N);
-    const long long ns = (long long)B * SS, nk = (long long)B * N * EFFDET_TAL_MAX_TOPK, na = (long long)B * A;
-    hipLaunchKernelGGL(tal_zero_kernel, dim3(grid_for(ns + nk + nk / EFFDET_TAL_MAX_TOPK * 2 + na)), dim3(256), 0, st, k.stat, ns, t, nk, na);
-    EFFDET_CHECK_LAUNCH();
-    if (t.topk <= 13) hipLaunchKernelGGL(tal_select_kernel<13>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
-    else hipLaunchKernelGGL(tal_select_kernel<EFFDET_TAL_MAX_TOPK>, dim3((unsigned)N, B), dim3(256), 0, st, k, t);
-    EFFDET_CHECK_LAUNCH();
-    hipLaunchKernelGGL(tal_assign_kernel, dim3((unsigned)k.na, B), dim3(256), 0, st, k, t, KneeBeta{opts->beta});
-    EFFDET_CHECK_LAUNCH();
-    if (!q) return EFFDET_OK;
-    if (const int rq = launch_quality(k, q, st)) return rq;
-    if (tal->aligned_target) {
-      hipLaunchKernelGGL(tal_target_kernel, dim3((unsigned)N, B), dim3(64), 0, st, k, t, q);
-      EFFDET_CHECK_LAUNCH();
-    }
-    return EFFDET_OK;
-   });
-  });
-  if (rc != EFFDET_OK || opts->box_kind == 0) return rc;
-  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, opts->box_kind, opts->box_weight, st);
-}
-
-// d(logits) into k.dcls, flat or (k.dld) pixel-major, with the upstream gradient applied.  No launch check: the caller's follows.
-template <typename F>
-void launch_bwd_cls(const LossK& k, const F f, int dtype, hipStream_t st) {
+// d(logits) of the call's class policy into k.dcls, flat or (k.dld) pixel-major, with the upstream gradient applied.  No launch check:
+// the caller's follows.
+void launch_bwd_cls(const LossK& k, const LossCall& c, const float* q) {
   const long long groups = k.dld ? (k.A / 9) * k.dld / 4 : (k.A * k.nc + 3) / 4;
   const dim3 g1((unsigned)((groups + 255) / 256), k.B);
-  by_dtype<false>(dtype, [&](auto t) {
+  with_class_policy(c, q, [&](auto f) {
+    using F = decltype(f);
+    by_dtype<false>(c.dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      if (k.dld) hipLaunchKernelGGL((loss_cls_pix_kernel<T, F, true, 1>), g1, dim3(256), 0, c.st, k, f);
+      else hipLaunchKernelGGL((loss_bwd_cls_kernel<T, F>), g1, dim3(256), 0, c.st, k, f);
+    });
+  });
+}
+
+// d(reg) of the call's box term into k.dreg: the box kernel of an IoU kind, else smooth-L1 with the options' knee or the reference's
+void launch_bwd_reg(const LossK& k, const LossCall& c) {
+  float weight;
+  const int kind = box_term(c, weight);
+  const dim3 g(grid_for((long long)k.B * k.A));
+  by_dtype<true>(c.dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    if (k.dld) hipLaunchKernelGGL((loss_cls_pix_kernel<T, F, true, 1>), g1, dim3(256), 0, st, k, f);
-    else hipLaunchKernelGGL((loss_bwd_cls_kernel<T, F>), g1, dim3(256), 0, st, k, f);
+    if (kind) hipLaunchKernelGGL(box_loss_bwd_reg_kernel<T>, g, dim3(256), 0, c.st, k, kind, weight);
+    else if (c.opts) hipLaunchKernelGGL((loss_bwd_reg_kernel<T, KneeBeta>), g, dim3(256), 0, c.st, k, KneeBeta{c.opts->beta}, c.opts->reg_weight);
+    else hipLaunchKernelGGL((loss_bwd_reg_kernel<T, KneeDefault>), g, dim3(256), 0, c.st, k, KneeDefault{}, 1.0f);
   });
 }
 
-template <typename Knee>
-void launch_bwd_reg(const LossK& k, const Knee knee, float reg_weight, int dtype, hipStream_t st) {
-  by_dtype<true>(dtype, [&](auto t) {
-    hipLaunchKernelGGL((loss_bwd_reg_kernel<typename decltype(t)::type, Knee>), dim3(grid_for((long long)k.B * k.A)), dim3(256), 0, st, k,
-                       knee, reg_weight);
-  });
-}
-
-int loss_bwd(const float* cls, const float* reg, const float* anchors, const float* annots, const float* gscale,
-             const void* workspace, void* dcls_logit, int dld, void* dreg, int dtype, int B, long long A, int num_classes,
-             int N, effdet_stream_t stream) {
-  if (!cls || !reg || !anchors || !annots || !gscale || !workspace || !dcls_logit || !dreg) return EFFDET_EINVAL;
-  if (const int rc = check_dcls(dcls_logit, dld, dtype, false, A, num_classes)) return rc;
-  LossK k = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k.gscale = gscale; k.dcls = dcls_logit; k.dreg = dreg; k.dld = dld;
-  carve_loss(k, const_cast<void*>(workspace), B, A);
-  launch_bwd_cls(k, FocalDefault{}, dtype, (hipStream_t)stream);
-  launch_bwd_reg(k, KneeDefault{}, 1.0f, dtype, (hipStream_t)stream);
+// the reference's combined backward: d(logits) and the smooth-L1 d(reg) [B][A][4] of the default forward
+int loss_bwd(const LossCall& c) {
+  LossK k = c.k;
+  if (!k.cls || !k.reg || !k.anchors || !k.annots || !k.gscale || !c.ws || !k.dcls || !k.dreg) return EFFDET_EINVAL;
+  if (const int rc = check_dcls(k.dcls, k.dld, c.dtype, false, k.A, k.nc)) return rc;
+  loss_workspace(k, c.ws);
+  launch_bwd_cls(k, c, nullptr);
+  launch_bwd_reg(k, c);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
 
-// every d(reg) entry point: launch(k, st) enqueues its kernel
-template <typename Launch>
-int loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale, const void* workspace, void* dreg,
-                 int reg_ld, int dtype, int B, long long A, int N, effdet_stream_t stream, Launch&& launch) {
-  if (!reg || !anchors || !annots || !gscale || !workspace || !dreg) return EFFDET_EINVAL;
-  if (const int rc = check_dreg(dreg, reg_ld, dtype, A)) return rc;
-  LossK k = loss_args(nullptr, reg, anchors, annots, B, A, 0, N); k.gscale = gscale; k.dreg = dreg; k.reg_ld = reg_ld;
-  carve_loss(k, const_cast<void*>(workspace), B, A);
-  launch(k, (hipStream_t)stream);
+// the class backward of the options, and with ql of a quality loss (q: where loss_workspace says the forward call left it)
+int loss_bwd_cls(const LossCall& c) {
+  LossK k = c.k;
+  if (c.need_ql && !quality_ok(c.ql)) return EFFDET_EINVAL;
+  if (!k.cls || !k.annots || !k.gscale || !c.ws || !k.dcls) return EFFDET_EINVAL;
+  if (!loss_opts_ok(c.opts) || k.B < 1 || k.B > 65535 || k.N < 1 || k.A < 1 || k.nc < 1 || k.dld < 0) return EFFDET_EINVAL;
+  if (const int rc = check_dcls(k.dcls, k.dld, c.dtype, false, k.A, k.nc)) return rc;
+  if (k.A * k.nc >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
+  LossBufs w{};
+  loss_workspace(k, w, c.ws, c.ql ? MATCH_BANDS : MATCH_DEFAULT, c.ql != nullptr);
+  launch_bwd_cls(k, c, w.q);
+  EFFDET_CHECK_LAUNCH();
+  return EFFDET_OK;
+}
+
+// every d(reg) entry point.  With a box kind in the options the call is the stand-alone box call: B, N, A are not checked.
+int loss_bwd_reg(const LossCall& c) {
+  LossK k = c.k;
+  if (c.box && !box_loss_args_ok(c.box_kind, c.box_weight)) return EFFDET_EINVAL;
+  if (c.matcher != MATCH_DEFAULT && !loss_opts_ok(c.opts)) return EFFDET_EINVAL;
+  if (c.opts && c.opts->box_kind == 0 && (k.B < 1 || k.N < 1 || k.A < 1)) return EFFDET_EINVAL;
+  if (!k.reg || !k.anchors || !k.annots || !k.gscale || !c.ws || !k.dreg) return EFFDET_EINVAL;
+  if (const int rc = check_dreg(k.dreg, k.reg_ld, c.dtype, k.A)) return rc;
+  loss_workspace(k, c.ws);
+  launch_bwd_reg(k, c);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
 }
 
 }  // namespace
-
-extern "C" long long effdet_loss_workspace_bytes(int B, long long A, int num_classes) {
-  LossK k{};
-  return (long long)carve_loss(k, nullptr, B, A, num_classes);
-}
 
 extern "C" int effdet_positive_pixel_map(const float* anchors, const float* annots, int B, long long A, int N, int nlev, const int* H,
                                          const int* W, unsigned char* map, effdet_stream_t stream) {
@@ -1499,206 +1504,191 @@ extern "C" int effdet_positive_pixel_map(const float* anchors, const float* anno
   return EFFDET_OK;
 }
 
+// ---- the loss entry points: each fills the record and makes one call
+extern "C" long long effdet_loss_workspace_bytes(int B, long long A, int num_classes) {
+  return loss_workspace_bytes(MATCH_DEFAULT, false, B, A, num_classes, 0);
+}
+
 extern "C" long long effdet_loss_opts_workspace_bytes(int B, long long A, int num_classes, int N) {
-  LossK k{}; OptsK o{};
-  return (long long)carve_loss_opts(k, o, nullptr, B, A, num_classes, N);
+  return loss_workspace_bytes(MATCH_BANDS, false, B, A, num_classes, N);
+}
+
+extern "C" long long effdet_loss_atss_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_atss_t* atss) {
+  return atss_ok(atss, A) ? loss_workspace_bytes(MATCH_ATSS, false, B, A, num_classes, N) : EFFDET_EINVAL;
+}
+
+extern "C" long long effdet_loss_quality_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_atss_t* atss) {
+  return !atss || atss_ok(atss, A) ? loss_workspace_bytes(MATCH_BANDS, true, B, A, num_classes, N) : EFFDET_EINVAL;
+}
+
+extern "C" long long effdet_loss_tal_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_tal_t* tal) {
+  return tal_ok(tal) ? loss_workspace_bytes(MATCH_TAL, false, B, A, num_classes, N) : EFFDET_EINVAL;
 }
 
 extern "C" int effdet_focal_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots,
                                      float* losses, void* workspace, long long workspace_bytes, int B, long long A,
                                      int num_classes, int N, effdet_stream_t stream) {
-  LossK k = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k.losses = losses;
-  return loss_forward_default(k, workspace, workspace_bytes, false, EFFDET_F32, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_focal_loss_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots,
                                           float* losses, void* workspace, long long workspace_bytes, void* dcls_pix, int dld,
                                           int dtype, int B, long long A, int num_classes, int N, effdet_stream_t stream) {
-  LossK k = loss_args(cls, reg, anchors, annots, B, A, num_classes, N); k.losses = losses; k.dcls = dcls_pix; k.dld = dld;
-  return loss_forward_default(k, workspace, workspace_bytes, true, dtype, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.k.dcls = dcls_pix; c.k.dld = dld; c.dtype = dtype; c.grad = true;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_focal_loss_bwd(const float* cls, const float* reg, const float* anchors, const float* annots,
                                      const float* gscale, const void* workspace, void* dcls_logit, void* dreg, int dtype,
                                      int B, long long A, int num_classes, int N, effdet_stream_t stream) {
-  return loss_bwd(cls, reg, anchors, annots, gscale, workspace, dcls_logit, 0, dreg, dtype, B, A, num_classes, N, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, 0, (hipStream_t)stream};
+  c.k.gscale = gscale; c.dtype = dtype; c.k.dcls = dcls_logit; c.k.dreg = dreg;
+  return loss_bwd(c);
 }
 
 extern "C" int effdet_focal_loss_bwd_pix(const float* cls, const float* reg, const float* anchors, const float* annots,
                                          const float* gscale, const void* workspace, void* dcls_pix, int dld, void* dreg,
                                          int dtype, int B, long long A, int num_classes, int N, effdet_stream_t stream) {
   if (dld <= 0) return EFFDET_EINVAL;
-  return loss_bwd(cls, reg, anchors, annots, gscale, workspace, dcls_pix, dld, dreg, dtype, B, A, num_classes, N, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, 0, (hipStream_t)stream};
+  c.k.gscale = gscale; c.dtype = dtype; c.k.dcls = dcls_pix; c.k.dld = dld; c.k.dreg = dreg;
+  return loss_bwd(c);
 }
 
 extern "C" int effdet_focal_loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
                                          const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N,
                                          effdet_stream_t stream) {
-  return loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, stream,
-                      [&](const LossK& k, hipStream_t st) { launch_bwd_reg(k, KneeDefault{}, 1.0f, dtype, st); });
+  LossCall c{loss_args(nullptr, reg, anchors, annots, B, A, 0, N), workspace, 0, (hipStream_t)stream};
+  c.k.gscale = gscale; c.dtype = dtype; c.k.dreg = dreg; c.k.reg_ld = reg_ld;
+  return loss_bwd_reg(c);
 }
 
 extern "C" int effdet_box_loss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                    void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N, int kind,
                                    float weight, effdet_stream_t stream) {
-  if (!box_loss_args_ok(kind, weight)) return EFFDET_EINVAL;
-  const int rc = effdet_focal_loss_fwd(cls, reg, anchors, annots, losses, workspace, workspace_bytes, B, A, num_classes, N, stream);
-  if (rc != EFFDET_OK) return rc;
-  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, kind, weight, (hipStream_t)stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.box = true; c.box_kind = kind; c.box_weight = weight;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_box_loss_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                         void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
                                         long long A, int num_classes, int N, int kind, float weight, effdet_stream_t stream) {
-  if (!box_loss_args_ok(kind, weight)) return EFFDET_EINVAL;
-  const int rc = effdet_focal_loss_fwd_grad(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, B, A,
-                                            num_classes, N, stream);
-  if (rc != EFFDET_OK) return rc;
-  return box_loss_finish(reg, anchors, annots, losses, workspace, B, A, N, kind, weight, (hipStream_t)stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.k.dcls = dcls_pix; c.k.dld = dld; c.dtype = dtype; c.grad = true;
+  c.box = true; c.box_kind = kind; c.box_weight = weight;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_box_loss_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
                                        const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N, int kind,
                                        float weight, effdet_stream_t stream) {
-  if (!box_loss_args_ok(kind, weight)) return EFFDET_EINVAL;
-  return loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, stream, [&](const LossK& k, hipStream_t st) {
-    by_dtype<true>(dtype, [&](auto t) {
-      hipLaunchKernelGGL(box_loss_bwd_reg_kernel<typename decltype(t)::type>, dim3(grid_for((long long)B * A)), dim3(256), 0, st, k, kind,
-                         weight);
-    });
-  });
+  LossCall c{loss_args(nullptr, reg, anchors, annots, B, A, 0, N), workspace, 0, (hipStream_t)stream};
+  c.k.gscale = gscale; c.dtype = dtype; c.k.dreg = dreg; c.k.reg_ld = reg_ld;
+  c.box = true; c.box_kind = kind; c.box_weight = weight;
+  return loss_bwd_reg(c);
 }
 
 extern "C" int effdet_loss_opts_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                     void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
                                     const effdet_loss_opts_t* opts, effdet_stream_t stream) {
-  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
-                           num_classes, N, opts, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.matcher = MATCH_BANDS; c.opts = opts;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_loss_opts_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                          void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
                                          long long A, int num_classes, int N, const effdet_loss_opts_t* opts, effdet_stream_t stream) {
-  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
-                           num_classes, N, opts, stream);
-}
-
-// the class backward of the options, and with ql of a quality loss
-int loss_opts_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls, int dld, int dtype,
-                      int B, long long A, int num_classes, int N, const effdet_loss_opts_t* opts, const effdet_quality_loss_t* ql,
-                      effdet_stream_t stream) {
-  if (!cls || !annots || !gscale || !workspace || !dcls) return EFFDET_EINVAL;
-  if (!loss_opts_ok(opts) || B < 1 || B > 65535 || N < 1 || A < 1 || num_classes < 1 || dld < 0) return EFFDET_EINVAL;
-  if (const int rc = check_dcls(dcls, dld, dtype, false, A, num_classes)) return rc;
-  if (A * num_classes >= 0x7fffffffLL) return EFFDET_EUNSUPPORTED;
-  LossK k = loss_args(cls, nullptr, nullptr, annots, B, A, num_classes, N); k.gscale = gscale; k.dcls = dcls; k.dld = dld;
-  carve_loss(k, const_cast<void*>(workspace), B, A);
-  const int rc = with_class_policy(opts, ql, const_cast<void*>(workspace), B, A, num_classes, N, 0, [&](auto f, float*, long long) -> int {
-    launch_bwd_cls(k, f, dtype, (hipStream_t)stream);
-    return EFFDET_OK;
-  });
-  if (rc != EFFDET_OK) return rc;
-  EFFDET_CHECK_LAUNCH();
-  return EFFDET_OK;
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.k.dcls = dcls_pix; c.k.dld = dld; c.dtype = dtype; c.grad = true;
+  c.matcher = MATCH_BANDS; c.opts = opts;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_loss_opts_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls,
                                         int dld, int dtype, int B, long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
                                         effdet_stream_t stream) {
-  return loss_opts_bwd_cls(cls, annots, gscale, workspace, dcls, dld, dtype, B, A, num_classes, N, opts, nullptr, stream);
+  LossCall c{loss_args(cls, nullptr, nullptr, annots, B, A, num_classes, N), workspace, 0, (hipStream_t)stream};
+  c.k.gscale = gscale; c.dtype = dtype; c.k.dcls = dcls; c.k.dld = dld; c.matcher = MATCH_BANDS; c.opts = opts;
+  return loss_bwd_cls(c);
 }
 
 extern "C" int effdet_loss_opts_bwd_reg(const float* reg, const float* anchors, const float* annots, const float* gscale,
                                         const void* workspace, void* dreg, int reg_ld, int dtype, int B, long long A, int N,
                                         const effdet_loss_opts_t* opts, effdet_stream_t stream) {
-  if (!loss_opts_ok(opts)) return EFFDET_EINVAL;
-  if (opts->box_kind != 0)
-    return effdet_box_loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, opts->box_kind,
-                                   opts->box_weight, stream);
-  if (B < 1 || N < 1 || A < 1) return EFFDET_EINVAL;
-  return loss_bwd_reg(reg, anchors, annots, gscale, workspace, dreg, reg_ld, dtype, B, A, N, stream, [&](const LossK& k, hipStream_t st) {
-    launch_bwd_reg(k, KneeBeta{opts->beta}, opts->reg_weight, dtype, st);
-  });
-}
-
-extern "C" long long effdet_loss_atss_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_atss_t* atss) {
-  if (!atss_ok(atss, A)) return EFFDET_EINVAL;
-  LossK k{}; AtssK t{};
-  return (long long)carve_loss_atss(k, t, nullptr, B, A, num_classes, N);
+  LossCall c{loss_args(nullptr, reg, anchors, annots, B, A, 0, N), workspace, 0, (hipStream_t)stream};
+  c.k.gscale = gscale; c.dtype = dtype; c.k.dreg = dreg; c.k.reg_ld = reg_ld; c.matcher = MATCH_BANDS; c.opts = opts;
+  return loss_bwd_reg(c);
 }
 
 extern "C" int effdet_loss_atss_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                     void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
                                     const effdet_loss_opts_t* opts, const effdet_atss_t* atss, effdet_stream_t stream) {
-  return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
-                           num_classes, N, opts, atss, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.matcher = MATCH_ATSS; c.opts = opts; c.atss = atss;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_loss_atss_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                          void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
                                          long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
                                          const effdet_atss_t* atss, effdet_stream_t stream) {
-  return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
-                           num_classes, N, opts, atss, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.k.dcls = dcls_pix; c.k.dld = dld; c.dtype = dtype; c.grad = true;
+  c.matcher = MATCH_ATSS; c.opts = opts; c.atss = atss;
+  return loss_forward(c);
 }
 
-extern "C" long long effdet_loss_quality_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_atss_t* atss) {
-  if (atss && !atss_ok(atss, A)) return EFFDET_EINVAL;
-  float* q = nullptr;
-  return (long long)carve_loss_quality(q, nullptr, B, A, num_classes, N);
-}
-
+// (a null atss: the bands of the options)
 extern "C" int effdet_loss_quality_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                        void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
                                        const effdet_loss_opts_t* opts, const effdet_atss_t* atss, const effdet_quality_loss_t* quality,
                                        effdet_stream_t stream) {
-  if (!quality_ok(quality)) return EFFDET_EINVAL;
-  if (atss)
-    return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
-                             num_classes, N, opts, atss, stream, quality);
-  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
-                           num_classes, N, opts, stream, quality);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.matcher = atss ? MATCH_ATSS : MATCH_BANDS; c.opts = opts; c.atss = atss; c.ql = quality; c.need_ql = true;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_loss_quality_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                             void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
                                             long long A, int num_classes, int N, const effdet_loss_opts_t* opts,
                                             const effdet_atss_t* atss, const effdet_quality_loss_t* quality, effdet_stream_t stream) {
-  if (!quality_ok(quality)) return EFFDET_EINVAL;
-  if (atss)
-    return loss_atss_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
-                             num_classes, N, opts, atss, stream, quality);
-  return loss_opts_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
-                           num_classes, N, opts, stream, quality);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.k.dcls = dcls_pix; c.k.dld = dld; c.dtype = dtype; c.grad = true;
+  c.matcher = atss ? MATCH_ATSS : MATCH_BANDS; c.opts = opts; c.atss = atss; c.ql = quality; c.need_ql = true;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_loss_quality_bwd_cls(const float* cls, const float* annots, const float* gscale, const void* workspace, void* dcls,
                                            int dld, int dtype, int B, long long A, int num_classes, int N,
                                            const effdet_loss_opts_t* opts, const effdet_quality_loss_t* quality, effdet_stream_t stream) {
-  if (!quality_ok(quality)) return EFFDET_EINVAL;
-  return loss_opts_bwd_cls(cls, annots, gscale, workspace, dcls, dld, dtype, B, A, num_classes, N, opts, quality, stream);
-}
-
-extern "C" long long effdet_loss_tal_workspace_bytes(int B, long long A, int num_classes, int N, const effdet_tal_t* tal) {
-  if (!tal_ok(tal)) return EFFDET_EINVAL;
-  LossK k{}; TalK t{};
-  return (long long)carve_loss_tal(k, t, nullptr, B, A, num_classes, N);
+  LossCall c{loss_args(cls, nullptr, nullptr, annots, B, A, num_classes, N), workspace, 0, (hipStream_t)stream};
+  c.k.gscale = gscale; c.dtype = dtype; c.k.dcls = dcls; c.k.dld = dld;
+  c.matcher = MATCH_BANDS; c.opts = opts; c.ql = quality; c.need_ql = true;
+  return loss_bwd_cls(c);
 }
 
 extern "C" int effdet_loss_tal_fwd(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                    void* workspace, long long workspace_bytes, int B, long long A, int num_classes, int N,
                                    const effdet_loss_opts_t* opts, const effdet_tal_t* tal, const effdet_quality_loss_t* quality,
                                    effdet_stream_t stream) {
-  return loss_tal_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, nullptr, 0, EFFDET_F32, false, B, A,
-                          num_classes, N, opts, tal, quality, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.matcher = MATCH_TAL; c.opts = opts; c.tal = tal; c.ql = quality;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_loss_tal_fwd_grad(const float* cls, const float* reg, const float* anchors, const float* annots, float* losses,
                                         void* workspace, long long workspace_bytes, void* dcls_pix, int dld, int dtype, int B,
                                         long long A, int num_classes, int N, const effdet_loss_opts_t* opts, const effdet_tal_t* tal,
                                         const effdet_quality_loss_t* quality, effdet_stream_t stream) {
-  return loss_tal_forward(cls, reg, anchors, annots, losses, workspace, workspace_bytes, dcls_pix, dld, dtype, true, B, A,
-                          num_classes, N, opts, tal, quality, stream);
+  LossCall c{loss_args(cls, reg, anchors, annots, B, A, num_classes, N), workspace, workspace_bytes, (hipStream_t)stream};
+  c.k.losses = losses; c.k.dcls = dcls_pix; c.k.dld = dld; c.dtype = dtype; c.grad = true;
+  c.matcher = MATCH_TAL; c.opts = opts; c.tal = tal; c.ql = quality;
+  return loss_forward(c);
 }
 
 extern "C" int effdet_loss_tal_metrics(const float* cls, const float* reg, const float* anchors, const float* annots, float* out, int B,

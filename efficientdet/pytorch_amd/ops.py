@@ -2026,15 +2026,18 @@ def merge_slices(lists, table, H, W, options=None):
 
 
 # ----------------------------------------------------------------------------- loss
-# Three sets of entry points, one per kind of call: effdet_focal_loss_* (the reference's constants), effdet_box_loss_* (an IoU-family
-# box term: kind, weight) and effdet_loss_opts_* (non-default LossOptions: the struct, with the box term inside it).  They take the same
-# arguments, the extra ones just before the stream.  Each public function below names the call it wants; _loss_entry chooses the set.
-# A matcher (ATSSOptions) is a fourth set for the two forward calls, effdet_loss_atss_* (the options struct, then the matcher's); its
-# backward calls are the options set's, with the options struct even where its values are the defaults.  A quality loss
-# (QualityLossOptions) is a fifth set for the forward calls and the class backward, effdet_loss_quality_* (the options struct, the
-# matcher's or NULL, its own); its d(reg) call is the options set's.  The task-aligned matcher (TaskAlignedOptions) has forward calls of
-# its own, effdet_loss_tal_* (the options struct, the matcher's, the quality loss's or NULL); its backward calls are the options set's
-# resp. the quality loss's.
+# Six sets of entry points, one per kind of call.  The calls of a kind take the same arguments in every set, the set's own ones just
+# before the stream; each public function below names the call it wants, and _loss_entry alone chooses the set:
+#   effdet_focal_loss_*    the reference's constants (no extra argument; the only set with the combined backward _bwd / _bwd_pix)
+#   effdet_box_loss_*      the same with an IoU-family box term: kind, weight
+#   effdet_loss_opts_*     non-default LossOptions: the options struct, with the box term inside it.  Its backward calls (_bwd_cls,
+#                          _bwd_reg) also serve every set below, with the struct even where its values are the defaults
+#   effdet_loss_atss_*     a matcher (ATSSOptions), forward calls only: the options struct, then the matcher's
+#   effdet_loss_quality_*  a quality loss (QualityLossOptions), forward calls and the class backward: the options struct, the matcher's
+#                          or NULL (forward only), its own
+#   effdet_loss_tal_*      the task-aligned matcher (TaskAlignedOptions), forward calls only: the options struct, the matcher's, the
+#                          quality loss's or NULL; its class backward is the options set's resp. the quality loss's
+# Every set has its workspace layout, which effdet_loss[_<set>]_workspace_bytes sizes (the box set shares the reference's).
 BOX_LOSS_KINDS = {'smooth_l1': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}     # EFFDET_BOX_LOSS_* (0: the effdet_focal_loss_* calls)
 
 
@@ -2302,28 +2305,32 @@ def _loss_opts_struct(loss, box=None, force=False):
 
 def _loss_entry(stem, loss=None, box=None, matcher=None, atss=None, quality=None):
     """-> (the entry point of the call `stem` for (loss, box, matcher, quality), its name, its extra arguments, whether it is of the
-    options set).  atss: the matcher's effdet_atss_t resp. effdet_tal_t, for the forward calls.  A quality loss has calls of its own
+    options set, and for a forward call ws_bytes(B, A, nc, N): the size of the workspace the call needs, by its set's own
+    *_workspace_bytes).  atss: the matcher's effdet_atss_t resp. effdet_tal_t, for the forward calls.  A quality loss has calls of its own
     for the forward and the class backward (the options struct, the matcher's or NULL on the forward calls, its own); its d(reg) call
     is the options set's, with the options struct even where its values are the defaults.  A TaskAlignedOptions has forward calls of
     its own (the options struct, its own, the quality loss's or NULL)."""
     check_matcher(matcher, loss)
     check_quality(quality, loss)
     o = _loss_opts_struct(loss, box, force=matcher is not None or quality is not None)
-    if isinstance(atss, L.Tal) and stem in ('fwd', 'fwd_grad'):
-        name = 'effdet_loss_tal_' + stem
-        extra = (C.byref(o), C.byref(atss), None if quality is None else C.byref(_quality_struct(quality)))
+    forward = stem in ('fwd', 'fwd_grad')
+    ref = lambda s: None if s is None else C.byref(s)      # noqa: E731
+    ql = None if quality is None else _quality_struct(quality)
+    sized = (ref(atss),)                                   # what the set's workspace-bytes call takes after (B, A, nc, N); None: no N
+    if isinstance(atss, L.Tal) and forward:
+        family, extra = 'loss_tal', (ref(o), ref(atss), ref(ql))
     elif quality is not None and stem != 'bwd_reg':
-        name = 'effdet_loss_quality_' + stem
-        mid = () if stem == 'bwd_cls' else (None if atss is None else C.byref(atss),)
-        extra = (C.byref(o),) + mid + (C.byref(_quality_struct(quality)),)
+        family, extra = 'loss_quality', (ref(o),) + ((ref(atss),) if forward else ()) + (ref(ql),)
     elif atss is not None:
-        name, extra = 'effdet_loss_atss_' + stem, (C.byref(o), C.byref(atss))
+        family, extra = 'loss_atss', (ref(o), ref(atss))
     elif o is not None:
-        name, extra = 'effdet_loss_opts_' + stem, (C.byref(o),)
+        family, extra, sized = 'loss_opts', (ref(o),), ()
     else:
         kw = _box_loss_args(box)
-        name, extra = ('effdet_focal_loss_' if kw is None else 'effdet_box_loss_') + stem, kw or ()
-    return getattr(L.require(name), name), name, extra, o is not None
+        family, extra, sized = 'focal_loss' if kw is None else 'box_loss', kw or (), None
+    name, wname = 'effdet_%s_%s' % (family, stem), 'effdet_%s_workspace_bytes' % ('loss' if sized is None else family)
+    ws_bytes = lambda B, A, nc, N: int(getattr(L.require(wname), wname)(B, A, nc, *(() if sized is None else (N,) + sized)))      # noqa: E731
+    return getattr(L.require(name), name), name, extra, o is not None, ws_bytes if forward else None
 
 
 def _dtype_code(dtype, split):
@@ -2336,18 +2343,8 @@ def _loss_forward(cls, reg, anc, annots, loss, box, grad=None, matcher=None, lev
     N = annots.shape[1]
     check_matcher(matcher, loss)
     atss = _matcher_struct(matcher, levels, A)
-    fn, name, extra, opts = _loss_entry('fwd_grad' if grad else 'fwd', loss, box, matcher, atss, quality)
-    if isinstance(atss, L.Tal):
-        nbytes = int(L.require('effdet_loss_tal_workspace_bytes').effdet_loss_tal_workspace_bytes(B, A, nc, N, C.byref(atss)))
-    elif quality is not None:
-        nbytes = int(L.require('effdet_loss_quality_workspace_bytes').effdet_loss_quality_workspace_bytes(
-            B, A, nc, N, None if atss is None else C.byref(atss)))
-    elif atss is not None:
-        nbytes = int(L.require('effdet_loss_atss_workspace_bytes').effdet_loss_atss_workspace_bytes(B, A, nc, N, C.byref(atss)))
-    elif opts:
-        nbytes = int(L.require('effdet_loss_opts_workspace_bytes').effdet_loss_opts_workspace_bytes(B, A, nc, N))
-    else:
-        nbytes = int(L.lib().effdet_loss_workspace_bytes(B, A, nc))
+    fn, name, extra, _, ws_bytes = _loss_entry('fwd_grad' if grad else 'fwd', loss, box, matcher, atss, quality)
+    nbytes = ws_bytes(B, A, nc, N)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=cls.device)
     losses = torch.empty(2, dtype=torch.float32, device=cls.device)
     out, args = (losses, ws), ()
@@ -2363,7 +2360,7 @@ def _loss_forward(cls, reg, anc, annots, loss, box, grad=None, matcher=None, lev
 def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box, matcher=None, quality=None):
     """-> dreg [B, A, 4], or with reg_ld pixel-major and channel-padded [B, A/9, reg_ld] (split=True: in the split layout), from the
     workspace of a forward call with the same (loss, box, matcher, quality)."""
-    fn, name, extra, _ = _loss_entry('bwd_reg', loss, box, matcher, quality=quality)
+    fn, name, extra = _loss_entry('bwd_reg', loss, box, matcher, quality=quality)[:3]
     B, A, _ = reg.shape
     dreg = torch.empty((B, A // 9, reg_ld) if reg_ld else (B, A, 4), dtype=dtype, device=reg.device)
     L.check(fn(L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dreg), reg_ld, _dtype_code(dtype, split), B, A,
@@ -2371,36 +2368,25 @@ def _loss_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld, split, loss, box,
     return dreg
 
 
-def _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld, loss=None, matcher=None, quality=None):
-    """d(logits) [B, A, nc], or with dld pixel-major and channel-padded [B, A/9, dld].  The reference's constants: the combined entry
-    points (dld None: the flat one), which also write the smooth-L1 dreg [B, A, 4] -> (dcls, dreg); options: the class gradient
-    alone -> dcls."""
+def focal_loss_fwd(cls, reg, anc, annots):
+    return _loss_forward(cls, reg, anc, annots, None, None)
+
+
+def focal_loss_bwd(cls, reg, anc, annots, gscale, ws, dtype):
+    return focal_loss_bwd_pix(cls, reg, anc, annots, gscale, ws, dtype, None)
+
+
+def focal_loss_bwd_pix(cls, reg, anc, annots, gscale, ws, dtype, dld):
+    """focal_loss_bwd with d(cls logits) pixel-major and channel-padded: -> (dcls_pix [B, A/9, dld], dreg [B, A, 4])."""
+    # the reference's constants have the combined entry points (dld None: the flat one, d(logits) [B, A, nc]), which also write dreg
     B, A, nc = cls.shape
     dcls = torch.empty((B, A // 9, dld) if dld else (B, A, nc), dtype=dtype, device=cls.device)
-    if loss is not None or matcher is not None or quality is not None:
-        fn, name, extra, _ = _loss_entry('bwd_cls', loss, None, matcher, quality=quality)
-        L.check(fn(L.ptr(cls), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls), dld, L.dtype_code(dtype), B, A, nc,
-                   annots.shape[1], *extra, L.stream_ptr()), name)
-        return dcls
     name = 'effdet_focal_loss_bwd' if dld is None else 'effdet_focal_loss_bwd_pix'
     dreg = torch.empty((B, A, 4), dtype=dtype, device=cls.device)
     L.check(getattr(L.lib(), name)(L.ptr(cls), L.ptr(reg), L.ptr(anc), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls),
                                    *(() if dld is None else (dld,)), L.ptr(dreg), L.dtype_code(dtype), B, A, nc, annots.shape[1],
                                    L.stream_ptr()), name)
     return dcls, dreg
-
-
-def focal_loss_fwd(cls, reg, anc, annots):
-    return _loss_forward(cls, reg, anc, annots, None, None)
-
-
-def focal_loss_bwd(cls, reg, anc, annots, gscale, ws, dtype):
-    return _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, None)
-
-
-def focal_loss_bwd_pix(cls, reg, anc, annots, gscale, ws, dtype, dld):
-    """focal_loss_bwd with d(cls logits) pixel-major and channel-padded: -> (dcls_pix [B, A/9, dld], dreg [B, A, 4])."""
-    return _loss_bwd_cls(cls, reg, anc, annots, gscale, ws, dtype, dld)
 
 
 def focal_loss_fwd_grad(cls, reg, anc, annots, dtype, dld, split=False):
@@ -2450,7 +2436,12 @@ def loss_opts_bwd_cls(cls, annots, gscale, ws, dtype, loss, dld=0, matcher=None,
     whatever loss."""
     if matcher is None and quality is None and _loss_opts_struct(loss) is None:
         raise ValueError('loss_opts_bwd_cls is the non-default path: the defaults are focal_loss_bwd / focal_loss_bwd_pix')
-    return _loss_bwd_cls(cls, None, None, annots, gscale, ws, dtype, dld, loss, matcher, quality)
+    B, A, nc = cls.shape
+    dcls = torch.empty((B, A // 9, dld) if dld else (B, A, nc), dtype=dtype, device=cls.device)
+    fn, name, extra = _loss_entry('bwd_cls', loss, None, matcher, quality=quality)[:3]
+    L.check(fn(L.ptr(cls), L.ptr(annots), L.ptr(gscale), L.ptr(ws), L.ptr(dcls), dld, L.dtype_code(dtype), B, A, nc, annots.shape[1],
+               *extra, L.stream_ptr()), name)
+    return dcls
 
 
 def loss_opts_bwd_reg(reg, anc, annots, gscale, ws, dtype, reg_ld=0, split=False, loss=None, box=None, matcher=None, quality=None):

@@ -113,7 +113,8 @@ RUNS = [('edges', 'default', 'qfl', None), ('edges', 'huber', 'vfl', ('giou', 2.
         ('s128_r05', 'huber', 'qfl', ('giou', 2.0)), ('s128_r20', 'default', 'vfl', None), ('s128_r20', 'default', 'qfl15', ('ciou', 1.0)),
         ('straddle_lq', 'lq', 'qfl', None), ('straddle_lq', 'lq', 'vfl15', ('ciou', 2.0)), ('straddle', 'default', 'vfl', None),
         ('tail_nc3', 'default', 'qfl', None), ('tail_nc3', 'huber', 'vfl15', None),
-        ('atss_nested', 'huber', 'qfl', ('giou', 2.0)), ('atss_straddle', 'default', 'vfl', None)]
+        ('atss_nested', 'huber', 'qfl', ('giou', 2.0)), ('atss_straddle', 'default', 'vfl', None),
+        ('atss_straddle', 'default', 'qfl', None), ('atss_straddle', 'huber', 'vfl', ('giou', 2.0))]      # ATSS x {QFL, smooth-L1} / {VFL, box kind}
 
 
 @functools.lru_cache(maxsize=None)

@@ -311,8 +311,8 @@ def test_without_a_matcher_the_entry_points_are_todays():
     m = ATSSOptions()
     t = ops._atss_struct(m, [252, 9], 261)
     for stem in ('fwd', 'fwd_grad'):
-        fn, name, extra, opts = ops._loss_entry(stem, None, None, m, t)
+        fn, name, extra, opts, _ = ops._loss_entry(stem, None, None, m, t)
         assert name == 'effdet_loss_atss_' + stem and len(extra) == 2 and opts is True
     for stem in ('bwd_cls', 'bwd_reg'):
-        fn, name, extra, opts = ops._loss_entry(stem, None, None, m)
+        fn, name, extra, opts, _ = ops._loss_entry(stem, None, None, m)
         assert name == 'effdet_loss_opts_' + stem and len(extra) == 1 and opts is True

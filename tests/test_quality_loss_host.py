@@ -301,7 +301,7 @@ def test_without_a_quality_loss_the_entry_points_are_todays():
     assert name('fwd', None, None, atss, t, quality=None) == 'effdet_loss_atss_fwd' and name('bwd_cls', loss) == 'effdet_loss_opts_bwd_cls'
     for kw in (dict(), dict(loss=loss), dict(box=box), dict(loss=loss, box=box, matcher=atss, atss=t)):
         for stem in ('fwd', 'fwd_grad'):
-            fn, nm, extra, o = ops._loss_entry(stem, quality=q, **kw)
+            fn, nm, extra, o, _ = ops._loss_entry(stem, quality=q, **kw)
             assert nm == 'effdet_loss_quality_' + stem and len(extra) == 3 and o and (extra[1] is None) == ('atss' not in kw)
     kw = dict(loss=loss, matcher=atss)
     assert name('bwd_cls', quality=q) == name('bwd_cls', quality=q, **kw) == 'effdet_loss_quality_bwd_cls'

@@ -288,7 +288,7 @@ def test_entry_points_chosen_for_a_task_aligned_matcher():
     t = ops._matcher_struct(o, None, 261)
     for stem in ('fwd', 'fwd_grad'):
         for quality, n_null in ((None, 1), (q, 0)):
-            fn, name, extra, opts = ops._loss_entry(stem, None, box, o, t, quality)
+            fn, name, extra, opts, _ = ops._loss_entry(stem, None, box, o, t, quality)
             assert name == 'effdet_loss_tal_' + stem and len(extra) == 3 and opts is True and sum(e is None for e in extra) == n_null
     assert ops._loss_entry('bwd_cls', None, None, o)[1] == 'effdet_loss_opts_bwd_cls'       # no backward entry points of its own
     assert ops._loss_entry('bwd_cls', None, None, o, quality=q)[1] == 'effdet_loss_quality_bwd_cls'
