@@ -1,7 +1,7 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h, include/effdet_affine.h,
 include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h, include/effdet_resample.h, include/effdet_slices.h,
-include/effdet_quality_loss.h, include/effdet_tal.h, include/effdet_op_point.h, include/effdet_track.h).
+include/effdet_quality_loss.h, include/effdet_tal.h, include/effdet_op_point.h, include/effdet_track.h, include/effdet_assign.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -456,6 +456,14 @@ TRACK_SIGNATURES = {
     'effdet_track_overflow': 'i:piips',
 }
 TRACK_MAX_TRACKS, TRACK_MAX_DET, TRACK_ROW_WORDS = 256, 128, 28                                  # EFFDET_TRACK_*
+# Optimal assignment (the batched op and the tracker's assignment stage), declared in include/effdet_assign.h (same generation, same
+# letters, same rule; tests/test_assign_host.py compares this table with that header's prototypes).
+ASSIGN_SIGNATURES = {
+    'effdet_assign': 'i:piiippfppps',
+    'effdet_track_step_assign': 'i:ppiipiffffffiiipppis',
+}
+ASSIGN_MAX_ROWS, ASSIGN_MAX_COLS, ASSIGN_SCALE_BITS = 256, 128, 20                               # EFFDET_ASSIGN_*
+ASSIGNMENTS = ('greedy', 'optimal')                                                              # EFFDET_ASSIGN_GREEDY, _OPTIMAL in order
 WGRAD_PATHS = ('tiled', 'thin', 'split', 'stem')                                                # EFFDET_WGRAD_PATH_* in order
 OPT_ROW, OPT_RULE_ADAMW, OPT_RULE_SGD, OPT_GATED, OPT_EMA = 8, 0, 1, 1, 2      # EFFDET_OPT_* of that header
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
@@ -486,7 +494,8 @@ def lib():
                 list(WGRAD_PAIR_SIGNATURES.items()) + list(OPT_GROUPS_SIGNATURES.items()) + list(GATE_OPERAND_SIGNATURES.items()) + \
                 list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
                 list(UNIT_LISTS_SIGNATURES.items()) + list(SLICES_SIGNATURES.items()) + list(QUALITY_LOSS_SIGNATURES.items()) + \
-                list(TAL_SIGNATURES.items()) + list(OP_POINT_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
+                list(TAL_SIGNATURES.items()) + list(OP_POINT_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + \
+                list(ASSIGN_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

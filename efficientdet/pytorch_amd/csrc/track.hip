@@ -10,10 +10,14 @@
 //     (wave shuffle butterfly + four ping-ponged LDS slots, ONE barrier per pick);
 //   * new tracks: the k-th free slot (ballot ranks) takes the k-th remaining detection (popcount ranks of the uniform mask);
 //   * duplicates: the LOST slots are listed in LDS, every TRACKED thread walks that list; marks are plain stores of 1;
-//   * output order: rank of a TRACKED slot's id among the ids in LDS.
+//   * output order: rank of a TRACKED slot's id among the ids in LDS;
+//   * effdet_track_step_assign's optimal assignment is the second instance of the kernel: track_optimal() in place of track_greedy(),
+//     the same rows, columns, track_similarity() and gate through assign.h's shortest-augmenting-path solver (its arrays in LDS, the
+//     row's dual, distance and predecessor in the slot's thread), a pair's integer weight recomputed whenever the search relaxes it.
 // No atomics of any kind.
 #include "common.h"
 #include "../../../include/effdet_track.h"
+#include "assign.h"
 
 namespace {
 
@@ -157,6 +161,39 @@ __device__ __forceinline__ int track_greedy(bool in_pool, const float4& tb, floa
   return mine;
 }
 
+// ---- assignment stage, optimal (include/effdet_assign.h): the same pool, columns (cols minus taken), similarity and gate; the weight of
+// a pair is recomputed from the two boxes at every relaxation.  Returns this thread's column or -1; taken gains the matched columns.
+struct TrackWeight {
+  float4 tb; float tlabel, gate; bool fuse, class_aware; const float4* dbox; const float* dscore; const float* dlabel;
+  __device__ __forceinline__ int operator()(int d) const {
+    return effdet_lap::assign_weight(track_similarity(tb, tlabel, dbox[d], dscore[d], dlabel[d], fuse, class_aware), gate);
+  }
+};
+__device__ __forceinline__ int track_optimal(bool in_pool, const float4& tb, float tlabel, const Mask& cols, Mask& taken, float gate, bool fuse,
+                                             bool class_aware, const float4* dbox, const float* dscore, const float* dlabel,
+                                             effdet_lap::AssignLds& lap, int& par, int tid) {
+  const Mask avail = mask_andnot(cols, taken);
+  const effdet_lap::AssignCols c{{avail.w[0], avail.w[1]}};
+  effdet_lap::AssignCols got;
+  int total;
+  const TrackWeight wt{tb, tlabel, gate, fuse, class_aware, dbox, dscore, dlabel};
+  const int mine = effdet_lap::assign_solve(in_pool, c, wt, lap, par, tid, got, total);
+  taken.w[0] |= got.w[0]; taken.w[1] |= got.w[1];
+  return mine;
+}
+
+// the solver's LDS, present only in the kernel instance that uses it
+template <bool OPTIMAL> struct LapStore { effdet_lap::AssignLds lds; };
+template <> struct LapStore<false> {};
+
+template <bool OPTIMAL>
+__device__ __forceinline__ int track_associate(bool in_pool, const float4& tb, float tlabel, const Mask& cols, Mask& taken, float gate, bool fuse,
+                                               bool class_aware, const float4* dbox, const float* dscore, const float* dlabel,
+                                               unsigned long long (*red)[TR_WAVES], LapStore<OPTIMAL>& lap, int& par, int tid) {
+  if constexpr (OPTIMAL) return track_optimal(in_pool, tb, tlabel, cols, taken, gate, fuse, class_aware, dbox, dscore, dlabel, lap.lds, par, tid);
+  else return track_greedy(in_pool, tb, tlabel, cols, taken, gate, fuse, class_aware, dbox, dscore, dlabel, red, par, tid);
+}
+
 __device__ __forceinline__ void slot_match(Slot& s, int d, const float4* dbox, const float* dscore, const float* dlabel, int frame) {
   float z[4];
   det_z(dbox[d], z);
@@ -164,7 +201,9 @@ __device__ __forceinline__ void slot_match(Slot& s, int d, const float4* dbox, c
   s.score = dscore[d]; s.label = dlabel[d]; s.last = frame;
 }
 
+template <bool OPTIMAL>
 __global__ __launch_bounds__(TR_T) void track_step_kernel(const TrackArgs a) {
+  __shared__ LapStore<OPTIMAL> lap;
   __shared__ float4 dbox[TR_D];
   __shared__ float dscore[TR_D], dlabel[TR_D];
   __shared__ int dkind[TR_D];                                          // 0 skipped / ignored, 1 low, 2 high
@@ -224,7 +263,8 @@ __global__ __launch_bounds__(TR_T) void track_step_kernel(const TrackArgs a) {
 
   // 3. first association: TRACKED + LOST x HIGH
   Mask taken = mask_none();
-  int d = track_greedy(state0 == TR_TRACKED || state0 == TR_LOST, pb, s.label, high, taken, a.match_sim, fuse, ca, dbox, dscore, dlabel, red, par, tid);
+  int d = track_associate<OPTIMAL>(state0 == TR_TRACKED || state0 == TR_LOST, pb, s.label, high, taken, a.match_sim, fuse, ca, dbox, dscore, dlabel,
+                                   red, lap, par, tid);
   bool matched = d >= 0;
   if (matched) {                                                       // 6.
     slot_match(s, d, dbox, dscore, dlabel, frame);
@@ -232,11 +272,13 @@ __global__ __launch_bounds__(TR_T) void track_step_kernel(const TrackArgs a) {
   }
   // 4. second association: the TRACKED left x LOW, plain IoU
   Mask taken_low = mask_none();
-  d = track_greedy(state0 == TR_TRACKED && !matched, pb, s.label, low, taken_low, a.second_sim, false, ca, dbox, dscore, dlabel, red, par, tid);
+  d = track_associate<OPTIMAL>(state0 == TR_TRACKED && !matched, pb, s.label, low, taken_low, a.second_sim, false, ca, dbox, dscore, dlabel, red,
+                               lap, par, tid);
   if (d >= 0) { slot_match(s, d, dbox, dscore, dlabel, frame); s.len += 1; matched = true; }
   if (state0 == TR_TRACKED && !matched) s.state = TR_LOST;
   // 5. third association: UNCONFIRMED x the HIGH left
-  d = track_greedy(state0 == TR_UNCONFIRMED, pb, s.label, high, taken, a.unconfirmed_sim, fuse, ca, dbox, dscore, dlabel, red, par, tid);
+  d = track_associate<OPTIMAL>(state0 == TR_UNCONFIRMED, pb, s.label, high, taken, a.unconfirmed_sim, fuse, ca, dbox, dscore, dlabel, red, lap, par,
+                               tid);
   if (state0 == TR_UNCONFIRMED) {
     if (d >= 0) { slot_match(s, d, dbox, dscore, dlabel, frame); s.len += 1; s.state = TR_TRACKED; }
     else s.state = TR_FREE;
@@ -379,22 +421,40 @@ extern "C" int effdet_track_overflow(const void* state, int B, int max_tracks, i
   return EFFDET_OK;
 }
 
-extern "C" int effdet_track_step(const float* dets, const int* counts, int B, int max_det, void* state, int max_tracks, float track_thr,
-                                 float low_thr, float new_thr, float match_sim, float second_sim, float unconfirmed_sim, int track_buffer,
-                                 int fuse_score, int class_aware, float* out_rows, int* out_ids, int* out_count, effdet_stream_t stream) {
+// effdet_track_step and effdet_track_step_assign: the refusals, then one launch of the instance `assignment` names
+static int track_step_launch(const float* dets, const int* counts, int B, int max_det, void* state, int max_tracks, float track_thr, float low_thr,
+                             float new_thr, float match_sim, float second_sim, float unconfirmed_sim, int track_buffer, int fuse_score,
+                             int class_aware, float* out_rows, int* out_ids, int* out_count, int assignment, effdet_stream_t stream) {
   if (!dets || !counts || !state || !out_rows || !out_ids || !out_count || max_det < 1) return EFFDET_EINVAL;
   const int e = track_shape(B, max_tracks);
   if (e == EFFDET_EINVAL) return e;
   if (!fin_ok(track_thr) || !fin_ok(low_thr) || !fin_ok(new_thr) || !lim_ok(match_sim) || !lim_ok(second_sim) || !lim_ok(unconfirmed_sim) ||
       low_thr > track_thr || track_buffer < 0)
     return EFFDET_EINVAL;
+  if (assignment != EFFDET_ASSIGN_GREEDY && assignment != EFFDET_ASSIGN_OPTIMAL) return EFFDET_EINVAL;
   if (e != EFFDET_OK || max_det > TR_D) return EFFDET_EUNSUPPORTED;
   TrackArgs a;
   a.dets = dets; a.counts = counts; a.hdr = (int*)state; a.rows = (unsigned*)state + (size_t)B * 4; a.B = B; a.max_det = max_det; a.T = max_tracks;
   a.track_thr = track_thr; a.low_thr = low_thr; a.new_thr = new_thr; a.match_sim = match_sim; a.second_sim = second_sim;
   a.unconfirmed_sim = unconfirmed_sim; a.track_buffer = track_buffer; a.fuse_score = fuse_score; a.class_aware = class_aware;
   a.out_rows = out_rows; a.out_ids = out_ids; a.out_count = out_count;
-  hipLaunchKernelGGL(track_step_kernel, dim3(B), dim3(TR_T), 0, (hipStream_t)stream, a);
+  if (assignment == EFFDET_ASSIGN_OPTIMAL) hipLaunchKernelGGL(track_step_kernel<true>, dim3(B), dim3(TR_T), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(track_step_kernel<false>, dim3(B), dim3(TR_T), 0, (hipStream_t)stream, a);
   EFFDET_CHECK_LAUNCH();
   return EFFDET_OK;
+}
+
+extern "C" int effdet_track_step(const float* dets, const int* counts, int B, int max_det, void* state, int max_tracks, float track_thr,
+                                 float low_thr, float new_thr, float match_sim, float second_sim, float unconfirmed_sim, int track_buffer,
+                                 int fuse_score, int class_aware, float* out_rows, int* out_ids, int* out_count, effdet_stream_t stream) {
+  return track_step_launch(dets, counts, B, max_det, state, max_tracks, track_thr, low_thr, new_thr, match_sim, second_sim, unconfirmed_sim,
+                           track_buffer, fuse_score, class_aware, out_rows, out_ids, out_count, EFFDET_ASSIGN_GREEDY, stream);
+}
+
+extern "C" int effdet_track_step_assign(const float* dets, const int* counts, int B, int max_det, void* state, int max_tracks, float track_thr,
+                                        float low_thr, float new_thr, float match_sim, float second_sim, float unconfirmed_sim,
+                                        int track_buffer, int fuse_score, int class_aware, float* out_rows, int* out_ids, int* out_count,
+                                        int assignment, effdet_stream_t stream) {
+  return track_step_launch(dets, counts, B, max_det, state, max_tracks, track_thr, low_thr, new_thr, match_sim, second_sim, unconfirmed_sim,
+                           track_buffer, fuse_score, class_aware, out_rows, out_ids, out_count, assignment, stream);
 }

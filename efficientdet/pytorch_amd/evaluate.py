@@ -215,7 +215,9 @@ class TrackedDetector:
     """A detector for video: every image of the batch is one camera stream, and each call is the streams' next frame.  ``update`` runs
     ``model``'s own detection pass (an EfficientDet, an EnsembleDetector or a SlicedDetector: its NMS and TTA settings apply), the eval
     consumer on the device (finalize_device; score_threshold None: options.low_thr, because ByteTrack needs the low detections) and ONE
-    ops.track_step (csrc/track.hip, include/effdet_track.h): ByteTrack with a greedy assignment, state on the device, no host read.  The
+    ops.track_step (csrc/track.hip, include/effdet_track.h): ByteTrack, state on the device, no host read.  Each association is greedy
+    by descending similarity by default; options = TrackOptions(assignment='optimal') solves it as the published tracker does, as a
+    linear assignment problem (include/effdet_assign.h) -- the wrapper only passes its options on.  The
     state is allocated at the first update for that batch size; another batch size later raises (reset() and a new wrapper are the ways
     to start over).  options is read at every update; its max_tracks is fixed once the state exists (ops.track_step refuses another).
 

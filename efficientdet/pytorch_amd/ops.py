@@ -2657,6 +2657,7 @@ def confusion_match(dets, counts, gt_boxes, gt_labels, num_classes, conf_thresho
 
 TRACK_MAX_TRACKS, TRACK_MAX_DET, TRACK_ROW_WORDS = L.TRACK_MAX_TRACKS, L.TRACK_MAX_DET, L.TRACK_ROW_WORDS
 _TRACK = ('effdet_track_state_bytes', 'effdet_track_reset', 'effdet_track_step', 'effdet_track_overflow')
+ASSIGN_MAX_ROWS, ASSIGN_MAX_COLS = L.ASSIGN_MAX_ROWS, L.ASSIGN_MAX_COLS
 
 
 class TrackOptions:
@@ -2664,10 +2665,15 @@ class TrackOptions:
     track_thr) low; the three associations allow a pair whose similarity is > match_sim (tracked + lost x high), > second_sim (the
     tracked left x low, plain IoU) and > unconfirmed_sim (unconfirmed x the high left); a high detection left over starts a track when
     its score is >= new_thr (None: track_thr + 0.1); a lost track is dropped after track_buffer frames without a match; fuse_score
-    multiplies the IoU by the detection's score; class_aware also wants equal labels; max_tracks slots per stream."""
+    multiplies the IoU by the detection's score; class_aware also wants equal labels; max_tracks slots per stream.  assignment:
+    'greedy' (the default: each association greedy by descending similarity) or 'optimal' (each association solved as the published
+    tracker does, a maximum-weight matching over the allowed pairs; include/effdet_assign.h)."""
 
     def __init__(self, track_thr=0.5, low_thr=0.1, new_thr=None, match_sim=0.2, second_sim=0.5, unconfirmed_sim=0.3, track_buffer=30,
-                 fuse_score=True, class_aware=False, max_tracks=128):
+                 fuse_score=True, class_aware=False, max_tracks=128, assignment='greedy'):
+        if assignment not in L.ASSIGNMENTS:
+            raise ValueError('TrackOptions: assignment must be one of %s, got %r' % (', '.join(map(repr, L.ASSIGNMENTS)), assignment))
+        self.assignment = assignment
         new_thr = float(np.float32(np.float32(track_thr) + np.float32(0.1))) if new_thr is None else new_thr
         for name, v in (('track_thr', track_thr), ('low_thr', low_thr), ('new_thr', new_thr)):
             if not abs(float(v)) < float('inf'):
@@ -2686,8 +2692,9 @@ class TrackOptions:
         self.track_buffer, self.fuse_score, self.class_aware, self.max_tracks = int(track_buffer), bool(fuse_score), bool(class_aware), int(max_tracks)
 
     def key(self):
-        return (self.track_thr, self.low_thr, self.new_thr, self.match_sim, self.second_sim, self.unconfirmed_sim, self.track_buffer,
-                self.fuse_score, self.class_aware, self.max_tracks)
+        k = (self.track_thr, self.low_thr, self.new_thr, self.match_sim, self.second_sim, self.unconfirmed_sim, self.track_buffer,
+             self.fuse_score, self.class_aware, self.max_tracks)
+        return k if self.assignment == 'greedy' else k + (self.assignment,)            # (the default keeps the ten-tuple it always had)
 
     def __eq__(self, other):
         return isinstance(other, TrackOptions) and self.key() == other.key()
@@ -2697,7 +2704,8 @@ class TrackOptions:
 
     def __repr__(self):
         return ('TrackOptions(track_thr=%r, low_thr=%r, new_thr=%r, match_sim=%r, second_sim=%r, unconfirmed_sim=%r, track_buffer=%d, '
-                'fuse_score=%r, class_aware=%r, max_tracks=%d)' % self.key())
+                'fuse_score=%r, class_aware=%r, max_tracks=%d' % self.key()[:10]
+                + ('' if self.assignment == 'greedy' else ', assignment=%r' % self.assignment) + ')')
 
 
 class TrackState:
@@ -2742,7 +2750,8 @@ def track_step(dets, counts, state, options=None, out=None):
     """One frame of every stream (include/effdet_track.h): dets [B, max_det, 6] fp32 + counts [B] int32 as finalize_dets writes them ->
     (rows [B, max_tracks, 8] fp32: x1, y1, x2, y2, score, label, tracklet_len, frames_since_start; ids [B, max_tracks] int32; count [B]
     int32), the activated tracks of each stream in ascending id, rows past the count zero with id -1.  Everything stays on the device and
-    nothing is read back, so the call can be captured in a graph.  out: such a triple of the caller's (every element is overwritten)."""
+    nothing is read back, so the call can be captured in a graph.  out: such a triple of the caller's (every element is overwritten).
+    options.assignment 'greedy' goes through effdet_track_step, 'optimal' through effdet_track_step_assign (include/effdet_assign.h)."""
     o = TrackOptions() if options is None else options
     if not isinstance(o, TrackOptions):
         raise TypeError('track_step: options must be a TrackOptions, not %r' % (o,))
@@ -2765,11 +2774,48 @@ def track_step(dets, counts, state, options=None, out=None):
     assert rows.dtype == torch.float32 and rows.is_contiguous() and tuple(rows.shape) == (B, T, 8)
     assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape) == (B, T)
     assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == B
-    L.check(L.require(*_TRACK).effdet_track_step(L.ptr(dets), L.ptr(counts), B, max_det, L.ptr(state.buf), T, o.track_thr, o.low_thr, o.new_thr,
-                                                 o.match_sim, o.second_sim, o.unconfirmed_sim, o.track_buffer, int(o.fuse_score),
-                                                 int(o.class_aware), L.ptr(rows), L.ptr(ids), L.ptr(count), L.stream_ptr()),
-            'effdet_track_step')
+    args = (L.ptr(dets), L.ptr(counts), B, max_det, L.ptr(state.buf), T, o.track_thr, o.low_thr, o.new_thr, o.match_sim, o.second_sim,
+            o.unconfirmed_sim, o.track_buffer, int(o.fuse_score), int(o.class_aware), L.ptr(rows), L.ptr(ids), L.ptr(count))
+    if o.assignment == 'greedy':
+        L.check(L.require(*_TRACK).effdet_track_step(*args, L.stream_ptr()), 'effdet_track_step')
+    else:
+        L.check(L.require('effdet_track_step_assign').effdet_track_step_assign(*args, L.ASSIGNMENTS.index(o.assignment), L.stream_ptr()),
+                'effdet_track_step_assign')
     return rows, ids, count
+
+
+def linear_assignment(sim, gate=0.0, n_rows=None, n_cols=None, out=None):
+    """Optimal assignment of B problems (include/effdet_assign.h): sim [B, R, C] fp32 (a 2-D sim is a batch of one), R <= 256 rows and
+    C <= 128 columns.  A pair is allowed when sim > gate; the answer is the matching over allowed pairs with the largest sum of
+    similarity above the gate (on a 2^-20 grid), nothing forced to be matched -- lap.lapjv(1 - sim, extend_cost=True, cost_limit=1 - gate).
+    n_rows / n_cols: [B] int32 tensors, the rows / columns of each problem that take part (None: all).  -> (row_to_col [B, R] int32,
+    col_to_row [B, C] int32, -1 = unmatched; total [B] int64, the sum of the integer weights); without the batch dimension for a 2-D
+    sim.  Everything stays on the device and nothing is read back, so the call can be captured in a graph.  out: such a triple of
+    the caller's (every element is overwritten)."""
+    if sim.dim() not in (2, 3):
+        raise ValueError('linear_assignment: sim must be [R, C] or [B, R, C], got %s' % (tuple(sim.shape),))
+    batched = sim.dim() == 3
+    B, R, C = (int(v) for v in (sim.shape if batched else (1,) + tuple(sim.shape)))
+    if B < 1 or not 1 <= R <= ASSIGN_MAX_ROWS or not 1 <= C <= ASSIGN_MAX_COLS:
+        raise ValueError('linear_assignment: B >= 1, 1..%d rows and 1..%d columns, got %d, %d, %d' % (ASSIGN_MAX_ROWS, ASSIGN_MAX_COLS, B, R, C))
+    gate = float(gate)
+    if not abs(gate) < float('inf'):
+        raise ValueError('linear_assignment: gate must be finite, got %r' % (gate,))
+    assert sim.dtype == torch.float32 and sim.is_contiguous()
+    for name, n in (('n_rows', n_rows), ('n_cols', n_cols)):
+        if n is not None:
+            assert n.dtype == torch.int32 and n.is_contiguous() and n.numel() == B and n.device == sim.device, name
+    if out is None:
+        out = (torch.empty((B, R) if batched else (R,), dtype=torch.int32, device=sim.device),
+               torch.empty((B, C) if batched else (C,), dtype=torch.int32, device=sim.device),
+               torch.empty((B,) if batched else (), dtype=torch.int64, device=sim.device))
+    r2c, c2r, total = out
+    assert r2c.dtype == torch.int32 and r2c.is_contiguous() and r2c.numel() == B * R and r2c.device == sim.device
+    assert c2r.dtype == torch.int32 and c2r.is_contiguous() and c2r.numel() == B * C and c2r.device == sim.device
+    assert total.dtype == torch.int64 and total.is_contiguous() and total.numel() == B and total.device == sim.device
+    L.check(L.require('effdet_assign').effdet_assign(L.ptr(sim), B, R, C, L.ptr(n_rows), L.ptr(n_cols), gate, L.ptr(r2c), L.ptr(c2r),
+                                                     L.ptr(total), L.stream_ptr()), 'effdet_assign')
+    return r2c, c2r, total
 
 
 COCO_MAX_GT = 2048                 # GT rows per image effdet_coco_match stages in LDS

@@ -50,8 +50,9 @@
  *    when sim > unconfirmed_sim.  A matched slot becomes TRACKED; an unmatched one becomes FREE (its row zeroed).
  * Assignment in each association is GREEDY BY DESCENDING SIMILARITY: repeatedly the allowed pair with the largest sim among the rows
  *    and columns not yet matched is matched; among equal sims the lower detection row wins, then the lower slot.  (The published
- *    ByteTrack solves each association optimally by LAPJV; this is the stated deviation.  csrc/track.hip keeps the similarity and the
- *    assignment as separate device functions so that another solver can replace the second.)
+ *    ByteTrack solves each association optimally by LAPJV; this is the stated deviation and the default.  csrc/track.hip keeps the
+ *    similarity and the assignment as separate device functions so that another solver can replace the second: effdet_assign.h's
+ *    effdet_track_step_assign(..., assignment = 1) is this step with the optimal assignment in its place.)
  * 6. Every match is a Kalman update of the slot with the detection's z; score and label become the detection's; last_frame =
  *    frame_id; tracklet_len += 1 -- except for a LOST slot matched in step 3, which becomes TRACKED with tracklet_len = 0 and keeps
  *    its id.
