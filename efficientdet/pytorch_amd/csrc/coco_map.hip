@@ -19,7 +19,7 @@
 //     a reverse sweep rebuilds the exact integer cumsums from the right, recall / precision in fp64, the envelope (running max
 //     from the right) and, at each point where recall steps, the recThrs it answers (searchsorted 'left').  A last launch reduces
 //     the 12 summary statistics in a fixed order.  Every launch geometry follows from the arguments alone.
-#include "common.h"
+#include "box_geom.h"
 #include "block_scan.h"
 #include "radix_sort.h"
 #include <limits.h>
@@ -44,11 +44,6 @@ struct CocoAccParams {
   int max_dets[COCO_MAX_M];
   int T, R, A, M;
 };
-
-__device__ __forceinline__ bool coco_label(float lf, int K, int& c) {
-  c = (int)lf;
-  return lf >= 0.f && lf < (float)K && (float)c == lf;
-}
 
 // maskApi.c bbIou for one (detection, GT) pair, fp64, in the C source's operation order
 __device__ __forceinline__ double coco_iou(double dx, double dy, double dw, double dh, double da, const double* g, bool crowd) {
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(256) void coco_match_kernel(const float* __restrict
   }
   for (int k = tid; k < n; k += 256) {
     int c;
-    if (coco_label(d[(long long)k * 6 + 5], K, c)) atomicAdd(&det_counter[c], 1);
+    if (label_class(d[(long long)k * 6 + 5], K, c)) atomicAdd(&det_counter[c], 1);
   }
   __syncthreads();
   if (tid == 0) {
@@ -153,7 +148,7 @@ __global__ __launch_bounds__(256) void coco_match_kernel(const float* __restrict
     for (int r0 = 0; r0 < n && rank < kept; r0 += 64) {          // (wave-uniform)
       const int k = r0 + lane;
       int ck;
-      const bool mine = k < n && coco_label(d[(long long)k * 6 + 5], K, ck) && ck == c;
+      const bool mine = k < n && label_class(d[(long long)k * 6 + 5], K, ck) && ck == c;
       unsigned long long mask = __ballot(mine);
       while (mask && rank < kept) {
         const int j = __ffsll((long long)mask) - 1;

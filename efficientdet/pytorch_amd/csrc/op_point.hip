@@ -2,7 +2,8 @@
 // records of effdet_voc_match, and a confusion matrix over the rows of effdet_finalize_dets.  Compiled with -ffp-contract=off: every
 // fp64 operation of the header's tables rounds once, and the IoU is voc_map.hip's expression in its operation order.
 //
-//   effdet_op_curves: the sort and the segment bounds of effdet_voc_ap (rs_init_kernel, rs_sort, rs_segment_bounds); then
+//   effdet_op_curves: the class sort of effdet_voc_ap (radix_sort.h's rs_class_sort(): rs_init_kernel, rs_sort(), then the
+//     rs_segment_bounds() of rs_segments_kernel); then
 //     op_sweep_kernel (one workgroup per class: exact integer inclusive cumsum of the TP bytes over the class's sorted segment, in
 //     256-record chunks with a carry), op_count_kernel (a grid over (class, threshold): a binary search of the threshold's key in the
 //     score-descending segment gives npred, the cumsum in front of it gives tp; precision, recall, f1 from them), op_mean_kernel (one
@@ -11,7 +12,7 @@
 //   effdet_confusion_match (one workgroup per image): the GT rows are staged in LDS as voc_match_kernel stages them; nothing is kept
 //     per detection, every pass recomputes a prediction's best object.  Pass 1: atomic max of the IoU bits per object; pass 2: atomic
 //     min of the row among the predictions holding that IoU; pass 3: the counts.
-#include "common.h"
+#include "box_geom.h"
 #include "block_scan.h"
 #include "radix_sort.h"
 #include "../../../include/effdet_op_point.h"
@@ -23,10 +24,6 @@ namespace {
 constexpr int OP_MAX_CLASSES = 65535;          // effdet_voc_ap's range: class values 0..C fit the two class passes of the sort
 constexpr int CM_MAX_GT = 2048;                // GT rows per image staged in LDS
 constexpr size_t CM_GT_LDS = 4 * sizeof(double) + sizeof(unsigned long long) + 2 * sizeof(int);   // box, winner's IoU bits, label, winner's row
-
-__global__ __launch_bounds__(256) void op_segments_kernel(const unsigned long long* __restrict__ skey, long long N, int C, int* __restrict__ seg) {
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < N; i += (long long)gridDim.x * 256) rs_segment_bounds(skey, i, N, C, seg);
-}
 
 // one workgroup per class: cum[i] = TP bytes of the class's sorted records up to and including position i
 __global__ __launch_bounds__(256) void op_sweep_kernel(const unsigned* __restrict__ sval, const unsigned char* __restrict__ rec_tp,
@@ -123,7 +120,7 @@ __global__ __launch_bounds__(256) void op_best_kernel(const double* __restrict__
     if (tid < s) {
       const double ov = bv[tid + s];
       const int oj = bj[tid + s];
-      if (ov > bv[tid] || (ov == bv[tid] && oj < bj[tid])) { bv[tid] = ov; bj[tid] = oj; }
+      if (ov > bv[tid] || (ov == bv[tid] && oj < bj[tid])) { bv[tid] = ov; bj[tid] = oj; }      // (block_best.h's order, on LDS slots)
     }
     __syncthreads();
   }
@@ -146,14 +143,13 @@ size_t op_carve(OpWs& w, void* base, long long N) {
 
 // a row of dets that is a prediction of the confusion matrix -> its class, else -1
 __device__ __forceinline__ int cm_pred_class(const float* r, int C, float conf) {
-  const float lf = r[5];
-  const int c = (int)lf;
-  if (!(lf >= 0.f && lf < (float)C) || (float)c != lf) return -1;
+  int c;
+  if (!label_class(r[5], C, c)) return -1;
   return r[4] > conf ? c : -1;
 }
 
-// the prediction's best candidate object: the first maximum of voc_assign's IoU over the objects (gl[j] >= 0) among those with
-// iou > thr; -1 without a candidate
+// the prediction's best candidate object: the first maximum of box_geom.h's box_overlap_f64 over the objects (gl[j] >= 0) among those
+// with iou > thr; -1 without a candidate
 __device__ __forceinline__ int cm_best_object(const float* r, const double* gb, const int* gl, int G, double thr, double& best) {
   const double a0 = r[0], a1 = r[1], a2 = r[2], a3 = r[3];
   const double aarea = (a2 - a0) * (a3 - a1);
@@ -161,15 +157,7 @@ __device__ __forceinline__ int cm_best_object(const float* r, const double* gb, 
   best = thr;
   for (int j = 0; j < G; ++j) {
     if (gl[j] < 0) continue;
-    const double b0 = gb[4 * j], b1 = gb[4 * j + 1], b2 = gb[4 * j + 2], b3 = gb[4 * j + 3];
-    const double area = (b2 - b0) * (b3 - b1);
-    double iw = fmin(a2, b2) - fmax(a0, b0);
-    double ih = fmin(a3, b3) - fmax(a1, b1);
-    iw = fmax(iw, 0.0);
-    ih = fmax(ih, 0.0);
-    double ua = aarea + area - iw * ih;
-    ua = fmax(ua, DBL_EPSILON);
-    const double iou = iw * ih / ua;
+    const double iou = box_overlap_f64(a0, a1, a2, a3, aarea, gb + 4 * j);
     if (iou > best) { best = iou; arg = j; }       // strictly above the threshold, then the first maximum
   }
   return arg;
@@ -251,15 +239,9 @@ extern "C" int effdet_op_curves(const unsigned long long* rec_key, const unsigne
   OpWs w;
   if ((long long)op_carve(w, workspace, N) > workspace_bytes) return EFFDET_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(rs_init_kernel<unsigned long long>, dim3(grid_for(N > 2LL * C ? N : 2LL * C)), dim3(256), 0, st, rec_key, w.rs.ka,
-                     w.rs.va, N, w.seg, C);
-  EFFDET_CHECK_LAUNCH();
-  unsigned long long *ki = w.rs.ka, *ko = w.rs.kb;
-  unsigned *vi = w.rs.va, *vo = w.rs.vb;
+  unsigned long long* ki; unsigned* vi;
+  if (const int rc = rs_class_sort(rec_key, N, C, w.rs, w.seg, ki, vi, st)) return rc;
   if (N > 0) {
-    const int passes = 4 + (C <= 255 ? 1 : 2);       // class values 0..C (C = empty slot): effdet_voc_ap's sort
-    if (const int rc = rs_sort(ki, vi, ko, vo, w.rs.hist, 1, N, w.rs.T, 0, passes, st)) return rc;
-    hipLaunchKernelGGL(op_segments_kernel, dim3(grid_for(N)), dim3(256), 0, st, (const unsigned long long*)ki, N, C, w.seg);
     hipLaunchKernelGGL(op_sweep_kernel, dim3(C), dim3(256), 0, st, (const unsigned*)vi, rec_tp, (const int*)w.seg, w.cum);
     EFFDET_CHECK_LAUNCH();
   }

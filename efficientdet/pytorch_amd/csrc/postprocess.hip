@@ -15,7 +15,8 @@
 //      exactly the sequential greedy result -- appends the kept boxes in order and files them into the grid.
 //   All loops are bounded by device-side counts; the host launches ceil(A / round) rounds blindly; every
 //   launch geometry depends on shapes only and the call consists of kernel nodes only: capture-safe.
-#include "common.h"
+#include "box_geom.h"
+#include "block_best.h"
 #include "../../../include/effdet_soft_nms.h"
 #include "radix_sort.h"
 #include <stdlib.h>
@@ -102,22 +103,10 @@ struct NmsWs {
   unsigned long long* rowbits; float4* surv_box; unsigned* surv_idx; int* surv_n; int RND, NW;
 };
 
-// THE IoU arithmetic of the file (greedy and rescoring NMS): f(iou) of the IoU from the stored fp32 areas, f's zero (false / 0.f)
-// for boxes that do not overlap
-template <typename F> __device__ __forceinline__ auto with_iou(const float4& a, float aa, const float4& b, float ab, F f) -> decltype(f(0.f)) {
-  const float iw = fminf(a.z, b.z) - fmaxf(a.x, b.x);
-  const float ih = fminf(a.w, b.w) - fmaxf(a.y, b.y);
-  if (iw <= 0.f || ih <= 0.f) return decltype(f(0.f))(0);
-  const float inter = iw * ih;
-  // (division-free forms -- bracketing products, or the exact f64 midpoint compare -- measured no faster: the phases that
-  //  call this are LDS/latency-bound, not VALU-bound)
-  return f(inter / (aa + ab - inter));
-}
+// greedy NMS: box_geom.h's IoU from the stored fp32 areas above thr; false for boxes that do not overlap, whatever thr is
 __device__ __forceinline__ bool suppresses(const float4& a, float aa, const float4& b, float ab, float thr) {
-  return with_iou(a, aa, b, ab, [thr](float iou) { return iou > thr; });
-}
-__device__ __forceinline__ float box_iou(const float4& a, float aa, const float4& b, float ab) {
-  return with_iou(a, aa, b, ab, [](float iou) { return iou; });
+  float inter;
+  return box_inter(a, b, inter) && inter / (aa + ab - inter) > thr;
 }
 
 // `me` against n kept boxes staged in LDS (tb / ta, padded to a multiple of 8 with boxes that suppress nothing).
@@ -166,8 +155,6 @@ __global__ void nms_gather_kernel(const float* __restrict__ boxes, const unsigne
 // hash collisions only add tests.
 constexpr int SB_MIN = 4, SB_MAX = 40;
 
-
-__device__ __forceinline__ float box_area(const float4& b) { return (b.z - b.x) * (b.w - b.y); }
 __device__ __forceinline__ bool box_live(const float4& b, float a) {       // can take part in suppression at all
   return a > 0.f && a < 3.0e38f && fabsf(b.x) < 1.0e18f && fabsf(b.y) < 1.0e18f && fabsf(b.z) < 1.0e18f && fabsf(b.w) < 1.0e18f;
 }
@@ -552,9 +539,7 @@ struct SoftNms {
   float thr, iou_thr, sigma; int method, top_n, max_det;
 };
 
-__device__ __forceinline__ bool area_ok(float a) { return a > 0.f && a < __builtin_huge_valf(); }
-// (s, position) arg-max order: larger score first, then the smaller position; dead entries are (-inf, INT_MAX)
-__device__ __forceinline__ void sn_better(float& s, int& q, float os, int oq) { if (os > s || (os == s && oq < q)) { s = os; q = oq; } }
+// the (score, sorted position) arg-max of a pick goes by block_best.h's order; dead entries are (-inf, INT_MAX)
 
 __global__ __launch_bounds__(SN_T) void soft_nms_kernel(const SoftNms p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -573,28 +558,28 @@ __global__ __launch_bounds__(SN_T) void soft_nms_kernel(const SoftNms p) {
     const float4 bx = ((const float4*)p.boxes)[src];
     const float s = p.score[src];                                      // (> thr: it is a candidate)
     tb[q] = bx; ta[q] = box_area(bx); ts[q] = s; tl[q] = p.label ? p.label[src] : 0;
-    sn_better(bs, bq, s, q);
+    best_take(bs, bq, s, q);
   }
   int k = 0;
   for (; k < p.max_det; ++k) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sn_better(bs, bq, __shfl_xor(bs, o, 64), __shfl_xor(bq, o, 64));
+    for (int o = 32; o > 0; o >>= 1) best_take(bs, bq, __shfl_xor(bs, o, 64), __shfl_xor(bq, o, 64));
     if (lane == 0) { red_s[k & 1][wave] = bs; red_q[k & 1][wave] = bq; }
     __syncthreads();                                                   // (also publishes the loads above before pick 0 reads a box)
     float ws = red_s[k & 1][lane & 15]; int wq = red_q[k & 1][lane & 15];
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) sn_better(ws, wq, __shfl_xor(ws, o, 64), __shfl_xor(wq, o, 64));
+    for (int o = 8; o > 0; o >>= 1) best_take(ws, wq, __shfl_xor(ws, o, 64), __shfl_xor(wq, o, 64));
     if (!(ws > p.thr)) break;                                          // nothing live (block-uniform: every thread reduced the same 16 slots)
     if (tid == 0) { p.out_idx[base + k] = (int)p.sidx[base + wq]; p.out_score[base + k] = ws; }
     const float4 pb = tb[wq]; const float pa = ta[wq]; const int pl = tl[wq];
-    const bool pick_ok = area_ok(pa);
+    const bool pick_ok = pos_finite(pa);
     bs = SN_DEAD; bq = 0x7fffffff;
     for (int q = tid; q < n; q += SN_T) {
       float s = ts[q];
       if (q == wq) { s = SN_DEAD; ts[q] = s; }
       else if (s > p.thr && pick_ok && tl[q] == pl) {
         const float a = ta[q];
-        if (area_ok(a)) {
+        if (pos_finite(a)) {
           const float iou = box_iou(pb, pa, tb[q], a);
           if (p.method == 0) { if (iou > p.iou_thr) s = SN_DEAD; }
           else if (p.method == 1) { if (iou > p.iou_thr) s = s * (1.f - iou); }
@@ -603,7 +588,7 @@ __global__ __launch_bounds__(SN_T) void soft_nms_kernel(const SoftNms p) {
           ts[q] = s;
         }
       }
-      sn_better(bs, bq, s, q);
+      best_take(bs, bq, s, q);
     }
   }
   if (tid == 0) p.out_count[b] = k;

@@ -4,7 +4,8 @@
 // A pass is three launches: rs_hist_kernel (per-tile digit counts), rs_scan_kernel (per-segment exclusive scan over (digit, tile)
 // in digit-major order) and rs_scatter_kernel (tile-ordered, rank-within-wave ordered stores: stable).  The grid depends on B and
 // A only.  rs_sort drives the passes over the buffers of an RsBufs; rs_score_key makes the score part of a key; the two metrics
-// also share the sort input (rs_init_kernel) and the segment bounds of their sorted 64-bit keys (rs_segment_bounds).
+// also share the sort input (rs_init_kernel) and the segment bounds of their sorted 64-bit keys (rs_segment_bounds); the VOC and the
+// operating-point metrics (op_point.hip) share their whole class sort (rs_class_sort, which ends on rs_segments_kernel).
 #pragma once
 #include "common.h"
 
@@ -136,6 +137,30 @@ __device__ __forceinline__ void rs_segment_bounds(const unsigned long long* __re
   if (c >= (unsigned)C) return;
   if (i == 0 || (unsigned)(skey[i - 1] >> 32) != c) seg[2 * c] = (int)i;
   if (i == N - 1 || (unsigned)(skey[i + 1] >> 32) != c) seg[2 * c + 1] = (int)(i + 1);
+}
+
+// the bounds alone (voc_map.hip, op_point.hip; coco_segments_kernel also gathers its payload and stays in coco_map.hip).  K is
+// unsigned long long; this kernel and rs_class_sort are templates so that only the files that call them get the 64-bit instances.
+template <typename K>
+__global__ __launch_bounds__(256) void rs_segments_kernel(const K* __restrict__ skey, long long N, int C, int* __restrict__ seg) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < N; i += (long long)gridDim.x * 256) rs_segment_bounds(skey, i, N, C, seg);
+}
+
+// The class sort of the VOC and operating-point metrics: N records (class << 32 | score key), class values 0..C (C = empty slot).
+// Sort input and reset of seg[2 * C]; then, for N > 0, 4 score passes + 1 class pass (2 above 255 classes) and the segment bounds.
+// (ki, vi) are the sorted keys and record indices (w.ka, w.va when N == 0).  -> EFFDET_OK or EFFDET_ELAUNCH
+template <typename K> int rs_class_sort(const K* rec_key, long long N, int C, const RsBufs<K>& w, int* seg, K*& ki, unsigned*& vi, hipStream_t st) {
+  hipLaunchKernelGGL(rs_init_kernel<K>, dim3(grid_for(N > 2LL * C ? N : 2LL * C)), dim3(256), 0, st, rec_key, w.ka, w.va, N, seg, C);
+  EFFDET_CHECK_LAUNCH();
+  ki = w.ka; vi = w.va;
+  if (N > 0) {
+    K* ko = w.kb;
+    unsigned* vo = w.vb;
+    if (const int rc = rs_sort(ki, vi, ko, vo, w.hist, 1, N, w.T, 0, 4 + (C <= 255 ? 1 : 2), st)) return rc;
+    hipLaunchKernelGGL(rs_segments_kernel<K>, dim3(grid_for(N)), dim3(256), 0, st, (const K*)ki, N, C, seg);
+    EFFDET_CHECK_LAUNCH();
+  }
+  return EFFDET_OK;
 }
 
 }  // namespace

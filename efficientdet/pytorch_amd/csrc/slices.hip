@@ -18,6 +18,7 @@
 //                       thread tests its alive candidates against the keeper's own box (an LDS broadcast).  Rounds are bounded
 //                       by max_det, not by the candidates.  min / fminf / fmaxf are order-independent: the result does not depend on
 //                       how the candidates are dealt.
+#include "box_geom.h"
 #include "radix_sort.h"
 #include "../../../include/effdet_slices.h"
 
@@ -89,9 +90,6 @@ struct Merge {
   int TPI, R, N, metric, class_aware, max_det; float W, H, thr, skip_thr;
 };
 
-__device__ __forceinline__ float sm_area(const float4& b) { return (b.z - b.x) * (b.w - b.y); }
-__device__ __forceinline__ bool pos_finite(float a) { return a > 0.f && a < __builtin_huge_valf(); }
-
 // slot j of image b in the image's frame, clipped (step 1 of the header)
 __device__ __forceinline__ float4 sm_box(const Merge& p, int b, int j) {
   const int t = j / p.R;
@@ -114,16 +112,15 @@ __global__ __launch_bounds__(256) void slice_key_kernel(const Merge p) {
   if (r < min(max(p.count[(long long)b * p.TPI + t], 0), p.R)) {
     const float s = p.score[at];
     const long long l = p.label[at];
-    if (s >= p.skip_thr && fabsf(s) < __builtin_huge_valf() && l >= 0 && l < 65536 && pos_finite(sm_area(sm_box(p, b, j)))) k = rs_score_key(s);
+    if (s >= p.skip_thr && fabsf(s) < __builtin_huge_valf() && l >= 0 && l < 65536 && pos_finite(box_area(sm_box(p, b, j)))) k = rs_score_key(s);
   }
   p.key[at] = k; p.val[at] = (unsigned)j;
 }
 
 __device__ __forceinline__ bool sm_match(const Merge& p, const float4& a, float aa, const float4& c) {
-  const float iw = fminf(a.z, c.z) - fmaxf(a.x, c.x);
-  const float ih = fminf(a.w, c.w) - fmaxf(a.y, c.y);
-  if (iw <= 0.f || ih <= 0.f) return false;                             // (inter = 0: 0 > thr never holds)
-  const float inter = iw * ih, ca = sm_area(c);
+  float inter;
+  if (!box_inter(a, c, inter)) return false;                            // (inter = 0: 0 > thr never holds)
+  const float ca = box_area(c);
   const float m = p.metric == EFFDET_SLICE_IOS ? inter / fminf(aa, ca) : inter / (aa + ca - inter);
   return m > p.thr;
 }
@@ -198,7 +195,7 @@ __global__ __launch_bounds__(SM_T) void slice_merge_kernel(const Merge p) {
     if (mi == SM_NONE || kept == p.max_det) break;
     ki = mi; kb = tb[ki];
     const int kl = tl[ki];
-    const float ka = sm_area(kb);
+    const float ka = box_area(kb);
     if ((ki & (SM_T - 1)) == tid) alive &= ~(1u << (ki >> 10));
     hull = make_float4(inf, inf, -inf, -inf);
 #pragma unroll
@@ -229,8 +226,6 @@ size_t carve(RsBufs<unsigned>& rs, void* base, int B, int N) {
   rs_carve(rs, c, (size_t)B, (size_t)N);
   return c.off;
 }
-
-bool finite_pos(float v) { return v > 0.f && v < __builtin_huge_valf(); }
 
 }  // namespace
 
@@ -274,7 +269,7 @@ extern "C" int effdet_slice_merge(const effdet_slice_merge_t* d, void* workspace
       ((uintptr_t)d->out_count & 3) || ((uintptr_t)workspace & 15))
     return EFFDET_EINVAL;
   if (!merge_shape_ok(d->TPI, d->R) || d->max_det < 1 || d->max_det > d->TPI * d->R || d->method < 0 || d->method > 1 || d->metric < 0 ||
-      d->metric > 1 || !(d->thr >= 0.f && d->thr <= 1.f) || d->skip_thr != d->skip_thr || !finite_pos(d->W) || !finite_pos(d->H))
+      d->metric > 1 || !(d->thr >= 0.f && d->thr <= 1.f) || d->skip_thr != d->skip_thr || !pos_finite(d->W) || !pos_finite(d->H))
     return EFFDET_EUNSUPPORTED;
   const int N = d->TPI * d->R;
   RsBufs<unsigned> rs;

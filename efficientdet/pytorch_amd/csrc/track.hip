@@ -15,7 +15,7 @@
 //     the same rows, columns, track_similarity() and gate through assign.h's shortest-augmenting-path solver (its arrays in LDS, the
 //     row's dual, distance and predecessor in the slot's thread), a pair's integer weight recomputed whenever the search relaxes it.
 // No atomics of any kind.
-#include "common.h"
+#include "box_geom.h"
 #include "../../../include/effdet_track.h"
 #include "assign.h"
 
@@ -57,13 +57,13 @@ __device__ __forceinline__ void det_z(const float4& b, float* z) {
   const float w = b.z - b.x, h = b.w - b.y;
   z[0] = b.x + 0.5f * w; z[1] = b.y + 0.5f * h; z[2] = w / h; z[3] = h;
 }
-__device__ __forceinline__ float tr_area(const float4& b) { return (b.z - b.x) * (b.w - b.y); }
+// box_geom.h's IoU arithmetic with this file's own refusal: !(iw > 0.f) sends a NaN extent to 0, where box_iou lets the NaN through
 __device__ __forceinline__ float tr_iou(const float4& a, const float4& b) {
   const float iw = fminf(a.z, b.z) - fmaxf(a.x, b.x);
   const float ih = fminf(a.w, b.w) - fmaxf(a.y, b.y);
   if (!(iw > 0.f) || !(ih > 0.f)) return 0.f;
   const float inter = iw * ih;
-  return inter / ((tr_area(a) + tr_area(b)) - inter);
+  return inter / ((box_area(a) + box_area(b)) - inter);
 }
 
 // ---- the Kalman filter in block form

@@ -15,7 +15,7 @@
 //     keys; then one workgroup per class: forward sweep (exact integer TP / FP cumsums -> fp64 recall, precision), reverse sweep
 //     (precision envelope = running max from the right, AP terms (r_k - r_{k-1}) * env_k at the TP positions k), and a fixed
 //     LDS tree over the per-thread partial sums.  Every launch geometry follows from (B, max_det, G, C, N) alone.
-#include "common.h"
+#include "box_geom.h"
 #include "block_scan.h"
 #include "radix_sort.h"
 #include <float.h>
@@ -27,7 +27,7 @@ constexpr int VOC_MAX_GT = 2048;              // GT rows per image staged in LDS
 constexpr size_t VOC_GT_LDS = 4 * sizeof(double) + 2 * sizeof(int);     // bytes per GT row: 4 fp64 box, label, claim
 constexpr int VOC_MAX_CLASSES = 65535;        // class values 0..C fit the two class passes of the sort
 
-// compute_overlap(d, gts of class c) and np.argmax, in the reference's fp64 operation order
+// compute_overlap(d, gts of class c) (box_geom.h's box_overlap_f64) and np.argmax
 __device__ __forceinline__ int voc_assign(const double a0, const double a1, const double a2, const double a3, int c,
                                           const double* gb, const int* gl, int G, double& best) {
   const double aarea = (a2 - a0) * (a3 - a1);
@@ -35,15 +35,7 @@ __device__ __forceinline__ int voc_assign(const double a0, const double a1, cons
   best = -1.0;
   for (int j = 0; j < G; ++j) {
     if (gl[j] != c) continue;
-    const double b0 = gb[4 * j], b1 = gb[4 * j + 1], b2 = gb[4 * j + 2], b3 = gb[4 * j + 3];
-    const double area = (b2 - b0) * (b3 - b1);
-    double iw = fmin(a2, b2) - fmax(a0, b0);
-    double ih = fmin(a3, b3) - fmax(a1, b1);
-    iw = fmax(iw, 0.0);
-    ih = fmax(ih, 0.0);
-    double ua = aarea + area - iw * ih;
-    ua = fmax(ua, DBL_EPSILON);
-    const double iou = iw * ih / ua;
+    const double iou = box_overlap_f64(a0, a1, a2, a3, aarea, gb + 4 * j);
     if (iou > best) { best = iou; arg = j; }       // first maximum
   }
   return arg;
@@ -74,9 +66,8 @@ __global__ __launch_bounds__(256) void voc_match_kernel(const float* __restrict_
   const float* d = dets + (long long)b * max_det * 6;
   for (int k = tid; k < n; k += 256) {
     const float* r = d + (long long)k * 6;
-    const float lf = r[5];
-    const int c = (int)lf;
-    if (!(lf >= 0.f && lf < (float)C) || (float)c != lf) continue;
+    int c;
+    if (!label_class(r[5], C, c)) continue;
     double best;
     const int a = voc_assign(r[0], r[1], r[2], r[3], c, gb, gl, G, best);
     if (a >= 0 && best >= thr) atomicMin(&claim[a], k);
@@ -88,9 +79,8 @@ __global__ __launch_bounds__(256) void voc_match_kernel(const float* __restrict_
     unsigned char tp = 0;
     if (k < n) {
       const float* r = d + (long long)k * 6;
-      const float lf = r[5];
-      const int c = (int)lf;
-      if (lf >= 0.f && lf < (float)C && (float)c == lf) {
+      int c;
+      if (label_class(r[5], C, c)) {
         double best;
         const int a = voc_assign(r[0], r[1], r[2], r[3], c, gb, gl, G, best);
         tp = (a >= 0 && best >= thr && claim[a] == k) ? 1 : 0;
@@ -100,11 +90,6 @@ __global__ __launch_bounds__(256) void voc_match_kernel(const float* __restrict_
     rec_key[o] = key;
     rec_tp[o] = tp;
   }
-}
-
-// seg[2c], seg[2c + 1] = [first, last + 1) sorted position of class c (0, 0 when the class has no records)
-__global__ __launch_bounds__(256) void voc_segments_kernel(const unsigned long long* __restrict__ skey, long long N, int C, int* __restrict__ seg) {
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < N; i += (long long)gridDim.x * 256) rs_segment_bounds(skey, i, N, C, seg);
 }
 
 // one workgroup per class: eval.py:225-241 + _compute_ap on the class's sorted records [seg[2c], seg[2c+1])
@@ -200,17 +185,8 @@ extern "C" int effdet_voc_ap(const unsigned long long* rec_key, const unsigned c
   if ((long long)voc_carve(w, workspace, N) > workspace_bytes) return EFFDET_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int C = num_classes;
-  hipLaunchKernelGGL(rs_init_kernel<unsigned long long>, dim3(grid_for(N > 2LL * C ? N : 2LL * C)), dim3(256), 0, st, rec_key, w.ka, w.va, N,
-                     seg, C);
-  EFFDET_CHECK_LAUNCH();
-  unsigned long long *ki = w.ka, *ko = w.kb;
-  unsigned *vi = w.va, *vo = w.vb;
-  if (N > 0) {
-    const int passes = 4 + (C <= 255 ? 1 : 2);       // class values 0..C (C = empty slot)
-    if (const int rc = rs_sort(ki, vi, ko, vo, w.hist, 1, N, w.T, 0, passes, st)) return rc;
-    hipLaunchKernelGGL(voc_segments_kernel, dim3(grid_for(N)), dim3(256), 0, st, (const unsigned long long*)ki, N, C, seg);
-    EFFDET_CHECK_LAUNCH();
-  }
+  unsigned long long* ki; unsigned* vi;
+  if (const int rc = rs_class_sort(rec_key, N, C, w, seg, ki, vi, st)) return rc;
   hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(256), 0, st, (const unsigned*)vi, rec_tp, (const int*)seg, gt_count, recall, precision,
                      ap, num_annotations);
   EFFDET_CHECK_LAUNCH();

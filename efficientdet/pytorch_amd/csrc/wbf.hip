@@ -13,7 +13,8 @@
 //      reduction slots with ONE barrier, then the owner joins or founds.  The number of clusters is block-uniform.
 //   4. the clusters' scores make keys the same way (~score bits << 32 | cluster index), the same sort orders them, and every owner
 //      writes its clusters to the rows the sort gave them; the remaining rows are zeroed.
-#include "common.h"
+#include "box_geom.h"
+#include "block_best.h"
 #include "../../../include/effdet_wbf.h"
 
 namespace {
@@ -28,34 +29,8 @@ struct Wbf {
   float* out_score; long long* out_label; float* out_boxes; int* out_count;
 };
 
-// THE IoU arithmetic of postprocess.hip (with_iou): inter / (aa + ab - inter) from the two areas, 0 for boxes that do not overlap
-__device__ __forceinline__ float wbf_area(const float4& b) { return (b.z - b.x) * (b.w - b.y); }
-__device__ __forceinline__ float wbf_iou(const float4& a, float aa, const float4& b, float ab) {
-  const float iw = fminf(a.z, b.z) - fmaxf(a.x, b.x);
-  const float ih = fminf(a.w, b.w) - fmaxf(a.y, b.y);
-  if (iw <= 0.f || ih <= 0.f) return 0.f;
-  const float inter = iw * ih;
-  return inter / (aa + ab - inter);
-}
-__device__ __forceinline__ bool pos_finite(float a) { return a > 0.f && a < __builtin_huge_valf(); }
-// (IoU, cluster) arg-max order: larger IoU first, then the lower cluster index; "none" is (-inf, INT_MAX) and a NaN never wins
-__device__ __forceinline__ void wbf_better(float& s, int& q, float os, int oq) { if (os > s || (os == s && oq < q)) { s = os; q = oq; } }
-
-// the wave's best in every lane: an xor butterfly whose four steps inside a row of 16 lanes are DPP moves (no LDS crossbar round
-// trip: the step sits on the critical path of every candidate), the two across rows shuffles.  All 64 lanes are active here.
-template <int CTRL> __device__ __forceinline__ void wbf_dpp_step(float& s, int& q) {
-  const float os = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), CTRL, 0xf, 0xf, false));
-  const int oq = __builtin_amdgcn_update_dpp(0, q, CTRL, 0xf, 0xf, false);
-  wbf_better(s, q, os, oq);
-}
-__device__ __forceinline__ void wbf_wave_best(float& s, int& q) {
-  wbf_dpp_step<0xB1>(s, q);                                            // quad_perm [1,0,3,2]: lane ^ 1
-  wbf_dpp_step<0x4E>(s, q);                                            // quad_perm [2,3,0,1]: lane ^ 2
-  wbf_dpp_step<0x141>(s, q);                                           // row_half_mirror: 7 - lane of 8, a lane of the other quad
-  wbf_dpp_step<0x140>(s, q);                                           // row_mirror: 15 - lane of 16, a lane of the other half row
-  wbf_better(s, q, __shfl_xor(s, 16, 64), __shfl_xor(q, 16, 64));
-  wbf_better(s, q, __shfl_xor(s, 32, 64), __shfl_xor(q, 32, 64));
-}
+// The IoU is box_geom.h's box_iou from the two areas; the (IoU, cluster) arg-max goes by block_best.h's order and starts with its DPP
+// wave step (all 64 lanes are active here).
 
 // row r of view v of image b after the view's transform -> takes part?
 __device__ __forceinline__ bool wbf_row(const Wbf& p, int b, int v, int r, float4& bx, float& conf) {
@@ -66,7 +41,7 @@ __device__ __forceinline__ bool wbf_row(const Wbf& p, int b, int v, int r, float
   const float m = p.mul[v];
   bx.x *= m; bx.y *= m; bx.z *= m; bx.w *= m;
   conf = s * p.weight[v];
-  return s >= p.skip_thr && pos_finite(conf) && pos_finite(wbf_area(bx));
+  return s >= p.skip_thr && pos_finite(conf) && pos_finite(box_area(bx));
 }
 
 // ascending bitonic sort of key[0 .. P) (P a power of two) by the whole workgroup; ends on a barrier
@@ -127,19 +102,19 @@ __global__ __launch_bounds__(WBF_T) void wbf_kernel(const Wbf p) {
   int ncl = 0;
   for (int i = 0; i < M; ++i) {
     const float4 cb = tb[i]; const float cc = tc[i]; const int cl = tl[i];
-    const float ca = wbf_area(cb);
+    const float ca = box_area(cb);
     float bs = -__builtin_huge_valf(); int bq = 0x7fffffff;
 #pragma unroll
     for (int u = 0; u < WBF_OWN; ++u) {
       const int c = tid + u * WBF_T;
-      if (c < ncl && lab[u] == cl) wbf_better(bs, bq, wbf_iou(fb[u], wbf_area(fb[u]), cb, ca), c);
+      if (c < ncl && lab[u] == cl) best_take(bs, bq, box_iou(fb[u], box_area(fb[u]), cb, ca), c);
     }
-    wbf_wave_best(bs, bq);
+    wave_best_dpp(bs, bq);
     if (lane == 0) { red_s[i & 1][wave] = bs; red_q[i & 1][wave] = bq; }
     __syncthreads();
     float ws = red_s[i & 1][lane & 15]; int wq = red_q[i & 1][lane & 15];
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) wbf_better(ws, wq, __shfl_xor(ws, o, 64), __shfl_xor(wq, o, 64));
+    for (int o = 8; o > 0; o >>= 1) best_take(ws, wq, __shfl_xor(ws, o, 64), __shfl_xor(wq, o, 64));
     const bool join = ws > p.iou_thr;                                  // (block-uniform: every thread reduced the same 16 slots)
     const int c = join ? wq : ncl;
     if ((c & (WBF_T - 1)) == tid) {
@@ -190,8 +165,6 @@ __global__ __launch_bounds__(WBF_T) void wbf_kernel(const Wbf p) {
   if (tid == 0) p.out_count[b] = ncl;
 }
 
-inline bool finite_pos(float v) { return v > 0.f && v < __builtin_huge_valf(); }
-
 }  // namespace
 
 extern "C" long long effdet_wbf_workspace_bytes(int B, int V, int top_n) {
@@ -213,7 +186,7 @@ extern "C" int effdet_wbf(const effdet_wbf_t* d, void* workspace, long long work
     if (on) {
       if (!d->score[v] || !d->label[v] || !d->boxes[v] || !d->count[v] || d->A[v] < 1 || ((unsigned long long)d->boxes[v] & 15ull) != 0ull)
         return EFFDET_EINVAL;
-      if (!finite_pos(d->weight[v]) || !finite_pos(d->mul[v]) || (d->flip[v] && !(fabsf(d->width[v]) < __builtin_huge_valf())))
+      if (!pos_finite(d->weight[v]) || !pos_finite(d->mul[v]) || (d->flip[v] && !(fabsf(d->width[v]) < __builtin_huge_valf())))
         return EFFDET_EUNSUPPORTED;
       p.wsum += d->weight[v]; p.wmax = fmaxf(p.wmax, d->weight[v]);
     }
@@ -222,7 +195,7 @@ extern "C" int effdet_wbf(const effdet_wbf_t* d, void* workspace, long long work
     p.A[v] = on ? d->A[v] : 0; p.weight[v] = on ? d->weight[v] : 0.f; p.width[v] = on ? d->width[v] : 0.f;
     p.mul[v] = on ? d->mul[v] : 0.f; p.flip[v] = on ? (d->flip[v] != 0) : 0;
   }
-  if (!finite_pos(p.wsum)) return EFFDET_EUNSUPPORTED;  // (the weights' fp32 sum overflowed)
+  if (!pos_finite(p.wsum)) return EFFDET_EUNSUPPORTED;  // (the weights' fp32 sum overflowed)
   const int N = d->V * d->top_n;
   p.V = d->V; p.top_n = d->top_n; p.conf_type = d->conf_type; p.iou_thr = d->iou_thr; p.skip_thr = d->skip_thr;
   p.P = 1; while (p.P < N) p.P <<= 1;

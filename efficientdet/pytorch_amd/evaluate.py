@@ -34,14 +34,18 @@ def default_max_detections(xywh, A, num_classes=None):
     return int(A) if xywh else 100
 
 
+def _scales_tensor(scales, device):
+    """finalize_dets' resize factors (tensor, array or list) -> contiguous fp32 on device."""
+    return torch.as_tensor(np.asarray(scales, dtype=np.float32) if not torch.is_tensor(scales) else scales,
+                           dtype=torch.float32, device=device).contiguous()
+
+
 def finalize(s, l, b, count, scales, score_threshold=0.05, max_detections=None, xywh=False, num_classes=None):
     """eval.py:104-117 / :279-292 for the batch on the device -> (dets [B,max_detections,6], counts [B]) on the HOST.
     max_detections=None: default_max_detections (100 per image for the VOC rows, every detection for the COCO rows)."""
     if max_detections is None:
         max_detections = default_max_detections(xywh, s.shape[1], num_classes)
-    sc = torch.as_tensor(np.asarray(scales, dtype=np.float32) if not torch.is_tensor(scales) else scales,
-                         dtype=torch.float32, device=s.device).contiguous()
-    out, oc = ops.finalize_dets(s, l, b, count, sc, score_threshold, max_detections, xywh)
+    out, oc = ops.finalize_dets(s, l, b, count, _scales_tensor(scales, s.device), score_threshold, max_detections, xywh)
     # counts first (a few bytes), then ONLY the filled rows: the uncapped COCO default makes `out` [B, A, 6] -- 1.18 MB per D0 image,
     # 4.7 MB per D4 image, nearly all of it padding rows past the count (zeros with label -1, as the kernel writes them) -- which the
     # host array reproduces without transferring them
@@ -57,9 +61,7 @@ def finalize(s, l, b, count, scales, score_threshold=0.05, max_detections=None, 
 def finalize_device(s, l, b, count, scales, score_threshold=0.05, max_detections=100):
     """finalize (the VOC rows: x1, y1, x2, y2, score, label, boxes / scale) without the copy -> (out [B, max_detections, 6] fp32,
     counts [B] int32), both left on the device; rows past counts[b] are zero with label -1."""
-    sc = torch.as_tensor(np.asarray(scales, dtype=np.float32) if not torch.is_tensor(scales) else scales,
-                         dtype=torch.float32, device=s.device).contiguous()
-    return ops.finalize_dets(s, l, b, count, sc, score_threshold, int(max_detections), False)
+    return ops.finalize_dets(s, l, b, count, _scales_tensor(scales, s.device), score_threshold, int(max_detections), False)
 
 
 def detections_batched(model, images, scales, score_threshold=0.05, max_detections=None, xywh=False):
@@ -71,7 +73,60 @@ def detections_batched(model, images, scales, score_threshold=0.05, max_detectio
         return finalize(s, l, b, count, scales, score_threshold, max_detections, xywh, getattr(model, 'num_classes', None))
 
 
-class EnsembleDetector:
+def leaf_models(model):
+    """The models with a pass of their own (forward_raw) under ``model``, in order: an EnsembleDetector's members, a SlicedDetector's
+    or a TrackedDetector's model, at any depth; a model that wraps nothing is its own only leaf."""
+    inner = getattr(model, 'models', None) or ([model.model] if hasattr(model, 'model') and not hasattr(model, 'forward_raw') else None)
+    return [model] if inner is None else [x for i in inner for x in leaf_models(i)]
+
+
+class _DetectorWrapper:
+    """What EnsembleDetector, SlicedDetector and TrackedDetector share: they stand in for a model (num_classes, eval, train,
+    parameters) over ``models`` or ``model``, and know whether a leaf computes in f16x3 (whose range flag they clear and check)."""
+
+    def _take_model(self, model, kinds):
+        if not hasattr(model, 'num_classes') or not (hasattr(model, 'forward_raw') or hasattr(model, 'detections')):
+            raise TypeError('%s: model must be %s, not %r' % (type(self).__name__, kinds, model))
+        self.model = model
+        self.num_classes = int(model.num_classes)
+
+    def _inner(self):
+        return self.models if hasattr(self, 'models') else [self.model]
+
+    def eval(self):
+        for m in self._inner():
+            m.eval()
+        return self
+
+    def train(self, mode=True):
+        for m in self._inner():
+            m.train(mode)
+        return self
+
+    def parameters(self):
+        return (p for m in self._inner() for p in m.parameters())
+
+    def _f16x3(self):
+        return any(ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3' for m in leaf_models(self))
+
+
+class _ListDetector(_DetectorWrapper):
+    """A wrapper whose ``detections(images, H, W)`` is one pass: EfficientDet's ``detect`` over it."""
+
+    def detect(self, images):
+        """-> list of (scores[K], labels[K] int64, boxes[K,4]) per image, score-descending, as EfficientDet.detect."""
+        f16x3 = self._f16x3()
+        if f16x3:
+            ops.clear_range_flag(images.device)
+        with torch.no_grad():
+            s, l, b, count = self.detections(images, int(images.shape[2]), int(images.shape[3]))
+        counts = count.tolist()
+        if f16x3 and not torch.cuda.is_current_stream_capturing():
+            ops.check_range_flag(s.device)
+        return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
+
+
+class EnsembleDetector(_ListDetector):
     """Several detectors as one: every member runs its own detection pass on the batch (its own set_nms and set_tta included) and the
     lists are merged on the device by weighted boxes fusion (ops.fuse_detections) under the members' weights.  Has ``detect(images)``
     like EfficientDet and is taken as ``model`` by detections_batched, evaluate_voc and evaluate_coco.  Members may differ in family
@@ -103,19 +158,6 @@ class EnsembleDetector:
         self.scales = scales
         self.num_classes = int(self.models[0].num_classes)
 
-    def eval(self):
-        for m in self.models:
-            m.eval()
-        return self
-
-    def train(self, mode=True):
-        for m in self.models:
-            m.train(mode)
-        return self
-
-    def parameters(self):
-        return (p for m in self.models for p in m.parameters())
-
     def detections(self, images, H, W):
         """ops.model_detections' tuple for the ensemble (what that function asks a model with its own pass for)."""
         scales = getattr(self, 'scales', None)                 # (an ensemble pickled before the option existed has no such attribute)
@@ -127,20 +169,8 @@ class EnsembleDetector:
         muls = [float(np.float32(float(H) / float(hw[0]))) for hw in sizes]
         return ops.fuse_detections(views, self.weights, None, muls, self.fusion)
 
-    def detect(self, images):
-        """-> list of (scores[K], labels[K] int64, boxes[K,4]) per image, score-descending, as EfficientDet.detect."""
-        f16x3 = any(ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3' for m in self.models)
-        if f16x3:
-            ops.clear_range_flag(images.device)
-        with torch.no_grad():
-            s, l, b, count = self.detections(images, int(images.shape[2]), int(images.shape[3]))
-        counts = count.tolist()
-        if f16x3 and not torch.cuda.is_current_stream_capturing():
-            ops.check_range_flag(s.device)
-        return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
 
-
-class SlicedDetector:
+class SlicedDetector(_ListDetector):
     """A detector for images larger than its network input (sliced inference, SAHI): the batch is cut into overlapping tiles of
     options.slice on the device (ops.slice_images), the tiles go through ``model``'s own detection pass tile_batch at a time (its
     set_nms and set_tta apply per tile), with options.full_view the whole image resampled to the tile size (ops.resample_images) goes
@@ -154,21 +184,8 @@ class SlicedDetector:
         options = ops.SliceOptions() if options is None else options
         if not isinstance(options, ops.SliceOptions):
             raise TypeError('SlicedDetector: options must be a SliceOptions, not %r' % (options,))
-        if not hasattr(model, 'num_classes') or not (hasattr(model, 'forward_raw') or hasattr(model, 'detections')):
-            raise TypeError('SlicedDetector: model must be an EfficientDet or an EnsembleDetector, not %r' % (model,))
-        self.model, self.options = model, options
-        self.num_classes = int(model.num_classes)
-
-    def eval(self):
-        self.model.eval()
-        return self
-
-    def train(self, mode=True):
-        self.model.train(mode)
-        return self
-
-    def parameters(self):
-        return self.model.parameters()
+        self._take_model(model, 'an EfficientDet or an EnsembleDetector')
+        self.options = options
 
     def detections(self, images, H, W):
         """ops.model_detections' tuple for the sliced pass (what that function asks a model with its own pass for)."""
@@ -197,21 +214,8 @@ class SlicedDetector:
             count = torch.cat([count, whole[3][:, None]], dim=1)
         return ops.merge_slices((gather(0, ()), gather(1, ()), gather(2, (4,)), count), table, H, W, o.merge)
 
-    def detect(self, images):
-        """-> list of (scores[K], labels[K] int64, boxes[K,4]) per image, score-descending, as EfficientDet.detect."""
-        members = getattr(self.model, 'models', [self.model])
-        f16x3 = any(ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3' for m in members)
-        if f16x3:
-            ops.clear_range_flag(images.device)
-        with torch.no_grad():
-            s, l, b, count = self.detections(images, int(images.shape[2]), int(images.shape[3]))
-        counts = count.tolist()
-        if f16x3 and not torch.cuda.is_current_stream_capturing():
-            ops.check_range_flag(s.device)
-        return [(s[i, :n], l[i, :n], b[i, :n]) for i, n in enumerate(counts)]
 
-
-class TrackedDetector:
+class TrackedDetector(_DetectorWrapper):
     """A detector for video: every image of the batch is one camera stream, and each call is the streams' next frame.  ``update`` runs
     ``model``'s own detection pass (an EfficientDet, an EnsembleDetector or a SlicedDetector: its NMS and TTA settings apply), the eval
     consumer on the device (finalize_device; score_threshold None: options.low_thr, because ByteTrack needs the low detections) and ONE
@@ -242,33 +246,14 @@ class TrackedDetector:
         options = ops.TrackOptions() if options is None else options
         if not isinstance(options, ops.TrackOptions):
             raise TypeError('TrackedDetector: options must be a TrackOptions, not %r' % (options,))
-        if not hasattr(model, 'num_classes') or not (hasattr(model, 'forward_raw') or hasattr(model, 'detections')):
-            raise TypeError('TrackedDetector: model must be an EfficientDet, an EnsembleDetector or a SlicedDetector, not %r' % (model,))
+        self._take_model(model, 'an EfficientDet, an EnsembleDetector or a SlicedDetector')
         if not 1 <= int(max_detections) <= ops.TRACK_MAX_DET:
             raise ValueError('TrackedDetector: max_detections must be in 1..%d' % ops.TRACK_MAX_DET)
         score_threshold = options.low_thr if score_threshold is None else float(score_threshold)
         if not abs(score_threshold) < float('inf'):
             raise ValueError('TrackedDetector: score_threshold must be finite')
-        self.model, self.options, self.score_threshold, self.max_detections = model, options, score_threshold, int(max_detections)
-        self.num_classes = int(model.num_classes)
+        self.options, self.score_threshold, self.max_detections = options, score_threshold, int(max_detections)
         self.state = None
-
-    def eval(self):
-        self.model.eval()
-        return self
-
-    def train(self, mode=True):
-        self.model.train(mode)
-        return self
-
-    def parameters(self):
-        return self.model.parameters()
-
-    def _f16x3(self):
-        def members(m):
-            inner = getattr(m, 'models', None) or ([m.model] if hasattr(m, 'model') and not hasattr(m, 'forward_raw') else None)
-            return [m] if inner is None else [x for i in inner for x in members(i)]
-        return any(ops.MODEL_ARITH[getattr(m, 'f32_arith', 'f32')][2] == 'f16x3' for m in members(self.model))
 
     def detections_device(self, images, scales=None):
         """The detection half of update -> finalize_device's (dets [B, max_detections, 6], counts [B]) on the device."""

@@ -1436,7 +1436,17 @@ NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}
 SOFT_NMS_MAX_TOP_N = 4096          # the kernel holds the top-N candidates of an image in one workgroup's LDS
 
 
-class NMSOptions:
+class _Options:
+    """What the options classes share: ``key()`` (each class's own tuple) decides equality, within one class, and the hash."""
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+
+class NMSOptions(_Options):
     """The rescoring NMS of EfficientDet.set_nms (effdet_soft_nms): method 'hard' | 'linear' | 'gaussian', gaussian sigma,
     per-class suppression, the top-N candidates per image that take part (<= 4096) and the picks per image."""
 
@@ -1454,12 +1464,6 @@ class NMSOptions:
 
     def key(self):
         return (self.method, self.sigma, self.class_aware, self.pre_nms_top_n, self.max_det)
-
-    def __eq__(self, other):
-        return isinstance(other, NMSOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'NMSOptions(method=%r, sigma=%r, class_aware=%r, pre_nms_top_n=%d, max_det=%d)' % self.key()
@@ -1514,7 +1518,7 @@ WBF_CONF_TYPES = {'avg': 0, 'max': 1}                # EFFDET_WBF_AVG, EFFDET_WB
 WBF_MAX_VIEWS, WBF_MAX_IN = L.WBF_MAX_VIEWS, L.WBF_MAX_IN
 
 
-class WBFOptions:
+class WBFOptions(_Options):
     """Weighted Boxes Fusion of fuse_detections (effdet_wbf): a candidate joins the same-label cluster it overlaps most when that IoU is
     > iou_thr; rows scoring below skip_box_thr take no part; the fused score is the members' mean confidence scaled by how many views
     agreed ('avg') or the largest one ('max'); of every view the first top_n rows per image take part (views * top_n <= 4096)."""
@@ -1532,12 +1536,6 @@ class WBFOptions:
 
     def key(self):
         return (self.iou_thr, self.skip_box_thr, self.conf_type, self.top_n)
-
-    def __eq__(self, other):
-        return isinstance(other, WBFOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'WBFOptions(iou_thr=%r, skip_box_thr=%r, conf_type=%r, top_n=%d)' % self.key()
@@ -1565,7 +1563,7 @@ def _tta_scales(scales):
     return sc
 
 
-class TTAOptions:
+class TTAOptions(_Options):
     """Test-time augmentation of EfficientDet.set_tta: views of the batch, each through the whole detection path (its own forward of batch
     B at the view's size), the lists merged by fuse_detections.  The views, in this order: the batch as given; with hflip its mirror
     image; then for each s of scales, in the order given, the batch resampled to (H * s, W * s) (resample_images: bilinear, no
@@ -1591,12 +1589,6 @@ class TTAOptions:
     def key(self):
         sc = getattr(self, 'scales', ())
         return (self.hflip, self.weights, self.fusion.key()) + ((sc,) if sc else ())
-
-    def __eq__(self, other):
-        return isinstance(other, TTAOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         sc = getattr(self, 'scales', ())
@@ -1789,7 +1781,7 @@ SLICE_METRICS = {'iou': L.SLICE_IOU, 'ios': L.SLICE_IOS}          # EFFDET_SLICE
 SLICE_MAX_TILES, SLICE_MAX_IN = L.SLICE_MAX_TILES, L.SLICE_MAX_IN
 
 
-class SliceMergeOptions:
+class SliceMergeOptions(_Options):
     """The cross-tile merge of merge_slices (effdet_slice_merge): candidates in score order; a keeper takes every later candidate whose
     metric with the keeper's own box is > thr ('iou', or 'ios': intersection over the smaller box, which is what lets a full box absorb
     one truncated at a tile edge) and, with class_aware, whose label is the keeper's.  'nms' drops what a keeper takes, 'nmm' also
@@ -1815,17 +1807,11 @@ class SliceMergeOptions:
     def key(self):
         return (self.method, self.metric, self.thr, self.class_aware, self.skip_thr, self.top_n, self.max_det)
 
-    def __eq__(self, other):
-        return isinstance(other, SliceMergeOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
-
     def __repr__(self):
         return 'SliceMergeOptions(method=%r, metric=%r, thr=%r, class_aware=%r, skip_thr=%r, top_n=%d, max_det=%d)' % self.key()
 
 
-class SliceOptions:
+class SliceOptions(_Options):
     """Sliced inference of evaluate.SlicedDetector: the image is cut into tiles of slice = (h, w) (whole multiples of 128: a tile is a
     network input) that overlap by overlap = (ratio_y, ratio_x) of the tile, each in [0, 0.9]; with full_view the whole image resampled
     to (h, w) is one more view; the tiles go through the detector tile_batch at a time; merge: the SliceMergeOptions (None: defaults)."""
@@ -1849,12 +1835,6 @@ class SliceOptions:
 
     def key(self):
         return (self.slice, self.overlap, self.full_view, self.tile_batch, self.merge.key())
-
-    def __eq__(self, other):
-        return isinstance(other, SliceOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'SliceOptions(slice=%r, overlap=%r, full_view=%r, tile_batch=%d, merge=%r)' % (self.slice, self.overlap, self.full_view,
@@ -2041,7 +2021,7 @@ def merge_slices(lists, table, H, W, options=None):
 BOX_LOSS_KINDS = {'smooth_l1': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}     # EFFDET_BOX_LOSS_* (0: the effdet_focal_loss_* calls)
 
 
-class BoxLossOptions:
+class BoxLossOptions(_Options):
     """The box regression term of EfficientDet.set_box_loss / FocalLoss(box_loss=) (include/effdet_box_loss.h): kind 'smooth_l1' (the
     reference's, on the encoded deltas) or 'iou' | 'giou' | 'diou' | 'ciou' between the decoded prediction and the assigned annotation,
     in place of smooth-L1; weight multiplies the IoU kinds' loss (and gradient).  smooth_l1 is the reference's term as it is: it takes
@@ -2063,12 +2043,6 @@ class BoxLossOptions:
     def is_default(self):
         return self.kind == 'smooth_l1'
 
-    def __eq__(self, other):
-        return isinstance(other, BoxLossOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
-
     def __repr__(self):
         return 'BoxLossOptions(kind=%r, weight=%r)' % self.key()
 
@@ -2089,7 +2063,7 @@ def _f32(v):
 LOSS_BETA_DEFAULT = _f32(1.0 / 9.0)                  # the reference's smooth-L1 knee as the fp32 the kernels compare with
 
 
-class LossOptions:
+class LossOptions(_Options):
     """The options of the training loss of EfficientDet.set_loss / FocalLoss(loss=) (include/effdet_loss_opts.h): focal alpha and gamma,
     label smoothing eps (soft target h (1 - eps) + eps / 2), the smooth-L1 knee beta (Huber delta) and its weight reg_weight, the
     matcher's bands (positive at IoU >= pos_iou, negative below neg_iou, ignored between) and low_quality (every annotation's best
@@ -2125,12 +2099,6 @@ class LossOptions:
     def is_default(self):
         return self.key() == _LOSS_DEFAULT_KEY
 
-    def __eq__(self, other):
-        return isinstance(other, LossOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
-
     def __repr__(self):
         return 'LossOptions(%s)' % ', '.join('%s=%r' % (f, getattr(self, f)) for f in self._FIELDS)
 
@@ -2138,7 +2106,7 @@ class LossOptions:
 _LOSS_DEFAULT_KEY = LossOptions().key()
 
 
-class ATSSOptions:
+class ATSSOptions(_Options):
     """The ATSS matcher of EfficientDet.set_matcher / FocalLoss(matcher=) (include/effdet_atss.h), in place of the IoU bands: per
     annotation the topk anchors nearest its centre on every pyramid level are candidates, positive where their IoU reaches the
     candidates' mean + standard deviation and their centre lies inside the box."""
@@ -2151,17 +2119,11 @@ class ATSSOptions:
     def key(self):
         return (self.topk,)
 
-    def __eq__(self, other):
-        return isinstance(other, ATSSOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
-
     def __repr__(self):
         return 'ATSSOptions(topk=%r)' % self.topk
 
 
-class TaskAlignedOptions:
+class TaskAlignedOptions(_Options):
     """The task-aligned matcher of EfficientDet.set_matcher / FocalLoss(matcher=) (include/effdet_tal.h; TOOD, PP-YOLOE, YOLOv8), in
     place of the IoU bands: per annotation, among the anchors whose centre lies inside its box, the topk with the largest alignment
     metric m = s^alpha u^beta are selected -- s the PREDICTED probability of the annotation's class, u the IoU between the DECODED
@@ -2185,12 +2147,6 @@ class TaskAlignedOptions:
     def key(self):
         return (self.topk, self.alpha, self.beta, self.aligned_target)
 
-    def __eq__(self, other):
-        return isinstance(other, TaskAlignedOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
-
     def __repr__(self):
         return 'TaskAlignedOptions(topk=%r, alpha=%r, beta=%r, aligned_target=%r)' % self.key()
 
@@ -2201,7 +2157,7 @@ MATCHERS = (ATSSOptions, TaskAlignedOptions)
 QUALITY_KINDS = {'qfl': L.QUALITY_QFL, 'vfl': L.QUALITY_VFL}     # EFFDET_QUALITY_*
 
 
-class QualityLossOptions:
+class QualityLossOptions(_Options):
     """The IoU-aware class term of EfficientDet.set_quality_loss / FocalLoss(quality=) (include/effdet_quality_loss.h), in place of the
     hard-target focal loss: the target of a positive anchor's assigned label is q, the IoU between its DECODED prediction and its
     annotation (a constant of the gradient).  kind 'qfl': GFL's quality focal loss |q - p|^beta BCE(p, q); kind 'vfl': the varifocal
@@ -2223,12 +2179,6 @@ class QualityLossOptions:
 
     def key(self):
         return (self.kind, self.beta, self.alpha, self.gamma)
-
-    def __eq__(self, other):
-        return isinstance(other, QualityLossOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'QualityLossOptions(kind=%r, beta=%r, alpha=%r, gamma=%r)' % self.key()
@@ -2660,7 +2610,7 @@ _TRACK = ('effdet_track_state_bytes', 'effdet_track_reset', 'effdet_track_step',
 ASSIGN_MAX_ROWS, ASSIGN_MAX_COLS = L.ASSIGN_MAX_ROWS, L.ASSIGN_MAX_COLS
 
 
-class TrackOptions:
+class TrackOptions(_Options):
     """ByteTrack's settings for track_step (include/effdet_track.h): detections scoring >= track_thr are high, those in (low_thr,
     track_thr) low; the three associations allow a pair whose similarity is > match_sim (tracked + lost x high), > second_sim (the
     tracked left x low, plain IoU) and > unconfirmed_sim (unconfirmed x the high left); a high detection left over starts a track when
@@ -2695,12 +2645,6 @@ class TrackOptions:
         k = (self.track_thr, self.low_thr, self.new_thr, self.match_sim, self.second_sim, self.unconfirmed_sim, self.track_buffer,
              self.fuse_score, self.class_aware, self.max_tracks)
         return k if self.assignment == 'greedy' else k + (self.assignment,)            # (the default keeps the ten-tuple it always had)
-
-    def __eq__(self, other):
-        return isinstance(other, TrackOptions) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return ('TrackOptions(track_thr=%r, low_thr=%r, new_thr=%r, match_sim=%r, second_sim=%r, unconfirmed_sim=%r, track_buffer=%d, '
