@@ -6,6 +6,7 @@ reference's nn.Module surface).  See DESIGN.md / INTEGRATION.md.
 """
 from .checkpoint import get_state_dict  # noqa: F401
 from .config import EFFICIENTDET, MODEL_MAP  # noqa: F401
+from .draw import DrawOptions  # noqa: F401
 from .efficientdet import EfficientDet, PackedImages  # noqa: F401
 from .evaluate import SlicedDetector  # noqa: F401
 from .ops import (ATSSOptions, BoxLossOptions, LossOptions, NMSOptions, QualityLossOptions, SliceMergeOptions, SliceOptions,  # noqa: F401

@@ -1,7 +1,7 @@
 """ctypes binding of libeffdet_hip.so (include/effdet_hip.h, include/effdet_soft_nms.h, include/effdet_ema.h, include/effdet_dwconv_plan.h,
 include/effdet_live_tiles.h, include/effdet_needed_tiles.h, include/effdet_box_loss.h, include/effdet_loss_opts.h, include/effdet_atss.h, include/effdet_conv_plan.h, include/effdet_wbf.h, include/effdet_mosaic.h, include/effdet_affine.h,
 include/effdet_opt_groups.h, include/effdet_gate_operand.h, include/effdet_wgrad_plan.h, include/effdet_resample.h, include/effdet_slices.h,
-include/effdet_quality_loss.h, include/effdet_tal.h, include/effdet_op_point.h, include/effdet_track.h, include/effdet_assign.h).
+include/effdet_quality_loss.h, include/effdet_tal.h, include/effdet_op_point.h, include/effdet_track.h, include/effdet_assign.h, include/effdet_draw.h).
 
 The library is the product: there is NO CPU / eager fallback.  ``lib()`` raises if the shared
 library is missing and every op raises if a call returns a non-zero status.
@@ -464,6 +464,14 @@ ASSIGN_SIGNATURES = {
 }
 ASSIGN_MAX_ROWS, ASSIGN_MAX_COLS, ASSIGN_SCALE_BITS = 256, 128, 20                               # EFFDET_ASSIGN_*
 ASSIGNMENTS = ('greedy', 'optimal')                                                              # EFFDET_ASSIGN_GREEDY, _OPTIMAL in order
+# The device renderer (boxes, fills and labels into uint8 frames), declared in include/effdet_draw.h (same generation, same letters,
+# same rule; tests/test_draw_host.py compares this table with that header's prototypes).
+DRAW_SIGNATURES = {
+    'effdet_draw_detections': 'i:pppiiipiipppppipiiiiiiiis',
+    'effdet_draw_glyph': 'Q:i',
+}
+DRAW_MAX_ROWS, DRAW_NAME_MAX, DRAW_MAX_THICKNESS, DRAW_MAX_TEXT_SCALE, DRAW_TEXT_MAX = 1024, 16, 16, 8, 32     # EFFDET_DRAW_*
+DRAW_TILE_W, DRAW_TILE_H, DRAW_MAX_SIDE, DRAW_MAX_BATCH = 64, 16, 1 << 20, 65535
 WGRAD_PATHS = ('tiled', 'thin', 'split', 'stem')                                                # EFFDET_WGRAD_PATH_* in order
 OPT_ROW, OPT_RULE_ADAMW, OPT_RULE_SGD, OPT_GATED, OPT_EMA = 8, 0, 1, 1, 2      # EFFDET_OPT_* of that header
 CONV_FORMS = ('plain', 'bf16x3', 'split', 'hsplit', 'skinny')                                     # EFFDET_CONV_FORM_* in order
@@ -495,7 +503,7 @@ def lib():
                 list(WGRAD_PLAN_SIGNATURES.items()) + list(AFFINE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + \
                 list(UNIT_LISTS_SIGNATURES.items()) + list(SLICES_SIGNATURES.items()) + list(QUALITY_LOSS_SIGNATURES.items()) + \
                 list(TAL_SIGNATURES.items()) + list(OP_POINT_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + \
-                list(ASSIGN_SIGNATURES.items()):
+                list(ASSIGN_SIGNATURES.items()) + list(DRAW_SIGNATURES.items()):
             f = getattr(_lib, name, None)      # an additive entry point the library predates stays unbound: require() refuses it
             if f is not None:
                 f.restype, f.argtypes = _CTYPE[sig[0]], [_CTYPE[c] for c in sig[2:]]

